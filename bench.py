@@ -18,6 +18,8 @@ path).  Prints ONE JSON line on rank 0.
                                                        ranks through torch.distributed.run, relays rank 0's line
   --config C2 | C3 | C4                                C3 = kbo find, 100 Mbp, 10 M reads per GPU; C4 = kbo map, 250 Mbp,
                                                        100 M reads in all, sharded over the ranks (strong scaling)
+  --dump-outputs DIR                                   after the timed steps: what the last one computed, as DIR/<name>.npy
+                                                       (float32 / float64, at most 64 MB: a fixed sample of larger outputs)
 The oracle (oracle/) is used after the timed region only: parity gate, CPU baseline, and the CPU model of the plan-guided
 stage whose work counts price the roofline.
 """
@@ -35,6 +37,22 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from benchlib.common import *  # noqa: E402,F401,F403  (arguments, presets, index, ranks, the timed loops)
 from benchlib.legs import *  # noqa: E402,F401,F403  (the legs behind the timed region)
 from benchlib.call import main_call  # noqa: E402  (--call / --config C5)
+
+
+def last_step_outputs(args, slabs):
+    """--dump-outputs: the arrays a caller of the timed path receives from one step over `slabs` (host copies, named for the files):
+    the characters - kbo::map's (relative_to_ref) or, with --find, the plain ones and format::run_lengths' records - and with
+    --two-kernels the MS values the first of the two calls returns.  A step of several slabs: the later slabs' arrays carry _slab<i>"""
+    out = {}
+    for i, dev in enumerate(slabs):
+        tag = "_slab%d" % i if i else ""
+        if args.two_kernels:
+            out["ms" + tag] = dev.ms[:dev.total].cpu().numpy()
+        out["chars" + tag] = dev.chars[:dev.total].cpu().numpy()
+        if args.find:
+            records, first = dev.run_lengths_host()
+            out["run_records" + tag], out["run_first" + tag] = records, first
+    return out
 
 
 def main(argv=None):
@@ -199,6 +217,7 @@ def main(argv=None):
         torch.cuda.synchronize(device)
         per_step = max(1e-6, (time.perf_counter() - t_cond) / 4)
         conditioned = 4 + min(4000, int(args.condition_ms * 1e-3 / per_step) + 1)  # (enqueued back to back: the warm-up steps follow with no gap)
+        conditioned += -conditioned % n_sets  # (whole rounds of the resident batches: which one the last timed step takes does not hang on the host's clock)
         for j in range(4, conditioned):
             one_step(j)
     for w in range(args.warmup):
@@ -223,6 +242,11 @@ def main(argv=None):
     rle_ms = float(np.mean([sum(e[2].elapsed_time(e[3]) for e in step) for step in ev])) if args.find and args.two_kernels else None  # (else: inside the call)
     # what the timed steps left behind (formatted unless --find): the first slab of either set, for rank 0's parity gate
     timed_chars_sets = [sl[0].chars[:sl[0].total].cpu().numpy() for sl in sets] if rank == 0 else None
+    dumped = None
+    if args.dump_outputs and rank == 0:  # what the last timed step computed: its batch's slabs, before any leg below runs them again
+        last_set = (conditioned + args.warmup + args.steps - 1) % n_sets
+        dumped = dump_outputs(args.dump_outputs, last_step_outputs(args, sets[last_set]))
+        dumped["batch"] = last_set
     if mstream is not None:  # (its streams go back to the runtime: the legs below make their own, and streams beyond the hardware queues share them)
         mstream.close()
         mstream = None
@@ -498,6 +522,8 @@ def main(argv=None):
             "one_shot_map": one_shot,
             "host_to_host": h2h,
         }
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -94,6 +94,19 @@ def main_call(args):
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
     walk_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+
+    def sites_of(counts_all, sites_h):
+        """the site records the walk left in its lists -> (records [n, 4] uint32, whether every list held its sites)"""
+        counts = counts_all[:LISTS * 16:16]
+        seg = cap // LISTS
+        fits = bool((counts <= seg).all()) and int(counts_all[LISTS * 16]) == 0
+        raw = np.concatenate([sites_h[g * seg:g * seg + min(int(counts[g]), seg)] for g in range(LISTS)]) if int(counts.sum()) else sites_h[:0]
+        return raw[raw[:, 0] != 0xFFFFFFFF], fits  # (void records: kbo_hip.h, kbo_call_walk_dev)
+    dumped = None
+    if args.dump_outputs:  # what the last timed step computed, before the counting launch below runs the walk again: the MS values and
+        # the sites (the lists' order is the device's: sorted here)
+        got, _ = sites_of(count.cpu().numpy(), sites.cpu().numpy().view(np.uint32))
+        dumped = dump_outputs(args.dump_outputs, {"ms": dev.ms[:dev.total].cpu().numpy(), "sites": got[np.lexsort(got.T[::-1])]})
     # the walk's own work, counted by its kernels on the timed reads (one more launch with the counters on: kbo_set_plan_stats)
     own = None
     L.kbo_set_plan_stats(1)
@@ -105,13 +118,7 @@ def main_call(args):
         own = None
     finally:
         L.kbo_set_plan_stats(0)
-    counts_all = count.cpu().numpy()
-    counts = counts_all[:LISTS * 16:16]
-    n_sites, seg = int(counts.sum()), cap // LISTS
-    fits = bool((counts <= seg).all()) and int(counts_all[LISTS * 16]) == 0
-    sites_h = sites.cpu().numpy().view(np.uint32)
-    raw = np.concatenate([sites_h[g * seg:g * seg + min(int(counts[g]), seg)] for g in range(LISTS)]) if n_sites else sites_h[:0]
-    raw = raw[raw[:, 0] != 0xFFFFFFFF]  # (void records: kbo_hip.h, kbo_call_walk_dev)
+    raw, fits = sites_of(count.cpu().numpy(), sites.cpu().numpy().view(np.uint32))
     n_sites = len(raw)
     exact = None
     oi = None
@@ -276,4 +283,5 @@ def main_call(args):
                    "host_phases_seconds": phases, "build_sha16": build_sha16()},
         "kernels_ms": {"ms_walk_call_mode": round(walk_ms, 4)},
         "whole_call": whole,
-        "bit_exact_vs_oracle": exact, "parity_scope": "sites of every read vs the oracle's first pass of call_variants"}), flush=True)
+        "bit_exact_vs_oracle": exact, "parity_scope": "sites of every read vs the oracle's first pass of call_variants"}
+        | ({"dump_outputs": dumped} if dumped is not None else {})), flush=True)

@@ -15,8 +15,8 @@ import numpy as np
 
 # The host batch pipeline keeps three streams per device (upload, kernels, download) next to whatever the caller uses; the HIP runtime
 # maps a process's streams onto 4 hardware queues unless told otherwise, and streams that share a queue do not overlap
-# (INTEGRATION.md "Streams and hardware queues").  More queues are the APPLICATION's to ask for - GPU_MAX_HW_QUEUES=8 in its environment
-# before the runtime starts, as bench.py and the tools do - or, for a process that wants this package to do it, KBO_HW_QUEUES=8 (opt-in:
+# (INTEGRATION.md "Streams and hardware queues").  The number of queues is the APPLICATION's to choose - in its environment before the
+# runtime starts, as bench.py and the tools do - or, for a process that wants this package to do it, through KBO_HW_QUEUES (opt-in:
 # importing a library does not change the runtime's settings for every other HIP user of the process).
 if os.environ.get("KBO_HW_QUEUES"):
     os.environ.setdefault("GPU_MAX_HW_QUEUES", os.environ["KBO_HW_QUEUES"])

@@ -31,6 +31,48 @@ def test_presets_and_sharding():
         assert all(parts[r][1] == sum(n for n, _ in parts[:r]) for r in range(world))
     a = b.parse(["--gpus", "4"])
     assert [b.shard(a, r, 4) for r in range(4)] == [(1_000_000, r * 1_000_000) for r in range(4)]  # weak: fixed per rank
+    # the launch the driver makes on an 8-GPU node, at the size tests/test_gpu_bench.py runs it with fewer ranks: contiguous shards of
+    # ceil(reads / 8), the last one short
+    a = b.parse(["--config", "C4", "--gpus", "8", "--genome", "300000", "--reads", "240003"])
+    assert [b.shard(a, r, 8) for r in range(8)] == [(30001, r * 30001) for r in range(7)] + [(29996, 7 * 30001)]
+
+
+def test_steps_is_the_number_of_timed_steps():
+    b = _bench()
+    assert b.parse([]).steps == 200 and b.parse(["--steps", "7"]).steps == 7
+    assert b.parse(["--config", "C5"]).steps == 3
+    for n in ("200", "1", "9"):  # (an explicit count is kept, the default's value included)
+        assert b.parse(["--config", "C5", "--steps", n]).steps == int(n)
+    try:
+        b.parse(["--steps", "0"])
+        raise AssertionError("--steps 0 accepted")
+    except SystemExit:
+        pass
+
+
+def test_dump_outputs_types_budget_and_sample(tmp_path):
+    b = _bench()
+    rng = np.random.default_rng(1)
+    chars = rng.integers(0, 256, 3_000_000, dtype=np.uint8)
+    recs = rng.integers(0, 2**32, (1000, 7), dtype=np.uint64).astype(np.uint32)
+    ms = rng.integers(0, 64, 5000, dtype=np.uint8)
+    budget = 4 << 20
+    info = b.dump_outputs(str(tmp_path / "a"), {"chars": chars, "run_records": recs, "ms": ms}, budget=budget)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("chars", "run_records", "ms")}
+    # narrow values as float32, 32-bit ones as float64, every value exact
+    assert got["chars"].dtype == np.float32 and got["ms"].dtype == np.float32 and got["run_records"].dtype == np.float64
+    assert np.array_equal(got["run_records"], recs) and np.array_equal(got["ms"], ms)
+    assert not info["arrays"]["ms"]["sampled"] and not (tmp_path / "a" / "ms_rows.npy").exists()
+    # the larger output: a sample of its rows, ascending, named by <name>_rows.npy, within the budget
+    rows = np.load(str(tmp_path / "a" / "chars_rows.npy"))
+    assert info["arrays"]["chars"]["sampled"] and info["arrays"]["chars"]["rows_of"] == len(chars)
+    assert rows.dtype == np.float64 and len(rows) == len(got["chars"]) > 100_000 and (np.diff(rows) > 0).all()
+    assert np.array_equal(got["chars"], chars[rows.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget + 4096
+    # the same rows in every run; the default budget stays within 64 MB
+    b.dump_outputs(str(tmp_path / "b"), {"chars": chars, "run_records": recs, "ms": ms}, budget=budget)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "chars_rows.npy")), rows)
+    assert b.DUMP_BYTES + 64 * 1024 <= 64_000_000
 
 
 def test_index_cache_round_trip_and_spawn_command(tmp_path):
