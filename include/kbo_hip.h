@@ -359,7 +359,12 @@ int kbo_find_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_
  * kbo_call_walk_dev - never touch those regions and check kbo_ms_work_bytes(...) only (the round-4 figure; <= kbo_work_bytes). */
 size_t kbo_work_bytes(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k);
 size_t kbo_ms_work_bytes(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k);
-/* the same for a given index: a sharded index needs total_bases + 32 bytes more (one further shard's MS values) */
+/* the same for a given index: kbo_work_bytes() for an ordinary index; for a sharded index (kbo_index_shards() > 1) that plus one
+ * further shard's MS values, round16(total_bases) + 16 <= total_bases + 32 bytes.  What a SHARDED index needs as d_work:
+ *   kbo_ms_batch_dev                                   kbo_ms_work_bytes() + round16(total_bases) + 16 (the walk's figure + one shard's
+ *                                                      values, which sit right behind the walk's own region)
+ *   kbo_map_batch_dev[_tail], kbo_find_batch_dev,      kbo_index_work_bytes() - NOT kbo_work_bytes(): both are refused with KBO_E_BAD_ARG
+ *   kbo_map_stream_* (sizes its slots itself)          (kbo_call_walk_dev and kbo_matches_packed_dev refuse a sharded index) */
 size_t kbo_index_work_bytes(const kbo_index_t *idx, size_t n_seqs, uint64_t total_bases, size_t max_seq_len);
 /* A1 over a batch.  total_bases = offsets[n_seqs] (known to the caller; avoids a device read-back);
  * max_seq_len = length of the longest sequence if the caller knows it, 0 = unknown.  Batches of reads

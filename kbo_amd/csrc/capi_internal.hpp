@@ -246,7 +246,7 @@ size_t packed_slab_bytes(const kbo_index *idx); // bases per slab of a packed ba
 // call mode of the walk (kernels.hpp WalkArgs::call_*): where the sites go
 struct CallSink {
     void *d_sites;        // kCallSegs lists of cap_per_list 16-byte records
-    uint32_t *d_counts;   // kCallSegs counters 64 bytes apart + the overflow counter behind them, zeroed by the caller
+    uint32_t *d_counts;   // kCallSegs counters 64 bytes apart + the overflow counter behind them, zeroed by ms_batch_dev_impl once the call is accepted
     uint32_t cap_per_list;
     uint32_t threshold;
 };

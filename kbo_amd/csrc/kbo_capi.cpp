@@ -1102,6 +1102,7 @@ int ms_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t 
         KBO_REQUIRE(work_bytes >= w.ms_bytes + shard_ms, KBO_E_BAD_ARG,
                     "d_work is smaller than kbo_ms_work_bytes() (+ one shard's MS values for a sharded index: kbo_index_work_bytes()) for this batch");
         KBO_REQUIRE(total_bases / w.chunk + n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
+        if (call) HIP_OK(hipMemsetAsync(call->d_counts, 0, kbo::kCallSegs * 64 + 64, s)); // (kbo_call_walk_dev's counters: once the call is accepted)
         // a batch of reads over a copy with a depth table, nothing but the MS values asked for: map_reads_kernel in the form that puts
         // the values together in LDS (k where nothing happened, the ramps behind the mismatches, the table's values right behind them),
         // stopping there - no characters are made - and the plain walk for the reads it leaves (C2: 0.33 against 0.61 ms per
@@ -1141,7 +1142,10 @@ int ms_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t 
         } else {
             HIP_OK(kbo::launch_make_items(d_offsets, (uint32_t)n_seqs, items, s));
         }
-        uint8_t *ms_shard = static_cast<uint8_t *>(d_work) + w.bytes; // (16-byte aligned: w.bytes is a multiple of 16)
+        // one further shard's values right behind the walks' own region (64-byte aligned), i.e. inside what the check above accepted:
+        // [w.ms_bytes, w.bytes) belongs to the kernels for long sequences and the piece-wise derandomize pass, which a sharded batch
+        // reaches only behind launch_max_bytes on this stream (map_batch_dev_impl's two-kernel route)
+        uint8_t *ms_shard = static_cast<uint8_t *>(d_work) + w.ms_bytes;
         for (size_t sh = 0; sh < shards.size(); sh++) {
             DevCopy::PlanState *plan_state = nullptr;
             const kbo::DevIndexView view = device_view(shards[sh], current_device(), &plan_state, count_bases ? total_bases : 0);
@@ -1185,7 +1189,6 @@ int kbo_call_walk_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t 
         last_error() = "kbo_call_walk_dev: bad site buffer";
         return KBO_E_BAD_ARG;
     }
-    if (hipMemsetAsync(d_count, 0, kbo::kCallSegs * 64 + 64, static_cast<hipStream_t>(stream)) != hipSuccess) return KBO_E_HIP;
     const CallSink sink{d_sites, d_count, (uint32_t)(capacity / kbo::kCallSegs), (uint32_t)threshold};
     return ms_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, d_ms_out, nullptr, nullptr, d_work,
                              work_bytes, stream, &sink);
@@ -1400,6 +1403,9 @@ int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t
                     KBO_E_BAD_ARG, "d_concat/d_work must be 16-byte, d_ms/d_chars_out 4-byte aligned");
         threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob);
         KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
+        // a sharded index takes the two-kernel route below: the walk's figure + one shard's values, and the derandomize pass's region
+        KBO_REQUIRE(!idx->sharded() || work_bytes >= kbo_index_work_bytes(idx, n_seqs, total_bases, max_seq_len), KBO_E_BAD_ARG,
+                    "d_work is smaller than kbo_index_work_bytes() for this batch over a sharded index");
         if (idx->sharded()) return; // (two kernels, below)
         hipStream_t s = static_cast<hipStream_t>(stream);
         const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k);
@@ -1515,7 +1521,17 @@ int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t
     rc = kbo_derand_translate_dev(d_ms, d_offsets, n_seqs, total_bases, idx->host.k, threshold, format ? d_concat : nullptr, d_chars_out,
                                   max_seq_len, w.derand_bytes ? static_cast<uint8_t *>(d_work) + w.derand_off : nullptr, w.derand_bytes, stream);
     if (rc != KBO_OK || !find) return rc;
-    return kbo_run_lengths_dev(d_chars_out, d_offsets, n_seqs, max_seq_len, find->max_gap_len, find->d_rle_work, find->d_records, find->capacity, stream);
+    // the run lengths of the kernels' own characters, like the one-kernel routes': no run for a sequence of fewer than 3 bases, whose
+    // bytes of d_chars_out this route leaves unwritten (kbo_run_lengths_dev would count runs in whatever the caller's buffer held there)
+    return guarded([&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        uint32_t *rle_scratch = static_cast<uint32_t *>(find->d_rle_work);
+        uint32_t *total = rle_scratch + kbo::chunk_items_scratch_words((uint32_t)n_seqs); // last word of the work buffer
+        const uint32_t gap = (uint32_t)std::min<size_t>(find->max_gap_len, 0xFFFFFFFFu), cap = (uint32_t)std::min<size_t>(find->capacity, 0xFFFFFFFFu);
+        const uint32_t longest = (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
+        HIP_OK(kbo::launch_rle_count(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, total, s, longest, true));
+        if (cap) HIP_OK(kbo::launch_rle_emit(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, find->d_records, cap, s, longest, true));
+    });
 }
 } // namespace
 

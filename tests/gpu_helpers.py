@@ -116,3 +116,82 @@ def long_reads(rng, g, n_reads, read_len, sub_rate):
         p[hit] = acgt[rng.integers(0, 4, int(hit.sum()))]
         out[r * read_len:(r + 1) * read_len] = p
     return out, np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(read_len)
+
+
+def round16(n):
+    return (int(n) + 15) // 16 * 16
+
+
+def scratch_guard_bytes(n_seqs, total, k):
+    """back guard of a d_work / scratch buffer: everything the largest figure of any route could reach beyond a buffer declared at the
+    smallest one (kbo_work_bytes at max_seq_len = 0 holds every region, plus two shards' MS values)"""
+    return int(kbo_amd.lib().kbo_work_bytes(n_seqs, total, 0, k)) + 2 * (round16(total) + 16)
+
+
+PER_BASE_GUARD = 64 << 10  # back guard of a per-base buffer
+
+
+class Guarded:
+    """A device buffer of exactly `n` bytes inside one torch uint8 tensor laid out [front guard][n bytes][back guard].  The front
+    guard is a multiple of 256 bytes, so the buffer keeps torch's alignment.  fill() writes a seeded pseudo-random pattern (never
+    zeros) over all of it, then the caller's bytes: `data` at the start of the buffer, `front_bytes` / `back_bytes` as the last bytes of the front guard / the first
+    bytes behind `data` (input buffers: bytes that continue the genome, so that a kernel that reads past them changes its results).  check()
+    names the first guard byte that changed."""
+
+    def __init__(self, name, n, back, device, front=4096, seed=0, data=None, front_bytes=None, back_bytes=None):
+        import torch
+        assert front % 256 == 0 and n >= 0 and back >= 0
+        self.name, self.n, self.front, self.back = name, int(n), int(front), int(back)
+        self.device = device
+        self.t = torch.empty(self.front + self.n + self.back, dtype=torch.uint8, device=device)
+        self.data, self.front_bytes, self.back_bytes = data, front_bytes, back_bytes
+        self.fill(seed)
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + self.front
+
+    @property
+    def buf(self):
+        return self.t[self.front:self.front + self.n]
+
+    def host(self):
+        return self.buf.cpu().numpy()
+
+    def fill(self, seed):
+        """every byte from the pattern of `seed`, then the caller's bytes over it; the guards are remembered for check()"""
+        import torch
+        rng = np.random.default_rng(0x6B626F ^ (seed * 7919) ^ (self.n << 3))
+        img = rng.integers(1, 256, len(self.t), dtype=np.uint8)  # (1 .. 255: never a zero byte)
+        if self.front_bytes is not None:
+            fb = np.asarray(self.front_bytes, dtype=np.uint8)[-self.front:]
+            img[self.front - len(fb):self.front] = fb
+        if self.data is not None:
+            d = np.asarray(self.data, dtype=np.uint8).ravel()
+            assert len(d) <= self.n
+            img[self.front:self.front + len(d)] = d
+        if self.back_bytes is not None:
+            bb = np.asarray(self.back_bytes, dtype=np.uint8)
+            a = self.front + (len(self.data) if self.data is not None else 0)  # (the buffer's unspecified tail continues as well)
+            bb = bb[:len(img) - a]
+            img[a:a + len(bb)] = bb
+        self.t.copy_(torch.from_numpy(img).to(self.device))
+        self.image = self.t.clone()
+
+    def check(self):
+        """None, or (side, first changed offset from the guard's start, number of changed bytes)"""
+        diff = self.t != self.image
+        for side, a, b in (("front", 0, self.front), ("back", self.front + self.n, len(self.t))):
+            bad = diff[a:b].nonzero()
+            if len(bad):
+                return side, int(bad[0]), int(len(bad))
+        return None
+
+    def changed(self):
+        """any byte of buffer or guards different from what fill() wrote"""
+        return bool((self.t != self.image).any())
+
+    def assert_intact(self, what=""):
+        r = self.check()
+        assert r is None, "%s%s: %s guard changed, first bad byte at guard offset %d, %d bytes changed" % (
+            what + ": " if what else "", self.name, r[0], r[1], r[2])

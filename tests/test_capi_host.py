@@ -402,3 +402,39 @@ def test_sharded_index_counts_the_union(oracle, revcomp):
                 assert e.value.code == -8  # KBO_E_UNSUPPORTED
     one, _ = kbo_amd.build(seqs, kbo_amd.BuildOpts(k=31))
     assert one.shards() == 1
+
+
+def test_work_byte_figures():
+    """The size arithmetic of the device-resident contract (kbo_hip.h, INTEGRATION.md "Device-resident buffers: slack"), host
+    only: the walks' figure is within the full one, both are whole 16-byte blocks and grow with the batch, and an index's figure
+    is kbo_work_bytes() - plus one further shard's MS values, round16(total) + 16 <= total + 32 bytes, for a sharded index."""
+    L = kbo_amd.lib()
+    rng = np.random.default_rng(5)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    seqs = [acgt[rng.integers(0, 4, 3000)].tobytes(), acgt[rng.integers(0, 4, 2000)].tobytes()]
+    totals = [1, 15, 16, 17, 160, 1000, 4096, 150_001, 10_000_000, 123_456_789, 4_000_000_000]
+    for k in (11, 31, 63):
+        plain, _ = kbo_amd.build(seqs, kbo_amd.BuildOpts(k=k))
+        try:
+            L.kbo_set_index_shards(2)
+            sharded, _ = kbo_amd.build(seqs, kbo_amd.BuildOpts(k=k))
+        finally:
+            L.kbo_set_index_shards(0)
+        assert plain.shards() == 1 and sharded.shards() == 2
+        for n in (1, 3, 1000, 1_000_000):
+            for max_len in (0, 1, 31, 160, 161, 1000):
+                prev = None
+                for total in totals:
+                    if total < n:
+                        continue
+                    full = int(L.kbo_work_bytes(n, total, max_len, k))
+                    walk = int(L.kbo_ms_work_bytes(n, total, max_len, k))
+                    what = (k, n, total, max_len)
+                    assert walk <= full and walk % 16 == 0 and full % 16 == 0, what
+                    if prev is not None:
+                        assert walk >= prev[0] and full >= prev[1], what
+                    prev = (walk, full)
+                    assert int(L.kbo_index_work_bytes(plain._h, n, total, max_len)) == full, what
+                    shard = (total + 15) // 16 * 16 + 16
+                    assert shard <= total + 32
+                    assert int(L.kbo_index_work_bytes(sharded._h, n, total, max_len)) == full + shard, what
