@@ -1,7 +1,8 @@
 // capi_internal.hpp — declarations shared by the translation units behind include/kbo_hip.h:
 //   device_index.cpp  the index handle and its per-device copies,
 //   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline, run-length sink,
-//   kbo_capi.cpp      the extern "C" entry points.
+//   kbo_capi.cpp      the extern "C" entry points,
+//   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*).
 #pragma once
 #include <atomic>
 #include <cstdint>

@@ -1020,890 +1020,10 @@ int kbo_find(kbo_index_t *idx, const uint8_t *query, size_t len, const kbo_find_
 
 void kbo_free(void *p) { std::free(p); }
 
-namespace {
-// work buffer of kbo_ms_batch_dev: items, then the scan scratch of the chunked item list
-struct DevWork {
-    bool chunked;
-    uint32_t chunk, n_slots;
-    size_t bytes, plan_off;
-    size_t ms_bytes;                 // what the walks alone need (kbo_ms_batch_dev, kbo_call_walk_dev: kbo_ms_work_bytes) - the regions below are kbo_map_batch_dev's / kbo_find_batch_dev's
-    size_t long_off, long_bytes;     // batches with sequences of more than 160 bases: work of map_long_kernel (long_kernels.hip) ...
-    size_t derand_off, derand_bytes; // ... and of the piece-wise derandomize + translate kernel behind the walk when it does not apply
-};
-DevWork dev_work(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k)
-{
-    DevWork w;
-    w.chunk = (uint32_t)walk_chunk(total_bases, n_seqs, k);
-    w.chunked = max_seq_len == 0 || max_seq_len > w.chunk;
-    const uint64_t slots = w.chunked ? total_bases / w.chunk + n_seqs : n_seqs;
-    w.n_slots = (uint32_t)std::min<uint64_t>(slots, 0xFFFFFFFFu);
-    w.bytes = std::max<uint64_t>(1, slots) * sizeof(kbo::WalkItem);
-    if (w.chunked) w.bytes += kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t) + 16;
-    w.bytes = (w.bytes + 15) / 16 * 16;
-    w.plan_off = w.bytes; // work of the plan-guided walk behind it
-    w.bytes += kbo::plan_work_bytes(std::max<uint64_t>(1, slots), total_bases);
-    w.bytes = (w.bytes + 63) / 64 * 64;
-    w.long_off = w.derand_off = w.ms_bytes = w.bytes;
-    w.long_bytes = w.derand_bytes = 0;
-    if (max_seq_len == 0 || max_seq_len > 160) {
-        w.long_bytes = (kbo::long_work_bytes(n_seqs, total_bases, k) + 63) / 64 * 64;
-        w.derand_bytes = (kbo::derand_piece_work_bytes((uint32_t)std::min<size_t>(n_seqs, 0xFFFFFFFEu), total_bases) + 63) / 64 * 64;
-        w.derand_off = w.long_off + w.long_bytes;
-        w.bytes += w.long_bytes + w.derand_bytes;
-    }
-    return w;
-}
-} // namespace
-
-size_t kbo_work_bytes(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k)
-{
-    return dev_work(n_seqs, total_bases, max_seq_len, k).bytes;
-}
-
-size_t kbo_ms_work_bytes(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k)
-{
-    return dev_work(n_seqs, total_bases, max_seq_len, k).ms_bytes;
-}
-
-size_t kbo_index_work_bytes(const kbo_index_t *idx, size_t n_seqs, uint64_t total_bases, size_t max_seq_len)
-{
-    if (!idx) return 0;
-    const size_t base = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k).bytes;
-    return base + (idx->sharded() ? ((size_t)total_bases + 15) / 16 * 16 + 16 : 0); // + one further shard's MS values
-}
-
-namespace {
-std::atomic<bool> g_ms_one_kernel{true}; // kbo_ms_batch_dev: batches of reads through map_reads_kernel's MS-emitting form (kbo_set_ms_one_kernel)
-int ms_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs,
-                      uint64_t total_bases, size_t max_seq_len, uint8_t *d_ms_out, uint32_t *d_lo_out,
-                      uint32_t *d_hi_out, void *d_work, size_t work_bytes, void *stream, const CallSink *call,
-                      bool count_bases = true /* false: the caller's own device_view() has counted this batch for the copy's lazy plan structures */)
-{
-    return guarded([&] {
-        KBO_REQUIRE(idx && d_concat && d_offsets && d_ms_out && d_work, KBO_E_BAD_ARG, "null argument");
-        KBO_REQUIRE(n_seqs > 0 && total_bases > 0, KBO_E_EMPTY_QUERY, "empty batch");
-        KBO_REQUIRE(n_seqs < (1ull << 28) && total_bases < 0xFFFFFF00ull, KBO_E_UNSUPPORTED,
-                    "one launch covers < 2^28 sequences and < 4 GiB of query: split the batch");
-        KBO_REQUIRE(((uintptr_t)d_concat & 15) == 0 && ((uintptr_t)d_ms_out & 3) == 0 &&
-                        ((uintptr_t)d_work & 15) == 0,
-                    KBO_E_BAD_ARG, "d_concat/d_work must be 16-byte and d_ms_out 4-byte aligned");
-#ifndef KBO_WALK_DEBUG
-        KBO_REQUIRE((d_lo_out == nullptr) == (d_hi_out == nullptr), KBO_E_BAD_ARG, "lo/hi must come together");
-#endif
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const std::vector<kbo_index *> shards = shards_of(idx); // (a sharded index: every shard is walked, the maximum kept)
-        KBO_REQUIRE(shards.size() == 1 || (!d_lo_out && !call), KBO_E_UNSUPPORTED,
-                    "intervals and the call mode need the rows of one index; this handle is a sharded index");
-        kbo::WalkItem *items = static_cast<kbo::WalkItem *>(d_work);
-        // reads: one item per sequence; batches that hold (or may hold) long sequences: chunks
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k);
-        const size_t shard_ms = shards.size() > 1 ? ((size_t)total_bases + 15) / 16 * 16 + 16 : 0; // one further shard's MS values
-        // (the walks never touch the regions of the kernels for long sequences: only kbo_map_batch_dev / kbo_find_batch_dev ask for those)
-        KBO_REQUIRE(work_bytes >= w.ms_bytes + shard_ms, KBO_E_BAD_ARG,
-                    "d_work is smaller than kbo_ms_work_bytes() (+ one shard's MS values for a sharded index: kbo_index_work_bytes()) for this batch");
-        KBO_REQUIRE(total_bases / w.chunk + n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
-        if (call) HIP_OK(hipMemsetAsync(call->d_counts, 0, kbo::kCallSegs * 64 + 64, s)); // (kbo_call_walk_dev's counters: once the call is accepted)
-        // a batch of reads over a copy with a depth table, nothing but the MS values asked for: map_reads_kernel in the form that puts
-        // the values together in LDS (k where nothing happened, the ramps behind the mismatches, the table's values right behind them),
-        // stopping there - no characters are made - and the plain walk for the reads it leaves (C2: 0.33 against 0.61 ms per
-        // 1 M reads for the plan-guided walk below, which stays what larger batches' chunks, the intervals, the call mode and the
-        // work counters take)
-        if (shards.size() == 1 && !d_lo_out && !call && !w.chunked && max_seq_len > 0 && g_ms_one_kernel.load() != 0 && !g_plan_stats.load()) {
-            DevCopy::PlanState *plan_state = nullptr;
-            const kbo::DevIndexView view = device_view(idx, current_device(), &plan_state, count_bases ? total_bases : 0);
-            kbo::WalkArgs a{};
-            a.ix = view;
-            a.q = d_concat;
-            a.q_bytes = total_bases;
-            a.items = items;
-            a.n_items = w.n_slots;
-            a.d_out = d_ms_out;
-            a.max_item_len = (uint32_t)max_seq_len;
-            attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, plan_state);
-            a.chars_out = nullptr;
-            a.map_thr = idx->host.k; // (no value is derandomised here)
-            a.map_fmt = 0;
-            a.map_want_ms = 1;
-            count_bases = false; // (this batch is counted: the walk below, should the copy not have what the kernel needs, must not count it again)
-            if (a.gitems && kbo::map_reads_applies(a)) {
-                a.seq_off = d_offsets;
-                a.host_bailed = plan_state ? plan_state->bailed : nullptr;
-                HIP_OK(kbo::launch_map_reads(a, s));
-                if (kbo::map_reads_finish_applies(a)) HIP_OK(kbo::launch_map_reads_finish(a, s)); // (the reads it left: their values by one kernel)
-                else HIP_OK(kbo::launch_redo_pass(a, s));
-                if (!a.host_bailed) plan_after_launch(a, s, plan_state);
-                return;
-            }
-        }
-        if (w.chunked) {
-            uint32_t *scratch = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d_work) +
-                                                            ((size_t)w.n_slots * sizeof(kbo::WalkItem) + 15) / 16 * 16);
-            HIP_OK(kbo::launch_make_chunk_items(d_offsets, (uint32_t)n_seqs, w.chunk, idx->host.k, w.n_slots, items, scratch, s, call != nullptr));
-        } else {
-            HIP_OK(kbo::launch_make_items(d_offsets, (uint32_t)n_seqs, items, s));
-        }
-        // one further shard's values right behind the walks' own region (64-byte aligned), i.e. inside what the check above accepted:
-        // [w.ms_bytes, w.bytes) belongs to the kernels for long sequences and the piece-wise derandomize pass, which a sharded batch
-        // reaches only behind launch_max_bytes on this stream (map_batch_dev_impl's two-kernel route)
-        uint8_t *ms_shard = static_cast<uint8_t *>(d_work) + w.ms_bytes;
-        for (size_t sh = 0; sh < shards.size(); sh++) {
-            DevCopy::PlanState *plan_state = nullptr;
-            const kbo::DevIndexView view = device_view(shards[sh], current_device(), &plan_state, count_bases ? total_bases : 0);
-            kbo::WalkArgs a{};
-            a.ix = view;
-            a.q = d_concat;
-            a.q_bytes = total_bases;
-            a.items = items;
-            a.n_items = w.n_slots;
-            a.rounds = 0;
-            a.d_out = sh == 0 ? d_ms_out : ms_shard;
-            a.lo_out = d_lo_out;
-            a.hi_out = d_hi_out;
-            a.call_sites = call ? static_cast<uint4 *>(call->d_sites) : nullptr;
-            a.call_counts = call ? call->d_counts : nullptr;
-            a.call_cap = call ? call->cap_per_list : 0;
-            a.call_thr = call ? call->threshold : 0;
-            a.max_item_len = w.chunked ? w.chunk + (call ? 2u : 1u) * idx->host.k : (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
-            attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, plan_state);
-            HIP_OK(kbo::launch_ms_walk(a, walk_max_waves(), s));
-            plan_after_launch(a, s, plan_state);
-            if (sh > 0) HIP_OK(kbo::launch_max_bytes(d_ms_out, ms_shard, total_bases, s)); // depth against the union = maximum
-        }
-    });
-}
-} // namespace
-
-int kbo_ms_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs,
-                     uint64_t total_bases, size_t max_seq_len, uint8_t *d_ms_out, uint32_t *d_lo_out,
-                     uint32_t *d_hi_out, void *d_work, size_t work_bytes, void *stream)
-{
-    return ms_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, d_ms_out, d_lo_out, d_hi_out, d_work,
-                             work_bytes, stream, nullptr);
-}
-
-int kbo_call_walk_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs,
-                      uint64_t total_bases, size_t max_seq_len, size_t threshold, uint8_t *d_ms_out, void *d_sites,
-                      size_t capacity, uint32_t *d_count, void *d_work, size_t work_bytes, void *stream)
-{
-    if (!d_sites || !d_count || capacity < kbo::kCallSegs || capacity > 0x7FFFFF00ull) {
-        last_error() = "kbo_call_walk_dev: bad site buffer";
-        return KBO_E_BAD_ARG;
-    }
-    const CallSink sink{d_sites, d_count, (uint32_t)(capacity / kbo::kCallSegs), (uint32_t)threshold};
-    return ms_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, d_ms_out, nullptr, nullptr, d_work,
-                             work_bytes, stream, &sink);
-}
-
-int kbo_plan_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k, const void *d_work,
-                       uint64_t out[KBO_PLAN_STATS], void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(d_work && out && n_seqs > 0 && total_bases > 0, KBO_E_BAD_ARG, "null / empty argument");
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, k);
-        const kbo::PlanLayout L = kbo::plan_layout(w.n_slots, total_bases);
-        const uint8_t *plan = static_cast<const uint8_t *>(d_work) + w.plan_off;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        uint32_t ctl[16], st[kbo::kPlanStatSlots * kbo::kPlanStatWords], tot[2];
-        const uint32_t last = 2u * w.n_slots; // the scan's extra entry: its prefix is the number of units
-        HIP_OK(hipMemcpyAsync(ctl, plan + L.qctl, sizeof ctl, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(st, plan + L.pstats, sizeof st, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(&tot[0], plan + L.ucount + (size_t)last * 4, 4, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(&tot[1], plan + L.usums + (size_t)(last / 1024u) * 4, 4, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < KBO_PLAN_STATS; i++) out[i] = 0;
-        for (uint32_t sl = 0; sl < kbo::kPlanStatSlots; sl++) {
-            for (uint32_t i = 0; i < 8; i++) out[i] += st[sl * kbo::kPlanStatWords + i];
-            for (uint32_t i = 0; i < 3; i++) out[12 + i] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabLookups + i];
-            out[16] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabAnchored];
-        }
-        out[15] = ctl[4];
-        out[17] = ctl[5];
-        out[8] = (uint64_t)tot[0] + tot[1];
-        out[9] = ctl[1];
-        out[10] = ctl[2];
-        out[11] = ctl[3];
-    });
-}
-
-int kbo_plan_flags_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k, const void *d_work, uint8_t *flags_out, void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(d_work && flags_out && n_seqs > 0 && total_bases > 0, KBO_E_BAD_ARG, "null / empty argument");
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, k);
-        KBO_REQUIRE(!w.chunked, KBO_E_UNSUPPORTED, "one item per sequence only (reads)");
-        const kbo::PlanLayout L = kbo::plan_layout(w.n_slots, total_bases);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        HIP_OK(hipMemcpyAsync(flags_out, static_cast<const uint8_t *>(d_work) + w.plan_off + L.redo, n_seqs, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-    });
-}
-
 int kbo_set_map_long(int mode)
 {
     kbo::set_map_long(mode);
     return KBO_OK;
-}
-
-int kbo_set_ms_one_kernel(int on)
-{
-    g_ms_one_kernel = on != 0;
-    return KBO_OK;
-}
-
-int kbo_long_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k, const void *d_work, uint64_t out[KBO_LONG_STATS],
-                       void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(d_work && out && n_seqs > 0 && total_bases > 0, KBO_E_BAD_ARG, "null / empty argument");
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, k);
-        KBO_REQUIRE(w.long_bytes != 0, KBO_E_UNSUPPORTED, "not a batch of long sequences");
-        uint32_t ctl[32], st[kbo::kPlanStatSlots * kbo::kPlanStatWords];
-        HIP_OK(kbo::long_read_stats(static_cast<const uint8_t *>(d_work) + w.long_off, n_seqs, total_bases, k, ctl, st, static_cast<hipStream_t>(stream)));
-        for (uint32_t i = 0; i < KBO_LONG_STATS; i++) out[i] = 0;
-        out[0] = ctl[0];
-        out[1] = ctl[4];
-        out[2] = ctl[1];
-        for (uint32_t i = 0; i < 5 && 8 + i < KBO_LONG_STATS; i++) out[8 + i] = (uint64_t)ctl[16 + i] << 4; // (KBO_LONG_X & 128: shader cycles by phase)
-        for (uint32_t i = 0; i < 9 && 16 + i < KBO_LONG_STATS; i++) out[16 + i] = ctl[8 + i]; // (why flagged: list cap / ext / back / on; +4: after the band pass)
-        for (uint32_t sl = 0; sl < kbo::kPlanStatSlots; sl++) {
-            out[3] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSeedLookups];
-            out[4] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSeedExtensions];
-            out[5] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabLookups];
-            out[6] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabAnchored];
-            out[13] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatUnits];
-            out[14] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatAccepted];
-        }
-    });
-}
-
-size_t kbo_derand_work_bytes(size_t n_seqs, uint64_t total_bases)
-{
-    return kbo::derand_piece_work_bytes((uint32_t)std::min<size_t>(n_seqs, 0xFFFFFFFEu), total_bases);
-}
-
-int kbo_derand_translate_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                             size_t k, size_t threshold, const uint8_t *d_ref, uint8_t *d_chars_out,
-                             size_t max_seq_len, void *d_work, size_t work_bytes, void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(d_ms && d_offsets && d_chars_out, KBO_E_BAD_ARG, "null argument");
-        KBO_REQUIRE(n_seqs > 0 && n_seqs < 0xFFFFFFFFull, KBO_E_EMPTY_QUERY, "empty batch");
-        KBO_REQUIRE(k > 0 && k <= 255, KBO_E_BAD_ARG, "k in 1..255");
-        KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
-        KBO_REQUIRE(((uintptr_t)d_ms & 3) == 0 && ((uintptr_t)d_chars_out & 3) == 0 && ((uintptr_t)d_ref & 3) == 0 &&
-                        ((uintptr_t)d_work & 15) == 0,
-                    KBO_E_BAD_ARG, "device buffers must be 4-byte (d_work 16-byte) aligned");
-        HIP_OK(kbo::launch_derand_translate(d_ms, d_offsets, (uint32_t)n_seqs, (uint32_t)k, (uint32_t)threshold,
-                                            d_ref, d_chars_out, nullptr,
-                                            (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu), 0xFFFFFFFFu,
-                                            static_cast<hipStream_t>(stream), total_bases, d_work, work_bytes));
-    });
-}
-
-size_t kbo_run_lengths_work_bytes(size_t n_seqs)
-{
-    return kbo::chunk_items_scratch_words((uint32_t)std::min<size_t>(n_seqs, 0xFFFFFFFEu)) * sizeof(uint32_t) + 16;
-}
-
-namespace {
-// kbo_set_stage_timing: event triples of the one-kernel route's calls (guarded by g_timing_mu)
-std::atomic<int> g_stage_timing{0};
-std::mutex g_timing_mu;
-struct StageEvents { hipEvent_t e0, e1, e1t, e2; };
-std::vector<StageEvents> g_timing_pool, g_timing_used;
-StageEvents timing_take()
-{
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    StageEvents ev{};
-    if (!g_timing_pool.empty()) {
-        ev = g_timing_pool.back();
-        g_timing_pool.pop_back();
-    } else {
-        HIP_OK(hipEventCreate(&ev.e0));
-        HIP_OK(hipEventCreate(&ev.e1));
-        HIP_OK(hipEventCreate(&ev.e1t));
-        HIP_OK(hipEventCreate(&ev.e2));
-    }
-    return ev;
-}
-} // namespace
-
-int kbo_set_stage_timing(int on)
-{
-    if (on <= 1) {
-        g_stage_timing = on != 0;
-        return KBO_OK;
-    }
-    // on > 1: the events of that many calls are made here, not inside the calls that are to be timed
-    return guarded([&] {
-        std::vector<StageEvents> held;
-        for (int i = 0; i < on; ++i)
-            held.push_back(timing_take());
-        std::lock_guard<std::mutex> g(g_timing_mu);
-        g_timing_pool.insert(g_timing_pool.end(), held.begin(), held.end());
-        g_stage_timing = 1;
-    });
-}
-
-int kbo_stage_timing_read(double *kernel_ms_sum, double *redo_ms_sum, int *n_calls)
-{
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(g_timing_mu);
-        double a = 0, b = 0;
-        for (const StageEvents &ev : g_timing_used) {
-            HIP_OK(hipEventSynchronize(ev.e2));
-            float x = 0, y = 0;
-            HIP_OK(hipEventElapsedTime(&x, ev.e0, ev.e1));
-            HIP_OK(hipEventElapsedTime(&y, ev.e1t, ev.e2));
-            a += x;
-            b += y;
-            g_timing_pool.push_back(ev);
-        }
-        if (kernel_ms_sum) *kernel_ms_sum = a;
-        if (redo_ms_sum) *redo_ms_sum = b;
-        if (n_calls) *n_calls = (int)g_timing_used.size();
-        g_timing_used.clear();
-    });
-}
-
-namespace {
-// one fence event per host thread and device: hipStreamWaitEvent takes the event's state at the time of the call, so recording it
-// again for the next batch does not disturb a wait that is already queued
-hipEvent_t tail_fence()
-{
-    thread_local std::map<int, hipEvent_t> evs;
-    hipEvent_t &ev = evs[current_device()];
-    if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    return ev;
-}
-
-// kbo::find behind the characters (kbo_find_batch_dev): format::run_lengths_gapped into d_records
-struct FindTail {
-    size_t max_gap_len;
-    void *d_rle_work;
-    uint32_t *d_records;
-    size_t capacity;
-};
-
-int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                       size_t max_seq_len, double max_error_prob, int format, int want_ms, uint8_t *d_ms, uint8_t *d_chars_out,
-                       void *d_work, size_t work_bytes, void *stream, void *tail_stream, bool split, int *fused,
-                       const FindTail *find = nullptr)
-{
-    if (fused) *fused = 0;
-    bool done = false, counted = false; // (counted: device_view() has seen this batch's bases for the copy's lazy plan structures)
-    size_t threshold = 0;
-    int rc = guarded([&] {
-        KBO_REQUIRE(idx && d_concat && d_offsets && d_ms && d_chars_out && d_work, KBO_E_BAD_ARG, "null argument");
-        KBO_REQUIRE(n_seqs > 0 && total_bases > 0, KBO_E_EMPTY_QUERY, "empty batch");
-        KBO_REQUIRE(n_seqs < (1ull << 28) && total_bases < 0xFFFFFF00ull, KBO_E_UNSUPPORTED,
-                    "one launch covers < 2^28 sequences and < 4 GiB of query: split the batch");
-        KBO_REQUIRE(((uintptr_t)d_concat & 15) == 0 && ((uintptr_t)d_ms & 3) == 0 && ((uintptr_t)d_chars_out & 3) == 0 &&
-                        ((uintptr_t)d_work & 15) == 0,
-                    KBO_E_BAD_ARG, "d_concat/d_work must be 16-byte, d_ms/d_chars_out 4-byte aligned");
-        threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob);
-        KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
-        // a sharded index takes the two-kernel route below: the walk's figure + one shard's values, and the derandomize pass's region
-        KBO_REQUIRE(!idx->sharded() || work_bytes >= kbo_index_work_bytes(idx, n_seqs, total_bases, max_seq_len), KBO_E_BAD_ARG,
-                    "d_work is smaller than kbo_index_work_bytes() for this batch over a sharded index");
-        if (idx->sharded()) return; // (two kernels, below)
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k);
-        KBO_REQUIRE(work_bytes >= w.bytes, KBO_E_BAD_ARG, "d_work is smaller than kbo_work_bytes() for this batch");
-        DevCopy::PlanState *plan_state = nullptr;
-        if (max_seq_len == 0 || max_seq_len > 160) {
-            // sequences of any length: one wave per piece of a sequence (long_kernels.hip), the pieces whose proof fails by the
-            // plain walk + the literal recurrences behind it (on the tail stream when the caller gave one)
-            if (want_ms || !w.long_bytes) return;
-            const kbo::DevIndexView view = device_view(idx, current_device(), &plan_state, total_bases);
-            counted = true;
-            if (!kbo::map_long_applies(view, (uint32_t)threshold)) return;
-            kbo::LongArgs la{};
-            HIP_OK(kbo::launch_map_long(view, d_concat, d_offsets, (uint32_t)n_seqs, total_bases, (uint32_t)threshold, format != 0, d_chars_out,
-                                        static_cast<uint8_t *>(d_work) + w.long_off, s, la, g_plan_stats.load()));
-            hipStream_t ts = s;
-            if (split && static_cast<hipStream_t>(tail_stream) != s) {
-                ts = static_cast<hipStream_t>(tail_stream);
-                hipEvent_t fence = tail_fence();
-                HIP_OK(hipEventRecord(fence, s));
-                HIP_OK(hipStreamWaitEvent(ts, fence, 0));
-            }
-            HIP_OK(kbo::launch_map_long_redo(la, d_ms, ts));
-            if (find) {
-                uint32_t *rle_scratch = static_cast<uint32_t *>(find->d_rle_work);
-                uint32_t *total = rle_scratch + kbo::chunk_items_scratch_words((uint32_t)n_seqs);
-                const uint32_t gap = (uint32_t)std::min<size_t>(find->max_gap_len, 0xFFFFFFFFu), cap = (uint32_t)std::min<size_t>(find->capacity, 0xFFFFFFFFu);
-                const uint32_t longest = (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
-                HIP_OK(kbo::launch_rle_count(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, total, ts, longest, true));
-                if (cap) HIP_OK(kbo::launch_rle_emit(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, find->d_records, cap, ts, longest, true));
-            }
-            done = true;
-            return;
-        }
-        if (w.chunked) return;
-        const kbo::DevIndexView view = device_view(idx, current_device(), &plan_state, total_bases);
-        counted = true;
-        kbo::WalkItem *items = static_cast<kbo::WalkItem *>(d_work);
-        kbo::WalkArgs a{};
-        a.ix = view;
-        a.q = d_concat;
-        a.q_bytes = total_bases;
-        a.items = items;
-        a.n_items = w.n_slots;
-        a.d_out = d_ms;
-        a.max_item_len = (uint32_t)max_seq_len;
-        attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, plan_state);
-        a.chars_out = d_chars_out;
-        a.map_thr = (uint32_t)threshold;
-        a.map_fmt = format ? 1u : 0u;
-        a.map_want_ms = want_ms ? 1u : 0u;
-        if (!a.gitems || !kbo::map_reads_applies(a)) return; // (no plan structures, or the copy is held off: two kernels)
-        a.seq_off = d_offsets; // (the kernel and redo_collect_kernel read the offsets themselves: no item list is made)
-        a.host_bailed = plan_state ? plan_state->bailed : nullptr; // (set by redo_collect_kernel itself: no 8-byte copy behind the launch)
-        // kbo::find with max_gap_len = 0: the kernel counts the runs of the reads it finishes (their characters are in LDS anyway), so
-        // that format::run_lengths_gapped is one pass over the characters instead of two
-        uint32_t *rle_scratch = find ? static_cast<uint32_t *>(find->d_rle_work) : nullptr;
-        const bool count_in_kernel = find && find->max_gap_len == 0 && !format && !want_ms && kbo::map_reads_direct(a);
-        if (count_in_kernel) a.run_counts = rle_scratch;
-        const bool timing = g_stage_timing.load() != 0;
-        StageEvents ev{};
-        if (timing) {
-            ev = timing_take();
-            HIP_OK(hipEventRecord(ev.e0, s));
-        }
-        HIP_OK(kbo::launch_map_reads(a, s));
-        if (timing) HIP_OK(hipEventRecord(ev.e1, s));
-        hipStream_t ts = s;
-        if (split && static_cast<hipStream_t>(tail_stream) != s) { // the second pass on the caller's other stream, behind the kernel
-            ts = static_cast<hipStream_t>(tail_stream);
-            hipEvent_t fence = tail_fence();
-            HIP_OK(hipEventRecord(fence, s));
-            HIP_OK(hipStreamWaitEvent(ts, fence, 0));
-            // (beside another batch's kernel the pass costs by the look-ups it takes away from that kernel rather than by its longest
-            // chain: longer pieces, fewer warm-up bases.  Pieces of 16 / 24 / 32 / 48 / 64 bases at C2, two batches in flight:
-            // 0.341 / 0.324 / 0.316 / 0.343 / 0.337 ms per batch)
-            static const bool env_piece = std::getenv("KBO_REDO_PIECE") != nullptr;
-            if (!env_piece) a.redo_piece = 32u;
-        }
-        if (timing) HIP_OK(hipEventRecord(ev.e1t, ts)); // (when the second pass starts: behind the kernel and behind what `ts` held)
-        if (kbo::map_reads_finish_applies(a)) {
-            // the reads the kernel listed, finished by one kernel: walk, derandomize + translate, characters (and their runs)
-            HIP_OK(kbo::launch_map_reads_finish(a, ts));
-        } else {
-            HIP_OK(kbo::launch_redo_pass(a, ts)); // (redo_collect_kernel reads the offsets as well: no item list at all)
-            HIP_OK(kbo::launch_derand_flagged(d_ms, d_offsets, (uint32_t)n_seqs, idx->host.k, (uint32_t)threshold, format ? d_concat : nullptr,
-                                              d_chars_out, a.redo, (uint32_t)max_seq_len, ts, count_in_kernel ? rle_scratch : nullptr));
-        }
-        if (timing) {
-            HIP_OK(hipEventRecord(ev.e2, ts));
-            std::lock_guard<std::mutex> g(g_timing_mu);
-            g_timing_used.push_back(ev);
-        }
-        if (!a.host_bailed) plan_after_launch(a, ts, plan_state);
-        if (find) { // the run lengths, behind the second pass
-            uint32_t *total = rle_scratch + kbo::chunk_items_scratch_words((uint32_t)n_seqs); // last word of the work buffer
-            const uint32_t gap = (uint32_t)std::min<size_t>(find->max_gap_len, 0xFFFFFFFFu), cap = (uint32_t)std::min<size_t>(find->capacity, 0xFFFFFFFFu);
-            if (count_in_kernel) { // (the flagged reads' counts: launch_derand_flagged's)
-                HIP_OK(kbo::launch_rle_scan_counts((uint32_t)n_seqs, rle_scratch, total, ts));
-            } else
-                HIP_OK(kbo::launch_rle_count(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, total, ts, (uint32_t)max_seq_len, true));
-            if (cap) HIP_OK(kbo::launch_rle_emit(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, find->d_records, cap, ts, (uint32_t)max_seq_len, true));
-        }
-        done = true;
-    });
-    if (rc != KBO_OK || done) {
-        if (fused && done) *fused = 1;
-        return rc;
-    }
-    rc = ms_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, d_ms, nullptr, nullptr, d_work, work_bytes, stream, nullptr, !counted);
-    if (rc != KBO_OK) return rc;
-    const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k);
-    rc = kbo_derand_translate_dev(d_ms, d_offsets, n_seqs, total_bases, idx->host.k, threshold, format ? d_concat : nullptr, d_chars_out,
-                                  max_seq_len, w.derand_bytes ? static_cast<uint8_t *>(d_work) + w.derand_off : nullptr, w.derand_bytes, stream);
-    if (rc != KBO_OK || !find) return rc;
-    // the run lengths of the kernels' own characters, like the one-kernel routes': no run for a sequence of fewer than 3 bases, whose
-    // bytes of d_chars_out this route leaves unwritten (kbo_run_lengths_dev would count runs in whatever the caller's buffer held there)
-    return guarded([&] {
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        uint32_t *rle_scratch = static_cast<uint32_t *>(find->d_rle_work);
-        uint32_t *total = rle_scratch + kbo::chunk_items_scratch_words((uint32_t)n_seqs); // last word of the work buffer
-        const uint32_t gap = (uint32_t)std::min<size_t>(find->max_gap_len, 0xFFFFFFFFu), cap = (uint32_t)std::min<size_t>(find->capacity, 0xFFFFFFFFu);
-        const uint32_t longest = (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
-        HIP_OK(kbo::launch_rle_count(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, total, s, longest, true));
-        if (cap) HIP_OK(kbo::launch_rle_emit(d_chars_out, d_offsets, (uint32_t)n_seqs, gap, rle_scratch, find->d_records, cap, s, longest, true));
-    });
-}
-} // namespace
-
-int kbo_find_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                       size_t max_seq_len, double max_error_prob, size_t max_gap_len, uint8_t *d_ms, uint8_t *d_chars_out, void *d_work,
-                       size_t work_bytes, void *d_rle_work, uint32_t *d_records, size_t capacity, void *stream, void *tail_stream, int *fused)
-{
-    if (!d_rle_work || (!d_records && capacity) || ((uintptr_t)d_rle_work & 3) || ((uintptr_t)d_records & 3) || n_seqs >= (1ull << 31)) {
-        last_error() = "kbo_find_batch_dev: bad run-length buffers";
-        return KBO_E_BAD_ARG;
-    }
-    const FindTail ft{max_gap_len, d_rle_work, d_records, capacity};
-    return map_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, 0, 0, d_ms, d_chars_out, d_work,
-                              work_bytes, stream, tail_stream, true, fused, &ft);
-}
-
-int kbo_map_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                      size_t max_seq_len, double max_error_prob, int format, int want_ms, uint8_t *d_ms, uint8_t *d_chars_out,
-                      void *d_work, size_t work_bytes, void *stream, int *fused)
-{
-    return map_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, want_ms, d_ms, d_chars_out,
-                              d_work, work_bytes, stream, nullptr, false, fused);
-}
-
-int kbo_map_batch_dev_tail(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                           size_t max_seq_len, double max_error_prob, int format, int want_ms, uint8_t *d_ms, uint8_t *d_chars_out,
-                           void *d_work, size_t work_bytes, void *stream, void *tail_stream, int *fused)
-{
-    return map_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, want_ms, d_ms, d_chars_out,
-                              d_work, work_bytes, stream, tail_stream, true, fused);
-}
-
-// ---- kbo_map_stream_*: pipelines of (kernel stream, second-pass stream), two slots each
-// A (kernel stream, second-pass stream) pair in which the KERNELS' stream is kept off some compute units (32 of the device's 256 by
-// default; KBO_TAIL_CUS / tail_cus = how many, 0 = two plain streams) and the second passes' stream is a plain one: a second pass is a
-// chain of dependent look-ups by a few hundred waves, and beside kernels that hold every wave slot of the device each link of the chain
-// waits for a slot - 0.12 ms alone, 0.37 beside two kernels, which then wait for it in turn.  With units the kernels cannot take, the
-// pass's workgroups find free slots at once - and one that is WORK (5 % substitutions, long sequences, repeats) still spreads over the
-// whole device.  C2, two pipelines, same box: plain / plain 757 Gbp/s; second passes CONFINED to 16 units of their own 973, but 5 %
-// substitutions 245 -> 76 (adaptive forms of that: LABNOTES round 6); kernels off 32 units, second passes plain: 967 and every variant at
-// or above the plain arrangement (reserved 16 / 24 / 32 / 40 / 48 units: 878 / 958 / 967 / 904 / 896 - 32 is four per XCD).
-static int tail_cus_default() // compute units the kernels' streams stay off (KBO_TAIL_CUS; 0 = plain streams, the arrangement of rounds 4 - 5)
-{
-    static const int v = std::getenv("KBO_TAIL_CUS") ? std::atoi(std::getenv("KBO_TAIL_CUS")) : 32;
-    return v;
-}
-static void make_stream_pair(int device, int tail_cus, hipStream_t *ks, hipStream_t *ts)
-{
-    const int want = tail_cus >= 0 ? tail_cus : tail_cus_default();
-    hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, device));
-    const int n_cu = prop.multiProcessorCount;
-    HIP_OK(hipStreamCreateWithFlags(ts, hipStreamNonBlocking));
-    if (want <= 0 || want >= n_cu) {
-        HIP_OK(hipStreamCreateWithFlags(ks, hipStreamNonBlocking));
-        return;
-    }
-    std::vector<uint32_t> mask_k((size_t)(n_cu + 31) / 32, 0u);
-    for (int cu = want; cu < n_cu; cu++) mask_k[(size_t)cu / 32] |= 1u << (cu % 32);
-    // (a runtime that refuses the mask - none seen - gets a plain stream: slower, never wrong)
-    if (hipExtStreamCreateWithCUMask(ks, (uint32_t)mask_k.size(), mask_k.data()) != hipSuccess) {
-        (void)hipGetLastError();
-        *ks = nullptr;
-        HIP_OK(hipStreamCreateWithFlags(ks, hipStreamNonBlocking));
-    }
-}
-
-int kbo_stream_pair_create(int tail_cus, void **stream, void **tail_stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(stream && tail_stream, KBO_E_BAD_ARG, "null argument");
-        hipStream_t ks = nullptr, ts = nullptr;
-        make_stream_pair(current_device(), tail_cus, &ks, &ts);
-        *stream = ks;
-        *tail_stream = ts;
-    });
-}
-
-void kbo_stream_pair_destroy(void *stream, void *tail_stream)
-{
-    if (stream) (void)hipStreamDestroy(static_cast<hipStream_t>(stream));
-    if (tail_stream) (void)hipStreamDestroy(static_cast<hipStream_t>(tail_stream));
-}
-
-struct kbo_map_stream {
-    kbo_index_t *idx = nullptr;
-    int device = 0;
-    // a pipeline: the kernels' stream `ks` (kept off 32 compute units) and the second passes' stream `ts` (plain): make_stream_pair
-    struct Pipe { hipStream_t ks = nullptr, ts = nullptr; };
-    struct Slot {
-        DevBuf work, ms;
-        hipEvent_t done = nullptr;
-        uint64_t ticket = 0; // the batch that used it last (0: none yet)
-    };
-    std::vector<Pipe> pipes;
-    std::deque<Slot> slots; // 2 per pipeline (a deque: the buffers do not move)
-    size_t max_seqs = 0, max_seq_len = 0, work_bytes = 0;
-    uint64_t max_bases = 0, next = 0;
-    hipEvent_t ready = nullptr, kdone = nullptr;
-    std::mutex mu;
-    kbo_map_stream() = default;
-    kbo_map_stream(const kbo_map_stream &) = delete;
-    kbo_map_stream &operator=(const kbo_map_stream &) = delete;
-    ~kbo_map_stream() // (also what a create that fails half-way leaves: whatever it had made so far)
-    {
-        for (auto &p : pipes) {
-            if (p.ks) (void)hipStreamSynchronize(p.ks);
-            if (p.ts) (void)hipStreamSynchronize(p.ts);
-        }
-        for (auto &sl : slots)
-            if (sl.done) (void)hipEventDestroy(sl.done);
-        if (ready) (void)hipEventDestroy(ready);
-        if (kdone) (void)hipEventDestroy(kdone);
-        for (auto &p : pipes) {
-            if (p.ks) (void)hipStreamDestroy(p.ks);
-            if (p.ts) (void)hipStreamDestroy(p.ts);
-        }
-    }
-};
-
-int kbo_map_stream_create(kbo_index_t *idx, int pipelines, size_t max_seqs, uint64_t max_bases, size_t max_seq_len, kbo_map_stream_t **out)
-{
-    return guarded([&] {
-        KBO_REQUIRE(idx && out && max_seqs > 0 && max_bases > 0, KBO_E_BAD_ARG, "null / empty argument");
-        KBO_REQUIRE(pipelines >= 1 && pipelines <= 8, KBO_E_BAD_ARG, "1 .. 8 pipelines");
-        *out = nullptr;
-        std::unique_ptr<kbo_map_stream> m(new kbo_map_stream());
-        m->idx = idx;
-        m->device = current_device();
-        m->max_seqs = max_seqs;
-        m->max_bases = max_bases;
-        m->max_seq_len = max_seq_len;
-        m->work_bytes = kbo_index_work_bytes(idx, max_seqs, max_bases, max_seq_len);
-        m->pipes.resize((size_t)pipelines);
-        m->slots.resize(2 * (size_t)pipelines);
-        for (auto &p : m->pipes) {
-            make_stream_pair(m->device, -1, &p.ks, &p.ts);
-        }
-        for (auto &sl : m->slots) {
-            sl.work.alloc(m->work_bytes + 64);
-            sl.ms.alloc(((size_t)max_bases + 15) / 16 * 16 + 64);
-            HIP_OK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        }
-        HIP_OK(hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&m->kdone, hipEventDisableTiming));
-        *out = m.release();
-    });
-}
-
-int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                          size_t max_seq_len, double max_error_prob, int format, uint8_t *d_ms_out, uint8_t *d_chars_out, void *ready_stream,
-                          uint64_t *ticket, int *fused)
-{
-    if (!m) {
-        last_error() = "kbo_map_stream_submit: null stream";
-        return KBO_E_BAD_ARG;
-    }
-    std::lock_guard<std::mutex> g(m->mu);
-    int rc = guarded([&] {
-        KBO_REQUIRE(n_seqs <= m->max_seqs && total_bases <= m->max_bases, KBO_E_BAD_ARG, "the batch exceeds what the stream's slots were made for");
-        // (the stream's queues, events and slots live on the device it was created on: a submit from a thread whose current device is another
-        // one would pair that device's copy of the index with them)
-        KBO_REQUIRE(current_device() == m->device, KBO_E_BAD_ARG, "kbo_map_stream_submit: the calling thread's current device is not the one the stream was created on");
-        KBO_REQUIRE(kbo_index_work_bytes(m->idx, n_seqs, total_bases, max_seq_len) <= m->work_bytes, KBO_E_BAD_ARG,
-                    "the batch needs more work memory than the stream's slots have (max_seq_len of kbo_map_stream_create)");
-    });
-    if (rc != KBO_OK) return rc;
-    const uint64_t n = m->next;
-    kbo_map_stream::Pipe &p = m->pipes[n % m->pipes.size()];
-    kbo_map_stream::Slot &sl = m->slots[n % m->slots.size()];
-    hipStream_t kern = p.ks, tail = p.ts;
-    rc = guarded([&] {
-        // the slot's buffers are free again behind its last batch; the inputs are there behind what ready_stream holds so far
-        if (sl.ticket) HIP_OK(hipStreamWaitEvent(kern, sl.done, 0));
-        if (ready_stream) {
-            HIP_OK(hipEventRecord(m->ready, static_cast<hipStream_t>(ready_stream)));
-            HIP_OK(hipStreamWaitEvent(kern, m->ready, 0));
-        }
-    });
-    if (rc != KBO_OK) return rc;
-    rc = map_batch_dev_impl(m->idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, d_ms_out ? 1 : 0,
-                            d_ms_out ? d_ms_out : sl.ms.as<uint8_t>(), d_chars_out, sl.work.p, m->work_bytes, kern, tail, true, fused);
-    if (rc != KBO_OK) return rc;
-    rc = guarded([&] { // complete when both streams have come this far
-        HIP_OK(hipEventRecord(m->kdone, kern));
-        HIP_OK(hipStreamWaitEvent(tail, m->kdone, 0));
-        HIP_OK(hipEventRecord(sl.done, tail));
-    });
-    if (rc != KBO_OK) return rc;
-    m->next = n + 1;
-    sl.ticket = n + 1;
-    if (ticket) *ticket = n + 1;
-    return KBO_OK;
-}
-
-namespace {
-// the event that says the batch with this ticket is complete: its own while its slot still holds it, else that of the next batch of
-// the same pipeline whose slot still holds it - a pipeline's batches complete in the order they were submitted (submit never blocks, so
-// a slot taken again says nothing about the batch that had it before; the pipeline's latest batch is always held)
-hipEvent_t map_stream_event(kbo_map_stream_t *m, uint64_t ticket)
-{
-    KBO_REQUIRE(m && ticket >= 1 && ticket <= m->next, KBO_E_BAD_ARG, "no such batch");
-    for (uint64_t t = ticket; t <= m->next; t += m->pipes.size()) {
-        kbo_map_stream::Slot &sl = m->slots[(t - 1) % m->slots.size()];
-        if (sl.ticket == t) return sl.done;
-    }
-    return nullptr; // (not reached: the pipeline's latest batch holds its slot)
-}
-} // namespace
-
-int kbo_map_stream_wait(kbo_map_stream_t *m, uint64_t ticket)
-{
-    return guarded([&] {
-        hipEvent_t ev;
-        {
-            KBO_REQUIRE(m, KBO_E_BAD_ARG, "null stream");
-            std::lock_guard<std::mutex> g(m->mu);
-            ev = map_stream_event(m, ticket);
-        }
-        if (ev) HIP_OK(hipEventSynchronize(ev));
-    });
-}
-
-int kbo_map_stream_wait_on(kbo_map_stream_t *m, uint64_t ticket, void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(m, KBO_E_BAD_ARG, "null stream");
-        std::lock_guard<std::mutex> g(m->mu);
-        hipEvent_t ev = map_stream_event(m, ticket);
-        if (ev) HIP_OK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), ev, 0));
-    });
-}
-
-int kbo_map_stream_sync(kbo_map_stream_t *m)
-{
-    return guarded([&] {
-        KBO_REQUIRE(m, KBO_E_BAD_ARG, "null stream");
-        std::lock_guard<std::mutex> g(m->mu);
-        for (auto &p : m->pipes)
-            for (hipStream_t s : {p.ks, p.ts})
-                if (s) HIP_OK(hipStreamSynchronize(s));
-    });
-}
-
-void kbo_map_stream_free(kbo_map_stream_t *m)
-{
-    delete m; // (waits for what its streams still hold)
-}
-
-namespace {
-struct PackedScratch { size_t q, ms, chars, pscr, exc, bytes; };
-PackedScratch packed_scratch(size_t n_seqs, uint64_t total_bases)
-{
-    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-    PackedScratch L{};
-    const size_t padded = up(total_bases + 32);
-    L.q = 0;
-    L.ms = L.q + padded;
-    L.chars = L.ms + padded;
-    L.pscr = L.chars + padded;
-    L.exc = L.pscr + up(kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t));
-    L.bytes = L.exc + up(n_seqs + 16);
-    return L;
-}
-} // namespace
-
-size_t kbo_matches_packed_dev_scratch_bytes(size_t n_seqs, uint64_t total_bases) { return packed_scratch(n_seqs, total_bases).bytes; }
-
-int kbo_matches_packed_dev(kbo_index_t *idx, const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                           size_t max_seq_len, size_t uniform_len, const uint64_t *d_exc_pos, const uint8_t *d_exc_byte, size_t n_exc,
-                           double max_error_prob, uint32_t *d_words_out, void *d_scratch, void *d_work, size_t work_bytes, void *stream,
-                           void *tail_stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(idx && d_words && d_offsets && d_words_out && d_scratch && d_work, KBO_E_BAD_ARG, "null argument");
-        KBO_REQUIRE(n_exc == 0 || (d_exc_pos && d_exc_byte), KBO_E_BAD_ARG, "exception list missing");
-        KBO_REQUIRE(n_seqs > 0 && total_bases > 0, KBO_E_EMPTY_QUERY, "empty batch");
-        KBO_REQUIRE(n_seqs < (1ull << 28) && total_bases < 0xFFFFFF00ull && n_exc < 0xFFFFFFFFull, KBO_E_UNSUPPORTED,
-                    "one launch covers < 2^28 sequences and < 4 GiB of query: split the batch");
-        KBO_REQUIRE(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_work & 15) == 0 && ((uintptr_t)d_words & 3) == 0 && ((uintptr_t)d_words_out & 3) == 0,
-                    KBO_E_BAD_ARG, "d_scratch/d_work must be 16-byte, the words 4-byte aligned");
-        KBO_REQUIRE(max_seq_len > 0 && max_seq_len <= 160 && !idx->sharded(), KBO_E_UNSUPPORTED,
-                    "kbo_matches_packed_dev: reads of at most 160 bases over an unsharded index (else: kbo_matches_batch_packed)");
-        const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob);
-        KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
-        hipStream_t s = static_cast<hipStream_t>(stream), ts = static_cast<hipStream_t>(tail_stream);
-        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k);
-        KBO_REQUIRE(!w.chunked, KBO_E_UNSUPPORTED, "reads only");
-        KBO_REQUIRE(work_bytes >= w.bytes, KBO_E_BAD_ARG, "d_work is smaller than kbo_work_bytes() for this batch");
-        const PackedScratch L = packed_scratch(n_seqs, total_bases);
-        uint8_t *sc = static_cast<uint8_t *>(d_scratch);
-        uint8_t *q = sc + L.q, *ms = sc + L.ms, *chars = sc + L.chars, *exc = sc + L.exc;
-        uint32_t *pscr = uniform_len ? nullptr : reinterpret_cast<uint32_t *>(sc + L.pscr);
-        const uint32_t wps = uniform_len ? (uint32_t)((uniform_len + 15) / 16) : 0u;
-        DevCopy::PlanState *plan_state = nullptr;
-        const kbo::DevIndexView view = device_view(idx, current_device(), &plan_state, total_bases);
-        kbo::WalkItem *items = static_cast<kbo::WalkItem *>(d_work);
-        kbo::WalkArgs a{};
-        a.ix = view;
-        a.q = q;
-        a.q_bytes = total_bases;
-        a.items = items;
-        a.n_items = w.n_slots;
-        a.d_out = ms;
-        a.max_item_len = (uint32_t)max_seq_len;
-        attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, plan_state);
-        a.chars_out = chars;
-        a.map_thr = (uint32_t)threshold;
-        a.map_fmt = 0;
-        a.map_want_ms = 0;
-        KBO_REQUIRE(a.gitems && kbo::map_reads_packed_applies(a, true), KBO_E_UNSUPPORTED,
-                    "this copy of the index cannot take the packed-native kernel (no depth table, a held-off copy, a threshold below the "
-                    "table's order): kbo_matches_batch_packed takes any batch");
-        if (pscr) HIP_OK(kbo::launch_packed_prefix(d_offsets, (uint32_t)n_seqs, pscr, s));
-        a.seq_off = d_offsets; // (no item list: the kernels read the offsets)
-        a.qp = d_words;
-        a.qp_wps = wps;
-        a.qp_data = pscr;
-        a.qp_sums = pscr ? pscr + n_seqs + 1u : nullptr;
-        a.packed_out = d_words_out;
-        if (n_exc) {
-            HIP_OK(hipMemsetAsync(exc, 0, n_seqs, s));
-            HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, 0, d_offsets, (uint32_t)n_seqs, exc, s));
-            a.qp_exc = exc;
-        }
-        const bool timing = g_stage_timing.load() != 0;
-        StageEvents ev{};
-        if (timing) {
-            ev = timing_take();
-            HIP_OK(hipEventRecord(ev.e0, s));
-        }
-        HIP_OK(kbo::launch_map_reads(a, s));
-        if (timing) HIP_OK(hipEventRecord(ev.e1, s));
-        if (ts != s) {
-            hipEvent_t fence = tail_fence();
-            HIP_OK(hipEventRecord(fence, s));
-            HIP_OK(hipStreamWaitEvent(ts, fence, 0));
-            static const bool env_piece = std::getenv("KBO_REDO_PIECE") != nullptr;
-            if (!env_piece) a.redo_piece = 32u;
-        }
-        if (timing) HIP_OK(hipEventRecord(ev.e1t, ts));
-        HIP_OK(kbo::launch_unpack_flagged(d_words, d_offsets, (uint32_t)n_seqs, wps, pscr, a.redo, q, ts));
-        HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, 0, q, ts));
-        HIP_OK(kbo::launch_redo_pass(a, ts));
-        HIP_OK(kbo::launch_derand_flagged(ms, d_offsets, (uint32_t)n_seqs, idx->host.k, (uint32_t)threshold, nullptr, chars, a.redo, (uint32_t)max_seq_len, ts));
-        HIP_OK(kbo::launch_pack_flagged(chars, d_offsets, (uint32_t)n_seqs, wps, pscr, a.redo, d_words_out, ts));
-        if (timing) {
-            HIP_OK(hipEventRecord(ev.e2, ts));
-            std::lock_guard<std::mutex> g(g_timing_mu);
-            g_timing_used.push_back(ev);
-        }
-        plan_after_launch(a, ts, plan_state);
-    });
-}
-
-int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len,
-                        size_t max_gap_len, void *d_work, uint32_t *d_records, size_t capacity, void *stream)
-{
-    return guarded([&] {
-        KBO_REQUIRE(d_chars && d_offsets && d_work && (d_records || capacity == 0), KBO_E_BAD_ARG, "null argument");
-        KBO_REQUIRE(n_seqs > 0 && n_seqs < (1ull << 31), KBO_E_BAD_ARG, "1 .. 2^31-1 sequences");
-        KBO_REQUIRE(((uintptr_t)d_work & 3) == 0 && ((uintptr_t)d_records & 3) == 0, KBO_E_BAD_ARG, "4-byte alignment");
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const uint32_t gap = (uint32_t)std::min<size_t>(max_gap_len, 0xFFFFFFFFu);
-        uint32_t *scratch = static_cast<uint32_t *>(d_work);
-        uint32_t *total = scratch + kbo::chunk_items_scratch_words((uint32_t)n_seqs); // last word of the work buffer
-        const uint32_t longest = (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
-        HIP_OK(kbo::launch_rle_count(d_chars, d_offsets, (uint32_t)n_seqs, gap, scratch, total, s, longest));
-        if (capacity)
-            HIP_OK(kbo::launch_rle_emit(d_chars, d_offsets, (uint32_t)n_seqs, gap, scratch, d_records,
-                                        (uint32_t)std::min<size_t>(capacity, 0xFFFFFFFFu), s, longest));
-    });
 }
 
 int kbo_walk_geometry(int *blocks, int *threads)

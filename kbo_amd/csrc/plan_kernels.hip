@@ -1681,8 +1681,7 @@ hipError_t launch_plan_table(WalkArgs &a, hipStream_t stream)
     if (a.n_items == 0) return hipSuccess;
     a.table_mode = 1;
     a.unit_bail = a.n_items / 2u + 64u;
-    static const int env_piece = std::getenv("KBO_REDO_PIECE") ? std::atoi(std::getenv("KBO_REDO_PIECE")) : 0; // experiments
-    a.redo_piece = env_piece >= 4 ? (uint32_t)env_piece : kRedoPieceTable;
+    a.redo_piece = kRedoPieceTable;
     hipError_t e = launch_plan_kernel(a, stream);
     if (e != hipSuccess) return e;
     if (!a.table_fused) { // (reads: plan_kernel has done the look-ups itself)
