@@ -57,6 +57,11 @@ pub mod ffi {
         // batches: what kbo-cli's loop over the reads / contigs of a file calls once
         pub fn kbo_matches_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, chars_out: *mut u8) -> c_int;
         pub fn kbo_map_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, format: c_int, out: *mut u8) -> c_int;
+        // kbo::map with any MapOpts over a batch; status[s] = 0 or the code kbo_map gives sequence s alone
+        pub fn kbo_map_batch_opts(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboMapOpts,
+                                  out: *mut u8, status: *mut i32) -> c_int;
+        pub fn kbo_fill_gaps_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, threshold: usize,
+                                   max_err_prob: f64, out: *mut u8, status: *mut i32) -> c_int;
         pub fn kbo_find_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboFindOpts,
                               rles: *mut *mut KboRle, rle_offsets: *mut u64) -> c_int;
         pub fn kbo_call_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboCallOpts,

@@ -298,6 +298,16 @@ int kbo_matches_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *o
 /* map with fill_gaps=false, call_variants=false (lib.rs:735-738, 756-760) over a batch. */
 int kbo_map_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
                   double max_error_prob, int format, uint8_t *out);
+/* kbo::map (lib.rs:720-761) with any MapOpts over a batch: out[offsets[s] .. offsets[s+1]) is what kbo_map(idx, seq s, opts)
+ * writes.  status[s] (n_seqs entries) = 0, or the KBO_E_* code kbo_map returns for sequence s alone (its bytes of `out` are
+ * then unspecified).  Whole-call errors (null args, KBO_E_K_MISMATCH, KBO_E_THRESHOLD_LE_1, sharded index -> KBO_E_UNSUPPORTED
+ * as kbo_map) are returned as the call's code.  Gap filling runs on the device (a sequence the device cannot finish is redone
+ * on the host), the variants of the whole batch come from kbo_call_batch_flat's passes. */
+int kbo_map_batch_opts(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                       const kbo_map_opts *opts, uint8_t *out, int32_t *status);
+/* gap_filling::fill_gaps over a batch, as kbo_fill_gaps per sequence (same threshold argument); out holds u8 characters. */
+int kbo_fill_gaps_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                        size_t threshold, double max_err_prob, uint8_t *out, int32_t *status);
 /* find over a batch: RLEs of all sequences concatenated, rle_offsets[i]..[i+1] = sequence i
  * (rle_offsets has n_seqs+1 entries, caller-allocated; *rles library-allocated, kbo_free).  The
  * run lengths are computed on the device (the translated characters never leave it). */

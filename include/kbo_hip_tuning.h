@@ -177,6 +177,14 @@ int kbo_stage_timing_read(double *kernel_ms_sum, double *redo_ms_sum, int *n_cal
 int kbo_run_automaton_depths(const uint8_t *seq, size_t len, uint32_t k, int add_revcomp, const uint8_t *kmers,
                              size_t n_kmers, uint32_t *depths_out);
 
+/* test hook: what the calling thread's last kbo_fill_gaps_batch / kbo_map_batch_opts did with the gaps: out[0] gaps found,
+ * out[1] gaps finished on the device (gap_kernels.hip), out[2] sequences redone whole on the host (kbo::fill_gaps), out[3]
+ * left-extension steps taken on the device. */
+int kbo_fill_gaps_stats(uint64_t out[4]);
+/* ... and where its time went, in seconds: out[0] walk, [1] translate, [2] gap kernels, [3] host fallback, [4] variant
+ * calling, [5] add_variants + relative_to_ref (tools/bench_map_opts.py) */
+int kbo_map_batch_opts_phases(double out[6]);
+
 /* ------------------------------------------------------------------ experiments recorded in DESIGN.md section 6 */
 /* plain walk kernel: only the first lane_limit lanes of every wave take reads (64 = all; what a sub-wave tiling would
  * have to beat), and every workgroup reserves dummy_lds_bytes of LDS it never touches (what staging a wave's MS values

@@ -47,6 +47,41 @@ def map_batch(sbwt, concat, offsets, max_error_prob=1e-7, format=True):  # noqa:
     return out[:total]
 
 
+def map_batch_opts(sbwt, concat, offsets, map_opts=None):
+    """kbo::map with any MapOpts (None = MapOpts(), the reference's defaults) over the batch ->
+    (uint8 chars, int32 status per sequence: 0 or the code kbo_map returns for that sequence alone)"""
+    from . import MapOpts
+    o = map_opts if map_opts is not None else MapOpts()
+    co = _capi.MapOpts(o.max_error_prob, int(o.fill_gaps), int(o.call_variants), int(o.format),
+                       o.sbwt_build_opts._to_c())
+    concat, offsets, n = _prep(concat, offsets)
+    total = int(offsets[-1]) if n > 0 else 0
+    out = np.zeros(max(total, 1), dtype=np.uint8)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    check(lib().kbo_map_batch_opts(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, C.byref(co), out.ctypes.data,
+                                   status.ctypes.data))
+    return out[:total], status[:n]
+
+
+def fill_gaps_batch(sbwt, concat, offsets, threshold, max_err_prob):
+    """gap_filling::fill_gaps over the batch, as kbo_fill_gaps per sequence -> (uint8 chars, int32 status)"""
+    concat, offsets, n = _prep(concat, offsets)
+    total = int(offsets[-1]) if n > 0 else 0
+    out = np.zeros(max(total, 1), dtype=np.uint8)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    check(lib().kbo_fill_gaps_batch(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, threshold, max_err_prob,
+                                    out.ctypes.data, status.ctypes.data))
+    return out[:total], status[:n]
+
+
+def fill_gaps_stats():
+    """kbo_fill_gaps_stats: (gaps found, finished on the device, sequences redone on the host, device extension steps)
+    of the calling thread's last fill_gaps_batch / map_batch_opts"""
+    v = (C.c_uint64 * 4)()
+    check(lib().kbo_fill_gaps_stats(v))
+    return tuple(int(x) for x in v)
+
+
 def find_batch(sbwt, concat, offsets, find_opts=None):
     """kbo::find over the batch -> (list of RLE tuples, rle_offsets uint64[n+1])"""
     from . import FindOpts

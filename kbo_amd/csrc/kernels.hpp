@@ -324,6 +324,17 @@ hipError_t launch_call_sites(const uint8_t *d_ms, const uint32_t *d_lo, const ui
                              uint32_t n_seqs, uint64_t total, uint32_t k, uint32_t threshold, void *d_sites, uint32_t cap,
                              uint32_t *d_count, hipStream_t stream);
 
+// gap_filling::fill_gaps over a batch (gap_kernels.hip): the gap starts of a slab's translation as {sequence, start} records
+// (d_count may end above cap: launch again with room), then one wave per gap writing the fills into d_out (a copy of d_tr);
+// d_host_flag[s] = 1 for a sequence the host has to redo; d_stats = {gaps finished, left-extension steps}.
+// d_log_tab[c] = log_rm_max_cdf(c + 1, 4, 1) for c < kGapFillLds; log_thr = log1p(-max_err_prob).
+constexpr uint32_t kGapFillLds = 2048; // bytes of extended k-mer one wave keeps in LDS: longer extensions go to the host
+hipError_t launch_gap_starts(const uint8_t *d_tr, const uint64_t *d_off, uint32_t n_seqs, uint64_t total, uint32_t threshold,
+                             void *d_gaps, uint32_t cap, uint32_t *d_count, hipStream_t stream);
+hipError_t launch_gap_fill(const uint8_t *d_q, const uint8_t *d_tr, uint8_t *d_out, const uint32_t *d_lo, const uint32_t *d_hi,
+                           const uint64_t *d_off, const void *d_gaps, uint32_t n_gaps, uint32_t k, uint32_t threshold,
+                           const double *d_log_tab, double log_thr, uint8_t *d_host_flag, unsigned long long *d_stats,
+                           const DevIndexView &ix, hipStream_t stream);
 // behind the first pass of a batch's call: every site of the kCallSegs lists becomes {sequence, i, j, row} (void records stay
 // void) at index d_prefix[list] + slot of d_recs, and its window - the k MS bytes ending at j, the k characters of the row -
 // goes to d_win (call_kernels.hip call_finalize_kernel); record stride = call_gather_stride(k) bytes: MS bytes at 0,

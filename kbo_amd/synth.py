@@ -30,3 +30,44 @@ def reads(genome_arr, n_reads, read_len=150, sub_rate=0.01, seed=READS_SEED, fir
       out.ctypes.data)
     offsets = np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(read_len)
     return out, offsets
+
+
+def variant_contigs(genome_arr, n_seqs, min_len, max_len=None, sub_rate=0.01, indel_every=2000, max_indel=20,
+                    insert_frac=0.05, insert_len=300, n_rate=0.0, seed=READS_SEED):
+    """Stretches of `genome_arr` as another strain would have them, for kbo::map with gap filling and variants
+    (tools/bench_map_opts.py, tests/test_gpu_map_batch_opts.py): sub_rate substitutions, one 1..max_indel base insertion or
+    deletion every ~indel_every bases, a foreign insert of insert_len random bases in insert_frac of the sequences and
+    n_rate 'N's.  Lengths uniform in [min_len, max_len].  -> (concat uint8, offsets uint64 [n_seqs + 1])"""
+    rng = np.random.default_rng(seed)
+    g = np.ascontiguousarray(genome_arr, dtype=np.uint8)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    max_len = max_len or min_len
+    seqs = []
+    for _ in range(n_seqs):
+        L = int(rng.integers(min_len, max_len + 1))
+        a = int(rng.integers(0, max(1, len(g) - L)))
+        s = g[a:a + L].copy()
+        hit = rng.random(len(s)) < sub_rate
+        s[hit] = acgt[(np.searchsorted(acgt, s[hit]) + rng.integers(1, 4, int(hit.sum()))) % 4]
+        parts, prev = [], 0
+        for p in sorted(rng.integers(0, len(s), int(rng.poisson(len(s) / indel_every)))):
+            if p < prev:
+                continue
+            n = int(rng.integers(1, max_indel + 1))
+            parts.append(s[prev:p])
+            if rng.random() < 0.5:
+                parts.append(acgt[rng.integers(0, 4, n)])
+                prev = p
+            else:
+                prev = min(len(s), p + n)
+        parts.append(s[prev:])
+        s = np.concatenate(parts)
+        if rng.random() < insert_frac and len(s) > 2:
+            p = int(rng.integers(1, len(s)))
+            s = np.concatenate([s[:p], acgt[rng.integers(0, 4, insert_len)], s[p:]])
+        if n_rate > 0:
+            s[rng.random(len(s)) < n_rate] = ord("N")
+        seqs.append(s[:max(len(s), 1)])
+    offsets = np.zeros(n_seqs + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in seqs])
+    return np.concatenate(seqs).astype(np.uint8), offsets
