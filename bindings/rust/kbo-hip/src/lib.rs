@@ -40,6 +40,9 @@ pub mod ffi {
         // kbo::build (lib.rs:501-506) / an index the sbwt crate built, handed over by its parts
         pub fn kbo_index_build(seqs: *const *const u8, lens: *const usize, n_seqs: usize, opts: *const KboBuildOpts,
                                out: *mut *mut KboIndex) -> c_int;
+        // ... by a HIP device (-1 = current); the same index, with that device's copy made there
+        pub fn kbo_index_build_device(seqs: *const *const u8, lens: *const usize, n_seqs: usize, opts: *const KboBuildOpts,
+                                      device: c_int, out: *mut *mut KboIndex) -> c_int;
         pub fn kbo_index_from_parts(k: u32, n_sets: u64, n_kmers: u64, rows: *const *const u64, c: *const u64, lcs: *const u8,
                                     out: *mut *mut KboIndex) -> c_int;
         pub fn kbo_index_free(idx: *mut KboIndex);

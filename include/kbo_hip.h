@@ -111,6 +111,17 @@ typedef struct kbo_index kbo_index_t;
 int kbo_index_build(const uint8_t *const *seqs, const size_t *lens, size_t n_seqs,
                     const kbo_build_opts *opts, kbo_index_t **out);
 
+/* kbo::build on HIP device `device` (-1 = current): the same index as kbo_index_build(seqs, lens, n_seqs, opts) - equal
+ * k, n_kmers, n_sets, C, subset-matrix rows and LCS - built by the device, with that device's copy made from the rows
+ * the device built (no host -> device copy of rows or LCS); the host copy is filled too (export / save / host stages).
+ * The copy equals what kbo_index_to_device(idx, device) makes of a host-built handle.  The current device is unchanged
+ * on return; num_threads is accepted and ignored.  Errors: those of kbo_index_build (checked before any HIP call),
+ * KBO_E_UNSUPPORTED for an input kbo_index_build would build as shards (kbo_index_build builds those), KBO_E_NOMEM when
+ * the build's peak does not fit the device's free memory: (32 W + 8) bytes per base and strand (W = 1 / 2 / 4 / 8 key
+ * words for k <= 32 / 64 / 128 / 255; e.g. 72 bytes per base at k = 63 without add_revcomp) + 1 byte per base. */
+int kbo_index_build_device(const uint8_t *const *seqs, const size_t *lens, size_t n_seqs,
+                           const kbo_build_opts *opts, int device, kbo_index_t **out);
+
 /* Adopt an index built elsewhere (e.g. by the sbwt crate on the Rust side): the four
  * SubsetMatrix rows as little-endian 64-bit words (bit i of word i/64 = row i), the C
  * array and the LCS array as bytes.  Replaces handing &SbwtIndexVariant/&LcsArray to

@@ -184,6 +184,10 @@ int kbo_fill_gaps_stats(uint64_t out[4]);
 /* ... and where its time went, in seconds: out[0] walk, [1] translate, [2] gap kernels, [3] host fallback, [4] variant
  * calling, [5] add_variants + relative_to_ref (tools/bench_map_opts.py) */
 int kbo_map_batch_opts_phases(double out[6]);
+/* Test hook: where the calling thread's last kbo_index_build_device spent its time, in seconds (HIP events, [8] host clock):
+ * out[0] upload, [1] extraction, [2] sort, [3] dedup, [4] orphans + dummy rows, [5] merge, [6] edge bits + LCS, [7] download of
+ * the rows and LCS, [8] the device copy (layout and plan structures, as kbo_index_to_device) (tools/bench_build.py) */
+int kbo_index_build_device_phases(double out[9]);
 
 /* ------------------------------------------------------------------ experiments recorded in DESIGN.md section 6 */
 /* plain walk kernel: only the first lane_limit lanes of every wave take reads (64 = all; what a sub-wave tiling would

@@ -74,9 +74,9 @@ class MapOpts:
     sbwt_build_opts: BuildOpts = field(default_factory=lambda: BuildOpts(build_select=True))
 
 
-def build(seq_data, build_opts=None):
-    """kbo::build (lib.rs:501-506) -> (SbwtIndexVariant, LcsArray)"""
-    return index.build_sbwt_from_vecs(seq_data, build_opts if build_opts is not None else BuildOpts())
+def build(seq_data, build_opts=None, device=None):
+    """kbo::build (lib.rs:501-506) -> (SbwtIndexVariant, LcsArray); device: None = on the host, an int = by that HIP device"""
+    return index.build_sbwt_from_vecs(seq_data, build_opts if build_opts is not None else BuildOpts(), device=device)
 
 
 def matches(query_seq, sbwt, lcs=None, match_opts=None):

@@ -2,7 +2,8 @@
 //   device_index.cpp  the index handle and its per-device copies,
 //   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline, run-length sink,
 //   kbo_capi.cpp      the extern "C" entry points,
-//   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*).
+//   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
+//   build_device.cpp  kbo_index_build_device (the index built by the device).
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -161,10 +162,16 @@ inline std::vector<kbo_index *> shards_of(kbo_index *idx)
 }
 // throws KBO_E_UNSUPPORTED for a sharded handle: `what` needs the rows of ONE index
 void require_unsharded(const kbo_index *idx, const char *what);
+// the rows (4 bit-vectors of ceil(n_sets / 64) words, back to back) and LCS bytes of an index as they already lie on a device
+struct DeviceRowsLcs {
+    const uint64_t *rows;
+    const uint8_t *lcs;
+};
 // uploads the index on first use; *plan (optional) receives the copy's plan hold-off state.  work_bases: the bases of the batch
-// that asks (a copy makes its plan structures - cover, tables - once the bases it has seen pay for them); prepare: make them now
+// that asks (a copy makes its plan structures - cover, tables - once the bases it has seen pay for them); prepare: make them now.
+// built: the index's rows and LCS on `device` already (kbo_index_build_device): the copy is made from them, nothing is uploaded
 kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **plan = nullptr, uint64_t work_bases = 0,
-                              bool prepare = false);
+                              bool prepare = false, const DeviceRowsLcs *built = nullptr);
 int walk_max_waves();                                     // upper bound on resident walk waves: CUs x waves per CU
 // points a.gitems / a.glist into `plan_work` (>= kbo::plan_work_bytes(n_items) bytes, 16-byte aligned) when the index
 // view carries a path cover and the launch wants MS values only; otherwise leaves them null (plain walk)
@@ -172,6 +179,9 @@ void attach_plan(kbo::WalkArgs &a, void *plan_work, DevCopy::PlanState *ps);
 void plan_reset_holdoff(); // every copy plans its next launch again
 // after launch_ms_walk: lets the host learn whether the plan paid (and whether a walk was cut short by its guard)
 void plan_after_launch(const kbo::WalkArgs &a, hipStream_t stream, DevCopy::PlanState *ps);
+
+// ---- kbo_capi.cpp: shards kbo_index_build makes of `bases` bases (one per 3.76 * 10^9 rows, or kbo_set_index_shards); > 1 = sharded
+size_t shards_wanted(uint64_t bases, bool add_revcomp);
 
 // ---- A3 (kbo_capi.cpp): derandomize.rs:91-145
 double log_rm_max_cdf(size_t t, size_t alphabet_size, size_t n_kmers);

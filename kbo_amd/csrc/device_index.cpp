@@ -340,7 +340,22 @@ uint64_t plan_break_even_bases(const kbo_index *idx)
 }
 } // namespace
 
-kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **plan, uint64_t work_bases, bool prepare)
+namespace {
+// a device copy's rank blocks, contraction entries and two-base blocks (d_pair: nullptr = none) from the index's rows and LCS bytes
+// as they lie on the current device: uploaded from the host copy (device_view) or made there by the build (kbo_index_build_device)
+void layout_from_device_rows(const kbo_index *idx, const uint64_t *d_rows, const uint8_t *d_lcs, size_t n_words, uint64_t n_blocks,
+                             uint4 *d_rank, uint8_t *d_ent, uint4 *d_pair)
+{
+    const uint64_t n_rows = idx->host.n_sets;
+    DevBuf d_scr(kbo::device_layout_scratch_bytes(n_rows));
+    const uint64_t *rows_dev[4];
+    for (int c = 0; c < 4; c++) rows_dev[c] = d_rows + (size_t)c * n_words;
+    HIP_OK(kbo::build_device_layout(rows_dev, n_words, d_lcs, n_rows, idx->host.C, (uint32_t)n_blocks, d_rank, reinterpret_cast<uint32_t *>(d_ent),
+                                    d_pair, d_scr.p, nullptr));
+}
+} // namespace
+
+kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **plan, uint64_t work_bases, bool prepare, const DeviceRowsLcs *built)
 {
     require_unsharded(idx, "this operation");
     std::lock_guard<std::mutex> g(idx->mu);
@@ -395,17 +410,17 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
             uint8_t *d_ent = dc->big ? dc->ent.as<uint8_t>() : dc->arena.as<uint8_t>() + rank_bytes;
             if (on_device) {
                 const size_t n_words = (size_t)((n_rows + 63) / 64);
-                DevBuf d_rows(4 * n_words * 8 + 64), d_lcs((size_t)n_rows + 64), d_scr(kbo::device_layout_scratch_bytes(n_rows));
-                const uint64_t *rows_dev[4];
-                for (int c = 0; c < 4; c++) {
-                    HIP_OK(hipMemcpy(d_rows.as<uint8_t>() + (size_t)c * n_words * 8, idx->host.rows[c].data(), n_words * 8, hipMemcpyHostToDevice));
-                    rows_dev[c] = reinterpret_cast<const uint64_t *>(d_rows.as<uint8_t>() + (size_t)c * n_words * 8);
-                }
-                if (n_rows) HIP_OK(hipMemcpy(d_lcs.p, idx->host.lcs.data(), (size_t)n_rows, hipMemcpyHostToDevice));
                 if (dc->big) HIP_OK(hipMemset(dc->ent.p, 0, ent_bytes + 16));
-                HIP_OK(kbo::build_device_layout(rows_dev, n_words, d_lcs.as<uint8_t>(), n_rows, idx->host.C, (uint32_t)lay_n_blocks,
-                                                dc->arena.as<uint4>(), reinterpret_cast<uint32_t *>(d_ent),
-                                                pair_bytes ? reinterpret_cast<uint4 *>(dc->arena.as<uint8_t>() + base_bytes) : nullptr, d_scr.p, nullptr));
+                uint4 *d_pair = pair_bytes ? reinterpret_cast<uint4 *>(dc->arena.as<uint8_t>() + base_bytes) : nullptr;
+                if (built) {
+                    layout_from_device_rows(idx, built->rows, built->lcs, n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
+                } else {
+                    DevBuf d_rows(4 * n_words * 8 + 64), d_lcs((size_t)n_rows + 64);
+                    for (int c = 0; c < 4; c++)
+                        HIP_OK(hipMemcpy(d_rows.as<uint8_t>() + (size_t)c * n_words * 8, idx->host.rows[c].data(), n_words * 8, hipMemcpyHostToDevice));
+                    if (n_rows) HIP_OK(hipMemcpy(d_lcs.p, idx->host.lcs.data(), (size_t)n_rows, hipMemcpyHostToDevice));
+                    layout_from_device_rows(idx, d_rows.as<uint64_t>(), d_lcs.as<uint8_t>(), n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
+                }
             } else {
                 for (int c = 0; c < 4; c++)
                     HIP_OK(hipMemcpy(dc->arena.as<uint8_t>() + per * c, lay.rank[c].data(), per, hipMemcpyHostToDevice));

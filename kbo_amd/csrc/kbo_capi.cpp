@@ -33,6 +33,16 @@ using namespace kbo_host;
 
 namespace kbo_host {
 
+// rows the index would have, at most: one per base and strand (+ dummies).  Beyond 32-bit row numbers (a human genome with its reverse
+// complements) - or when a test asks for it - kbo_index_build builds the index as shards (capi_internal.hpp)
+size_t shards_wanted(uint64_t bases, bool add_revcomp)
+{
+    const uint64_t est_rows = bases * (add_revcomp ? 2u : 1u);
+    const uint64_t kShardRows = 0xE0000000ull; // (3.76 * 10^9: leaves room for the dummy rows)
+    const int forced = g_index_shards.load();
+    return forced > 0 ? (size_t)forced : (size_t)((est_rows + kShardRows - 1) / kShardRows);
+}
+
 // ---- A3: derandomize.rs:91-145, f64, identical operation order -------------------------
 double powi_f64(double a, int b) // Rust f64::powi == llvm.powi == compiler-rt __powidf2
 {
@@ -341,10 +351,7 @@ int kbo_index_build(const uint8_t *const *seqs, const size_t *lens, size_t n_seq
         // with its reverse complements) - or when a test asks for it - the index is built as shards (capi_internal.hpp)
         uint64_t bases = 0;
         for (size_t s = 0; s < n_seqs; s++) bases += lens[s];
-        const uint64_t est_rows = bases * (p.add_revcomp ? 2u : 1u);
-        const uint64_t kShardRows = 0xE0000000ull; // (3.76 * 10^9: leaves room for the dummy rows)
-        const int forced = g_index_shards.load();
-        const size_t want = forced > 0 ? (size_t)forced : (size_t)((est_rows + kShardRows - 1) / kShardRows);
+        const size_t want = shards_wanted(bases, p.add_revcomp);
         std::unique_ptr<kbo_index> idx(new kbo_index());
         if (want <= 1) kbo::build_host_index(seqs, lens, n_seqs, p, idx->host);
         else build_sharded(seqs, lens, n_seqs, p, want, *idx);

@@ -358,6 +358,39 @@ size_t device_layout_scratch_bytes(uint64_t n_sets);
 hipError_t build_device_layout(const uint64_t *const d_rows[4], uint64_t n_words, const uint8_t *d_lcs, uint64_t n, const uint64_t C[4],
                                uint32_t n_blocks, uint4 *d_rank, uint32_t *d_ent, uint4 *d_pair, void *d_scratch, hipStream_t stream);
 
+// ---- kbo::build on the device (build_kernels.hip, driven by build_device.cpp).  Keys are colex keys of W 64-bit words (sbwt_build.cpp
+// Key<W>) stored as W word arrays: word j of key i at keys[j * stride + i].  Real counts ("real": non-$ characters of a row) are bytes.
+constexpr uint32_t kBuildTile = 4096; // keys per tile of the radix sort and of the compaction
+struct RadixPass {
+    uint32_t a, nb; // the digit: key bits [a, a + nb) counted from the most significant bit of word 0 (nb <= 8)
+    uint32_t real;  // 1: the digit is the real byte instead
+};
+size_t build_tiles(uint64_t n);
+// every k-mer (and / or its reverse complement) ending an ACGT run of >= k bases of d_seq, appended at *d_count (any order)
+hipError_t launch_build_extract(uint32_t W, const uint8_t *d_seq, uint64_t n_bytes, uint32_t k, bool fw, bool rc, uint64_t *d_keys,
+                                uint64_t stride, unsigned long long *d_count, hipStream_t s);
+// one stable LSD pass d_in -> d_out (n_words word arrays + the real bytes when d_rin); d_hist: 256 * build_tiles(n) words, d_sums:
+// 256 * build_tiles(n) / kScanBlock + 2 words
+hipError_t launch_build_radix_pass(const uint64_t *d_in, uint64_t *d_out, uint32_t n_words, uint64_t stride, const uint8_t *d_rin, uint8_t *d_rout,
+                                   uint64_t n, const RadixPass &ps, uint32_t *d_hist, uint32_t *d_sums, hipStream_t s);
+// flags[i] = key i (with its real byte when d_real) != key i - 1; flags[x] = sorted k-mer x has no predecessor
+hipError_t launch_build_flag_distinct(uint32_t W, const uint64_t *d_keys, uint64_t stride, const uint8_t *d_real, uint64_t n, uint8_t *d_flags, hipStream_t s);
+hipError_t launch_build_flag_orphan(uint32_t W, const uint64_t *d_keys, uint64_t stride, uint64_t n, uint32_t k, uint8_t *d_flags, hipStream_t s);
+// the flagged keys, in order; *d_total += their number.  d_counts: build_tiles(n) words, d_sums: build_tiles(n) / kScanBlock + 2 words
+hipError_t launch_build_compact(const uint64_t *d_in, uint64_t in_stride, uint64_t *d_out, uint64_t out_stride, uint32_t n_words, const uint8_t *d_rin,
+                                uint8_t *d_rout, const uint8_t *d_flags, uint64_t n, uint32_t *d_counts, uint32_t *d_sums,
+                                unsigned long long *d_total, hipStream_t s);
+// the root and the k - 1 $-padded prefixes of every orphan: 1 + n_orph (k - 1) keys with their real bytes
+hipError_t launch_build_dummies(uint32_t W, const uint64_t *d_orph, uint64_t o_stride, uint64_t n_orph, uint32_t k, uint64_t *d_keys, uint64_t stride,
+                                uint8_t *d_real, hipStream_t s);
+// sorted distinct k-mers + sorted distinct dummy rows -> rows in colex order (d_lb: n_d words)
+hipError_t launch_build_merge(uint32_t W, const uint64_t *d_km, uint64_t km_stride, uint64_t n_km, uint32_t k, const uint64_t *d_dk, uint64_t d_stride,
+                              const uint8_t *d_dreal, uint64_t n_d, uint32_t *d_lb, uint64_t *d_rk, uint64_t r_stride, uint8_t *d_rreal, hipStream_t s);
+// edge bits into d_rows (4 zeroed bit-vectors of n_words words), LCS bytes; d_ctr (9 zeroed words): [0] rows without an incoming edge,
+// [1 + c] rows >= 1 ending with c, [5 + c] edge bits of B_c
+hipError_t launch_build_edges_lcs(uint32_t W, const uint64_t *d_rk, uint64_t stride, const uint8_t *d_rreal, uint64_t n, uint32_t k, uint64_t *d_rows,
+                                  uint64_t n_words, uint8_t *d_lcs, unsigned long long *d_ctr, hipStream_t s);
+
 // ---- the path cover laid out on the device (cover_kernels.hip; what it is: path_cover.cpp).  *ok = false: rows on cycles - the host's decides
 hipError_t build_path_cover_device(const uint4 *d_rank, const uint32_t *d_ent, uint64_t n, uint32_t n_blocks, uint32_t k, const uint64_t C[4],
                                    uint8_t *d_text, uint32_t *d_pos, uint32_t *d_node, hipStream_t stream, bool *ok);

@@ -160,8 +160,9 @@ class LcsArray:
         self.sbwt = sbwt
 
 
-def build_sbwt_from_vecs(slices, build_options=None):
-    """index::build_sbwt_from_vecs (index.rs:56-99) -> (SbwtIndexVariant, LcsArray)."""
+def build_sbwt_from_vecs(slices, build_options=None, device=None):
+    """index::build_sbwt_from_vecs (index.rs:56-99) -> (SbwtIndexVariant, LcsArray).  device=None: built on the host
+    (kbo_index_build); an int: built by that HIP device (-1 = the current one), which keeps its copy (kbo_index_build_device)."""
     from . import BuildOpts
     o = build_options if build_options is not None else BuildOpts()
     seqs = [bytes(_u8(s)) for s in slices]
@@ -171,7 +172,10 @@ def build_sbwt_from_vecs(slices, build_options=None):
     lens = (C.c_size_t * len(seqs))(*[len(s) for s in seqs])
     co = o._to_c()
     h = C.c_void_p()
-    check(lib().kbo_index_build(arr, lens, len(seqs), C.byref(co), C.byref(h)))
+    if device is None:
+        check(lib().kbo_index_build(arr, lens, len(seqs), C.byref(co), C.byref(h)))
+    else:
+        check(lib().kbo_index_build_device(arr, lens, len(seqs), C.byref(co), int(device), C.byref(h)))
     sbwt = SbwtIndexVariant(h)
     return sbwt, LcsArray(sbwt)
 
