@@ -9,7 +9,7 @@ Batches are in flight on TWO PIPELINES of two streams each: a batch's kernel on 
 the second one (kbo_map_batch_dev_tail) beside the pipeline's next kernel; consecutive steps go to the pipelines in turn and take
 four resident batches of the same shape in turn (different reads, own buffers), so two kernels and two second passes share
 the device at any time; every step's work - both passes - ends inside the timed region.  --one-at-a-time: a single stream
-(also reported in the line: `one_batch_at_a_time`).  Default workload = BASELINE config C2: 5 Mbp iid genome, k=31 SBWT, 1 M x 150 bp forward reads with
+(with --full also reported in the line: `one_batch_at_a_time`).  Default workload = BASELINE config C2: 5 Mbp iid genome, k=31 SBWT, 1 M x 150 bp forward reads with
 1 % substitutions per GPU (weak scaling: every rank holds the replicated index and its own reads; no collective on the data
 path).  Prints ONE JSON line on rank 0.
 
@@ -20,8 +20,14 @@ path).  Prints ONE JSON line on rank 0.
                                                        100 M reads in all, sharded over the ranks (strong scaling)
   --dump-outputs DIR                                   after the timed steps: what the last one computed, as DIR/<name>.npy
                                                        (float32 / float64, at most 64 MB: a fixed sample of larger outputs)
-The oracle (oracle/) is used after the timed region only: parity gate, CPU baseline, and the CPU model of the plan-guided
-stage whose work counts price the roofline.
+  --full                                               after the timed steps, everything beyond the headline (below)
+A run builds its index: it reads no index file an earlier run left unless --index-cache names one.  Without --full it sets up,
+warms up, times its steps, writes --dump-outputs and prints the line: value, ms_per_step, the kernels' durations from the timed
+steps; roofline, cpu_baseline, bit_exact_vs_oracle, one_batch_at_a_time and the variants are null.  With --full, on rank 0 behind
+the timed region: the same steps on one stream, one more launch with the kernels' counters on (the roofline), the oracle (oracle/:
+parity gate on every read of the first slab of every resident batch, CPU baseline, and the CPU model of the plan-guided stage
+whose work counts price the roofline), the sensitivity variants, the entry points that return MS values, the one-shot map and
+the host-to-host rate.  --call / --config C5 run their own legs either way (--no-cpu-baseline, --no-whole-call).
 """
 import argparse
 import json
@@ -102,7 +108,7 @@ def main(argv=None):
     t_index = time.perf_counter()
     if world > 1:
         if rank == 0:
-            genome, sbwt = build_or_load_index(args, usable_cores()[0])
+            genome, sbwt = build_or_load_index(args, usable_cores()[0], share=True)
         dist.barrier()
         if rank != 0:
             genome, sbwt = build_or_load_index(args, threads, may_build=not os.path.exists(cache_path(args)))
@@ -240,8 +246,8 @@ def main(argv=None):
         float(np.mean([sum(e[0].elapsed_time(e[1]) for e in step) for step in ev]))
     dt_ms = float(np.mean([sum(e[1].elapsed_time(e[2]) for e in step) for step in ev])) if args.two_kernels else 0.0
     rle_ms = float(np.mean([sum(e[2].elapsed_time(e[3]) for e in step) for step in ev])) if args.find and args.two_kernels else None  # (else: inside the call)
-    # what the timed steps left behind (formatted unless --find): the first slab of either set, for rank 0's parity gate
-    timed_chars_sets = [sl[0].chars[:sl[0].total].cpu().numpy() for sl in sets] if rank == 0 else None
+    # what the timed steps left behind (formatted unless --find): the first slab of either set, for rank 0's parity gate (--full)
+    timed_chars_sets = [sl[0].chars[:sl[0].total].cpu().numpy() for sl in sets] if rank == 0 and args.full else None
     dumped = None
     if args.dump_outputs and rank == 0:  # what the last timed step computed: its batch's slabs, before any leg below runs them again
         last_set = (conditioned + args.warmup + args.steps - 1) % n_sets
@@ -251,7 +257,7 @@ def main(argv=None):
         mstream.close()
         mstream = None
     serial = None
-    if piped and rank == 0 and world == 1:  # the same steps on one stream, for the record
+    if args.full and piped and rank == 0 and world == 1:  # the same steps on one stream, for the record
         n_ser = max(1, min(args.steps, 10))
         condition(lambda n: [one_step(j, None, on_tail=False) for j in range(n)], 2, torch, device)  # (the parity copies above were host work)
         sync_all()
@@ -286,189 +292,191 @@ def main(argv=None):
     result = None
     if rank == 0:
         dev = slabs[0]
-        # the stage's own work counters: one more launch over the first slab with the counting instantiations of the
-        # kernels (instrumentation, off inside the timed region: about 1 % of the stage's time)
-        timed_chars = timed_chars_sets[0]
-        L.kbo_set_plan_stats(1)
-        if one_kernel:
-            dev.run(stream)
-            torch.cuda.synchronize(device)
-            map_stats = dev.plan_stats(stream)
-        dev.walk(stream)
-        torch.cuda.synchronize(device)
-        stats = dev.plan_stats(stream)
-        L.kbo_set_plan_stats(0)
-        gpu_d = dev.ms.cpu().numpy()
-        cpu = b_ref = exact = ops = b_plan = model = None
-        sens = h2h = ms_var = one_shot = None
-        if world == 1 and not args.no_cpu_baseline and not args.no_extras and (args.extras or not args.custom):
-            # (first of the legs behind the timed region: its pinned staging buffers are made by its first call, and behind the
-            # oracle's and the variants' gigabytes of host allocations they come out of scattered pages - 21 instead of 40 Gbp/s)
-            h2h = host_to_host_leg(args, sbwt, genome)
         planned = (not args.no_plan) and sbwt.device_plan_bytes() > 0
-        if not args.no_cpu_baseline:
-            from oracle import binding as ora
-            rows, Carr, lcs = sbwt.export_parts()
-            # (the oracle adopts the product-built index: its own row-sorting builder needs minutes and > 30 B/base beyond
-            # ~20 Mbp; builder equality is tests/test_builder_vs_oracle.py)
-            oi = ora.Index.from_parts(args.k, sbwt.n_sets(), sbwt.n_kmers(), rows, Carr, lcs)
-            # parity gate (rank 0's first slab) + CPU baseline on the unformatted characters, at every world size
-            fmt = dev.format
-            dev.format = False
-            dev.derand_translate(stream)
+        table = planned and sbwt.depth_table_order() > 0
+        cpu = b_ref = exact = ops = b_plan = model = roofline = None
+        sens = h2h = ms_var = one_shot = None
+        if args.full:
+            # the stage's own work counters: one more launch over the first slab with the counting instantiations of the
+            # kernels (instrumentation, off inside the timed region: about 1 % of the stage's time)
+            timed_chars = timed_chars_sets[0]
+            L.kbo_set_plan_stats(1)
+            if one_kernel:
+                dev.run(stream)
+                torch.cuda.synchronize(device)
+                map_stats = dev.plan_stats(stream)
+            dev.walk(stream)
             torch.cuda.synchronize(device)
-            cpu, b_ref, exact, ops = cpu_baseline_leg(args, oi, concat0, offsets0, gpu_d, dev.chars.cpu().numpy())
-            dev.format = fmt
-            # EVERY read of the slab: the characters the timed steps wrote (kbo::map's output) and the MS values, against the oracle
-            exp_chars, exp_d = oi.matches_batch(concat0, offsets0, 1e-7, n_threads=usable_cores()[0], want_d=True)
-            exp_out = np.frombuffer(ora.relative_to_ref(concat0, exp_chars), dtype=np.uint8) if fmt else exp_chars
-            exact = bool(exact and np.array_equal(timed_chars, exp_out) and np.array_equal(gpu_d[:dev.total], exp_d))
-            for b in range(1, n_sets):  # ... and of the other batch in flight
-                cb, ob = first_slab[b]
-                exp_chars = oi.matches_batch(cb, ob, 1e-7, n_threads=usable_cores()[0])
-                exp_out = np.frombuffer(ora.relative_to_ref(cb, exp_chars), dtype=np.uint8) if fmt else exp_chars
-                exact = bool(exact and np.array_equal(timed_chars_sets[b], exp_out))
-            del exp_chars, exp_d, exp_out
-            if planned and not stats["gave_up"] and not one_kernel:
-                b_plan, model, _ = stage_model_leg(args, sbwt, oi, concat0, offsets0, gpu_d)
-                exact = bool(exact and model["ms_equal_to_gpu"])
-            if world == 1 and not args.no_extras and (args.extras or not args.custom):
-                sens = sensitivity_leg(args, genome, sbwt, oi, torch, device, stream, n_pipes if piped else None)
-                ms_var = ms_leg(args, sbwt, oi, concat0, offsets0, torch, device, stream, n_pipes if piped else None)
-                one_shot = one_shot_map_leg(args, genome, oi) if args.genome <= 20_000_000 else None
-        # fabric-side traffic and L2 misses of the A1 stage, from the committed rocprofv3 passes of this exact
-        # workload and walk mode (PMC passes cannot run inside the timed region: separate runs, tools/profile_bench.sh)
-        wl_key = f"{args.genome}x{n_mine}x{args.read_len}x{args.sub_rate:g}:{('map' if one_kernel else 'table' if sbwt.depth_table_order() > 0 else 'plan') if planned else 'plain'}"
-        sha = build_sha16()
-        traffic = tsrc = misses = walk_misses = plan_misses = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath):
-            try:
-                entry = json.load(open(tpath)).get("workloads", {}).get(wl_key)
-                if entry and one_kernel and entry.get("build_sha16") != sha:
-                    tsrc = "none: %s was taken of another build (%s, this one is %s) - tools/profile_bench.sh renews it" % (
-                        entry.get("source"), entry.get("build_sha16"), sha)
-                    entry = None
-                if entry:
-                    traffic, misses, tsrc = entry.get("a1_bytes_per_launch"), entry.get("a1_tcc_miss_per_launch"), entry.get("source")
-                    kern = entry.get("kernels", {})
-                    walk_misses = (kern.get("ms_walk_guided_kernel") or kern.get("ms_walk_recovery_kernel") or {}).get("tcc_miss")
-                    plan_misses = (kern.get("plan_kernel") or {}).get("tcc_miss")
-            except Exception:
-                pass
+            stats = dev.plan_stats(stream)
+            L.kbo_set_plan_stats(0)
+            gpu_d = dev.ms.cpu().numpy()
+            if world == 1 and not args.no_cpu_baseline and not args.no_extras and (args.extras or not args.custom):
+                # (first of the legs behind the timed region: its pinned staging buffers are made by its first call, and behind the
+                # oracle's and the variants' gigabytes of host allocations they come out of scattered pages - 21 instead of 40 Gbp/s)
+                h2h = host_to_host_leg(args, sbwt, genome)
+            if not args.no_cpu_baseline:
+                from oracle import binding as ora
+                rows, Carr, lcs = sbwt.export_parts()
+                # (the oracle adopts the product-built index: its own row-sorting builder needs minutes and > 30 B/base beyond
+                # ~20 Mbp; builder equality is tests/test_builder_vs_oracle.py)
+                oi = ora.Index.from_parts(args.k, sbwt.n_sets(), sbwt.n_kmers(), rows, Carr, lcs)
+                # parity gate (rank 0's first slab) + CPU baseline on the unformatted characters, at every world size
+                fmt = dev.format
+                dev.format = False
+                dev.derand_translate(stream)
+                torch.cuda.synchronize(device)
+                cpu, b_ref, exact, ops = cpu_baseline_leg(args, oi, concat0, offsets0, gpu_d, dev.chars.cpu().numpy())
+                dev.format = fmt
+                # EVERY read of the slab: the characters the timed steps wrote (kbo::map's output) and the MS values, against the oracle
+                exp_chars, exp_d = oi.matches_batch(concat0, offsets0, 1e-7, n_threads=usable_cores()[0], want_d=True)
+                exp_out = np.frombuffer(ora.relative_to_ref(concat0, exp_chars), dtype=np.uint8) if fmt else exp_chars
+                exact = bool(exact and np.array_equal(timed_chars, exp_out) and np.array_equal(gpu_d[:dev.total], exp_d))
+                for b in range(1, n_sets):  # ... and of the other batch in flight
+                    cb, ob = first_slab[b]
+                    exp_chars = oi.matches_batch(cb, ob, 1e-7, n_threads=usable_cores()[0])
+                    exp_out = np.frombuffer(ora.relative_to_ref(cb, exp_chars), dtype=np.uint8) if fmt else exp_chars
+                    exact = bool(exact and np.array_equal(timed_chars_sets[b], exp_out))
+                del exp_chars, exp_d, exp_out
+                if planned and not stats["gave_up"] and not one_kernel:
+                    b_plan, model, _ = stage_model_leg(args, sbwt, oi, concat0, offsets0, gpu_d)
+                    exact = bool(exact and model["ms_equal_to_gpu"])
+                if world == 1 and not args.no_extras and (args.extras or not args.custom):
+                    sens = sensitivity_leg(args, genome, sbwt, oi, torch, device, stream, n_pipes if piped else None)
+                    ms_var = ms_leg(args, sbwt, oi, concat0, offsets0, torch, device, stream, n_pipes if piped else None)
+                    one_shot = one_shot_map_leg(args, genome, oi) if args.genome <= 20_000_000 else None
         lay = sbwt.device_layout()
-        rank_b, lcs_b = sbwt.device_bytes()
-        dto = sbwt.depth_table_order()
-        dtab_b = 0 if dto == 0 else (4 ** (dto + 1) if dto >= 4 else 4 ** dto)  # (grouped from 4 bases on: DESIGN.md section 4.2)
-        seed_d = int(lay["seed_depth"]) if planned else 0  # (from the library: kbo_index_device_layout - what the copy really holds)
-        seed_b = 8 * 4 ** seed_d if seed_d else 0
-        pair_b, plan_b = sbwt.device_pair_bytes(), sbwt.device_plan_bytes()
         std = (args.genome, args.reads, args.read_len, args.sub_rate, args.k) in tuple((g, r, 150, 0.01, 31) for g, r, _, _ in PRESETS.values())
         label = (args.config if std else "custom") + ": " + \
             ("kbo find (max_gap_len=0; run lengths on the device)" if args.find else
              "kbo map (fill_gaps=false, call_variants=false, format=true)")
-        table = planned and sbwt.depth_table_order() > 0
-        a1_kernels = ("plan_kernel (with the depth-table look-ups; dtab_resolve_kernel for items that cannot be staged) + redo_collect + ms_walk_kernel (reads the table could not resolve)" if table
-                      else "plan_kernel + plan_count/scan/emit + ms_walk_guided_kernel (ms_walk_recovery_kernel from 24 Mi rows on) + redo_collect + ms_walk_kernel (flagged reads)"
-                      if planned else "ms_walk_kernel")
-        walk_s = walk_ms * 1e-3
-        # what the stage is priced by: its OWN compulsory bytes (B_plan, counted by the model on the timed reads) when it
-        # planned, the reference algorithm's bytes when it walked plainly
-        b_alg = b_plan if b_plan is not None else b_ref
-        achieved = b_alg * bases / walk_s / 1e9 if b_alg is not None else None
-        ref_achieved = b_ref * bases / walk_s / 1e9 if b_ref is not None else None
-        roofline = {
-            "bound": "hbm",
-            "bound_detail": ("independent random byte gathers from the depth table (one fill each) + plan_kernel's streams and compare loop "
-                             "(DESIGN.md section 4.2)" if table else
-                             "L2-miss line fills by their rate and latency: integer gather work, 16 bytes used per 128-byte fill; the guided walk "
-                             "keeps 8-12 waves per CU so that the lines of the lanes in flight stay in L2 (DESIGN.md sections 4.2, 6)"),
-            "achieved": round(achieved, 1) if achieved is not None else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBPS, 4) if achieved is not None else None,
-            "frac_meaning": ("compulsory bytes of the plan-guided stage (B_plan: streams, records, " +
-                             ("one table byte per look-up and the query window of every mismatch" if table else "two 16-byte loads per walk iteration") +
-                             "; counted on the timed reads by oracle/plan_model.c, whose counts equal the kernels' own counters) / A1 stage time / 8 TB/s"
-                             if b_plan is not None else "reference-algorithm bytes (SURVEY.md 8(d)) / A1 stage time / 8 TB/s"),
-            "algorithmic_bytes_per_base": round(b_alg, 3) if b_alg is not None else None,
-            "units_per_launch": bases, "kernel": "A1 stage = " + a1_kernels, "kernel_ms": round(walk_ms, 4),
-            "kernel_ms_per_rank": {"min": round(min(walk_all), 4), "max": round(max(walk_all), 4)},
-            "traffic": int(traffic) if traffic else None, "traffic_source": tsrc,
-            "traffic_frac": round(traffic / walk_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
-            "wasted_traffic": round(traffic / (b_alg * bases), 3) if traffic and b_alg else None,
-            "l2_miss_per_launch": int(misses) if misses else None,
-            "fill_rate_frac": round(misses / walk_s / FILL_CEILING_PER_S, 4) if misses else None,
-            "fill_rate_ceiling": {"fills_per_s": FILL_CEILING_PER_S, "source": FILL_CEILING_SOURCE},
-            "fills_min_per_unit": model["per_unit"]["distinct_lines_beyond_l2"] if model and "per_unit" in model else None,
-            "fills_min_per_read": model.get("fills_min_per_read") if model else None,
-            "l2_miss_per_read": round(misses / (bases / args.read_len), 2) if misses else None,
-            # measured L2 misses per unit: of the whole stage, and of the walk kernel alone (to set against fills_min_per_unit:
-            # the difference is the rank-block look-ups that miss although the blocks would fit the L2)
-            "l2_miss_per_unit": round(misses / max(1, stats["units"] * bases / dev.total), 2) if misses and planned and not table else None,
-            "walk_kernel_l2_miss_per_unit": round(walk_misses / max(1, stats["units"] * bases / dev.total), 2) if walk_misses and planned and not table else None,
-            "plan_kernel_l2_miss_per_read": round(plan_misses / (bases / args.read_len), 2) if plan_misses and table else None,
-            "frac_reference_algorithm": round(ref_achieved / HBM_PEAK_GBPS, 4) if ref_achieved is not None else None,
-            "reference_algorithm_bytes_per_base": round(b_ref, 2) if b_ref is not None else None,
-            "cross_check_whole_step_gbps": round(b_alg * bases / (elapsed / args.steps) / 1e9, 1) if b_alg is not None else None,
-            "stage_model": model,
-            "stage_counters_gpu_first_slab": stats if planned else None,
-        }
-        if one_kernel:
-            # the dominant kernel priced by its OWN compulsory bytes, counted by the kernel itself on the first slab (kbo_set_plan_stats:
-            # one extra launch behind the timed region): what it must read and write however well it is written
-            c = map_stats
-            seeded = dev.n_seqs - c["items_noplan"]
-            by = {"query_bytes_in": dev.total, "characters_out": dev.total, "offsets_and_flags": 9 * dev.n_seqs,
-                  "seed_positions": 4 * c["seed_lookups"], "text_2bit_and_marks": 96 * seeded, "depth_table_bytes": c["tab_lookups"],
-                  "filter_words": 4 * c["seed_extensions"]}  # (seed_extensions: this kernel counts its filter look-ups there)
-            b_map = sum(by.values()) / dev.total
-            # the kernel's duration, launch by launch (HIP events around it).  With two pipelines two launches share the device
-            # for the whole of their durations: the device's time per launch is then the timed region / launches, not a launch's
-            # own duration - the bytes are priced by that (never less than duration / pipelines), the duration is printed beside it
-            k_launch_s = map_kernel_ms * 1e-3
-            shared = piped and n_pipes > 1
-            k_s = max(elapsed / args.steps, k_launch_s / n_pipes) if shared else k_launch_s
-            achieved = b_map * bases / k_s / 1e9
-            lines_min = (2 * dev.total / 128 + c["seed_lookups"] + c["tab_lookups"]) / dev.n_seqs  # streams + one line per table access (the filter's 2 MB stay in L2)
+        if args.full:
+            # fabric-side traffic and L2 misses of the A1 stage, from the committed rocprofv3 passes of this exact
+            # workload and walk mode (PMC passes cannot run inside the timed region: separate runs, tools/profile_bench.sh)
+            wl_key = f"{args.genome}x{n_mine}x{args.read_len}x{args.sub_rate:g}:{('map' if one_kernel else 'table' if sbwt.depth_table_order() > 0 else 'plan') if planned else 'plain'}"
+            sha = build_sha16()
+            traffic = tsrc = misses = walk_misses = plan_misses = None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath):
+                try:
+                    entry = json.load(open(tpath)).get("workloads", {}).get(wl_key)
+                    if entry and one_kernel and entry.get("build_sha16") != sha:
+                        tsrc = "none: %s was taken of another build (%s, this one is %s) - tools/profile_bench.sh renews it" % (
+                            entry.get("source"), entry.get("build_sha16"), sha)
+                        entry = None
+                    if entry:
+                        traffic, misses, tsrc = entry.get("a1_bytes_per_launch"), entry.get("a1_tcc_miss_per_launch"), entry.get("source")
+                        kern = entry.get("kernels", {})
+                        walk_misses = (kern.get("ms_walk_guided_kernel") or kern.get("ms_walk_recovery_kernel") or {}).get("tcc_miss")
+                        plan_misses = (kern.get("plan_kernel") or {}).get("tcc_miss")
+                except Exception:
+                    pass
+            rank_b, lcs_b = sbwt.device_bytes()
+            dto = sbwt.depth_table_order()
+            dtab_b = 0 if dto == 0 else (4 ** (dto + 1) if dto >= 4 else 4 ** dto)  # (grouped from 4 bases on: DESIGN.md section 4.2)
+            seed_d = int(lay["seed_depth"]) if planned else 0  # (from the library: kbo_index_device_layout - what the copy really holds)
+            seed_b = 8 * 4 ** seed_d if seed_d else 0
+            pair_b, plan_b = sbwt.device_pair_bytes(), sbwt.device_plan_bytes()
+            a1_kernels = ("plan_kernel (with the depth-table look-ups; dtab_resolve_kernel for items that cannot be staged) + redo_collect + ms_walk_kernel (reads the table could not resolve)" if table
+                          else "plan_kernel + plan_count/scan/emit + ms_walk_guided_kernel (ms_walk_recovery_kernel from 24 Mi rows on) + redo_collect + ms_walk_kernel (flagged reads)"
+                          if planned else "ms_walk_kernel")
+            walk_s = walk_ms * 1e-3
+            # what the stage is priced by: its OWN compulsory bytes (B_plan, counted by the model on the timed reads) when it
+            # planned, the reference algorithm's bytes when it walked plainly
+            b_alg = b_plan if b_plan is not None else b_ref
+            achieved = b_alg * bases / walk_s / 1e9 if b_alg is not None else None
+            ref_achieved = b_ref * bases / walk_s / 1e9 if b_ref is not None else None
             roofline = {
                 "bound": "hbm",
-                "bound_detail": "integer gather work, no MFMA: per read one seed-position look-up, three depth-table bytes per mismatch (each a line "
-                                "of its own; four in five settled by a 2 MB filter in L2 before they reach the table), the 2-bit text on the diagonal "
-                                "(L2 / Infinity Cache) and 2 B per base of streams.  Alone the kernel is not bound by its fills (with or without the "
-                                "filter: the same time), nor by its instructions: the wave's own chain of dependent loads is what is left (DESIGN.md 4.1)"
-                                + ("; the timed kernels ran beside the other batches' kernels and second passes (batches_in_flight)" if piped else ""),
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                "frac_meaning": "compulsory bytes of map_reads_kernel (counted by the kernel on the timed reads: bytes_by_part) x bases per step / " +
-                                ("the device's time per launch / 8 TB/s.  %d launches share the device at any time (one per pipeline), each for the "
-                                 "whole of its duration (kernel_ms: HIP events around every launch of the timed region, what rocprofv3 shows per "
-                                 "dispatch), so the device's time per launch is the timed region / launches = ms_per_step, second passes included "
-                                 "(never taken below kernel_ms / pipelines).  per_launch_duration prices the same bytes by kernel_ms as if the "
-                                 "launch had the device to itself; alone is the kernel with nothing beside it (one_batch_at_a_time)" % n_pipes
-                                 if shared else "its own duration (HIP events around it in every timed step) / 8 TB/s"),
-                "launches_sharing_the_device": n_pipes if shared else 1,
-                "device_ms_per_launch": round(k_s * 1e3, 4),
-                "per_launch_duration": {"achieved": round(b_map * bases / k_launch_s / 1e9, 1), "frac": round(b_map * bases / k_launch_s / 1e9 / HBM_PEAK_GBPS, 4)},
-                "alone": ({"kernel_ms": serial["map_reads_kernel_ms"], "achieved": round(b_map * bases / (serial["map_reads_kernel_ms"] * 1e-3) / 1e9, 1),
-                           "frac": round(b_map * bases / (serial["map_reads_kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
-                          if serial and serial.get("map_reads_kernel_ms") else None),
-                "algorithmic_bytes_per_base": round(b_map, 3), "bytes_by_part_first_slab": by, "units_per_launch": bases,
-                "kernel": "map_reads_kernel (kbo_amd/csrc/map_kernels.hip): MS -> derandomize -> translate -> relative_to_ref of every read it can finish",
-                "kernel_ms": round(map_kernel_ms, 4), "kernel_ms_per_rank": {"min": round(min(walk_all), 4), "max": round(max(walk_all), 4)},
-                "redo_pass_ms": round(map_redo_ms, 4),
-                "redo_pass": "finish_reads_kernel over the %.2f %% of the reads the kernel leaves: a wave a read, its lanes walk pieces of it "
-                             "behind k - 1 warm-up bases (a chain of about k + 10 dependent look-ups), then derandomize + translate and the "
-                             "characters" % (100.0 * c["tab_unresolved"] / dev.n_seqs),
+                "bound_detail": ("independent random byte gathers from the depth table (one fill each) + plan_kernel's streams and compare loop "
+                                 "(DESIGN.md section 4.2)" if table else
+                                 "L2-miss line fills by their rate and latency: integer gather work, 16 bytes used per 128-byte fill; the guided walk "
+                                 "keeps 8-12 waves per CU so that the lines of the lanes in flight stay in L2 (DESIGN.md sections 4.2, 6)"),
+                "achieved": round(achieved, 1) if achieved is not None else None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBPS, 4) if achieved is not None else None,
+                "frac_meaning": ("compulsory bytes of the plan-guided stage (B_plan: streams, records, " +
+                                 ("one table byte per look-up and the query window of every mismatch" if table else "two 16-byte loads per walk iteration") +
+                                 "; counted on the timed reads by oracle/plan_model.c, whose counts equal the kernels' own counters) / A1 stage time / 8 TB/s"
+                                 if b_plan is not None else "reference-algorithm bytes (SURVEY.md 8(d)) / A1 stage time / 8 TB/s"),
+                "algorithmic_bytes_per_base": round(b_alg, 3) if b_alg is not None else None,
+                "units_per_launch": bases, "kernel": "A1 stage = " + a1_kernels, "kernel_ms": round(walk_ms, 4),
+                "kernel_ms_per_rank": {"min": round(min(walk_all), 4), "max": round(max(walk_all), 4)},
                 "traffic": int(traffic) if traffic else None, "traffic_source": tsrc,
-                "traffic_frac": round(traffic / k_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
-                "wasted_traffic": round(traffic / (b_map * bases), 3) if traffic else None,
+                "traffic_frac": round(traffic / walk_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
+                "wasted_traffic": round(traffic / (b_alg * bases), 3) if traffic and b_alg else None,
                 "l2_miss_per_launch": int(misses) if misses else None,
-                "fill_rate_frac": round(misses / k_s / FILL_CEILING_PER_S, 4) if misses else None,
+                "fill_rate_frac": round(misses / walk_s / FILL_CEILING_PER_S, 4) if misses else None,
                 "fill_rate_ceiling": {"fills_per_s": FILL_CEILING_PER_S, "source": FILL_CEILING_SOURCE},
-                "fills_min_per_read": round(lines_min, 2), "l2_miss_per_read": round(misses / (bases / args.read_len), 2) if misses else None,
-                "frac_reference_algorithm": round(b_ref * bases / k_s / 1e9 / HBM_PEAK_GBPS, 4) if b_ref is not None else None,
+                "fills_min_per_unit": model["per_unit"]["distinct_lines_beyond_l2"] if model and "per_unit" in model else None,
+                "fills_min_per_read": model.get("fills_min_per_read") if model else None,
+                "l2_miss_per_read": round(misses / (bases / args.read_len), 2) if misses else None,
+                # measured L2 misses per unit: of the whole stage, and of the walk kernel alone (to set against fills_min_per_unit:
+                # the difference is the rank-block look-ups that miss although the blocks would fit the L2)
+                "l2_miss_per_unit": round(misses / max(1, stats["units"] * bases / dev.total), 2) if misses and planned and not table else None,
+                "walk_kernel_l2_miss_per_unit": round(walk_misses / max(1, stats["units"] * bases / dev.total), 2) if walk_misses and planned and not table else None,
+                "plan_kernel_l2_miss_per_read": round(plan_misses / (bases / args.read_len), 2) if plan_misses and table else None,
+                "frac_reference_algorithm": round(ref_achieved / HBM_PEAK_GBPS, 4) if ref_achieved is not None else None,
                 "reference_algorithm_bytes_per_base": round(b_ref, 2) if b_ref is not None else None,
-                "cross_check_whole_step_gbps": round(b_map * bases / (elapsed / args.steps) / 1e9, 1),
-                "stage_counters_gpu_first_slab": c, "build_sha16": sha,
+                "cross_check_whole_step_gbps": round(b_alg * bases / (elapsed / args.steps) / 1e9, 1) if b_alg is not None else None,
+                "stage_model": model,
+                "stage_counters_gpu_first_slab": stats if planned else None,
             }
+            if one_kernel:
+                # the dominant kernel priced by its OWN compulsory bytes, counted by the kernel itself on the first slab (kbo_set_plan_stats:
+                # one extra launch behind the timed region): what it must read and write however well it is written
+                c = map_stats
+                seeded = dev.n_seqs - c["items_noplan"]
+                by = {"query_bytes_in": dev.total, "characters_out": dev.total, "offsets_and_flags": 9 * dev.n_seqs,
+                      "seed_positions": 4 * c["seed_lookups"], "text_2bit_and_marks": 96 * seeded, "depth_table_bytes": c["tab_lookups"],
+                      "filter_words": 4 * c["seed_extensions"]}  # (seed_extensions: this kernel counts its filter look-ups there)
+                b_map = sum(by.values()) / dev.total
+                # the kernel's duration, launch by launch (HIP events around it).  With two pipelines two launches share the device
+                # for the whole of their durations: the device's time per launch is then the timed region / launches, not a launch's
+                # own duration - the bytes are priced by that (never less than duration / pipelines), the duration is printed beside it
+                k_launch_s = map_kernel_ms * 1e-3
+                shared = piped and n_pipes > 1
+                k_s = max(elapsed / args.steps, k_launch_s / n_pipes) if shared else k_launch_s
+                achieved = b_map * bases / k_s / 1e9
+                lines_min = (2 * dev.total / 128 + c["seed_lookups"] + c["tab_lookups"]) / dev.n_seqs  # streams + one line per table access (the filter's 2 MB stay in L2)
+                roofline = {
+                    "bound": "hbm",
+                    "bound_detail": "integer gather work, no MFMA: per read one seed-position look-up, three depth-table bytes per mismatch (each a line "
+                                    "of its own; four in five settled by a 2 MB filter in L2 before they reach the table), the 2-bit text on the diagonal "
+                                    "(L2 / Infinity Cache) and 2 B per base of streams.  Alone the kernel is not bound by its fills (with or without the "
+                                    "filter: the same time), nor by its instructions: the wave's own chain of dependent loads is what is left (DESIGN.md 4.1)"
+                                    + ("; the timed kernels ran beside the other batches' kernels and second passes (batches_in_flight)" if piped else ""),
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                    "frac_meaning": "compulsory bytes of map_reads_kernel (counted by the kernel on the timed reads: bytes_by_part) x bases per step / " +
+                                    ("the device's time per launch / 8 TB/s.  %d launches share the device at any time (one per pipeline), each for the "
+                                     "whole of its duration (kernel_ms: HIP events around every launch of the timed region, what rocprofv3 shows per "
+                                     "dispatch), so the device's time per launch is the timed region / launches = ms_per_step, second passes included "
+                                     "(never taken below kernel_ms / pipelines).  per_launch_duration prices the same bytes by kernel_ms as if the "
+                                     "launch had the device to itself; alone is the kernel with nothing beside it (one_batch_at_a_time)" % n_pipes
+                                     if shared else "its own duration (HIP events around it in every timed step) / 8 TB/s"),
+                    "launches_sharing_the_device": n_pipes if shared else 1,
+                    "device_ms_per_launch": round(k_s * 1e3, 4),
+                    "per_launch_duration": {"achieved": round(b_map * bases / k_launch_s / 1e9, 1), "frac": round(b_map * bases / k_launch_s / 1e9 / HBM_PEAK_GBPS, 4)},
+                    "alone": ({"kernel_ms": serial["map_reads_kernel_ms"], "achieved": round(b_map * bases / (serial["map_reads_kernel_ms"] * 1e-3) / 1e9, 1),
+                               "frac": round(b_map * bases / (serial["map_reads_kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+                              if serial and serial.get("map_reads_kernel_ms") else None),
+                    "algorithmic_bytes_per_base": round(b_map, 3), "bytes_by_part_first_slab": by, "units_per_launch": bases,
+                    "kernel": "map_reads_kernel (kbo_amd/csrc/map_kernels.hip): MS -> derandomize -> translate -> relative_to_ref of every read it can finish",
+                    "kernel_ms": round(map_kernel_ms, 4), "kernel_ms_per_rank": {"min": round(min(walk_all), 4), "max": round(max(walk_all), 4)},
+                    "redo_pass_ms": round(map_redo_ms, 4),
+                    "redo_pass": "finish_reads_kernel over the %.2f %% of the reads the kernel leaves: a wave a read, its lanes walk pieces of it "
+                                 "behind k - 1 warm-up bases (a chain of about k + 10 dependent look-ups), then derandomize + translate and the "
+                                 "characters" % (100.0 * c["tab_unresolved"] / dev.n_seqs),
+                    "traffic": int(traffic) if traffic else None, "traffic_source": tsrc,
+                    "traffic_frac": round(traffic / k_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
+                    "wasted_traffic": round(traffic / (b_map * bases), 3) if traffic else None,
+                    "l2_miss_per_launch": int(misses) if misses else None,
+                    "fill_rate_frac": round(misses / k_s / FILL_CEILING_PER_S, 4) if misses else None,
+                    "fill_rate_ceiling": {"fills_per_s": FILL_CEILING_PER_S, "source": FILL_CEILING_SOURCE},
+                    "fills_min_per_read": round(lines_min, 2), "l2_miss_per_read": round(misses / (bases / args.read_len), 2) if misses else None,
+                    "frac_reference_algorithm": round(b_ref * bases / k_s / 1e9 / HBM_PEAK_GBPS, 4) if b_ref is not None else None,
+                    "reference_algorithm_bytes_per_base": round(b_ref, 2) if b_ref is not None else None,
+                    "cross_check_whole_step_gbps": round(b_map * bases / (elapsed / args.steps) / 1e9, 1),
+                    "stage_counters_gpu_first_slab": c, "build_sha16": sha,
+                }
         result = {
             "metric": f"query Mbp/sec for kbo {'find' if args.find else 'map'}, k={args.k}, {args.genome / 1e6:g} Mbp SBWT; bit-exact MS vs CPU",
             "value": round(total_bases * args.steps / elapsed / 1e6, 1),
@@ -479,7 +487,7 @@ def main(argv=None):
                                              "with low clocks, and 5 warm-up steps are under 1 ms of load (--condition-ms 0: none)"},
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "u32", "data": "synthetic",
+            "dtype": "u32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{label}, {args.genome / 1e6:g} Mbp iid genome SBWT k={args.k}, "
                                    + (f"{args.reads} x {args.read_len} bp reads in all, {n_mine} per GPU, " if args.scaling == "strong"
                                       else f"{args.reads} x {args.read_len} bp reads per GPU, ")

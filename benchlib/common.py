@@ -45,11 +45,17 @@ def parse(argv=None):
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--sub-rate", type=float, default=0.01)
     ap.add_argument("--k", type=int, default=31)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall-clock budget of the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beyond the headline: the one-stream run of the same steps, the kernels' own "
+                         "counters and the roofline, the parity gate against the oracle, the CPU baseline, the stage model, the "
+                         "sensitivity variants, the entry points that return MS values, the one-shot map and the host-to-host rate.  "
+                         "Without it a run sets up, warms up, times its steps, writes --dump-outputs and prints the line "
+                         "(--call / --config C5 run their own legs either way: --no-cpu-baseline, --no-whole-call)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall-clock budget of the CPU baseline leg (--full)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip everything that runs the oracle (parity gate, CPU "
-                    "baseline, stage model) and the sensitivity / host-to-host legs: profiling runs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sensitivity and host-to-host legs only")
-    ap.add_argument("--extras", action="store_true", help="run the sensitivity and host-to-host legs on a custom workload too "
+                    "baseline, stage model) and the sensitivity / host-to-host legs of --full or --call: profiling runs")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the sensitivity and host-to-host legs")
+    ap.add_argument("--extras", action="store_true", help="--full: run the sensitivity and host-to-host legs on a custom workload too "
                     "(they run by default on the preset configurations, on rank 0 at N = 1)")
     ap.add_argument("--find", action="store_true",
                     help="time kbo::find instead of kbo::map: the step ends with format::run_lengths on the device")
@@ -149,14 +155,16 @@ def cache_path(args):
     return os.path.join(d, f"kbo_bench_iid_{args.genome}_k{args.k}{'_noplan' if args.no_plan else ''}.kbohip")
 
 
-def build_or_load_index(args, threads, may_build=True):
+def build_or_load_index(args, threads, may_build=True, share=False):
     """-> (genome, sbwt).  The index file carries the path cover (kbo_index_save), so a rank that loads it uploads after a
-    few streaming passes instead of repeating the build and the cover's pointer chase."""
+    few streaming passes instead of repeating the build and the cover's pointer chase.  A run reads no index file an earlier run
+    left unless --index-cache names it: otherwise it builds, and writes the file only for the ranks of its own run (`share`: the
+    parent of --gpus N, rank 0 of a run started without one); may_build=False: a rank that loads what its run wrote."""
     import kbo_amd
     from kbo_amd import index as kindex, synth
     genome = synth.genome(args.genome)
     path = cache_path(args)
-    if os.path.exists(path):
+    if (args.index_cache or not may_build) and os.path.exists(path):
         try:
             sbwt, _ = kindex.load_flat(path)
             if sbwt.k() == args.k and sbwt.n_kmers() > 0:
@@ -166,7 +174,7 @@ def build_or_load_index(args, threads, may_build=True):
     if not may_build:
         raise SystemExit(f"bench.py: index cache {path} missing")
     sbwt, _ = kbo_amd.build([genome], kbo_amd.BuildOpts(k=args.k, num_threads=min(16, max(1, threads))))
-    if os.environ.get("KBO_BENCH_NO_CACHE") == "1":  # (a run that builds the index once and uses it once: tests)
+    if not (args.index_cache or share) or os.environ.get("KBO_BENCH_NO_CACHE") == "1":  # (a run that builds the index once and uses it once)
         return genome, sbwt
     try:
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -201,7 +209,7 @@ def spawn_ranks(args, argv):
     if args.no_plan:
         kbo_amd.lib().kbo_set_plan(0, 0, 0)
     cores, _ = usable_cores()
-    build_or_load_index(args, cores)
+    build_or_load_index(args, cores, share=True)
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]

@@ -50,6 +50,30 @@ def test_steps_is_the_number_of_timed_steps():
         pass
 
 
+def test_full_is_off_by_default():
+    b = _bench()
+    assert b.parse([]).full is False and b.parse(["--steps", "20", "--warmup", "5"]).full is False
+    assert b.parse(["--full"]).full is True and b.parse(["--config", "C3", "--full"]).full is True
+
+
+def test_a_run_reads_no_index_file_an_earlier_run_left(tmp_path, monkeypatch):
+    """without --index-cache a run builds its index: a file under the cache's name is neither read nor written by one process; the
+    parent of --gpus N (share) builds afresh too and leaves the file for its own ranks"""
+    b = _bench()
+    monkeypatch.setenv("KBO_BENCH_CACHE_DIR", str(tmp_path))
+    monkeypatch.delenv("KBO_BENCH_NO_CACHE", raising=False)
+    a = b.parse(["--genome", "50000", "--reads", "500"])
+    other = b.parse(["--genome", "60000", "--reads", "500", "--index-cache", b.cache_path(a)])
+    b.build_or_load_index(other, 2)                  # an earlier run's file, of another index, under this run's cache name
+    before = os.stat(b.cache_path(a)).st_mtime_ns
+    _, s = b.build_or_load_index(a, 2)
+    assert s.n_sets() == 50_001 and os.stat(b.cache_path(a)).st_mtime_ns == before
+    _, s = b.build_or_load_index(a, 2, share=True)
+    assert s.n_sets() == 50_001
+    _, s2 = b.build_or_load_index(a, 2, may_build=False)  # a rank of the same run
+    assert s2.n_sets() == 50_001
+
+
 def test_dump_outputs_types_budget_and_sample(tmp_path):
     b = _bench()
     rng = np.random.default_rng(1)

@@ -1,8 +1,8 @@
-"""bench.py end to end on the GPU box, at reduced size: the single-process line (kbo_map_batch_dev's one kernel priced by its own
+"""bench.py end to end on the GPU box, at reduced size: with --full, the single-process line (kbo_map_batch_dev's one kernel priced by its own
 counters; with --two-kernels / without a depth table the round-3 route priced by the stage model; CPU baseline, sensitivity
 variants, host-to-host rate) and `--gpus 2` started from a plain `python bench.py` (the parent builds
 the index cache on the host and spawns the ranks; with KBO_BENCH_ONE_GPU=1 both ranks share cuda:0 over gloo - a functional
-test of the multi-process path, its numbers mean nothing)."""
+test of the multi-process path, its numbers mean nothing); without it, the lean line of a plain run and its --dump-outputs."""
 import json
 import os
 import subprocess
@@ -59,12 +59,12 @@ def _check_line(r, n_gpus, table=True, one_kernel=True):
 
 def test_bench_line_two_kernels(tmp_path):
     """--two-kernels: round 3's route (plan_kernel with the table look-ups, then the derandomize / translate kernel), priced by the model"""
-    r = _run(["--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--no-extras", "--two-kernels"], tmp_path)
+    r = _run(["--full", "--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--no-extras", "--two-kernels"], tmp_path)
     _check_line(r, 1, one_kernel=False)
 
 
 def test_bench_line_single_process_with_extras(tmp_path):
-    r = _run(["--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1.5", "--extras"], tmp_path)
+    r = _run(["--full", "--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1.5", "--extras"], tmp_path)
     _check_line(r, 1)
     names = [v["variant"] for v in r["sensitivity"]]
     assert len(names) == 8 and any("reverse" in n for n in names) and any("repeat" in n for n in names) and any("10 kbp reads, 1%" in n for n in names)
@@ -81,7 +81,7 @@ def test_bench_line_single_process_with_extras(tmp_path):
 
 def test_bench_line_guided_walk(tmp_path):
     """--depth-table -1: units and the guided walk (what larger indexes get), priced by the same model"""
-    r = _run(["--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--no-extras", "--depth-table", "-1"],
+    r = _run(["--full", "--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--no-extras", "--depth-table", "-1"],
              tmp_path)
     _check_line(r, 1, table=False, one_kernel=False)
     assert "guided walk" in r["config"]["walk"]
@@ -89,14 +89,19 @@ def test_bench_line_guided_walk(tmp_path):
 
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs: the characters the last timed step computed - kbo::map's, of the resident batch that step took - equal to the
-    oracle's for the same reads; --steps is the number of timed steps"""
+    oracle's for the same reads; --steps is the number of timed steps.  A plain run (no --full): the headline and nothing behind it"""
     import numpy as np
     sys.path.insert(0, ROOT)
     from kbo_amd import synth
     from oracle import binding as ora
     out = tmp_path / "out"
-    r = _run(["--genome", "400000", "--reads", "30000", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(out)], tmp_path)
+    r = _run(["--genome", "400000", "--reads", "30000", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)], tmp_path)
     assert r["steps"] == 5 and r["ms_per_step"] > 0
+    assert r["full"] is False and r["value"] > 0 and r["unit"] == "Mbp/s" and r["higher_is_better"] is True and r["dtype"] == "u32"
+    assert r["kernels_ms"]["map_reads_kernel"] > 0 and r["config"]["batches_in_flight"].startswith("4 on 2 pipeline")
+    for key in ("roofline", "one_batch_at_a_time", "cpu_baseline", "bit_exact_vs_oracle", "sensitivity", "ms_variant", "one_shot_map", "host_to_host"):
+        assert r[key] is None, key
+    assert not [f for f in os.listdir(str(tmp_path)) if f.endswith(".kbohip")]  # (one process: the index is built, no file is left for a later run)
     d = r["dump_outputs"]
     assert sorted(os.listdir(str(out))) == ["chars.npy"] and not d["arrays"]["chars"]["sampled"]
     chars = np.load(str(out / "chars.npy"))
@@ -111,7 +116,7 @@ def test_bench_dump_outputs(tmp_path):
 
 def test_bench_c4_shape_strong_scaling_two_ranks(tmp_path):
     """--config C4 at reduced size: the reads are a fixed set, sharded over the ranks (strong scaling)"""
-    r = _run(["--config", "C4", "--gpus", "2", "--genome", "400000", "--reads", "50001", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"],
+    r = _run(["--full", "--config", "C4", "--gpus", "2", "--genome", "400000", "--reads", "50001", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"],
              tmp_path, {"KBO_BENCH_ONE_GPU": "1"})
     _check_line(r, 2)
     assert r["scaling"] == "strong" and "50001 x 150 bp reads in all, 25001 per GPU" in r["config"]["workload"]
@@ -122,7 +127,7 @@ def test_bench_c4_shape_four_ranks(tmp_path):
     gloo: functional only; four ranks and this test's process keep the processes with the GPU open within what a shared machine
     allows - the 8-way shards are tests/test_bench_host.py's): --config C4's strong-scaling shards - contiguous, ceil(reads / 4) each,
     the last one short, tiling the read set exactly - the index cache built once by the parent, the CPU quota split cores // world"""
-    r = _run(["--config", "C4", "--gpus", "4", "--genome", "300000", "--reads", "240003", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--no-extras"],
+    r = _run(["--full", "--config", "C4", "--gpus", "4", "--genome", "300000", "--reads", "240003", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--no-extras"],
              tmp_path, {"KBO_BENCH_ONE_GPU": "1"})
     _check_line(r, 4)
     assert r["scaling"] == "strong" and "240003 x 150 bp reads in all, 60001 per GPU" in r["config"]["workload"] and "x4" in r["config"]["parallelism"]
@@ -131,7 +136,7 @@ def test_bench_c4_shape_four_ranks(tmp_path):
 
 
 def test_bench_gpus_2_spawns_two_ranks(tmp_path):
-    r = _run(["--gpus", "2", "--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1.5"],
+    r = _run(["--full", "--gpus", "2", "--genome", "400000", "--reads", "30000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1.5"],
              tmp_path, {"KBO_BENCH_ONE_GPU": "1"})
     _check_line(r, 2)
     assert r["scaling"] == "weak" and "x2" in r["config"]["parallelism"]

@@ -6,7 +6,7 @@ VAR=$1; shift
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = "-" ]; then unset $VAR; else export $VAR=$v; fi
-  python3 $ROOT/bench.py --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 $ROOT/bench.py --full --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 o=d.get('one_batch_at_a_time') or {}

@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 CACHE=/tmp/$CFG.kbohip
-ARGS="--config $CFG --steps 3 --warmup 1 --no-cpu-baseline --index-cache $CACHE $*"
+ARGS="--full --config $CFG --steps 3 --warmup 1 --no-cpu-baseline --index-cache $CACHE $*"
 if [ "$CFG" = C5 ]; then ARGS="$ARGS --no-whole-call"; fi   # (the profiler passes: the first pass's kernels only)
 python3 "$ROOT/bench.py" --config $CFG --steps 1 --warmup 0 --no-cpu-baseline --index-cache $CACHE > /dev/null 2>&1   # (writes the cache)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/stats.log" 2>&1

@@ -6,7 +6,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd /tmp && export TMPDIR=/tmp
 OUT="$ROOT/gpurun_out/stats_$TAG"
 rm -rf "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --config C3 --steps 6 --warmup 2 --no-cpu-baseline "$@" > "$OUT.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --full --config C3 --steps 6 --warmup 2 --no-cpu-baseline "$@" > "$OUT.log" 2>&1
 tail -1 "$OUT.log" | cut -c1-400
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)
 cp "$f" "$ROOT/gpurun_out/stats_${TAG}_kernel_stats.csv"
