@@ -448,7 +448,9 @@ int kbo_stream_pair_create(int tail_cus, void **stream, void **tail_stream);
 void kbo_stream_pair_destroy(void *stream, void *tail_stream);
 /* ---- several batches in flight, the library's own arrangement (what bench.py's headline is measured with): `pipelines` pairs of
  * (kernel stream, second-pass stream) that take the batches in turn, two slots - work and MS buffers, a completion event - per
- * pipeline, so that a batch's second pass runs beside the next batches' kernels.  max_* size the slots' buffers: a batch may not
+ * pipeline, so that a batch's second pass runs beside the next batches' kernels.  When max_seq_len is 1 .. 160 over an unsharded index
+ * (batches of reads) the kernels' stream is a plain one on every compute unit and the second-pass stream one of the device's highest
+ * priority, the second pass in workgroups of one wave; else the pair is kbo_stream_pair_create(-1, ..)'s.  max_* size the slots' buffers: a batch may not
  * exceed them.  The batch's own buffers (d_concat, d_offsets, d_chars_out) stay the caller's and must stay valid and untouched
  * until the batch is complete.
  *   kbo_map_stream_submit   enqueues kbo::map (format != 0) / kbo::matches of one device-resident batch and returns at once;

@@ -481,7 +481,8 @@ void run_lengths(const FindTail &f, const uint8_t *d_chars, const uint64_t *d_of
 // map_reads_kernel (both *fused = 1), else two kernels - the walk, then derandomize + translate; kbo::find's run lengths behind it
 int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                        size_t max_seq_len, double max_error_prob, int format, int want_ms, uint8_t *d_ms, uint8_t *d_chars_out,
-                       void *d_work, size_t work_bytes, void *stream, void *tail_stream, int *fused, const FindTail *find = nullptr)
+                       void *d_work, size_t work_bytes, void *stream, void *tail_stream, int *fused, const FindTail *find = nullptr,
+                       bool urgent_tail = false)
 {
     if (fused) *fused = 0;
     return guarded([&] {
@@ -521,7 +522,7 @@ int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t
             ts = map_reads_then(a, s, static_cast<hipStream_t>(tail_stream), [&](hipStream_t t) {
                 if (kbo::map_reads_finish_applies(a)) {
                     // the reads the kernel listed, finished by one kernel: walk, derandomize + translate, characters (and their runs)
-                    HIP_OK(kbo::launch_map_reads_finish(a, t));
+                    HIP_OK(kbo::launch_map_reads_finish(a, t, urgent_tail && t != s));
                 } else {
                     HIP_OK(kbo::launch_redo_pass(a, t)); // (redo_collect_kernel reads the offsets as well: no item list at all)
                     HIP_OK(kbo::launch_derand_flagged(d_ms, d_offsets, n, idx->host.k, thr, format ? d_concat : nullptr, d_chars_out, a.redo,
@@ -587,6 +588,19 @@ static int tail_cus_default() // compute units the kernels' streams stay off (KB
     static const int v = std::getenv("KBO_TAIL_CUS") ? std::atoi(std::getenv("KBO_TAIL_CUS")) : 32;
     return v;
 }
+// The pair of kbo_map_stream's pipelines whose batches are reads (map_reads_kernel, its list finished by finish_reads_kernel): the kernels'
+// stream a plain one on all 256 units, the second passes' stream one of the device's highest priority, and the second pass launched as
+// workgroups of one wave (launch_map_reads_finish).  A wave slot that a kernel's wave leaves then goes to the second pass first, and any
+// free slot takes one of its waves: its few hundred waves are resident within microseconds, not behind the kernels' waves - each of which
+// needed four slots on one unit at once before.  Priority alone: 918 Gbp/s, one-wave workgroups alone: 795, both: 1075 against 1035 for
+// the 32 reserved units on the same box - what a build that never runs the second pass reaches
+static void make_urgent_pair(hipStream_t *ks, hipStream_t *ts)
+{
+    int least = 0, greatest = 0;
+    HIP_OK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_OK(hipStreamCreateWithPriority(ts, hipStreamNonBlocking, greatest));
+    HIP_OK(hipStreamCreateWithFlags(ks, hipStreamNonBlocking));
+}
 static void make_stream_pair(int device, int tail_cus, hipStream_t *ks, hipStream_t *ts)
 {
     const int want = tail_cus >= 0 ? tail_cus : tail_cus_default();
@@ -628,8 +642,10 @@ void kbo_stream_pair_destroy(void *stream, void *tail_stream)
 struct kbo_map_stream {
     kbo_index_t *idx = nullptr;
     int device = 0;
-    // a pipeline: the kernels' stream `ks` (kept off 32 compute units) and the second passes' stream `ts` (plain): make_stream_pair
+    // a pipeline: the kernels' stream `ks` and the second passes' stream `ts`: make_urgent_pair (plain, highest priority) or make_stream_pair
+    // (kept off 32 compute units, plain)
     struct Pipe { hipStream_t ks = nullptr, ts = nullptr; };
+    bool urgent = false; // the pipelines are make_urgent_pair's (batches of reads), not make_stream_pair's
     struct Slot {
         DevBuf work, ms;
         hipEvent_t done = nullptr;
@@ -676,8 +692,13 @@ int kbo_map_stream_create(kbo_index_t *idx, int pipelines, size_t max_seqs, uint
         m->work_bytes = dev_work(max_seqs, max_bases, max_seq_len, idx->host.k, idx->sharded()).map_min;
         m->pipes.resize((size_t)pipelines);
         m->slots.resize(2 * (size_t)pipelines);
+        // batches of reads (map_reads_kernel, then finish_reads_kernel) take the unmasked pair; sequences of any length, a sharded index, the
+        // three-launch second pass (KBO_MAP_FINISH=0) and an explicit KBO_TAIL_CUS keep the kernels' stream off KBO_TAIL_CUS units
+        const char *fin = std::getenv("KBO_MAP_FINISH");
+        m->urgent = !idx->sharded() && max_seq_len > 0 && max_seq_len <= 160 && !std::getenv("KBO_TAIL_CUS") && !(fin && std::atoi(fin) == 0);
         for (auto &p : m->pipes) {
-            make_stream_pair(m->device, -1, &p.ks, &p.ts);
+            if (m->urgent) make_urgent_pair(&p.ks, &p.ts);
+            else make_stream_pair(m->device, -1, &p.ks, &p.ts);
         }
         for (auto &sl : m->slots) {
             sl.work.alloc(m->work_bytes + 64);
@@ -722,7 +743,8 @@ int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const ui
     });
     if (rc != KBO_OK) return rc;
     rc = map_batch_dev_impl(m->idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, d_ms_out ? 1 : 0,
-                            d_ms_out ? d_ms_out : sl.ms.as<uint8_t>(), d_chars_out, sl.work.p, m->work_bytes, kern, tail, fused);
+                            d_ms_out ? d_ms_out : sl.ms.as<uint8_t>(), d_chars_out, sl.work.p, m->work_bytes, kern, tail, fused, nullptr,
+                            m->urgent);
     if (rc != KBO_OK) return rc;
     rc = guarded([&] { // complete when both streams have come this far
         HIP_OK(hipEventRecord(m->kdone, kern));

@@ -227,7 +227,7 @@ bool map_reads_applies(const WalkArgs &a);
 // translates them)
 hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream);
 bool map_reads_finish_applies(const WalkArgs &a);
-hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream);
+hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream, bool one_wave_groups = false);
 bool map_reads_direct(const WalkArgs &a);
 bool map_reads_packed_applies(const WalkArgs &a, bool packed_out); // (a.qp set: the reads as 2-bit words; a.packed_out: the characters too)
 // packed-native batches (pack_kernels.hip): exc[s] = 1 for every read that holds a listed byte (d_exc zeroed first); the bytes of the

@@ -1492,7 +1492,7 @@ bool map_reads_finish_applies(const WalkArgs &a)
     return env_finish != 0 && a.seq_off != nullptr && a.qp == nullptr && a.units != nullptr && a.max_item_len != 0 && a.max_item_len <= 16u * kMapWords;
 }
 
-hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream)
+hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream, bool one_wave_groups)
 {
     if (a.n_items == 0) return hipSuccess;
     const uint32_t waves = std::min(kFinishWaves, ((a.n_items + 63u) / 64u + 3u) & ~3u);
@@ -1500,7 +1500,10 @@ hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream)
     // beside other batches' kernels a long list costs by those, not by its chain)
     static const int env_r1 = std::getenv("KBO_FINISH_R1") ? std::atoi(std::getenv("KBO_FINISH_R1")) : 1024; // experiments
     static const int env_r4 = std::getenv("KBO_FINISH_R4") ? std::atoi(std::getenv("KBO_FINISH_R4")) : 4096;
-    hipLaunchKernelGGL(finish_reads_kernel, dim3(waves / 4u), dim3(256), 4u * kFinishLds, stream, a, (uint32_t)env_r1, (uint32_t)env_r4);
+    // one_wave_groups: beside kernels that hold the whole device (kbo_map_stream's unmasked pipelines) a workgroup of four waves waits for
+    // four free slots on one compute unit at once, a workgroup of one for any free slot
+    const uint32_t wpb = one_wave_groups ? 1u : 4u;
+    hipLaunchKernelGGL(finish_reads_kernel, dim3(waves / wpb), dim3(64u * wpb), wpb * kFinishLds, stream, a, (uint32_t)env_r1, (uint32_t)env_r4);
     return hipGetLastError();
 }
 
