@@ -363,6 +363,27 @@ typedef struct {
 int kbo_find_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs,
                           const uint64_t *exc_pos, const uint8_t *exc_byte, size_t n_exc, const kbo_find_opts *opts,
                           kbo_rle32 **rles, uint64_t *rle_offsets);
+/* kbo::matches over a packed batch in its SPARSE form: only the runs of characters other than 'M'.  A run is a maximal stretch
+ * of one character other than 'M' inside one sequence's kbo::matches output (never across sequences; "-X" is two runs).
+ * Records are ordered by (seq, start); a sequence without one is all 'M', and one of fewer than 3 bases (no alignment) has
+ * none.  12 bytes a run and nothing per sequence: at 1 % substitutions a small fraction of the dense words' bytes.  Lossless:
+ * kbo_sparse_expand rebuilds kbo_matches_batch's characters, and with the reads kbo_map_batch(..., format = 1)'s
+ * (format::relative_to_ref, format.rs:266-287).  Inputs, checks and error codes are kbo_matches_batch_packed's; sequences must
+ * be shorter than 2^30 bases (KBO_E_UNSUPPORTED).  *runs is library-allocated (kbo_free), *n_runs records. */
+typedef struct {
+    uint32_t seq;      /* index of the sequence in the batch (0 .. n_seqs-1) */
+    uint32_t start;    /* first position of the run within that sequence (0-based) */
+    uint32_t len_code; /* (length << 2) | code; code as in the packed alphabet: 1 = '-', 2 = 'X', 3 = 'R' (0 = 'M' never occurs) */
+} kbo_aln_run;
+int kbo_matches_batch_sparse(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs,
+                             const uint64_t *exc_pos, const uint8_t *exc_byte, size_t n_exc, double max_error_prob,
+                             kbo_aln_run **runs, uint64_t *n_runs);
+/* Host helper (threaded): sparse records -> one byte per base, offsets[n_seqs] bytes at `out`.  ref_concat == NULL: kbo::matches'
+ * characters (M - X R, what kbo_matches_batch returns); ref_concat = the reads: format::relative_to_ref of them (the read's base for
+ * 'M' and 'R', '-' for 'X' and '-': what kbo_map_batch(..., format = 1) returns).  KBO_E_BAD_ARG for records out of (seq, start)
+ * order, overlapping, of length 0, with code 0 or outside their sequence. */
+int kbo_sparse_expand(const kbo_aln_run *runs, uint64_t n_runs, const uint64_t *offsets, size_t n_seqs, const uint8_t *ref_concat,
+                      uint8_t *out);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`
@@ -503,6 +524,18 @@ int kbo_matches_packed_dev(kbo_index_t *idx, const uint32_t *d_words, const uint
 size_t kbo_run_lengths_work_bytes(size_t n_seqs);
 int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len,
                         size_t max_gap_len, void *d_work, uint32_t *d_records, size_t capacity, void *stream);
+/* The sparse form (kbo_aln_run, above) of a device-resident packed batch of kbo::matches characters - what kbo_matches_packed_dev
+ * writes: kbo_packed_words() words, every sequence starts a word, M - X R = 0 .. 3; the padding bits of a sequence's last word
+ * are ignored - enqueued on `stream`; the library never synchronises.  d_offsets counts bases (n_seqs + 1 entries, 8-byte
+ * aligned); d_words 4-byte aligned, no slack needed.  max_seq_len = the longest sequence if known: it bounds the work (0 =
+ * unknown: as many workgroups as for the largest batch), and 2^30 or more is refused (KBO_E_UNSUPPORTED; every sequence must be shorter than 2^30 bases, the batch hold fewer
+ * than 2^32 - 256 words and 2^32 bases).  d_work: kbo_sparse_runs_work_bytes(n_seqs, total words) bytes, 16-byte aligned
+ * (0 from it: the batch is too large).  d_runs: `capacity` records (12 bytes each, 4-byte aligned); runs beyond capacity are
+ * counted but not written, and nothing past d_runs[capacity] is.  *d_n_runs (one u32, 4-byte aligned) receives the number
+ * of runs of the batch; a sequence of fewer than 3 bases has none.  seq in the records = the index in this batch. */
+size_t kbo_sparse_runs_work_bytes(size_t n_seqs, uint64_t total_words);
+int kbo_sparse_runs_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, void *d_work,
+                        kbo_aln_run *d_runs, size_t capacity, uint32_t *d_n_runs, void *stream);
 /* Options of ONE index handle: what the process-wide setters below and in kbo_hip_tuning.h (kbo_set_devices, kbo_set_slab_bytes,
  * kbo_set_plan, kbo_set_depth_table, kbo_set_depth_table_anchors) decide for every index, decided for this one - two indexes of one
  * process (a small reference next to a large one; a service with one handle per tenant) no longer share them.  A field left at its

@@ -111,6 +111,7 @@ SYMBOLS = [
     "kbo_index_opts_default", "kbo_index_set_opts", "kbo_index_get_opts", "kbo_matches_packed_dev", "kbo_matches_packed_dev_scratch_bytes",
     "kbo_find_batch_dev", "kbo_map_stream_create", "kbo_map_stream_submit", "kbo_map_stream_wait", "kbo_map_stream_wait_on",
     "kbo_map_stream_sync", "kbo_map_stream_free", "kbo_map_batch_opts", "kbo_fill_gaps_batch", "kbo_index_build_device",
+    "kbo_matches_batch_sparse", "kbo_sparse_expand", "kbo_sparse_runs_work_bytes", "kbo_sparse_runs_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -118,7 +119,7 @@ TUNING_SYMBOLS = [
     "kbo_set_pair_steps", "kbo_set_force_big_layout", "kbo_set_seed_table_depth", "kbo_set_plan", "kbo_set_plan_tuning",
     "kbo_set_plan_unit_cap_divisor", "kbo_index_plan_holdoff", "kbo_set_walk_experiment", "kbo_plan_stats_dev", "kbo_set_plan_stats", "kbo_set_index_shards", "kbo_index_shard", "kbo_set_depth_table", "kbo_set_depth_table_anchors", "kbo_index_depth_table", "kbo_run_automaton_depths",
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
-    "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases",
+    "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
 ]
 
 _lib = None
@@ -224,6 +225,11 @@ def lib():
     L.kbo_unpack_matches.argtypes = [vp, vp, sz, vp]
     L.kbo_matches_batch_packed.argtypes = [vp, vp, vp, sz, vp, vp, sz, dbl, vp]
     L.kbo_find_batch_packed.argtypes = [vp, vp, vp, sz, vp, vp, sz, C.POINTER(FindOpts), C.POINTER(vp), vp]
+    L.kbo_matches_batch_sparse.argtypes = [vp, vp, vp, sz, vp, vp, sz, dbl, C.POINTER(vp), C.POINTER(u64)]
+    L.kbo_sparse_expand.argtypes = [vp, u64, vp, sz, vp, vp]
+    L.kbo_sparse_runs_work_bytes.argtypes = [sz, u64]; L.kbo_sparse_runs_work_bytes.restype = sz
+    L.kbo_sparse_runs_dev.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
+    L.kbo_sparse_runs_blocks.argtypes = [sz, sz]; L.kbo_sparse_runs_blocks.restype = u32
     L.kbo_set_plan_stats.argtypes = [C.c_int]
     L.kbo_set_index_shards.argtypes = [C.c_int]
     L.kbo_set_depth_table.argtypes = [C.c_int]

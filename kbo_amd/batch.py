@@ -147,6 +147,50 @@ def matches_batch_packed(sbwt, words, offsets, exc_pos, exc_byte, max_error_prob
     return out
 
 
+# kbo_hip.h kbo_aln_run as the C ABI lays it out, and as the Python side hands it out: length and code apart
+_ALN_RUN = np.dtype([("seq", "<u4"), ("start", "<u4"), ("len_code", "<u4")])
+SPARSE_DTYPE = np.dtype([("seq", "<u4"), ("start", "<u4"), ("len", "<u4"), ("code", "u1")])
+
+
+def _sparse_from_raw(raw):
+    out = np.empty(len(raw), dtype=SPARSE_DTYPE)
+    out["seq"], out["start"] = raw["seq"], raw["start"]
+    out["len"], out["code"] = raw["len_code"] >> 2, raw["len_code"] & 3
+    return out
+
+
+def _sparse_to_raw(runs):
+    raw = np.empty(len(runs), dtype=_ALN_RUN)
+    raw["seq"], raw["start"] = runs["seq"], runs["start"]
+    raw["len_code"] = (runs["len"].astype(np.uint32) << np.uint32(2)) | runs["code"].astype(np.uint32)
+    return raw
+
+
+def matches_batch_sparse(sbwt, words, offsets, exc_pos, exc_byte, max_error_prob=1e-7):
+    """kbo::matches over 2-bit packed reads, only the runs of characters other than 'M' -> structured array (SPARSE_DTYPE: seq,
+    start, len, code with 1 = '-', 2 = 'X', 3 = 'R'), ordered by (seq, start)"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    p, n = C.c_void_p(), C.c_uint64(0)
+    check(lib().kbo_matches_batch_sparse(sbwt._h, words.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                         exc_pos.ctypes.data if len(exc_pos) else None, exc_byte.ctypes.data if len(exc_byte) else None,
+                                         len(exc_pos), max_error_prob, C.byref(p), C.byref(n)))
+    total = int(n.value)
+    raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(max(1, total) * 3,))[:total * 3].copy().view(_ALN_RUN)
+    lib().kbo_free(p)
+    return _sparse_from_raw(raw)
+
+
+def expand_sparse(runs, offsets, ref=None):
+    """sparse records -> one byte per base: kbo::matches' characters, or with the reads (ref) format::relative_to_ref of them"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    raw = _sparse_to_raw(runs)
+    out = np.zeros(int(offsets[-1]), dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8) if ref is not None else None
+    check(lib().kbo_sparse_expand(raw.ctypes.data if len(raw) else None, len(raw), offsets.ctypes.data, len(offsets) - 1,
+                                  ref.ctypes.data if ref is not None else None, out.ctypes.data))
+    return out
+
+
 def find_batch_packed(sbwt, words, offsets, exc_pos, exc_byte, find_opts=None):
     from . import FindOpts
     o = find_opts if find_opts is not None else FindOpts()
@@ -252,6 +296,26 @@ class PackedDeviceBatch:
     def chars(self):
         """the characters as bytes, on the host"""
         return unpack_matches(self.words_out[:len(self.words)].cpu().numpy().view(np.uint32), self.offsets)
+
+    def sparse_runs(self, stream=None, capacity=None):
+        """the runs other than 'M' of the characters run() left in words_out (kbo_hip.h kbo_sparse_runs_dev), on the host as
+        matches_batch_sparse returns them; synchronises the stream (a second pass when they are more than `capacity`)"""
+        torch = self.torch
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if getattr(self, "sparse_work", None) is None:
+            wb = int(lib().kbo_sparse_runs_work_bytes(self.n_seqs, len(self.words)))
+            self.sparse_work = torch.zeros(wb // 8 + 2, dtype=torch.int64, device=self.device)
+            self.sparse_count = torch.zeros(4, dtype=torch.int32, device=self.device)
+        cap = capacity if capacity is not None else 2 * self.n_seqs + 16
+        while True:
+            recs = torch.zeros(max(1, cap) * 3, dtype=torch.int32, device=self.device)
+            check(lib().kbo_sparse_runs_dev(self.words_out.data_ptr(), self.off.data_ptr(), self.n_seqs, self.max_len,
+                                            self.sparse_work.data_ptr(), recs.data_ptr(), cap, self.sparse_count.data_ptr(), s.cuda_stream))
+            s.synchronize()
+            total = int(self.sparse_count[0].item())
+            if total <= cap:
+                return _sparse_from_raw(recs[:total * 3].cpu().numpy().view(np.uint32).view(_ALN_RUN))
+            cap = total
 
 
 class DeviceBatch:

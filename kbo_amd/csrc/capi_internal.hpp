@@ -244,6 +244,17 @@ struct RleSink {
     }
 };
 constexpr size_t kRleWords = 7; // device run-length records are seven u32; kbo_rle has the reference's usize fields
+// Where kbo_matches_batch_sparse collects the runs of characters other than 'M' of every slab (sparse_kernels.hip; the
+// character words never leave the device).  Records carry the sequence's index in the whole batch, so nothing is rewritten.
+struct SparseSink {
+    // one device: slabs complete in order, their records go straight into the result array
+    kbo_aln_run *all = nullptr;
+    size_t all_cap = 0, all_used = 0;
+    bool direct = false;
+    // several devices: slabs complete out of order, kept per slab and put together at the end
+    std::vector<std::vector<kbo_aln_run>> runs;
+    ~SparseSink() { std::free(all); }
+};
 
 uint32_t max_len(const uint64_t *offsets, size_t n_seqs);
 uint64_t walk_chunk(uint64_t total, size_t n_seqs, uint32_t k);
@@ -304,7 +315,7 @@ void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team);
 void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
                         double max_error_prob, bool format, uint8_t *chars_out, RleSink *sink = nullptr);
 // the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list; the characters come
-// back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths
+// back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths, or, with a sparse sink, as their runs other than 'M'
 struct PackedBatch {
     const uint32_t *words;
     const uint64_t *exc_pos;
@@ -312,7 +323,7 @@ struct PackedBatch {
     size_t n_exc;
 };
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink *sink = nullptr);
+                               uint32_t *packed_out, RleSink *sink = nullptr, SparseSink *sparse = nullptr);
 // A1 over a host batch: MS values, and intervals when lo/hi are given
 void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint8_t *d_out,
                    uint32_t *lo_out, uint32_t *hi_out);

@@ -891,3 +891,47 @@ int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_
                     (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu), static_cast<hipStream_t>(stream), false);
     });
 }
+
+// ---- the sparse form of kbo::matches over device-resident character words (sparse_kernels.hip)
+namespace {
+size_t sparse_prefix_bytes(size_t n_seqs) { return (kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t) + 15) / 16 * 16; }
+// the words are known on the device only: the longest sequence bounds them, an unknown length takes the most workgroups
+uint32_t sparse_dev_blocks(size_t n_seqs, size_t max_seq_len)
+{
+    return max_seq_len ? kbo::sparse_blocks((uint64_t)n_seqs * ((max_seq_len + 15) / 16)) : kbo::kSparseMaxBlocks;
+}
+} // namespace
+
+uint32_t kbo_sparse_runs_blocks(size_t n_seqs, size_t max_seq_len)
+{
+    if (n_seqs == 0 || n_seqs >= (1ull << 31) || max_seq_len >= (1ull << 30)) return 0;
+    return sparse_dev_blocks(n_seqs, max_seq_len);
+}
+
+size_t kbo_sparse_runs_work_bytes(size_t n_seqs, uint64_t total_words)
+{
+    if (n_seqs == 0 || n_seqs >= (1ull << 31) || total_words > 0xFFFFFF00ull) return 0;
+    return sparse_prefix_bytes(n_seqs) + (kbo::kSparseScratchWords * sizeof(uint32_t) + 15) / 16 * 16;
+}
+
+int kbo_sparse_runs_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, void *d_work,
+                        kbo_aln_run *d_runs, size_t capacity, uint32_t *d_n_runs, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(d_words && d_offsets && d_work && d_n_runs && (d_runs || capacity == 0), KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < (1ull << 31), KBO_E_BAD_ARG, "1 .. 2^31-1 sequences");
+        KBO_REQUIRE(max_seq_len < (1ull << 30), KBO_E_UNSUPPORTED, "sequences of 2^30 bases or more (the records' length field has 30 bits)");
+        KBO_REQUIRE(((uintptr_t)d_work & 15) == 0 && ((uintptr_t)d_words & 3) == 0 && ((uintptr_t)d_offsets & 7) == 0 &&
+                        ((uintptr_t)d_runs & 3) == 0 && ((uintptr_t)d_n_runs & 3) == 0,
+                    KBO_E_BAD_ARG, "device buffers must be 4-byte (d_offsets 8-byte, d_work 16-byte) aligned");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        uint32_t *prefix = static_cast<uint32_t *>(d_work);
+        uint32_t *scratch = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_work) + sparse_prefix_bytes(n_seqs));
+        const uint32_t n_blocks = sparse_dev_blocks(n_seqs, max_seq_len);
+        const uint32_t cap = (uint32_t)std::min<size_t>(capacity, 0xFFFFFFFFu);
+        HIP_OK(kbo::launch_packed_prefix(d_offsets, (uint32_t)n_seqs, prefix, s));
+        HIP_OK(kbo::launch_sparse_count(d_words, d_offsets, (uint32_t)n_seqs, 0u, prefix, n_blocks, scratch, s));
+        HIP_OK(kbo::launch_sparse_emit(d_words, d_offsets, (uint32_t)n_seqs, 0u, prefix, n_blocks, scratch, 0u,
+                                       reinterpret_cast<uint32_t *>(d_runs), cap, d_n_runs, s));
+    });
+}

@@ -262,6 +262,25 @@ __global__ void scan_kernel(uint32_t *__restrict__ data, uint32_t n, uint32_t pe
     if (sums && t == nt - 1) sums[blockIdx.x] = sh[t];
 }
 
+// word w of the packed batch -> (sequence, block of 16 bases inside it).  uniform_wps != 0: every sequence has that many
+// words; otherwise binary search over the scanned word counts (prefix(e) = sums[e / kScanBlock] + data[e])
+__device__ __forceinline__ void locate_word(uint32_t w, uint32_t n_seqs, uint32_t uniform_wps, const uint32_t *data, const uint32_t *sums,
+                                            uint32_t &seq, uint32_t &blk)
+{
+    if (uniform_wps) {
+        seq = w / uniform_wps;
+        blk = w - seq * uniform_wps;
+        return;
+    }
+    uint32_t s0 = 0, s1 = n_seqs; // largest s with prefix(s) <= w
+    while (s1 - s0 > 1) {
+        const uint32_t m = s0 + (s1 - s0) / 2;
+        if (sums[m / kScanBlock] + data[m] <= w) s0 = m;
+        else s1 = m;
+    }
+    seq = s0;
+    blk = w - (sums[s0 / kScanBlock] + data[s0]);
+}
 
 } // namespace
 

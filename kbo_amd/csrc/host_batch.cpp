@@ -421,6 +421,11 @@ struct HostSlot {
     PinBuf rle_total_pin, rle_first_pin;
     size_t rle_capacity = 0, slab_id = 0, n_seqs = 0;
     uint32_t longest = 0;
+    // sparse output (kbo_matches_batch_sparse): runs per workgroup + scan, the records, their number (device word, pinned copy)
+    DevBuf sp_scratch, sp_runs, sp_total;
+    PinBuf sp_total_pin;
+    size_t sp_capacity = 0, sp_spec = 0; // records the emit has room for / the download took behind the count, unasked
+    uint32_t sp_blocks = 0;
 };
 struct HostCtx {
     int dev = 0;
@@ -452,7 +457,7 @@ struct HostCtx {
                 if (e) (void)hipEventDestroy(e);
         for (HostSlot &S : slot) { // buffers belong to `dev`
             S.B.release();
-            for (DevBuf *b : {&S.chars, &S.rle_scratch, &S.rles, &S.rle_total, &S.dt_work}) b->release();
+            for (DevBuf *b : {&S.chars, &S.rle_scratch, &S.rles, &S.rle_total, &S.dt_work, &S.sp_scratch, &S.sp_runs, &S.sp_total}) b->release();
         }
         (void)hipSetDevice(prev);
     }
@@ -574,9 +579,11 @@ struct BatchJob {
     bool in_pinned, out_pinned; // user buffers the DMA engines reach directly are used in place
     const std::vector<Slab> *slabs;
     PhaseClock *clk;     // phase timing (worker 0 only)
-    // packed mode (kbo_matches_batch_packed / kbo_find_batch_packed): 2-bit words in, 2-bit words (or run lengths) out
+    // packed mode (kbo_matches_batch_packed / kbo_find_batch_packed / kbo_matches_batch_sparse): 2-bit words in, 2-bit words (or
+    // run lengths, or the runs other than 'M') out
     const PackedBatch *packed = nullptr;
     uint32_t *packed_out = nullptr;
+    SparseSink *sparse = nullptr;
     const uint64_t *pw = nullptr;   // first word of every sequence (n_seqs + 1), nullptr when ...
     uint32_t uniform_len = 0;       // ... all sequences have this many bases
     uint64_t word_of(size_t s) const { return pw ? pw[s] : (uint64_t)s * ((uniform_len + 15u) / 16u); }
@@ -710,7 +717,7 @@ private:
         if (!job_.ms_out) { // kbo::matches / map / find: the characters' buffer first, so that the one kernel can write into it
             S.chars.ensure(((bytes + 15) / 16) * 16 + 32);
             fm.d_chars = S.chars.as<uint8_t>();
-            if (job_.packed_out && !job_.sink) { // (the words' buffer as well: the packed-native kernel writes them itself)
+            if ((job_.packed_out || job_.sparse) && !job_.sink) { // (the words' buffer as well: the packed-native kernel writes them itself)
                 S.B.packed_out.ensure((size_t)(w1 - w0) * 4 + 16);
                 fm.d_packed_out = S.B.packed_out.as<uint32_t>();
             }
@@ -773,8 +780,9 @@ private:
             // engines carry both directions at once (tools/bench_host.py: 37-40 Gbp/s host->host;
             // a small kernel storing into pinned memory, or A5/A6 storing there themselves, gave
             // 28 and 26 Gbp/s).
-            uint8_t *dst = job_.packed_out ? nullptr : job_.chars_out + sl.b0;
-            if (!job_.out_pinned && !job_.packed_out) {
+            const bool words_out = job_.packed_out || job_.sparse;
+            uint8_t *dst = words_out ? nullptr : job_.chars_out + sl.b0;
+            if (!job_.out_pinned && !words_out) {
                 S.out.ensure(bytes + 32);
                 dst = S.out.as<uint8_t>();
             }
@@ -782,13 +790,43 @@ private:
                 derand_translate_host_offsets(S.B.ms.as<uint8_t>(), S.B.off.as<uint64_t>(), off, ns, job_.k, job_.threshold,
                                               job_.format ? S.B.q.as<uint8_t>() : nullptr, S.chars.as<uint8_t>(), nullptr,
                                               st_res, mx, &S.dt_work);
-            if (job_.packed_out) { // the characters leave as 2-bit words: a quarter of the bytes
+            if (words_out) { // the characters leave as 2-bit words: a quarter of the bytes
                 const size_t nw = (size_t)(w1 - w0);
+                const uint32_t wps = job_.uniform_len ? (job_.uniform_len + 15u) / 16u : 0u;
                 S.B.packed_out.ensure(nw * 4 + 16);
                 if (!fm.packed_done)
-                    HIP_OK(kbo::launch_pack2(S.chars.as<uint8_t>(), (uint32_t)nw, S.B.off.as<uint64_t>(), (uint32_t)ns,
-                                             job_.uniform_len ? (job_.uniform_len + 15u) / 16u : 0u,
+                    HIP_OK(kbo::launch_pack2(S.chars.as<uint8_t>(), (uint32_t)nw, S.B.off.as<uint64_t>(), (uint32_t)ns, wps,
                                              job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>(), S.B.packed_out.as<uint32_t>(), st_res));
+                if (job_.sparse) { // ... or only their runs other than 'M': counted, scanned and (speculatively, into the room the
+                                   // slot has) emitted behind them, and downloaded with their number as many as the slabs before had
+                                   // (no round trip per slab); the completing thread fetches the rest, if any
+                    S.sp_scratch.ensure(kbo::kSparseScratchWords * sizeof(uint32_t));
+                    S.sp_total.ensure(16);
+                    S.sp_total_pin.ensure(16);
+                    if (S.sp_capacity < 2 * ns + 16) {
+                        S.sp_capacity = 2 * ns + 16;
+                        S.sp_runs.ensure(S.sp_capacity * sizeof(kbo_aln_run));
+                    }
+                    S.sp_blocks = kbo::sparse_blocks(nw);
+                    const uint32_t *pre = job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>();
+                    HIP_OK(kbo::launch_sparse_count(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
+                                                    S.sp_scratch.as<uint32_t>(), st_res));
+                    HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
+                                                   S.sp_scratch.as<uint32_t>(), (uint32_t)sl.s0, S.sp_runs.as<uint32_t>(),
+                                                   (uint32_t)S.sp_capacity, S.sp_total.as<uint32_t>(), st_res));
+                    HIP_OK(hipEventRecord(S.computed, st_res));
+                    HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
+                    const uint64_t per_kseq = sp_runs_per_kseq_.load(std::memory_order_relaxed); // (0: no slab finished yet)
+                    S.sp_spec = per_kseq ? std::min<size_t>(S.sp_capacity, (size_t)(ns * per_kseq / 1024 * 5 / 4) + 1024) : S.sp_capacity;
+                    S.out.ensure(S.sp_capacity * sizeof(kbo_aln_run));
+                    HIP_OK(hipMemcpyAsync(S.sp_total_pin.p, S.sp_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
+                    HIP_OK(hipMemcpyAsync(S.out.p, S.sp_runs.p, S.sp_spec * sizeof(kbo_aln_run), hipMemcpyDeviceToHost, C.st_down));
+                    HIP_OK(hipEventRecord(S.done, C.st_down));
+                    S.slab_id = slab_id;
+                    S.n_seqs = ns;
+                    S.busy = true;
+                    return;
+                }
                 HIP_OK(hipEventRecord(S.computed, st_res));
                 HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
                 uint8_t *pdst = reinterpret_cast<uint8_t *>(job_.packed_out + w0);
@@ -843,6 +881,29 @@ private:
         S.out_bytes = total; // records
     }
 
+    // sparse records: those the speculative download did not take (more runs than the slabs before had: the rest of the emitted
+    // ones; more than the emit had room for: emitted again into a larger buffer, all of them)
+    void fetch_sparse_rest(HostSlot &S, uint32_t total)
+    {
+        HostCtx &C = *C_;
+        size_t from = S.sp_spec;
+        if (total > S.sp_capacity) {
+            const uint32_t wps = job_.uniform_len ? (job_.uniform_len + 15u) / 16u : 0u;
+            S.sp_capacity = (size_t)total + total / 4 + 16;
+            S.sp_runs.ensure(S.sp_capacity * sizeof(kbo_aln_run));
+            HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)S.n_seqs, wps,
+                                           job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>(), S.sp_blocks, S.sp_scratch.as<uint32_t>(),
+                                           (uint32_t)(*job_.slabs)[S.slab_id].s0, S.sp_runs.as<uint32_t>(), (uint32_t)S.sp_capacity,
+                                           S.sp_total.as<uint32_t>(), C.st_down));
+            S.out.ensure((size_t)total * sizeof(kbo_aln_run)); // (a new buffer: everything comes again)
+            from = 0;
+        }
+        HIP_OK(hipMemcpyAsync(S.out.as<kbo_aln_run>() + from, S.sp_runs.as<kbo_aln_run>() + from, (total - from) * sizeof(kbo_aln_run),
+                              hipMemcpyDeviceToHost, C.st_down));
+        HIP_OK(hipEventRecord(S.done, C.st_down));
+        HIP_OK(hipEventSynchronize(S.done));
+    }
+
     void finish(size_t turn)
     {
         HostSlot &S = slot(turn);
@@ -855,6 +916,25 @@ private:
                     HostTeam::out().copy(job_.lo_out + S.out_b0, S.lo_pin.p, S.out_bytes * sizeof(uint32_t));
                     HostTeam::out().copy(job_.hi_out + S.out_b0, S.hi_pin.p, S.out_bytes * sizeof(uint32_t));
                 }
+            }
+        } else if (job_.sparse) {
+            SparseSink *sp = job_.sparse;
+            const uint32_t total = *S.sp_total_pin.as<uint32_t>();
+            if (total > S.sp_spec) fetch_sparse_rest(S, total);
+            sp_runs_per_kseq_.store(std::max<uint64_t>(1, (uint64_t)total * 1024 / std::max<size_t>(1, S.n_seqs)), std::memory_order_relaxed);
+            const kbo_aln_run *src = S.out.as<kbo_aln_run>();
+            if (job_.sink_direct) {
+                if (sp->all_used + total > sp->all_cap) {
+                    const size_t cap = (sp->all_used + total) * 2;
+                    kbo_aln_run *p = static_cast<kbo_aln_run *>(std::realloc(sp->all, cap * sizeof(kbo_aln_run)));
+                    if (!p) throw std::bad_alloc();
+                    sp->all = p;
+                    sp->all_cap = cap;
+                }
+                HostTeam::out().copy(sp->all + sp->all_used, src, total * sizeof(kbo_aln_run));
+                sp->all_used += total;
+            } else {
+                sp->runs[S.slab_id].assign(src, src + total);
             }
         } else if (!sink) {
             if (!job_.out_pinned) HostTeam::out().copy(job_.chars_out + S.out_b0, S.out.p, S.out_bytes);
@@ -953,6 +1033,7 @@ private:
     std::mutex mu_;
     std::condition_variable cv_;
     size_t submitted_ = 0, drained_ = 0;
+    std::atomic<uint64_t> sp_runs_per_kseq_{0}; // runs per 1024 sequences of the last sparse slab finished (sizes the next downloads)
     bool stop_ = false;
     int drain_code_ = KBO_OK;
     std::string drain_error_;
@@ -1047,9 +1128,9 @@ void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *o
 
 // kbo::matches / kbo::find over a batch of 2-bit packed reads: the same pipeline, a quarter of the bytes over PCIe each way
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink *sink)
+                               uint32_t *packed_out, RleSink *sink, SparseSink *sparse)
 {
-    KBO_REQUIRE(idx && in.words && (packed_out || sink), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(idx && in.words && (packed_out || sink || sparse), KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(in.n_exc == 0 || (in.exc_pos && in.exc_byte), KBO_E_BAD_ARG, "null exception list");
     PhaseClock clk;
     const size_t k = idx->host.k;
@@ -1064,6 +1145,7 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
     KBO_REQUIRE(scan.longest < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "sequence longer than 2^32-1");
     KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
     KBO_REQUIRE(scan.shortest > 2, KBO_E_LEN_LE_2, "len > 2 (derandomize.rs:276, translate.rs:270)");
+    KBO_REQUIRE(!sparse || scan.longest < (1ull << 30), KBO_E_UNSUPPORTED, "sequence of 2^30 bases or more (kbo_aln_run has 30 bits of length)");
     for (size_t x = 0; x < in.n_exc; x++) // (ascending, inside the batch: the slabs cut the list by binary search)
         KBO_REQUIRE(in.exc_pos[x] < offsets[n_seqs] && (x == 0 || in.exc_pos[x] > in.exc_pos[x - 1]), KBO_E_BAD_ARG,
                     "exception positions must ascend and lie inside the batch");
@@ -1087,14 +1169,15 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
     job.threshold = (uint32_t)threshold;
     job.format = false;
     job.chars_out = reinterpret_cast<uint8_t *>(packed_out); // (finish() copies bytes: the packed words of a slab)
-    job.packed_out = sink ? nullptr : packed_out;
+    job.packed_out = (sink || sparse) ? nullptr : packed_out;
     job.sink = sink;
-    job.sink_direct = sink && nd == 1;
+    job.sparse = sparse;
+    job.sink_direct = (sink || sparse) && nd == 1;
     job.packed = &in;
     job.pw = uniform ? nullptr : pw.data();
     job.uniform_len = uniform ? (uint32_t)scan.longest : 0u;
     job.in_pinned = is_pinned_host(in.words);
-    job.out_pinned = sink || is_pinned_host(packed_out);
+    job.out_pinned = sink || sparse || is_pinned_host(packed_out);
     job.slabs = &slabs;
     job.clk = &clk;
     if (sink) {
@@ -1102,7 +1185,7 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
         sink->runs32.assign(slabs.size(), {});
         sink->first.assign(slabs.size(), {});
     }
-    if (job.sink_direct && !sink->caller_owns) {
+    if (sink && job.sink_direct && !sink->caller_owns) {
         sink->all_cap = 2 * n_seqs + 1024;
         if (sink->compact) {
             sink->all32 = static_cast<uint32_t *>(std::malloc(sink->all_cap * kRleWords * sizeof(uint32_t)));
@@ -1113,7 +1196,16 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
         }
     }
     if (sink) sink->direct = job.sink_direct;
-    if (job.sink_direct) sink->rle_offsets[0] = 0;
+    if (sink && job.sink_direct) sink->rle_offsets[0] = 0;
+    if (sparse) {
+        sparse->direct = job.sink_direct;
+        sparse->runs.assign(slabs.size(), {});
+        if (job.sink_direct) { // room for 2 runs per sequence to start with (untouched pages cost nothing)
+            sparse->all_cap = 2 * n_seqs + 1024;
+            sparse->all = static_cast<kbo_aln_run *>(std::malloc(sparse->all_cap * sizeof(kbo_aln_run)));
+            if (!sparse->all) throw std::bad_alloc();
+        }
+    }
     clk.lap("slab list");
     run_on_devices(job, devices, nd);
 }

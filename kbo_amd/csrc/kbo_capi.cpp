@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
@@ -1008,6 +1009,80 @@ int kbo_find_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_
             for (size_t q = 1; q <= ns; q++) rle_offsets[slabs[i].s0 + q] = base[i] + sink.first[i][q];
         });
         *rles = reinterpret_cast<kbo_rle32 *>(all);
+    });
+}
+
+int kbo_matches_batch_sparse(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                             const uint8_t *exc_byte, size_t n_exc, double max_error_prob, kbo_aln_run **runs, uint64_t *n_runs)
+{
+    return guarded([&] {
+        KBO_REQUIRE(idx && words && runs && n_runs, KBO_E_BAD_ARG, "null argument");
+        static_assert(sizeof(kbo_aln_run) == 12, "kbo_aln_run is the device's record");
+        SparseSink sink;
+        const PackedBatch in{words, exc_pos, exc_byte, n_exc};
+        matches_batch_packed_impl(idx, in, offsets, n_seqs, max_error_prob, nullptr, nullptr, &sink);
+        if (sink.direct) { // one device: the records are already in place
+            if (!sink.all) {
+                sink.all = static_cast<kbo_aln_run *>(std::malloc(sizeof(kbo_aln_run)));
+                if (!sink.all) throw std::bad_alloc();
+            }
+            *n_runs = sink.all_used;
+            *runs = sink.all;
+            sink.all = nullptr;
+            return;
+        }
+        // several devices: slabs completed out of order and were kept per slab; put them together (seq is already the batch's)
+        std::vector<uint64_t> base(sink.runs.size() + 1, 0);
+        for (size_t i = 0; i < sink.runs.size(); i++) base[i + 1] = base[i] + sink.runs[i].size();
+        kbo_aln_run *all = static_cast<kbo_aln_run *>(std::malloc(std::max<uint64_t>(1, base.back()) * sizeof(kbo_aln_run)));
+        if (!all) throw std::bad_alloc();
+        HostTeam::get().run(sink.runs.size(), [&](size_t i) {
+            if (!sink.runs[i].empty()) std::memcpy(all + base[i], sink.runs[i].data(), sink.runs[i].size() * sizeof(kbo_aln_run));
+        });
+        *n_runs = base.back();
+        *runs = all;
+    });
+}
+
+int kbo_sparse_expand(const kbo_aln_run *runs, uint64_t n_runs, const uint64_t *offsets, size_t n_seqs, const uint8_t *ref_concat,
+                      uint8_t *out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(offsets && out && (runs || n_runs == 0), KBO_E_BAD_ARG, "null argument");
+        for (size_t s = 0; s < n_seqs; s++) KBO_REQUIRE(offsets[s + 1] >= offsets[s], KBO_E_BAD_ARG, "offsets not monotone");
+        // every record inside its sequence and behind the one before it (same sequence: at or past its end)
+        const size_t piece = 1u << 16;
+        HostTeam &team = HostTeam::get();
+        std::atomic<bool> bad{false};
+        team.run((size_t)((n_runs + piece - 1) / piece), [&](size_t t) {
+            const uint64_t a = t * piece, b = std::min<uint64_t>(n_runs, a + piece);
+            for (uint64_t r = a; r < b && !bad.load(std::memory_order_relaxed); r++) {
+                const kbo_aln_run &x = runs[r];
+                const uint64_t len = x.len_code >> 2, code = x.len_code & 3u;
+                bool ok = x.seq < n_seqs && len > 0 && code != 0 && x.start + len <= offsets[x.seq + 1] - offsets[x.seq];
+                if (ok && r > 0) {
+                    const kbo_aln_run &p = runs[r - 1];
+                    ok = p.seq < x.seq || (p.seq == x.seq && (uint64_t)p.start + (p.len_code >> 2) <= x.start);
+                }
+                if (!ok) bad.store(true, std::memory_order_relaxed);
+            }
+        });
+        KBO_REQUIRE(!bad.load(), KBO_E_BAD_ARG, "records out of (seq, start) order, overlapping, empty, of code 0 or outside their sequence");
+        // sequences in pieces; a piece's records by binary search over seq (they are in order)
+        const size_t spiece = 4096;
+        team.run((n_seqs + spiece - 1) / spiece, [&](size_t t) {
+            const size_t s0 = t * spiece, s1 = std::min(n_seqs, s0 + spiece);
+            const uint64_t b0 = offsets[s0], b1 = offsets[s1];
+            if (ref_concat) std::memcpy(out + b0, ref_concat + b0, b1 - b0); // format.rs:270-286: 'M' and 'R' take the read's base
+            else std::memset(out + b0, 'M', b1 - b0);
+            auto by_seq = [](const kbo_aln_run &x, size_t s) { return x.seq < s; };
+            const kbo_aln_run *r = std::lower_bound(runs, runs + n_runs, s0, by_seq), *e = std::lower_bound(r, runs + n_runs, s1, by_seq);
+            for (; r < e; r++) {
+                const uint32_t code = r->len_code & 3u;
+                if (ref_concat && code == 3u) continue;
+                std::memset(out + offsets[r->seq] + r->start, ref_concat ? '-' : "M-XR"[code], r->len_code >> 2);
+            }
+        });
     });
 }
 

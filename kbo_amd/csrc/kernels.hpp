@@ -438,6 +438,21 @@ hipError_t launch_exceptions(const uint64_t *d_pos, const uint8_t *d_byte, uint3
 hipError_t launch_pack2(const uint8_t *d_chars, uint32_t n_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps,
                         const uint32_t *d_scratch, uint32_t *d_packed, hipStream_t stream);
 
+// the sparse form of kbo::matches (sparse_kernels.hip): the runs of characters other than 'M' of a packed batch's character words
+// (the layout above), as kbo_aln_run records {seq_base + seq, start, (length << 2) | code} in (seq, start) order.  d_prefix: the
+// scanned words-per-sequence (launch_packed_prefix) unless uniform_wps != 0; d_scratch: kSparseScratchWords u32.  n_blocks =
+// sparse_blocks(an upper bound of the batch's words), the same for both launches; the batch itself holds < 2^32 - 256 words.
+// launch_sparse_count: runs per workgroup, scanned; launch_sparse_emit: the first `capacity` records (the others are counted
+// only) and *d_total = the number of runs; it may run again with a larger buffer behind the same count.
+constexpr uint32_t kSparseMaxBlocks = 2048;
+constexpr size_t kSparseScratchWords = kSparseMaxBlocks + 1 + 3; // counts per workgroup + 1, the scan's block sums
+uint32_t sparse_blocks(uint64_t words_bound);
+hipError_t launch_sparse_count(const uint32_t *d_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps, const uint32_t *d_prefix,
+                               uint32_t n_blocks, uint32_t *d_scratch, hipStream_t stream);
+hipError_t launch_sparse_emit(const uint32_t *d_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps, const uint32_t *d_prefix,
+                              uint32_t n_blocks, const uint32_t *d_scratch, uint32_t seq_base, uint32_t *d_runs, uint32_t capacity,
+                              uint32_t *d_total, hipStream_t stream);
+
 // a[i] = max(a[i], b[i]) over n bytes (n rounded up to 16: both buffers have that slack): the MS values of a further shard of a
 // sharded index folded into the batch's (pack_kernels.hip)
 hipError_t launch_max_bytes(uint8_t *d_a, const uint8_t *d_b, uint64_t n, hipStream_t stream);

@@ -28,26 +28,6 @@ __global__ __launch_bounds__(256) void uniform_offsets_kernel(uint64_t *__restri
     if (s <= n_seqs) off[s] = (uint64_t)s * len;
 }
 
-// word w of the packed batch -> (sequence, block of 16 bases inside it).  uniform_wps != 0: every sequence has that many
-// words; otherwise binary search over the scanned word counts (prefix(e) = sums[e / kScanBlock] + data[e])
-__device__ __forceinline__ void locate_word(uint32_t w, uint32_t n_seqs, uint32_t uniform_wps, const uint32_t *data, const uint32_t *sums,
-                                            uint32_t &seq, uint32_t &blk)
-{
-    if (uniform_wps) {
-        seq = w / uniform_wps;
-        blk = w - seq * uniform_wps;
-        return;
-    }
-    uint32_t s0 = 0, s1 = n_seqs; // largest s with prefix(s) <= w
-    while (s1 - s0 > 1) {
-        const uint32_t m = s0 + (s1 - s0) / 2;
-        if (sums[m / kScanBlock] + data[m] <= w) s0 = m;
-        else s1 = m;
-    }
-    seq = s0;
-    blk = w - (sums[s0 / kScanBlock] + data[s0]);
-}
-
 // stores bytes [lo, hi) of a 16-byte block to o + lo .. o + hi (0 <= lo <= hi <= 16)
 __device__ __forceinline__ void st_bytes(uint8_t *o, const uint4 &v, uint32_t lo, uint32_t hi)
 {

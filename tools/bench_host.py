@@ -16,7 +16,8 @@ G, R = int(os.environ.get("G", 5_000_000)), int(os.environ.get("R", 4_000_000))
 g = synth.genome(G)
 sbwt, _ = kbo_amd.build([g], kbo_amd.BuildOpts(k=31, num_threads=16))
 sbwt.to_device()
-concat, offsets = synth.reads(g, R, 150, 0.01)
+SUB = float(os.environ.get("SUB", 0.01))  # substitution rate of the reads (C2: 1 %)
+concat, offsets = synth.reads(g, R, 150, SUB)
 out = np.zeros(len(concat), dtype=np.uint8)  # allocated and touched once, outside the timed region
 L = kbo_amd.lib()
 PINNED = bool(os.environ.get("PINNED"))  # the caller's buffers in pinned memory (hipHostMalloc): used in place, no staging copies
@@ -34,7 +35,8 @@ def pinned_like(a):
 _KEEP = []
 if PINNED:
     concat, out = pinned_like(concat), pinned_like(out)
-if os.environ.get("PACKED"):  # 2-bit words in, 2-bit words / run lengths out (kbo_matches_batch_packed, kbo_find_batch_packed)
+if os.environ.get("PACKED"):  # 2-bit words in, 2-bit words / runs other than 'M' / run lengths out (kbo_matches_batch_packed,
+    # kbo_matches_batch_sparse, kbo_find_batch_packed)
     import ctypes as C
     from kbo_amd import _capi
     from oracle import binding as ora
@@ -49,8 +51,21 @@ if os.environ.get("PACKED"):  # 2-bit words in, 2-bit words / run lengths out (k
             t0 = time.perf_counter()
             kbo_amd.check(L.kbo_matches_batch_packed(sbwt._h, words.ctypes.data, offsets.ctypes.data, R, None, None, 0, 1e-7, wout.ctypes.data))
             best = min(best, time.perf_counter() - t0)
+        # slabs the library cuts the batch into, estimated: a packed slab holds up to 4x the slab size in bases (host_batch.cpp
+        # packed_slab_bytes; make_slabs cuts at sequence boundaries: for these equally long reads the count is off by one at most)
+        n_slabs = -(-R * 150 // min(4 * (slab_mb << 20), 0xC0000000))
         print(f"slab {slab_mb:4d} MiB: matches, packed {R * 150 / best / 1e9:6.2f} Gbp/s host->host ({best * 1e3:.1f} ms for {R * 150 / 1e6:.0f} Mbp, "
-              f"{len(words) * 4 / 1e6:.0f} MB each way)", flush=True)
+              f"{len(words) * 4 / 1e6:.0f} MB each way, ~{n_slabs} slabs: ~{best * 1e3 / n_slabs:.2f} ms a slab)", flush=True)
+        best = 1e9
+        n_runs = C.c_uint64(0)
+        for _ in range(5):
+            p = C.c_void_p()
+            t0 = time.perf_counter()
+            kbo_amd.check(L.kbo_matches_batch_sparse(sbwt._h, words.ctypes.data, offsets.ctypes.data, R, None, None, 0, 1e-7, C.byref(p), C.byref(n_runs)))
+            best = min(best, time.perf_counter() - t0)
+            L.kbo_free(p)
+        print(f"slab {slab_mb:4d} MiB: matches, sparse {R * 150 / best / 1e9:6.2f} Gbp/s host->host ({best * 1e3:.1f} ms, ~{n_slabs} slabs: "
+              f"~{best * 1e3 / n_slabs:.2f} ms a slab; {n_runs.value} runs, {n_runs.value * 12 / 1e6:.1f} MB back)", flush=True)
         co = _capi.FindOpts(1e-7, 0)
         ro = np.zeros(R + 1, dtype=np.uint64)
         best = 1e9
@@ -67,6 +82,10 @@ if os.environ.get("PACKED"):  # 2-bit words in, 2-bit words / run lengths out (k
     exp = oi.matches_batch(concat[:n_chk * 150], offsets[:n_chk + 1], 1e-7, n_threads=16)
     got = batch.unpack_matches(wout, offsets)
     print("packed output equals the oracle on the first", n_chk, "reads:", bool(np.array_equal(got[:n_chk * 150], exp)))
+    runs = batch.matches_batch_sparse(sbwt, words, offsets, pos, byt)
+    head = runs[runs["seq"] < n_chk]
+    print("sparse output equals the oracle on the first", n_chk, "reads:",
+          bool(np.array_equal(batch.expand_sparse(head, offsets[:n_chk + 1]), exp)), f"({len(runs)} runs in all)")
     sys.exit(0)
 for slab_mb in [int(x) for x in os.environ.get('SLABS', '32,64,128,256').split(',')]:
     L.kbo_set_slab_bytes(slab_mb << 20)
