@@ -385,7 +385,7 @@ __global__ __launch_bounds__(64) void derand_translate_piece_lds_kernel(
     int x_cur = 0, x_next = 0, a_under = 0;
     bool active = false;
     // the sequence that holds the span's first byte (wave-uniform search), then, per lane, the one that
-    // holds its piece: at most 63 sequences further on
+    // holds its piece: 63 pieces further on at most, but any number of sequences (empty ones have no piece)
     uint32_t s_first = 0;
     {
         uint32_t hi = n_seqs;
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(64) void derand_translate_piece_lds_kernel(
         }
     }
     if (it.len) {
-        uint32_t lo = s_first, hi = min(n_seqs, s_first + 64u);
+        uint32_t lo = s_first, hi = n_seqs;
         while (hi - lo > 1) {
             const uint32_t mid = lo + (hi - lo) / 2;
             if (off[mid] <= it.start) lo = mid;

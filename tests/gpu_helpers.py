@@ -105,6 +105,39 @@ def oracle_sites(ora, concat, offsets, thr):
     return {(int(b + i), int(b + j), int(r)) for b, i, j, r in zip(base, recs[:, 1], recs[:, 2], recs[:, 3])}
 
 
+RUN_CODE = np.zeros(256, dtype=np.uint8)
+RUN_CODE[ord("-")], RUN_CODE[ord("X")], RUN_CODE[ord("R")] = 1, 2, 3
+
+
+def expected_runs(chars, offsets, min_len=0):
+    """maximal runs of one character other than 'M' inside each sequence (numpy), as batch.SPARSE_DTYPE; sequences shorter than
+    min_len get none"""
+    from kbo_amd import batch
+    chars = np.asarray(chars, dtype=np.uint8)
+    off = np.asarray(offsets, dtype=np.int64)
+    n = len(chars)
+    first, last = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    lens = np.diff(off)
+    first[off[:-1][lens > 0]] = True
+    last[off[1:][lens > 0] - 1] = True
+    other = chars != ord("M")
+    prev_diff = np.ones(n, dtype=bool)
+    prev_diff[1:] = chars[1:] != chars[:-1]
+    next_diff = np.ones(n, dtype=bool)
+    next_diff[:-1] = chars[:-1] != chars[1:]
+    starts = np.nonzero(other & (first | prev_diff))[0]
+    ends = np.nonzero(other & (last | next_diff))[0]
+    assert len(starts) == len(ends)
+    seq = np.searchsorted(off, starts, side="right") - 1
+    keep = lens[seq] >= min_len
+    out = np.zeros(int(keep.sum()), dtype=batch.SPARSE_DTYPE)
+    out["seq"] = seq[keep]
+    out["start"] = (starts - off[seq])[keep]
+    out["len"] = (ends - starts + 1)[keep]
+    out["code"] = RUN_CODE[chars[starts]][keep]
+    return out
+
+
 def long_reads(rng, g, n_reads, read_len, sub_rate):
     """reads of read_len bases off g with substitutions (numpy; synth.reads is for 150 bp reads at scale)"""
     starts = rng.integers(0, len(g) - read_len, n_reads)

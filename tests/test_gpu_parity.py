@@ -953,3 +953,44 @@ def test_sharded_index_equals_the_index_of_everything(oracle, revcomp):
             with pytest.raises(kbo_amd.KboError) as e:
                 refused()
             assert e.value.code == -8  # KBO_E_UNSUPPORTED
+
+
+def test_empty_sequences_inside_a_batch_of_unknown_length(oracle):
+    """kbo_map_batch_dev with max_seq_len = 0 (the two-kernel route's piece-wise derandomize / translate kernel, 64 pieces per wave) over
+    reads of 128 bases with empty and 1- and 2-base sequences among them (kbo_hip.h: no alignment for those, every other sequence as
+    without them): the sequence of a wave's last piece lies more than 63 sequences behind its first (random configuration 32)"""
+    import torch
+    rng = np.random.default_rng(32)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    g = acgt[rng.integers(0, 4, 2000)]
+    lens = [128] * 676
+    for where, n in ((17, 1), (19, 0), (20, 0), (115, 0), (300, 0), (301, 2), (655, 2)):
+        lens.insert(where, n)
+    lens = np.asarray(lens)
+    pieces = []
+    for n in lens:
+        a = int(rng.integers(0, len(g) - n))
+        p = g[a:a + n].copy()
+        hit = rng.random(n) < 0.01
+        p[hit] = acgt[rng.integers(0, 4, int(hit.sum()))]
+        pieces.append(p)
+    concat = np.concatenate(pieces).astype(np.uint8)
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    keep = np.repeat(lens >= 3, lens)
+    kept_off = np.concatenate([[0], np.cumsum(lens[lens >= 3])]).astype(np.uint64)
+    L = kbo_amd.lib()
+    for k in (31, 76):
+        sbwt, _ = kbo_amd.build([g], kbo_amd.BuildOpts(k=k, num_threads=4))
+        oi = oracle.Index.build([g.tobytes()], k=k)
+        exp_chars, exp_d = oi.matches_batch(concat[keep], kept_off, 1e-7, n_threads=4, want_d=True)
+        for max_len in (0, 128):
+            dev = batch.DeviceBatch(sbwt, concat, offsets, device=torch.device("cuda:0"), format=False, want_ms=True)
+            dev.max_len = max_len
+            dev.work_bytes = int(L.kbo_work_bytes(dev.n_seqs, dev.total, max_len, k))
+            dev.work = torch.zeros(dev.work_bytes // 8 + 2, dtype=torch.int64, device="cuda:0")
+            dev.chars.fill_(0xEE)
+            dev.run()
+            torch.cuda.synchronize()
+            assert np.array_equal(dev.ms.cpu().numpy()[:len(concat)][keep], exp_d), (k, max_len)
+            got = dev.chars.cpu().numpy()[:len(concat)][keep]
+            assert np.array_equal(got, exp_chars), (k, max_len, np.flatnonzero(got != exp_chars)[:10])
