@@ -367,32 +367,6 @@ namespace {
 
 // The variants of a batch as they leave the library's inside: flat arrays in the order of (sequence, query position) - what
 // kbo_call_batch_flat hands out as it is and kbo_call_batch turns into the reference's records (variant_calling.rs:8-26).
-template <typename T> struct GrowBuf { // a vector whose storage can be handed to the caller (malloc / realloc; kbo_call_flat_free)
-    T *p = nullptr;
-    size_t n = 0, cap = 0;
-    GrowBuf() = default;
-    GrowBuf(const GrowBuf &) = delete;
-    GrowBuf &operator=(const GrowBuf &) = delete;
-    ~GrowBuf() { std::free(p); }
-    size_t size() const { return n; }
-    T *data() { return p; }
-    const T *data() const { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-    void reserve(size_t want)
-    {
-        if (want <= cap) return;
-        const size_t c = std::max<size_t>({want, cap + cap / 2, 1024});
-        T *q = static_cast<T *>(std::realloc(p, c * sizeof(T)));
-        if (!q) throw std::bad_alloc();
-        p = q;
-        cap = c;
-    }
-    void resize(size_t m) { reserve(m); n = m; }
-    void push_back(const T &v) { reserve(n + 1); p[n++] = v; }
-    void append(const T *a, const T *b) { reserve(n + (size_t)(b - a)); std::memcpy(p + n, a, (size_t)(b - a) * sizeof(T)); n += (size_t)(b - a); }
-    T *release() { T *q = p; p = nullptr; n = cap = 0; return q; }
-};
 struct FlatCalls {
     GrowBuf<uint32_t> pos;
     GrowBuf<uint16_t> qlen, rlen;
@@ -966,8 +940,8 @@ extern "C" int kbo_call_batch(kbo_index_t *query_idx, const uint8_t *concat, con
         // ---- the reference's records (variant_calling.rs:8-26): one allocation, the records, then the characters
         const size_t nv = fc.pos.size(), nc = fc.chars.size();
         const size_t head = std::max<size_t>(1, nv) * sizeof(kbo_variant);
-        uint8_t *mem = static_cast<uint8_t *>(std::malloc(head + nc + 1));
-        if (!mem) throw std::bad_alloc();
+        MallocPtr<uint8_t> owned = malloc_array<uint8_t>(head + nc + 1); // (the team's runs below may throw)
+        uint8_t *mem = owned.get();
         kbo_variant *rec = reinterpret_cast<kbo_variant *>(mem);
         if (nc) HostTeam::get().copy(mem + head, fc.chars.data(), nc);
         // (where a variant's characters start: a running sum, by blocks)
@@ -991,7 +965,7 @@ extern "C" int kbo_call_batch(kbo_index_t *query_idx, const uint8_t *concat, con
                 cp += ql + rl;
             }
         });
-        *out = rec;
+        *out = reinterpret_cast<kbo_variant *>(owned.release());
         clk.lap("the reference's records");
     });
 }

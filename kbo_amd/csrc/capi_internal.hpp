@@ -1,6 +1,6 @@
 // capi_internal.hpp — declarations shared by the translation units behind include/kbo_hip.h:
 //   device_index.cpp  the index handle and its per-device copies,
-//   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline, run-length sink,
+//   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline with one output stage per mode,
 //   kbo_capi.cpp      the extern "C" entry points,
 //   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
 //   build_device.cpp  kbo_index_build_device (the index built by the device).
@@ -219,41 +219,139 @@ struct OffsetScan { // one pass over the offsets of a batch: order, shortest and
     bool monotone = true;
     uint64_t shortest = ~0ull, longest = 0;
 };
-// Where kbo_find_batch collects format::run_lengths_gapped of every slab (computed on the device
-// from the slab's characters, which then never leave it)
-struct RleSink {
-    size_t max_gap_len = 0;
-    uint64_t *rle_offsets = nullptr; // caller's n_seqs + 1 entries
-    // one device: slabs complete in order, so their records go straight into the result array
-    kbo_rle *all = nullptr;
-    size_t all_cap = 0, all_used = 0;
-    bool caller_owns = false; // `all` is the caller's buffer of all_cap records: never grown; all_used keeps counting
-    bool direct = false;      // set by matches_batch_impl: one worker, records went straight into `all`
-    // compact = true (kbo_find_batch_packed): the records stay the seven u32 the device writes (kbo_rle32), nothing is
-    // widened: all32 / runs32 take the place of all / runs (all_cap and all_used count records either way)
-    bool compact = false;
-    uint32_t *all32 = nullptr;
-    std::vector<std::vector<uint32_t>> runs32;
-    // several devices: slabs complete out of order, kept per slab and put together at the end
-    std::vector<std::vector<kbo_rle>> runs;
-    std::vector<std::vector<uint32_t>> first; // index of the first run of each sequence of the slab, +1 entry
-    ~RleSink()
+constexpr size_t kRleWords = 7; // device run-length records are seven u32; kbo_rle has the reference's usize fields
+void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team);
+// how a slab's records, as the device wrote them, become the sink's: as they are, or (kbo_rle) widened
+template <typename T> void convert_records(T *dst, const void *src, size_t n, HostTeam &team) { team.copy(dst, src, n * sizeof(T)); }
+inline void convert_records(kbo_rle *dst, const void *src, size_t n, HostTeam &team)
+{
+    widen_rles(dst, static_cast<const uint32_t *>(src), n, team);
+}
+
+// Where a host batch collects the records of its slabs (kbo_rle: kbo_find_batch, kbo_find_batch_into; kbo_rle32:
+// kbo_find_batch_packed; kbo_aln_run: kbo_matches_batch_sparse), in one of two forms.
+//   direct:   one worker, slabs complete in order: records are appended to one growing array - or to the caller's buffer
+//             (use_buffer), which is never grown and never written past its capacity, while `used` keeps counting;
+//   per slab: several workers, slabs complete out of order: kept per slab and put together by take().
+template <typename T> struct RecordSink {
+    bool direct = false;
+    size_t used = 0;   // direct: records of the slabs so far
+    GrowBuf<T> all;    // direct: the library's array
+    T *fixed = nullptr; // ... or the caller's, of fixed_cap records
+    size_t fixed_cap = 0;
+    bool caller_owns = false;
+    std::vector<std::vector<T>> per_slab;
+    std::vector<uint64_t> base; // per slab, set by take(): where each slab's records start in the whole (+ the total)
+
+    void use_buffer(T *buf, size_t capacity)
     {
-        if (!caller_owns) std::free(all);
-        std::free(all32);
+        caller_owns = true;
+        fixed = buf;
+        fixed_cap = buf ? capacity : 0;
+    }
+    void begin(size_t n_slabs, size_t n_seqs, bool direct_)
+    {
+        direct = direct_;
+        used = 0;
+        if (!direct) per_slab.assign(n_slabs, {});
+        else if (!caller_owns) all.reserve(2 * n_seqs + 1024); // room for 2 runs per sequence to start with (untouched pages cost nothing)
+    }
+    // the n records of a slab; returns where they start among the batch's (direct form; the other learns it in take())
+    size_t append(size_t slab_id, const void *src, size_t n, HostTeam &team)
+    {
+        if (!direct) {
+            per_slab[slab_id].resize(n);
+            convert_records(per_slab[slab_id].data(), src, n, team);
+            return 0;
+        }
+        const size_t at = used;
+        if (caller_owns) {
+            if (at + n <= fixed_cap) convert_records(fixed + at, src, n, team); // a caller's buffer that is too small only gets the count
+        } else {
+            if (at + n > all.cap) all.reserve((at + n) * 2);
+            convert_records(all.p + at, src, n, team);
+            all.n = at + n;
+        }
+        used += n;
+        return at;
+    }
+    // The batch's records in slab order and their number.  The library's array (malloc'ed, at least one record long, the
+    // caller's to free) goes to *out; a caller's buffer stays where it is and holds the records only if all of them fit.
+    size_t take(T **out)
+    {
+        if (direct) {
+            if (!caller_owns) {
+                all.reserve(1);
+                *out = all.release();
+            }
+            return used;
+        }
+        base.assign(per_slab.size() + 1, 0);
+        for (size_t i = 0; i < per_slab.size(); i++) base[i + 1] = base[i] + per_slab[i].size();
+        const size_t total = base.back();
+        MallocPtr<T> mine;
+        if (!caller_owns) mine = malloc_array<T>(total);
+        T *dst = caller_owns ? fixed : mine.get();
+        if (!caller_owns || total <= fixed_cap)
+            HostTeam::get().run(per_slab.size(), [&](size_t i) {
+                if (!per_slab[i].empty()) std::memcpy(dst + base[i], per_slab[i].data(), per_slab[i].size() * sizeof(T));
+            });
+        if (!caller_owns) *out = mine.release();
+        return total;
     }
 };
-constexpr size_t kRleWords = 7; // device run-length records are seven u32; kbo_rle has the reference's usize fields
-// Where kbo_matches_batch_sparse collects the runs of characters other than 'M' of every slab (sparse_kernels.hip; the
-// character words never leave the device).  Records carry the sequence's index in the whole batch, so nothing is rewritten.
-struct SparseSink {
-    // one device: slabs complete in order, their records go straight into the result array
-    kbo_aln_run *all = nullptr;
-    size_t all_cap = 0, all_used = 0;
-    bool direct = false;
-    // several devices: slabs complete out of order, kept per slab and put together at the end
-    std::vector<std::vector<kbo_aln_run>> runs;
-    ~SparseSink() { std::free(all); }
+
+// Where kbo::find over a batch collects format::run_lengths_gapped of every slab (computed on the device from the slab's
+// characters, which then never leave it): the records, wide or as the device writes them, and where each sequence's begin
+template <typename T> struct RleSink {
+    size_t max_gap_len = 0;
+    uint64_t *rle_offsets = nullptr; // caller's n_seqs + 1 entries
+    RecordSink<T> records;
+    std::vector<size_t> s0;                   // first sequence of every slab (+ n_seqs)
+    std::vector<std::vector<uint32_t>> first; // per slab form: index of the first run of each sequence of the slab, +1 entry
+
+    void begin(const std::vector<Slab> &slabs, size_t n_seqs, bool direct)
+    {
+        records.begin(slabs.size(), n_seqs, direct);
+        s0.clear();
+        for (const Slab &sl : slabs) s0.push_back(sl.s0);
+        s0.push_back(n_seqs);
+        if (!direct) first.assign(slabs.size(), {});
+        rle_offsets[0] = 0;
+    }
+    // A slab's records and the device's scan of its sequences' run counts as it leaves the device: n + 1 indices within
+    // blocks of 1024 sequences, then the blocks' sums.
+    void append(size_t slab_id, const void *src, size_t n_records, const uint32_t *local, HostTeam &team)
+    {
+        const size_t ns = s0[slab_id + 1] - s0[slab_id];
+        const uint32_t *sums = local + ns + 1;
+        const size_t at = records.append(slab_id, src, n_records, team);
+        if (records.direct) {
+            set_offsets(slab_id, at, [&](size_t q) { return (uint64_t)sums[q / 1024] + local[q]; }, team);
+        } else {
+            first[slab_id].resize(ns + 1);
+            for (size_t q = 0; q <= ns; q++) first[slab_id][q] = sums[q / 1024] + local[q];
+        }
+    }
+    size_t take(T **out)
+    {
+        const size_t total = records.take(out);
+        if (!records.direct)
+            for (size_t i = 0; i < first.size(); i++)
+                set_offsets(i, records.base[i], [&](size_t q) { return (uint64_t)first[i][q]; }, HostTeam::get());
+        return total;
+    }
+
+private:
+    // rle_offsets of a slab's sequences: the slab's base + the index of the sequence's first run within the slab
+    template <typename First> void set_offsets(size_t slab_id, uint64_t slab_base, First first_run, HostTeam &team)
+    {
+        const size_t at = s0[slab_id], ns = s0[slab_id + 1] - at, piece = 1u << 15;
+        team.run((ns + piece - 1) / piece, [&](size_t t) {
+            const size_t a = t * piece + 1, b = std::min(ns, a + piece - 1);
+            for (size_t q = a; q <= b; q++) rle_offsets[at + q] = slab_base + first_run(q);
+        });
+    }
 };
 
 uint32_t max_len(const uint64_t *offsets, size_t n_seqs);
@@ -284,11 +382,6 @@ struct FusedMap {
     // wrote them there itself (its packed-native form), else the characters are in d_chars as for any batch
     uint32_t *d_packed_out = nullptr;
     bool packed_done = false;
-    // a second stream for the second pass (the plain walk of the reads the kernel leaves), so that the next slab's kernel need
-    // not wait for it, and an event to order it behind the kernel; `results` = the stream the slab's characters are complete on
-    hipStream_t tail = nullptr;
-    hipEvent_t fence = nullptr;
-    hipStream_t results = nullptr;
     // kbo::find with max_gap_len = 0: where the number of runs of every sequence goes (rle scratch, n_seqs + 1 words); counted = the
     // one kernel (and, for the reads of its second pass, derand_flagged_kernel) filled it: scan + emit are what is left
     uint32_t *run_counts = nullptr;
@@ -309,11 +402,10 @@ void derand_translate_host_offsets(const uint8_t *d_ms, const uint64_t *d_off, c
                                    uint32_t k, uint32_t threshold, const uint8_t *d_ref, uint8_t *d_chars,
                                    int32_t *d_derand, hipStream_t stream, uint32_t longest = 0,
                                    DevBuf *piece_work = nullptr /* lets long reads / contigs be split into pieces */);
-void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team);
 // kbo::matches over a batch (lib.rs:618-627); optional relative_to_ref (lib.rs:756-757); with a sink the
 // characters are turned into run lengths on the device instead of being downloaded (lib.rs:816-820)
 void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink *sink = nullptr);
+                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink = nullptr);
 // the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list; the characters come
 // back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths, or, with a sparse sink, as their runs other than 'M'
 struct PackedBatch {
@@ -323,7 +415,7 @@ struct PackedBatch {
     size_t n_exc;
 };
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink *sink = nullptr, SparseSink *sparse = nullptr);
+                               uint32_t *packed_out, RleSink<kbo_rle32> *sink = nullptr, RecordSink<kbo_aln_run> *sparse = nullptr);
 // A1 over a host batch: MS values, and intervals when lo/hi are given
 void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint8_t *d_out,
                    uint32_t *lo_out, uint32_t *hi_out);

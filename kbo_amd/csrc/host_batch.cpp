@@ -1,6 +1,6 @@
 // host_batch.cpp — host batches: work decomposition, slabs, pinned staging with helper threads, the
-// three-stage (upload / kernels / download) pipeline with pooled per-device scratch, and the
-// run-length sink of kbo_find_batch.  No compute here: kernels live in the *_kernels.hip files.
+// three-stage (upload / kernels / download) pipeline with pooled per-device scratch and one output
+// stage per mode.  No compute here: kernels live in the *_kernels.hip files.
 #include "capi_internal.hpp"
 
 #include <chrono>
@@ -186,19 +186,6 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                                       B.q.as<uint8_t>(), stream));
     };
     static const int env_native = std::getenv("KBO_PACKED_NATIVE") ? std::atoi(std::getenv("KBO_PACKED_NATIVE")) : 1; // experiments
-    // (off: beside the copies and the next slabs' kernels the pass finishes late and the downloads wait for it - 600 Mbp host to host,
-    // packed 118 -> 95 Gbp/s, bytes 39 -> 40 Gbp/s with a tail stream of the highest priority, 78 / 26 Gbp/s with an ordinary one)
-    static const int env_tail = std::getenv("KBO_HOST_TAIL") ? std::atoi(std::getenv("KBO_HOST_TAIL")) : 0; // experiments
-    // the stream the second pass of the one-kernel route goes to: the caller's tail stream behind the kernel (kbo_capi.cpp
-    // map_batch_dev_impl has the pieces' size), or the kernel's own
-    auto second_pass_stream = [&](kbo::WalkArgs &a) -> hipStream_t {
-        if (!map || !map->tail || !map->fence || !env_tail) return stream;
-        HIP_OK(hipEventRecord(map->fence, stream));
-        HIP_OK(hipStreamWaitEvent(map->tail, map->fence, 0));
-        a.redo_piece = 32u;
-        map->results = map->tail;
-        return map->tail;
-    };
     if (device_items) HIP_OK(kbo::launch_make_items(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.items.as<kbo::WalkItem>(), stream));
     for (size_t sh = 0; sh < shards.size(); sh++) {
         DevCopy::PlanState *plan_state = nullptr;
@@ -245,20 +232,19 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                 const bool count_runs = map->run_counts && !map->format && !map->d_packed_out;
                 if (count_runs) a.run_counts = map->run_counts;
                 HIP_OK(kbo::launch_map_reads(a, stream));
-                hipStream_t ts = second_pass_stream(a);
-                HIP_OK(kbo::launch_unpack_flagged(a.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, B.q.as<uint8_t>(), ts));
+                HIP_OK(kbo::launch_unpack_flagged(a.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, B.q.as<uint8_t>(), stream));
                 HIP_OK(kbo::launch_exceptions(B.exc_pos.as<uint64_t>(), B.exc_byte.as<uint8_t>(), (uint32_t)packed->n_exc, packed->base,
-                                              B.q.as<uint8_t>(), ts));
-                HIP_OK(kbo::launch_redo_pass(a, ts));
+                                              B.q.as<uint8_t>(), stream));
+                HIP_OK(kbo::launch_redo_pass(a, stream));
                 HIP_OK(kbo::launch_derand_flagged(B.ms.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, idx->host.k, map->threshold,
-                                                  map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, ts,
+                                                  map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, stream,
                                                   count_runs ? map->run_counts : nullptr));
                 if (map->d_packed_out) {
-                    HIP_OK(kbo::launch_pack_flagged(map->d_chars, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, map->d_packed_out, ts));
+                    HIP_OK(kbo::launch_pack_flagged(map->d_chars, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, map->d_packed_out, stream));
                     map->packed_done = true;
                 }
                 if (count_runs) map->counted = true;
-                plan_after_launch(a, ts, plan_state);
+                plan_after_launch(a, stream, plan_state);
                 map->done = true;
                 return;
             }
@@ -267,19 +253,18 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                 const bool count_runs = map->run_counts && !map->format && kbo::map_reads_direct(a);
                 if (count_runs) a.run_counts = map->run_counts;
                 HIP_OK(kbo::launch_map_reads(a, stream));
-                hipStream_t ts = second_pass_stream(a);
                 a.seq_off = B.off.as<uint64_t>(); // (item s is sequence s, whole: finish_reads_kernel reads the offsets)
                 if (kbo::map_reads_finish_applies(a)) {
-                    HIP_OK(kbo::launch_map_reads_finish(a, ts)); // the reads the kernel listed: walk, derandomize + translate, characters, runs
+                    HIP_OK(kbo::launch_map_reads_finish(a, stream)); // the reads the kernel listed: walk, derandomize + translate, characters, runs
                 } else {
                     a.seq_off = nullptr;
-                    HIP_OK(kbo::launch_redo_pass(a, ts));
+                    HIP_OK(kbo::launch_redo_pass(a, stream));
                     HIP_OK(kbo::launch_derand_flagged(B.ms.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, idx->host.k, map->threshold,
-                                                      map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, ts,
+                                                      map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, stream,
                                                       count_runs ? map->run_counts : nullptr)); // (the flagged reads' runs counted on the way)
                 }
                 if (count_runs) map->counted = true;
-                plan_after_launch(a, ts, plan_state);
+                plan_after_launch(a, stream, plan_state);
                 map->done = true;
                 return;
             }
@@ -412,15 +397,15 @@ struct HostSlot {
     DevBuf chars;
     PinBuf in, out, off, lo_pin, hi_pin;
     std::vector<kbo::WalkItem> items;
-    hipEvent_t copied = nullptr, computed = nullptr, done = nullptr, fence = nullptr;
+    hipEvent_t copied = nullptr, computed = nullptr, done = nullptr;
     bool busy = false;     // a slab is in flight in this slot
-    uint64_t out_b0 = 0, out_bytes = 0;
+    size_t slab_id = 0, n_seqs = 0; // which slab, its sequences ...
+    uint32_t longest = 0;           // ... and the longest of them
     // run-length output (kbo_find_batch): per-sequence first-run indices + block sums, the records,
     // the number of runs (device word and its pinned copy), what the slab holds
     DevBuf rle_scratch, rles, rle_total, dt_work;
     PinBuf rle_total_pin, rle_first_pin;
-    size_t rle_capacity = 0, slab_id = 0, n_seqs = 0;
-    uint32_t longest = 0;
+    size_t rle_capacity = 0, rle_count = 0; // records the emit has room for / the slab has (known once its kernels are done)
     // sparse output (kbo_matches_batch_sparse): runs per workgroup + scan, the records, their number (device word, pinned copy)
     DevBuf sp_scratch, sp_runs, sp_total;
     PinBuf sp_total_pin;
@@ -433,27 +418,21 @@ struct HostCtx {
     // one stream per stage, so that every stage runs one slab at a time, in order, next to the
     // other two stages: upload (copy engine), kernels, download (copy kernel)
     hipStream_t st_up = nullptr, st_run = nullptr, st_down = nullptr;
-    hipStream_t st_tail = nullptr; // the second pass of the one-kernel route: beside the next slab's kernel
     explicit HostCtx(int d) : dev(d)
     {
         for (hipStream_t *st : {&st_up, &st_run, &st_down}) HIP_OK(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-        if (std::getenv("KBO_HOST_TAIL") && std::atoi(std::getenv("KBO_HOST_TAIL")) != 0) { // (experiment: enqueue_walk_host; every stream takes part of a hardware queue)
-            int pr_lo = 0, pr_hi = 0; // (the second pass is a chain of dependent look-ups of a few waves: it goes first wherever it can)
-            HIP_OK(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-            HIP_OK(hipStreamCreateWithPriority(&st_tail, hipStreamNonBlocking, pr_hi));
-        }
         for (HostSlot &S : slot)
-            for (hipEvent_t *e : {&S.copied, &S.computed, &S.done, &S.fence}) HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            for (hipEvent_t *e : {&S.copied, &S.computed, &S.done}) HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     ~HostCtx()
     {
         int prev = 0;
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(dev);
-        for (hipStream_t st : {st_up, st_run, st_down, st_tail})
+        for (hipStream_t st : {st_up, st_run, st_down})
             if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         for (HostSlot &S : slot)
-            for (hipEvent_t e : {S.copied, S.computed, S.done, S.fence})
+            for (hipEvent_t e : {S.copied, S.computed, S.done})
                 if (e) (void)hipEventDestroy(e);
         for (HostSlot &S : slot) { // buffers belong to `dev`
             S.B.release();
@@ -489,8 +468,7 @@ struct CtxLease { // takes a context of the device out of the pool (or makes one
             S.busy = false;
         }
         if (busy)
-            for (hipStream_t st : {ctx->st_up, ctx->st_run, ctx->st_down, ctx->st_tail})
-                if (st) (void)hipStreamSynchronize(st);
+            for (hipStream_t st : {ctx->st_up, ctx->st_run, ctx->st_down}) (void)hipStreamSynchronize(st);
         // keep at most kPooledPerDevice contexts per device (each holds ~0.8 GB of device and ~0.3 GB of
         // pinned memory at the default slab size); the scratch of further concurrent callers is freed
         std::unique_lock<std::mutex> g(g_ctx_mu);
@@ -560,33 +538,49 @@ void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team)
 }
 
 
-// kbo::matches over a batch (lib.rs:618-627); optional relative_to_ref (lib.rs:756-757); with a sink
-// the characters are turned into run lengths on the device instead of being downloaded (lib.rs:816-820)
+// ---- the slab pipeline of kbo::matches / map / find / the MS values over a host batch (lib.rs:618-627; relative_to_ref
+// lib.rs:756-757; run lengths lib.rs:816-820): every slab is staged, walked, and leaves by its mode's output stage
 namespace {
+
+// what leaves the device for a slab of a host batch, and where it goes
+enum class OutMode {
+    Ms,     // kbo_ms_batch: the MS values (and the intervals, when lo / hi are given)
+    Chars,  // kbo_matches_batch, kbo_map_batch: one character per base
+    Words,  // kbo_matches_batch_packed: the characters as 2-bit words
+    Rle,    // kbo_find_batch, kbo_find_batch_into: run-length records, widened to kbo_rle
+    Rle32,  // kbo_find_batch_packed: run-length records as the device writes them
+    Sparse, // kbo_matches_batch_sparse: the runs of characters other than 'M'
+};
 
 // what a batch call hands to its per-device workers
 struct BatchJob {
+    OutMode mode;
     kbo_index *idx;
-    const uint8_t *concat;
+    const uint8_t *concat = nullptr; // nullptr for a packed batch
     const uint64_t *offsets;
-    uint32_t k, threshold;
-    bool format;         // apply format::relative_to_ref
-    uint8_t *chars_out;  // nullptr when a sink takes run lengths instead, or in ms mode
-    RleSink *sink;
-    uint8_t *ms_out = nullptr;             // ms mode: A1 only, the MS values come back ...
+    uint32_t k, threshold = 0;
+    bool format = false; // Chars: apply format::relative_to_ref
+    bool in_pinned = false, out_pinned = false; // user buffers the DMA engines reach directly are used in place
+    std::vector<Slab> slabs;
+    std::vector<int> devices;
+    size_t n_workers = 1; // one per device of the list, as far as there are slabs
+    PhaseClock *clk;      // phase timing (worker 0 only)
+    // the mode's destination
+    uint8_t *ms_out = nullptr;                     // Ms ...
     uint32_t *lo_out = nullptr, *hi_out = nullptr; // ... with the intervals when these are given
-    bool sink_direct;    // one worker: records go straight into sink->all
-    bool in_pinned, out_pinned; // user buffers the DMA engines reach directly are used in place
-    const std::vector<Slab> *slabs;
-    PhaseClock *clk;     // phase timing (worker 0 only)
-    // packed mode (kbo_matches_batch_packed / kbo_find_batch_packed / kbo_matches_batch_sparse): 2-bit words in, 2-bit words (or
-    // run lengths, or the runs other than 'M') out
+    uint8_t *chars_out = nullptr;                  // Chars
+    uint32_t *packed_out = nullptr;                // Words
+    RleSink<kbo_rle> *rle = nullptr;               // Rle
+    RleSink<kbo_rle32> *rle32 = nullptr;           // Rle32
+    RecordSink<kbo_aln_run> *sparse = nullptr;     // Sparse
+    size_t max_gap_len = 0;                        // Rle, Rle32: FindOpts' max_gap_len
+    // a packed batch (kbo_matches_batch_packed / kbo_find_batch_packed / kbo_matches_batch_sparse): 2-bit words in
     const PackedBatch *packed = nullptr;
-    uint32_t *packed_out = nullptr;
-    SparseSink *sparse = nullptr;
-    const uint64_t *pw = nullptr;   // first word of every sequence (n_seqs + 1), nullptr when ...
+    std::vector<uint64_t> pw;       // first word of every sequence (n_seqs + 1), empty when ...
     uint32_t uniform_len = 0;       // ... all sequences have this many bases
-    uint64_t word_of(size_t s) const { return pw ? pw[s] : (uint64_t)s * ((uniform_len + 15u) / 16u); }
+    uint64_t word_of(size_t s) const { return pw.empty() ? (uint64_t)s * ((uniform_len + 15u) / 16u) : pw[s]; }
+    uint32_t words_per_seq() const { return uniform_len ? (uniform_len + 15u) / 16u : 0u; }
+    bool rle_mode() const { return mode == OutMode::Rle || mode == OutMode::Rle32; }
 };
 
 // One device's share of a batch: slabs `first`, `first + stride`, ... rotate through the slots of a
@@ -616,7 +610,7 @@ public:
         };
         try {
             size_t turn = 0;
-            for (size_t i = first_; i < job_.slabs->size(); i += stride_, turn++) {
+            for (size_t i = first_; i < job_.slabs.size(); i += stride_, turn++) {
                 {
                     std::unique_lock<std::mutex> g(mu_);
                     cv_.wait(g, [&] { return turn < drained_ + kHostSlots; }); // the slot is free again
@@ -647,28 +641,57 @@ private:
     }
     HostSlot &slot(size_t turn) { return C_->slot[turn % kHostSlots]; }
 
-    // ---- submitting thread: stage the slab, enqueue upload, kernels and (characters) the download
+    // a slab as stage() leaves it: what the walk reads and what the mode's output stage needs to know of it
+    struct SlabIn {
+        const Slab *sl;
+        size_t ns;           // sequences
+        uint64_t bytes;      // bases
+        const uint64_t *off; // slab-relative offsets (pinned)
+        uint32_t longest;    // longest sequence
+        const uint8_t *src;  // the bases (the caller's pinned memory or the slot's staging copy), nullptr for a packed batch ...
+        PackedIn pin;        // ... which has this
+        uint64_t w0, n_words; // a packed batch: the slab's first word in the batch's, its number of words
+    };
+
+    // ---- submitting thread: stage the slab, enqueue upload, kernels and the mode's output stage
     void submit(size_t turn, size_t slab_id)
     {
-        const Slab &sl = (*job_.slabs)[slab_id];
         HostSlot &S = slot(turn);
-        HostCtx &C = *C_;
-        HostTeam &team = HostTeam::get();
-        const size_t ns = sl.s1 - sl.s0;
-        const uint64_t bytes = sl.b1 - sl.b0;
         S.busy = true; // from the first enqueue on: if anything below throws, ~CtxLease drains the streams before the
                        // context (and the caller's pinned buffers the copies read) can be reused
-        // stage: slab-relative offsets (and the longest sequence of the slab), query bytes
+        const SlabIn in = stage(S, slab_id);
+        lap("  offsets + copy in");
+        switch (job_.mode) {
+        case OutMode::Ms: submit_ms(S, in); break;
+        case OutMode::Chars: submit_chars(S, in); break;
+        case OutMode::Words: submit_words(S, in); break;
+        case OutMode::Rle:
+        case OutMode::Rle32: submit_rle(S, in); break;
+        case OutMode::Sparse: submit_sparse(S, in); break;
+        }
+    }
+
+    // slab-relative offsets (and the longest sequence of the slab), query bytes or words
+    SlabIn stage(HostSlot &S, size_t slab_id)
+    {
+        const Slab &sl = job_.slabs[slab_id];
+        HostTeam &team = HostTeam::get();
+        SlabIn in{};
+        in.sl = &sl;
+        in.ns = sl.s1 - sl.s0;
+        in.bytes = sl.b1 - sl.b0;
+        S.slab_id = slab_id;
+        S.n_seqs = in.ns;
+        const size_t ns = in.ns;
         S.off.ensure((ns + 1) * sizeof(uint64_t));
         uint64_t *off = S.off.as<uint64_t>();
         const uint64_t *offsets = job_.offsets;
-        uint32_t mx = 0;
         if (job_.packed && job_.uniform_len && job_.uniform_len <= 255u) { // (reads: below every chunk length, walk_chunk() >= 256)
             // equally long reads, packed: the offsets are made on the device and nothing below reads more of the host
             // copy than its last entry (one item per read, A5/A6 by the longest length)
             off[0] = 0;
-            off[ns] = bytes;
-            mx = job_.uniform_len;
+            off[ns] = in.bytes;
+            in.longest = job_.uniform_len;
         } else {
             const size_t piece = 1u << 15, n_tasks = (ns + 1 + piece - 1) / piece;
             std::vector<uint64_t> longest(n_tasks, 0);
@@ -681,14 +704,16 @@ private:
                 }
                 longest[t] = m;
             });
-            mx = (uint32_t)*std::max_element(longest.begin(), longest.end());
+            in.longest = (uint32_t)*std::max_element(longest.begin(), longest.end());
         }
-        const uint8_t *src = job_.concat ? job_.concat + sl.b0 : nullptr;
-        PackedIn pin{};
-        const uint64_t w0 = job_.packed ? job_.word_of(sl.s0) : 0, w1 = job_.packed ? job_.word_of(sl.s1) : 0;
+        in.off = off;
+        S.longest = in.longest;
         if (job_.packed) {
-            pin.words = job_.packed->words + w0;
-            pin.n_words = (size_t)(w1 - w0);
+            PackedIn &pin = in.pin;
+            in.w0 = job_.word_of(sl.s0);
+            in.n_words = job_.word_of(sl.s1) - in.w0;
+            pin.words = job_.packed->words + in.w0;
+            pin.n_words = (size_t)in.n_words;
             if (!job_.in_pinned) {
                 S.in.ensure(pin.n_words * 4 + 16);
                 team.copy(S.in.p, pin.words, pin.n_words * 4);
@@ -701,154 +726,182 @@ private:
             pin.n_exc = (size_t)(e1 - e0);
             pin.base = sl.b0;
             pin.uniform_len = job_.uniform_len;
-        } else if (!job_.in_pinned) {
-            S.in.ensure(bytes);
-            team.copy(S.in.p, src, bytes);
-            src = S.in.as<uint8_t>();
-        }
-        lap("  offsets + copy in");
-        FusedMap fm{nullptr, job_.threshold, job_.format && !job_.sink};
-        fm.tail = C.st_tail;
-        fm.fence = S.fence;
-        if (job_.sink && job_.sink->max_gap_len == 0) { // kbo::find, FindOpts' default: the one kernel counts the runs itself
-            S.rle_scratch.ensure(kbo::chunk_items_scratch_words((uint32_t)ns) * sizeof(uint32_t));
-            fm.run_counts = S.rle_scratch.as<uint32_t>();
-        }
-        if (!job_.ms_out) { // kbo::matches / map / find: the characters' buffer first, so that the one kernel can write into it
-            S.chars.ensure(((bytes + 15) / 16) * 16 + 32);
-            fm.d_chars = S.chars.as<uint8_t>();
-            if ((job_.packed_out || job_.sparse) && !job_.sink) { // (the words' buffer as well: the packed-native kernel writes them itself)
-                S.B.packed_out.ensure((size_t)(w1 - w0) * 4 + 16);
-                fm.d_packed_out = S.B.packed_out.as<uint32_t>();
-            }
-        }
-        enqueue_walk_host(job_.idx, src, off, ns, job_.lo_out != nullptr, S.B, S.items, C.st_run, mx, C.st_up, S.copied, nullptr,
-                          job_.packed ? &pin : nullptr, job_.ms_out ? nullptr : &fm);
-        // (the one-kernel route with its second pass on the tail stream: what follows the characters follows them there)
-        hipStream_t st_res = (fm.done && fm.results) ? fm.results : C.st_run;
-        if (job_.ms_out) { // A1 only: MS values (and intervals) straight back
-            HIP_OK(hipEventRecord(S.computed, C.st_run));
-            HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
-            uint8_t *dst = job_.ms_out + sl.b0;
-            uint32_t *dlo = job_.lo_out ? job_.lo_out + sl.b0 : nullptr, *dhi = job_.hi_out ? job_.hi_out + sl.b0 : nullptr;
-            if (!job_.out_pinned) {
-                S.out.ensure(bytes + 32);
-                dst = S.out.as<uint8_t>();
-                if (dlo) {
-                    S.lo_pin.ensure(bytes * sizeof(uint32_t));
-                    S.hi_pin.ensure(bytes * sizeof(uint32_t));
-                    dlo = S.lo_pin.as<uint32_t>();
-                    dhi = S.hi_pin.as<uint32_t>();
-                }
-            }
-            HIP_OK(hipMemcpyAsync(dst, S.B.ms.p, bytes, hipMemcpyDeviceToHost, C.st_down));
-            if (dlo) {
-                HIP_OK(hipMemcpyAsync(dlo, S.B.lo.p, bytes * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
-                HIP_OK(hipMemcpyAsync(dhi, S.B.hi.p, bytes * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
-            }
-            HIP_OK(hipEventRecord(S.done, C.st_down));
-        } else if (job_.sink) {
-            // characters stay on the device; run lengths are counted, scanned and (speculatively, into
-            // the room the slot has) emitted right behind A5/A6; the completing thread downloads them
-            if (!fm.done)
-                derand_translate_host_offsets(S.B.ms.as<uint8_t>(), S.B.off.as<uint64_t>(), off, ns, job_.k, job_.threshold,
-                                              nullptr, S.chars.as<uint8_t>(), nullptr, st_res, mx, &S.dt_work);
-            const uint32_t gap = (uint32_t)std::min<size_t>(job_.sink->max_gap_len, 0xFFFFFFFFu);
-            S.rle_scratch.ensure(kbo::chunk_items_scratch_words((uint32_t)ns) * sizeof(uint32_t));
-            S.rle_total.ensure(16);
-            S.rle_total_pin.ensure(16);
-            if (S.rle_capacity < 2 * ns + 16) {
-                S.rle_capacity = 2 * ns + 16;
-                S.rles.ensure(S.rle_capacity * kRleWords * sizeof(uint32_t));
-            }
-            if (fm.done && fm.counted) // (counts are there: scan + total)
-                HIP_OK(kbo::launch_rle_scan_counts((uint32_t)ns, S.rle_scratch.as<uint32_t>(), S.rle_total.as<uint32_t>(), st_res));
-            else
-                HIP_OK(kbo::launch_rle_count(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, gap,
-                                             S.rle_scratch.as<uint32_t>(), S.rle_total.as<uint32_t>(), st_res, mx, true));
-            HIP_OK(hipMemcpyAsync(S.rle_total_pin.p, S.rle_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st_res));
-            HIP_OK(kbo::launch_rle_emit(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, gap,
-                                        S.rle_scratch.as<uint32_t>(), S.rles.as<uint32_t>(), (uint32_t)S.rle_capacity,
-                                        st_res, mx, true)); // (the characters are the kernels' own: M - X R)
-            S.longest = mx;
-            HIP_OK(hipEventRecord(S.computed, st_res));
-            HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
-            S.slab_id = slab_id;
-            S.n_seqs = ns;
         } else {
-            // D2H leg: hipMemcpyAsync on the download stream.  With one stream per stage the copy
-            // engines carry both directions at once (tools/bench_host.py: 37-40 Gbp/s host->host;
-            // a small kernel storing into pinned memory, or A5/A6 storing there themselves, gave
-            // 28 and 26 Gbp/s).
-            const bool words_out = job_.packed_out || job_.sparse;
-            uint8_t *dst = words_out ? nullptr : job_.chars_out + sl.b0;
-            if (!job_.out_pinned && !words_out) {
-                S.out.ensure(bytes + 32);
-                dst = S.out.as<uint8_t>();
+            in.src = job_.concat + sl.b0;
+            if (!job_.in_pinned) {
+                S.in.ensure(in.bytes);
+                team.copy(S.in.p, in.src, in.bytes);
+                in.src = S.in.as<uint8_t>();
             }
-            if (!fm.done)
-                derand_translate_host_offsets(S.B.ms.as<uint8_t>(), S.B.off.as<uint64_t>(), off, ns, job_.k, job_.threshold,
-                                              job_.format ? S.B.q.as<uint8_t>() : nullptr, S.chars.as<uint8_t>(), nullptr,
-                                              st_res, mx, &S.dt_work);
-            if (words_out) { // the characters leave as 2-bit words: a quarter of the bytes
-                const size_t nw = (size_t)(w1 - w0);
-                const uint32_t wps = job_.uniform_len ? (job_.uniform_len + 15u) / 16u : 0u;
-                S.B.packed_out.ensure(nw * 4 + 16);
-                if (!fm.packed_done)
-                    HIP_OK(kbo::launch_pack2(S.chars.as<uint8_t>(), (uint32_t)nw, S.B.off.as<uint64_t>(), (uint32_t)ns, wps,
-                                             job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>(), S.B.packed_out.as<uint32_t>(), st_res));
-                if (job_.sparse) { // ... or only their runs other than 'M': counted, scanned and (speculatively, into the room the
-                                   // slot has) emitted behind them, and downloaded with their number as many as the slabs before had
-                                   // (no round trip per slab); the completing thread fetches the rest, if any
-                    S.sp_scratch.ensure(kbo::kSparseScratchWords * sizeof(uint32_t));
-                    S.sp_total.ensure(16);
-                    S.sp_total_pin.ensure(16);
-                    if (S.sp_capacity < 2 * ns + 16) {
-                        S.sp_capacity = 2 * ns + 16;
-                        S.sp_runs.ensure(S.sp_capacity * sizeof(kbo_aln_run));
-                    }
-                    S.sp_blocks = kbo::sparse_blocks(nw);
-                    const uint32_t *pre = job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>();
-                    HIP_OK(kbo::launch_sparse_count(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
-                                                    S.sp_scratch.as<uint32_t>(), st_res));
-                    HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
-                                                   S.sp_scratch.as<uint32_t>(), (uint32_t)sl.s0, S.sp_runs.as<uint32_t>(),
-                                                   (uint32_t)S.sp_capacity, S.sp_total.as<uint32_t>(), st_res));
-                    HIP_OK(hipEventRecord(S.computed, st_res));
-                    HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
-                    const uint64_t per_kseq = sp_runs_per_kseq_.load(std::memory_order_relaxed); // (0: no slab finished yet)
-                    S.sp_spec = per_kseq ? std::min<size_t>(S.sp_capacity, (size_t)(ns * per_kseq / 1024 * 5 / 4) + 1024) : S.sp_capacity;
-                    S.out.ensure(S.sp_capacity * sizeof(kbo_aln_run));
-                    HIP_OK(hipMemcpyAsync(S.sp_total_pin.p, S.sp_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
-                    HIP_OK(hipMemcpyAsync(S.out.p, S.sp_runs.p, S.sp_spec * sizeof(kbo_aln_run), hipMemcpyDeviceToHost, C.st_down));
-                    HIP_OK(hipEventRecord(S.done, C.st_down));
-                    S.slab_id = slab_id;
-                    S.n_seqs = ns;
-                    S.busy = true;
-                    return;
-                }
-                HIP_OK(hipEventRecord(S.computed, st_res));
-                HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
-                uint8_t *pdst = reinterpret_cast<uint8_t *>(job_.packed_out + w0);
-                if (!job_.out_pinned) {
-                    S.out.ensure(nw * 4 + 32);
-                    pdst = S.out.as<uint8_t>();
-                }
-                HIP_OK(hipMemcpyAsync(pdst, S.B.packed_out.p, nw * 4, hipMemcpyDeviceToHost, C.st_down));
-                HIP_OK(hipEventRecord(S.done, C.st_down));
-                S.busy = true;
-                S.out_b0 = w0 * 4; // (finish() copies out_bytes bytes to chars_out + out_b0: chars_out is the packed buffer here)
-                S.out_bytes = nw * 4;
-                return;
-            }
-            HIP_OK(hipEventRecord(S.computed, st_res));
-            HIP_OK(hipStreamWaitEvent(C.st_down, S.computed, 0));
-            HIP_OK(hipMemcpyAsync(dst, S.chars.p, bytes, hipMemcpyDeviceToHost, C.st_down));
-            HIP_OK(hipEventRecord(S.done, C.st_down));
         }
-        S.busy = true;
-        S.out_b0 = sl.b0;
-        S.out_bytes = bytes;
+        return in;
+    }
+
+    // upload + A1 (or, with `fm`, the one kernel where it applies) on the slot's streams
+    void walk(HostSlot &S, const SlabIn &in, FusedMap *fm)
+    {
+        enqueue_walk_host(job_.idx, in.src, in.off, in.ns, job_.lo_out != nullptr, S.B, S.items, C_->st_run, in.longest, C_->st_up,
+                          S.copied, nullptr, job_.packed ? &in.pin : nullptr, fm);
+    }
+    // kbo::matches / map / find: the characters' buffer (and, words = true, that of their 2-bit words) before the walk, so
+    // that the one kernel can write into it
+    FusedMap fused_map(HostSlot &S, const SlabIn &in, bool words)
+    {
+        FusedMap fm{nullptr, job_.threshold, job_.format};
+        S.chars.ensure(((in.bytes + 15) / 16) * 16 + 32);
+        fm.d_chars = S.chars.as<uint8_t>();
+        if (words) {
+            S.B.packed_out.ensure((size_t)in.n_words * 4 + 16);
+            fm.d_packed_out = S.B.packed_out.as<uint32_t>();
+        }
+        return fm;
+    }
+    // A5/A6 behind the walk where the one kernel has not left the characters already
+    void chars_after_walk(HostSlot &S, const SlabIn &in, const FusedMap &fm)
+    {
+        if (fm.done) return;
+        derand_translate_host_offsets(S.B.ms.as<uint8_t>(), S.B.off.as<uint64_t>(), in.off, in.ns, job_.k, job_.threshold,
+                                      job_.format ? S.B.q.as<uint8_t>() : nullptr, S.chars.as<uint8_t>(), nullptr, C_->st_run,
+                                      in.longest, &S.dt_work);
+    }
+    // ... and their 2-bit words (a quarter of the bytes) where the packed-native kernel has not written them itself
+    void words_after_walk(HostSlot &S, const SlabIn &in, const FusedMap &fm)
+    {
+        chars_after_walk(S, in, fm);
+        if (fm.packed_done) return;
+        HIP_OK(kbo::launch_pack2(S.chars.as<uint8_t>(), (uint32_t)in.n_words, S.B.off.as<uint64_t>(), (uint32_t)in.ns,
+                                 job_.words_per_seq(), job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>(),
+                                 S.B.packed_out.as<uint32_t>(), C_->st_run));
+    }
+    void download_waits_for_kernels(HostSlot &S)
+    {
+        HIP_OK(hipEventRecord(S.computed, C_->st_run));
+        HIP_OK(hipStreamWaitEvent(C_->st_down, S.computed, 0));
+    }
+
+    // A1 only: MS values (and intervals) straight back
+    void submit_ms(HostSlot &S, const SlabIn &in)
+    {
+        HostCtx &C = *C_;
+        const uint64_t bytes = in.bytes;
+        walk(S, in, nullptr);
+        download_waits_for_kernels(S);
+        uint8_t *dst = job_.ms_out + in.sl->b0;
+        uint32_t *dlo = job_.lo_out ? job_.lo_out + in.sl->b0 : nullptr, *dhi = job_.hi_out ? job_.hi_out + in.sl->b0 : nullptr;
+        if (!job_.out_pinned) {
+            S.out.ensure(bytes + 32);
+            dst = S.out.as<uint8_t>();
+            if (dlo) {
+                S.lo_pin.ensure(bytes * sizeof(uint32_t));
+                S.hi_pin.ensure(bytes * sizeof(uint32_t));
+                dlo = S.lo_pin.as<uint32_t>();
+                dhi = S.hi_pin.as<uint32_t>();
+            }
+        }
+        HIP_OK(hipMemcpyAsync(dst, S.B.ms.p, bytes, hipMemcpyDeviceToHost, C.st_down));
+        if (dlo) {
+            HIP_OK(hipMemcpyAsync(dlo, S.B.lo.p, bytes * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
+            HIP_OK(hipMemcpyAsync(dhi, S.B.hi.p, bytes * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
+        }
+        HIP_OK(hipEventRecord(S.done, C.st_down));
+    }
+
+    // one character per base.  D2H leg: hipMemcpyAsync on the download stream.  With one stream per stage the copy
+    // engines carry both directions at once (tools/bench_host.py: 37-40 Gbp/s host->host; a small kernel storing
+    // into pinned memory, or A5/A6 storing there themselves, gave 28 and 26 Gbp/s).
+    void submit_chars(HostSlot &S, const SlabIn &in)
+    {
+        FusedMap fm = fused_map(S, in, false);
+        walk(S, in, &fm);
+        uint8_t *dst = job_.chars_out + in.sl->b0;
+        if (!job_.out_pinned) {
+            S.out.ensure(in.bytes + 32);
+            dst = S.out.as<uint8_t>();
+        }
+        chars_after_walk(S, in, fm);
+        download_waits_for_kernels(S);
+        HIP_OK(hipMemcpyAsync(dst, S.chars.p, in.bytes, hipMemcpyDeviceToHost, C_->st_down));
+        HIP_OK(hipEventRecord(S.done, C_->st_down));
+    }
+
+    // the characters as 2-bit words
+    void submit_words(HostSlot &S, const SlabIn &in)
+    {
+        FusedMap fm = fused_map(S, in, true);
+        walk(S, in, &fm);
+        words_after_walk(S, in, fm);
+        download_waits_for_kernels(S);
+        uint32_t *dst = job_.packed_out + in.w0;
+        if (!job_.out_pinned) {
+            S.out.ensure((size_t)in.n_words * 4 + 32);
+            dst = S.out.as<uint32_t>();
+        }
+        HIP_OK(hipMemcpyAsync(dst, S.B.packed_out.p, (size_t)in.n_words * 4, hipMemcpyDeviceToHost, C_->st_down));
+        HIP_OK(hipEventRecord(S.done, C_->st_down));
+    }
+
+    // run lengths: the characters stay on the device; their runs are counted, scanned and (speculatively, into
+    // the room the slot has) emitted right behind A5/A6; the completing thread downloads them (start_download)
+    void submit_rle(HostSlot &S, const SlabIn &in)
+    {
+        hipStream_t st = C_->st_run;
+        const size_t ns = in.ns;
+        const uint32_t gap = (uint32_t)std::min<size_t>(job_.max_gap_len, 0xFFFFFFFFu);
+        FusedMap fm = fused_map(S, in, false);
+        S.rle_scratch.ensure(kbo::chunk_items_scratch_words((uint32_t)ns) * sizeof(uint32_t));
+        if (job_.max_gap_len == 0) fm.run_counts = S.rle_scratch.as<uint32_t>(); // FindOpts' default: the one kernel counts the runs itself
+        walk(S, in, &fm);
+        chars_after_walk(S, in, fm);
+        S.rle_total.ensure(16);
+        S.rle_total_pin.ensure(16);
+        if (S.rle_capacity < 2 * ns + 16) {
+            S.rle_capacity = 2 * ns + 16;
+            S.rles.ensure(S.rle_capacity * kRleWords * sizeof(uint32_t));
+        }
+        if (fm.done && fm.counted) // (counts are there: scan + total)
+            HIP_OK(kbo::launch_rle_scan_counts((uint32_t)ns, S.rle_scratch.as<uint32_t>(), S.rle_total.as<uint32_t>(), st));
+        else
+            HIP_OK(kbo::launch_rle_count(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, gap,
+                                         S.rle_scratch.as<uint32_t>(), S.rle_total.as<uint32_t>(), st, in.longest, true));
+        HIP_OK(hipMemcpyAsync(S.rle_total_pin.p, S.rle_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(kbo::launch_rle_emit(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, gap,
+                                    S.rle_scratch.as<uint32_t>(), S.rles.as<uint32_t>(), (uint32_t)S.rle_capacity,
+                                    st, in.longest, true)); // (the characters are the kernels' own: M - X R)
+        download_waits_for_kernels(S);
+    }
+
+    // only the runs of characters other than 'M': counted, scanned and (speculatively, into the room the slot has) emitted
+    // behind the words, and downloaded with their number as many as the slabs before had (no round trip per slab); the
+    // completing thread fetches the rest, if any (fetch_sparse_rest)
+    void submit_sparse(HostSlot &S, const SlabIn &in)
+    {
+        HostCtx &C = *C_;
+        const size_t ns = in.ns;
+        FusedMap fm = fused_map(S, in, true);
+        walk(S, in, &fm);
+        words_after_walk(S, in, fm);
+        S.sp_scratch.ensure(kbo::kSparseScratchWords * sizeof(uint32_t));
+        S.sp_total.ensure(16);
+        S.sp_total_pin.ensure(16);
+        if (S.sp_capacity < 2 * ns + 16) {
+            S.sp_capacity = 2 * ns + 16;
+            S.sp_runs.ensure(S.sp_capacity * sizeof(kbo_aln_run));
+        }
+        S.sp_blocks = kbo::sparse_blocks((size_t)in.n_words);
+        const uint32_t wps = job_.words_per_seq();
+        const uint32_t *pre = job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>();
+        HIP_OK(kbo::launch_sparse_count(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
+                                        S.sp_scratch.as<uint32_t>(), C.st_run));
+        HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)ns, wps, pre, S.sp_blocks,
+                                       S.sp_scratch.as<uint32_t>(), (uint32_t)in.sl->s0, S.sp_runs.as<uint32_t>(),
+                                       (uint32_t)S.sp_capacity, S.sp_total.as<uint32_t>(), C.st_run));
+        download_waits_for_kernels(S);
+        const uint64_t per_kseq = sp_runs_per_kseq_.load(std::memory_order_relaxed); // (0: no slab finished yet)
+        S.sp_spec = per_kseq ? std::min<size_t>(S.sp_capacity, (size_t)(ns * per_kseq / 1024 * 5 / 4) + 1024) : S.sp_capacity;
+        S.out.ensure(S.sp_capacity * sizeof(kbo_aln_run));
+        HIP_OK(hipMemcpyAsync(S.sp_total_pin.p, S.sp_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
+        HIP_OK(hipMemcpyAsync(S.out.p, S.sp_runs.p, S.sp_spec * sizeof(kbo_aln_run), hipMemcpyDeviceToHost, C.st_down));
+        HIP_OK(hipEventRecord(S.done, C.st_down));
     }
 
     // ---- completing thread
@@ -857,7 +910,6 @@ private:
     // copy engine and the host copy work on different slabs
     void start_download(size_t turn)
     {
-        if (!job_.sink) return;
         HostSlot &S = slot(turn);
         HostCtx &C = *C_;
         HIP_OK(hipEventSynchronize(S.computed));
@@ -866,7 +918,7 @@ private:
             S.rle_capacity = (size_t)total + total / 4 + 16;
             S.rles.ensure(S.rle_capacity * kRleWords * sizeof(uint32_t));
             HIP_OK(kbo::launch_rle_emit(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)S.n_seqs,
-                                        (uint32_t)std::min<size_t>(job_.sink->max_gap_len, 0xFFFFFFFFu),
+                                        (uint32_t)std::min<size_t>(job_.max_gap_len, 0xFFFFFFFFu),
                                         S.rle_scratch.as<uint32_t>(), S.rles.as<uint32_t>(), (uint32_t)S.rle_capacity,
                                         C.st_down, S.longest, true));
         }
@@ -878,7 +930,7 @@ private:
                                   C.st_down));
         HIP_OK(hipMemcpyAsync(S.rle_first_pin.p, S.rle_scratch.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st_down));
         HIP_OK(hipEventRecord(S.done, C.st_down));
-        S.out_bytes = total; // records
+        S.rle_count = total;
     }
 
     // sparse records: those the speculative download did not take (more runs than the slabs before had: the rest of the emitted
@@ -888,12 +940,11 @@ private:
         HostCtx &C = *C_;
         size_t from = S.sp_spec;
         if (total > S.sp_capacity) {
-            const uint32_t wps = job_.uniform_len ? (job_.uniform_len + 15u) / 16u : 0u;
             S.sp_capacity = (size_t)total + total / 4 + 16;
             S.sp_runs.ensure(S.sp_capacity * sizeof(kbo_aln_run));
-            HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)S.n_seqs, wps,
+            HIP_OK(kbo::launch_sparse_emit(S.B.packed_out.as<uint32_t>(), S.B.off.as<uint64_t>(), (uint32_t)S.n_seqs, job_.words_per_seq(),
                                            job_.uniform_len ? nullptr : S.B.pscr.as<uint32_t>(), S.sp_blocks, S.sp_scratch.as<uint32_t>(),
-                                           (uint32_t)(*job_.slabs)[S.slab_id].s0, S.sp_runs.as<uint32_t>(), (uint32_t)S.sp_capacity,
+                                           (uint32_t)job_.slabs[S.slab_id].s0, S.sp_runs.as<uint32_t>(), (uint32_t)S.sp_capacity,
                                            S.sp_total.as<uint32_t>(), C.st_down));
             S.out.ensure((size_t)total * sizeof(kbo_aln_run)); // (a new buffer: everything comes again)
             from = 0;
@@ -907,77 +958,14 @@ private:
     void finish(size_t turn)
     {
         HostSlot &S = slot(turn);
-        RleSink *sink = job_.sink;
         HIP_OK(hipEventSynchronize(S.done));
-        if (job_.ms_out) {
-            if (!job_.out_pinned) {
-                HostTeam::out().copy(job_.ms_out + S.out_b0, S.out.p, S.out_bytes);
-                if (job_.lo_out) {
-                    HostTeam::out().copy(job_.lo_out + S.out_b0, S.lo_pin.p, S.out_bytes * sizeof(uint32_t));
-                    HostTeam::out().copy(job_.hi_out + S.out_b0, S.hi_pin.p, S.out_bytes * sizeof(uint32_t));
-                }
-            }
-        } else if (job_.sparse) {
-            SparseSink *sp = job_.sparse;
-            const uint32_t total = *S.sp_total_pin.as<uint32_t>();
-            if (total > S.sp_spec) fetch_sparse_rest(S, total);
-            sp_runs_per_kseq_.store(std::max<uint64_t>(1, (uint64_t)total * 1024 / std::max<size_t>(1, S.n_seqs)), std::memory_order_relaxed);
-            const kbo_aln_run *src = S.out.as<kbo_aln_run>();
-            if (job_.sink_direct) {
-                if (sp->all_used + total > sp->all_cap) {
-                    const size_t cap = (sp->all_used + total) * 2;
-                    kbo_aln_run *p = static_cast<kbo_aln_run *>(std::realloc(sp->all, cap * sizeof(kbo_aln_run)));
-                    if (!p) throw std::bad_alloc();
-                    sp->all = p;
-                    sp->all_cap = cap;
-                }
-                HostTeam::out().copy(sp->all + sp->all_used, src, total * sizeof(kbo_aln_run));
-                sp->all_used += total;
-            } else {
-                sp->runs[S.slab_id].assign(src, src + total);
-            }
-        } else if (!sink) {
-            if (!job_.out_pinned) HostTeam::out().copy(job_.chars_out + S.out_b0, S.out.p, S.out_bytes);
-        } else {
-            const size_t total = S.out_bytes;
-            const uint32_t *local = S.rle_first_pin.as<uint32_t>(), *sums = local + S.n_seqs + 1;
-            if (job_.sink_direct) {
-                if (sink->all_used + total > sink->all_cap && !sink->caller_owns) {
-                    const size_t cap = (sink->all_used + total) * 2;
-                    if (sink->compact) {
-                        uint32_t *p = static_cast<uint32_t *>(std::realloc(sink->all32, cap * kRleWords * sizeof(uint32_t)));
-                        if (!p) throw std::bad_alloc();
-                        sink->all32 = p;
-                    } else {
-                        kbo_rle *p = static_cast<kbo_rle *>(std::realloc(sink->all, cap * sizeof(kbo_rle)));
-                        if (!p) throw std::bad_alloc();
-                        sink->all = p;
-                    }
-                    sink->all_cap = cap;
-                }
-                const size_t base = sink->all_used, s0 = (*job_.slabs)[S.slab_id].s0, ns_slab = S.n_seqs;
-                if (sink->compact) // the device's records as they are
-                    HostTeam::out().copy(sink->all32 + base * kRleWords, S.out.p, total * kRleWords * sizeof(uint32_t));
-                else if (base + total <= sink->all_cap) // a caller's buffer that is too small only gets the count
-                    widen_rles(sink->all + base, S.out.as<uint32_t>(), total, HostTeam::out());
-                const size_t piece = 1u << 15;
-                HostTeam::out().run((ns_slab + piece - 1) / piece, [&](size_t t) {
-                    const size_t a = t * piece + 1, b = std::min(ns_slab, a + piece - 1);
-                    for (size_t q = a; q <= b; q++) sink->rle_offsets[s0 + q] = base + sums[q / 1024] + local[q];
-                });
-                sink->all_used += total;
-            } else {
-                if (sink->compact) {
-                    sink->runs32[S.slab_id].assign(S.out.as<uint32_t>(), S.out.as<uint32_t>() + total * kRleWords);
-                } else {
-                    std::vector<kbo_rle> &runs = sink->runs[S.slab_id];
-                    runs.resize(total);
-                    widen_rles(runs.data(), S.out.as<uint32_t>(), total, HostTeam::out());
-                }
-                std::vector<uint32_t> &first = sink->first[S.slab_id];
-                first.resize(S.n_seqs + 1);
-                for (size_t q = 0; q <= S.n_seqs; q++) first[q] = sums[q / 1024] + local[q];
-            }
+        switch (job_.mode) {
+        case OutMode::Ms: finish_ms(S); break;
+        case OutMode::Chars: finish_chars(S); break;
+        case OutMode::Words: finish_words(S); break;
+        case OutMode::Rle: finish_rle(S, *job_.rle); break;
+        case OutMode::Rle32: finish_rle(S, *job_.rle32); break;
+        case OutMode::Sparse: finish_sparse(S); break;
         }
         S.busy = false;
         {
@@ -985,6 +973,41 @@ private:
             drained_++;
         }
         cv_.notify_all();
+    }
+
+    // (the first three: a pinned destination took the download itself; otherwise the staged output is copied out)
+    void finish_ms(HostSlot &S)
+    {
+        if (job_.out_pinned) return;
+        const Slab &sl = job_.slabs[S.slab_id];
+        const uint64_t bytes = sl.b1 - sl.b0;
+        HostTeam::out().copy(job_.ms_out + sl.b0, S.out.p, bytes);
+        if (job_.lo_out) {
+            HostTeam::out().copy(job_.lo_out + sl.b0, S.lo_pin.p, bytes * sizeof(uint32_t));
+            HostTeam::out().copy(job_.hi_out + sl.b0, S.hi_pin.p, bytes * sizeof(uint32_t));
+        }
+    }
+    void finish_chars(HostSlot &S)
+    {
+        const Slab &sl = job_.slabs[S.slab_id];
+        if (!job_.out_pinned) HostTeam::out().copy(job_.chars_out + sl.b0, S.out.p, sl.b1 - sl.b0);
+    }
+    void finish_words(HostSlot &S)
+    {
+        const Slab &sl = job_.slabs[S.slab_id];
+        const uint64_t w0 = job_.word_of(sl.s0), w1 = job_.word_of(sl.s1);
+        if (!job_.out_pinned) HostTeam::out().copy(job_.packed_out + w0, S.out.p, (size_t)(w1 - w0) * 4);
+    }
+    template <typename T> void finish_rle(HostSlot &S, RleSink<T> &sink)
+    {
+        sink.append(S.slab_id, S.out.p, S.rle_count, S.rle_first_pin.as<uint32_t>(), HostTeam::out());
+    }
+    void finish_sparse(HostSlot &S)
+    {
+        const uint32_t total = *S.sp_total_pin.as<uint32_t>();
+        if (total > S.sp_spec) fetch_sparse_rest(S, total);
+        sp_runs_per_kseq_.store(std::max<uint64_t>(1, (uint64_t)total * 1024 / std::max<size_t>(1, S.n_seqs)), std::memory_order_relaxed);
+        job_.sparse->append(S.slab_id, S.out.p, total, HostTeam::out());
     }
 
     void drain_loop()
@@ -1011,7 +1034,7 @@ private:
                 const size_t prev = pending;
                 pending = none;
                 if (can_start) {
-                    start_download(started);
+                    if (job_.rle_mode()) start_download(started);
                     pending = started++;
                 }
                 if (prev != none) finish(prev);
@@ -1041,15 +1064,16 @@ private:
 
 // one worker per device (index replicated on each, slabs dealt round-robin, disjoint output slices: no
 // exchange between devices); a single device runs on the calling thread
-void run_on_devices(const BatchJob &job, const std::vector<int> &devices, size_t nd)
+void run_on_devices(const BatchJob &job)
 {
+    const size_t nd = job.n_workers;
     if (nd == 1) {
         const int prev = current_device();
         struct Restore { // also when run() throws
             int prev, used;
             ~Restore() { if (prev != used) (void)hipSetDevice(prev); }
-        } restore{prev, devices[0]};
-        SlabWorker(job, devices[0], 0, 1, true).run();
+        } restore{prev, job.devices[0]};
+        SlabWorker(job, job.devices[0], 0, 1, true).run();
         return;
     }
     std::vector<std::thread> threads;
@@ -1058,7 +1082,7 @@ void run_on_devices(const BatchJob &job, const std::vector<int> &devices, size_t
     for (size_t w = 0; w < nd; w++)
         threads.emplace_back([&, w] {
             try {
-                SlabWorker(job, devices[w], w, nd, w == 0).run();
+                SlabWorker(job, job.devices[w], w, nd, w == 0).run();
             } catch (const KboError &e) {
                 codes[w] = e.code;
                 errors[w] = e.what();
@@ -1072,16 +1096,12 @@ void run_on_devices(const BatchJob &job, const std::vector<int> &devices, size_t
         if (codes[w] != KBO_OK) throw KboError(codes[w], errors[w]);
 }
 
-} // namespace
-
-void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink *sink)
+// The checks the host batch entry points share, in the order the tests pin (which error a doubly wrong call gets), and the
+// scan of the offsets they are made from.  matches = true: + what derandomize / translate assert (kbo::matches, map, find).
+// (k > 0 cannot fire, for the byte forms no more than for the packed ones: random_match_threshold has refused k = 0 before,
+// and no handle has it - kbo_index_from_parts, the builders and the loader all refuse it; it stays as the reference's assert.)
+OffsetScan checked_scan(const uint64_t *offsets, size_t n_seqs, bool matches, size_t k = 0, size_t threshold = 0)
 {
-    KBO_REQUIRE(idx && (chars_out || sink), KBO_E_BAD_ARG, "null argument");
-    PhaseClock clk;
-    const size_t k = idx->host.k;
-    const size_t threshold = random_match_threshold(k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
-    KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
     KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "no sequences");
     KBO_REQUIRE(n_seqs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 sequences per call");
     KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] must be 0");
@@ -1089,125 +1109,97 @@ void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *o
     KBO_REQUIRE(scan.monotone, KBO_E_BAD_ARG, "offsets not monotone");
     KBO_REQUIRE(scan.shortest > 0, KBO_E_EMPTY_QUERY, "empty query (index.rs:248 assert!(!query.is_empty()))");
     KBO_REQUIRE(scan.longest < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "sequence longer than 2^32-1");
+    if (!matches) return scan;
     KBO_REQUIRE(k > 0, KBO_E_BAD_ARG, "k > 0 (derandomize.rs:274)");
     KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
     KBO_REQUIRE(scan.shortest > 2, KBO_E_LEN_LE_2, "len > 2 (derandomize.rs:276, translate.rs:270)");
-    clk.lap("argument checks");
-    const std::vector<Slab> slabs = make_slabs(offsets, n_seqs, slab_bytes_for(idx));
-    std::vector<int> devices = devices_for(idx);
-    if (devices.empty()) devices.push_back(current_device());
-    const size_t nd = std::min(devices.size(), std::max<size_t>(1, slabs.size()));
+    return scan;
+}
+
+// the slab list, the devices and their workers, and what else of a job does not depend on its mode
+BatchJob make_job(OutMode mode, kbo_index *idx, const uint64_t *offsets, size_t n_seqs, size_t slab_bytes, size_t threshold,
+                  PhaseClock &clk)
+{
     BatchJob job;
+    job.mode = mode;
     job.idx = idx;
-    job.concat = concat;
     job.offsets = offsets;
-    job.k = (uint32_t)k;
+    job.k = idx->host.k;
     job.threshold = (uint32_t)threshold;
-    job.format = format;
-    job.chars_out = chars_out;
-    job.sink = sink;
-    job.sink_direct = sink && nd == 1;
-    job.in_pinned = is_pinned_host(concat);
-    job.out_pinned = sink || is_pinned_host(chars_out);
-    job.slabs = &slabs;
+    job.slabs = make_slabs(offsets, n_seqs, slab_bytes);
+    job.devices = devices_for(idx);
+    if (job.devices.empty()) job.devices.push_back(current_device());
+    job.n_workers = std::min(job.devices.size(), std::max<size_t>(1, job.slabs.size()));
     job.clk = &clk;
+    return job;
+}
+
+} // namespace
+
+void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink)
+{
+    KBO_REQUIRE(idx && (chars_out || sink), KBO_E_BAD_ARG, "null argument");
+    PhaseClock clk;
+    const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
+    KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
+    checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
+    clk.lap("argument checks");
+    BatchJob job = make_job(sink ? OutMode::Rle : OutMode::Chars, idx, offsets, n_seqs, slab_bytes_for(idx), threshold, clk);
+    job.concat = concat;
+    job.in_pinned = is_pinned_host(concat);
     if (sink) {
-        sink->runs.assign(slabs.size(), {});
-        sink->first.assign(slabs.size(), {});
+        job.rle = sink;
+        job.max_gap_len = sink->max_gap_len;
+        sink->begin(job.slabs, n_seqs, job.n_workers == 1);
+    } else {
+        job.format = format;
+        job.chars_out = chars_out;
+        job.out_pinned = is_pinned_host(chars_out);
     }
-    if (job.sink_direct && !sink->caller_owns) { // room for 2 runs per sequence to start with (untouched pages cost nothing)
-        sink->all_cap = 2 * n_seqs + 1024;
-        sink->all = static_cast<kbo_rle *>(std::malloc(sink->all_cap * sizeof(kbo_rle)));
-        if (!sink->all) throw std::bad_alloc();
-    }
-    if (sink) sink->direct = job.sink_direct;
-    if (job.sink_direct) sink->rle_offsets[0] = 0;
     clk.lap("slab list");
-    run_on_devices(job, devices, nd);
+    run_on_devices(job);
 }
 
 // kbo::matches / kbo::find over a batch of 2-bit packed reads: the same pipeline, a quarter of the bytes over PCIe each way
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink *sink, SparseSink *sparse)
+                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse)
 {
     KBO_REQUIRE(idx && in.words && (packed_out || sink || sparse), KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(in.n_exc == 0 || (in.exc_pos && in.exc_byte), KBO_E_BAD_ARG, "null exception list");
     PhaseClock clk;
-    const size_t k = idx->host.k;
-    const size_t threshold = random_match_threshold(k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
+    const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
     KBO_REQUIRE(offsets, KBO_E_BAD_ARG, "null offsets");
-    KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "no sequences");
-    KBO_REQUIRE(n_seqs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 sequences per call");
-    KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] must be 0");
-    const OffsetScan scan = scan_offsets(offsets, n_seqs);
-    KBO_REQUIRE(scan.monotone, KBO_E_BAD_ARG, "offsets not monotone");
-    KBO_REQUIRE(scan.shortest > 0, KBO_E_EMPTY_QUERY, "empty query (index.rs:248 assert!(!query.is_empty()))");
-    KBO_REQUIRE(scan.longest < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "sequence longer than 2^32-1");
-    KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
-    KBO_REQUIRE(scan.shortest > 2, KBO_E_LEN_LE_2, "len > 2 (derandomize.rs:276, translate.rs:270)");
+    const OffsetScan scan = checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
     KBO_REQUIRE(!sparse || scan.longest < (1ull << 30), KBO_E_UNSUPPORTED, "sequence of 2^30 bases or more (kbo_aln_run has 30 bits of length)");
     for (size_t x = 0; x < in.n_exc; x++) // (ascending, inside the batch: the slabs cut the list by binary search)
         KBO_REQUIRE(in.exc_pos[x] < offsets[n_seqs] && (x == 0 || in.exc_pos[x] > in.exc_pos[x - 1]), KBO_E_BAD_ARG,
                     "exception positions must ascend and lie inside the batch");
     clk.lap("argument checks");
-    const std::vector<Slab> slabs = make_slabs(offsets, n_seqs, packed_slab_bytes(idx));
-    std::vector<int> devices = devices_for(idx);
-    if (devices.empty()) devices.push_back(current_device());
-    const size_t nd = std::min(devices.size(), std::max<size_t>(1, slabs.size()));
-    std::vector<uint64_t> pw;
-    const bool uniform = scan.shortest == scan.longest;
-    if (!uniform) { // first word of every sequence
-        pw.resize(n_seqs + 1);
-        pw[0] = 0;
-        for (size_t s = 0; s < n_seqs; s++) pw[s + 1] = pw[s] + (offsets[s + 1] - offsets[s] + 15) / 16;
-    }
-    BatchJob job;
-    job.idx = idx;
-    job.concat = nullptr;
-    job.offsets = offsets;
-    job.k = (uint32_t)k;
-    job.threshold = (uint32_t)threshold;
-    job.format = false;
-    job.chars_out = reinterpret_cast<uint8_t *>(packed_out); // (finish() copies bytes: the packed words of a slab)
-    job.packed_out = (sink || sparse) ? nullptr : packed_out;
-    job.sink = sink;
-    job.sparse = sparse;
-    job.sink_direct = (sink || sparse) && nd == 1;
+    const OutMode mode = sink ? OutMode::Rle32 : sparse ? OutMode::Sparse : OutMode::Words;
+    BatchJob job = make_job(mode, idx, offsets, n_seqs, packed_slab_bytes(idx), threshold, clk);
     job.packed = &in;
-    job.pw = uniform ? nullptr : pw.data();
-    job.uniform_len = uniform ? (uint32_t)scan.longest : 0u;
     job.in_pinned = is_pinned_host(in.words);
-    job.out_pinned = sink || sparse || is_pinned_host(packed_out);
-    job.slabs = &slabs;
-    job.clk = &clk;
+    if (scan.shortest == scan.longest) {
+        job.uniform_len = (uint32_t)scan.longest;
+    } else { // first word of every sequence
+        job.pw.resize(n_seqs + 1);
+        job.pw[0] = 0;
+        for (size_t s = 0; s < n_seqs; s++) job.pw[s + 1] = job.pw[s] + (offsets[s + 1] - offsets[s] + 15) / 16;
+    }
     if (sink) {
-        sink->runs.assign(slabs.size(), {});
-        sink->runs32.assign(slabs.size(), {});
-        sink->first.assign(slabs.size(), {});
-    }
-    if (sink && job.sink_direct && !sink->caller_owns) {
-        sink->all_cap = 2 * n_seqs + 1024;
-        if (sink->compact) {
-            sink->all32 = static_cast<uint32_t *>(std::malloc(sink->all_cap * kRleWords * sizeof(uint32_t)));
-            if (!sink->all32) throw std::bad_alloc();
-        } else {
-            sink->all = static_cast<kbo_rle *>(std::malloc(sink->all_cap * sizeof(kbo_rle)));
-            if (!sink->all) throw std::bad_alloc();
-        }
-    }
-    if (sink) sink->direct = job.sink_direct;
-    if (sink && job.sink_direct) sink->rle_offsets[0] = 0;
-    if (sparse) {
-        sparse->direct = job.sink_direct;
-        sparse->runs.assign(slabs.size(), {});
-        if (job.sink_direct) { // room for 2 runs per sequence to start with (untouched pages cost nothing)
-            sparse->all_cap = 2 * n_seqs + 1024;
-            sparse->all = static_cast<kbo_aln_run *>(std::malloc(sparse->all_cap * sizeof(kbo_aln_run)));
-            if (!sparse->all) throw std::bad_alloc();
-        }
+        job.rle32 = sink;
+        job.max_gap_len = sink->max_gap_len;
+        sink->begin(job.slabs, n_seqs, job.n_workers == 1);
+    } else if (sparse) {
+        job.sparse = sparse;
+        sparse->begin(job.slabs.size(), n_seqs, job.n_workers == 1);
+    } else {
+        job.packed_out = packed_out;
+        job.out_pinned = is_pinned_host(packed_out);
     }
     clk.lap("slab list");
-    run_on_devices(job, devices, nd);
+    run_on_devices(job);
 }
 
 // A1 over a host batch: MS values (and intervals) only
@@ -1217,37 +1209,18 @@ void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offset
     KBO_REQUIRE(idx && d_out, KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE((lo_out == nullptr) == (hi_out == nullptr), KBO_E_BAD_ARG, "lo/hi must come together");
     KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
-    KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "no sequences");
-    KBO_REQUIRE(n_seqs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 sequences per call");
-    KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] must be 0");
-    const OffsetScan scan = scan_offsets(offsets, n_seqs);
-    KBO_REQUIRE(scan.monotone, KBO_E_BAD_ARG, "offsets not monotone");
-    KBO_REQUIRE(scan.shortest > 0, KBO_E_EMPTY_QUERY, "empty query (index.rs:248 assert!(!query.is_empty()))");
-    KBO_REQUIRE(scan.longest < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "sequence longer than 2^32-1");
+    checked_scan(offsets, n_seqs, false);
     PhaseClock clk;
     // intervals cost 8 more bytes per base on the device and on the way back: smaller slabs
-    const std::vector<Slab> slabs = make_slabs(offsets, n_seqs, lo_out ? std::max<size_t>(1u << 16, slab_bytes_for(idx) / 4) : slab_bytes_for(idx));
-    std::vector<int> devices = devices_for(idx);
-    if (devices.empty()) devices.push_back(current_device());
-    const size_t nd = std::min(devices.size(), std::max<size_t>(1, slabs.size()));
-    BatchJob job;
-    job.idx = idx;
+    const size_t slab_bytes = lo_out ? std::max<size_t>(1u << 16, slab_bytes_for(idx) / 4) : slab_bytes_for(idx);
+    BatchJob job = make_job(OutMode::Ms, idx, offsets, n_seqs, slab_bytes, 0, clk);
     job.concat = concat;
-    job.offsets = offsets;
-    job.k = idx->host.k;
-    job.threshold = 0;
-    job.format = false;
-    job.chars_out = nullptr;
-    job.sink = nullptr;
-    job.sink_direct = false;
     job.ms_out = d_out;
     job.lo_out = lo_out;
     job.hi_out = hi_out;
     job.in_pinned = is_pinned_host(concat);
     job.out_pinned = is_pinned_host(d_out) && (!lo_out || (is_pinned_host(lo_out) && is_pinned_host(hi_out)));
-    job.slabs = &slabs;
-    job.clk = &clk;
-    run_on_devices(job, devices, nd);
+    run_on_devices(job);
 }
 
 void release_host_scratch()

@@ -8,9 +8,11 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -128,6 +130,46 @@ struct PinBuf { // pinned host staging memory, grow-only
     ~PinBuf() { if (p) (void)hipHostFree(p); }
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
+
+// ---- memory the library allocates and the caller frees (kbo_free, kbo_call_flat_free): owned from the allocation to the
+// line that stores it into the caller's out parameter, so that nothing thrown in between leaks it
+template <typename T> struct GrowBuf { // a vector whose storage can be handed to the caller (malloc / realloc; kbo_call_flat_free)
+    T *p = nullptr;
+    size_t n = 0, cap = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    ~GrowBuf() { std::free(p); }
+    size_t size() const { return n; }
+    T *data() { return p; }
+    const T *data() const { return p; }
+    T &operator[](size_t i) { return p[i]; }
+    const T &operator[](size_t i) const { return p[i]; }
+    void reserve(size_t want)
+    {
+        if (want <= cap) return;
+        const size_t c = std::max<size_t>({want, cap + cap / 2, 1024});
+        T *q = static_cast<T *>(std::realloc(p, c * sizeof(T)));
+        if (!q) throw std::bad_alloc();
+        p = q;
+        cap = c;
+    }
+    void resize(size_t m) { reserve(m); n = m; }
+    void push_back(const T &v) { reserve(n + 1); p[n++] = v; }
+    void append(const T *a, const T *b) { reserve(n + (size_t)(b - a)); std::memcpy(p + n, a, (size_t)(b - a) * sizeof(T)); n += (size_t)(b - a); }
+    T *release() { T *q = p; p = nullptr; n = cap = 0; return q; }
+};
+struct FreeDeleter {
+    void operator()(void *p) const { std::free(p); }
+};
+template <typename T> using MallocPtr = std::unique_ptr<T[], FreeDeleter>;
+// n elements, uninitialised; at least one, so that an empty result is still a pointer kbo_free takes
+template <typename T> MallocPtr<T> malloc_array(size_t n)
+{
+    MallocPtr<T> p(static_cast<T *>(std::malloc(std::max<size_t>(1, n) * sizeof(T))));
+    if (!p) throw std::bad_alloc();
+    return p;
+}
 
 // ---- host helper threads: staging copies and offset scans of the host batch entry points.
 // A process-wide team (leaked on purpose: its threads sleep on a condition variable until the

@@ -153,10 +153,9 @@ kbo_variant *pack_variants(const std::vector<kbo::Variant> &v)
     size_t chars = 0;
     for (const auto &x : v) chars += x.query_chars.size() + x.ref_chars.size();
     const size_t head = std::max<size_t>(1, v.size()) * sizeof(kbo_variant);
-    uint8_t *mem = static_cast<uint8_t *>(std::malloc(head + chars + 1));
-    if (!mem) throw std::bad_alloc();
-    kbo_variant *out = reinterpret_cast<kbo_variant *>(mem);
-    uint8_t *cp = mem + head;
+    MallocPtr<uint8_t> mem = malloc_array<uint8_t>(head + chars + 1);
+    kbo_variant *out = reinterpret_cast<kbo_variant *>(mem.get());
+    uint8_t *cp = mem.get() + head;
     for (size_t i = 0; i < v.size(); i++) {
         out[i].query_pos = v[i].query_pos;
         out[i].query_chars = cp;
@@ -168,7 +167,7 @@ kbo_variant *pack_variants(const std::vector<kbo::Variant> &v)
         std::memcpy(cp, v[i].ref_chars.data(), v[i].ref_chars.size());
         cp += v[i].ref_chars.size();
     }
-    return out;
+    return reinterpret_cast<kbo_variant *>(mem.release());
 }
 
 // format.rs:143-193, statement for statement (sequential, variable-length output: host).  Returns false where the reference
@@ -218,10 +217,9 @@ bool run_lengths_gapped_impl(const uint8_t *aln, size_t len, size_t max_gap_len,
 
 kbo_rle *copy_rles(const std::vector<kbo_rle> &v)
 {
-    kbo_rle *p = static_cast<kbo_rle *>(std::malloc(std::max<size_t>(1, v.size()) * sizeof(kbo_rle)));
-    if (!p) throw std::bad_alloc();
-    if (!v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(kbo_rle));
-    return p;
+    MallocPtr<kbo_rle> p = malloc_array<kbo_rle>(v.size());
+    if (!v.empty()) std::memcpy(p.get(), v.data(), v.size() * sizeof(kbo_rle));
+    return p.release();
 }
 
 } // namespace
@@ -808,12 +806,11 @@ int kbo_run_lengths_gapped_batch(const uint8_t *aln_concat, const uint64_t *offs
         std::vector<uint32_t> compact((size_t)n_runs * kRleWords + 1), words(kbo::chunk_items_scratch_words((uint32_t)n_seqs));
         if (n_runs) HIP_OK(hipMemcpy(compact.data(), d_runs.p, (size_t)n_runs * kRleWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(words.data(), scratch.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        kbo_rle *all = static_cast<kbo_rle *>(std::malloc(std::max<size_t>(1, n_runs) * sizeof(kbo_rle)));
-        if (!all) throw std::bad_alloc();
-        widen_rles(all, compact.data(), n_runs, HostTeam::get());
+        MallocPtr<kbo_rle> all = malloc_array<kbo_rle>(n_runs);
+        widen_rles(all.get(), compact.data(), n_runs, HostTeam::get());
         const uint32_t *local = words.data(), *sums = local + n_seqs + 1;
         for (size_t q = 0; q <= n_seqs; q++) rle_offsets[q] = (uint64_t)sums[q / 1024] + local[q];
-        *rles = all;
+        *rles = all.release();
     });
 }
 
@@ -842,40 +839,12 @@ size_t find_batch_impl(kbo_index_t *idx, const uint8_t *concat, const uint64_t *
 {
     kbo_find_opts o;
     if (opts) o = *opts; else kbo_find_opts_default(&o);
-    RleSink sink;
+    RleSink<kbo_rle> sink;
     sink.max_gap_len = o.max_gap_len;
     sink.rle_offsets = rle_offsets;
-    if (into) {
-        sink.caller_owns = true;
-        sink.all = buf;
-        sink.all_cap = buf ? capacity : 0;
-    }
+    if (into) sink.records.use_buffer(buf, capacity);
     matches_batch_impl(idx, concat, offsets, n_seqs, o.max_error_prob, false, nullptr, &sink);
-    if (sink.direct) { // one device: the records are already in place
-        if (!into) {
-            *rles_out = sink.all;
-            sink.all = nullptr;
-        }
-        return sink.all_used;
-    }
-    // several devices: slabs completed out of order and were kept per slab; put them together
-    const std::vector<Slab> slabs = make_slabs(offsets, n_seqs, slab_bytes_for(idx));
-    std::vector<uint64_t> base(slabs.size() + 1, 0);
-    for (size_t i = 0; i < slabs.size(); i++) base[i + 1] = base[i] + sink.runs[i].size();
-    kbo_rle *all = buf;
-    if (!into) {
-        all = static_cast<kbo_rle *>(std::malloc(std::max<uint64_t>(1, base.back()) * sizeof(kbo_rle)));
-        if (!all) throw std::bad_alloc();
-    }
-    const bool fits = !into || (buf && base.back() <= capacity);
-    rle_offsets[0] = 0;
-    HostTeam::get().run(slabs.size(), [&](size_t i) {
-        if (fits && !sink.runs[i].empty()) std::memcpy(all + base[i], sink.runs[i].data(), sink.runs[i].size() * sizeof(kbo_rle));
-        const size_t ns = slabs[i].s1 - slabs[i].s0;
-        for (size_t q = 1; q <= ns; q++) rle_offsets[slabs[i].s0 + q] = base[i] + sink.first[i][q];
-    });
-    if (!into) *rles_out = all;
-    return base.back();
+    return sink.take(rles_out);
 }
 } // namespace
 
@@ -985,30 +954,12 @@ int kbo_find_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_
         static_assert(sizeof(kbo_rle32) == kRleWords * sizeof(uint32_t), "kbo_rle32 is the device's record");
         kbo_find_opts o;
         if (opts) o = *opts; else kbo_find_opts_default(&o);
-        RleSink sink;
+        RleSink<kbo_rle32> sink;
         sink.max_gap_len = o.max_gap_len;
         sink.rle_offsets = rle_offsets;
-        sink.compact = true;
         const PackedBatch in{words, exc_pos, exc_byte, n_exc};
         matches_batch_packed_impl(idx, in, offsets, n_seqs, o.max_error_prob, nullptr, &sink);
-        if (sink.direct) { // one device: the records are already in place
-            *rles = reinterpret_cast<kbo_rle32 *>(sink.all32);
-            sink.all32 = nullptr;
-            return;
-        }
-        // several devices: slabs completed out of order and were kept per slab; put them together
-        const std::vector<Slab> slabs = make_slabs(offsets, n_seqs, packed_slab_bytes(idx)); // (as matches_batch_packed_impl)
-        std::vector<uint64_t> base(slabs.size() + 1, 0);
-        for (size_t i = 0; i < slabs.size(); i++) base[i + 1] = base[i] + sink.runs32[i].size() / kRleWords;
-        uint32_t *all = static_cast<uint32_t *>(std::malloc(std::max<uint64_t>(1, base.back()) * kRleWords * sizeof(uint32_t)));
-        if (!all) throw std::bad_alloc();
-        rle_offsets[0] = 0;
-        HostTeam::get().run(slabs.size(), [&](size_t i) {
-            if (!sink.runs32[i].empty()) std::memcpy(all + base[i] * kRleWords, sink.runs32[i].data(), sink.runs32[i].size() * sizeof(uint32_t));
-            const size_t ns = slabs[i].s1 - slabs[i].s0;
-            for (size_t q = 1; q <= ns; q++) rle_offsets[slabs[i].s0 + q] = base[i] + sink.first[i][q];
-        });
-        *rles = reinterpret_cast<kbo_rle32 *>(all);
+        sink.take(rles);
     });
 }
 
@@ -1018,29 +969,10 @@ int kbo_matches_batch_sparse(kbo_index_t *idx, const uint32_t *words, const uint
     return guarded([&] {
         KBO_REQUIRE(idx && words && runs && n_runs, KBO_E_BAD_ARG, "null argument");
         static_assert(sizeof(kbo_aln_run) == 12, "kbo_aln_run is the device's record");
-        SparseSink sink;
+        RecordSink<kbo_aln_run> sink; // (records carry the sequence's index in the whole batch: nothing is rewritten)
         const PackedBatch in{words, exc_pos, exc_byte, n_exc};
         matches_batch_packed_impl(idx, in, offsets, n_seqs, max_error_prob, nullptr, nullptr, &sink);
-        if (sink.direct) { // one device: the records are already in place
-            if (!sink.all) {
-                sink.all = static_cast<kbo_aln_run *>(std::malloc(sizeof(kbo_aln_run)));
-                if (!sink.all) throw std::bad_alloc();
-            }
-            *n_runs = sink.all_used;
-            *runs = sink.all;
-            sink.all = nullptr;
-            return;
-        }
-        // several devices: slabs completed out of order and were kept per slab; put them together (seq is already the batch's)
-        std::vector<uint64_t> base(sink.runs.size() + 1, 0);
-        for (size_t i = 0; i < sink.runs.size(); i++) base[i + 1] = base[i] + sink.runs[i].size();
-        kbo_aln_run *all = static_cast<kbo_aln_run *>(std::malloc(std::max<uint64_t>(1, base.back()) * sizeof(kbo_aln_run)));
-        if (!all) throw std::bad_alloc();
-        HostTeam::get().run(sink.runs.size(), [&](size_t i) {
-            if (!sink.runs[i].empty()) std::memcpy(all + base[i], sink.runs[i].data(), sink.runs[i].size() * sizeof(kbo_aln_run));
-        });
-        *n_runs = base.back();
-        *runs = all;
+        *n_runs = sink.take(runs);
     });
 }
 

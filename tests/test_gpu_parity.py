@@ -585,6 +585,75 @@ def test_find_batch_with_contigs(oracle):
             assert [tuple(int(v) for v in r) for r in rles[ro[s]:ro[s + 1]]] == exp, (gap, s)
 
 
+def _find_reads_input():  # the batch of test_find_batch_every_read_against_oracle
+    g = synth.genome(200_000, seed=23)
+    return g, synth.reads(g, 30_000, 150, 0.04, seed=24)
+
+
+def _find_contigs_input():  # the batch of test_find_batch_with_contigs
+    rng = np.random.default_rng(9)
+    g = synth.genome(300_000, seed=25)
+    pieces = []
+    for n in [150, 90_000, 300, 5_000, 70_001, 3, 151]:
+        s0 = int(rng.integers(0, len(g) - n))
+        p = g[s0:s0 + n].copy()
+        hit = rng.random(n) < 0.01
+        p[hit] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, int(hit.sum()))]
+        if n > 1000:
+            p[n // 2:n // 2 + 200] = ord("N")
+        pieces.append(p)
+    return g, (np.concatenate(pieces), np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.uint64))
+
+
+@pytest.mark.parametrize("make_input, slab_bytes, gaps", [(_find_reads_input, 1 << 20, (0, 5, 40)),
+                                                          (_find_contigs_input, 1 << 16, (0, 100, 1000))])
+def test_find_batch_into_a_callers_buffer(make_input, slab_bytes, gaps):
+    """kbo_find_batch_into over the batches of test_find_batch_every_read_against_oracle and test_find_batch_with_contigs
+    (whose records those tests check against the oracle): a caller's buffer of more records than the batch has runs, and of
+    exactly as many, gets kbo_find_batch's records; one of one record less, and none at all (null, capacity 0), gives
+    KBO_E_NOMEM with rle_offsets and *n_runs complete all the same, and no byte behind `capacity` records is written in
+    any case.  Several slabs; one worker (records go straight to the buffer), two workers on one device (kept per slab, put
+    together at the end) and, where there are two devices, on both."""
+    import ctypes as C
+    import torch
+    from kbo_amd import _capi
+    g, (concat, offsets) = make_input()
+    sbwt, _ = kbo_amd.build([g], kbo_amd.BuildOpts(k=31, num_threads=4))
+    L = kbo_amd.lib()
+    n = len(offsets) - 1
+    pad = 64  # records behind the capacity the call is told of
+    dev_lists = [None, (0, 0)] + ([(0, 1)] if torch.cuda.device_count() >= 2 else [])
+    try:
+        L.kbo_set_slab_bytes(slab_bytes)
+        for gap in gaps:
+            rles, exp_ro = batch.find_batch(sbwt, concat, offsets, kbo_amd.FindOpts(max_gap_len=gap))
+            exp = np.array(rles, dtype=np.uint64).reshape(-1, 7)
+            total = len(exp)
+            assert total > 1 and total == int(exp_ro[-1])
+            co = _capi.FindOpts(1e-7, gap)
+            for devs in dev_lists:
+                if devs:
+                    kbo_amd.check(L.kbo_set_devices((C.c_int * 2)(*devs), 2))
+                for capacity, null in ((total + 17, False), (total, False), (total - 1, False), (0, True)):
+                    what = (gap, devs, capacity, null)
+                    pattern = np.random.default_rng(capacity + 1).integers(1, 1 << 62, size=(capacity + pad, 7), dtype=np.uint64)
+                    buf = pattern.copy()
+                    ro = np.full(n + 1, 0xABABABABABABABAB, dtype=np.uint64)
+                    n_runs = C.c_size_t(0xABABABAB)
+                    rc = L.kbo_find_batch_into(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, C.byref(co),
+                                               None if null else buf.ctypes.data, capacity, ro.ctypes.data, C.byref(n_runs))
+                    assert rc == (0 if capacity >= total else -5), what  # KBO_OK / KBO_E_NOMEM
+                    assert n_runs.value == total, what
+                    assert np.array_equal(ro, exp_ro), what
+                    assert np.array_equal(buf[capacity:], pattern[capacity:]), what
+                    if capacity >= total:
+                        assert np.array_equal(buf[:total], exp), what
+                L.kbo_set_devices(None, 0)
+    finally:
+        L.kbo_set_devices(None, 0)
+        L.kbo_set_slab_bytes(32 << 20)
+
+
 def test_host_batches_in_slabs(oracle):
     """Host batches larger than the slab size go through the staged slab pipeline (more slabs than
     slots, so staging buffers and device buffers are reused within one call)."""
