@@ -84,6 +84,24 @@ pub mod ffi {
         pub fn kbo_find_batch_packed(idx: *mut KboIndex, words: *const u32, offsets: *const u64, n_seqs: usize, exc_pos: *const u64,
                                      exc_byte: *const u8, n_exc: usize, opts: *const KboFindOpts, rles: *mut *mut KboRle32,
                                      rle_offsets: *mut u64) -> c_int;
+        // both strands of every sequence in one call, the batch staged to the device once (kbo_hip.h "both strands")
+        pub fn kbo_revcomp_batch(concat: *const u8, offsets: *const u64, n_seqs: usize, out: *mut u8) -> c_int;
+        pub fn kbo_matches_batch_strands(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, format: c_int,
+                                         strands: c_int, out_fwd: *mut u8, out_rev: *mut u8) -> c_int;
+        pub fn kbo_find_batch_strands(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboFindOpts,
+                                      strands: c_int, rles: *mut *mut KboRle, rle_offsets: *mut u64) -> c_int;
+        pub fn kbo_matches_batch_packed_strands(idx: *mut KboIndex, words: *const u32, offsets: *const u64, n_seqs: usize,
+                                                exc_pos: *const u64, exc_byte: *const u8, n_exc: usize, p: f64, strands: c_int,
+                                                words_fwd: *mut u32, words_rev: *mut u32) -> c_int;
+        pub fn kbo_find_batch_packed_strands(idx: *mut KboIndex, words: *const u32, offsets: *const u64, n_seqs: usize,
+                                             exc_pos: *const u64, exc_byte: *const u8, n_exc: usize, opts: *const KboFindOpts,
+                                             strands: c_int, rles: *mut *mut KboRle32, rle_offsets: *mut u64) -> c_int;
+        pub fn kbo_revcomp_batch_dev(d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_seq_len: usize,
+                                     d_out: *mut u8, stream: *mut c_void) -> c_int;
+        pub fn kbo_revcomp_packed_scratch_bytes(n_seqs: usize) -> usize;
+        pub fn kbo_revcomp_packed_dev(d_words: *const u32, d_offsets: *const u64, n_seqs: usize, total_words: u64, d_exc_pos: *const u64,
+                                      d_exc_byte: *const u8, n_exc: usize, d_words_out: *mut u32, d_exc_pos_out: *mut u64,
+                                      d_exc_byte_out: *mut u8, d_scratch: *mut c_void, stream: *mut c_void) -> c_int;
         // device-resident batches on a hipStream_t (kbo_hip.h): kbo::map / matches for reads as ONE kernel; `_tail`: its second
         // pass on a second stream, beside the next batch's kernel; packed: 2-bit words in and out
         pub fn kbo_work_bytes(n_seqs: usize, total_bases: u64, max_seq_len: usize, k: u32) -> usize;
@@ -249,6 +267,35 @@ pub fn find_batch(reads: &[Vec<u8>], idx: &GpuIndex, opts: kbo::FindOpts) -> Vec
     let out = (0..reads.len()).map(|i| all[ro[i] as usize..ro[i + 1] as usize].iter().map(|r| kbo::format::RLE {
         start: r.start as usize, end: r.end as usize, matches: r.matches as usize, mismatches: r.mismatches as usize,
         jumps: r.jumps as usize, gap_bases: r.gap_bases as usize, gap_opens: r.gap_opens as usize }).collect()).collect();
+    unsafe { ffi::kbo_free(p as *mut c_void) };
+    out
+}
+
+pub const STRAND_FWD: c_int = 1;
+pub const STRAND_REV: c_int = 2;
+
+/// `kbo::find` of every read and of its reverse complement (what kbo-cli runs per strand), 2-bit packed over PCIe and staged once
+/// (`kbo_find_batch_packed_strands`): reads[i] -> (its '+' runs, its '-' runs).  The '-' runs are in the coordinates of the
+/// reverse-complemented read: position p there is base len - 1 - p of reads[i].
+pub fn find_batch_strands(reads: &[Vec<u8>], idx: &GpuIndex, opts: kbo::FindOpts) -> Vec<(Vec<kbo::format::RLE>, Vec<kbo::format::RLE>)> {
+    let n = reads.len();
+    let mut offsets = vec![0u64; n + 1];
+    for (i, r) in reads.iter().enumerate() { offsets[i + 1] = offsets[i] + r.len() as u64; }
+    let concat: Vec<u8> = reads.concat();
+    let mut words = vec![0u32; unsafe { ffi::kbo_packed_words(offsets.as_ptr(), n) }];
+    let cap = concat.iter().filter(|b| !matches!(**b, b'A' | b'C' | b'G' | b'T')).count();
+    let (mut exc_pos, mut exc_byte, mut n_exc) = (vec![0u64; cap], vec![0u8; cap], 0usize);
+    check(unsafe { ffi::kbo_pack_reads(concat.as_ptr(), offsets.as_ptr(), n, words.as_mut_ptr(), exc_pos.as_mut_ptr(),
+                                       exc_byte.as_mut_ptr(), cap, &mut n_exc) });
+    let o = ffi::KboFindOpts { max_error_prob: opts.max_error_prob, max_gap_len: opts.max_gap_len };
+    let (mut p, mut ro) = (std::ptr::null_mut(), vec![0u64; 2 * n + 1]);
+    check(unsafe { ffi::kbo_find_batch_packed_strands(idx.0, words.as_ptr(), offsets.as_ptr(), n, exc_pos.as_ptr(), exc_byte.as_ptr(),
+                                                      n_exc, &o, STRAND_FWD | STRAND_REV, &mut p, ro.as_mut_ptr()) });
+    let all = unsafe { std::slice::from_raw_parts(p, ro[2 * n] as usize) };
+    let runs = |j: usize| -> Vec<kbo::format::RLE> { all[ro[j] as usize..ro[j + 1] as usize].iter().map(|r| kbo::format::RLE {
+        start: r.start as usize, end: r.end as usize, matches: r.matches as usize, mismatches: r.mismatches as usize,
+        jumps: r.jumps as usize, gap_bases: r.gap_bases as usize, gap_opens: r.gap_opens as usize }).collect() };
+    let out = (0..n).map(|i| (runs(2 * i), runs(2 * i + 1))).collect();
     unsafe { ffi::kbo_free(p as *mut c_void) };
     out
 }

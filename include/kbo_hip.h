@@ -385,6 +385,60 @@ int kbo_matches_batch_sparse(kbo_index_t *idx, const uint32_t *words, const uint
 int kbo_sparse_expand(const kbo_aln_run *runs, uint64_t n_runs, const uint64_t *offsets, size_t n_seqs, const uint8_t *ref_concat,
                       uint8_t *out);
 
+/* ------------------------------------------------------------------ both strands
+ * A read comes from either strand of what the index was built of, a gene lies on either strand of an assembly.  Instead of an
+ * index built with add_revcomp (twice the rows and plan structures; a human-scale index then has 2^32 rows or more and becomes
+ * a sharded one, see above) or a second call with sequences the host has reverse-complemented (every base crosses PCIe twice),
+ * these entry points compare every sequence AND its reverse complement with the index as it is.  The batch is staged to the
+ * device ONCE; the '-' strand is made there (kbo_amd/csrc/revcomp_kernels.hip).
+ * Reverse complement, per sequence and never across a boundary: output base i = complement of input base len - 1 - i;
+ * A <-> T, C <-> G, a <-> t, c <-> g, every other byte unchanged (N stays N and breaks matches as ever).
+ * strands: KBO_STRAND_FWD, KBO_STRAND_REV or both (3); 0 or anything else -> KBO_E_BAD_ARG.  The '-' result of sequence s is
+ * exactly what the single-strand entry point returns for revcomp(sequence s), and it is IN THE COORDINATES OF THE
+ * REVERSE-COMPLEMENTED SEQUENCE: position i of a '-' output (a character, a run's start / end) is base len - 1 - i of the
+ * sequence as given.  Errors, limits and the behaviour for sharded indexes are the single-strand entry point's; the output of a
+ * strand that is not asked for may be NULL and is not touched. */
+#define KBO_STRAND_FWD 1
+#define KBO_STRAND_REV 2
+/* host helper (threaded): out[offsets[s] .. offsets[s+1]) = revcomp(sequence s).  Sequences may be empty.  KBO_E_BAD_ARG for
+ * null arguments, offsets that do not ascend from 0, and an `out` that overlaps `concat`. */
+int kbo_revcomp_batch(const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint8_t *out);
+/* kbo_matches_batch (format = 0) / kbo_map_batch (format != 0: format::relative_to_ref of the '-' strand takes the
+ * reverse-complemented read) per strand; out_fwd / out_rev hold offsets[n_seqs] bytes each. */
+int kbo_matches_batch_strands(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                              int format, int strands, uint8_t *out_fwd, uint8_t *out_rev);
+/* kbo_find_batch per strand: rle_offsets has 2 * n_seqs + 1 entries (caller-allocated); the runs of sequence s are
+ * [rle_offsets[2 s], rle_offsets[2 s + 1]) for '+' and [rle_offsets[2 s + 1], rle_offsets[2 s + 2]) for '-'; a strand that is
+ * not asked for has none.  *rles is library-allocated (kbo_free). */
+int kbo_find_batch_strands(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_find_opts *opts,
+                           int strands, kbo_rle **rles, uint64_t *rle_offsets);
+/* the same over the packed input of kbo_matches_batch_packed / kbo_find_batch_packed; words_fwd / words_rev hold
+ * kbo_packed_words() words each, with kbo_matches_batch_packed's conventions (M - X R = 0 .. 3; kbo_unpack_matches) */
+int kbo_matches_batch_packed_strands(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                                     const uint8_t *exc_byte, size_t n_exc, double max_error_prob, int strands, uint32_t *words_fwd,
+                                     uint32_t *words_rev);
+int kbo_find_batch_packed_strands(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                                  const uint8_t *exc_byte, size_t n_exc, const kbo_find_opts *opts, int strands, kbo_rle32 **rles,
+                                  uint64_t *rle_offsets);
+/* The reverse complement of a device-resident batch, enqueued on `stream` (a hipStream_t); the library never synchronises.
+ * Alignment and SLACK as for the device-resident path below: d_concat 16-byte aligned with 16 readable bytes behind its last
+ * base, d_offsets 8-byte, d_out 4-byte aligned.  Exactly [d_out, d_out + total_bases) is written - d_out needs no slack of its own
+ * for this call.  Sequences may be empty; max_seq_len (0 = unknown) is accepted for symmetry and changes nothing: the work is cut
+ * by 4 KiB of output, so millions of reads and a handful of Mbp contigs fill the device alike.  KBO_E_BAD_ARG for null or
+ * misaligned arguments and for a d_out that overlaps the input, KBO_E_UNSUPPORTED for total_bases + 16 > 2^32. */
+int kbo_revcomp_batch_dev(const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, size_t max_seq_len,
+                          uint8_t *d_out, void *stream);
+/* ... of a device-resident PACKED batch (the layout of kbo_matches_batch_packed; total_words = kbo_packed_words()): a
+ * sequence's words reversed in 2-bit groups, complemented and shifted by (16 - len mod 16) mod 16 groups across word boundaries,
+ * the padding bits of its last word zero; the exception list mirrored within each sequence (p -> offsets[s] + offsets[s+1] - 1 - p,
+ * the byte complemented) and ascending again.  The 2 bits at a listed position are unspecified, as on input.  d_scratch:
+ * kbo_revcomp_packed_scratch_bytes(n_seqs) bytes, 16-byte aligned (0 from it: too many sequences for one launch).  No output may
+ * overlap its input (KBO_E_BAD_ARG). */
+size_t kbo_revcomp_packed_scratch_bytes(size_t n_seqs);
+int kbo_revcomp_packed_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_words, const uint64_t *d_exc_pos,
+                           const uint8_t *d_exc_byte, size_t n_exc, uint32_t *d_words_out, uint64_t *d_exc_pos_out, uint8_t *d_exc_byte_out,
+                           void *d_scratch, void *stream);
+
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`
  * (a hipStream_t) and the call returns immediately.  d_concat must be 16-byte aligned,

@@ -188,6 +188,10 @@ int kbo_map_batch_opts_phases(double out[6]);
  * out[0] upload, [1] extraction, [2] sort, [3] dedup, [4] orphans + dummy rows, [5] merge, [6] edge bits + LCS, [7] download of
  * the rows and LCS, [8] the device copy (layout and plan structures, as kbo_index_to_device) (tools/bench_build.py) */
 int kbo_index_build_device_phases(double out[9]);
+/* Test hook: bytes the calling thread's last host batch (kbo_ms_batch, kbo_matches_batch / kbo_map_batch / kbo_find_batch, their
+ * packed and *_strands forms) copied from the host to the device: bases or words, exception lists, offsets, work items.  A batch
+ * run in both strands stages what it stages for one (tests/test_gpu_strands.py). */
+uint64_t kbo_last_batch_staged_bytes(void);
 /* Test hook: the number of workgroups kbo_sparse_runs_dev launches its count and emit kernels with for these arguments (1 .. 2048;
  * max_seq_len = 0, unknown: the most; 0 for arguments it refuses) */
 uint32_t kbo_sparse_runs_blocks(size_t n_seqs, size_t max_seq_len);

@@ -112,6 +112,8 @@ SYMBOLS = [
     "kbo_find_batch_dev", "kbo_map_stream_create", "kbo_map_stream_submit", "kbo_map_stream_wait", "kbo_map_stream_wait_on",
     "kbo_map_stream_sync", "kbo_map_stream_free", "kbo_map_batch_opts", "kbo_fill_gaps_batch", "kbo_index_build_device",
     "kbo_matches_batch_sparse", "kbo_sparse_expand", "kbo_sparse_runs_work_bytes", "kbo_sparse_runs_dev",
+    "kbo_revcomp_batch", "kbo_matches_batch_strands", "kbo_find_batch_strands", "kbo_matches_batch_packed_strands",
+    "kbo_find_batch_packed_strands", "kbo_revcomp_batch_dev", "kbo_revcomp_packed_scratch_bytes", "kbo_revcomp_packed_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -120,6 +122,7 @@ TUNING_SYMBOLS = [
     "kbo_set_plan_unit_cap_divisor", "kbo_index_plan_holdoff", "kbo_set_walk_experiment", "kbo_plan_stats_dev", "kbo_set_plan_stats", "kbo_set_index_shards", "kbo_index_shard", "kbo_set_depth_table", "kbo_set_depth_table_anchors", "kbo_index_depth_table", "kbo_run_automaton_depths",
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
+    "kbo_last_batch_staged_bytes",
 ]
 
 _lib = None
@@ -230,6 +233,15 @@ def lib():
     L.kbo_sparse_runs_work_bytes.argtypes = [sz, u64]; L.kbo_sparse_runs_work_bytes.restype = sz
     L.kbo_sparse_runs_dev.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
     L.kbo_sparse_runs_blocks.argtypes = [sz, sz]; L.kbo_sparse_runs_blocks.restype = u32
+    L.kbo_revcomp_batch.argtypes = [vp, vp, sz, vp]
+    L.kbo_matches_batch_strands.argtypes = [vp, vp, vp, sz, dbl, C.c_int, C.c_int, vp, vp]
+    L.kbo_find_batch_strands.argtypes = [vp, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(C.POINTER(RLE)), vp]
+    L.kbo_matches_batch_packed_strands.argtypes = [vp, vp, vp, sz, vp, vp, sz, dbl, C.c_int, vp, vp]
+    L.kbo_find_batch_packed_strands.argtypes = [vp, vp, vp, sz, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(vp), vp]
+    L.kbo_revcomp_batch_dev.argtypes = [vp, vp, sz, u64, sz, vp, vp]
+    L.kbo_revcomp_packed_scratch_bytes.argtypes = [sz]; L.kbo_revcomp_packed_scratch_bytes.restype = sz
+    L.kbo_revcomp_packed_dev.argtypes = [vp, vp, sz, u64, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.kbo_last_batch_staged_bytes.argtypes = []; L.kbo_last_batch_staged_bytes.restype = u64
     L.kbo_set_plan_stats.argtypes = [C.c_int]
     L.kbo_set_index_shards.argtypes = [C.c_int]
     L.kbo_set_depth_table.argtypes = [C.c_int]

@@ -207,6 +207,81 @@ def find_batch_packed(sbwt, words, offsets, exc_pos, exc_byte, find_opts=None):
     return rles, ro
 
 
+# ---- both strands (kbo_hip.h "both strands"): the batch is staged to the device once, the '-' strand is made there
+STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
+
+
+def revcomp_batch(concat, offsets):
+    """kbo_revcomp_batch (host, threaded): the reverse complement of every sequence, in place of the sequence -> uint8"""
+    concat, offsets, n = _prep(concat, offsets)
+    out = np.zeros(max(len(concat), 1), dtype=np.uint8)
+    check(lib().kbo_revcomp_batch(concat.ctypes.data, offsets.ctypes.data, n, out.ctypes.data))
+    return out[:len(concat)]
+
+
+def last_batch_staged_bytes():
+    """host -> device bytes the calling thread's last host batch staged (kbo_hip_tuning.h)"""
+    return int(lib().kbo_last_batch_staged_bytes())
+
+
+def matches_batch_strands(sbwt, concat, offsets, max_error_prob=1e-7, format=False, strands=STRAND_BOTH):  # noqa: A002
+    """kbo::matches (format=False) / kbo::map without refinement (format=True) of every sequence and of its reverse complement
+    -> (chars '+' | None, chars '-' | None); '-' is in the coordinates of the reverse-complemented sequence"""
+    concat, offsets, n = _prep(concat, offsets)
+    total = int(offsets[-1]) if n > 0 else 0
+    fwd = np.zeros(max(total, 1), dtype=np.uint8) if strands & 1 else None
+    rev = np.zeros(max(total, 1), dtype=np.uint8) if strands & 2 else None
+    check(lib().kbo_matches_batch_strands(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, max_error_prob, int(format), strands,
+                                          fwd.ctypes.data if fwd is not None else None, rev.ctypes.data if rev is not None else None))
+    return (fwd[:total] if fwd is not None else None), (rev[:total] if rev is not None else None)
+
+
+def find_batch_strands(sbwt, concat, offsets, find_opts=None, strands=STRAND_BOTH):
+    """kbo::find per strand -> ([n_runs, 7] uint64 records, rle_offsets uint64[2 n + 1]): the runs of sequence s are
+    [ro[2 s], ro[2 s + 1]) for '+' and [ro[2 s + 1], ro[2 s + 2]) for '-'"""
+    from . import FindOpts
+    o = find_opts if find_opts is not None else FindOpts()
+    co = _capi.FindOpts(o.max_error_prob, o.max_gap_len)
+    concat, offsets, n = _prep(concat, offsets)
+    ro = np.zeros(2 * n + 1, dtype=np.uint64)
+    p = C.POINTER(_capi.RLE)()
+    check(lib().kbo_find_batch_strands(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, C.byref(co), strands, C.byref(p), ro.ctypes.data))
+    total = int(ro[-1])
+    rles = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(max(1, total), 7))[:total].copy()
+    lib().kbo_free(p)
+    return rles, ro
+
+
+def matches_batch_packed_strands(sbwt, words, offsets, exc_pos, exc_byte, max_error_prob=1e-7, strands=STRAND_BOTH):
+    """matches_batch_packed per strand -> (words '+' | None, words '-' | None)"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    fwd = np.zeros(max(len(words), 1), dtype=np.uint32) if strands & 1 else None
+    rev = np.zeros(max(len(words), 1), dtype=np.uint32) if strands & 2 else None
+    check(lib().kbo_matches_batch_packed_strands(sbwt._h, words.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                                 exc_pos.ctypes.data if len(exc_pos) else None, exc_byte.ctypes.data if len(exc_byte) else None,
+                                                 len(exc_pos), max_error_prob, strands, fwd.ctypes.data if fwd is not None else None,
+                                                 rev.ctypes.data if rev is not None else None))
+    return (fwd[:len(words)] if fwd is not None else None), (rev[:len(words)] if rev is not None else None)
+
+
+def find_batch_packed_strands(sbwt, words, offsets, exc_pos, exc_byte, find_opts=None, strands=STRAND_BOTH):
+    """find_batch_packed per strand -> ([n_runs, 7] uint64 records, rle_offsets uint64[2 n + 1]) as find_batch_strands"""
+    from . import FindOpts
+    o = find_opts if find_opts is not None else FindOpts()
+    co = _capi.FindOpts(o.max_error_prob, o.max_gap_len)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    ro = np.zeros(2 * n + 1, dtype=np.uint64)
+    p = C.c_void_p()
+    check(lib().kbo_find_batch_packed_strands(sbwt._h, words.ctypes.data, offsets.ctypes.data, n, exc_pos.ctypes.data if len(exc_pos) else None,
+                                              exc_byte.ctypes.data if len(exc_byte) else None, len(exc_pos), C.byref(co), strands, C.byref(p),
+                                              ro.ctypes.data))
+    total = int(ro[-1])
+    rles = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(max(1, total), 7))[:total].astype(np.uint64)  # (kbo_rle32)
+    lib().kbo_free(p)
+    return rles, ro
+
+
 class _FlatOwner:
     """keeps a kbo_call_flat alive for the numpy views into it (freed with the last of them)"""
 

@@ -193,11 +193,12 @@ struct BatchOnDevice {
     DevBuf longw; // work of the kernel for sequences of more than 160 bases (long_kernels.hip)
     DevBuf ms_shard; // sharded indexes: the MS values of one further shard, folded into `ms` by maximum
     DevBuf packed, pscr, exc_pos, exc_byte, packed_out, exc_flag; // (exc_flag: one byte per read of a packed-native launch)
+    DevBuf raw; // the '-' strand alone: the slab as uploaded (bytes or words); its reverse complement goes where the walk reads
     // packed entry points: 2-bit words in, scanned words per sequence, non-ACGT list, 2-bit words out
     uint64_t total = 0;
     void release()
     {
-        for (DevBuf *b : {&q, &off, &items, &ms, &lo, &hi, &plan, &longw, &packed, &pscr, &exc_pos, &exc_byte, &packed_out, &exc_flag, &ms_shard}) b->release();
+        for (DevBuf *b : {&q, &off, &items, &ms, &lo, &hi, &plan, &longw, &packed, &pscr, &exc_pos, &exc_byte, &packed_out, &exc_flag, &ms_shard, &raw}) b->release();
     }
 };
 // a slab of a packed batch (pack_kernels.hip: sequence s = ceil(len / 16) u32 words, 2 bits per base): what
@@ -226,6 +227,13 @@ template <typename T> void convert_records(T *dst, const void *src, size_t n, Ho
 inline void convert_records(kbo_rle *dst, const void *src, size_t n, HostTeam &team)
 {
     widen_rles(dst, static_cast<const uint32_t *>(src), n, team);
+}
+
+// ... a few records, on the calling thread
+template <typename T> void convert_records(T *dst, const uint32_t *src, size_t n) { std::memcpy(dst, src, n * sizeof(T)); }
+inline void convert_records(kbo_rle *dst, const uint32_t *src, size_t n)
+{
+    for (size_t q = 0; q < n; q++, src += kRleWords) dst[q] = kbo_rle{src[0], src[1], src[2], src[3], src[4], src[5], src[6]};
 }
 
 // Where a host batch collects the records of its slabs (kbo_rle: kbo_find_batch, kbo_find_batch_into; kbo_rle32:
@@ -275,6 +283,21 @@ template <typename T> struct RecordSink {
         used += n;
         return at;
     }
+    // room for the n records of a slab that the caller fills itself (nullptr: a caller's buffer that is too small); *at as append's
+    T *place(size_t slab_id, size_t n, size_t *at)
+    {
+        if (!direct) {
+            per_slab[slab_id].resize(n);
+            *at = 0;
+            return per_slab[slab_id].data();
+        }
+        *at = used;
+        used += n;
+        if (caller_owns) return *at + n <= fixed_cap ? fixed + *at : nullptr;
+        if (*at + n > all.cap) all.reserve((*at + n) * 2);
+        all.n = *at + n;
+        return all.p + *at;
+    }
     // The batch's records in slab order and their number.  The library's array (malloc'ed, at least one record long, the
     // caller's to free) goes to *out; a caller's buffer stays where it is and holds the records only if all of them fit.
     size_t take(T **out)
@@ -305,7 +328,11 @@ template <typename T> struct RecordSink {
 // characters, which then never leave it): the records, wide or as the device writes them, and where each sequence's begin
 template <typename T> struct RleSink {
     size_t max_gap_len = 0;
-    uint64_t *rle_offsets = nullptr; // caller's n_seqs + 1 entries
+    uint64_t *rle_offsets = nullptr; // caller's n_seqs + 1 entries (strands != 0: 2 n_seqs + 1)
+    // kbo_find_batch*_strands (KBO_STRAND_*; 0: the single-strand entry points): sequence s has the entries 2 s ('+') and
+    // 2 s + 1 ('-'), a strand not asked for has no runs.  With both, a slab arrives as the device ran it - 2 ns sequences, the
+    // '-' strands behind the '+' strands (HostStage) - and its records are put in (sequence, strand) order here.
+    int strands = 0;
     RecordSink<T> records;
     std::vector<size_t> s0;                   // first sequence of every slab (+ n_seqs)
     std::vector<std::vector<uint32_t>> first; // per slab form: index of the first run of each sequence of the slab, +1 entry
@@ -324,6 +351,7 @@ template <typename T> struct RleSink {
     void append(size_t slab_id, const void *src, size_t n_records, const uint32_t *local, HostTeam &team)
     {
         const size_t ns = s0[slab_id + 1] - s0[slab_id];
+        if (strands) return append_strands(slab_id, src, n_records, local, team);
         const uint32_t *sums = local + ns + 1;
         const size_t at = records.append(slab_id, src, n_records, team);
         if (records.direct) {
@@ -343,10 +371,48 @@ template <typename T> struct RleSink {
     }
 
 private:
+    void append_strands(size_t slab_id, const void *src, size_t n_records, const uint32_t *local, HostTeam &team)
+    {
+        const size_t ns = s0[slab_id + 1] - s0[slab_id], dn = strands == 3 ? 2 * ns : ns; // sequences: the caller's / the device's
+        const uint32_t *sums = local + dn + 1;
+        auto first_run = [&](size_t q) { return sums[q / 1024] + local[q]; };
+        const uint32_t fwd_runs = strands == 3 ? first_run(ns) : 0;
+        // where the runs of (sequence q, strand) begin within the slab's: entries 2 q and 2 q + 1, + the end
+        std::vector<uint32_t> lo(2 * ns + 1);
+        const size_t piece = 1u << 14, n_tasks = (ns + piece - 1) / piece;
+        team.run(n_tasks, [&](size_t t) {
+            for (size_t q = t * piece; q < std::min(ns, (t + 1) * piece); q++) {
+                if (strands == 3) {
+                    const uint32_t rev = first_run(ns + q) - fwd_runs;
+                    lo[2 * q] = first_run(q) + rev;
+                    lo[2 * q + 1] = first_run(q + 1) + rev;
+                } else {
+                    lo[2 * q] = first_run(q);
+                    lo[2 * q + 1] = strands == 1 ? first_run(q + 1) : first_run(q);
+                }
+            }
+        });
+        lo[2 * ns] = (uint32_t)n_records;
+        size_t at = 0;
+        if (strands != 3) {
+            at = records.append(slab_id, src, n_records, team);
+        } else if (T *dst = records.place(slab_id, n_records, &at)) {
+            const uint32_t *rec = static_cast<const uint32_t *>(src);
+            team.run(n_tasks, [&](size_t t) {
+                for (size_t q = t * piece; q < std::min(ns, (t + 1) * piece); q++) {
+                    const uint32_t f0 = first_run(q), nf = first_run(q + 1) - f0, r0 = first_run(ns + q), nr = first_run(ns + q + 1) - r0;
+                    if (nf) convert_records(dst + lo[2 * q], rec + (size_t)f0 * kRleWords, nf);
+                    if (nr) convert_records(dst + lo[2 * q + 1], rec + (size_t)r0 * kRleWords, nr);
+                }
+            });
+        }
+        if (records.direct) set_offsets(slab_id, at, [&](size_t q) { return (uint64_t)lo[q]; }, team);
+        else first[slab_id] = std::move(lo);
+    }
     // rle_offsets of a slab's sequences: the slab's base + the index of the sequence's first run within the slab
     template <typename First> void set_offsets(size_t slab_id, uint64_t slab_base, First first_run, HostTeam &team)
     {
-        const size_t at = s0[slab_id], ns = s0[slab_id + 1] - at, piece = 1u << 15;
+        const size_t per = strands ? 2 : 1, at = per * s0[slab_id], ns = per * (s0[slab_id + 1] - s0[slab_id]), piece = 1u << 15;
         team.run((ns + piece - 1) / piece, [&](size_t t) {
             const size_t a = t * piece + 1, b = std::min(ns, a + piece - 1);
             for (size_t q = a; q <= b; q++) rle_offsets[at + q] = slab_base + first_run(q);
@@ -387,6 +453,15 @@ struct FusedMap {
     uint32_t *run_counts = nullptr;
     bool counted = false;
 };
+// Strands of a host batch (kbo_*_batch_strands) and the count of what it uploads.  strands = KBO_STRAND_FWD: the slab as it is;
+// KBO_STRAND_REV: its reverse complement, made on the device from the uploaded slab; both: the slab DOUBLED on the device -
+// `offsets` / `n_seqs` (and a packed slab's uniform_len) then describe 2 n sequences, n .. 2n-1 the reverse complements of
+// 0 .. n-1 behind them, of which only the first half - bases or words, exceptions, offsets, items - is uploaded (concat,
+// PackedIn::words / n_words / n_exc are that half) and the rest is made by revcomp_kernels.hip.
+struct HostStage {
+    int strands = 1;
+    std::atomic<uint64_t> *staged = nullptr; // += bytes of every host -> device copy
+};
 void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, bool want_ival,
                        BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
                        uint32_t longest = 0 /* longest sequence if the caller knows it */,
@@ -394,7 +469,8 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                        hipEvent_t copied = nullptr /* ... and `stream` waits for this event */,
                        const CallSink *call = nullptr /* call mode: MS values + sites, no intervals */,
                        const PackedIn *packed = nullptr /* the queries arrive 2-bit packed (concat is not read) */,
-                       FusedMap *map = nullptr /* kbo::matches / map: the one kernel where it applies */);
+                       FusedMap *map = nullptr /* kbo::matches / map: the one kernel where it applies */,
+                       const HostStage *hs = nullptr /* strands, upload count */);
 void run_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, bool want_ival,
                    BatchOnDevice &B, hipStream_t stream);
 // A5+A6 over a batch whose offsets are known on the host
@@ -405,7 +481,8 @@ void derand_translate_host_offsets(const uint8_t *d_ms, const uint64_t *d_off, c
 // kbo::matches over a batch (lib.rs:618-627); optional relative_to_ref (lib.rs:756-757); with a sink the
 // characters are turned into run lengths on the device instead of being downloaded (lib.rs:816-820)
 void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink = nullptr);
+                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink = nullptr,
+                        int strands = 0 /* 0: one strand as given; else KBO_STRAND_*: chars_out '+', rev_out '-' */, uint8_t *rev_out = nullptr);
 // the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list; the characters come
 // back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths, or, with a sparse sink, as their runs other than 'M'
 struct PackedBatch {
@@ -415,7 +492,10 @@ struct PackedBatch {
     size_t n_exc;
 };
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink<kbo_rle32> *sink = nullptr, RecordSink<kbo_aln_run> *sparse = nullptr);
+                               uint32_t *packed_out, RleSink<kbo_rle32> *sink = nullptr, RecordSink<kbo_aln_run> *sparse = nullptr,
+                               int strands = 0, uint32_t *rev_out = nullptr);
+// host -> device bytes the calling thread's last host batch staged (kbo_last_batch_staged_bytes)
+extern thread_local uint64_t t_last_staged;
 // A1 over a host batch: MS values, and intervals when lo/hi are given
 void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint8_t *d_out,
                    uint32_t *lo_out, uint32_t *hi_out);

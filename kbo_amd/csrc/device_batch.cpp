@@ -935,3 +935,57 @@ int kbo_sparse_runs_dev(const uint32_t *d_words, const uint64_t *d_offsets, size
                                        reinterpret_cast<uint32_t *>(d_runs), cap, d_n_runs, s));
     });
 }
+
+// ---- the reverse complement of a device-resident batch (revcomp_kernels.hip)
+
+namespace {
+bool dev_ranges_overlap(const void *a, const void *b, uint64_t n)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + n && y < x + n;
+}
+} // namespace
+
+int kbo_revcomp_batch_dev(const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, size_t max_seq_len,
+                          uint8_t *d_out, void *stream)
+{
+    return guarded([&] {
+        (void)max_seq_len; // (the work is cut by output bytes, not by sequence: every shape of batch fills the device alike)
+        KBO_REQUIRE(d_concat && d_offsets && d_out, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < 0xFFFFFFFFull, KBO_E_BAD_ARG, "1 .. 2^32-2 sequences");
+        KBO_REQUIRE(((uintptr_t)d_concat & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_out & 3) == 0, KBO_E_BAD_ARG,
+                    "d_concat must be 16-byte, d_offsets 8-byte, d_out 4-byte aligned");
+        KBO_REQUIRE(total_bases + 16 <= (1ull << 32), KBO_E_UNSUPPORTED, "4 GiB or more of bases in one launch");
+        KBO_REQUIRE(!dev_ranges_overlap(d_concat, d_out, total_bases), KBO_E_BAD_ARG, "d_out overlaps d_concat");
+        HIP_OK(kbo::launch_revcomp_bytes(d_concat, d_offsets, (uint32_t)n_seqs, total_bases, d_out, static_cast<hipStream_t>(stream)));
+    });
+}
+
+size_t kbo_revcomp_packed_scratch_bytes(size_t n_seqs)
+{
+    if (n_seqs == 0 || n_seqs >= (1ull << 28)) return 0;
+    return (kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t) + 15) / 16 * 16;
+}
+
+int kbo_revcomp_packed_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_words, const uint64_t *d_exc_pos,
+                           const uint8_t *d_exc_byte, size_t n_exc, uint32_t *d_words_out, uint64_t *d_exc_pos_out, uint8_t *d_exc_byte_out,
+                           void *d_scratch, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(d_words && d_offsets && d_words_out && d_scratch, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_exc == 0 || (d_exc_pos && d_exc_byte && d_exc_pos_out && d_exc_byte_out), KBO_E_BAD_ARG, "null exception list");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < (1ull << 28), KBO_E_BAD_ARG, "1 .. 2^28-1 sequences");
+        KBO_REQUIRE(total_words < 0xFFFFFF00ull && n_exc < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "2^32 - 256 words or more in one launch");
+        KBO_REQUIRE(((uintptr_t)d_words & 3) == 0 && ((uintptr_t)d_words_out & 3) == 0 && ((uintptr_t)d_offsets & 7) == 0 &&
+                        ((uintptr_t)d_exc_pos & 7) == 0 && ((uintptr_t)d_exc_pos_out & 7) == 0 && ((uintptr_t)d_scratch & 15) == 0,
+                    KBO_E_BAD_ARG, "device buffers must be 4-byte (offsets and positions 8-byte, d_scratch 16-byte) aligned");
+        KBO_REQUIRE(!dev_ranges_overlap(d_words, d_words_out, total_words * 4), KBO_E_BAD_ARG, "d_words_out overlaps d_words");
+        KBO_REQUIRE(n_exc == 0 || (!dev_ranges_overlap(d_exc_pos, d_exc_pos_out, n_exc * 8) && !dev_ranges_overlap(d_exc_byte, d_exc_byte_out, n_exc)),
+                    KBO_E_BAD_ARG, "the exception list's output overlaps its input");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        uint32_t *prefix = static_cast<uint32_t *>(d_scratch);
+        HIP_OK(kbo::launch_packed_prefix(d_offsets, (uint32_t)n_seqs, prefix, s));
+        HIP_OK(kbo::launch_revcomp_packed(d_words, (uint32_t)total_words, d_offsets, (uint32_t)n_seqs, 0u, prefix, prefix + n_seqs + 1u, d_words_out, s));
+        HIP_OK(kbo::launch_revcomp_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, 0, d_offsets, (uint32_t)n_seqs, 0, d_exc_pos_out, d_exc_byte_out, s));
+    });
+}

@@ -114,9 +114,16 @@ struct PhaseClock {
 // `items_keep` must stay alive until the stream has been synchronised.
 void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
                        bool want_ival, BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
-                       uint32_t longest, hipStream_t copy_stream, hipEvent_t copied, const CallSink *call, const PackedIn *packed, FusedMap *map)
+                       uint32_t longest, hipStream_t copy_stream, hipEvent_t copied, const CallSink *call, const PackedIn *packed, FusedMap *map,
+                       const HostStage *hs)
 {
     KBO_REQUIRE(idx->host.k <= 255, KBO_E_UNSUPPORTED, "k > 255");
+    // strands (HostStage): what is uploaded is the first n_up sequences' up_total bases; `rev` = a reverse complement is made of it
+    const int strands = hs ? hs->strands : 1;
+    const bool both = strands == 3, rev = (strands & 2) != 0;
+    KBO_REQUIRE(!both || n_seqs % 2 == 0, KBO_E_BAD_ARG, "both strands: a doubled slab");
+    const size_t n_up = both ? n_seqs / 2 : n_seqs;
+    const uint64_t up_total = both ? offsets[n_up] : offsets[n_seqs];
     const int dev = current_device();
     const std::vector<kbo_index *> shards = shards_of(idx); // (a sharded index: every shard is walked, the maximum kept)
     KBO_REQUIRE(shards.size() == 1 || (!want_ival && !call), KBO_E_UNSUPPORTED,
@@ -146,27 +153,36 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
         B.hi.ensure(total * sizeof(uint32_t));
     }
     hipStream_t up = copy_stream ? copy_stream : stream;
+    auto upload = [&](void *dst, const void *src, size_t n) {
+        HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, up));
+        if (hs && hs->staged) hs->staged->fetch_add(n, std::memory_order_relaxed);
+    };
     const bool uniform = packed && packed->uniform_len != 0;
+    // the '-' strand alone: the upload goes to B.raw and its reverse complement where the walk reads; both: the upload is the
+    // first half of the walk's buffers and its reverse complement the second
+    const size_t up_words = packed ? packed->n_words : 0, up_exc = packed ? packed->n_exc : 0;
+    if (strands == 2) B.raw.ensure(packed ? up_words * 4 + 16 : ((up_total + 15) / 16) * 16 + 16);
     if (packed) { // a quarter of the bytes: 2-bit words + the non-ACGT list; unpacked into B.q below
-        B.packed.ensure(packed->n_words * 4 + 16);
-        HIP_OK(hipMemcpyAsync(B.packed.p, packed->words, packed->n_words * 4, hipMemcpyHostToDevice, up));
-        if (packed->n_exc) {
-            B.exc_pos.ensure(packed->n_exc * 8);
-            B.exc_byte.ensure(packed->n_exc);
-            HIP_OK(hipMemcpyAsync(B.exc_pos.p, packed->exc_pos, packed->n_exc * 8, hipMemcpyHostToDevice, up));
-            HIP_OK(hipMemcpyAsync(B.exc_byte.p, packed->exc_byte, packed->n_exc, hipMemcpyHostToDevice, up));
+        B.packed.ensure((both ? 2 : 1) * up_words * 4 + 16);
+        upload(strands == 2 ? B.raw.p : B.packed.p, packed->words, up_words * 4);
+        if (up_exc) {
+            B.exc_pos.ensure((rev ? 2 : 1) * up_exc * 8);
+            B.exc_byte.ensure((rev ? 2 : 1) * up_exc);
+            upload(B.exc_pos.p, packed->exc_pos, up_exc * 8);
+            upload(B.exc_byte.p, packed->exc_byte, up_exc);
         }
     } else {
-        HIP_OK(hipMemcpyAsync(B.q.p, concat, total, hipMemcpyHostToDevice, up));
+        upload(strands == 2 ? B.raw.p : B.q.p, concat, up_total);
     }
-    if (!uniform) HIP_OK(hipMemcpyAsync(B.off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-    if (!device_items)
-        HIP_OK(hipMemcpyAsync(B.items.p, items_keep.data(), items_keep.size() * sizeof(kbo::WalkItem),
-                              hipMemcpyHostToDevice, up));
+    if (!uniform) upload(B.off.p, offsets, (n_up + 1) * sizeof(uint64_t));
+    if (!device_items) upload(B.items.p, items_keep.data(), items_keep.size() / (both ? 2 : 1) * sizeof(kbo::WalkItem));
     if (copy_stream) {
         HIP_OK(hipEventRecord(copied, copy_stream));
         HIP_OK(hipStreamWaitEvent(stream, copied, 0));
     }
+    if (both && !uniform) HIP_OK(kbo::launch_double_offsets(B.off.as<uint64_t>(), (uint32_t)n_up, stream));
+    if (both && !device_items) // (a sequence's chunks depend on its length alone: the second half's items are the first's, up_total on)
+        HIP_OK(kbo::launch_double_items(B.items.as<kbo::WalkItem>(), (uint32_t)(items_keep.size() / 2), up_total, stream));
     if (packed) {
         if (uniform) HIP_OK(kbo::launch_uniform_offsets(B.off.as<uint64_t>(), (uint32_t)n_seqs, packed->uniform_len, stream));
         else {
@@ -174,16 +190,31 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
             HIP_OK(kbo::launch_packed_prefix(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.pscr.as<uint32_t>(), stream));
         }
     }
-    // the bytes of a packed batch: only when something needs them (the one kernel takes the words as they are)
     const uint32_t wps = uniform ? (packed->uniform_len + 15u) / 16u : 0u;
+    // what the kernels below see of a packed slab: its words and its list, with the '-' strand where asked for
+    const size_t n_words = (both ? 2 : 1) * up_words, n_exc = (both ? 2 : 1) * up_exc;
+    const uint64_t *d_exc_pos = B.exc_pos.as<uint64_t>() + (strands == 2 ? up_exc : 0);
+    const uint8_t *d_exc_byte = B.exc_byte.as<uint8_t>() + (strands == 2 ? up_exc : 0);
+    if (rev && packed) {
+        const uint32_t *pre = uniform ? nullptr : B.pscr.as<uint32_t>();
+        HIP_OK(kbo::launch_revcomp_packed(strands == 2 ? B.raw.as<uint32_t>() : B.packed.as<uint32_t>(), (uint32_t)up_words, B.off.as<uint64_t>(),
+                                          (uint32_t)n_up, wps, pre, pre ? pre + n_seqs + 1u : nullptr,
+                                          B.packed.as<uint32_t>() + (both ? up_words : 0), stream));
+        HIP_OK(kbo::launch_revcomp_exceptions(B.exc_pos.as<uint64_t>(), B.exc_byte.as<uint8_t>(), (uint32_t)up_exc, packed->base, B.off.as<uint64_t>(),
+                                              (uint32_t)n_up, packed->base + (both ? up_total : 0), B.exc_pos.as<uint64_t>() + up_exc,
+                                              B.exc_byte.as<uint8_t>() + up_exc, stream));
+    } else if (rev) {
+        HIP_OK(kbo::launch_revcomp_bytes(strands == 2 ? B.raw.as<uint8_t>() : B.q.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_up, up_total,
+                                         B.q.as<uint8_t>() + (both ? up_total : 0), stream));
+    }
+    // the bytes of a packed batch: only when something needs them (the one kernel takes the words as they are)
     bool have_bytes = !packed;
     auto need_bytes = [&] {
         if (have_bytes) return;
         have_bytes = true;
-        HIP_OK(kbo::launch_unpack2(B.packed.as<uint32_t>(), (uint32_t)packed->n_words, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps,
+        HIP_OK(kbo::launch_unpack2(B.packed.as<uint32_t>(), (uint32_t)n_words, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps,
                                    uniform ? nullptr : B.pscr.as<uint32_t>(), B.q.as<uint8_t>(), stream));
-        HIP_OK(kbo::launch_exceptions(B.exc_pos.as<uint64_t>(), B.exc_byte.as<uint8_t>(), (uint32_t)packed->n_exc, packed->base,
-                                      B.q.as<uint8_t>(), stream));
+        HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
     };
     static const int env_native = std::getenv("KBO_PACKED_NATIVE") ? std::atoi(std::getenv("KBO_PACKED_NATIVE")) : 1; // experiments
     if (device_items) HIP_OK(kbo::launch_make_items(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.items.as<kbo::WalkItem>(), stream));
@@ -222,10 +253,10 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                 a.qp_data = uniform ? nullptr : B.pscr.as<uint32_t>();
                 a.qp_sums = uniform ? nullptr : B.pscr.as<uint32_t>() + n_seqs + 1u;
                 a.packed_out = map->d_packed_out;
-                if (packed->n_exc) {
+                if (n_exc) {
                     B.exc_flag.ensure(n_seqs + 16);
                     HIP_OK(hipMemsetAsync(B.exc_flag.p, 0, n_seqs, stream));
-                    HIP_OK(kbo::launch_flag_exceptions(B.exc_pos.as<uint64_t>(), (uint32_t)packed->n_exc, packed->base, B.off.as<uint64_t>(),
+                    HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, packed->base, B.off.as<uint64_t>(),
                                                        (uint32_t)n_seqs, B.exc_flag.as<uint8_t>(), stream));
                     a.qp_exc = B.exc_flag.as<uint8_t>();
                 }
@@ -233,8 +264,7 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
                 if (count_runs) a.run_counts = map->run_counts;
                 HIP_OK(kbo::launch_map_reads(a, stream));
                 HIP_OK(kbo::launch_unpack_flagged(a.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, B.q.as<uint8_t>(), stream));
-                HIP_OK(kbo::launch_exceptions(B.exc_pos.as<uint64_t>(), B.exc_byte.as<uint8_t>(), (uint32_t)packed->n_exc, packed->base,
-                                              B.q.as<uint8_t>(), stream));
+                HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
                 HIP_OK(kbo::launch_redo_pass(a, stream));
                 HIP_OK(kbo::launch_derand_flagged(B.ms.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, idx->host.k, map->threshold,
                                                   map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, stream,
@@ -581,6 +611,18 @@ struct BatchJob {
     uint64_t word_of(size_t s) const { return pw.empty() ? (uint64_t)s * ((uniform_len + 15u) / 16u) : pw[s]; }
     uint32_t words_per_seq() const { return uniform_len ? (uniform_len + 15u) / 16u : 0u; }
     bool rle_mode() const { return mode == OutMode::Rle || mode == OutMode::Rle32; }
+    // the strands the batch is compared in (KBO_STRAND_*; Chars, Words, Rle, Rle32).  With both, every slab is doubled on the
+    // device (HostStage): uploaded once, walked as 2 ns sequences, and its two halves leave for chars_out / packed_out ('+')
+    // and chars_rev / packed_rev ('-'); a sink puts the records in (sequence, strand) order.  One strand: that destination only.
+    int strands = 1;
+    uint8_t *chars_rev = nullptr;
+    uint32_t *packed_rev = nullptr;
+    std::atomic<uint64_t> *staged = nullptr; // host -> device bytes of the whole batch
+    template <typename T, typename F> void for_strands(T *fwd, T *rev, size_t half, F f) const // f(destination, where the strand begins in the slab's output)
+    {
+        if (strands & 1) f(fwd, (size_t)0);
+        if (strands & 2) f(rev, strands == 3 ? half : (size_t)0);
+    }
 };
 
 // One device's share of a batch: slabs `first`, `first + stride`, ... rotate through the slots of a
@@ -644,13 +686,15 @@ private:
     // a slab as stage() leaves it: what the walk reads and what the mode's output stage needs to know of it
     struct SlabIn {
         const Slab *sl;
-        size_t ns;           // sequences
-        uint64_t bytes;      // bases
-        const uint64_t *off; // slab-relative offsets (pinned)
+        size_t ns;           // sequences ...
+        uint64_t bytes;      // ... and bases as the device sees them: twice the slab's own (hns, hbytes) when both strands run
+        size_t hns;
+        uint64_t hbytes;
+        const uint64_t *off; // slab-relative offsets (pinned), ns + 1
         uint32_t longest;    // longest sequence
         const uint8_t *src;  // the bases (the caller's pinned memory or the slot's staging copy), nullptr for a packed batch ...
         PackedIn pin;        // ... which has this
-        uint64_t w0, n_words; // a packed batch: the slab's first word in the batch's, its number of words
+        uint64_t w0, n_words, hwords; // a packed batch: the slab's first word in the batch's, its words on the device / of its own
     };
 
     // ---- submitting thread: stage the slab, enqueue upload, kernels and the mode's output stage
@@ -677,20 +721,24 @@ private:
         const Slab &sl = job_.slabs[slab_id];
         HostTeam &team = HostTeam::get();
         SlabIn in{};
+        const bool both = job_.strands == 3;
         in.sl = &sl;
-        in.ns = sl.s1 - sl.s0;
-        in.bytes = sl.b1 - sl.b0;
+        in.hns = sl.s1 - sl.s0;
+        in.hbytes = sl.b1 - sl.b0;
+        in.ns = both ? 2 * in.hns : in.hns;
+        in.bytes = both ? 2 * in.hbytes : in.hbytes;
         S.slab_id = slab_id;
         S.n_seqs = in.ns;
-        const size_t ns = in.ns;
-        S.off.ensure((ns + 1) * sizeof(uint64_t));
+        const size_t ns = in.hns;
+        S.off.ensure((in.ns + 1) * sizeof(uint64_t));
         uint64_t *off = S.off.as<uint64_t>();
         const uint64_t *offsets = job_.offsets;
         if (job_.packed && job_.uniform_len && job_.uniform_len <= 255u) { // (reads: below every chunk length, walk_chunk() >= 256)
             // equally long reads, packed: the offsets are made on the device and nothing below reads more of the host
             // copy than its last entry (one item per read, A5/A6 by the longest length)
             off[0] = 0;
-            off[ns] = in.bytes;
+            off[ns] = in.hbytes;
+            off[in.ns] = in.bytes;
             in.longest = job_.uniform_len;
         } else {
             const size_t piece = 1u << 15, n_tasks = (ns + 1 + piece - 1) / piece;
@@ -700,6 +748,7 @@ private:
                 uint64_t m = 0;
                 for (size_t j = a; j < b; j++) {
                     off[j] = offsets[sl.s0 + j] - sl.b0;
+                    if (both && j) off[ns + j] = in.hbytes + off[j]; // (the '-' strands behind the '+' strands)
                     if (j < ns) m = std::max(m, offsets[sl.s0 + j + 1] - offsets[sl.s0 + j]);
                 }
                 longest[t] = m;
@@ -711,9 +760,10 @@ private:
         if (job_.packed) {
             PackedIn &pin = in.pin;
             in.w0 = job_.word_of(sl.s0);
-            in.n_words = job_.word_of(sl.s1) - in.w0;
+            in.hwords = job_.word_of(sl.s1) - in.w0;
+            in.n_words = both ? 2 * in.hwords : in.hwords;
             pin.words = job_.packed->words + in.w0;
-            pin.n_words = (size_t)in.n_words;
+            pin.n_words = (size_t)in.hwords;
             if (!job_.in_pinned) {
                 S.in.ensure(pin.n_words * 4 + 16);
                 team.copy(S.in.p, pin.words, pin.n_words * 4);
@@ -729,8 +779,8 @@ private:
         } else {
             in.src = job_.concat + sl.b0;
             if (!job_.in_pinned) {
-                S.in.ensure(in.bytes);
-                team.copy(S.in.p, in.src, in.bytes);
+                S.in.ensure(in.hbytes);
+                team.copy(S.in.p, in.src, in.hbytes);
                 in.src = S.in.as<uint8_t>();
             }
         }
@@ -740,8 +790,9 @@ private:
     // upload + A1 (or, with `fm`, the one kernel where it applies) on the slot's streams
     void walk(HostSlot &S, const SlabIn &in, FusedMap *fm)
     {
+        const HostStage hs{job_.strands, job_.staged};
         enqueue_walk_host(job_.idx, in.src, in.off, in.ns, job_.lo_out != nullptr, S.B, S.items, C_->st_run, in.longest, C_->st_up,
-                          S.copied, nullptr, job_.packed ? &in.pin : nullptr, fm);
+                          S.copied, nullptr, job_.packed ? &in.pin : nullptr, fm, &hs);
     }
     // kbo::matches / map / find: the characters' buffer (and, words = true, that of their 2-bit words) before the walk, so
     // that the one kernel can write into it
@@ -813,14 +864,13 @@ private:
     {
         FusedMap fm = fused_map(S, in, false);
         walk(S, in, &fm);
-        uint8_t *dst = job_.chars_out + in.sl->b0;
-        if (!job_.out_pinned) {
-            S.out.ensure(in.bytes + 32);
-            dst = S.out.as<uint8_t>();
-        }
+        if (!job_.out_pinned) S.out.ensure(in.bytes + 32);
         chars_after_walk(S, in, fm);
         download_waits_for_kernels(S);
-        HIP_OK(hipMemcpyAsync(dst, S.chars.p, in.bytes, hipMemcpyDeviceToHost, C_->st_down));
+        job_.for_strands(job_.chars_out, job_.chars_rev, in.hbytes, [&](uint8_t *user, size_t at) {
+            uint8_t *dst = job_.out_pinned ? user + in.sl->b0 : S.out.as<uint8_t>() + at;
+            HIP_OK(hipMemcpyAsync(dst, S.chars.as<uint8_t>() + at, in.hbytes, hipMemcpyDeviceToHost, C_->st_down));
+        });
         HIP_OK(hipEventRecord(S.done, C_->st_down));
     }
 
@@ -831,12 +881,11 @@ private:
         walk(S, in, &fm);
         words_after_walk(S, in, fm);
         download_waits_for_kernels(S);
-        uint32_t *dst = job_.packed_out + in.w0;
-        if (!job_.out_pinned) {
-            S.out.ensure((size_t)in.n_words * 4 + 32);
-            dst = S.out.as<uint32_t>();
-        }
-        HIP_OK(hipMemcpyAsync(dst, S.B.packed_out.p, (size_t)in.n_words * 4, hipMemcpyDeviceToHost, C_->st_down));
+        if (!job_.out_pinned) S.out.ensure((size_t)in.n_words * 4 + 32);
+        job_.for_strands(job_.packed_out, job_.packed_rev, (size_t)in.hwords, [&](uint32_t *user, size_t at) {
+            uint32_t *dst = job_.out_pinned ? user + in.w0 : S.out.as<uint32_t>() + at;
+            HIP_OK(hipMemcpyAsync(dst, S.B.packed_out.as<uint32_t>() + at, (size_t)in.hwords * 4, hipMemcpyDeviceToHost, C_->st_down));
+        });
         HIP_OK(hipEventRecord(S.done, C_->st_down));
     }
 
@@ -990,13 +1039,19 @@ private:
     void finish_chars(HostSlot &S)
     {
         const Slab &sl = job_.slabs[S.slab_id];
-        if (!job_.out_pinned) HostTeam::out().copy(job_.chars_out + sl.b0, S.out.p, sl.b1 - sl.b0);
+        if (job_.out_pinned) return;
+        job_.for_strands(job_.chars_out, job_.chars_rev, (size_t)(sl.b1 - sl.b0), [&](uint8_t *user, size_t at) {
+            HostTeam::out().copy(user + sl.b0, S.out.as<uint8_t>() + at, sl.b1 - sl.b0);
+        });
     }
     void finish_words(HostSlot &S)
     {
         const Slab &sl = job_.slabs[S.slab_id];
         const uint64_t w0 = job_.word_of(sl.s0), w1 = job_.word_of(sl.s1);
-        if (!job_.out_pinned) HostTeam::out().copy(job_.packed_out + w0, S.out.p, (size_t)(w1 - w0) * 4);
+        if (job_.out_pinned) return;
+        job_.for_strands(job_.packed_out, job_.packed_rev, (size_t)(w1 - w0), [&](uint32_t *user, size_t at) {
+            HostTeam::out().copy(user + w0, S.out.as<uint32_t>() + at, (size_t)(w1 - w0) * 4);
+        });
     }
     template <typename T> void finish_rle(HostSlot &S, RleSink<T> &sink)
     {
@@ -1136,36 +1191,57 @@ BatchJob make_job(OutMode mode, kbo_index *idx, const uint64_t *offsets, size_t 
 
 } // namespace
 
-void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink)
+thread_local uint64_t t_last_staged = 0;
+
+namespace {
+// the strands of a job (0: a single-strand entry point) and its upload count; slabs of half the bytes when they are doubled
+size_t strand_slab_bytes(size_t bytes, int strands) { return strands == 3 ? std::max<size_t>(bytes / 2, 1u << 15) : bytes; }
+void run_counted(BatchJob &job)
 {
-    KBO_REQUIRE(idx && (chars_out || sink), KBO_E_BAD_ARG, "null argument");
+    std::atomic<uint64_t> staged{0};
+    job.staged = &staged;
+    run_on_devices(job);
+    t_last_staged = staged.load();
+}
+} // namespace
+
+void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink, int strands, uint8_t *rev_out)
+{
+    KBO_REQUIRE(strands >= 0 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(idx && (sink || ((chars_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))), KBO_E_BAD_ARG, "null argument");
     PhaseClock clk;
     const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
     KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
     checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
     clk.lap("argument checks");
-    BatchJob job = make_job(sink ? OutMode::Rle : OutMode::Chars, idx, offsets, n_seqs, slab_bytes_for(idx), threshold, clk);
+    BatchJob job = make_job(sink ? OutMode::Rle : OutMode::Chars, idx, offsets, n_seqs, strand_slab_bytes(slab_bytes_for(idx), strands),
+                            threshold, clk);
     job.concat = concat;
     job.in_pinned = is_pinned_host(concat);
+    job.strands = strands ? strands : 1;
     if (sink) {
         job.rle = sink;
         job.max_gap_len = sink->max_gap_len;
+        sink->strands = strands;
         sink->begin(job.slabs, n_seqs, job.n_workers == 1);
     } else {
         job.format = format;
         job.chars_out = chars_out;
-        job.out_pinned = is_pinned_host(chars_out);
+        job.chars_rev = rev_out;
+        job.out_pinned = (!(job.strands & 1) || is_pinned_host(chars_out)) && (!(job.strands & 2) || is_pinned_host(rev_out));
     }
     clk.lap("slab list");
-    run_on_devices(job);
+    run_counted(job);
 }
 
 // kbo::matches / kbo::find over a batch of 2-bit packed reads: the same pipeline, a quarter of the bytes over PCIe each way
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse)
+                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse, int strands, uint32_t *rev_out)
 {
-    KBO_REQUIRE(idx && in.words && (packed_out || sink || sparse), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!sparse || !strands), KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(idx && in.words && (sink || sparse || ((packed_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))),
+                KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(in.n_exc == 0 || (in.exc_pos && in.exc_byte), KBO_E_BAD_ARG, "null exception list");
     PhaseClock clk;
     const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
@@ -1177,8 +1253,9 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
                     "exception positions must ascend and lie inside the batch");
     clk.lap("argument checks");
     const OutMode mode = sink ? OutMode::Rle32 : sparse ? OutMode::Sparse : OutMode::Words;
-    BatchJob job = make_job(mode, idx, offsets, n_seqs, packed_slab_bytes(idx), threshold, clk);
+    BatchJob job = make_job(mode, idx, offsets, n_seqs, strand_slab_bytes(packed_slab_bytes(idx), strands), threshold, clk);
     job.packed = &in;
+    job.strands = strands ? strands : 1;
     job.in_pinned = is_pinned_host(in.words);
     if (scan.shortest == scan.longest) {
         job.uniform_len = (uint32_t)scan.longest;
@@ -1190,16 +1267,18 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
     if (sink) {
         job.rle32 = sink;
         job.max_gap_len = sink->max_gap_len;
+        sink->strands = strands;
         sink->begin(job.slabs, n_seqs, job.n_workers == 1);
     } else if (sparse) {
         job.sparse = sparse;
         sparse->begin(job.slabs.size(), n_seqs, job.n_workers == 1);
     } else {
         job.packed_out = packed_out;
-        job.out_pinned = is_pinned_host(packed_out);
+        job.packed_rev = rev_out;
+        job.out_pinned = (!(job.strands & 1) || is_pinned_host(packed_out)) && (!(job.strands & 2) || is_pinned_host(rev_out));
     }
     clk.lap("slab list");
-    run_on_devices(job);
+    run_counted(job);
 }
 
 // A1 over a host batch: MS values (and intervals) only
@@ -1220,7 +1299,7 @@ void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offset
     job.hi_out = hi_out;
     job.in_pinned = is_pinned_host(concat);
     job.out_pinned = is_pinned_host(d_out) && (!lo_out || (is_pinned_host(lo_out) && is_pinned_host(hi_out)));
-    run_on_devices(job);
+    run_counted(job);
 }
 
 void release_host_scratch()

@@ -1441,3 +1441,107 @@ int kbo_set_walk_waves_per_cu(int waves_per_cu)
 }
 
 } // extern "C"
+
+// ---- both strands (revcomp_kernels.hip; host_batch.cpp doubles every slab on the device) ---------------------------------------
+
+namespace {
+inline uint8_t complement_byte(uint8_t c)
+{
+    switch (c) {
+    case 'A': return 'T';
+    case 'T': return 'A';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'a': return 't';
+    case 't': return 'a';
+    case 'c': return 'g';
+    case 'g': return 'c';
+    default: return c;
+    }
+}
+bool ranges_overlap(const void *a, const void *b, uint64_t n)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + n && y < x + n;
+}
+void require_strands(int strands) { KBO_REQUIRE(strands >= 1 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both"); }
+} // namespace
+
+int kbo_revcomp_batch(const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint8_t *out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(concat && offsets && out, KBO_E_BAD_ARG, "null argument");
+        for (size_t s = 0; s < n_seqs; s++) KBO_REQUIRE(offsets[s + 1] >= offsets[s], KBO_E_BAD_ARG, "offsets not monotone");
+        KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] must be 0");
+        const uint64_t total = offsets[n_seqs];
+        KBO_REQUIRE(!ranges_overlap(concat, out, total), KBO_E_BAD_ARG, "out overlaps concat");
+        // pieces of the OUTPUT, so that a few long sequences keep every thread as busy as many short ones
+        const uint64_t piece = 1u << 18;
+        HostTeam::get().run((size_t)((total + piece - 1) / piece), [&](size_t t) {
+            const uint64_t a = t * piece, b = std::min(total, a + piece);
+            size_t s = std::upper_bound(offsets, offsets + n_seqs + 1, a) - offsets - 1; // the sequence that holds base a
+            for (uint64_t p = a; p < b;) {
+                while (p >= offsets[s + 1]) s++;
+                const uint64_t e = std::min(b, offsets[s + 1]), mirror = offsets[s] + offsets[s + 1] - 1;
+                for (; p < e; p++) out[p] = complement_byte(concat[mirror - p]);
+            }
+        });
+    });
+}
+
+int kbo_matches_batch_strands(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                              int format, int strands, uint8_t *out_fwd, uint8_t *out_rev)
+{
+    return guarded([&] {
+        require_strands(strands);
+        matches_batch_impl(idx, concat, offsets, n_seqs, max_error_prob, format != 0, out_fwd, nullptr, strands, out_rev);
+    });
+}
+
+int kbo_find_batch_strands(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_find_opts *opts,
+                           int strands, kbo_rle **rles, uint64_t *rle_offsets)
+{
+    return guarded([&] {
+        require_strands(strands);
+        KBO_REQUIRE(idx && rles && rle_offsets, KBO_E_BAD_ARG, "null argument");
+        kbo_find_opts o;
+        if (opts) o = *opts; else kbo_find_opts_default(&o);
+        RleSink<kbo_rle> sink;
+        sink.max_gap_len = o.max_gap_len;
+        sink.rle_offsets = rle_offsets;
+        matches_batch_impl(idx, concat, offsets, n_seqs, o.max_error_prob, false, nullptr, &sink, strands);
+        sink.take(rles);
+    });
+}
+
+int kbo_matches_batch_packed_strands(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                                     const uint8_t *exc_byte, size_t n_exc, double max_error_prob, int strands, uint32_t *words_fwd,
+                                     uint32_t *words_rev)
+{
+    return guarded([&] {
+        require_strands(strands);
+        KBO_REQUIRE(idx && words, KBO_E_BAD_ARG, "null argument");
+        const PackedBatch in{words, exc_pos, exc_byte, n_exc};
+        matches_batch_packed_impl(idx, in, offsets, n_seqs, max_error_prob, words_fwd, nullptr, nullptr, strands, words_rev);
+    });
+}
+
+int kbo_find_batch_packed_strands(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                                  const uint8_t *exc_byte, size_t n_exc, const kbo_find_opts *opts, int strands, kbo_rle32 **rles,
+                                  uint64_t *rle_offsets)
+{
+    return guarded([&] {
+        require_strands(strands);
+        KBO_REQUIRE(idx && words && rles && rle_offsets, KBO_E_BAD_ARG, "null argument");
+        kbo_find_opts o;
+        if (opts) o = *opts; else kbo_find_opts_default(&o);
+        RleSink<kbo_rle32> sink;
+        sink.max_gap_len = o.max_gap_len;
+        sink.rle_offsets = rle_offsets;
+        const PackedBatch in{words, exc_pos, exc_byte, n_exc};
+        matches_batch_packed_impl(idx, in, offsets, n_seqs, o.max_error_prob, nullptr, &sink, nullptr, strands);
+        sink.take(rles);
+    });
+}
+
+uint64_t kbo_last_batch_staged_bytes(void) { return t_last_staged; }

@@ -438,6 +438,22 @@ hipError_t launch_exceptions(const uint64_t *d_pos, const uint8_t *d_byte, uint3
 hipError_t launch_pack2(const uint8_t *d_chars, uint32_t n_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps,
                         const uint32_t *d_scratch, uint32_t *d_packed, hipStream_t stream);
 
+// the reverse complement of a batch (revcomp_kernels.hip), per sequence: output base i = complement of input base len - 1 - i
+// (A <-> T, C <-> G, a <-> t, c <-> g, other bytes as they are).  Bytes: d_in 16-byte aligned with the usual 16 bytes of slack,
+// d_out anywhere; exactly [d_out, d_out + total) is written; sequences may be empty.  Packed: the layout above (d_data / d_sums:
+// the scanned words-per-sequence and its block sums unless uniform_wps != 0), padding bits of the output zero.  The exception
+// list mirrored within each sequence, ascending again: position p (pos - base in the batch of d_off) -> out_base + off[s] +
+// off[s + 1] - 1 - p, the byte complemented.  None of them works in place.
+hipError_t launch_revcomp_bytes(const uint8_t *d_in, const uint64_t *d_off, uint32_t n_seqs, uint64_t total, uint8_t *d_out, hipStream_t stream);
+hipError_t launch_revcomp_packed(const uint32_t *d_in, uint32_t n_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps,
+                                 const uint32_t *d_data, const uint32_t *d_sums, uint32_t *d_out, hipStream_t stream);
+hipError_t launch_revcomp_exceptions(const uint64_t *d_pos, const uint8_t *d_byte, uint32_t n, uint64_t base, const uint64_t *d_off,
+                                     uint32_t n_seqs, uint64_t out_base, uint64_t *d_pos_out, uint8_t *d_byte_out, hipStream_t stream);
+// a batch doubled on the device: off[n + 1 + j] = off[n] + off[j + 1] (d_off holds 2 n + 1 entries), items[n + i] = items[i]
+// `shift` bases on
+hipError_t launch_double_offsets(uint64_t *d_off, uint32_t n_seqs, hipStream_t stream);
+hipError_t launch_double_items(WalkItem *d_items, uint32_t n_items, uint64_t shift, hipStream_t stream);
+
 // the sparse form of kbo::matches (sparse_kernels.hip): the runs of characters other than 'M' of a packed batch's character words
 // (the layout above), as kbo_aln_run records {seq_base + seq, start, (length << 2) | code} in (seq, start) order.  d_prefix: the
 // scanned words-per-sequence (launch_packed_prefix) unless uniform_wps != 0; d_scratch: kSparseScratchWords u32.  n_blocks =

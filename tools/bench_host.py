@@ -35,6 +35,76 @@ def pinned_like(a):
 _KEEP = []
 if PINNED:
     concat, out = pinned_like(concat), pinned_like(out)
+if os.environ.get("STRANDS"):  # both strands of every read: kbo_*_batch_strands (staged once, the '-' strand made on the device)
+    # against the route without them: kbo_revcomp_batch on the host + two calls of the single-strand entry point.  Five runs
+    # each, interleaved; medians.  STRANDS=kernels: the two revcomp kernels and a device-to-device copy of the same bytes,
+    # for one rocprofv3 --kernel-trace --stats run
+    import ctypes as C
+    import statistics
+    rng = np.random.default_rng(11)
+    flip = np.flatnonzero(rng.random(R) < 0.5)  # half of the reads come from the other strand
+    v = concat.reshape(R, 150)
+    v[flip] = batch.revcomp_batch(v[flip].reshape(-1), np.arange(len(flip) + 1, dtype=np.uint64) * 150).reshape(-1, 150)
+    words, pos, byt = batch.pack_reads(concat, offsets)
+    if os.environ["STRANDS"] == "kernels":
+        import torch
+        dev = torch.device("cuda:0")
+        st = torch.cuda.current_stream(dev).cuda_stream
+        d_q = torch.zeros(len(concat) + 64, dtype=torch.uint8, device=dev)
+        d_q[:len(concat)] = torch.from_numpy(concat).to(dev)
+        d_o, d_c = torch.empty_like(d_q), torch.empty_like(d_q)
+        d_off = torch.from_numpy(offsets.view(np.int64)).to(dev)
+        d_w = torch.from_numpy(words.view(np.int32)).to(dev)
+        d_wo, d_wc = torch.empty_like(d_w), torch.empty_like(d_w)
+        d_scr = torch.empty(L.kbo_revcomp_packed_scratch_bytes(R), dtype=torch.uint8, device=dev)
+        for _ in range(5):
+            kbo_amd.check(L.kbo_revcomp_batch_dev(d_q.data_ptr(), d_off.data_ptr(), R, len(concat), 150, d_o.data_ptr(), st))
+            kbo_amd.check(L.kbo_revcomp_packed_dev(d_w.data_ptr(), d_off.data_ptr(), R, len(words), None, None, 0, d_wo.data_ptr(), None, None,
+                                                   d_scr.data_ptr(), st))
+            d_c.copy_(d_q)    # the yardsticks: device-to-device copies of the same bytes
+            d_wc.copy_(d_w)
+        torch.cuda.synchronize()
+        ok = np.array_equal(d_o.cpu().numpy()[:len(concat)], batch.revcomp_batch(concat, offsets))
+        print(f"revcomp kernels: {len(concat) / 1e6:.0f} MB of bases, {len(words) * 4 / 1e6:.0f} MB of words, 5 launches each; bytes equal the host helper's: {ok}")
+        sys.exit(0)
+    fwd, rev = np.zeros(len(concat), dtype=np.uint8), np.zeros(len(concat), dtype=np.uint8)
+    rc = np.zeros(len(concat), dtype=np.uint8)
+    wf, wr = np.zeros(len(words), dtype=np.uint32), np.zeros(len(words), dtype=np.uint32)
+    rwords = np.zeros(len(words), dtype=np.uint32)
+    ne = C.c_size_t(0)
+    h, o = sbwt._h, offsets.ctypes.data
+
+    def bytes_new():
+        kbo_amd.check(L.kbo_matches_batch_strands(h, concat.ctypes.data, o, R, 1e-7, 0, 3, fwd.ctypes.data, rev.ctypes.data))
+
+    def bytes_two_calls():
+        kbo_amd.check(L.kbo_revcomp_batch(concat.ctypes.data, o, R, rc.ctypes.data))
+        kbo_amd.check(L.kbo_matches_batch(h, concat.ctypes.data, o, R, 1e-7, fwd.ctypes.data))
+        kbo_amd.check(L.kbo_matches_batch(h, rc.ctypes.data, o, R, 1e-7, rev.ctypes.data))
+
+    def packed_new():
+        kbo_amd.check(L.kbo_matches_batch_packed_strands(h, words.ctypes.data, o, R, None, None, 0, 1e-7, 3, wf.ctypes.data, wr.ctypes.data))
+
+    def packed_two_calls():  # (a caller that holds bytes: reverse complement, pack, two calls)
+        kbo_amd.check(L.kbo_revcomp_batch(concat.ctypes.data, o, R, rc.ctypes.data))
+        kbo_amd.check(L.kbo_pack_reads(rc.ctypes.data, o, R, rwords.ctypes.data, None, None, 0, C.byref(ne)))
+        kbo_amd.check(L.kbo_matches_batch_packed(h, words.ctypes.data, o, R, None, None, 0, 1e-7, wf.ctypes.data))
+        kbo_amd.check(L.kbo_matches_batch_packed(h, rwords.ctypes.data, o, R, None, None, 0, 1e-7, wr.ctypes.data))
+
+    for name, new, old in (("bytes", bytes_new, bytes_two_calls), ("packed", packed_new, packed_two_calls)):
+        new(), old()  # (warm: device copy, pinned staging)
+        t = {"new": [], "two calls": []}
+        for _ in range(5):
+            for what, f in (("new", new), ("two calls", old)):
+                t0 = time.perf_counter()
+                f()
+                t[what].append(time.perf_counter() - t0)
+        for what in t:
+            ms = sorted(x * 1e3 for x in t[what])
+            print(f"strands, {name:6s} {what:9s}: median {statistics.median(ms):7.1f} ms ({2 * R * 150 / statistics.median(ms) / 1e6:6.1f} Gbp/s of strand-bases), "
+                  f"runs {' '.join('%.1f' % x for x in ms)}", flush=True)
+    print("staged by the last call:", batch.last_batch_staged_bytes(), "bytes for", len(words) * 4, "bytes of words")
+    sys.exit(0)
 if os.environ.get("PACKED"):  # 2-bit words in, 2-bit words / runs other than 'M' / run lengths out (kbo_matches_batch_packed,
     # kbo_matches_batch_sparse, kbo_find_batch_packed)
     import ctypes as C
