@@ -85,6 +85,22 @@ pub mod ffi {
                                      exc_byte: *const u8, n_exc: usize, opts: *const KboFindOpts, rles: *mut *mut KboRle32,
                                      rle_offsets: *mut u64) -> c_int;
         // both strands of every sequence in one call, the batch staged to the device once (kbo_hip.h "both strands")
+        pub fn kbo_summary_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64,
+                                 summary_out: *mut super::AlnSummary) -> c_int;
+        pub fn kbo_summary_batch_packed(idx: *mut KboIndex, words: *const u32, offsets: *const u64, n_seqs: usize, exc_pos: *const u64,
+                                        exc_byte: *const u8, n_exc: usize, p: f64, summary_out: *mut super::AlnSummary) -> c_int;
+        pub fn kbo_summary_work_bytes(idx: *mut KboIndex, n_seqs: usize, total_bases: u64, max_seq_len: usize) -> usize;
+        pub fn kbo_summary_batch_dev(idx: *mut KboIndex, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                     max_seq_len: usize, p: f64, d_ms: *mut u8, d_summary_out: *mut super::AlnSummary, d_work: *mut c_void,
+                                     work_bytes: usize, stream: *mut c_void, tail_stream: *mut c_void, fused: *mut c_int) -> c_int;
+        pub fn kbo_summary_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, max_seq_len: usize,
+                               d_summary_out: *mut super::AlnSummary, stream: *mut c_void) -> c_int;
+        pub fn kbo_summary_words_work_bytes(n_seqs: usize) -> usize;
+        pub fn kbo_summary_words_dev(d_words: *const u32, d_offsets: *const u64, n_seqs: usize, max_seq_len: usize,
+                                     d_summary_out: *mut super::AlnSummary, d_work: *mut c_void, stream: *mut c_void) -> c_int;
+        pub fn kbo_map_stream_submit_summary(ms: *mut KboMapStream, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                             max_seq_len: usize, p: f64, d_summary_out: *mut super::AlnSummary, ready_stream: *mut c_void,
+                                             ticket: *mut u64, fused: *mut c_int) -> c_int;
         pub fn kbo_revcomp_batch(concat: *const u8, offsets: *const u64, n_seqs: usize, out: *mut u8) -> c_int;
         pub fn kbo_matches_batch_strands(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, format: c_int,
                                          strands: c_int, out_fwd: *mut u8, out_rev: *mut u8) -> c_int;
@@ -268,6 +284,37 @@ pub fn find_batch(reads: &[Vec<u8>], idx: &GpuIndex, opts: kbo::FindOpts) -> Vec
         start: r.start as usize, end: r.end as usize, matches: r.matches as usize, mismatches: r.mismatches as usize,
         jumps: r.jumps as usize, gap_bases: r.gap_bases as usize, gap_opens: r.gap_opens as usize }).collect()).collect();
     unsafe { ffi::kbo_free(p as *mut c_void) };
+    out
+}
+
+/// `kbo_aln_summary`: what `kbo::matches` returns for one sequence, counted on the device - its numbers of 'M', 'X' and 'R' and of
+/// maximal stretches without '-' (the runs `kbo::find` reports with `max_gap_len = 0`).  The '-' are `len - (n_match + n_mismatch + n_jump)`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct AlnSummary {
+    pub n_match: u32,
+    pub n_mismatch: u32,
+    pub n_jump: u32,
+    pub n_runs: u32,
+}
+
+/// One `AlnSummary` per read, 2-bit packed on the way in and 16 bytes per read on the way back (`kbo_summary_batch_packed`):
+/// screening, presence / absence, identity and coverage.  Reads of up to 160 bases over an index with a depth table are counted inside the
+/// mapping kernel and no character is ever made; longer sequences keep a byte per base in device memory, counted there by a second kernel -
+/// either way no character crosses PCIe.  Panics (through `check`, like the other wrappers) when the library refuses the batch: every
+/// read must have 3 bases or more (`kbo::matches` asserts the same), and the batch must not be empty.
+pub fn summary_batch(reads: &[Vec<u8>], idx: &GpuIndex, opts: kbo::MatchOpts) -> Vec<AlnSummary> {
+    let mut offsets = vec![0u64; reads.len() + 1];
+    for (i, r) in reads.iter().enumerate() { offsets[i + 1] = offsets[i] + r.len() as u64; }
+    let concat: Vec<u8> = reads.concat();
+    let mut words = vec![0u32; unsafe { ffi::kbo_packed_words(offsets.as_ptr(), reads.len()) }];
+    let cap = concat.iter().filter(|b| !matches!(**b, b'A' | b'C' | b'G' | b'T')).count();
+    let (mut exc_pos, mut exc_byte, mut n_exc) = (vec![0u64; cap], vec![0u8; cap], 0usize);
+    check(unsafe { ffi::kbo_pack_reads(concat.as_ptr(), offsets.as_ptr(), reads.len(), words.as_mut_ptr(), exc_pos.as_mut_ptr(),
+                                       exc_byte.as_mut_ptr(), cap, &mut n_exc) });
+    let mut out = vec![AlnSummary::default(); reads.len()];
+    check(unsafe { ffi::kbo_summary_batch_packed(idx.0, words.as_ptr(), offsets.as_ptr(), reads.len(), exc_pos.as_ptr(), exc_byte.as_ptr(),
+                                                 n_exc, opts.max_error_prob, out.as_mut_ptr()) });
     out
 }
 

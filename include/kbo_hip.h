@@ -385,6 +385,28 @@ int kbo_matches_batch_sparse(kbo_index_t *idx, const uint32_t *words, const uint
 int kbo_sparse_expand(const kbo_aln_run *runs, uint64_t n_runs, const uint64_t *offsets, size_t n_seqs, const uint8_t *ref_concat,
                       uint8_t *out);
 
+/* ------------------------------------------------------------------ per-sequence alignment summaries
+ * Read screening, decontamination, presence / absence and identity / coverage tables reduce kbo::matches' characters to a few
+ * counts per sequence; these entry points do that on the device, and 16 bytes per sequence leave it instead of a character (or two
+ * bits) per base.  The record of one sequence describes the characters kbo_matches_batch returns for it: n_match, n_mismatch and
+ * n_jump are its numbers of 'M', 'X' and 'R'; n_runs is the number of maximal stretches without '-' (what kbo_find_batch counts
+ * with max_gap_len = 0); the number of '-' is len - (n_match + n_mismatch + n_jump).  A sequence of fewer than 3 bases has no
+ * alignment (the reference asserts, derandomize.rs:274-276): the device-resident entry points give it an all-zero record, the host
+ * entry points refuse the batch as kbo_matches_batch does.  Both strands: kbo_revcomp_batch_dev / kbo_revcomp_packed_dev, then a
+ * summary of each.  There is no relative_to_ref form: the summary is of kbo::matches' characters. */
+typedef struct {
+    uint32_t n_match, n_mismatch, n_jump, n_runs;
+} kbo_aln_summary; /* 16 bytes */
+/* kbo_matches_batch / kbo_matches_batch_packed with the records as output: summary_out holds n_seqs records (the caller's; the library
+ * allocates nothing).  Inputs, checks and error codes are those of kbo_matches_batch / kbo_matches_batch_packed; the same slab
+ * pipeline, over the devices of kbo_set_devices and over sharded indexes alike; a slab downloads 16 bytes per sequence.  A slab of reads
+ * (at most 160 bases, a copy with a depth table) goes through map_reads_kernel's summary form - bytes in, or the words as they are - and
+ * makes no character at all; any other slab keeps its characters on the device and a reducer counts them there. */
+int kbo_summary_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                      kbo_aln_summary *summary_out);
+int kbo_summary_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                             const uint8_t *exc_byte, size_t n_exc, double max_error_prob, kbo_aln_summary *summary_out);
+
 /* ------------------------------------------------------------------ both strands
  * A read comes from either strand of what the index was built of, a gene lies on either strand of an assembly.  Instead of an
  * index built with add_revcomp (twice the rows and plan structures; a human-scale index then has 2^32 rows or more and becomes
@@ -590,6 +612,48 @@ int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_
 size_t kbo_sparse_runs_work_bytes(size_t n_seqs, uint64_t total_words);
 int kbo_sparse_runs_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, void *d_work,
                         kbo_aln_run *d_runs, size_t capacity, uint32_t *d_n_runs, void *stream);
+/* ---- alignment summaries (kbo_aln_summary, above) of device-resident batches; asynchronous, the library never synchronises.
+ * kbo_summary_batch_dev: kbo::matches over the batch as kbo_map_batch_dev_tail runs it (format = 0: the same routes, streams and
+ * second pass on `tail_stream`; the records are complete when BOTH streams have reached this point), with d_summary_out - n_seqs records,
+ * 16-byte aligned, nothing beyond them is written - as the only output.  Reads (max_seq_len 1 .. 160) over an unsharded copy with a
+ * depth table: map_reads_kernel counts the characters while they are in LDS and stores a record per read, its second pass the records of
+ * the reads it leaves - no character and no MS value reaches memory (*fused = 1), d_ms is not touched, and the batch is planned whatever
+ * the batches before it did to the copy's plan.  Every other batch - longer sequences, no depth table, a sharded index - runs as
+ * kbo_map_batch_dev_tail does (*fused as there) with the characters in d_work, and a reducer (summary_kernels.hip) counts them there.
+ * d_ms: total_bases + 16 bytes, 4-byte aligned (scratch of those routes).  d_work: kbo_summary_work_bytes() bytes, 16-byte aligned -
+ * exact for the route the batch takes on the current device: what the walk needs for the one kernel, kbo_index_work_bytes() plus the
+ * characters (total_bases + 16, rounded up to 64) otherwise.  What "exact" rests on: the route is decided from the index's copy on the
+ * current device and the process-wide settings AT THE TIME OF THE QUERY - the query makes that copy (an upload, as kbo_index_to_device) if
+ * there is none yet, so that the copy's depth table and path cover are there to be looked at - and kbo_summary_batch_dev decides again by
+ * the same rule.  Both agree as long as kbo_set_plan, kbo_set_plan_stats - counted batches take the second route -, the handle's depth-table
+ * option and the environment's KBO_MAP_FINISH are not changed in between; the copy's hold-off after a batch that gave its plan up does
+ * NOT change the route.  When they disagree nothing is overrun: a d_work smaller than the batch's route needs is refused with
+ * KBO_E_BAD_ARG, a larger one is accepted.  A caller that wants one size for any route takes the larger figure:
+ * kbo_index_work_bytes() + total_bases + 16 rounded up to 64, + 64.  0 = bad arguments.  Errors as kbo_map_batch_dev_tail. */
+size_t kbo_summary_work_bytes(kbo_index_t *idx, size_t n_seqs, uint64_t total_bases, size_t max_seq_len);
+int kbo_summary_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                          size_t max_seq_len, double max_error_prob, uint8_t *d_ms, kbo_aln_summary *d_summary_out, void *d_work,
+                          size_t work_bytes, void *stream, void *tail_stream, int *fused);
+/* The reducer alone, for characters the caller already has: one byte a character at d_chars + d_offsets[s] (kbo_matches_batch's
+ * M - X R; any other byte counts as none of the three and does not end a run; d_chars of any alignment, no slack needed; d_offsets[0]
+ * need not be 0 - only the aligned 16-byte blocks that hold a character of a sequence are read), or
+ * (kbo_summary_words_dev) the 2-bit character words of kbo_matches_batch_packed / kbo_matches_packed_dev.  A sequence of fewer than 3
+ * bases gets zeros whatever its characters are.  Sequences of any length: a wave takes 1 KiB of characters, a contig is reduced by as
+ * many waves as it has KiB and a run that crosses from one to the next is counted once.  max_seq_len = the longest sequence if known
+ * (it bounds the grid), 0 = unknown.  d_summary_out: n_seqs records, 16-byte aligned; d_offsets 8-byte aligned.  kbo_summary_words_dev's
+ * d_work: kbo_summary_words_work_bytes(n_seqs) bytes, 16-byte aligned (0 from it: too many sequences). */
+int kbo_summary_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, kbo_aln_summary *d_summary_out,
+                    void *stream);
+size_t kbo_summary_words_work_bytes(size_t n_seqs);
+int kbo_summary_words_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, kbo_aln_summary *d_summary_out,
+                          void *d_work, void *stream);
+/* kbo_map_stream_submit for a summary batch: the same pipelines, slots and tickets (kbo_map_stream_wait / _wait_on / _sync); a stream
+ * takes character batches and summary batches in any order.  d_summary_out as for kbo_summary_batch_dev; the slots' buffers serve as
+ * d_work and d_ms (a batch that does not take the one kernel keeps its characters in a buffer the slot gets when the first summary batch
+ * that takes that route comes - a hipMalloc inside that one submit; streams of reads never make it). */
+int kbo_map_stream_submit_summary(kbo_map_stream_t *ms, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                  size_t max_seq_len, double max_error_prob, kbo_aln_summary *d_summary_out, void *ready_stream,
+                                  uint64_t *ticket, int *fused);
 /* Options of ONE index handle: what the process-wide setters below and in kbo_hip_tuning.h (kbo_set_devices, kbo_set_slab_bytes,
  * kbo_set_plan, kbo_set_depth_table, kbo_set_depth_table_anchors) decide for every index, decided for this one - two indexes of one
  * process (a small reference next to a large one; a service with one handle per tenant) no longer share them.  A field left at its

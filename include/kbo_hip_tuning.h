@@ -192,6 +192,9 @@ int kbo_index_build_device_phases(double out[9]);
  * packed and *_strands forms) copied from the host to the device: bases or words, exception lists, offsets, work items.  A batch
  * run in both strands stages what it stages for one (tests/test_gpu_strands.py). */
 uint64_t kbo_last_batch_staged_bytes(void);
+/* inspection / tests: slabs of kbo_summary_batch[_packed] since the process started, by route - records straight from map_reads_kernel's
+ * summary form and its second pass (no character made), or characters on the device and the reducer over them.  Either may be NULL. */
+int kbo_summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs);
 /* Test hook: the number of workgroups kbo_sparse_runs_dev launches its count and emit kernels with for these arguments (1 .. 2048;
  * max_seq_len = 0, unknown: the most; 0 for arguments it refuses) */
 uint32_t kbo_sparse_runs_blocks(size_t n_seqs, size_t max_seq_len);

@@ -114,6 +114,8 @@ SYMBOLS = [
     "kbo_matches_batch_sparse", "kbo_sparse_expand", "kbo_sparse_runs_work_bytes", "kbo_sparse_runs_dev",
     "kbo_revcomp_batch", "kbo_matches_batch_strands", "kbo_find_batch_strands", "kbo_matches_batch_packed_strands",
     "kbo_find_batch_packed_strands", "kbo_revcomp_batch_dev", "kbo_revcomp_packed_scratch_bytes", "kbo_revcomp_packed_dev",
+    "kbo_summary_batch", "kbo_summary_batch_packed", "kbo_summary_work_bytes", "kbo_summary_batch_dev", "kbo_summary_dev",
+    "kbo_summary_words_work_bytes", "kbo_summary_words_dev", "kbo_map_stream_submit_summary",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -122,7 +124,7 @@ TUNING_SYMBOLS = [
     "kbo_set_plan_unit_cap_divisor", "kbo_index_plan_holdoff", "kbo_set_walk_experiment", "kbo_plan_stats_dev", "kbo_set_plan_stats", "kbo_set_index_shards", "kbo_index_shard", "kbo_set_depth_table", "kbo_set_depth_table_anchors", "kbo_index_depth_table", "kbo_run_automaton_depths",
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
-    "kbo_last_batch_staged_bytes",
+    "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes",
 ]
 
 _lib = None
@@ -292,6 +294,15 @@ def lib():
     L.kbo_index_get_opts.argtypes = [vp, C.POINTER(IndexOpts)]
     L.kbo_map_batch_dev_tail.argtypes = [vp, vp, vp, sz, u64, sz, dbl, C.c_int, C.c_int, vp, vp, vp, sz, vp, vp, C.POINTER(C.c_int)]
     L.kbo_index_device_layout.argtypes = [vp, C.c_int, C.POINTER(DeviceLayout)]
+    L.kbo_summary_slab_routes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+    L.kbo_summary_batch.argtypes = [vp, vp, vp, sz, dbl, vp]
+    L.kbo_summary_batch_packed.argtypes = [vp, vp, vp, sz, vp, vp, sz, dbl, vp]
+    L.kbo_summary_work_bytes.argtypes = [vp, sz, u64, sz]; L.kbo_summary_work_bytes.restype = sz
+    L.kbo_summary_batch_dev.argtypes = [vp, vp, vp, sz, u64, sz, dbl, vp, vp, vp, sz, vp, vp, C.POINTER(C.c_int)]
+    L.kbo_summary_dev.argtypes = [vp, vp, sz, sz, vp, vp]
+    L.kbo_summary_words_work_bytes.argtypes = [sz]; L.kbo_summary_words_work_bytes.restype = sz
+    L.kbo_summary_words_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+    L.kbo_map_stream_submit_summary.argtypes = [vp, vp, vp, sz, u64, sz, dbl, vp, vp, vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 

@@ -191,6 +191,56 @@ def expand_sparse(runs, offsets, ref=None):
     return out
 
 
+def summary_of_chars(chars, offsets):
+    """The per-sequence alignment summaries (kbo_hip.h kbo_aln_summary) of kbo::matches' characters, in plain numpy: an (n, 4) uint32
+    array of [n_match ('M'), n_mismatch ('X'), n_jump ('R'), n_runs (maximal stretches without '-')]; all zero for a sequence
+    of fewer than 3 bases (no alignment: derandomize.rs:274-276), whatever its characters are.  What the device entry points
+    are tested against."""
+    chars = np.frombuffer(chars, dtype=np.uint8) if isinstance(chars, (bytes, bytearray)) else np.asarray(chars, dtype=np.uint8)
+    offsets = np.asarray(offsets, dtype=np.uint64).astype(np.int64)
+    n = len(offsets) - 1
+    out = np.zeros((max(n, 0), 4), dtype=np.uint32)
+    if n <= 0:
+        return out
+    lens = np.diff(offsets)
+    total = int(offsets[-1])
+    c = chars[:total]
+    csum = np.zeros((4, total + 1), dtype=np.int64)
+    for j, ch in enumerate(b"MXR"):
+        np.cumsum(c == ch, out=csum[j, 1:])
+    nd = c != ord("-")
+    starts = nd.copy()                      # a run starts at a character that is not '-' ...
+    starts[1:] &= ~nd[:-1]                  # ... behind one that is ...
+    heads = offsets[:-1][lens > 0]
+    starts[heads] = nd[heads]               # ... or at the head of its sequence
+    np.cumsum(starts, out=csum[3, 1:])
+    for j in range(4):
+        out[:, j] = csum[j, offsets[1:]] - csum[j, offsets[:-1]]
+    out[lens < 3] = 0
+    return out
+
+
+def summary_batch(sbwt, seqs, max_error_prob=1e-7, packed=False):
+    """kbo_summary_batch / kbo_summary_batch_packed: kbo::matches over every sequence, counted on the device -> (n, 4) uint32
+    [n_match, n_mismatch, n_jump, n_runs] (summary_of_chars of matches_batch's characters; 16 bytes per sequence come back).
+    seqs: (concat, offsets), or a list of bytes-like sequences.  packed: the reads cross to the device as 2-bit words."""
+    if isinstance(seqs, tuple) and len(seqs) == 2:
+        concat, offsets = seqs
+    else:
+        seqs = [np.frombuffer(bytes(q), dtype=np.uint8) for q in seqs]
+        concat = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint8)
+        offsets = np.concatenate([[0], np.cumsum([len(q) for q in seqs])]).astype(np.uint64)
+    concat, offsets, n = _prep(concat, offsets)
+    out = np.zeros((max(n, 1), 4), dtype=np.uint32)
+    if packed:
+        words, epos, ebyt = pack_reads(concat, offsets)
+        check(lib().kbo_summary_batch_packed(sbwt._h, words.ctypes.data, offsets.ctypes.data, n, epos.ctypes.data if len(epos) else None,
+                                             ebyt.ctypes.data if len(ebyt) else None, len(epos), max_error_prob, out.ctypes.data))
+    else:
+        check(lib().kbo_summary_batch(sbwt._h, concat.ctypes.data, offsets.ctypes.data, n, max_error_prob, out.ctypes.data))
+    return out[:n]
+
+
 def find_batch_packed(sbwt, words, offsets, exc_pos, exc_byte, find_opts=None):
     from . import FindOpts
     o = find_opts if find_opts is not None else FindOpts()
@@ -539,6 +589,36 @@ class DeviceBatch:
         self.fused = bool(fused.value)
 
 
+    def _summary_buffers(self):
+        torch = self.torch
+        if getattr(self, "summary", None) is None:
+            with torch.cuda.device(self.device):
+                self.summary = torch.zeros((self.n_seqs, 4), dtype=torch.int32, device=self.device)
+                self.summary_work_bytes = int(lib().kbo_summary_work_bytes(self.sbwt._h, self.n_seqs, self.total, self.max_len))
+                self.summary_work = torch.zeros(self.summary_work_bytes // 8 + 2, dtype=torch.int64, device=self.device)
+
+    def run_summary(self, stream=None, tail_stream=None):
+        """kbo_summary_batch_dev: self.summary ([n_seqs, 4] int32: n_match, n_mismatch, n_jump, n_runs) of kbo::matches' characters,
+        which are never stored when the one kernel takes the batch (self.fused)"""
+        self._summary_buffers()
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        t = tail_stream if tail_stream is not None else s
+        fused = C.c_int(0)
+        check(lib().kbo_summary_batch_dev(self.sbwt._h, self.q.data_ptr(), self.off.data_ptr(), self.n_seqs, self.total, self.max_len,
+                                          self.max_error_prob, self.ms.data_ptr(), self.summary.data_ptr(), self.summary_work.data_ptr(),
+                                          self.summary_work_bytes, s.cuda_stream, t.cuda_stream, C.byref(fused)))
+        self.fused = bool(fused.value)
+
+    def summary_of_device_chars(self, stream=None):
+        """kbo_summary_dev over self.chars (as run() left them) -> self.summary"""
+        self._summary_buffers()
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        check(lib().kbo_summary_dev(self.chars.data_ptr(), self.off.data_ptr(), self.n_seqs, self.max_len, self.summary.data_ptr(), s.cuda_stream))
+
+    def summary_host(self):
+        return self.summary.cpu().numpy().view(np.uint32)
+
+
 def stream_pair(device, tail_cus=-1):
     """(stream, tail_stream) as torch streams, made by the library (kbo_hip.h kbo_stream_pair_create): the tail stream - a batch's second
     pass - on compute units of its own.  The pair lives as long as the process (the torch wrappers do not own the streams)."""
@@ -567,6 +647,17 @@ class MapStream:
         check(lib().kbo_map_stream_submit(self._h, dev.q.data_ptr(), dev.off.data_ptr(), dev.n_seqs, dev.total, dev.max_len, dev.max_error_prob,
                                           int(dev.format), dev.ms.data_ptr() if dev.want_ms else None, dev.chars.data_ptr(),
                                           ready_stream.cuda_stream if ready_stream is not None else None, C.byref(t), C.byref(fused)))
+        dev.fused = bool(fused.value)
+        return int(t.value)
+
+    def submit_summary(self, dev, ready_stream=None):
+        """kbo_map_stream_submit_summary: the alignment summaries of a DeviceBatch's sequences into dev.summary -> ticket"""
+        dev._summary_buffers()
+        t = C.c_uint64(0)
+        fused = C.c_int(0)
+        check(lib().kbo_map_stream_submit_summary(self._h, dev.q.data_ptr(), dev.off.data_ptr(), dev.n_seqs, dev.total, dev.max_len,
+                                                  dev.max_error_prob, dev.summary.data_ptr(),
+                                                  ready_stream.cuda_stream if ready_stream is not None else None, C.byref(t), C.byref(fused)))
         dev.fused = bool(fused.value)
         return int(t.value)
 

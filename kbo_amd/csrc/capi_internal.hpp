@@ -452,6 +452,10 @@ struct FusedMap {
     // one kernel (and, for the reads of its second pass, derand_flagged_kernel) filled it: scan + emit are what is left
     uint32_t *run_counts = nullptr;
     bool counted = false;
+    // kbo_summary_batch[_packed]: where the sequences' records go (n_seqs x 16 bytes); summarized = the one kernel's summary form and
+    // its second pass wrote them and no character was made, else the characters are in d_chars for the reducer (summary_kernels.hip)
+    uint4 *d_summary = nullptr;
+    bool summarized = false;
 };
 // Strands of a host batch (kbo_*_batch_strands) and the count of what it uploads.  strands = KBO_STRAND_FWD: the slab as it is;
 // KBO_STRAND_REV: its reverse complement, made on the device from the uploaded slab; both: the slab DOUBLED on the device -
@@ -482,7 +486,8 @@ void derand_translate_host_offsets(const uint8_t *d_ms, const uint64_t *d_off, c
 // characters are turned into run lengths on the device instead of being downloaded (lib.rs:816-820)
 void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
                         double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink = nullptr,
-                        int strands = 0 /* 0: one strand as given; else KBO_STRAND_*: chars_out '+', rev_out '-' */, uint8_t *rev_out = nullptr);
+                        int strands = 0 /* 0: one strand as given; else KBO_STRAND_*: chars_out '+', rev_out '-' */, uint8_t *rev_out = nullptr,
+                        kbo_aln_summary *summary_out = nullptr /* kbo_summary_batch: n_seqs records instead of the characters */);
 // the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list; the characters come
 // back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths, or, with a sparse sink, as their runs other than 'M'
 struct PackedBatch {
@@ -491,9 +496,10 @@ struct PackedBatch {
     const uint8_t *exc_byte;
     size_t n_exc;
 };
+void summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs);
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
                                uint32_t *packed_out, RleSink<kbo_rle32> *sink = nullptr, RecordSink<kbo_aln_run> *sparse = nullptr,
-                               int strands = 0, uint32_t *rev_out = nullptr);
+                               int strands = 0, uint32_t *rev_out = nullptr, kbo_aln_summary *summary_out = nullptr);
 // host -> device bytes the calling thread's last host batch staged (kbo_last_batch_staged_bytes)
 extern thread_local uint64_t t_last_staged;
 // A1 over a host batch: MS values, and intervals when lo/hi are given

@@ -120,7 +120,8 @@ CopyView copy_view(kbo_index *idx, uint64_t total_bases)
 // map_reads_kernel's arguments over a batch of reads (one item per read; the kernel and its second pass read the offsets themselves:
 // no item list is made)
 kbo::WalkArgs reads_args(const CopyView &c, const DevWork &w, void *d_work, const uint8_t *q, const uint64_t *d_offsets,
-                         uint64_t total_bases, uint32_t longest, uint8_t *d_ms, uint8_t *chars_out, uint32_t thr, bool format, bool want_ms)
+                         uint64_t total_bases, uint32_t longest, uint8_t *d_ms, uint8_t *chars_out, uint32_t thr, bool format, bool want_ms,
+                         bool whatever_the_holdoff = false /* planned even while the copy's plan is held off (summary batches) */)
 {
     kbo::WalkArgs a{};
     a.ix = c.ix;
@@ -130,7 +131,7 @@ kbo::WalkArgs reads_args(const CopyView &c, const DevWork &w, void *d_work, cons
     a.n_items = w.n_slots;
     a.d_out = d_ms;
     a.max_item_len = longest;
-    attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, c.plan);
+    attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, whatever_the_holdoff ? nullptr : c.plan);
     a.chars_out = chars_out;
     a.map_thr = thr;
     a.map_fmt = format ? 1u : 0u;
@@ -482,7 +483,7 @@ void run_lengths(const FindTail &f, const uint8_t *d_chars, const uint64_t *d_of
 int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                        size_t max_seq_len, double max_error_prob, int format, int want_ms, uint8_t *d_ms, uint8_t *d_chars_out,
                        void *d_work, size_t work_bytes, void *stream, void *tail_stream, int *fused, const FindTail *find = nullptr,
-                       bool urgent_tail = false)
+                       bool urgent_tail = false, uint4 *summary_of_chars = nullptr)
 {
     if (fused) *fused = 0;
     return guarded([&] {
@@ -540,6 +541,8 @@ int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t
         // the run lengths of the kernels' own characters: on the two-kernel route no run for a sequence of fewer than 3 bases, whose bytes
         // of d_chars_out it leaves unwritten (kbo_run_lengths_dev would count runs in whatever the caller's buffer held there)
         if (find) run_lengths(*find, d_chars_out, d_offsets, n, longest, ts, true, counted);
+        // kbo_summary_batch_dev's batches that do not take map_reads_kernel's summary form: the records off the characters, behind them
+        if (summary_of_chars) HIP_OK(kbo::launch_summary_bytes(d_chars_out, d_offsets, n, total_bases, summary_of_chars, ts));
         if (fused) *fused = one_kernel ? 1 : 0;
     });
 }
@@ -572,6 +575,138 @@ int kbo_map_batch_dev_tail(kbo_index_t *idx, const uint8_t *d_concat, const uint
 {
     return map_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, want_ms, d_ms, d_chars_out,
                               d_work, work_bytes, stream, tail_stream, fused);
+}
+
+// ---- per-sequence alignment summaries (kbo_aln_summary): kbo::matches' characters counted on the device, 16 bytes a sequence
+namespace {
+// Two routes.  Reads over an unsharded copy that map_reads_kernel takes: the kernel's summary form and finish_reads_kernel's - no
+// character and no MS value is stored, d_work is the walk's alone.  Every other batch: kbo_map_batch_dev_tail's routes with the
+// characters in d_work behind the map's own regions, and the reducer (summary_kernels.hip) over them.
+struct SummaryWork {
+    bool one_kernel;
+    size_t chars_off, bytes; // (one_kernel: no characters, chars_off == bytes)
+};
+size_t summary_chars_bytes(uint64_t total_bases) { return ((size_t)total_bases + 16 + 63) / 64 * 64; }
+SummaryWork summary_work(const kbo_index *idx, const kbo::DevIndexView *ix, const DevWork &w, size_t max_seq_len, uint64_t total_bases)
+{
+    SummaryWork sw{};
+    const bool long_seqs = max_seq_len == 0 || max_seq_len > 160;
+    sw.one_kernel = !idx->sharded() && !long_seqs && !w.chunked && ix && !g_plan_stats.load() &&
+                    kbo::map_reads_summary_applies(*ix, (uint32_t)max_seq_len);
+    sw.chars_off = sw.one_kernel ? w.bytes : (w.map_min + 63) / 64 * 64;
+    sw.bytes = sw.one_kernel ? w.bytes : sw.chars_off + summary_chars_bytes(total_bases);
+    return sw;
+}
+
+// slot_chars: a pipeline slot's buffer for the characters of the second route (made here, slot_chars_bytes, when the first batch that takes
+// that route comes) - null: they go into d_work at SummaryWork::chars_off (work_bytes covers them)
+int summary_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                           size_t max_seq_len, double max_error_prob, uint8_t *d_ms, kbo_aln_summary *d_summary_out, void *d_work,
+                           size_t work_bytes, DevBuf *slot_chars, size_t slot_chars_bytes, void *stream, void *tail_stream, int *fused,
+                           bool urgent_tail)
+{
+    uint8_t *d_chars = nullptr;
+    if (fused) *fused = 0;
+    bool generic = false;
+    size_t map_bytes = 0;
+    int rc = guarded([&] {
+        require_batch(idx && d_concat && d_offsets && d_ms && d_summary_out && d_work, n_seqs, total_bases, {d_concat, d_work, d_summary_out}, {d_ms},
+                      "d_concat/d_work/d_summary_out must be 16-byte, d_ms 4-byte aligned");
+        const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob);
+        KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
+        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k, idx->sharded());
+        CopyView c;
+        if (!idx->sharded()) c = copy_view(idx, total_bases);
+        const SummaryWork sw = summary_work(idx, idx->sharded() ? nullptr : &c.ix, w, max_seq_len, total_bases);
+        KBO_REQUIRE(work_bytes >= (slot_chars ? (sw.one_kernel ? w.bytes : w.map_min) : sw.bytes), KBO_E_BAD_ARG,
+                    "d_work is smaller than kbo_summary_work_bytes() for this batch");
+        if (!sw.one_kernel) {
+            generic = true;
+            map_bytes = w.map_min;
+            if (slot_chars) { // (a pipeline's slot: its character buffer is made when the first batch that needs one comes, and kept)
+                if (!slot_chars->p) slot_chars->alloc(slot_chars_bytes);
+                d_chars = slot_chars->as<uint8_t>();
+            } else {
+                d_chars = static_cast<uint8_t *>(d_work) + sw.chars_off;
+            }
+            return;
+        }
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        // (planned whatever the copy's hold-off says - summary_work: the route is the copy's and the batch's alone -, and a batch that
+        // leaves most of its reads to the second pass still reports it: the character batches behind it honour the hold-off)
+        kbo::WalkArgs a = reads_args(c, w, d_work, d_concat, d_offsets, total_bases, (uint32_t)max_seq_len, nullptr, nullptr, (uint32_t)threshold,
+                                     false, false, true);
+        a.summary_out = reinterpret_cast<uint4 *>(d_summary_out);
+        KBO_REQUIRE(a.gitems && kbo::map_reads_applies(a) && kbo::map_reads_finish_applies(a), KBO_E_UNSUPPORTED, "the summary form of map_reads_kernel does not apply");
+        a.host_bailed = c.plan ? c.plan->bailed : nullptr;
+        const hipStream_t ts = map_reads_then(a, s, static_cast<hipStream_t>(tail_stream), [&](hipStream_t t) {
+            HIP_OK(kbo::launch_map_reads_finish(a, t, urgent_tail && t != s));
+        });
+        if (!a.host_bailed) plan_after_launch(a, ts, c.plan);
+        if (fused) *fused = 1;
+    });
+    if (rc != KBO_OK || !generic) return rc;
+    return map_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, 0, 0, d_ms, d_chars, d_work, map_bytes,
+                              stream, tail_stream, fused, nullptr, urgent_tail, reinterpret_cast<uint4 *>(d_summary_out));
+}
+} // namespace
+
+size_t kbo_summary_work_bytes(kbo_index_t *idx, size_t n_seqs, uint64_t total_bases, size_t max_seq_len)
+{
+    size_t bytes = 0;
+    (void)guarded([&] {
+        KBO_REQUIRE(idx && n_seqs > 0 && total_bases > 0, KBO_E_BAD_ARG, "null / empty argument");
+        const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k, idx->sharded());
+        CopyView c;
+        if (!idx->sharded()) c = copy_view(idx, 0);
+        bytes = summary_work(idx, idx->sharded() ? nullptr : &c.ix, w, max_seq_len, total_bases).bytes;
+    });
+    return bytes;
+}
+
+int kbo_summary_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                          size_t max_seq_len, double max_error_prob, uint8_t *d_ms, kbo_aln_summary *d_summary_out, void *d_work,
+                          size_t work_bytes, void *stream, void *tail_stream, int *fused)
+{
+    return summary_batch_dev_impl(idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, d_ms, d_summary_out, d_work,
+                                  work_bytes, nullptr, 0, stream, tail_stream, fused, false);
+}
+
+int kbo_summary_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, kbo_aln_summary *d_summary_out,
+                    void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(d_chars && d_offsets && d_summary_out, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < (1ull << 31), KBO_E_BAD_ARG, "1 .. 2^31-1 sequences");
+        KBO_REQUIRE(((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_summary_out & 15) == 0, KBO_E_BAD_ARG,
+                    "d_offsets must be 8-byte, d_summary_out 16-byte aligned");
+        const uint64_t bound = max_seq_len && max_seq_len < (1ull << 32) ? (uint64_t)n_seqs * max_seq_len : 0;
+        HIP_OK(kbo::launch_summary_bytes(d_chars, d_offsets, (uint32_t)n_seqs, bound, reinterpret_cast<uint4 *>(d_summary_out),
+                                         static_cast<hipStream_t>(stream)));
+    });
+}
+
+size_t kbo_summary_words_work_bytes(size_t n_seqs)
+{
+    if (n_seqs == 0 || n_seqs >= (1ull << 31)) return 0;
+    return (kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t) + 15) / 16 * 16;
+}
+
+int kbo_summary_words_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, kbo_aln_summary *d_summary_out,
+                          void *d_work, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(d_words && d_offsets && d_summary_out && d_work, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < (1ull << 31), KBO_E_BAD_ARG, "1 .. 2^31-1 sequences");
+        KBO_REQUIRE(((uintptr_t)d_words & 3) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_summary_out & 15) == 0 &&
+                        ((uintptr_t)d_work & 15) == 0,
+                    KBO_E_BAD_ARG, "d_words must be 4-byte, d_offsets 8-byte, d_summary_out and d_work 16-byte aligned");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        uint32_t *prefix = static_cast<uint32_t *>(d_work);
+        const uint64_t bound = max_seq_len && max_seq_len < (1ull << 32) ? (uint64_t)n_seqs * max_seq_len : 0;
+        HIP_OK(kbo::launch_packed_prefix(d_offsets, (uint32_t)n_seqs, prefix, s));
+        HIP_OK(kbo::launch_summary_words(d_words, d_offsets, (uint32_t)n_seqs, prefix, bound, reinterpret_cast<uint4 *>(d_summary_out), s));
+    });
 }
 
 // ---- kbo_map_stream_*: pipelines of (kernel stream, second-pass stream), two slots each
@@ -648,6 +783,7 @@ struct kbo_map_stream {
     bool urgent = false; // the pipelines are make_urgent_pair's (batches of reads), not make_stream_pair's
     struct Slot {
         DevBuf work, ms;
+        DevBuf chars; // (summary batches that do not take the one kernel: their characters - made when the first such batch comes)
         hipEvent_t done = nullptr;
         uint64_t ticket = 0; // the batch that used it last (0: none yet)
     };
@@ -711,9 +847,10 @@ int kbo_map_stream_create(kbo_index_t *idx, int pipelines, size_t max_seqs, uint
     });
 }
 
-int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
-                          size_t max_seq_len, double max_error_prob, int format, uint8_t *d_ms_out, uint8_t *d_chars_out, void *ready_stream,
-                          uint64_t *ticket, int *fused)
+namespace {
+// one batch into the next pipeline and slot; run(slot, kernels' stream, second passes' stream) enqueues it and returns its code
+template <class Run>
+int map_stream_submit_impl(kbo_map_stream_t *m, size_t n_seqs, uint64_t total_bases, size_t max_seq_len, void *ready_stream, uint64_t *ticket, Run run)
 {
     if (!m) {
         last_error() = "kbo_map_stream_submit: null stream";
@@ -742,9 +879,7 @@ int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const ui
         }
     });
     if (rc != KBO_OK) return rc;
-    rc = map_batch_dev_impl(m->idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, d_ms_out ? 1 : 0,
-                            d_ms_out ? d_ms_out : sl.ms.as<uint8_t>(), d_chars_out, sl.work.p, m->work_bytes, kern, tail, fused, nullptr,
-                            m->urgent);
+    rc = run(sl, kern, tail);
     if (rc != KBO_OK) return rc;
     rc = guarded([&] { // complete when both streams have come this far
         HIP_OK(hipEventRecord(m->kdone, kern));
@@ -756,6 +891,28 @@ int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const ui
     sl.ticket = n + 1;
     if (ticket) *ticket = n + 1;
     return KBO_OK;
+}
+} // namespace
+
+int kbo_map_stream_submit(kbo_map_stream_t *m, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                          size_t max_seq_len, double max_error_prob, int format, uint8_t *d_ms_out, uint8_t *d_chars_out, void *ready_stream,
+                          uint64_t *ticket, int *fused)
+{
+    return map_stream_submit_impl(m, n_seqs, total_bases, max_seq_len, ready_stream, ticket, [&](kbo_map_stream::Slot &sl, hipStream_t kern, hipStream_t tail) {
+        return map_batch_dev_impl(m->idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, format, d_ms_out ? 1 : 0,
+                                  d_ms_out ? d_ms_out : sl.ms.as<uint8_t>(), d_chars_out, sl.work.p, m->work_bytes, kern, tail, fused, nullptr,
+                                  m->urgent);
+    });
+}
+
+int kbo_map_stream_submit_summary(kbo_map_stream_t *m, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                  size_t max_seq_len, double max_error_prob, kbo_aln_summary *d_summary_out, void *ready_stream, uint64_t *ticket,
+                                  int *fused)
+{
+    return map_stream_submit_impl(m, n_seqs, total_bases, max_seq_len, ready_stream, ticket, [&](kbo_map_stream::Slot &sl, hipStream_t kern, hipStream_t tail) {
+        return summary_batch_dev_impl(m->idx, d_concat, d_offsets, n_seqs, total_bases, max_seq_len, max_error_prob, sl.ms.as<uint8_t>(), d_summary_out,
+                                      sl.work.p, m->work_bytes, &sl.chars, summary_chars_bytes(m->max_bases) + 64, kern, tail, fused, m->urgent);
+    });
 }
 
 namespace {

@@ -245,6 +245,47 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
             a.map_thr = map->threshold;
             a.map_fmt = map->format ? 1u : 0u;
             a.map_want_ms = 0;
+            // kbo_summary_batch[_packed]: the kernel's summary form - reads as bytes, or (packed-native, direct form) as words - and
+            // finish_reads_kernel's behind it, over the bytes of the reads the kernel listed: records, no characters, no MS values
+            if (map->d_summary && !map->format && a.gitems && !a.pstats) {
+                kbo::WalkArgs sa = a;
+                sa.chars_out = nullptr;
+                sa.d_out = nullptr;
+                sa.summary_out = map->d_summary;
+                const bool native = packed && env_native && kbo::map_reads_packed_applies(sa, false);
+                if (native) {
+                    sa.qp = B.packed.as<uint32_t>();
+                    sa.qp_wps = wps;
+                    sa.qp_data = uniform ? nullptr : B.pscr.as<uint32_t>();
+                    sa.qp_sums = uniform ? nullptr : B.pscr.as<uint32_t>() + n_seqs + 1u;
+                    if (n_exc) {
+                        B.exc_flag.ensure(n_seqs + 16);
+                        HIP_OK(hipMemsetAsync(B.exc_flag.p, 0, n_seqs, stream));
+                        HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, packed->base, B.off.as<uint64_t>(),
+                                                           (uint32_t)n_seqs, B.exc_flag.as<uint8_t>(), stream));
+                        sa.qp_exc = B.exc_flag.as<uint8_t>();
+                    }
+                } else {
+                    need_bytes();
+                }
+                kbo::WalkArgs fa = sa; // (the second pass reads bytes: those of the listed reads are unpacked for it)
+                fa.qp = nullptr;
+                fa.seq_off = B.off.as<uint64_t>();
+                if (kbo::map_reads_applies(sa) && kbo::map_reads_finish_applies(fa)) {
+                    HIP_OK(kbo::launch_map_reads(sa, stream));
+                    if (native) {
+                        HIP_OK(kbo::launch_unpack_flagged(sa.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, sa.qp_data, sa.redo, B.q.as<uint8_t>(), stream));
+                        HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
+                    }
+                    fa = sa;
+                    fa.qp = nullptr;
+                    fa.seq_off = B.off.as<uint64_t>();
+                    HIP_OK(kbo::launch_map_reads_finish(fa, stream));
+                    plan_after_launch(sa, stream, plan_state);
+                    map->done = map->summarized = true;
+                    return;
+                }
+            }
             if (packed && env_native && a.gitems && kbo::map_reads_packed_applies(a, map->d_packed_out != nullptr)) {
                 // packed-native: the words go into the kernel as they are and (kbo_matches_batch_packed) the characters leave it
                 // as words; only the reads it leaves to the plain walk get their bytes, and their characters are packed behind it
@@ -438,6 +479,7 @@ struct HostSlot {
     size_t rle_capacity = 0, rle_count = 0; // records the emit has room for / the slab has (known once its kernels are done)
     // sparse output (kbo_matches_batch_sparse): runs per workgroup + scan, the records, their number (device word, pinned copy)
     DevBuf sp_scratch, sp_runs, sp_total;
+    DevBuf summary; // kbo_summary_batch[_packed]: the slab's records
     PinBuf sp_total_pin;
     size_t sp_capacity = 0, sp_spec = 0; // records the emit has room for / the download took behind the count, unasked
     uint32_t sp_blocks = 0;
@@ -572,6 +614,9 @@ void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team)
 // lib.rs:756-757; run lengths lib.rs:816-820): every slab is staged, walked, and leaves by its mode's output stage
 namespace {
 
+// slabs of kbo_summary_batch[_packed] by the route they took (kbo_hip_tuning.h kbo_summary_slab_routes)
+std::atomic<uint64_t> g_summary_kernel_slabs{0}, g_summary_reducer_slabs{0};
+
 // what leaves the device for a slab of a host batch, and where it goes
 enum class OutMode {
     Ms,     // kbo_ms_batch: the MS values (and the intervals, when lo / hi are given)
@@ -580,6 +625,7 @@ enum class OutMode {
     Rle,    // kbo_find_batch, kbo_find_batch_into: run-length records, widened to kbo_rle
     Rle32,  // kbo_find_batch_packed: run-length records as the device writes them
     Sparse, // kbo_matches_batch_sparse: the runs of characters other than 'M'
+    Summary, // kbo_summary_batch, kbo_summary_batch_packed: one kbo_aln_summary per sequence, the characters stay on the device
 };
 
 // what a batch call hands to its per-device workers
@@ -603,6 +649,7 @@ struct BatchJob {
     RleSink<kbo_rle> *rle = nullptr;               // Rle
     RleSink<kbo_rle32> *rle32 = nullptr;           // Rle32
     RecordSink<kbo_aln_run> *sparse = nullptr;     // Sparse
+    kbo_aln_summary *summary_out = nullptr;        // Summary: n_seqs records
     size_t max_gap_len = 0;                        // Rle, Rle32: FindOpts' max_gap_len
     // a packed batch (kbo_matches_batch_packed / kbo_find_batch_packed / kbo_matches_batch_sparse): 2-bit words in
     const PackedBatch *packed = nullptr;
@@ -712,6 +759,7 @@ private:
         case OutMode::Rle:
         case OutMode::Rle32: submit_rle(S, in); break;
         case OutMode::Sparse: submit_sparse(S, in); break;
+        case OutMode::Summary: submit_summary(S, in); break;
         }
     }
 
@@ -919,6 +967,29 @@ private:
         download_waits_for_kernels(S);
     }
 
+    // one record per sequence: the characters (bytes; a packed batch's reads go through the packed-native kernel that writes bytes) are
+    // counted where they are (summary_kernels.hip) and 16 bytes a sequence leave
+    void submit_summary(HostSlot &S, const SlabIn &in)
+    {
+        FusedMap fm = fused_map(S, in, false);
+        S.summary.ensure(in.ns * sizeof(kbo_aln_summary));
+        fm.d_summary = S.summary.as<uint4>();
+        walk(S, in, &fm);
+        (fm.summarized ? g_summary_kernel_slabs : g_summary_reducer_slabs).fetch_add(1);
+        if (!fm.summarized) { // (longer sequences, no depth table, a sharded index, a held-off copy: characters, then the reducer)
+            chars_after_walk(S, in, fm);
+            HIP_OK(kbo::launch_summary_bytes(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)in.ns, in.bytes, S.summary.as<uint4>(), C_->st_run));
+        }
+        download_waits_for_kernels(S);
+        kbo_aln_summary *dst = job_.summary_out + in.sl->s0;
+        if (!job_.out_pinned) {
+            S.out.ensure(in.ns * sizeof(kbo_aln_summary));
+            dst = S.out.as<kbo_aln_summary>();
+        }
+        HIP_OK(hipMemcpyAsync(dst, S.summary.p, in.ns * sizeof(kbo_aln_summary), hipMemcpyDeviceToHost, C_->st_down));
+        HIP_OK(hipEventRecord(S.done, C_->st_down));
+    }
+
     // only the runs of characters other than 'M': counted, scanned and (speculatively, into the room the slot has) emitted
     // behind the words, and downloaded with their number as many as the slabs before had (no round trip per slab); the
     // completing thread fetches the rest, if any (fetch_sparse_rest)
@@ -1015,6 +1086,7 @@ private:
         case OutMode::Rle: finish_rle(S, *job_.rle); break;
         case OutMode::Rle32: finish_rle(S, *job_.rle32); break;
         case OutMode::Sparse: finish_sparse(S); break;
+        case OutMode::Summary: finish_summary(S); break;
         }
         S.busy = false;
         {
@@ -1052,6 +1124,12 @@ private:
         job_.for_strands(job_.packed_out, job_.packed_rev, (size_t)(w1 - w0), [&](uint32_t *user, size_t at) {
             HostTeam::out().copy(user + w0, S.out.as<uint32_t>() + at, (size_t)(w1 - w0) * 4);
         });
+    }
+    void finish_summary(HostSlot &S)
+    {
+        const Slab &sl = job_.slabs[S.slab_id];
+        if (job_.out_pinned) return;
+        HostTeam::out().copy(job_.summary_out + sl.s0, S.out.p, (sl.s1 - sl.s0) * sizeof(kbo_aln_summary));
     }
     template <typename T> void finish_rle(HostSlot &S, RleSink<T> &sink)
     {
@@ -1206,17 +1284,18 @@ void run_counted(BatchJob &job)
 } // namespace
 
 void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink, int strands, uint8_t *rev_out)
+                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink, int strands, uint8_t *rev_out,
+                        kbo_aln_summary *summary_out)
 {
-    KBO_REQUIRE(strands >= 0 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
-    KBO_REQUIRE(idx && (sink || ((chars_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!summary_out || (!strands && !sink && !format)), KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(idx && (sink || summary_out || ((chars_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))), KBO_E_BAD_ARG, "null argument");
     PhaseClock clk;
     const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
     KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
     checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
     clk.lap("argument checks");
-    BatchJob job = make_job(sink ? OutMode::Rle : OutMode::Chars, idx, offsets, n_seqs, strand_slab_bytes(slab_bytes_for(idx), strands),
-                            threshold, clk);
+    BatchJob job = make_job(sink ? OutMode::Rle : summary_out ? OutMode::Summary : OutMode::Chars, idx, offsets, n_seqs,
+                            strand_slab_bytes(slab_bytes_for(idx), strands), threshold, clk);
     job.concat = concat;
     job.in_pinned = is_pinned_host(concat);
     job.strands = strands ? strands : 1;
@@ -1225,6 +1304,9 @@ void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *o
         job.max_gap_len = sink->max_gap_len;
         sink->strands = strands;
         sink->begin(job.slabs, n_seqs, job.n_workers == 1);
+    } else if (summary_out) {
+        job.summary_out = summary_out;
+        job.out_pinned = is_pinned_host(summary_out);
     } else {
         job.format = format;
         job.chars_out = chars_out;
@@ -1237,10 +1319,12 @@ void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *o
 
 // kbo::matches / kbo::find over a batch of 2-bit packed reads: the same pipeline, a quarter of the bytes over PCIe each way
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse, int strands, uint32_t *rev_out)
+                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse, int strands, uint32_t *rev_out,
+                               kbo_aln_summary *summary_out)
 {
-    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!sparse || !strands), KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
-    KBO_REQUIRE(idx && in.words && (sink || sparse || ((packed_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))),
+    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!sparse || !strands) && (!summary_out || (!strands && !sink && !sparse)), KBO_E_BAD_ARG,
+                "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(idx && in.words && (sink || sparse || summary_out || ((packed_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))),
                 KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(in.n_exc == 0 || (in.exc_pos && in.exc_byte), KBO_E_BAD_ARG, "null exception list");
     PhaseClock clk;
@@ -1252,7 +1336,7 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
         KBO_REQUIRE(in.exc_pos[x] < offsets[n_seqs] && (x == 0 || in.exc_pos[x] > in.exc_pos[x - 1]), KBO_E_BAD_ARG,
                     "exception positions must ascend and lie inside the batch");
     clk.lap("argument checks");
-    const OutMode mode = sink ? OutMode::Rle32 : sparse ? OutMode::Sparse : OutMode::Words;
+    const OutMode mode = sink ? OutMode::Rle32 : sparse ? OutMode::Sparse : summary_out ? OutMode::Summary : OutMode::Words;
     BatchJob job = make_job(mode, idx, offsets, n_seqs, strand_slab_bytes(packed_slab_bytes(idx), strands), threshold, clk);
     job.packed = &in;
     job.strands = strands ? strands : 1;
@@ -1272,6 +1356,9 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
     } else if (sparse) {
         job.sparse = sparse;
         sparse->begin(job.slabs.size(), n_seqs, job.n_workers == 1);
+    } else if (summary_out) {
+        job.summary_out = summary_out;
+        job.out_pinned = is_pinned_host(summary_out);
     } else {
         job.packed_out = packed_out;
         job.packed_rev = rev_out;
@@ -1300,6 +1387,12 @@ void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offset
     job.in_pinned = is_pinned_host(concat);
     job.out_pinned = is_pinned_host(d_out) && (!lo_out || (is_pinned_host(lo_out) && is_pinned_host(hi_out)));
     run_counted(job);
+}
+
+void summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs)
+{
+    if (kernel_slabs) *kernel_slabs = g_summary_kernel_slabs.load();
+    if (reducer_slabs) *reducer_slabs = g_summary_reducer_slabs.load();
 }
 
 void release_host_scratch()

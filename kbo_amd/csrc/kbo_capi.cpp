@@ -642,6 +642,15 @@ int kbo_matches_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *o
     return guarded([&] { matches_batch_impl(idx, concat, offsets, n_seqs, max_error_prob, false, chars_out); });
 }
 
+int kbo_summary_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                      kbo_aln_summary *summary_out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(summary_out, KBO_E_BAD_ARG, "null argument");
+        matches_batch_impl(idx, concat, offsets, n_seqs, max_error_prob, false, nullptr, nullptr, 0, nullptr, summary_out);
+    });
+}
+
 int kbo_map_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
                   double max_error_prob, int format, uint8_t *out)
 {
@@ -944,6 +953,22 @@ int kbo_matches_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint
         const PackedBatch in{words, exc_pos, exc_byte, n_exc};
         matches_batch_packed_impl(idx, in, offsets, n_seqs, max_error_prob, words_out, nullptr);
     });
+}
+
+int kbo_summary_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,
+                             const uint8_t *exc_byte, size_t n_exc, double max_error_prob, kbo_aln_summary *summary_out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(idx && words && summary_out, KBO_E_BAD_ARG, "null argument");
+        const PackedBatch in{words, exc_pos, exc_byte, n_exc};
+        matches_batch_packed_impl(idx, in, offsets, n_seqs, max_error_prob, nullptr, nullptr, nullptr, 0, nullptr, summary_out);
+    });
+}
+
+int kbo_summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs)
+{
+    summary_slab_routes(kernel_slabs, reducer_slabs);
+    return KBO_OK;
 }
 
 int kbo_find_batch_packed(kbo_index_t *idx, const uint32_t *words, const uint64_t *offsets, size_t n_seqs, const uint64_t *exc_pos,

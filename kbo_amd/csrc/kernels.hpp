@@ -166,6 +166,8 @@ struct WalkArgs {
     const uint32_t *qp_data, *qp_sums;
     const uint8_t *qp_exc;
     uint32_t *packed_out;
+    uint4 *summary_out;      // (the summary forms of map_reads_kernel / finish_reads_kernel, launch_map_reads with summary = true: one record
+                             // { 'M's, 'X's, 'R's, runs } per read instead of its characters - kbo_hip.h kbo_aln_summary; chars_out and d_out are null)
 };
 // Work counters the plan-guided stage keeps about itself (one wave-level atomic per counter and wave, spread over slots):
 // what the CPU model of the stage (oracle/plan_model.c) is pinned to, tests/test_gpu_model.py
@@ -229,6 +231,7 @@ hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream);
 bool map_reads_finish_applies(const WalkArgs &a);
 hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream, bool one_wave_groups = false);
 bool map_reads_direct(const WalkArgs &a);
+bool map_reads_summary_applies(const DevIndexView &ix, uint32_t longest); // (a.summary_out: launch_map_reads + launch_map_reads_finish store records, no characters)
 bool map_reads_packed_applies(const WalkArgs &a, bool packed_out); // (a.qp set: the reads as 2-bit words; a.packed_out: the characters too)
 // packed-native batches (pack_kernels.hip): exc[s] = 1 for every read that holds a listed byte (d_exc zeroed first); the bytes of the
 // flagged reads from their words (for the plain walk; the listed bytes then go over them: launch_exceptions); the characters of
@@ -468,6 +471,15 @@ hipError_t launch_sparse_count(const uint32_t *d_words, const uint64_t *d_off, u
 hipError_t launch_sparse_emit(const uint32_t *d_words, const uint64_t *d_off, uint32_t n_seqs, uint32_t uniform_wps, const uint32_t *d_prefix,
                               uint32_t n_blocks, const uint32_t *d_scratch, uint32_t seq_base, uint32_t *d_runs, uint32_t capacity,
                               uint32_t *d_total, hipStream_t stream);
+
+// per-sequence alignment summaries of characters in memory (summary_kernels.hip): d_out[s] = { 'M's, 'X's, 'R's, runs } of sequence s (a run:
+// a maximal stretch without '-'), zeros for a sequence of fewer than 3 bases.  Bytes: one character a byte at d_chars + d_off[s] (any
+// alignment; nothing outside the 16-byte aligned blocks that hold a character is read); words: the packed layout's character words
+// (M - X R = 0 .. 3) with d_prefix = the scanned words-per-sequence (launch_packed_prefix).  bases_bound: an upper bound of d_off[n_seqs] that
+// sizes the grid, 0 = unknown (the most workgroups).  d_out is zeroed first and exactly n_seqs records are written.
+hipError_t launch_summary_bytes(const uint8_t *d_chars, const uint64_t *d_off, uint32_t n_seqs, uint64_t bases_bound, uint4 *d_out, hipStream_t stream);
+hipError_t launch_summary_words(const uint32_t *d_words, const uint64_t *d_off, uint32_t n_seqs, const uint32_t *d_prefix, uint64_t bases_bound,
+                                uint4 *d_out, hipStream_t stream);
 
 // a[i] = max(a[i], b[i]) over n bytes (n rounded up to 16: both buffers have that slack): the MS values of a further shard of a
 // sharded index folded into the batch's (pack_kernels.hip)

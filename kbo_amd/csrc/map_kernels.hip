@@ -214,7 +214,10 @@ __device__ __forceinline__ void literal_chars(uint8_t *at, uint32_t len, int K, 
     at[0] = (uint8_t)((x_cur > T && in_next) ? (uint32_t)'R' : plain(x_cur, x_next, K));
 }
 // STATS: the kernel counts its own work (kbo_set_plan_stats) - instrumentation, compiled out of the default instantiations
-template <int NP, bool DIRECT, int IO = 0, bool STATS = false>
+// SUM: the summary form (kbo_summary_batch_dev): the characters are counted off LDS where kbo::find's runs are, and stage 5 stores one
+// 16-byte record { 'M's, 'X's, 'R's, runs } per read the kernel finishes (a.summary_out) and no character - a.chars_out, a.d_out and
+// a.run_counts are null.  IO = 0 (both threshold cases) and IO = 1 (packed words in: the codes stand where the bytes would).  A read left to the second pass gets its record there (finish_reads_kernel's summary form).
+template <int NP, bool DIRECT, int IO = 0, bool STATS = false, bool SUM = false>
 __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint32_t stage_bytes, uint32_t lin_words)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t map_lds_all[];
@@ -271,6 +274,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     const bool staged = __ballot(bad_item || bad_words) == 0 && wave_hi > lo && (uint64_t)span + kMapSlack <= stage_bytes &&
                         (IO == 0 || (uint64_t)16u * nwords + kMapSlack <= stage_bytes);
     if (!staged) { // (cannot happen for a batch of reads the host sent here; if it does, every item takes the plain walk)
+        if (SUM && have_item && len == 0) a.summary_out[idx] = make_uint4(0, 0, 0, 0);
         if (have_item) a.redo[idx] = len != 0 ? 1 : 0;
         const uint64_t fm = __ballot(have_item && len != 0);
         if (lane == 0 && fm) atomicAdd(a.qctl + 4, (uint32_t)__popcll(fm));
@@ -1088,7 +1092,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         }
         if (cand) put(e, cX); // (the read's first base: its prev is k)
         (void)K;
-    } else if (a.chars_out != nullptr && plannable && !flag && len >= 3u) { // (chars_out == nullptr: kbo_ms_batch_dev - the MS values were all that was asked for)
+    } else if ((SUM || a.chars_out != nullptr) && plannable && !flag && len >= 3u) { // (chars_out == nullptr: kbo_ms_batch_dev - the MS values were all that was asked for)
         literal_chars(so + soff, len, (int)k, (int)a.map_thr);
     }
     // kbo::find: the runs of the read (format::run_lengths_gapped with max_gap_len = 0 closes a run at every '-': rle_kernels.hip),
@@ -1111,12 +1115,45 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         }
         a.run_counts[idx] = n_runs;
     }
+    // the summary form: the read's 'M's, 'X's, 'R's and runs off the same characters - the codes sixteen a word (DIRECT), or the bytes the
+    // literal pass left - kept in registers until the read's flag is final (the searches behind stage 5 may still hand it to the second pass)
+    uint4 summary = make_uint4(0, 0, 0, 0);
+    if (SUM && plannable && !flag && len >= 3u) { // (fewer than 3 bases: no alignment, an all-zero record)
+        if (DIRECT) {
+            const uint32_t b0 = ooff, b1 = ooff + len;
+            uint32_t carry = 0; // bit 0: the character in front of the word was not a '-'
+            for (uint32_t w_ = b0 >> 4; 16u * w_ < b1; w_++) {
+                const uint32_t v = cw[w_];
+                const uint32_t lo_ = 16u * w_ < b0 ? b0 - 16u * w_ : 0u, hi_ = 16u * w_ + 16u > b1 ? b1 - 16u * w_ : 16u;
+                const uint32_t in = (hi_ >= 16u ? 0xFFFFFFFFu : (1u << (2u * hi_)) - 1u) & ~((1u << (2u * lo_)) - 1u) & 0x55555555u;
+                const uint32_t c0 = v & in, c1 = (v >> 1) & in; // the codes' two bits: M - R X = 0 1 2 3
+                const uint32_t nd = in & ~(c0 & ~c1);
+                summary.x += (uint32_t)__popc(in & ~(c0 | c1));
+                summary.y += (uint32_t)__popc(c0 & c1);
+                summary.z += (uint32_t)__popc(c1 & ~c0);
+                summary.w += (uint32_t)__popc(nd & ~((nd << 2) | carry));
+                carry = nd >> 30;
+            }
+        } else {
+            uint32_t gap = 1;
+            for (uint32_t p = 0; p < len; p++) {
+                const uint32_t ch = so[ooff + p], gp = ch == (uint32_t)'-' ? 1u : 0u;
+                summary.x += ch == (uint32_t)'M' ? 1u : 0u;
+                summary.y += ch == (uint32_t)'X' ? 1u : 0u;
+                summary.z += ch == (uint32_t)'R' ? 1u : 0u;
+                summary.w += gap & (gp ^ 1u);
+                gap = gp;
+            }
+        }
+    }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
     // ---- 5. the characters leave in whole lines; format::relative_to_ref (format.rs:270-286) on the way: 'M' and 'R' keep the
     // read's base, everything else becomes '-' (flagged reads' bytes are rewritten by launch_derand_flagged)
-    if (IO == 2) { // as 2-bit words, where the read's own words stand in the batch (the packed alphabet is M - X R: codes 2 and 3 change places)
+    if (SUM) {
+        // (the summary form: no character leaves - the records go out below, when the flags are final)
+    } else if (IO == 2) { // as 2-bit words, where the read's own words stand in the batch (the packed alphabet is M - X R: codes 2 and 3 change places)
         for (uint32_t c = lane; c < nwords; c += 64u) {
             const uint32_t w_ = cw[c];
             a.packed_out[w_lo + c] = w_ ^ ((w_ >> 1) & 0x55555555u);
@@ -1284,6 +1321,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         if (nm) atomicAdd(a.qctl + 5, (uint32_t)__popcll(nm));
     }
     if (have_item) a.redo[idx] = flag ? 1 : 0;
+    if (SUM && have_item && !flag) a.summary_out[idx] = summary; // (one 16-byte store a lane: a wave's records leave as one KiB)
     // ... and listed for finish_reads_kernel (qctl[6] counts them; the list - where the guided walk's units would be - holds every read)
     if (flag && have_item) reinterpret_cast<uint32_t *>(a.units)[atomicAdd(a.qctl + 6, 1u)] = idx;
 }
@@ -1299,6 +1337,9 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
 // than the launch has waves (a chain of k + 1 + len / 64 steps), four or sixteen beyond (a batch with 5 % substitutions leaves 3 % of its
 // reads) -, so that a batch's second pass is as long as its longest chain, and that is short.
 constexpr uint32_t kFinishStride = 176, kFinishMaxR = 16, kFinishWaves = 8192, kFinishLds = 2u * kFinishMaxR * kFinishStride;
+// SUM: the summary form - behind the literal pass the read's lanes count its characters and its first lane stores the read's record
+// (a.summary_out) instead of the characters
+template <bool SUM = false>
 __global__ __launch_bounds__(256) void finish_reads_kernel(WalkArgs a, uint32_t r1, uint32_t r4)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t fin_lds_all[];
@@ -1365,9 +1406,28 @@ __global__ __launch_bounds__(256) void finish_reads_kernel(WalkArgs a, uint32_t 
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (a.d_out && (a.map_want_ms || !a.chars_out))
+        if (!SUM && a.d_out && (a.map_want_ms || !a.chars_out))
             for (uint32_t p = s; p < len; p += L) a.d_out[o0 + p] = mL[p];
-        if (a.chars_out) {
+        if (SUM) {
+            // the literal pass by the read's first lane, then all of the read's L lanes count its characters - a run starts at a character
+            // that is not '-' behind one that is, or at the read's head - and their counts (two 16-bit fields a word: at most 160 each)
+            // are summed over the L lanes, which are neighbours
+            if (s == 0u && slot < n_f && len >= 3u) literal_chars(mL, len, (int)k, (int)a.map_thr);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            uint32_t pa = 0, pb = 0;
+            if (len >= 3u) // (fewer: no alignment, an all-zero record)
+                for (uint32_t p = s; p < len; p += L) {
+                    const uint32_t ch = mL[p], gap = p == 0u ? 1u : (mL[p - 1u] == (uint8_t)'-' ? 1u : 0u);
+                    pa += (ch == (uint32_t)'M' ? 1u : 0u) | (ch == (uint32_t)'X' ? 0x10000u : 0u);
+                    pb += (ch == (uint32_t)'R' ? 1u : 0u) | ((ch != (uint32_t)'-' ? gap : 0u) << 16);
+                }
+            for (uint32_t o = L >> 1; o > 0u; o >>= 1) {
+                pa += __shfl_xor(pa, (int)o);
+                pb += __shfl_xor(pb, (int)o);
+            }
+            if (s == 0u && slot < n_f) a.summary_out[ridx] = make_uint4(pa & 0xFFFFu, pa >> 16, pb & 0xFFFFu, pb >> 16);
+        } else if (a.chars_out) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             if (s == 0u && slot < n_f) {
@@ -1412,11 +1472,16 @@ hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, ui
     return hipGetLastError();
 }
 
+// what the index copy and the batch's longest read have to be like ...
+static bool map_reads_index_applies(const DevIndexView &ix, uint32_t longest)
+{
+    return ix.dtab && ix.pc_tm && ix.seed_pos && ix.seed_d >= 4u && ix.seed_d <= 14u && ix.dtab_order >= 4u && ix.dtab_order <= 17u &&
+           ix.dtab_order <= ix.k && longest != 0 && longest <= 16u * kMapWords;
+}
+// ... and the launch: its plan work attached (attach_plan: not while the copy's plan is held off), no intervals, no call mode
 bool map_reads_applies(const WalkArgs &a)
 {
-    return a.ix.dtab && a.ix.pc_tm && a.ix.seed_pos && a.ix.seed_d >= 4u && a.ix.seed_d <= 14u && a.ix.dtab_order >= 4u && a.ix.dtab_order <= 17u &&
-           a.ix.dtab_order <= a.ix.k && !a.call_sites && !a.lo_out && a.max_item_len != 0 && a.max_item_len <= 16u * kMapWords && a.redo && a.qctl &&
-           a.units;
+    return map_reads_index_applies(a.ix, a.max_item_len) && !a.call_sites && !a.lo_out && a.redo && a.qctl && a.units;
 }
 
 // the characters straight from the mismatch positions where no table value can anchor (order <= t < k) and the MS values
@@ -1469,6 +1534,23 @@ hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream)
         if (a.pstats) hipLaunchKernelGGL((map_reads_kernel<NP_, DIRECT_, IO_, true>), grid, block, lds, stream, a, stage_bytes, lin_words);       \
         else hipLaunchKernelGGL((map_reads_kernel<NP_, DIRECT_, IO_, false>), grid, block, lds, stream, a, stage_bytes, lin_words);               \
     } while (0)
+    // the summary forms (a.summary_out): reads as bytes in both threshold cases, reads as packed words in the direct form; no counting
+    // instantiations (a batch whose work is to be counted takes the character forms and the reducer: the callers see to it)
+#define KBO_MAP_LAUNCH_SUM(NP_, DIRECT_, IO_) \
+    hipLaunchKernelGGL((map_reads_kernel<NP_, DIRECT_, IO_, false, true>), grid, block, lds, stream, a, stage_bytes, lin_words)
+    if (a.summary_out) {
+        if (io == 2 || a.pstats || a.chars_out || a.d_out || a.run_counts || a.map_fmt || a.map_want_ms) return hipErrorInvalidValue;
+        if (a.ix.dtab_order <= 15u) {
+            if (io == 1) KBO_MAP_LAUNCH_SUM(16, true, 1);
+            else if (direct) KBO_MAP_LAUNCH_SUM(16, true, 0);
+            else KBO_MAP_LAUNCH_SUM(16, false, 0);
+        } else {
+            if (io == 1) KBO_MAP_LAUNCH_SUM(18, true, 1);
+            else if (direct) KBO_MAP_LAUNCH_SUM(18, true, 0);
+            else KBO_MAP_LAUNCH_SUM(18, false, 0);
+        }
+        return hipGetLastError();
+    }
     if (a.ix.dtab_order <= 15u) {
         if (io == 2) KBO_MAP_LAUNCH(16, true, 2);
         else if (io == 1) KBO_MAP_LAUNCH(16, true, 1);
@@ -1481,15 +1563,27 @@ hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream)
         else KBO_MAP_LAUNCH(18, false, 0);
     }
 #undef KBO_MAP_LAUNCH
+#undef KBO_MAP_LAUNCH_SUM
     return hipGetLastError();
 }
 
 // the reads launch_map_reads' kernel left (its list: qctl[6] entries where the units would be), finished by one kernel: their matching
 // statistics where a.d_out wants them (a.map_want_ms, or no characters asked for), their characters, their runs (a.run_counts)
-bool map_reads_finish_applies(const WalkArgs &a)
+static bool map_finish_enabled()
 {
     static const int env_finish = std::getenv("KBO_MAP_FINISH") ? std::atoi(std::getenv("KBO_MAP_FINISH")) : 1; // experiments: 0 = the three launches
-    return env_finish != 0 && a.seq_off != nullptr && a.qp == nullptr && a.units != nullptr && a.max_item_len != 0 && a.max_item_len <= 16u * kMapWords;
+    return env_finish != 0;
+}
+// the summary forms of the kernel and of finish_reads_kernel take a batch of reads (bytes, one item a read) over this copy: a matter of
+// the copy and the longest read alone - a summary batch is planned even while the copy's plan is held off, its route (and with it the
+// size of its work memory, kbo_summary_work_bytes) does not depend on the batches before it
+bool map_reads_summary_applies(const DevIndexView &ix, uint32_t longest)
+{
+    return ix.pc_text && map_reads_index_applies(ix, longest) && map_finish_enabled();
+}
+bool map_reads_finish_applies(const WalkArgs &a)
+{
+    return map_finish_enabled() && a.seq_off != nullptr && a.qp == nullptr && a.units != nullptr && a.max_item_len != 0 && a.max_item_len <= 16u * kMapWords;
 }
 
 hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream, bool one_wave_groups)
@@ -1503,7 +1597,8 @@ hipError_t launch_map_reads_finish(const WalkArgs &a, hipStream_t stream, bool o
     // one_wave_groups: beside kernels that hold the whole device (kbo_map_stream's unmasked pipelines) a workgroup of four waves waits for
     // four free slots on one compute unit at once, a workgroup of one for any free slot
     const uint32_t wpb = one_wave_groups ? 1u : 4u;
-    hipLaunchKernelGGL(finish_reads_kernel, dim3(waves / wpb), dim3(64u * wpb), wpb * kFinishLds, stream, a, (uint32_t)env_r1, (uint32_t)env_r4);
+    if (a.summary_out) hipLaunchKernelGGL(finish_reads_kernel<true>, dim3(waves / wpb), dim3(64u * wpb), wpb * kFinishLds, stream, a, (uint32_t)env_r1, (uint32_t)env_r4);
+    else hipLaunchKernelGGL(finish_reads_kernel<false>, dim3(waves / wpb), dim3(64u * wpb), wpb * kFinishLds, stream, a, (uint32_t)env_r1, (uint32_t)env_r4);
     return hipGetLastError();
 }
 
