@@ -461,6 +461,44 @@ int kbo_revcomp_packed_dev(const uint32_t *d_words, const uint64_t *d_offsets, s
                            const uint8_t *d_exc_byte, size_t n_exc, uint32_t *d_words_out, uint64_t *d_exc_pos_out, uint8_t *d_exc_byte_out,
                            void *d_scratch, void *stream);
 
+/* ------------------------------------------------------------------ find against a set of references
+ * kbo::find over a file of reference sequences - a resistance-gene or virulence-factor database: hundreds to thousands of sequences
+ * of 0.3 - 5 kbp - is one index PER REFERENCE in the reference crate (kbo::build on that one sequence, lib.rs:501-506; kbo::find for
+ * every (reference, query contig) pair, lib.rs:808-821), and no single index of all of them gives the same runs: the derandomisation
+ * threshold comes from each index's own n_kmers (derandomize.rs:127-145), and the matching statistics against the union are the
+ * maximum over the references.  A kbo_refset_t is N such indexes - index r exactly what kbo_index_build of sequence r alone builds:
+ * the same rows, C, LCS, n_kmers and k - in ONE packed device layout without plan structures (2 bytes a row), and kbo_find_refset
+ * queries all of them in one call: the query batch is uploaded once, its '-' strand is made on the device, and a kernel that keeps a
+ * whole reference in a compute unit's LDS walks (reference, query chunk) pairs (kbo_amd/csrc/refset_kernels.hip).  A reference of
+ * more than 16 384 rows does not fit that form; the set keeps an ordinary index handle for it and the call takes it through the
+ * single-index pipeline, one such reference at a time, with the same results.
+ * A reference without a k-mer - shorter than k, or without a run of k bases A, C, G, T - cannot be queried (kbo_find on its own
+ * handle fails in random_match_threshold, derandomize.rs:134); the set still builds, kbo_refset_status says so (KBO_E_BAD_ARG, the
+ * code that call returns) and the reference contributes no runs.  Whole-call errors of the build (null arguments, n_refs == 0, k
+ * outside 1 .. 255) are kbo_index_build's, checked before any HIP call; opts->num_threads threads build the references. */
+typedef struct kbo_refset kbo_refset_t;
+int kbo_refset_build(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, kbo_refset_t **out);
+void kbo_refset_free(kbo_refset_t *set);
+size_t kbo_refset_size(const kbo_refset_t *set);                /* N */
+size_t kbo_refset_k(const kbo_refset_t *set);
+uint64_t kbo_refset_n_kmers(const kbo_refset_t *set, size_t r); /* 0 for r >= N */
+int kbo_refset_status(const kbo_refset_t *set, size_t r);       /* 0, or the KBO_E_* of building / querying r alone */
+int kbo_refset_to_device(kbo_refset_t *set, int device);        /* idempotent, -1 = current */
+/* The records with (ref = r, seq = s, strand) are, in order, exactly the runs kbo_find returns for sequence s - strand
+ * KBO_STRAND_REV: for its reverse complement, in the coordinates of the reverse-complemented sequence as for kbo_find_batch_strands -
+ * against reference r's own index: derandomised with the threshold of that index's n_kmers and opts->max_error_prob, run lengths
+ * with opts->max_gap_len.  Records are ordered by (ref, seq, strand with '+' first, start); a pair without a hit has no record, and
+ * there is no cap on their number.  *runs is library-allocated (kbo_free), *n_runs records.  Only runs leave the device.
+ * Errors, all checked before the first HIP call: strands outside 1 .. 3 and null arguments KBO_E_BAD_ARG, offsets as for
+ * kbo_find_batch_strands, a sequence of fewer than 3 bases refuses the batch with KBO_E_LEN_LE_2, KBO_E_THRESHOLD_LE_1 when some
+ * reference's threshold is (kbo_find on its handle fails so), KBO_E_UNSUPPORTED for a batch of 2^31 bases or more. */
+typedef struct {
+    uint32_t ref, seq, strand; /* strand: KBO_STRAND_FWD or KBO_STRAND_REV */
+    kbo_rle32 run;
+} kbo_ref_run; /* 40 bytes */
+int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_find_opts *opts,
+                    int strands, kbo_ref_run **runs, uint64_t *n_runs);
+
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`
  * (a hipStream_t) and the call returns immediately.  d_concat must be 16-byte aligned,

@@ -199,6 +199,18 @@ int kbo_summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs);
  * max_seq_len = 0, unknown: the most; 0 for arguments it refuses) */
 uint32_t kbo_sparse_runs_blocks(size_t n_seqs, size_t max_seq_len);
 
+/* ------------------------------------------------------------------ kbo_find_refset */
+/* bases a lane of refset_kernels.hip emits: a sequence is cut every max(KBO_REFSET_CHUNK, 4 k) bases, every chunk behind the first
+ * restarts k - 1 bases upstream; rows of the largest index that takes that kernel (larger ones: the single-index pipeline) */
+#define KBO_REFSET_CHUNK 256
+#define KBO_REFSET_MAX_ROWS 16384
+/* test hook: records the device buffer of a slab's runs has room for at first (default 65 536, at least 1; a slab with more runs
+ * grows it - the run-length stage counts before it emits) */
+int kbo_set_refset_record_capacity(size_t records);
+/* test hook: what the calling thread's last kbo_find_refset did: out[0] references walked by the LDS kernel, out[1] references taken
+ * through the single-index pipeline, out[2] (reference, sequence, strand) pairs walked over both routes, out[3] slabs */
+int kbo_refset_last_routes(uint64_t out[4]);
+
 /* ------------------------------------------------------------------ experiments recorded in DESIGN.md section 6 */
 /* plain walk kernel: only the first lane_limit lanes of every wave take reads (64 = all; what a sub-wave tiling would
  * have to beat), and every workgroup reserves dummy_lds_bytes of LDS it never touches (what staging a wave's MS values

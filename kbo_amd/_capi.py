@@ -116,6 +116,8 @@ SYMBOLS = [
     "kbo_find_batch_packed_strands", "kbo_revcomp_batch_dev", "kbo_revcomp_packed_scratch_bytes", "kbo_revcomp_packed_dev",
     "kbo_summary_batch", "kbo_summary_batch_packed", "kbo_summary_work_bytes", "kbo_summary_batch_dev", "kbo_summary_dev",
     "kbo_summary_words_work_bytes", "kbo_summary_words_dev", "kbo_map_stream_submit_summary",
+    "kbo_refset_build", "kbo_refset_free", "kbo_refset_size", "kbo_refset_k", "kbo_refset_n_kmers", "kbo_refset_status",
+    "kbo_refset_to_device", "kbo_find_refset",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -124,7 +126,7 @@ TUNING_SYMBOLS = [
     "kbo_set_plan_unit_cap_divisor", "kbo_index_plan_holdoff", "kbo_set_walk_experiment", "kbo_plan_stats_dev", "kbo_set_plan_stats", "kbo_set_index_shards", "kbo_index_shard", "kbo_set_depth_table", "kbo_set_depth_table_anchors", "kbo_index_depth_table", "kbo_run_automaton_depths",
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
-    "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes",
+    "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
 ]
 
 _lib = None
@@ -303,6 +305,16 @@ def lib():
     L.kbo_summary_words_work_bytes.argtypes = [sz]; L.kbo_summary_words_work_bytes.restype = sz
     L.kbo_summary_words_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     L.kbo_map_stream_submit_summary.argtypes = [vp, vp, vp, sz, u64, sz, dbl, vp, vp, vp, C.POINTER(C.c_int)]
+    L.kbo_refset_build.argtypes = [C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.POINTER(BuildOpts), C.POINTER(vp)]
+    L.kbo_refset_free.argtypes = [vp]; L.kbo_refset_free.restype = None
+    L.kbo_refset_size.argtypes = [vp]; L.kbo_refset_size.restype = sz
+    L.kbo_refset_k.argtypes = [vp]; L.kbo_refset_k.restype = sz
+    L.kbo_refset_n_kmers.argtypes = [vp, sz]; L.kbo_refset_n_kmers.restype = u64
+    L.kbo_refset_status.argtypes = [vp, sz]
+    L.kbo_refset_to_device.argtypes = [vp, C.c_int]
+    L.kbo_find_refset.argtypes = [vp, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(vp), C.POINTER(u64)]
+    L.kbo_set_refset_record_capacity.argtypes = [sz]
+    L.kbo_refset_last_routes.argtypes = [vp]
     _lib = L
     return L
 

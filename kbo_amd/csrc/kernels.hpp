@@ -519,6 +519,35 @@ hipError_t long_read_stats(const void *d_work, size_t n_seqs, uint64_t total_bas
 // the plain walk over a list of items whose number is counted on the device (walk_kernels.hip): `lanes` lanes share them
 hipError_t launch_walk_list(WalkArgs a, const WalkItem *d_list, uint32_t cap, const uint32_t *d_count, uint32_t lanes, hipStream_t stream);
 
+// ---- the walk against a set of small indexes, each staged whole into LDS (refset_kernels.hip)
+// LDS form of one index of n rows, in 16-byte units: 2 (n / 32 + 1) units of rank blocks - block b covers rows [32 b, 32 b + 32) and
+// holds, for c = A, C, G, T, the 8 bytes { C[c] + rank_c(32 b), the 32 row bits } (one ds_read_b64 per rank) - then ceil((n + 1) / 16)
+// units of LCS bytes with the sentinel LCS[n] = 0.  2 bytes a row; the packed device layout of a set is these forms back to back.
+constexpr uint32_t kRefsetMaxRows = 16384; // rows of an index that takes this kernel: 32.8 KiB of LDS, four workgroups of it a compute unit
+constexpr uint32_t kRefsetChunk = 256;     // bases a lane emits (== KBO_REFSET_CHUNK; max(this, 4 k) in all), + k - 1 warm-up bases
+constexpr uint32_t kRefsetThreads = 256;   // lanes of a workgroup = the most chunks of one task
+__host__ __device__ inline uint32_t refset_rank_units(uint32_t n_sets) { return 2u * (n_sets / 32u + 1u); }
+__host__ __device__ inline uint32_t refset_units(uint32_t n_sets) { return refset_rank_units(n_sets) + (n_sets + 1u + 15u) / 16u; }
+struct RefsetDesc { // one per reference of the set, on the device
+    uint32_t off;     // first 16-byte unit of its LDS form in the set's arena
+    uint32_t n_sets;
+    uint32_t C[4];
+    int32_t status;   // 0, or why the reference cannot be queried (then it has no units)
+    uint32_t route;   // 0: this kernel, 1: an ordinary index of its own
+    uint64_t n_kmers;
+};
+struct RefsetWalkArgs {
+    const RefsetDesc *descs;
+    const uint4 *arena;
+    const uint4 *tasks;  // { reference, first item, items (<= kRefsetThreads), 0 }: one workgroup each
+    const uint4 *items;  // { first base in q, first byte in ms, bases | warm-up bases << 16, 0 }: one lane each
+    uint32_t n_tasks;
+    uint32_t k;
+    const uint8_t *q;    // the query batch, both strands
+    uint8_t *ms;         // the slab: one byte per (pair, base)
+};
+hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units /* the largest refset_units() among the tasks' references */, hipStream_t stream);
+
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256
 void set_walk_experiment(int lane_limit, int dummy_lds_bytes); // experiments behind DESIGN.md section 6

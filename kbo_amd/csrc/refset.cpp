@@ -1,0 +1,435 @@
+// refset.cpp — kbo_refset_t (N one-sequence indexes in one packed device layout) and kbo_find_refset (kbo_hip.h "find against a
+// set of references").  The walk is refset_kernels.hip's; what follows it - derandomize_ms_vec / translate_ms_vec,
+// run_lengths_gapped - are the single-index pipeline's kernels as they are: a slab of (reference, sequence, strand) pairs is laid
+// out pair by pair and looks like an ordinary batch to them.  They take one threshold a launch, so the references are walked in
+// the order of their thresholds (at most k values) and a slab never mixes two; the records go back into reference order at the end.
+#include "../../include/kbo_hip_tuning.h"
+#include "capi_internal.hpp"
+
+#include <algorithm>
+#include <thread>
+
+using namespace kbo_host;
+
+static_assert(kbo::kRefsetChunk == KBO_REFSET_CHUNK && kbo::kRefsetMaxRows == KBO_REFSET_MAX_ROWS, "kbo_hip_tuning.h states the kernel's constants");
+
+namespace {
+std::atomic<size_t> g_record_capacity{1u << 16};
+thread_local uint64_t t_routes[4] = {0, 0, 0, 0};
+
+struct DevSet {
+    DevBuf arena, descs;
+};
+
+struct DeviceScope { // the calling thread on `device` until the scope ends
+    int prev = -1;
+    bool moved = false;
+    explicit DeviceScope(int device)
+    {
+        HIP_OK(hipGetDevice(&prev));
+        if (device >= 0 && device != prev) {
+            HIP_OK(hipSetDevice(device));
+            moved = true;
+        }
+    }
+    ~DeviceScope()
+    {
+        if (moved) (void)hipSetDevice(prev);
+    }
+};
+
+struct StreamScope {
+    hipStream_t s = nullptr;
+    StreamScope() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~StreamScope()
+    {
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+    }
+};
+} // namespace
+
+struct kbo_refset {
+    uint32_t k = 0;
+    std::vector<kbo::RefsetDesc> descs;
+    std::vector<uint32_t> arena;                  // the LDS forms back to back, four words a unit
+    std::vector<std::unique_ptr<kbo_index>> own;  // per reference: its ordinary index when it does not fit the LDS form, else null
+    std::mutex mu;
+    std::map<int, DevSet *> dev;
+    ~kbo_refset()
+    {
+        for (auto &kv : dev) delete kv.second;
+    }
+};
+
+namespace {
+
+// the LDS form of an index (kernels.hpp), appended to `arena`
+void append_lds_form(const kbo::HostIndex &h, std::vector<uint32_t> &arena)
+{
+    const uint32_t n = (uint32_t)h.n_sets, nb = n / 32u + 1u;
+    const size_t at = arena.size(), nw = h.rows[0].size();
+    arena.resize(at + 4u * (size_t)kbo::refset_units(n), 0u);
+    uint32_t *rank = arena.data() + at;
+    uint32_t cum[4] = {(uint32_t)h.C[0], (uint32_t)h.C[1], (uint32_t)h.C[2], (uint32_t)h.C[3]};
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t c = 0; c < 4; c++) {
+            const size_t w = b >> 1;
+            const uint32_t bits = w < nw ? (uint32_t)(h.rows[c][w] >> (32u * (b & 1u))) : 0u;
+            rank[(b * 4u + c) * 2u] = cum[c];
+            rank[(b * 4u + c) * 2u + 1u] = bits;
+            cum[c] += (uint32_t)__builtin_popcount(bits);
+        }
+    uint8_t *lcs = reinterpret_cast<uint8_t *>(rank + 4u * (size_t)kbo::refset_rank_units(n));
+    std::memcpy(lcs, h.lcs.data(), n);
+    lcs[0] = 0;
+    lcs[n] = 0; // the sentinel that ends the contraction's scan upwards
+}
+
+DevSet *device_set(kbo_refset *set, int device)
+{
+    std::lock_guard<std::mutex> g(set->mu);
+    auto it = set->dev.find(device);
+    if (it != set->dev.end()) return it->second;
+    DeviceScope on(device);
+    std::unique_ptr<DevSet> d(new DevSet());
+    d->arena.alloc(set->arena.size() * sizeof(uint32_t) + 16);
+    d->descs.alloc(set->descs.size() * sizeof(kbo::RefsetDesc));
+    if (!set->arena.empty()) HIP_OK(hipMemcpy(d->arena.p, set->arena.data(), set->arena.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d->descs.p, set->descs.data(), set->descs.size() * sizeof(kbo::RefsetDesc), hipMemcpyHostToDevice));
+    set->dev[device] = d.get();
+    return d.release();
+}
+
+// the pairs of a slab, their chunks and the workgroups' tasks, as they go to the device
+struct SlabPlan {
+    std::vector<uint32_t> ref, seq, strand; // per pair
+    std::vector<uint64_t> off;              // per pair + 1: its first byte in the slab
+    std::vector<uint32_t> items, tasks;     // four words a record (kernels.hpp RefsetWalkArgs)
+    uint32_t longest = 0, lds_units = 0;
+    void clear()
+    {
+        ref.clear(); seq.clear(); strand.clear(); items.clear(); tasks.clear();
+        off.assign(1, 0);
+        longest = 0;
+        lds_units = 0;
+    }
+    size_t pairs() const { return ref.size(); }
+    uint64_t bytes() const { return off.back(); }
+};
+
+struct Finder {
+    kbo_refset *set;
+    const uint64_t *offsets;
+    uint32_t k, chunk, gap;
+    uint64_t rev_base; // where the '-' strand of the batch begins in d_q
+    hipStream_t st;
+    DevSet *ds;
+    DevBuf d_q, d_off, d_ms, d_chars, d_poff, d_items, d_tasks, d_scratch, d_total, d_rles, d_piece;
+    size_t rle_capacity = 0;
+    std::vector<uint32_t> first, recs;
+    std::vector<kbo_ref_run> out;
+    std::vector<uint64_t> ref_begin, ref_end; // where every reference's records lie in `out`
+    std::vector<uint8_t> walked;              // per reference: a launch of the LDS kernel has held it (the route counters)
+
+    void add_pair(SlabPlan &P, uint32_t r, uint32_t s, uint32_t strand)
+    {
+        const uint64_t len = offsets[s + 1] - offsets[s], q0 = (strand == KBO_STRAND_REV ? rev_base : 0) + offsets[s], o0 = P.bytes();
+        bool fresh = P.tasks.empty() || P.tasks[P.tasks.size() - 4] != r;
+        for (uint64_t c0 = 0; c0 < len; c0 += chunk) {
+            const uint64_t c1 = std::min(len, c0 + chunk), warm = std::min<uint64_t>(c0, k - 1);
+            if (fresh || P.tasks[P.tasks.size() - 2] == kbo::kRefsetThreads) {
+                const uint32_t t[4] = {r, (uint32_t)(P.items.size() / 4), 0u, 0u};
+                P.tasks.insert(P.tasks.end(), t, t + 4);
+                fresh = false;
+            }
+            const uint32_t it[4] = {(uint32_t)(q0 + c0 - warm), (uint32_t)(o0 + c0), (uint32_t)(c1 - c0 + warm) | (uint32_t)warm << 16, 0u};
+            P.items.insert(P.items.end(), it, it + 4);
+            P.tasks[P.tasks.size() - 2]++;
+        }
+        P.ref.push_back(r);
+        P.seq.push_back(s);
+        P.strand.push_back(strand);
+        P.off.push_back(o0 + len);
+        P.longest = std::max<uint32_t>(P.longest, (uint32_t)len);
+        P.lds_units = std::max(P.lds_units, kbo::refset_units(set->descs[r].n_sets));
+    }
+
+    // walk, derandomize + translate, run lengths of one slab; its records behind those of the slabs so far
+    void run_slab(const SlabPlan &P, uint32_t threshold)
+    {
+        const size_t np = P.pairs();
+        if (!np) return;
+        const size_t bytes = ((size_t)P.bytes() + 15) / 16 * 16 + 64;
+        d_ms.ensure(bytes);
+        d_chars.ensure(bytes);
+        d_poff.ensure((np + 1) * sizeof(uint64_t));
+        d_items.ensure(P.items.size() * sizeof(uint32_t));
+        d_tasks.ensure(P.tasks.size() * sizeof(uint32_t));
+        const size_t scratch_words = kbo::chunk_items_scratch_words((uint32_t)np);
+        d_scratch.ensure(scratch_words * sizeof(uint32_t));
+        d_total.ensure(16);
+        HIP_OK(hipMemcpyAsync(d_poff.p, P.off.data(), (np + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_items.p, P.items.data(), P.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_tasks.p, P.tasks.data(), P.tasks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        kbo::RefsetWalkArgs a;
+        a.descs = ds->descs.as<kbo::RefsetDesc>();
+        a.arena = ds->arena.as<uint4>();
+        a.tasks = d_tasks.as<uint4>();
+        a.items = d_items.as<uint4>();
+        a.n_tasks = (uint32_t)(P.tasks.size() / 4);
+        a.k = k;
+        a.q = d_q.as<uint8_t>();
+        a.ms = d_ms.as<uint8_t>();
+        HIP_OK(kbo::launch_refset_walk(a, P.lds_units, st));
+        for (size_t p = 0; p < np; p++)
+            if (!walked[P.ref[p]]) {
+                walked[P.ref[p]] = 1;
+                t_routes[0]++;
+            }
+        t_routes[2] += np;
+        derand_translate_host_offsets(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), P.off.data(), np, k, threshold, nullptr, d_chars.as<uint8_t>(),
+                                      nullptr, st, P.longest, &d_piece);
+        HIP_OK(kbo::launch_rle_count(d_chars.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, gap, d_scratch.as<uint32_t>(),
+                                     d_total.as<uint32_t>(), st, P.longest, true));
+        uint32_t total = 0;
+        first.resize(scratch_words);
+        HIP_OK(hipMemcpyAsync(&total, d_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(first.data(), d_scratch.p, scratch_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (!rle_capacity) {
+            rle_capacity = g_record_capacity.load();
+            d_rles.ensure(rle_capacity * kRleWords * sizeof(uint32_t));
+        }
+        if (total > rle_capacity) { // (the count is known before anything is emitted: room for all of them, and some to spare)
+            rle_capacity = (size_t)total + total / 4 + 16;
+            d_rles.ensure(rle_capacity * kRleWords * sizeof(uint32_t));
+        }
+        if (total) {
+            HIP_OK(kbo::launch_rle_emit(d_chars.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, gap, d_scratch.as<uint32_t>(),
+                                        d_rles.as<uint32_t>(), (uint32_t)rle_capacity, st, P.longest, true));
+            recs.resize((size_t)total * kRleWords);
+            HIP_OK(hipMemcpyAsync(recs.data(), d_rles.p, recs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+        }
+        const uint32_t *sums = first.data() + np + 1;
+        auto first_run = [&](size_t p) { return (size_t)sums[p / 1024] + first[p]; };
+        for (size_t p = 0; p < np; p++) {
+            const uint32_t r = P.ref[p];
+            if (ref_begin[r] == ~0ull) ref_begin[r] = out.size();
+            for (size_t x = first_run(p); x < first_run(p + 1); x++) {
+                const uint32_t *w = recs.data() + x * kRleWords;
+                out.push_back(kbo_ref_run{r, P.seq[p], P.strand[p], kbo_rle32{w[0], w[1], w[2], w[3], w[4], w[5], w[6]}});
+            }
+            ref_end[r] = out.size();
+        }
+        t_routes[3]++;
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+int kbo_refset_build(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, kbo_refset_t **out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(out, KBO_E_BAD_ARG, "null out");
+        *out = nullptr;
+        KBO_REQUIRE(seqs && lens && n_refs > 0, KBO_E_BAD_ARG, "assert!(!slices.is_empty()) (index.rs:60)");
+        KBO_REQUIRE(n_refs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 references");
+        for (size_t r = 0; r < n_refs; r++) KBO_REQUIRE(seqs[r] || lens[r] == 0, KBO_E_BAD_ARG, "null reference sequence");
+        kbo_build_opts o;
+        if (opts) o = *opts; else kbo_build_opts_default(&o);
+        KBO_REQUIRE(o.k > 0 && o.k <= 255, KBO_E_BAD_ARG, "k must be in 1..255");
+        std::unique_ptr<kbo_refset> set(new kbo_refset());
+        set->k = o.k;
+        set->descs.assign(n_refs, kbo::RefsetDesc{});
+        set->own.resize(n_refs);
+        std::vector<std::vector<uint32_t>> forms(n_refs);
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (size_t r; (r = next.fetch_add(1)) < n_refs;) {
+                kbo::RefsetDesc &d = set->descs[r];
+                std::unique_ptr<kbo_index> idx(new kbo_index());
+                try {
+                    kbo::BuildParams p;
+                    p.k = o.k;
+                    p.add_revcomp = o.add_revcomp != 0;
+                    p.num_threads = 1;
+                    kbo::build_host_index(&seqs[r], &lens[r], 1, p, idx->host);
+                } catch (const std::exception &) {
+                    d.status = KBO_E_UNSUPPORTED; // (what kbo_index_build of it alone cannot build either)
+                    continue;
+                }
+                const kbo::HostIndex &h = idx->host;
+                d.n_sets = (uint32_t)h.n_sets;
+                d.n_kmers = h.n_kmers;
+                for (int c = 0; c < 4; c++) d.C[c] = (uint32_t)h.C[c];
+                if (h.n_kmers == 0) d.status = KBO_E_BAD_ARG; // n_kmers > 0 (derandomize.rs:134)
+                else if (h.n_sets > kbo::kRefsetMaxRows) {
+                    d.route = 1;
+                    set->own[r] = std::move(idx);
+                } else append_lds_form(h, forms[r]);
+            }
+        };
+        std::vector<std::thread> team;
+        for (uint32_t t = 1; t < std::min<size_t>(std::max(1u, o.num_threads), n_refs); t++) team.emplace_back(work);
+        work();
+        for (auto &t : team) t.join();
+        size_t words = 0;
+        for (auto &f : forms) words += f.size();
+        KBO_REQUIRE(words / 4 < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "the set's packed layout exceeds 2^32 units");
+        set->arena.reserve(words);
+        for (size_t r = 0; r < n_refs; r++) {
+            set->descs[r].off = (uint32_t)(set->arena.size() / 4);
+            set->arena.insert(set->arena.end(), forms[r].begin(), forms[r].end());
+            std::vector<uint32_t>().swap(forms[r]);
+        }
+        *out = set.release();
+    });
+}
+
+void kbo_refset_free(kbo_refset_t *set) { delete set; }
+size_t kbo_refset_size(const kbo_refset_t *set) { return set ? set->descs.size() : 0; }
+size_t kbo_refset_k(const kbo_refset_t *set) { return set ? set->k : 0; }
+uint64_t kbo_refset_n_kmers(const kbo_refset_t *set, size_t r) { return set && r < set->descs.size() ? set->descs[r].n_kmers : 0; }
+int kbo_refset_status(const kbo_refset_t *set, size_t r) { return set && r < set->descs.size() ? set->descs[r].status : KBO_E_BAD_ARG; }
+
+int kbo_refset_to_device(kbo_refset_t *set, int device)
+{
+    return guarded([&] {
+        KBO_REQUIRE(set, KBO_E_BAD_ARG, "null set");
+        const int dev = device < 0 ? current_device() : device;
+        (void)device_set(set, dev);
+        for (auto &idx : set->own)
+            if (idx) (void)device_view(idx.get(), dev, nullptr, 0, true);
+    });
+}
+
+int kbo_set_refset_record_capacity(size_t records)
+{
+    g_record_capacity = std::max<size_t>(1, records);
+    return KBO_OK;
+}
+
+int kbo_refset_last_routes(uint64_t out[4])
+{
+    if (!out) return KBO_E_BAD_ARG;
+    std::copy(t_routes, t_routes + 4, out);
+    return KBO_OK;
+}
+
+int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_find_opts *opts,
+                    int strands, kbo_ref_run **runs, uint64_t *n_runs)
+{
+    return guarded([&] {
+        static_assert(sizeof(kbo_ref_run) == 40, "kbo_ref_run is 40 bytes");
+        KBO_REQUIRE(strands >= 1 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+        KBO_REQUIRE(set && runs && n_runs, KBO_E_BAD_ARG, "null argument");
+        *runs = nullptr;
+        *n_runs = 0;
+        kbo_find_opts o;
+        if (opts) o = *opts; else kbo_find_opts_default(&o);
+        KBO_REQUIRE(o.max_error_prob <= 1.0 && o.max_error_prob > 0.0, KBO_E_BAD_ARG, "0 < max_error_prob <= 1 (derandomize.rs:136-137)");
+        const size_t n_refs = set->descs.size();
+        std::vector<uint32_t> thr(n_refs, 0);
+        for (size_t r = 0; r < n_refs; r++) {
+            if (set->descs[r].status) continue;
+            thr[r] = (uint32_t)random_match_threshold(set->k, set->descs[r].n_kmers, 4, o.max_error_prob); // lib.rs:620
+            KBO_REQUIRE(thr[r] > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
+        }
+        check_batch(concat, offsets, n_seqs);
+        check_len_threshold(offsets, n_seqs, set->k, 2);
+        const uint64_t total = offsets[n_seqs];
+        KBO_REQUIRE(total < (1ull << 31), KBO_E_UNSUPPORTED, "a batch of 2^31 bases or more");
+        std::fill(t_routes, t_routes + 4, 0);
+
+        const int dev = current_device();
+        Finder F;
+        F.set = set;
+        F.offsets = offsets;
+        F.k = set->k;
+        F.chunk = std::max<uint32_t>(kbo::kRefsetChunk, 4u * set->k);
+        F.gap = (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu);
+        F.rev_base = (total + 15) / 16 * 16;
+        F.ds = device_set(set, dev);
+        F.ref_begin.assign(n_refs, ~0ull);
+        F.ref_end.assign(n_refs, 0);
+        F.walked.assign(n_refs, 0);
+        StreamScope stream;
+        F.st = stream.s;
+        // the batch, once; its '-' strand behind it, made where it is
+        F.d_q.alloc(2 * F.rev_base + 64);
+        F.d_off.alloc((n_seqs + 1) * sizeof(uint64_t));
+        HIP_OK(hipMemsetAsync(F.d_q.p, 0, 2 * F.rev_base + 64, F.st));
+        HIP_OK(hipMemcpyAsync(F.d_q.p, concat, total, hipMemcpyHostToDevice, F.st));
+        HIP_OK(hipMemcpyAsync(F.d_off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, F.st));
+        if (strands & KBO_STRAND_REV)
+            HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
+
+        // the references of the LDS kernel in the order of their thresholds: a slab has one
+        std::vector<uint32_t> order;
+        for (size_t r = 0; r < n_refs; r++)
+            if (!set->descs[r].status && !set->descs[r].route) order.push_back((uint32_t)r);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return thr[a] < thr[b]; });
+        const uint64_t budget = slab_bytes_for(nullptr);
+        const uint32_t n_strands = strands == 3 ? 2 : 1;
+        SlabPlan P;
+        P.clear();
+        uint32_t slab_thr = 0;
+        for (uint32_t r : order) {
+            for (size_t s = 0; s < n_seqs; s++)
+                for (uint32_t strand = 1; strand <= 2; strand++) {
+                    if (!(strands & strand)) continue;
+                    const uint64_t len = offsets[s + 1] - offsets[s];
+                    if (P.pairs() && (P.bytes() + len > budget || slab_thr != thr[r])) {
+                        F.run_slab(P, slab_thr);
+                        P.clear();
+                    }
+                    slab_thr = thr[r];
+                    F.add_pair(P, r, (uint32_t)s, strand);
+                }
+        }
+        F.run_slab(P, slab_thr);
+
+        // the references that do not fit the LDS form: their own index through the single-index pipeline, one at a time
+        std::vector<uint64_t> rle_off(2 * n_seqs + 1);
+        for (size_t r = 0; r < n_refs; r++) {
+            if (set->descs[r].status || !set->descs[r].route) continue;
+            RleSink<kbo_rle> sink;
+            sink.max_gap_len = o.max_gap_len;
+            sink.rle_offsets = rle_off.data();
+            matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, o.max_error_prob, false, nullptr, &sink, strands);
+            kbo_rle *got = nullptr;
+            sink.take(&got);
+            MallocPtr<kbo_rle> hold(got);
+            F.ref_begin[r] = F.out.size();
+            for (size_t s = 0; s < n_seqs; s++)
+                for (uint32_t strand = 1; strand <= 2; strand++)
+                    for (uint64_t x = rle_off[2 * s + strand - 1]; x < rle_off[2 * s + strand]; x++) {
+                        const kbo_rle &w = got[x];
+                        F.out.push_back(kbo_ref_run{(uint32_t)r, (uint32_t)s, strand,
+                                                    kbo_rle32{(uint32_t)w.start, (uint32_t)w.end, (uint32_t)w.matches, (uint32_t)w.mismatches,
+                                                              (uint32_t)w.jumps, (uint32_t)w.gap_bases, (uint32_t)w.gap_opens}});
+                    }
+            F.ref_end[r] = F.out.size();
+            t_routes[1]++;
+            t_routes[2] += n_seqs * n_strands;
+        }
+
+        MallocPtr<kbo_ref_run> res = malloc_array<kbo_ref_run>(F.out.size());
+        size_t at = 0;
+        for (size_t r = 0; r < n_refs; r++) {
+            if (F.ref_begin[r] == ~0ull) continue;
+            std::copy(F.out.begin() + F.ref_begin[r], F.out.begin() + F.ref_end[r], res.get() + at);
+            at += F.ref_end[r] - F.ref_begin[r];
+        }
+        *n_runs = at;
+        *runs = res.release();
+    });
+}
+
+} // extern "C"

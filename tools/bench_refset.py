@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""kbo::find against a set of references: kbo_refset_build + kbo_refset_to_device and kbo_find_refset, against the only way there was
+before - one kbo_index_build + kbo_index_to_device + kbo_find_batch_strands per reference.  Prints one JSON line: seconds of the
+set's build + upload, seconds of the find (median of REPEATS calls behind one warm-up call, with their spread), the pair-bases per
+second that is, the per-reference seconds of the loop (timed over LOOP references behind two warm-up references, and scaled to all
+of them), the ratio, and whether the set's records equal the loop's for the references the loop took.
+Workload: REFS random references of REF_BP bases at k = 31 against a query of QUERY_BP bases in CONTIGS contigs, both strands; a
+copy of every 40th reference with 1 % substitutions lies in the query, so that there are runs to report.
+Usage: tools/bench_refset.py   (environment: REFS=2000 REF_BP=1000 QUERY_BP=5000000 CONTIGS=50 LOOP=50 REPEATS=3)
+The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import kbo_amd  # noqa: E402
+from kbo_amd import batch, refset  # noqa: E402
+
+REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS = (int(os.environ.get(n, d)) for n, d in (
+    ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3)))
+K, THREADS = 31, 16
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+rng = np.random.default_rng(2024)
+refs = [ACGT[rng.integers(0, 4, REF_BP)] for _ in range(REFS)]
+per = QUERY_BP // CONTIGS
+contigs = [ACGT[rng.integers(0, 4, per)] for _ in range(CONTIGS)]
+for i, r in enumerate(range(0, REFS, 40)):
+    c = contigs[i % CONTIGS]
+    at = int(rng.integers(0, per - REF_BP))
+    copy = refs[r].copy()
+    pos = np.flatnonzero(rng.random(REF_BP) < 0.01)
+    copy[pos] = ACGT[(np.searchsorted(ACGT, copy[pos]) + 1) % 4]
+    c[at:at + REF_BP] = copy
+concat = np.concatenate(contigs)
+offsets = (np.arange(CONTIGS + 1, dtype=np.uint64) * np.uint64(per))
+opts = kbo_amd.BuildOpts(k=K, num_threads=THREADS)
+fopts = kbo_amd.FindOpts()
+pair_bases = REFS * 2 * int(offsets[-1])
+
+import torch  # noqa: E402
+assert torch.cuda.is_available(), "this measures the GPU path: no device, no number"
+
+t0 = time.perf_counter()
+rs = refset.RefSet.build(refs, opts)
+t1 = time.perf_counter()
+rs.to_device()
+torch.cuda.synchronize()
+t2 = time.perf_counter()
+got = refset.find_refset(contigs, rs, fopts, strands=3)  # warm-up: code objects, the call's buffers
+times = []
+for _ in range(REPEATS):
+    t = time.perf_counter()
+    got = refset.find_refset(contigs, rs, fopts, strands=3)
+    times.append(time.perf_counter() - t)
+find_s = statistics.median(times)
+res = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+       "refset_build_s": round(t1 - t0, 4), "refset_to_device_s": round(t2 - t1, 4), "find_refset_s": round(find_s, 4),
+       "find_refset_s_all": [round(t, 4) for t in times], "find_refset_gbp_per_s": round(pair_bases / find_s / 1e9, 2),
+       "records": int(len(got)), "routes": refset.last_routes()}
+
+if LOOP > 0:
+    def one(r):
+        """(seconds of build, of to_device, of find) for reference r alone, and its records"""
+        a = time.perf_counter()
+        sbwt, _ = kbo_amd.build([refs[r]], kbo_amd.BuildOpts(k=K))
+        b = time.perf_counter()
+        sbwt.to_device()
+        torch.cuda.synchronize()
+        c = time.perf_counter()
+        rles, ro = batch.find_batch_strands(sbwt, concat, offsets, fopts, strands=3)
+        d = time.perf_counter()
+        return (b - a, c - b, d - c), rles
+    for r in (REFS - 1, REFS - 2):
+        one(r)
+    picks = list(range(0, REFS, max(1, REFS // LOOP)))[:LOOP]
+    sums, equal = np.zeros(3), True
+    for r in picks:
+        t, rles = one(r)
+        sums += t
+        mine = got[got["ref"] == r]
+        equal = equal and len(mine) == len(rles) and all(
+            np.array_equal(mine[f].astype(np.uint64), rles[:, i]) for i, f in enumerate(("start", "end", "matches", "mismatches", "jumps", "gap_bases", "gap_opens")))
+    per_ref = sums / len(picks)
+    loop_all = float(per_ref.sum()) * REFS
+    res.update({"loop_refs_timed": len(picks), "loop_per_ref_s": {"build": round(per_ref[0], 5), "to_device": round(per_ref[1], 5), "find": round(per_ref[2], 5)},
+                "loop_scaled_s": round(loop_all, 2), "set_total_s": round(t2 - t0 + find_s, 4),
+                "ratio_loop_over_set": round(loop_all / (t2 - t0 + find_s), 1), "ratio_find_only": round(float(per_ref[2]) * REFS / find_s, 1),
+                "records_equal_loop": bool(equal)})
+print(json.dumps(res))
