@@ -146,6 +146,11 @@ pub mod ffi {
                                   max_seq_len: usize, p: f64, max_gap_len: usize, d_ms: *mut u8, d_chars_out: *mut u8, d_work: *mut c_void,
                                   work_bytes: usize, d_rle_work: *mut c_void, d_records: *mut u32, capacity: usize, stream: *mut c_void,
                                   tail_stream: *mut c_void, fused: *mut c_int) -> c_int;
+        // derandomize_ms_vec + translate_ms_vec over device-resident MS bytes with a threshold per sequence, at any length
+        pub fn kbo_derand_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize;
+        pub fn kbo_derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
+                                            d_thresholds: *const u32, min_threshold: usize, d_ref: *const u8, d_chars_out: *mut u8,
+                                            d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
         pub fn kbo_matches_packed_dev_scratch_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_matches_packed_dev(idx: *mut KboIndex, d_words: *const u32, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
                                       max_seq_len: usize, uniform_len: usize, d_exc_pos: *const u64, d_exc_byte: *const u8, n_exc: usize,
@@ -163,6 +168,24 @@ fn check(rc: c_int) {
         let msg = unsafe { std::ffi::CStr::from_ptr(ffi::kbo_last_error()) }.to_string_lossy().into_owned();
         panic!("kbo_hip error {}: {}", rc, msg);
     }
+}
+
+/// `translate_ms_vec(derandomize_ms_vec(ms_s, k, t_s), k, t_s)` (derandomize.rs:269-288, translate.rs:263-293) for every sequence of
+/// a device-resident batch, `t_s = d_thresholds[s]`; with `d_ref` non-null `format::relative_to_ref` of it (format.rs:266-287).
+/// Enqueues a constant number of launches on `stream` and returns; nothing is read back.  `d_work`: `derand_seq_work_bytes` bytes,
+/// 16-byte aligned; the per-base buffers carry 16 bytes of slack; not in place.
+///
+/// # Safety
+/// Every pointer is a device pointer of the size `include/kbo_hip.h` documents for `kbo_derand_translate_seq_dev`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
+                                       d_thresholds: *const u32, min_threshold: usize, d_ref: *const u8, d_chars_out: *mut u8,
+                                       d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) {
+    check(ffi::kbo_derand_translate_seq_dev(d_ms, d_offsets, n_seqs, total_bases, k, d_thresholds, min_threshold, d_ref, d_chars_out,
+                                            d_work, work_bytes, stream));
+}
+pub fn derand_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize {
+    unsafe { ffi::kbo_derand_seq_work_bytes(n_seqs, total_bases, k, min_threshold) }
 }
 
 /// Stands in for `(&SbwtIndexVariant, &LcsArray)`: the index resident in HBM.  Immutable after construction.

@@ -547,6 +547,30 @@ int kbo_derand_translate_dev(const uint8_t *d_ms, const uint64_t *d_offsets, siz
                              uint64_t total_bases, size_t k, size_t threshold, const uint8_t *d_ref,
                              uint8_t *d_chars_out, size_t max_seq_len, void *d_work, size_t work_bytes,
                              void *stream);
+/* The same stage for a batch in which every sequence has a threshold of its own, at any length: d_thresholds[s] (on the device) is
+ * sequence s's threshold and min_threshold (known on the host) a lower bound of them that sizes the tables; a looser bound costs
+ * scratch and time, never a character.  For every sequence of >= 3 bases with min_threshold <= d_thresholds[s] <= k the characters
+ * are exactly translate_ms_vec(derandomize_ms_vec(ms_s, k, t_s), k, t_s) - for ANY MS bytes <= k, not only those a walk produces,
+ * with no look-ahead heuristic and no fallback launch - and with d_ref != NULL format::relative_to_ref of that.  Sequences of fewer
+ * than 3 bases are skipped (their bytes of d_chars_out stay as they were); a threshold outside [min_threshold, k] gives that sequence
+ * unspecified characters and nothing else.  The call enqueues 11 kernel launches and no memset on `stream`, whatever n_seqs, the
+ * lengths and the thresholds are, reads nothing back and returns: chunks of KBO_DERAND_SEQ_CHUNK positions and groups of
+ * KBO_DERAND_SEQ_GROUP positions (kbo_hip_tuning.h), neither ever spanning two sequences, are listed on the device from d_offsets;
+ * every chunk and every group gets a table of k - min_threshold + 1 states that says what it does to the value entering it, one
+ * lane per sequence runs over that sequence's groups, and a last pass per chunk writes the characters.
+ * d_ms, d_ref, d_chars_out: total_bases + 16 bytes, 4-byte aligned; d_chars_out must NOT be d_ms (a chunk reads the MS byte below
+ * it, which belongs to another workgroup).  d_work: required, 16-byte aligned, kbo_derand_seq_work_bytes() bytes - about
+ * total_bases * (k - min_threshold + 6) / 32 + n_seqs * (8 (k - min_threshold) + 64) bytes: 4 (k - min_threshold + 1) bytes of table per
+ * chunk of 128 bases, 1/64 of that per group, 20 bytes of descriptor and value per chunk, and a chunk and a group more per sequence
+ * (0.7 bytes a base at k = 31, t >= 14; 8.1 at k = 255, t >= 2).
+ * No byte of d_work beyond that figure is touched.  n_seqs < 2^28.
+ * Errors, before anything is enqueued: KBO_E_BAD_ARG (null argument, k outside 1..255, min_threshold > k, work_bytes too small,
+ * alignment), KBO_E_EMPTY_QUERY (n_seqs == 0), KBO_E_THRESHOLD_LE_1 (min_threshold <= 1, derandomize.rs:275), KBO_E_UNSUPPORTED
+ * (total_bases + 16 > 2^32, n_seqs >= 2^28). */
+size_t kbo_derand_seq_work_bytes(size_t n_seqs, uint64_t total_bases, size_t k, size_t min_threshold);
+int kbo_derand_translate_seq_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 size_t k, const uint32_t *d_thresholds, size_t min_threshold, const uint8_t *d_ref,
+                                 uint8_t *d_chars_out, void *d_work, size_t work_bytes, void *stream);
 /* kbo::map with fill_gaps = false and call_variants = false (lib.rs:726-738; format != 0: + relative_to_ref, lib.rs:756-757) or
  * kbo::matches (lib.rs:612-628; format = 0) over a device-resident batch, the whole chain MS -> derandomize_ms_vec ->
  * translate_ms_vec enqueued on `stream`; the threshold comes from the index and max_error_prob (lib.rs:620, 731).  Batches of

@@ -211,6 +211,12 @@ int kbo_set_refset_record_capacity(size_t records);
  * through the single-index pipeline, out[2] (reference, sequence, strand) pairs walked over both routes, out[3] slabs */
 int kbo_refset_last_routes(uint64_t out[4]);
 
+/* ------------------------------------------------------------------ kbo_derand_translate_seq_dev */
+/* positions of a chunk and of a group (64 chunks) of derand_seq_kernels.hip; neither spans two sequences.  A sequence of more than
+ * KBO_DERAND_SEQ_GROUP positions makes the lane that owns it loop over its groups */
+#define KBO_DERAND_SEQ_CHUNK 128
+#define KBO_DERAND_SEQ_GROUP 8192
+
 /* ------------------------------------------------------------------ experiments recorded in DESIGN.md section 6 */
 /* plain walk kernel: only the first lane_limit lanes of every wave take reads (64 = all; what a sub-wave tiling would
  * have to beat), and every workgroup reserves dummy_lds_bytes of LDS it never touches (what staging a wave's MS values

@@ -619,6 +619,42 @@ class DeviceBatch:
         return self.summary.cpu().numpy().view(np.uint32)
 
 
+def derand_translate_seq(ms, offsets, k, thresholds, ref=None, stream=None, min_threshold=None):
+    """kbo_derand_translate_seq_dev over torch tensors on the device: derandomize_ms_vec + translate_ms_vec (+ relative_to_ref when
+    `ref` is given) with thresholds[s] for sequence s, at any length.  ms, ref: uint8; offsets: int64 or uint64 (n_seqs + 1);
+    thresholds: int32 (n_seqs).  min_threshold: a lower bound of the thresholds when the caller knows one (it sizes the scratch);
+    otherwise their minimum, from a host copy.  Returns the characters as a uint8 tensor of offsets[-1] elements; the bytes of
+    sequences of fewer than 3 bases are unspecified.  Enqueued on `stream` (default: the current one), not synchronised."""
+    import torch
+    device = ms.device
+    n_seqs = int(offsets.numel()) - 1
+    assert ms.dtype == torch.uint8 and thresholds.dtype == torch.int32 and int(thresholds.numel()) == n_seqs
+    assert offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    if min_threshold is None:
+        min_threshold = int(thresholds.min().item()) if n_seqs > 0 else 2
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+
+    def padded(t):  # the 16 bytes of slack behind a per-base buffer
+        t = t.contiguous()
+        if int(t.numel()) >= total + 16:
+            return t
+        p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+        p[:total].copy_(t[:total])
+        return p
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(s):
+        ms_p = padded(ms)
+        ref_p = padded(ref) if ref is not None else None
+        off, thr = offsets.contiguous(), thresholds.contiguous()
+        out = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+        wb = int(lib().kbo_derand_seq_work_bytes(n_seqs, total, k, min_threshold))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=device)
+        check(lib().kbo_derand_translate_seq_dev(ms_p.data_ptr(), off.data_ptr(), n_seqs, total, k, thr.data_ptr(), min_threshold,
+                                                 ref_p.data_ptr() if ref_p is not None else None, out.data_ptr(), work.data_ptr(), wb,
+                                                 s.cuda_stream))
+    return out[:total]  # (the scratch and the padded copies were allocated on `s`: the allocator reuses them in that stream's order)
+
+
 def stream_pair(device, tail_cus=-1):
     """(stream, tail_stream) as torch streams, made by the library (kbo_hip.h kbo_stream_pair_create): the tail stream - a batch's second
     pass - on compute units of its own.  The pair lives as long as the process (the torch wrappers do not own the streams)."""

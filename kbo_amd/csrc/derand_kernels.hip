@@ -25,19 +25,7 @@ namespace {
 //     res[pos]  = 'R'                                  if 2 <= pos < len-1 && condR(pos-1)
 //               = translate_ms_val(x[pos], next, prev).0   otherwise
 //     next = pos < len-1 ? x[pos+1] : x[pos];   prev = pos > 1 ? x[pos-1] : k   (note pos > 1)
-// so one right-to-left pass with a three-value window produces the characters.
-__device__ __forceinline__ uint32_t translate_char(int xm, int xc, int xn, uint32_t rel, uint32_t len, int K, int T)
-{
-    // branch-free; 0 < v < T is written (unsigned)(v - 1) < (unsigned)(T - 1), 2 <= rel <= len-2 as
-    // (rel - 2) < (len - 3) (len >= 3)
-    const uint32_t Tm1 = (uint32_t)(T - 1);
-    const int prev = rel > 1u ? xm : K;
-    const int next = rel < len - 1u ? xn : xc;
-    const bool inherits = (rel - 2u) < (len - 3u) && xm > T && (uint32_t)(xc - 1) < Tm1;
-    const bool own = xc > T && (uint32_t)(next - 1) < Tm1;
-    const uint32_t plain = xc <= 0 ? ((next == 1 && prev > 0) ? (uint32_t)'X' : (uint32_t)'-') : (uint32_t)'M';
-    return (inherits || own) ? (uint32_t)'R' : plain;
-}
+// so one right-to-left pass with a three-value window produces the characters (translate_char, device_util.hpp).
 
 struct DtState {
     int x_cur, x_next, x_prev;
@@ -207,16 +195,6 @@ __global__ __launch_bounds__(256) void derand_flagged_kernel(
 // MS value in, character out), and the wave copies the span back out, applying
 // format::relative_to_ref on the way when a reference is given.  Global traffic is fully
 // coalesced (the per-lane kernel above issues one 16-byte request per lane instead).
-__device__ __forceinline__ uint32_t fmt_word(uint32_t ch, uint32_t rf)
-{ // per byte: ch in {'M','R'} ? rf : '-'
-    const uint32_t xm = ch ^ 0x4D4D4D4Du, xr = ch ^ 0x52525252u; // zero byte where equal
-    const uint32_t zm = ~(((xm & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | xm | 0x7F7F7F7Fu);
-    const uint32_t zr = ~(((xr & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | xr | 0x7F7F7F7Fu);
-    const uint32_t hi = zm | zr;                 // 0x80 in matching bytes
-    const uint32_t mask = (hi >> 7) * 0xFFu;     // 0xFF in matching bytes
-    return (rf & mask) | (0x2D2D2D2Du & ~mask);
-}
-
 // SKEW: the LDS image gets 4 bytes of padding after every 128 bytes.  Lanes touch position p of their own
 // sequence in the same step, so with sequences whose common length is a multiple of 32 bytes the flat image
 // puts 8..64 lanes on one bank (reads of 128 or 256 bases: 3.2x slower); the padding spreads them.

@@ -65,6 +65,31 @@ template <int J> __device__ __forceinline__ void blk_or_byte(uint4 &v, uint32_t 
     else v.w |= sh;
 }
 
+// One character of translate_ms_vec (translate.rs:263-293) from the derandomised values x[rel-1], x[rel], x[rel+1] of a sequence
+// of len >= 3 positions: the closed form of its sequential 'R','R' look-ahead (derand_kernels.hip has the derivation).
+__device__ __forceinline__ uint32_t translate_char(int xm, int xc, int xn, uint32_t rel, uint32_t len, int K, int T)
+{
+    // branch-free; 0 < v < T is written (unsigned)(v - 1) < (unsigned)(T - 1), 2 <= rel <= len-2 as
+    // (rel - 2) < (len - 3) (len >= 3)
+    const uint32_t Tm1 = (uint32_t)(T - 1);
+    const int prev = rel > 1u ? xm : K;
+    const int next = rel < len - 1u ? xn : xc;
+    const bool inherits = (rel - 2u) < (len - 3u) && xm > T && (uint32_t)(xc - 1) < Tm1;
+    const bool own = xc > T && (uint32_t)(next - 1) < Tm1;
+    const uint32_t plain = xc <= 0 ? ((next == 1 && prev > 0) ? (uint32_t)'X' : (uint32_t)'-') : (uint32_t)'M';
+    return (inherits || own) ? (uint32_t)'R' : plain;
+}
+// format::relative_to_ref (format.rs:266-287) on four characters at once
+__device__ __forceinline__ uint32_t fmt_word(uint32_t ch, uint32_t rf)
+{ // per byte: ch in {'M','R'} ? rf : '-'
+    const uint32_t xm = ch ^ 0x4D4D4D4Du, xr = ch ^ 0x52525252u; // zero byte where equal
+    const uint32_t zm = ~(((xm & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | xm | 0x7F7F7F7Fu);
+    const uint32_t zr = ~(((xr & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | xr | 0x7F7F7F7Fu);
+    const uint32_t hi = zm | zr;                 // 0x80 in matching bytes
+    const uint32_t mask = (hi >> 7) * 0xFFu;     // 0xFF in matching bytes
+    return (rf & mask) | (0x2D2D2D2Du & ~mask);
+}
+
 // Rank inside one 16-byte block { base, w0, w1, w2 }: base + popcount of the o lowest of
 // the 96 row bits, 0 <= o < 96.  One 64-bit shift builds the "bits to drop" masks of all
 // three words: X = ~0 << (o mod 64) is the drop mask of (w0,w1) when o < 64 and of w2

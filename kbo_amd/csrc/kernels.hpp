@@ -316,6 +316,16 @@ size_t derand_long_scratch_bytes(uint64_t len, uint32_t k, uint32_t threshold);
 hipError_t launch_derand_long(const uint8_t *d_ms, uint32_t len, uint32_t k, uint32_t threshold, const uint8_t *d_ref,
                               uint8_t *d_chars_out, int32_t *d_derand_out, void *d_scratch, hipStream_t stream);
 constexpr uint32_t kLongSeq = 1u << 16; // sequences longer than this take the chunked path
+// A5+A6 (+ relative_to_ref when d_ref != nullptr) for a batch in which sequence s has the threshold d_thresholds[s] and any length
+// (derand_seq_kernels.hip): bit-identical to the sequential loops for every sequence of >= 3 bases whose threshold lies in
+// [min_threshold, k]; shorter sequences are skipped, other thresholds give unspecified characters.  A constant number of launches,
+// nothing read back; d_work >= derand_seq_work_bytes(), 16-byte aligned; n_seqs < 2^28, total_bases + 16 <= 2^32; not in place.
+constexpr uint32_t kDerandSeqChunk = 128;      // positions per chunk (== KBO_DERAND_SEQ_CHUNK)
+constexpr uint32_t kDerandSeqGroupChunks = 64; // chunks per group: KBO_DERAND_SEQ_GROUP = 8192 positions
+size_t derand_seq_work_bytes(uint32_t n_seqs, uint64_t total_bases, uint32_t k, uint32_t min_threshold);
+hipError_t launch_derand_translate_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
+                                       const uint32_t *d_thresholds, uint32_t min_threshold, const uint8_t *d_ref, uint8_t *d_chars_out,
+                                       void *d_work, hipStream_t stream);
 // A6 alone on clamped i32 derandomised values: one lane per position.
 hipError_t launch_translate(const int32_t *d_derand, uint64_t len, uint32_t k, uint32_t threshold,
                             uint8_t *d_chars_out, hipStream_t stream);

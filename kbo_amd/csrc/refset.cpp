@@ -1,8 +1,7 @@
 // refset.cpp — kbo_refset_t (N one-sequence indexes in one packed device layout) and kbo_find_refset (kbo_hip.h "find against a
-// set of references").  The walk is refset_kernels.hip's; what follows it - derandomize_ms_vec / translate_ms_vec,
-// run_lengths_gapped - are the single-index pipeline's kernels as they are: a slab of (reference, sequence, strand) pairs is laid
-// out pair by pair and looks like an ordinary batch to them.  They take one threshold a launch, so the references are walked in
-// the order of their thresholds (at most k values) and a slab never mixes two; the records go back into reference order at the end.
+// set of references").  The walk is refset_kernels.hip's.  A slab of (reference, sequence, strand) pairs is laid out
+// pair by pair and looks like an ordinary batch to what follows: derandomize_ms_vec / translate_ms_vec with a threshold per pair
+// (derand_seq_kernels.hip: the pair's reference's), then the single-index pipeline's run_lengths_gapped kernels as they are.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 
@@ -105,13 +104,13 @@ DevSet *device_set(kbo_refset *set, int device)
 
 // the pairs of a slab, their chunks and the workgroups' tasks, as they go to the device
 struct SlabPlan {
-    std::vector<uint32_t> ref, seq, strand; // per pair
+    std::vector<uint32_t> ref, seq, strand, thr; // per pair; thr: its reference's threshold
     std::vector<uint64_t> off;              // per pair + 1: its first byte in the slab
     std::vector<uint32_t> items, tasks;     // four words a record (kernels.hpp RefsetWalkArgs)
     uint32_t longest = 0, lds_units = 0;
     void clear()
     {
-        ref.clear(); seq.clear(); strand.clear(); items.clear(); tasks.clear();
+        ref.clear(); seq.clear(); strand.clear(); thr.clear(); items.clear(); tasks.clear();
         off.assign(1, 0);
         longest = 0;
         lds_units = 0;
@@ -123,18 +122,18 @@ struct SlabPlan {
 struct Finder {
     kbo_refset *set;
     const uint64_t *offsets;
-    uint32_t k, chunk, gap;
+    uint32_t k, chunk, gap, min_thr; // min_thr: the smallest threshold of the references that take the LDS kernel
     uint64_t rev_base; // where the '-' strand of the batch begins in d_q
     hipStream_t st;
     DevSet *ds;
-    DevBuf d_q, d_off, d_ms, d_chars, d_poff, d_items, d_tasks, d_scratch, d_total, d_rles, d_piece;
+    DevBuf d_q, d_off, d_ms, d_chars, d_poff, d_pthr, d_items, d_tasks, d_scratch, d_total, d_rles, d_derand;
     size_t rle_capacity = 0;
     std::vector<uint32_t> first, recs;
     std::vector<kbo_ref_run> out;
     std::vector<uint64_t> ref_begin, ref_end; // where every reference's records lie in `out`
     std::vector<uint8_t> walked;              // per reference: a launch of the LDS kernel has held it (the route counters)
 
-    void add_pair(SlabPlan &P, uint32_t r, uint32_t s, uint32_t strand)
+    void add_pair(SlabPlan &P, uint32_t r, uint32_t s, uint32_t strand, uint32_t threshold)
     {
         const uint64_t len = offsets[s + 1] - offsets[s], q0 = (strand == KBO_STRAND_REV ? rev_base : 0) + offsets[s], o0 = P.bytes();
         bool fresh = P.tasks.empty() || P.tasks[P.tasks.size() - 4] != r;
@@ -152,13 +151,14 @@ struct Finder {
         P.ref.push_back(r);
         P.seq.push_back(s);
         P.strand.push_back(strand);
+        P.thr.push_back(threshold);
         P.off.push_back(o0 + len);
         P.longest = std::max<uint32_t>(P.longest, (uint32_t)len);
         P.lds_units = std::max(P.lds_units, kbo::refset_units(set->descs[r].n_sets));
     }
 
     // walk, derandomize + translate, run lengths of one slab; its records behind those of the slabs so far
-    void run_slab(const SlabPlan &P, uint32_t threshold)
+    void run_slab(const SlabPlan &P)
     {
         const size_t np = P.pairs();
         if (!np) return;
@@ -166,12 +166,15 @@ struct Finder {
         d_ms.ensure(bytes);
         d_chars.ensure(bytes);
         d_poff.ensure((np + 1) * sizeof(uint64_t));
+        d_pthr.ensure(np * sizeof(uint32_t));
+        d_derand.ensure(kbo::derand_seq_work_bytes((uint32_t)np, P.bytes(), k, min_thr));
         d_items.ensure(P.items.size() * sizeof(uint32_t));
         d_tasks.ensure(P.tasks.size() * sizeof(uint32_t));
         const size_t scratch_words = kbo::chunk_items_scratch_words((uint32_t)np);
         d_scratch.ensure(scratch_words * sizeof(uint32_t));
         d_total.ensure(16);
         HIP_OK(hipMemcpyAsync(d_poff.p, P.off.data(), (np + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_pthr.p, P.thr.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_items.p, P.items.data(), P.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_tasks.p, P.tasks.data(), P.tasks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         kbo::RefsetWalkArgs a;
@@ -190,8 +193,8 @@ struct Finder {
                 t_routes[0]++;
             }
         t_routes[2] += np;
-        derand_translate_host_offsets(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), P.off.data(), np, k, threshold, nullptr, d_chars.as<uint8_t>(),
-                                      nullptr, st, P.longest, &d_piece);
+        HIP_OK(kbo::launch_derand_translate_seq(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, P.bytes(), k, d_pthr.as<uint32_t>(), min_thr,
+                                                nullptr, d_chars.as<uint8_t>(), d_derand.p, st));
         HIP_OK(kbo::launch_rle_count(d_chars.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, gap, d_scratch.as<uint32_t>(),
                                      d_total.as<uint32_t>(), st, P.longest, true));
         uint32_t total = 0;
@@ -370,30 +373,28 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
         if (strands & KBO_STRAND_REV)
             HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
 
-        // the references of the LDS kernel in the order of their thresholds: a slab has one
-        std::vector<uint32_t> order;
-        for (size_t r = 0; r < n_refs; r++)
-            if (!set->descs[r].status && !set->descs[r].route) order.push_back((uint32_t)r);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return thr[a] < thr[b]; });
+        // the references of the LDS kernel: every pair carries its reference's threshold, so a slab is cut by the budget alone
         const uint64_t budget = slab_bytes_for(nullptr);
         const uint32_t n_strands = strands == 3 ? 2 : 1;
+        F.min_thr = set->k;
+        for (size_t r = 0; r < n_refs; r++)
+            if (!set->descs[r].status && !set->descs[r].route) F.min_thr = std::min(F.min_thr, thr[r]);
         SlabPlan P;
         P.clear();
-        uint32_t slab_thr = 0;
-        for (uint32_t r : order) {
+        for (size_t r = 0; r < n_refs; r++) {
+            if (set->descs[r].status || set->descs[r].route) continue;
             for (size_t s = 0; s < n_seqs; s++)
                 for (uint32_t strand = 1; strand <= 2; strand++) {
                     if (!(strands & strand)) continue;
                     const uint64_t len = offsets[s + 1] - offsets[s];
-                    if (P.pairs() && (P.bytes() + len > budget || slab_thr != thr[r])) {
-                        F.run_slab(P, slab_thr);
+                    if (P.pairs() && P.bytes() + len > budget) {
+                        F.run_slab(P);
                         P.clear();
                     }
-                    slab_thr = thr[r];
-                    F.add_pair(P, r, (uint32_t)s, strand);
+                    F.add_pair(P, (uint32_t)r, (uint32_t)s, strand, thr[r]);
                 }
         }
-        F.run_slab(P, slab_thr);
+        F.run_slab(P);
 
         // the references that do not fit the LDS form: their own index through the single-index pipeline, one at a time
         std::vector<uint64_t> rle_off(2 * n_seqs + 1);

@@ -6,13 +6,15 @@ second that is, the per-reference seconds of the loop (timed over LOOP reference
 of them), the ratio, and whether the set's records equal the loop's for the references the loop took.
 Workload: REFS random references of REF_BP bases at k = 31 against a query of QUERY_BP bases in CONTIGS contigs, both strands; a
 copy of every 40th reference with 1 % substitutions lies in the query, so that there are runs to report.
-Usage: tools/bench_refset.py   (environment: REFS=2000 REF_BP=1000 QUERY_BP=5000000 CONTIGS=50 LOOP=50 REPEATS=3)
+Usage: tools/bench_refset.py   (environment: REFS=2000 REF_BP=1000 QUERY_BP=5000000 CONTIGS=50 LOOP=50 REPEATS=3; CONTIGS=100 makes
+the contigs 50 kbp, below the 65 536 bases at which the single-index stage changes kernels; records_crc32 compares two builds)
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
 import statistics
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -60,7 +62,7 @@ find_s = statistics.median(times)
 res = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
        "refset_build_s": round(t1 - t0, 4), "refset_to_device_s": round(t2 - t1, 4), "find_refset_s": round(find_s, 4),
        "find_refset_s_all": [round(t, 4) for t in times], "find_refset_gbp_per_s": round(pair_bases / find_s / 1e9, 2),
-       "records": int(len(got)), "routes": refset.last_routes()}
+       "records": int(len(got)), "records_crc32": zlib.crc32(got.tobytes()), "routes": refset.last_routes()}
 
 if LOOP > 0:
     def one(r):
