@@ -541,7 +541,11 @@ int kbo_ms_batch_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *
  * max_seq_len = length of the longest sequence in the batch if the caller knows it (selects
  * the LDS-staged kernel for short reads), 0 = unknown.  d_work (optional, NULL = none): scratch of
  * kbo_derand_work_bytes() bytes, 16-byte aligned; with it long reads / contigs are processed in
- * pieces of 256 positions, one lane each, instead of one lane per sequence. */
+ * pieces of 132 positions, one lane each, instead of one lane per sequence (a smaller work_bytes is not an error: one lane per
+ * sequence, the same characters).  d_ms, d_ref, d_chars_out: total_bases + 16 bytes, 4-byte aligned.  d_chars_out must NOT be d_ms
+ * (KBO_E_BAD_ARG) nor overlap it: a piece reads MS bytes up to 1024 positions above itself, which belong to other workgroups, and
+ * sequences it cannot finish that way are read again by a second launch after their other pieces' characters were written.
+ * Sequences of fewer than 3 bases are skipped (their bytes of d_chars_out are unspecified). */
 size_t kbo_derand_work_bytes(size_t n_seqs, uint64_t total_bases);
 int kbo_derand_translate_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs,
                              uint64_t total_bases, size_t k, size_t threshold, const uint8_t *d_ref,

@@ -217,6 +217,17 @@ int kbo_refset_last_routes(uint64_t out[4]);
 #define KBO_DERAND_SEQ_CHUNK 128
 #define KBO_DERAND_SEQ_GROUP 8192
 
+/* ------------------------------------------------------------------ kbo_derand_translate_dev and the host batches' stage behind the walk */
+/* test hook: the derandomize + translate stage of kbo_matches_batch / kbo_map_batch / kbo_find_batch / kbo_map_batch_opts over MS bytes
+ * of the caller's making instead of a walk's.  ms (offsets[n_seqs] bytes, any values <= k), offsets (n_seqs + 1 values from 0, ascending)
+ * and the optional ref (offsets[n_seqs] bytes, NULL = none: with it format::relative_to_ref is applied) are on the HOST; they are
+ * uploaded into buffers of offsets[n_seqs] + 16 bytes and handed to the router the slab pipeline calls, scratch for the piece-wise kernel
+ * included: sequences of up to 480 bases through the LDS kernel when none is longer, otherwise pieces up to 65 536 bases and the
+ * chunk-table scan for every longer sequence.  chars_out (host, offsets[n_seqs] bytes) gets the characters; the bytes of sequences of
+ * fewer than 3 bases are unspecified.  Synchronous, on the current device's default stream. */
+int kbo_derand_translate_host(const uint8_t *ms, const uint64_t *offsets, size_t n_seqs, size_t k, size_t threshold, const uint8_t *ref,
+                              uint8_t *chars_out);
+
 /* ------------------------------------------------------------------ experiments recorded in DESIGN.md section 6 */
 /* plain walk kernel: only the first lane_limit lanes of every wave take reads (64 = all; what a sub-wave tiling would
  * have to beat), and every workgroup reserves dummy_lds_bytes of LDS it never touches (what staging a wave's MS values

@@ -128,6 +128,7 @@ TUNING_SYMBOLS = [
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
     "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
+    "kbo_derand_translate_host",
 ]
 
 _lib = None
@@ -318,6 +319,7 @@ def lib():
     L.kbo_find_refset.argtypes = [vp, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(vp), C.POINTER(u64)]
     L.kbo_set_refset_record_capacity.argtypes = [sz]
     L.kbo_refset_last_routes.argtypes = [vp]
+    L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L
 

@@ -338,6 +338,8 @@ int kbo_derand_translate_dev(const uint8_t *d_ms, const uint64_t *d_offsets, siz
         KBO_REQUIRE(((uintptr_t)d_ms & 3) == 0 && ((uintptr_t)d_chars_out & 3) == 0 && ((uintptr_t)d_ref & 3) == 0 &&
                         ((uintptr_t)d_work & 15) == 0,
                     KBO_E_BAD_ARG, "device buffers must be 4-byte (d_work 16-byte) aligned");
+        // (the piece-wise route reads d_ms again - look-aheads into other waves' spans, the redo launch - after characters were written)
+        KBO_REQUIRE(d_chars_out != d_ms, KBO_E_BAD_ARG, "not in place");
         HIP_OK(kbo::launch_derand_translate(d_ms, d_offsets, (uint32_t)n_seqs, (uint32_t)k, (uint32_t)threshold,
                                             d_ref, d_chars_out, nullptr,
                                             (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu), 0xFFFFFFFFu,

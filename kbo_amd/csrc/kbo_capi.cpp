@@ -1570,3 +1570,36 @@ int kbo_find_batch_packed_strands(kbo_index_t *idx, const uint32_t *words, const
 }
 
 uint64_t kbo_last_batch_staged_bytes(void) { return t_last_staged; }
+
+// test hook (kbo_hip_tuning.h): the router of the slab pipeline's derandomize + translate stage over host MS bytes of any content
+int kbo_derand_translate_host(const uint8_t *ms, const uint64_t *offsets, size_t n_seqs, size_t k, size_t threshold, const uint8_t *ref,
+                              uint8_t *chars_out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(ms && offsets && chars_out, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0 && n_seqs < 0xFFFFFFFFull, KBO_E_EMPTY_QUERY, "empty batch");
+        KBO_REQUIRE(k > 0 && k <= 255, KBO_E_BAD_ARG, "k in 1..255");
+        KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
+        KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] == 0");
+        for (size_t s = 0; s < n_seqs; s++) KBO_REQUIRE(offsets[s] <= offsets[s + 1], KBO_E_BAD_ARG, "offsets ascend");
+        const uint64_t total = offsets[n_seqs];
+        KBO_REQUIRE(total > 0 && total + 16 <= (1ull << 32), KBO_E_UNSUPPORTED, "an empty batch, or one of 2^32 - 16 bases or more");
+        hipStream_t stream = nullptr;
+        const size_t bytes = (size_t)total + 16; // what kbo_derand_translate_dev documents for its per-base buffers
+        DevBuf dms(bytes), doff((n_seqs + 1) * sizeof(uint64_t)), dch(bytes), dref, piece;
+        HIP_OK(hipMemsetAsync(dms.p, 0, bytes, stream));
+        HIP_OK(hipMemsetAsync(dch.p, 0, bytes, stream));
+        HIP_OK(hipMemcpyAsync(dms.p, ms, total, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(doff.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        if (ref) {
+            dref.alloc(bytes);
+            HIP_OK(hipMemsetAsync(dref.p, 0, bytes, stream));
+            HIP_OK(hipMemcpyAsync(dref.p, ref, total, hipMemcpyHostToDevice, stream));
+        }
+        derand_translate_host_offsets(dms.as<uint8_t>(), doff.as<uint64_t>(), offsets, n_seqs, (uint32_t)k,
+                                      (uint32_t)std::min<size_t>(threshold, 0x7FFFFFFF), ref ? dref.as<uint8_t>() : nullptr,
+                                      dch.as<uint8_t>(), nullptr, stream, 0, &piece);
+        HIP_OK(hipMemcpyAsync(chars_out, dch.p, total, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+    });
+}

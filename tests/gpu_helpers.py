@@ -228,3 +228,166 @@ class Guarded:
         r = self.check()
         assert r is None, "%s%s: %s guard changed, first bad byte at guard offset %d, %d bytes changed" % (
             what + ": " if what else "", self.name, r[0], r[1], r[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------- derandomize + translate
+# over MS bytes made by numpy - no index, no walk: arbitrary bytes <= k (tests/test_gpu_derand_seq.py, tests/test_gpu_derand_arbitrary.py)
+
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+DERAND_CONTENTS = ["uniform", "below", "all_k", "anchors", "walk", "k_last", "k_first"]
+DT_PIECE, DT_REACH = 132, 1023  # kDtPiece, kDtLookahead - 1 (derand_kernels.hip): a piece looks at the positions [c1, c1 + DT_REACH]
+# sparse_k: distance from the end of the piece behind one k to the next k - just inside and just outside [c1, c1 + 1023], both sides
+SPARSE_NEAR = [1023, 1024, 1022, 1025, 1000, 1028, 1016, 1024, 1023, 1012]
+SPARSE_INSIDE = [1023, 1022, 1000, 1016, 1023, 1012]
+
+
+def derand_content(kind, rng, n, k, t, period=128):
+    """n MS bytes (values 0 .. k) of one sequence with threshold t; `period`: the granule k_last / k_first put their k at the last /
+    first position of (a chunk, a piece, a 16-byte block)"""
+    if kind == "uniform":
+        return rng.integers(0, k + 1, n, dtype=np.int64).astype(np.uint8)
+    if kind == "below":  # nothing fires but the last position: the values count down to -len
+        return rng.integers(0, t + 1, n, dtype=np.int64).astype(np.uint8)
+    if kind == "all_k":
+        return np.full(n, k, dtype=np.uint8)
+    if kind == "anchors":  # only values in (t, k): rising and falling ramps.  (t >= k - 1 has no such value: t itself, nothing fires)
+        lo, hi = t + 1, k - 1
+        if lo > hi:
+            return np.full(n, t, dtype=np.uint8)
+        span = hi - lo
+        p = np.arange(n) + int(rng.integers(0, 1000))
+        tri = np.abs((p % (2 * span + 2)) - (span + 1)).clip(0, span) if span else np.zeros(n, dtype=np.int64)
+        return (lo + tri).astype(np.uint8)
+    if kind == "walk":  # k, with ramps 0, 1, 2, ... behind mismatches every about 100 bases
+        a = np.full(n, k, dtype=np.int64)
+        p = int(rng.integers(0, 100))
+        while p < n:
+            m = min(k, n - p)
+            a[p:p + m] = np.arange(m)
+            p += int(rng.integers(k // 2 + 1, 200))
+        return a.astype(np.uint8)
+    base = rng.integers(0, k, n, dtype=np.int64)  # 0 .. k - 1
+    if kind == "sparse_k":
+        # single k's 1000 .. 1160 positions apart: behind a k at p the next one lies d positions above the end c1 of the piece that
+        # holds p (pieces of DT_PIECE positions from the sequence's start), d cycling through values around DT_REACH - so the gap
+        # d + (c1 - p) sweeps 1000 + 1 .. 1028 + 132 as p's place inside its piece moves.  Every other sequence draws only d <=
+        # DT_REACH: none of its pieces gives up.
+        cyc = SPARSE_NEAR if rng.integers(0, 2) else SPARSE_INSIDE
+        i, p = int(rng.integers(0, len(cyc))), int(rng.integers(0, 200))
+        while p < n:
+            base[p] = k
+            p = (p // DT_PIECE + 1) * DT_PIECE + cyc[i % len(cyc)]
+            i += 1
+        return base.astype(np.uint8)
+    pos = np.arange(n)
+    base[pos % period == (period - 1 if kind == "k_last" else 0)] = k  # the last / first position of every granule
+    return base.astype(np.uint8)
+
+
+def piece_gives_up(ms, k, reach=DT_REACH, piece=DT_PIECE):
+    """the piece rule of derand_translate_piece_lds_kernel for one sequence: the ends c1 < len of its pieces, the distance from each
+    to the nearest k at or above it (the last position where there is none), and whether the piece gives up - neither a k nor the
+    last position in [c1, c1 + reach].  A sequence with one such piece is redone by one lane."""
+    n = len(ms)
+    c1 = np.arange(piece, n, piece)
+    nxt = np.where(np.asarray(ms) == k, np.arange(n), n - 1)
+    nxt = np.minimum.accumulate(nxt[::-1])[::-1]  # nearest k at or above p, else the last position
+    d = nxt[c1] - c1
+    return c1, d, d > reach
+
+
+def compare_chars(got, exp, keep, off, what):
+    bad = np.flatnonzero((got != exp) & keep)
+    if len(bad):
+        p = int(bad[0])
+        s = int(np.searchsorted(off, p, side="right") - 1)
+        raise AssertionError("%s: %d characters differ, first at sequence %d (%d bases) position %d: got %r, expected %r" % (
+            what, len(bad), s, int(off[s + 1] - off[s]), p - int(off[s]), chr(got[p]), chr(exp[p])))
+
+
+def oracle_chars(ora, ms, off, k, t, ref):
+    """oracle.translate_ms_vec(oracle.derandomize_ms_vec(ms_s, k, t), k, t) of every sequence of 3 bases or more, relative_to_ref of it,
+    and which bytes these are (the others - sequences of 0, 1 and 2 bases - are unspecified)"""
+    total = int(off[-1])
+    plain, rel, keep = np.zeros(total, dtype=np.uint8), np.zeros(total, dtype=np.uint8), np.zeros(total, dtype=bool)
+    for s in range(len(off) - 1):
+        a, b = int(off[s]), int(off[s + 1])
+        if b - a < 3:
+            continue
+        ch = ora.translate_ms_vec(ora.derandomize_ms_vec(ms[a:b], k, t), k, t).encode()
+        plain[a:b] = np.frombuffer(ch, dtype=np.uint8)
+        rel[a:b] = np.frombuffer(ora.relative_to_ref(ref[a:b].tobytes(), ch), dtype=np.uint8)
+        keep[a:b] = True
+    return plain, rel, keep
+
+
+def derand_thresholds(k):
+    """{2, 3, ceil(k / 2), k - 1, k} clipped to 2 .. k"""
+    return sorted({min(max(t, 2), k) for t in (2, 3, (k + 1) // 2, k - 1, k)})
+
+
+DT_TINY = [1, 2, 0, 2, 1]  # sequences of 0, 1 and 2 bases: 6 bytes, so that what follows them starts inside the batch's first 16 bytes
+DT_READS = [150, 37, 480, 100]
+
+
+def piece_lengths(order, seed):
+    """the batch of the piece route: every length at which a piece, a wave of 64 pieces or the look-ahead begins or ends, reads and
+    sequences of 0, 1 and 2 bases between them.  order 0: tiny sequences first (the first wave's span begins inside the batch's first
+    16 bytes, nothing staged below it, and the first real sequence starts at byte 6); 1: the longest first; 2: the longest last (its
+    pieces' look-ahead is capped by total_bases)"""
+    P = DT_PIECE
+    mid = [P - 1, P, P + 1, 2 * P, 2 * P + 1, 481, 64 * P - 1, 64 * P, 64 * P + 1, 1024 + P - 1, 1024 + P, 1024 + P + 1, 20_000]
+    rng = np.random.default_rng(seed)
+    body = []
+    for i, n in enumerate(mid[j] for j in rng.permutation(len(mid))):
+        body += [n, DT_TINY[i % 5], DT_READS[i % 4]]
+    if order == 0:
+        return DT_TINY + body + [70_000, 5]
+    if order == 1:
+        return [70_000] + body + DT_TINY
+    return [3] + body + DT_TINY + [70_000]
+
+
+LDS_MAX_LENS = [3, 31, 32, 150, 256, 479, 480]
+LDS_SEQS = 391  # 7 waves: a last wave of 7 sequences, and a last workgroup that is not full at 2, 3 and 4 waves a workgroup
+LDS_FULL_WAVE = (128, 192)  # these 64 sequences all have the maximal length: the largest span the LDS image is sized for
+
+
+def lds_lengths(mx, variant, seed):
+    """the batch of the LDS route for reads of at most mx bases: lengths from {0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, ..., mx - 1,
+    mx}, one whole wave at mx; variant 0: the first sequence 1 base, the last one mx, total_bases mod 16 = 0; variant 1: the first
+    one mx, the last one 2 bases, total_bases mod 16 = 7"""
+    rng = np.random.default_rng(seed)
+    cand = sorted({c for c in (0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, mx - 1, mx) if c <= mx})
+    lens = rng.choice(cand, LDS_SEQS)
+    lens[LDS_FULL_WAVE[0]:LDS_FULL_WAVE[1]] = mx
+    lens[0], lens[-1] = (1, mx) if variant == 0 else (mx, 2)
+    target = 0 if variant == 0 else 7
+    for i in range(LDS_SEQS - 2, LDS_FULL_WAVE[1], -1):  # a base less for one sequence after the other until the total fits
+        if (int(lens.sum()) - target) % 16 == 0:
+            break
+        if lens[i] > 0:
+            lens[i] -= 1
+    assert int(lens.sum()) % 16 == target and int(lens.max()) == mx
+    return [int(n) for n in lens]
+
+
+def lds_waves_per_workgroup(mx):
+    """launch_derand_translate's choice (derand_kernels.hip): as many waves, at most 4, as 64 KiB of LDS hold"""
+    lds = (64 * mx + 15) // 16 * 16 + 16
+    wave = ((lds + lds // 32 + 16 if mx % 32 == 0 else lds) + 15) // 16 * 16
+    return max(1, min(4, 65536 // wave))
+
+
+def derand_world(ora, lens, k, t, kind, period, seed):
+    """(offsets, MS bytes, reference bytes, the oracle's characters, those relative to the reference, which bytes are specified)"""
+    rng = np.random.default_rng(seed)
+    off = np.zeros(len(lens) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens)
+    ms = np.concatenate([derand_content(kind, rng, n, k, t, period) for n in lens] + [np.zeros(0, dtype=np.uint8)])
+    ref = ACGT[rng.integers(0, 4, int(off[-1]))]
+    plain, rel, keep = oracle_chars(ora, ms, off, k, t, ref) if ora is not None else (None, None, None)
+    for v in (off, ms, ref, plain, rel, keep):
+        if v is not None:
+            v.setflags(write=False)
+    return off, ms, ref, plain, rel, keep

@@ -13,15 +13,13 @@ import numpy as np
 import pytest
 
 import kbo_amd
-from gpu_helpers import PER_BASE_GUARD, Guarded
+from gpu_helpers import ACGT, DERAND_CONTENTS as CONTENTS, PER_BASE_GUARD, Guarded, compare_chars as _compare, derand_content as _content
 from oracle import binding as ora
 
 pytestmark = pytest.mark.gpu
 
 C_, G_ = 128, 8192  # KBO_DERAND_SEQ_CHUNK, KBO_DERAND_SEQ_GROUP (tests/test_derand_seq_cpu.py pins them to the header)
 KS = [3, 31, 96, 255]
-CONTENTS = ["uniform", "below", "all_k", "anchors", "walk", "k_last", "k_first"]
-ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 
 
 def _lengths(k):
@@ -38,36 +36,6 @@ def _thresholds(k, n, high):
     cand = sorted(set([t_mid, k - 1, k] if high else [2, 3, t_mid, k - 1, k]) - {0, 1} - set(range(k + 1, 300)))
     assert len(cand) >= 2
     return np.array([cand[s % len(cand)] for s in range(n)], dtype=np.int32)
-
-
-def _content(kind, rng, n, k, t):
-    """n MS bytes (values 0 .. k) of one sequence with threshold t"""
-    if kind == "uniform":
-        return rng.integers(0, k + 1, n, dtype=np.int64).astype(np.uint8)
-    if kind == "below":  # nothing fires but the last position: the values count down to -len
-        return rng.integers(0, t + 1, n, dtype=np.int64).astype(np.uint8)
-    if kind == "all_k":
-        return np.full(n, k, dtype=np.uint8)
-    if kind == "anchors":  # only values in (t, k): rising and falling ramps.  (t >= k - 1 has no such value: t itself, nothing fires)
-        lo, hi = t + 1, k - 1
-        if lo > hi:
-            return np.full(n, t, dtype=np.uint8)
-        span = hi - lo
-        p = np.arange(n) + int(rng.integers(0, 1000))
-        tri = np.abs((p % (2 * span + 2)) - (span + 1)).clip(0, span) if span else np.zeros(n, dtype=np.int64)
-        return (lo + tri).astype(np.uint8)
-    if kind == "walk":  # k, with ramps 0, 1, 2, ... behind mismatches every about 100 bases
-        a = np.full(n, k, dtype=np.int64)
-        p = int(rng.integers(0, 100))
-        while p < n:
-            m = min(k, n - p)
-            a[p:p + m] = np.arange(m)
-            p += int(rng.integers(k // 2 + 1, 200))
-        return a.astype(np.uint8)
-    base = rng.integers(0, k, n, dtype=np.int64)  # 0 .. k - 1
-    pos = np.arange(n)
-    base[pos % C_ == (C_ - 1 if kind == "k_last" else 0)] = k  # the last / first position of every chunk, and so of every group
-    return base.astype(np.uint8)
 
 
 _cache = {}
@@ -134,15 +102,6 @@ class _Call:
         for b in (self.ms, self.ref, self.off, self.thr):  # inputs are not written, d_ms included (the call is not in place)
             assert b is None or not b.changed(), b.name
         return self.out.host()[:self.total]
-
-
-def _compare(got, exp, keep, off, what):
-    bad = np.flatnonzero((got != exp) & keep)
-    if len(bad):
-        p = int(bad[0])
-        s = int(np.searchsorted(off, p, side="right") - 1)
-        raise AssertionError("%s: %d characters differ, first at sequence %d (%d bases) position %d: got %r, expected %r" % (
-            what, len(bad), s, int(off[s + 1] - off[s]), p - int(off[s]), chr(got[p]), chr(exp[p])))
 
 
 @pytest.mark.parametrize("kind", CONTENTS)

@@ -372,7 +372,9 @@ def test_long_derandomize_vs_oracle_adversarial(oracle, k, t):
 
 @pytest.mark.parametrize("k,t", [(3, 2), (7, 3), (31, 22), (31, 16), (51, 23), (200, 100), (5, 5)])
 def test_derand_translate_vs_oracle_fuzz(oracle, k, t):
-    """The fused kernel's closed-form translate vs the literal sequential oracle."""
+    """Single sequences of arbitrary values: the derandomized VALUES (kbo_derandomize_ms_vec: derand_one_sequence's i32 output) and the
+    stencil kernel alone (kbo_translate_ms_vec: translate_kernel) vs the literal sequential oracle.  The characters of the fused
+    kernels are not compared here (that entry discards them): tests/test_gpu_derand_arbitrary.py compares those."""
     rng = np.random.default_rng(k * 100 + t)
     for trial in range(40):
         n = int(rng.integers(3, 400))
