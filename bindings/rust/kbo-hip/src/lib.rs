@@ -151,6 +151,11 @@ pub mod ffi {
         pub fn kbo_derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
                                             d_thresholds: *const u32, min_threshold: usize, d_ref: *const u8, d_chars_out: *mut u8,
                                             d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+        // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
+        pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
+        pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
+                                       d_work: *mut c_void, work_bytes: usize, d_records: *mut u32, capacity: usize, d_first: *mut u32,
+                                       stream: *mut c_void) -> c_int;
         pub fn kbo_matches_packed_dev_scratch_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_matches_packed_dev(idx: *mut KboIndex, d_words: *const u32, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
                                       max_seq_len: usize, uniform_len: usize, d_exc_pos: *const u64, d_exc_byte: *const u8, n_exc: usize,
@@ -186,6 +191,25 @@ pub unsafe fn derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n
 }
 pub fn derand_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize {
     unsafe { ffi::kbo_derand_seq_work_bytes(n_seqs, total_bases, k, min_threshold) }
+}
+
+/// `format::run_lengths_gapped(aln_s, max_gap_len)` (format.rs:143-193) for every sequence of a device-resident batch, at any length:
+/// records of seven `u32` `{start, end, matches, mismatches, jumps, gap_bases, gap_opens}` ordered by (sequence, start), `d_first[s]` the
+/// index of sequence `s`'s first record and `d_first[n_seqs]` their number (those beyond `capacity` are counted, not written).
+/// Enqueues a constant number of launches on `stream` and returns; nothing is read back.  `d_work`: `run_lengths_seq_work_bytes`
+/// bytes, 16-byte aligned; `d_chars` carries 16 bytes of slack.
+///
+/// # Safety
+/// Every pointer is a device pointer of the size `include/kbo_hip.h` documents for `kbo_run_lengths_seq_dev`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
+                                  d_work: *mut c_void, work_bytes: usize, d_records: *mut u32, capacity: usize, d_first: *mut u32,
+                                  stream: *mut c_void) {
+    check(ffi::kbo_run_lengths_seq_dev(d_chars, d_offsets, n_seqs, total_bases, max_gap_len, d_work, work_bytes, d_records, capacity,
+                                       d_first, stream));
+}
+pub fn run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize {
+    unsafe { ffi::kbo_run_lengths_seq_work_bytes(n_seqs, total_bases) }
 }
 
 /// Stands in for `(&SbwtIndexVariant, &LcsArray)`: the index resident in HBM.  Immutable after construction.

@@ -662,10 +662,31 @@ int kbo_matches_packed_dev(kbo_index_t *idx, const uint32_t *d_words, const uint
  * word s of d_work plus word (n_seqs + 1 + s / 1024) is the index of sequence s's first run, and the
  * last word of d_work the total number of runs.  Records are seven u32 {start, end, matches,
  * mismatches, jumps, gap_bases, gap_opens}; runs beyond `capacity` are counted but not written.
- * max_seq_len = length of the longest sequence if known (reads take LDS-staged kernels), 0 = unknown. */
+ * max_seq_len = length of the longest sequence if known (reads take LDS-staged kernels), 0 = unknown.
+ * Sequences of more than 480 characters, and every sequence when max_gap_len > 0, cost one lane a sequence here, a step per
+ * character: long sequences belong to kbo_run_lengths_seq_dev, below. */
 size_t kbo_run_lengths_work_bytes(size_t n_seqs);
 int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len,
                         size_t max_gap_len, void *d_work, uint32_t *d_records, size_t capacity, void *stream);
+/* The same records in the same order - ordered by (sequence, start), start and end relative to the sequence - for a batch of
+ * sequences of any length, any byte values and any max_gap_len (2^32 - 1 and more: no gap is too long), segmented: chunks of
+ * KBO_RLE_SEG_CHUNK positions and groups of KBO_RLE_SEG_GROUP positions (kbo_hip_tuning.h), neither ever spanning two sequences,
+ * are listed on the device from d_offsets; a lane per chunk steps over its characters, staged in LDS, a lane per group over its
+ * chunks' summaries and a lane per sequence over that sequence's groups only.  The call enqueues 18 kernel launches and no memset
+ * on `stream` whatever the batch holds, reads nothing back and returns.  Sequences of length 0 are legal.
+ * d_first (n_seqs + 1 u32): d_first[s] = index of sequence s's first run, d_first[n_seqs] = the number of runs of the batch, those
+ * beyond `capacity` included - a plain exclusive prefix.  Runs beyond `capacity` are counted, not written; nothing is written at or
+ * behind d_records[7 * capacity] (d_records may be NULL when capacity == 0).
+ * d_chars: total_bases + 16 readable bytes; d_offsets 8-byte, d_records and d_first 4-byte aligned.  d_work: required, 16-byte
+ * aligned, kbo_run_lengths_seq_work_bytes() bytes - about total_bases * 77 / 128 + n_seqs * 158 bytes: per chunk of 128 positions
+ * 16 bytes of descriptor, 8 of dash carry, 48 of open run and 4 of count, per group (1/64 of the chunks) 72 more, and a chunk, a
+ * group and 8 bytes of listing more per sequence (0.6 bytes a position).  No byte of d_work beyond that figure is touched.
+ * Errors, before anything is enqueued: KBO_E_BAD_ARG (null argument, alignment, work_bytes too small), KBO_E_EMPTY_QUERY
+ * (n_seqs == 0), KBO_E_UNSUPPORTED (total_bases + 16 > 2^32, n_seqs >= 2^28). */
+size_t kbo_run_lengths_seq_work_bytes(size_t n_seqs, uint64_t total_bases);
+int kbo_run_lengths_seq_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                            size_t max_gap_len, void *d_work, size_t work_bytes, uint32_t *d_records, size_t capacity,
+                            uint32_t *d_first /* n_seqs + 1 */, void *stream);
 /* The sparse form (kbo_aln_run, above) of a device-resident packed batch of kbo::matches characters - what kbo_matches_packed_dev
  * writes: kbo_packed_words() words, every sequence starts a word, M - X R = 0 .. 3; the padding bits of a sequence's last word
  * are ignored - enqueued on `stream`; the library never synchronises.  d_offsets counts bases (n_seqs + 1 entries, 8-byte

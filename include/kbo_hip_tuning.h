@@ -217,6 +217,25 @@ int kbo_refset_last_routes(uint64_t out[4]);
 #define KBO_DERAND_SEQ_CHUNK 128
 #define KBO_DERAND_SEQ_GROUP 8192
 
+/* ------------------------------------------------------------------ kbo_run_lengths_seq_dev */
+/* positions of a chunk and of a group (64 chunks) of rle_seg_kernels.hip; neither spans two sequences.  A sequence of more than
+ * KBO_RLE_SEG_GROUP positions makes the lane that owns it loop over its groups.  The library's own callers (kbo_find_batch and its
+ * forms, kbo_run_lengths_gapped_batch, kbo_find_refset) do NOT take that stage yet: from which sequence length on it beats one lane
+ * per sequence has to be measured first (tools/bench_rle_seg.py) */
+#define KBO_RLE_SEG_CHUNK 128
+#define KBO_RLE_SEG_GROUP 8192
+/* test hook: count and emit calls of that stage since the process started (either pointer may be NULL) */
+int kbo_run_lengths_seg_calls(uint64_t *count_calls, uint64_t *emit_calls);
+/* test hook: the passes of kbo_run_lengths_seq_dev restated on the CPU over the same chunk-summary and combine functions
+ * (kbo_amd/csrc/rle_seg.hpp), with chunks of `chunk` >= 1 positions and groups of `group` positions, a multiple of it; aln, offsets,
+ * records (7 u32 each, `capacity` of them; more runs are counted, not written) and first (n_seqs + 1) are on the HOST.  A sequence
+ * shorter than min_len has no run.  No HIP call: it runs without a GPU. */
+int kbo_run_lengths_seq_host(const uint8_t *aln, const uint64_t *offsets, size_t n_seqs, size_t max_gap_len, size_t chunk, size_t group,
+                             size_t min_len, uint32_t *records, size_t capacity, uint32_t *first);
+/* ... with every sequence of the batch handed to it as a batch of ONE, in a buffer of exactly its own length; same outputs */
+int kbo_run_lengths_seq_host_each(const uint8_t *aln, const uint64_t *offsets, size_t n_seqs, size_t max_gap_len, size_t chunk, size_t group,
+                                  size_t min_len, uint32_t *records, size_t capacity, uint32_t *first);
+
 /* ------------------------------------------------------------------ kbo_derand_translate_dev and the host batches' stage behind the walk */
 /* test hook: the derandomize + translate stage of kbo_matches_batch / kbo_map_batch / kbo_find_batch / kbo_map_batch_opts over MS bytes
  * of the caller's making instead of a walk's.  ms (offsets[n_seqs] bytes, any values <= k), offsets (n_seqs + 1 values from 0, ascending)

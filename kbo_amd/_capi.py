@@ -104,7 +104,7 @@ SYMBOLS = [
     "kbo_ms_batch_dev", "kbo_derand_translate_dev", "kbo_set_slab_bytes", "kbo_set_devices", "kbo_set_host_threads",
     "kbo_release_scratch", "kbo_run_lengths_gapped_batch", "kbo_find_batch_into", "kbo_derand_work_bytes",
     "kbo_derand_seq_work_bytes", "kbo_derand_translate_seq_dev",
-    "kbo_run_lengths_work_bytes", "kbo_run_lengths_dev", "kbo_index_device_pair_bytes", "kbo_index_device_plan_bytes",
+    "kbo_run_lengths_work_bytes", "kbo_run_lengths_dev", "kbo_run_lengths_seq_work_bytes", "kbo_run_lengths_seq_dev", "kbo_index_device_pair_bytes", "kbo_index_device_plan_bytes",
     "kbo_index_path_cover", "kbo_index_recovery_lines", "kbo_call_batch", "kbo_call_batch_flat", "kbo_call_flat_free", "kbo_stream_pair_create", "kbo_stream_pair_destroy", "kbo_call_sites_dev", "kbo_call_walk_dev",
     "kbo_index_save_sbwt", "kbo_index_load_sbwt", "kbo_packed_words", "kbo_pack_reads", "kbo_unpack_matches",
     "kbo_matches_batch_packed", "kbo_find_batch_packed", "kbo_index_shards", "kbo_index_work_bytes",
@@ -128,7 +128,7 @@ TUNING_SYMBOLS = [
     "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
     "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
-    "kbo_derand_translate_host",
+    "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
 ]
 
 _lib = None
@@ -223,6 +223,11 @@ def lib():
     L.kbo_find_batch_into.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp]
     L.kbo_run_lengths_work_bytes.argtypes = [sz]; L.kbo_run_lengths_work_bytes.restype = sz
     L.kbo_run_lengths_dev.argtypes = [vp, vp, sz, sz, sz, vp, vp, sz, vp]
+    L.kbo_run_lengths_seq_work_bytes.argtypes = [sz, u64]; L.kbo_run_lengths_seq_work_bytes.restype = sz
+    L.kbo_run_lengths_seq_dev.argtypes = [vp, vp, sz, u64, sz, vp, sz, vp, sz, vp, vp]
+    L.kbo_run_lengths_seg_calls.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+    L.kbo_run_lengths_seq_host.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, vp]
+    L.kbo_run_lengths_seq_host_each.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, vp]
     L.kbo_index_device_pair_bytes.argtypes = [vp]
     L.kbo_index_device_pair_bytes.restype = C.c_uint64
     L.kbo_set_devices.argtypes = [C.POINTER(C.c_int), C.c_int]

@@ -655,6 +655,40 @@ def derand_translate_seq(ms, offsets, k, thresholds, ref=None, stream=None, min_
     return out[:total]  # (the scratch and the padded copies were allocated on `s`: the allocator reuses them in that stream's order)
 
 
+def run_lengths_seq(chars, offsets, max_gap_len=0, stream=None):
+    """kbo_run_lengths_seq_dev over torch tensors on the device: format::run_lengths_gapped of every sequence of a batch, at any length.
+    chars: uint8; offsets: int64 or uint64 (n_seqs + 1).  Returns (records, first): records an (n, 7) int32 tensor that holds the u32
+    values {start, end, matches, mismatches, jumps, gap_bases, gap_opens} of the batch's n runs, ordered by (sequence, start), and first
+    an int32 tensor of n_seqs + 1 elements, first[s] the index of sequence s's first run and first[n_seqs] = n.  The number of runs is
+    known on the device only: the call waits for `stream` (default: the current one) once to size the records, and runs the stage
+    again when the room it guessed - a run per 64 characters - was too little."""
+    import torch
+    device = chars.device
+    n_seqs = int(offsets.numel()) - 1
+    assert chars.dtype == torch.uint8 and offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(s):
+        ch = chars.contiguous()
+        if int(ch.numel()) < total + 16:  # the 16 bytes of slack behind a per-base buffer
+            p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+            p[:total].copy_(ch[:total])
+            ch = p
+        off = offsets.contiguous()
+        wb = int(lib().kbo_run_lengths_seq_work_bytes(n_seqs, total))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=device)
+        first = torch.zeros(n_seqs + 1, dtype=torch.int32, device=device)
+        capacity = max(1024, 2 * n_seqs + total // 64)
+        while True:
+            records = torch.empty((capacity, 7), dtype=torch.int32, device=device)
+            check(lib().kbo_run_lengths_seq_dev(ch.data_ptr(), off.data_ptr(), n_seqs, total, max_gap_len, work.data_ptr(), wb,
+                                                records.data_ptr(), capacity, first.data_ptr(), s.cuda_stream))
+            n = int(first[-1].item()) & 0xFFFFFFFF
+            if n <= capacity:
+                return records[:n], first
+            capacity = n
+
+
 def stream_pair(device, tail_cus=-1):
     """(stream, tail_stream) as torch streams, made by the library (kbo_hip.h kbo_stream_pair_create): the tail stream - a batch's second
     pass - on compute units of its own.  The pair lives as long as the process (the torch wrappers do not own the streams)."""

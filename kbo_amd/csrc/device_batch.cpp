@@ -1081,6 +1081,39 @@ int kbo_run_lengths_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_
     });
 }
 
+static_assert(kbo::kRleSegChunk == KBO_RLE_SEG_CHUNK && kbo::kRleSegChunk * kbo::kRleSegGroupChunks == KBO_RLE_SEG_GROUP,
+              "kbo_hip_tuning.h states the kernels' constants");
+
+size_t kbo_run_lengths_seq_work_bytes(size_t n_seqs, uint64_t total_bases)
+{
+    return kbo::rle_seg_work_bytes((uint32_t)std::min<size_t>(n_seqs, 0xFFFFFFFEu), total_bases);
+}
+
+int kbo_run_lengths_seq_dev(const uint8_t *d_chars, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, size_t max_gap_len,
+                            void *d_work, size_t work_bytes, uint32_t *d_records, size_t capacity, uint32_t *d_first, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(d_chars && d_offsets && d_work && d_first && (d_records || capacity == 0), KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+        KBO_REQUIRE(total_bases <= (1ull << 32) - 16 && n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "a batch of 2^32 - 16 bases or 2^28 sequences, or more");
+        KBO_REQUIRE(((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_records & 3) == 0 && ((uintptr_t)d_first & 3) == 0 &&
+                        ((uintptr_t)d_work & 15) == 0,
+                    KBO_E_BAD_ARG, "d_offsets 8-byte, d_records and d_first 4-byte, d_work 16-byte aligned");
+        KBO_REQUIRE(work_bytes >= kbo_run_lengths_seq_work_bytes(n_seqs, total_bases), KBO_E_BAD_ARG, "work_bytes too small");
+        const uint32_t gap = (uint32_t)std::min<size_t>(max_gap_len, 0xFFFFFFFFu);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        HIP_OK(kbo::launch_rle_seg_count(d_chars, d_offsets, (uint32_t)n_seqs, total_bases, gap, 0u, d_work, d_first, s));
+        HIP_OK(kbo::launch_rle_seg_emit(d_chars, (uint32_t)n_seqs, total_bases, gap, d_work, d_records,
+                                        (uint32_t)std::min<size_t>(capacity, 0xFFFFFFFFu), s));
+    });
+}
+
+int kbo_run_lengths_seg_calls(uint64_t *count_calls, uint64_t *emit_calls)
+{
+    kbo::rle_seg_calls(count_calls, emit_calls);
+    return KBO_OK;
+}
+
 // ---- the sparse form of kbo::matches over device-resident character words (sparse_kernels.hip)
 namespace {
 size_t sparse_prefix_bytes(size_t n_seqs) { return (kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t) + 15) / 16 * 16; }

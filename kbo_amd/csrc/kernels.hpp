@@ -298,6 +298,19 @@ hipError_t launch_rle_emit(const uint8_t *d_chars, const uint64_t *d_offsets, ui
                            uint32_t *d_scratch, uint32_t *d_rles, uint32_t capacity, hipStream_t stream,
                            uint32_t max_seq_len = 0 /* longest sequence if known: reads take the LDS-staged kernels */,
                            bool own_alphabet = false);
+// The same stage segmented, for sequences of any length (rle_seg_kernels.hip): chunks and groups listed on the device, two carries
+// along the chunks of a sequence, no lane over more than a chunk of characters.  The same records in the same order.  Count: 17
+// launches, d_first[s] = index of sequence s's first run, d_first[n_seqs] = all runs (a plain prefix).  Emit: one launch over what
+// the count left in d_work.  A sequence shorter than min_len has no run.  d_work >= rle_seg_work_bytes(), 16-byte aligned;
+// n_seqs < 2^28, total_bases <= 2^32 - 16.
+constexpr uint32_t kRleSegChunk = 128;      // positions per chunk (== KBO_RLE_SEG_CHUNK)
+constexpr uint32_t kRleSegGroupChunks = 64; // chunks per group: KBO_RLE_SEG_GROUP = 8192 positions
+size_t rle_seg_work_bytes(uint32_t n_seqs, uint64_t total_bases);
+hipError_t launch_rle_seg_count(const uint8_t *d_chars, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t max_gap_len,
+                                uint32_t min_len, void *d_work, uint32_t *d_first, hipStream_t stream);
+hipError_t launch_rle_seg_emit(const uint8_t *d_chars, uint32_t n_seqs, uint64_t total_bases, uint32_t max_gap_len, void *d_work, uint32_t *d_rles,
+                               uint32_t capacity, hipStream_t stream);
+void rle_seg_calls(uint64_t *count_calls, uint64_t *emit_calls); // launches of each since the process started
 // A1: k-bounded matching statistics over all items
 hipError_t launch_ms_walk(WalkArgs a, int max_waves, hipStream_t stream);
 // A5+A6 (+ optional relative_to_ref when ref != nullptr, + optional i32 derandomised
