@@ -15,6 +15,7 @@ pub mod ffi {
     use super::*;
     #[repr(C)] pub struct KboIndex { _private: [u8; 0] }
     #[repr(C)] pub struct KboMapStream { _private: [u8; 0] }
+    #[repr(C)] pub struct KboRefset { _private: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Debug, PartialEq)]
     pub struct KboRle { pub start: u64, pub end: u64, pub matches: u64, pub mismatches: u64,
                         pub jumps: u64, pub gap_bases: u64, pub gap_opens: u64 }
@@ -151,6 +152,14 @@ pub mod ffi {
         pub fn kbo_derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
                                             d_thresholds: *const u32, min_threshold: usize, d_ref: *const u8, d_chars_out: *mut u8,
                                             d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+        // ... and its summary form: one AlnExtent per sequence instead of a character per base
+        pub fn kbo_derand_summary_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize;
+        pub fn kbo_derand_summary_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
+                                          d_thresholds: *const u32, min_threshold: usize, d_out: *mut super::AlnExtent,
+                                          d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+        // the summary of every (reference, sequence, strand) pair of a reference set with a hit (the set: kbo_refset_build, kbo_hip.h)
+        pub fn kbo_summary_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
+                                  records: *mut *mut super::RefSummary, n_records: *mut u64) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -191,6 +200,62 @@ pub unsafe fn derand_translate_seq_dev(d_ms: *const u8, d_offsets: *const u64, n
 }
 pub fn derand_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize {
     unsafe { ffi::kbo_derand_seq_work_bytes(n_seqs, total_bases, k, min_threshold) }
+}
+
+/// `kbo_aln_extent`: the counts of `AlnSummary` with the extent of the alignment - `start` the position of the first character other
+/// than '-', `end` one past the last, both 0 when there is none.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct AlnExtent {
+    pub n_match: u32,
+    pub n_mismatch: u32,
+    pub n_jump: u32,
+    pub n_runs: u32,
+    pub start: u32,
+    pub end: u32,
+}
+
+/// `kbo_ref_summary` (36 bytes): what `kbo_summary_refset` returns per (reference, sequence, strand) pair with a hit.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefSummary {
+    pub ref_: u32,
+    pub seq: u32,
+    pub strand: u32,
+    pub aln: AlnExtent,
+}
+
+/// The summary form of `derand_translate_seq_dev`: the same inputs and contract, one `AlnExtent` per sequence at `d_out` (every one
+/// written; sequences of fewer than 3 bases get zeros) and no character buffer.  `d_work`: `derand_summary_seq_work_bytes` bytes.
+///
+/// # Safety
+/// Every pointer is a device pointer of the size `include/kbo_hip.h` documents for `kbo_derand_summary_seq_dev`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn derand_summary_seq_dev(d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, k: usize,
+                                     d_thresholds: *const u32, min_threshold: usize, d_out: *mut AlnExtent, d_work: *mut c_void,
+                                     work_bytes: usize, stream: *mut c_void) {
+    check(ffi::kbo_derand_summary_seq_dev(d_ms, d_offsets, n_seqs, total_bases, k, d_thresholds, min_threshold, d_out, d_work, work_bytes,
+                                          stream));
+}
+pub fn derand_summary_seq_work_bytes(n_seqs: usize, total_bases: u64, k: usize, min_threshold: usize) -> usize {
+    unsafe { ffi::kbo_derand_summary_seq_work_bytes(n_seqs, total_bases, k, min_threshold) }
+}
+
+/// `kbo_summary_refset` over a set handle a caller built with `kbo_refset_build`: the records of the pairs with a hit, ordered by
+/// (ref, seq, strand).
+///
+/// # Safety
+/// `set` is a live `kbo_refset_t`.
+pub unsafe fn summary_refset(set: *mut ffi::KboRefset, seqs: &[Vec<u8>], max_error_prob: f64, strands: c_int) -> Vec<RefSummary> {
+    let mut offsets = vec![0u64; seqs.len() + 1];
+    for (i, r) in seqs.iter().enumerate() { offsets[i + 1] = offsets[i] + r.len() as u64; }
+    let concat: Vec<u8> = seqs.concat();
+    let (mut p, mut n) = (std::ptr::null_mut::<RefSummary>(), 0u64);
+    check(ffi::kbo_summary_refset(set, concat.as_ptr(), offsets.as_ptr(), seqs.len(), max_error_prob, strands, &mut p, &mut n));
+    if n == 0 { return Vec::new(); }
+    let out = std::slice::from_raw_parts(p, n as usize).to_vec();
+    ffi::kbo_free(p as *mut c_void);
+    out
 }
 
 /// `format::run_lengths_gapped(aln_s, max_gap_len)` (format.rs:143-193) for every sequence of a device-resident batch, at any length:

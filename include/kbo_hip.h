@@ -397,6 +397,13 @@ int kbo_sparse_expand(const kbo_aln_run *runs, uint64_t n_runs, const uint64_t *
 typedef struct {
     uint32_t n_match, n_mismatch, n_jump, n_runs;
 } kbo_aln_summary; /* 16 bytes */
+/* The same counts with the extent of the alignment, of the characters c = translate_ms_vec(derandomize_ms_vec(ms, k, t), k, t) of one
+ * sequence: start is the 0-based position of the first character other than '-', end one past the last such character, both 0 when
+ * there is none.  A sequence of fewer than 3 bases gets an all-zero record.  What kbo_derand_summary_seq_dev writes and
+ * kbo_summary_refset returns per pair. */
+typedef struct {
+    uint32_t n_match, n_mismatch, n_jump, n_runs, start, end;
+} kbo_aln_extent; /* 24 bytes */
 /* kbo_matches_batch / kbo_matches_batch_packed with the records as output: summary_out holds n_seqs records (the caller's; the library
  * allocates nothing).  Inputs, checks and error codes are those of kbo_matches_batch / kbo_matches_batch_packed; the same slab
  * pipeline, over the devices of kbo_set_devices and over sharded indexes alike; a slab downloads 16 bytes per sequence.  A slab of reads
@@ -498,6 +505,25 @@ typedef struct {
 } kbo_ref_run; /* 40 bytes */
 int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_find_opts *opts,
                     int strands, kbo_ref_run **runs, uint64_t *n_runs);
+/* The summary of the same pairs: which references are present, on which strand, with what identity and coverage - one record per
+ * (reference, sequence, strand) pair whose alignment holds at least one character other than '-', a pair without a hit has none.
+ * aln (kbo_aln_extent, above) describes kbo::matches of sequence s - strand KBO_STRAND_REV: of its reverse complement, in the
+ * coordinates of the reverse-complemented sequence - against reference r's own index, with the threshold of that index's n_kmers and
+ * max_error_prob: the pairs, thresholds and coordinates of kbo_find_refset, and aln.n_runs is the number of records
+ * kbo_find_refset(max_gap_len = 0) has for the pair.  Records are ordered by (ref, seq, strand with '+' first).  *records is
+ * library-allocated (kbo_free); *n_records == 0 leaves it NULL.  The slabs, the upload, the '-' strand and the walk are
+ * kbo_find_refset's; behind the walk a slab runs kbo_derand_summary_seq_dev's stage with the pairs' thresholds and keeps the records
+ * with n_runs > 0 on the device, in pair order: one count and the kept records leave the device per slab - no character buffer, no
+ * run-length stage.  A reference of more than KBO_REFSET_MAX_ROWS rows goes through the single-index pipeline, whose characters are
+ * counted on the host.  Errors, all checked before the first HIP call: those of kbo_find_refset, max_error_prob as
+ * opts->max_error_prob there.  References with a status set contribute nothing.  kbo_refset_last_routes reports this call's routes
+ * as it does kbo_find_refset's. */
+typedef struct {
+    uint32_t ref, seq, strand; /* strand: KBO_STRAND_FWD or KBO_STRAND_REV */
+    kbo_aln_extent aln;
+} kbo_ref_summary; /* 36 bytes */
+int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                       int strands, kbo_ref_summary **records, uint64_t *n_records);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`
@@ -575,6 +601,19 @@ size_t kbo_derand_seq_work_bytes(size_t n_seqs, uint64_t total_bases, size_t k, 
 int kbo_derand_translate_seq_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                                  size_t k, const uint32_t *d_thresholds, size_t min_threshold, const uint8_t *d_ref,
                                  uint8_t *d_chars_out, void *d_work, size_t work_bytes, void *stream);
+/* The summary form of that stage: the same inputs, the same contract - any MS bytes <= k, a threshold per sequence, any length,
+ * exact - and one kbo_aln_extent record per sequence instead of a character per base.  The passes up to the value entering every
+ * chunk are the character form's, called as they are; the last one counts the characters of a chunk where the character form packs
+ * them, in LDS, and the lanes of a wave that sit on one sequence are summed before its record is added to - so no character buffer
+ * exists.  The call enqueues 13 kernel launches and no memset on `stream`, whatever n_seqs, the lengths and the thresholds are,
+ * reads nothing back and returns.  d_out: n_seqs records (24 n_seqs bytes), 4-byte aligned, every one written: a sequence of fewer
+ * than 3 bases gets zeros.  d_ms: total_bases + 16 bytes, 4-byte aligned, not written.  d_work: required, 16-byte aligned,
+ * kbo_derand_summary_seq_work_bytes() bytes (the figure of kbo_derand_seq_work_bytes()); no byte beyond it is touched.
+ * Errors and limits are kbo_derand_translate_seq_dev's, checked before anything is enqueued. */
+size_t kbo_derand_summary_seq_work_bytes(size_t n_seqs, uint64_t total_bases, size_t k, size_t min_threshold);
+int kbo_derand_summary_seq_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, size_t k,
+                               const uint32_t *d_thresholds, size_t min_threshold, kbo_aln_extent *d_out, void *d_work,
+                               size_t work_bytes, void *stream);
 /* kbo::map with fill_gaps = false and call_variants = false (lib.rs:726-738; format != 0: + relative_to_ref, lib.rs:756-757) or
  * kbo::matches (lib.rs:612-628; format = 0) over a device-resident batch, the whole chain MS -> derandomize_ms_vec ->
  * translate_ms_vec enqueued on `stream`; the threshold comes from the index and max_error_prob (lib.rs:620, 731).  Batches of

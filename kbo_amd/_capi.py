@@ -103,7 +103,7 @@ SYMBOLS = [
     "kbo_ms_batch", "kbo_matches_batch", "kbo_map_batch", "kbo_find_batch", "kbo_work_bytes", "kbo_ms_work_bytes",
     "kbo_ms_batch_dev", "kbo_derand_translate_dev", "kbo_set_slab_bytes", "kbo_set_devices", "kbo_set_host_threads",
     "kbo_release_scratch", "kbo_run_lengths_gapped_batch", "kbo_find_batch_into", "kbo_derand_work_bytes",
-    "kbo_derand_seq_work_bytes", "kbo_derand_translate_seq_dev",
+    "kbo_derand_seq_work_bytes", "kbo_derand_translate_seq_dev", "kbo_derand_summary_seq_work_bytes", "kbo_derand_summary_seq_dev",
     "kbo_run_lengths_work_bytes", "kbo_run_lengths_dev", "kbo_run_lengths_seq_work_bytes", "kbo_run_lengths_seq_dev", "kbo_index_device_pair_bytes", "kbo_index_device_plan_bytes",
     "kbo_index_path_cover", "kbo_index_recovery_lines", "kbo_call_batch", "kbo_call_batch_flat", "kbo_call_flat_free", "kbo_stream_pair_create", "kbo_stream_pair_destroy", "kbo_call_sites_dev", "kbo_call_walk_dev",
     "kbo_index_save_sbwt", "kbo_index_load_sbwt", "kbo_packed_words", "kbo_pack_reads", "kbo_unpack_matches",
@@ -118,7 +118,7 @@ SYMBOLS = [
     "kbo_summary_batch", "kbo_summary_batch_packed", "kbo_summary_work_bytes", "kbo_summary_batch_dev", "kbo_summary_dev",
     "kbo_summary_words_work_bytes", "kbo_summary_words_dev", "kbo_map_stream_submit_summary",
     "kbo_refset_build", "kbo_refset_free", "kbo_refset_size", "kbo_refset_k", "kbo_refset_n_kmers", "kbo_refset_status",
-    "kbo_refset_to_device", "kbo_find_refset",
+    "kbo_refset_to_device", "kbo_find_refset", "kbo_summary_refset",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -208,6 +208,8 @@ def lib():
     L.kbo_derand_work_bytes.argtypes = [sz, u64]; L.kbo_derand_work_bytes.restype = sz
     L.kbo_derand_seq_work_bytes.argtypes = [sz, u64, sz, sz]; L.kbo_derand_seq_work_bytes.restype = sz
     L.kbo_derand_translate_seq_dev.argtypes = [vp, vp, sz, u64, sz, vp, sz, vp, vp, vp, sz, vp]
+    L.kbo_derand_summary_seq_work_bytes.argtypes = [sz, u64, sz, sz]; L.kbo_derand_summary_seq_work_bytes.restype = sz
+    L.kbo_derand_summary_seq_dev.argtypes = [vp, vp, sz, u64, sz, vp, sz, vp, vp, sz, vp]
     L.kbo_walk_geometry.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.kbo_set_walk_waves_per_cu.argtypes = [C.c_int]
     L.kbo_set_walk_threads.argtypes = [C.c_int]
@@ -322,6 +324,7 @@ def lib():
     L.kbo_refset_status.argtypes = [vp, sz]
     L.kbo_refset_to_device.argtypes = [vp, C.c_int]
     L.kbo_find_refset.argtypes = [vp, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(vp), C.POINTER(u64)]
+    L.kbo_summary_refset.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(u64)]
     L.kbo_set_refset_record_capacity.argtypes = [sz]
     L.kbo_refset_last_routes.argtypes = [vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]

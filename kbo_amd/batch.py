@@ -655,6 +655,35 @@ def derand_translate_seq(ms, offsets, k, thresholds, ref=None, stream=None, min_
     return out[:total]  # (the scratch and the padded copies were allocated on `s`: the allocator reuses them in that stream's order)
 
 
+def derand_summary_seq(ms, offsets, k, thresholds, stream=None, min_threshold=None):
+    """kbo_derand_summary_seq_dev over torch tensors on the device: the counts, runs and extent (kbo_hip.h kbo_aln_extent) of
+    translate_ms_vec(derandomize_ms_vec(ms_s, k, thresholds[s]), k, thresholds[s]) for every sequence s, at any length - no characters
+    are written anywhere.  Arguments as for derand_translate_seq.  Returns an (n_seqs, 6) int32 tensor that holds the u32 values
+    {n_match, n_mismatch, n_jump, n_runs, start, end}; sequences of fewer than 3 bases have zeros.  Enqueued on `stream` (default:
+    the current one), not synchronised."""
+    import torch
+    device = ms.device
+    n_seqs = int(offsets.numel()) - 1
+    assert ms.dtype == torch.uint8 and thresholds.dtype == torch.int32 and int(thresholds.numel()) == n_seqs
+    assert offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    if min_threshold is None:
+        min_threshold = int(thresholds.min().item()) if n_seqs > 0 else 2
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(s):
+        ms_p = ms.contiguous()
+        if int(ms_p.numel()) < total + 16:  # the 16 bytes of slack behind a per-base buffer
+            ms_p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+            ms_p[:total].copy_(ms[:total])
+        off, thr = offsets.contiguous(), thresholds.contiguous()
+        out = torch.empty((n_seqs, 6), dtype=torch.int32, device=device)
+        wb = int(lib().kbo_derand_summary_seq_work_bytes(n_seqs, total, k, min_threshold))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=device)
+        check(lib().kbo_derand_summary_seq_dev(ms_p.data_ptr(), off.data_ptr(), n_seqs, total, k, thr.data_ptr(), min_threshold,
+                                               out.data_ptr(), work.data_ptr(), wb, s.cuda_stream))
+    return out
+
+
 def run_lengths_seq(chars, offsets, max_gap_len=0, stream=None):
     """kbo_run_lengths_seq_dev over torch tensors on the device: format::run_lengths_gapped of every sequence of a batch, at any length.
     chars: uint8; offsets: int64 or uint64 (n_seqs + 1).  Returns (records, first): records an (n, 7) int32 tensor that holds the u32

@@ -11,6 +11,12 @@
 //   ds_chunk_inputs_kernel  lane = group: the exact value entering each of its chunks
 //   ds_emit_kernel          lane = chunk, staged in LDS: characters, moved out in 16-byte blocks
 // Eleven launches whatever the batch holds, nothing read back.  Integer / byte work only.  Wavefront = 64 lanes.
+// The summary form (kbo_hip.h kbo_aln_extent: counts, runs and extent per sequence instead of characters) shares every pass up to
+// ds_chunk_inputs_kernel and ends differently - thirteen launches:
+//   ds_extent_init_kernel   lane = sequence: its record as the atomics expect it
+//   ds_count_chars_kernel   lane = chunk, staged in LDS: the characters are counted where ds_emit_kernel packs them and never leave
+//                           the lane; the lanes of a wave that sit on one sequence are summed, then added to its record
+//   ds_extent_finish_kernel lane = sequence: start of a sequence without a hit
 #include "device_util.hpp"
 
 #include <algorithm>
@@ -274,6 +280,124 @@ __global__ __launch_bounds__(64) void ds_emit_kernel(const uint8_t *__restrict__
     }
 }
 
+// the summary form's record: kbo_aln_extent as six words; while the chunks arrive `start` is a minimum over 0xFFFFFFFF
+constexpr uint32_t kExtentWords = 6;
+constexpr uint32_t kNoStart = 0xFFFFFFFFu;
+
+__global__ void ds_extent_init_kernel(uint32_t n_seqs, uint32_t *__restrict__ out)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seqs) return;
+    uint32_t *o = out + (size_t)s * kExtentWords;
+    o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = kNoStart; o[5] = 0;
+}
+
+__global__ void ds_extent_finish_kernel(uint32_t n_seqs, uint32_t *__restrict__ out)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seqs) return;
+    uint32_t *o = out + (size_t)s * kExtentWords;
+    if (o[4] == kNoStart) o[4] = 0; // no character other than '-': start = end = 0
+}
+
+// lane = chunk: ds_emit_kernel's pass with the characters counted instead of packed.  A run is counted where it STARTS - a
+// character other than '-' at the head of the sequence or behind a '-' - so one that crosses a chunk, a wave's 64 chunks or a group
+// is counted once: the character in front of the chunk is another lane's, and the lane makes that one character itself from
+// x[p0 - 2 .. p0] (one more step of the recurrence with the MS byte at p0 - 2).  The chunks of a sequence are consecutive slots, so
+// the lanes of a wave that share an owner are neighbours: a segmented sum over the wave, then the segment's first lane adds to the
+// record (integers: any order gives the same record).  Nothing is written to LDS behind the staging and no character exists in memory.
+__global__ __launch_bounds__(64) void ds_count_chars_kernel(const uint8_t *__restrict__ ms, const uint4 *__restrict__ cdesc,
+                                                            const int32_t *__restrict__ c_in, uint32_t n_cslots, uint32_t k,
+                                                            const uint32_t *__restrict__ cc, const uint32_t *__restrict__ csums,
+                                                            uint32_t n_seqs, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t rows[kRows * kRowWords];
+    __shared__ uint32_t sh_start[kRows], sh_len[kRows];
+    const uint32_t lane = threadIdx.x, c = blockIdx.x * kRows + lane;
+    uint4 d = make_uint4(0, 0, 0, 0);
+    if (c < n_cslots) d = cdesc[c];
+    const uint32_t cl = d.z ? chunk_len(d) : 0u;
+    sh_start[lane] = d.x;
+    sh_len[lane] = cl;
+    __syncthreads();
+    ds_stage(ms, sh_start, sh_len, rows);
+    __syncthreads();
+    // per chunk at most 128 of anything: 'M's, 'X's, 'R's and run starts in the four bytes of one word
+    uint32_t cnt = 0, first = kNoStart, last = 0; // first / last: positions in the sequence; last is one past
+    if (cl) {
+        const int K = (int)k, T = (int)d.w;
+        const uint32_t len = d.z, p0 = d.y, p1 = p0 + cl;
+        const uint32_t *row = rows + lane * kRowWords;
+        const uint32_t a_under = p0 > 0 ? (uint32_t)ms[d.x - 1u] : 0u; // the MS bytes below the chunk: the same sequence's
+        const uint32_t a_under2 = p0 > 0 ? (uint32_t)ms[d.x - 2u] : 0u; // (p0 > 0: p0 >= kC)
+        const int a_top = (int)((row[(cl - 1u) >> 2] >> (8u * ((cl - 1u) & 3u))) & 0xFFu);
+        int x_next = c_in[c], x_cur;
+        if (p1 == len) { // derandomize.rs:282
+            x_cur = a_top > T ? a_top : 0;
+            x_next = x_cur;
+        } else x_cur = ds_step(a_top, x_next, K, T);
+        uint32_t v = row[(cl - 1u) >> 2];
+        bool above = false; // the character one position up is not a '-'
+        for (uint32_t w = (cl + 3u) >> 2; w-- > 0;) {
+            const uint32_t below = w > 0 ? row[w - 1u] : a_under << 24;
+#pragma unroll
+            for (int j = 3; j >= 0; j--) {
+                const uint32_t q = 4u * w + (uint32_t)j;
+                if (q < cl) {
+                    const int a = (int)((j > 0 ? v >> (8 * (j - 1)) : below >> 24) & 0xFFu); // noisy[p - 1]
+                    const int x_prev = p0 + q > 0 ? ds_step(a, x_cur, K, T) : K;
+                    const uint32_t ch = translate_char(x_prev, x_cur, x_next, p0 + q, len, K, T);
+                    const bool hit = ch != (uint32_t)'-';
+                    cnt += (ch == (uint32_t)'M' ? 1u : 0u) + (ch == (uint32_t)'X' ? 1u << 8 : 0u) + (ch == (uint32_t)'R' ? 1u << 16 : 0u) +
+                           (above && !hit ? 1u << 24 : 0u); // a run starts one position up
+                    if (hit) {
+                        first = p0 + q;
+                        if (!last) last = p0 + q + 1u;
+                    }
+                    above = hit;
+                    x_next = x_cur;
+                    x_cur = x_prev;
+                }
+            }
+            v = below;
+        }
+        // the chunk's first position: x_cur = x[p0 - 1], x_next = x[p0]
+        bool front = false; // the character in front of the chunk is not a '-'
+        if (p0 > 0) {
+            const int x_pp = ds_step((int)a_under2, x_cur, K, T); // x[p0 - 2]
+            front = translate_char(x_pp, x_cur, x_next, p0 - 1u, len, K, T) != (uint32_t)'-';
+        }
+        if (above && !front) cnt += 1u << 24;
+    }
+    // the owner: a search per first chunk of a sequence (and per wave), handed on to the lanes behind it
+    const bool head = cl && (lane == 0u || d.y == 0u);
+    uint32_t own = head ? ds_owner(cc, csums, n_seqs, c) : 0u;
+    const uint64_t heads = __ballot(head);
+    own = __shfl(own, cl ? 63 - __clzll(heads & (~0ull >> (63u - lane))) : (int)lane);
+    if (!cl) own = kNoStart; // (empty slots: behind every chunk of the batch)
+    uint32_t pa = (cnt & 0xFFu) | ((cnt >> 8 & 0xFFu) << 16), pb = (cnt >> 16 & 0xFFu) | ((cnt >> 24) << 16); // a wave: at most 8 192 of each
+#pragma unroll
+    for (uint32_t step = 1; step < 64u; step <<= 1) {
+        const uint32_t o2 = __shfl_down(own, step), a2 = __shfl_down(pa, step), b2 = __shfl_down(pb, step);
+        const uint32_t f2 = __shfl_down(first, step), l2 = __shfl_down(last, step);
+        if (lane + step < 64u && o2 == own) {
+            pa += a2;
+            pb += b2;
+            first = min(first, f2);
+            last = max(last, l2);
+        }
+    }
+    if (head && last) { // (a hit: at least one character other than '-', so first and last are set)
+        uint32_t *o = out + (size_t)own * kExtentWords;
+        if (pa & 0xFFFFu) atomicAdd(o + 0, pa & 0xFFFFu);
+        if (pa >> 16) atomicAdd(o + 1, pa >> 16);
+        if (pb & 0xFFFFu) atomicAdd(o + 2, pb & 0xFFFFu);
+        if (pb >> 16) atomicAdd(o + 3, pb >> 16);
+        atomicMin(o + 4, first);
+        atomicMax(o + 5, last);
+    }
+}
+
 struct SeqLayout {
     uint32_t n_cslots, n_gslots, stride;
     size_t cc, gc, cdesc, gdesc, t1, t2, g_in, c_in, end;
@@ -307,11 +431,20 @@ size_t derand_seq_work_bytes(uint32_t n_seqs, uint64_t total_bases, uint32_t k, 
     return seq_layout(n_seqs, total_bases, k, min_threshold).end;
 }
 
-hipError_t launch_derand_translate_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
-                                       const uint32_t *d_thresholds, uint32_t min_threshold, const uint8_t *d_ref, uint8_t *d_chars_out,
-                                       void *d_work, hipStream_t stream)
+namespace {
+
+struct SeqWork {
+    SeqLayout L;
+    uint32_t *cc, *csums;
+    uint4 *cdesc;
+    int32_t *c_in;
+    dim3 chunk_groups;
+};
+
+// the ten launches both forms share: everything up to the exact value entering every chunk
+hipError_t enqueue_chunk_inputs(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
+                                const uint32_t *d_thresholds, uint32_t min_threshold, void *d_work, hipStream_t stream, SeqWork &W)
 {
-    if (n_seqs == 0) return hipSuccess;
     const SeqLayout L = seq_layout(n_seqs, total_bases, k, min_threshold);
     if ((uint64_t)L.n_cslots + L.n_gslots > 0xFFFFFFFFull) return hipErrorInvalidValue; // (n_seqs < 2^31: the callers check)
     uint8_t *w = static_cast<uint8_t *>(d_work);
@@ -335,7 +468,36 @@ hipError_t launch_derand_translate_seq(const uint8_t *d_ms, const uint64_t *d_of
     hipLaunchKernelGGL(ds_group_tables_kernel, blocks((uint64_t)L.n_gslots * L.stride), dim3(T), 0, stream, t1, gdesc, L.n_gslots, k, L.stride, t2);
     hipLaunchKernelGGL(ds_top_kernel, blocks(n_seqs), dim3(T), 0, stream, t2, gdesc, gc, gsums, n_seqs, L.stride, g_in);
     hipLaunchKernelGGL(ds_chunk_inputs_kernel, blocks(L.n_gslots), dim3(T), 0, stream, t1, g_in, gdesc, L.n_gslots, L.stride, c_in);
-    hipLaunchKernelGGL(ds_emit_kernel, chunk_groups, dim3(kRows), 0, stream, d_ms, cdesc, c_in, L.n_cslots, k, d_ref, d_chars_out);
+    W = SeqWork{L, cc, csums, cdesc, c_in, chunk_groups};
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_derand_translate_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
+                                       const uint32_t *d_thresholds, uint32_t min_threshold, const uint8_t *d_ref, uint8_t *d_chars_out,
+                                       void *d_work, hipStream_t stream)
+{
+    if (n_seqs == 0) return hipSuccess;
+    SeqWork W;
+    const hipError_t e = enqueue_chunk_inputs(d_ms, d_offsets, n_seqs, total_bases, k, d_thresholds, min_threshold, d_work, stream, W);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ds_emit_kernel, W.chunk_groups, dim3(kRows), 0, stream, d_ms, W.cdesc, W.c_in, W.L.n_cslots, k, d_ref, d_chars_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_derand_summary_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
+                                     const uint32_t *d_thresholds, uint32_t min_threshold, uint32_t *d_out, void *d_work, hipStream_t stream)
+{
+    if (n_seqs == 0) return hipSuccess;
+    SeqWork W;
+    const hipError_t e = enqueue_chunk_inputs(d_ms, d_offsets, n_seqs, total_bases, k, d_thresholds, min_threshold, d_work, stream, W);
+    if (e != hipSuccess) return e;
+    const dim3 per_seq((n_seqs + 255u) / 256u);
+    hipLaunchKernelGGL(ds_extent_init_kernel, per_seq, dim3(256), 0, stream, n_seqs, d_out);
+    hipLaunchKernelGGL(ds_count_chars_kernel, W.chunk_groups, dim3(kRows), 0, stream, d_ms, W.cdesc, W.c_in, W.L.n_cslots, k, W.cc, W.csums, n_seqs,
+                       d_out);
+    hipLaunchKernelGGL(ds_extent_finish_kernel, per_seq, dim3(256), 0, stream, n_seqs, d_out);
     return hipGetLastError();
 }
 

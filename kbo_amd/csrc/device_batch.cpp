@@ -377,6 +377,31 @@ int kbo_derand_translate_seq_dev(const uint8_t *d_ms, const uint64_t *d_offsets,
     });
 }
 
+size_t kbo_derand_summary_seq_work_bytes(size_t n_seqs, uint64_t total_bases, size_t k, size_t min_threshold)
+{
+    return kbo_derand_seq_work_bytes(n_seqs, total_bases, k, min_threshold); // (the owner of a chunk is found in the scanned counts)
+}
+
+int kbo_derand_summary_seq_dev(const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, size_t k,
+                               const uint32_t *d_thresholds, size_t min_threshold, kbo_aln_extent *d_out, void *d_work, size_t work_bytes,
+                               void *stream)
+{
+    return guarded([&] {
+        static_assert(sizeof(kbo_aln_extent) == 24, "kbo_aln_extent is 24 bytes");
+        KBO_REQUIRE(d_ms && d_offsets && d_thresholds && d_out && d_work, KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+        KBO_REQUIRE(k > 0 && k <= 255, KBO_E_BAD_ARG, "k in 1..255");
+        KBO_REQUIRE(min_threshold <= k, KBO_E_BAD_ARG, "min_threshold <= k");
+        KBO_REQUIRE(min_threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
+        KBO_REQUIRE(total_bases + 16 <= (1ull << 32) && n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "a batch of 2^32 - 16 bases or 2^28 sequences, or more");
+        KBO_REQUIRE(((uintptr_t)d_ms & 3) == 0 && ((uintptr_t)d_out & 3) == 0 && ((uintptr_t)d_work & 15) == 0, KBO_E_BAD_ARG,
+                    "device buffers must be 4-byte (d_work 16-byte) aligned");
+        KBO_REQUIRE(work_bytes >= kbo_derand_summary_seq_work_bytes(n_seqs, total_bases, k, min_threshold), KBO_E_BAD_ARG, "work_bytes too small");
+        HIP_OK(kbo::launch_derand_summary_seq(d_ms, d_offsets, (uint32_t)n_seqs, total_bases, (uint32_t)k, d_thresholds, (uint32_t)min_threshold,
+                                              reinterpret_cast<uint32_t *>(d_out), d_work, static_cast<hipStream_t>(stream)));
+    });
+}
+
 size_t kbo_run_lengths_work_bytes(size_t n_seqs)
 {
     return kbo::chunk_items_scratch_words((uint32_t)std::min<size_t>(n_seqs, 0xFFFFFFFEu)) * sizeof(uint32_t) + 16;

@@ -339,6 +339,10 @@ size_t derand_seq_work_bytes(uint32_t n_seqs, uint64_t total_bases, uint32_t k, 
 hipError_t launch_derand_translate_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
                                        const uint32_t *d_thresholds, uint32_t min_threshold, const uint8_t *d_ref, uint8_t *d_chars_out,
                                        void *d_work, hipStream_t stream);
+// The same passes with the characters counted in LDS instead of written (kbo_hip.h kbo_aln_extent): d_out = n_seqs records of six u32
+// { 'M's, 'X's, 'R's, runs, start, end }, every one written (sequences of fewer than 3 bases: zeros); the same d_work.
+hipError_t launch_derand_summary_seq(const uint8_t *d_ms, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t total_bases, uint32_t k,
+                                     const uint32_t *d_thresholds, uint32_t min_threshold, uint32_t *d_out, void *d_work, hipStream_t stream);
 // A6 alone on clamped i32 derandomised values: one lane per position.
 hipError_t launch_translate(const int32_t *d_derand, uint64_t len, uint32_t k, uint32_t threshold,
                             uint8_t *d_chars_out, hipStream_t stream);
@@ -570,6 +574,10 @@ struct RefsetWalkArgs {
     uint8_t *ms;         // the slab: one byte per (pair, base)
 };
 hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units /* the largest refset_units() among the tasks' references */, hipStream_t stream);
+// kbo_summary_refset: of the n_pairs extents of a slab (six u32 a pair, launch_derand_summary_seq's) those with n_runs > 0, in pair
+// order, as records of seven u32 { pair, extent } at d_kept (room for n_pairs of them) and their number at d_total;
+// d_scratch: chunk_items_scratch_words(n_pairs) u32.  Nothing read back.
+hipError_t launch_refset_keep(const uint32_t *d_ext, uint32_t n_pairs, uint32_t *d_scratch, uint32_t *d_kept, uint32_t *d_total, hipStream_t stream);
 
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256

@@ -2,6 +2,8 @@
 // set of references").  The walk is refset_kernels.hip's.  A slab of (reference, sequence, strand) pairs is laid out
 // pair by pair and looks like an ordinary batch to what follows: derandomize_ms_vec / translate_ms_vec with a threshold per pair
 // (derand_seq_kernels.hip: the pair's reference's), then the single-index pipeline's run_lengths_gapped kernels as they are.
+// kbo_summary_refset shares the slabs, the upload, the '-' strand and the walk; behind the walk it runs the counting form of the
+// derandomize / translate stage and keeps the pairs with a hit on the device: no characters, no run-length stage.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 
@@ -119,18 +121,16 @@ struct SlabPlan {
     uint64_t bytes() const { return off.back(); }
 };
 
-struct Finder {
+// what kbo_find_refset and kbo_summary_refset share: the batch on the device, slabs of pairs and their walk
+struct SlabWalker {
     kbo_refset *set;
     const uint64_t *offsets;
-    uint32_t k, chunk, gap, min_thr; // min_thr: the smallest threshold of the references that take the LDS kernel
+    uint32_t k, chunk, min_thr; // min_thr: the smallest threshold of the references that take the LDS kernel
     uint64_t rev_base; // where the '-' strand of the batch begins in d_q
     hipStream_t st;
     DevSet *ds;
-    DevBuf d_q, d_off, d_ms, d_chars, d_poff, d_pthr, d_items, d_tasks, d_scratch, d_total, d_rles, d_derand;
-    size_t rle_capacity = 0;
-    std::vector<uint32_t> first, recs;
-    std::vector<kbo_ref_run> out;
-    std::vector<uint64_t> ref_begin, ref_end; // where every reference's records lie in `out`
+    DevBuf d_q, d_off, d_ms, d_poff, d_pthr, d_items, d_tasks, d_derand;
+    std::vector<uint64_t> ref_begin, ref_end; // where every reference's records lie in the call's list
     std::vector<uint8_t> walked;              // per reference: a launch of the LDS kernel has held it (the route counters)
 
     void add_pair(SlabPlan &P, uint32_t r, uint32_t s, uint32_t strand, uint32_t threshold)
@@ -157,22 +157,16 @@ struct Finder {
         P.lds_units = std::max(P.lds_units, kbo::refset_units(set->descs[r].n_sets));
     }
 
-    // walk, derandomize + translate, run lengths of one slab; its records behind those of the slabs so far
-    void run_slab(const SlabPlan &P)
+    // the slab's pairs, thresholds and tasks to the device, and the walk: the MS bytes of every pair in d_ms
+    void walk_slab(const SlabPlan &P)
     {
         const size_t np = P.pairs();
-        if (!np) return;
-        const size_t bytes = ((size_t)P.bytes() + 15) / 16 * 16 + 64;
-        d_ms.ensure(bytes);
-        d_chars.ensure(bytes);
+        d_ms.ensure(slab_buffer_bytes(P));
         d_poff.ensure((np + 1) * sizeof(uint64_t));
         d_pthr.ensure(np * sizeof(uint32_t));
         d_derand.ensure(kbo::derand_seq_work_bytes((uint32_t)np, P.bytes(), k, min_thr));
         d_items.ensure(P.items.size() * sizeof(uint32_t));
         d_tasks.ensure(P.tasks.size() * sizeof(uint32_t));
-        const size_t scratch_words = kbo::chunk_items_scratch_words((uint32_t)np);
-        d_scratch.ensure(scratch_words * sizeof(uint32_t));
-        d_total.ensure(16);
         HIP_OK(hipMemcpyAsync(d_poff.p, P.off.data(), (np + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_pthr.p, P.thr.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_items.p, P.items.data(), P.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -193,6 +187,27 @@ struct Finder {
                 t_routes[0]++;
             }
         t_routes[2] += np;
+    }
+    static size_t slab_buffer_bytes(const SlabPlan &P) { return ((size_t)P.bytes() + 15) / 16 * 16 + 64; }
+};
+
+struct Finder : SlabWalker {
+    uint32_t gap;
+    DevBuf d_chars, d_scratch, d_total, d_rles;
+    size_t rle_capacity = 0;
+    std::vector<uint32_t> first, recs;
+    std::vector<kbo_ref_run> out;
+
+    // walk, derandomize + translate, run lengths of one slab; its records behind those of the slabs so far
+    void run_slab(const SlabPlan &P)
+    {
+        const size_t np = P.pairs();
+        if (!np) return;
+        d_chars.ensure(slab_buffer_bytes(P));
+        const size_t scratch_words = kbo::chunk_items_scratch_words((uint32_t)np);
+        d_scratch.ensure(scratch_words * sizeof(uint32_t));
+        d_total.ensure(16);
+        walk_slab(P);
         HIP_OK(kbo::launch_derand_translate_seq(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, P.bytes(), k, d_pthr.as<uint32_t>(), min_thr,
                                                 nullptr, d_chars.as<uint8_t>(), d_derand.p, st));
         HIP_OK(kbo::launch_rle_count(d_chars.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, gap, d_scratch.as<uint32_t>(),
@@ -231,6 +246,155 @@ struct Finder {
         t_routes[3]++;
     }
 };
+
+struct Summarizer : SlabWalker {
+    DevBuf d_ext, d_scratch, d_kept, d_total;
+    std::vector<uint32_t> kept;
+    std::vector<kbo_ref_summary> out;
+
+    // walk, the counting form of derandomize + translate, the pairs with a hit kept: one count and those records come back
+    void run_slab(const SlabPlan &P)
+    {
+        const size_t np = P.pairs();
+        if (!np) return;
+        d_ext.ensure(np * sizeof(kbo_aln_extent));
+        d_scratch.ensure(kbo::chunk_items_scratch_words((uint32_t)np) * sizeof(uint32_t));
+        d_kept.ensure(np * 7 * sizeof(uint32_t));
+        d_total.ensure(16);
+        walk_slab(P);
+        HIP_OK(kbo::launch_derand_summary_seq(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, P.bytes(), k, d_pthr.as<uint32_t>(), min_thr,
+                                              d_ext.as<uint32_t>(), d_derand.p, st));
+        HIP_OK(kbo::launch_refset_keep(d_ext.as<uint32_t>(), (uint32_t)np, d_scratch.as<uint32_t>(), d_kept.as<uint32_t>(), d_total.as<uint32_t>(), st));
+        uint32_t total = 0;
+        HIP_OK(hipMemcpyAsync(&total, d_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        kept.resize((size_t)total * 7);
+        if (total) { // (nothing runs in between: a copy, not a second pass)
+            HIP_OK(hipMemcpyAsync(kept.data(), d_kept.p, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+        }
+        size_t x = 0;
+        for (size_t p = 0; p < np; p++) { // (every pair of the slab, so that a reference without a hit still has its place)
+            const uint32_t r = P.ref[p];
+            if (ref_begin[r] == ~0ull) ref_begin[r] = out.size();
+            if (x < total && kept[7 * x] == p) {
+                const uint32_t *w = kept.data() + 7 * x + 1;
+                out.push_back(kbo_ref_summary{r, P.seq[p], P.strand[p], kbo_aln_extent{w[0], w[1], w[2], w[3], w[4], w[5]}});
+                x++;
+            }
+            ref_end[r] = out.size();
+        }
+        t_routes[3]++;
+    }
+};
+
+// the threshold of every reference that can be queried (lib.rs:620); the errors of kbo_find on its handle
+std::vector<uint32_t> refset_thresholds(const kbo_refset *set, double max_error_prob)
+{
+    KBO_REQUIRE(max_error_prob <= 1.0 && max_error_prob > 0.0, KBO_E_BAD_ARG, "0 < max_error_prob <= 1 (derandomize.rs:136-137)");
+    std::vector<uint32_t> thr(set->descs.size(), 0);
+    for (size_t r = 0; r < thr.size(); r++) {
+        if (set->descs[r].status) continue;
+        thr[r] = (uint32_t)random_match_threshold(set->k, set->descs[r].n_kmers, 4, max_error_prob);
+        KBO_REQUIRE(thr[r] > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
+    }
+    return thr;
+}
+
+// the checks on the batch, all before the first HIP call; its bases
+uint64_t check_refset_batch(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs)
+{
+    check_batch(concat, offsets, n_seqs);
+    check_len_threshold(offsets, n_seqs, set->k, 2);
+    const uint64_t total = offsets[n_seqs];
+    KBO_REQUIRE(total < (1ull << 31), KBO_E_UNSUPPORTED, "a batch of 2^31 bases or more");
+    return total;
+}
+
+// the batch to the device, once; its '-' strand behind it, made where it is
+void upload_batch(SlabWalker &F, kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint64_t total, int strands,
+                  hipStream_t stream)
+{
+    const size_t n_refs = set->descs.size();
+    F.set = set;
+    F.offsets = offsets;
+    F.k = set->k;
+    F.chunk = std::max<uint32_t>(kbo::kRefsetChunk, 4u * set->k);
+    F.rev_base = (total + 15) / 16 * 16;
+    F.ds = device_set(set, current_device());
+    F.ref_begin.assign(n_refs, ~0ull);
+    F.ref_end.assign(n_refs, 0);
+    F.walked.assign(n_refs, 0);
+    F.st = stream;
+    F.d_q.alloc(2 * F.rev_base + 64);
+    F.d_off.alloc((n_seqs + 1) * sizeof(uint64_t));
+    HIP_OK(hipMemsetAsync(F.d_q.p, 0, 2 * F.rev_base + 64, F.st));
+    HIP_OK(hipMemcpyAsync(F.d_q.p, concat, total, hipMemcpyHostToDevice, F.st));
+    HIP_OK(hipMemcpyAsync(F.d_off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, F.st));
+    if (strands & KBO_STRAND_REV)
+        HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
+}
+
+// the references of the LDS kernel: every pair carries its reference's threshold, so a slab is cut by the budget alone
+template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, size_t n_seqs, int strands)
+{
+    const kbo_refset *set = f.set;
+    const size_t n_refs = set->descs.size();
+    const uint64_t budget = slab_bytes_for(nullptr);
+    f.min_thr = set->k;
+    for (size_t r = 0; r < n_refs; r++)
+        if (!set->descs[r].status && !set->descs[r].route) f.min_thr = std::min(f.min_thr, thr[r]);
+    SlabPlan P;
+    P.clear();
+    for (size_t r = 0; r < n_refs; r++) {
+        if (set->descs[r].status || set->descs[r].route) continue;
+        for (size_t s = 0; s < n_seqs; s++)
+            for (uint32_t strand = 1; strand <= 2; strand++) {
+                if (!(strands & strand)) continue;
+                const uint64_t len = f.offsets[s + 1] - f.offsets[s];
+                if (P.pairs() && P.bytes() + len > budget) {
+                    f.run_slab(P);
+                    P.clear();
+                }
+                f.add_pair(P, (uint32_t)r, (uint32_t)s, strand, thr[r]);
+            }
+    }
+    f.run_slab(P);
+}
+
+// the call's list: every reference's records, in the order of the references
+template <typename T> T *gather_by_ref(const SlabWalker &F, const std::vector<T> &out, uint64_t *n)
+{
+    MallocPtr<T> res = malloc_array<T>(out.size());
+    size_t at = 0;
+    for (size_t r = 0; r < F.ref_begin.size(); r++) {
+        if (F.ref_begin[r] == ~0ull) continue;
+        std::copy(out.begin() + F.ref_begin[r], out.begin() + F.ref_end[r], res.get() + at);
+        at += F.ref_end[r] - F.ref_begin[r];
+    }
+    *n = at;
+    return res.release();
+}
+
+// kbo_aln_extent of one sequence's characters (the references that take the single-index pipeline)
+kbo_aln_extent extent_of_chars(const uint8_t *c, uint64_t len)
+{
+    kbo_aln_extent e{0, 0, 0, 0, 0, 0};
+    bool in_run = false;
+    for (uint64_t i = 0; i < len; i++) {
+        const bool hit = c[i] != '-';
+        e.n_match += c[i] == 'M';
+        e.n_mismatch += c[i] == 'X';
+        e.n_jump += c[i] == 'R';
+        if (hit) {
+            if (!in_run) e.n_runs++;
+            if (!e.end) e.start = (uint32_t)i;
+            e.end = (uint32_t)i + 1;
+        }
+        in_run = hit;
+    }
+    return e;
+}
 
 } // namespace
 
@@ -336,65 +500,17 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
         *n_runs = 0;
         kbo_find_opts o;
         if (opts) o = *opts; else kbo_find_opts_default(&o);
-        KBO_REQUIRE(o.max_error_prob <= 1.0 && o.max_error_prob > 0.0, KBO_E_BAD_ARG, "0 < max_error_prob <= 1 (derandomize.rs:136-137)");
-        const size_t n_refs = set->descs.size();
-        std::vector<uint32_t> thr(n_refs, 0);
-        for (size_t r = 0; r < n_refs; r++) {
-            if (set->descs[r].status) continue;
-            thr[r] = (uint32_t)random_match_threshold(set->k, set->descs[r].n_kmers, 4, o.max_error_prob); // lib.rs:620
-            KBO_REQUIRE(thr[r] > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275, translate.rs:269)");
-        }
-        check_batch(concat, offsets, n_seqs);
-        check_len_threshold(offsets, n_seqs, set->k, 2);
-        const uint64_t total = offsets[n_seqs];
-        KBO_REQUIRE(total < (1ull << 31), KBO_E_UNSUPPORTED, "a batch of 2^31 bases or more");
+        const std::vector<uint32_t> thr = refset_thresholds(set, o.max_error_prob);
+        const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
         std::fill(t_routes, t_routes + 4, 0);
 
-        const int dev = current_device();
-        Finder F;
-        F.set = set;
-        F.offsets = offsets;
-        F.k = set->k;
-        F.chunk = std::max<uint32_t>(kbo::kRefsetChunk, 4u * set->k);
-        F.gap = (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu);
-        F.rev_base = (total + 15) / 16 * 16;
-        F.ds = device_set(set, dev);
-        F.ref_begin.assign(n_refs, ~0ull);
-        F.ref_end.assign(n_refs, 0);
-        F.walked.assign(n_refs, 0);
-        StreamScope stream;
-        F.st = stream.s;
-        // the batch, once; its '-' strand behind it, made where it is
-        F.d_q.alloc(2 * F.rev_base + 64);
-        F.d_off.alloc((n_seqs + 1) * sizeof(uint64_t));
-        HIP_OK(hipMemsetAsync(F.d_q.p, 0, 2 * F.rev_base + 64, F.st));
-        HIP_OK(hipMemcpyAsync(F.d_q.p, concat, total, hipMemcpyHostToDevice, F.st));
-        HIP_OK(hipMemcpyAsync(F.d_off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, F.st));
-        if (strands & KBO_STRAND_REV)
-            HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
-
-        // the references of the LDS kernel: every pair carries its reference's threshold, so a slab is cut by the budget alone
-        const uint64_t budget = slab_bytes_for(nullptr);
+        const size_t n_refs = set->descs.size();
         const uint32_t n_strands = strands == 3 ? 2 : 1;
-        F.min_thr = set->k;
-        for (size_t r = 0; r < n_refs; r++)
-            if (!set->descs[r].status && !set->descs[r].route) F.min_thr = std::min(F.min_thr, thr[r]);
-        SlabPlan P;
-        P.clear();
-        for (size_t r = 0; r < n_refs; r++) {
-            if (set->descs[r].status || set->descs[r].route) continue;
-            for (size_t s = 0; s < n_seqs; s++)
-                for (uint32_t strand = 1; strand <= 2; strand++) {
-                    if (!(strands & strand)) continue;
-                    const uint64_t len = offsets[s + 1] - offsets[s];
-                    if (P.pairs() && P.bytes() + len > budget) {
-                        F.run_slab(P);
-                        P.clear();
-                    }
-                    F.add_pair(P, (uint32_t)r, (uint32_t)s, strand, thr[r]);
-                }
-        }
-        F.run_slab(P);
+        Finder F;
+        F.gap = (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu);
+        StreamScope stream;
+        upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+        run_slabs(F, thr, n_seqs, strands);
 
         // the references that do not fit the LDS form: their own index through the single-index pipeline, one at a time
         std::vector<uint64_t> rle_off(2 * n_seqs + 1);
@@ -420,16 +536,53 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
             t_routes[1]++;
             t_routes[2] += n_seqs * n_strands;
         }
+        *runs = gather_by_ref(F, F.out, n_runs);
+    });
+}
 
-        MallocPtr<kbo_ref_run> res = malloc_array<kbo_ref_run>(F.out.size());
-        size_t at = 0;
+int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob, int strands,
+                       kbo_ref_summary **records, uint64_t *n_records)
+{
+    return guarded([&] {
+        static_assert(sizeof(kbo_ref_summary) == 36, "kbo_ref_summary is 36 bytes");
+        KBO_REQUIRE(strands >= 1 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+        KBO_REQUIRE(set && records && n_records, KBO_E_BAD_ARG, "null argument");
+        *records = nullptr;
+        *n_records = 0;
+        const std::vector<uint32_t> thr = refset_thresholds(set, max_error_prob);
+        const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
+        std::fill(t_routes, t_routes + 4, 0);
+
+        const size_t n_refs = set->descs.size();
+        const uint32_t n_strands = strands == 3 ? 2 : 1;
+        Summarizer F;
+        StreamScope stream;
+        upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+        run_slabs(F, thr, n_seqs, strands);
+
+        // the references that do not fit the LDS form: the characters of the single-index pipeline, counted here
+        std::vector<uint8_t> fwd, rev;
         for (size_t r = 0; r < n_refs; r++) {
-            if (F.ref_begin[r] == ~0ull) continue;
-            std::copy(F.out.begin() + F.ref_begin[r], F.out.begin() + F.ref_end[r], res.get() + at);
-            at += F.ref_end[r] - F.ref_begin[r];
+            if (set->descs[r].status || !set->descs[r].route) continue;
+            if (strands & KBO_STRAND_FWD) fwd.resize(total);
+            if (strands & KBO_STRAND_REV) rev.resize(total);
+            matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, max_error_prob, false, fwd.data(), nullptr, strands, rev.data());
+            F.ref_begin[r] = F.out.size();
+            for (size_t s = 0; s < n_seqs; s++)
+                for (uint32_t strand = 1; strand <= 2; strand++) {
+                    if (!(strands & strand)) continue;
+                    const uint8_t *c = (strand == KBO_STRAND_FWD ? fwd.data() : rev.data()) + offsets[s];
+                    const kbo_aln_extent e = extent_of_chars(c, offsets[s + 1] - offsets[s]);
+                    if (e.n_runs) F.out.push_back(kbo_ref_summary{(uint32_t)r, (uint32_t)s, strand, e});
+                }
+            F.ref_end[r] = F.out.size();
+            t_routes[1]++;
+            t_routes[2] += n_seqs * n_strands;
         }
-        *n_runs = at;
-        *runs = res.release();
+        uint64_t n = 0;
+        MallocPtr<kbo_ref_summary> res(gather_by_ref(F, F.out, &n));
+        *n_records = n;
+        if (n) *records = res.release(); // (none: *records stays NULL)
     });
 }
 

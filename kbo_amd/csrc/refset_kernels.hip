@@ -112,7 +112,44 @@ __global__ __launch_bounds__(kRefsetThreads) void refset_walk_kernel(RefsetWalkA
     }
 }
 
+// kbo_summary_refset: the pairs of a slab with a hit (n_runs > 0), kept in pair order.  ext: six words a pair (kbo_aln_extent)
+__global__ void refset_keep_flag_kernel(const uint32_t *__restrict__ ext, uint32_t n_pairs, uint32_t *__restrict__ flag)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n_pairs) return;
+    flag[p] = p < n_pairs && ext[(size_t)p * 6u + 3u] ? 1u : 0u;
+}
+
+// kept record: { pair, the six words of its extent }; *total: their number
+__global__ void refset_keep_kernel(const uint32_t *__restrict__ ext, uint32_t n_pairs, const uint32_t *__restrict__ at,
+                                   const uint32_t *__restrict__ sums, uint32_t *__restrict__ kept, uint32_t *__restrict__ total)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n_pairs) return;
+    const uint32_t pos = sums[p / kScanBlock] + at[p];
+    if (p == n_pairs) {
+        *total = pos;
+        return;
+    }
+    const uint32_t *e = ext + (size_t)p * 6u;
+    if (!e[3]) return;
+    uint32_t *o = kept + (size_t)pos * 7u;
+    o[0] = p;
+    for (uint32_t i = 0; i < 6u; i++) o[1u + i] = e[i];
+}
+
 } // namespace
+
+hipError_t launch_refset_keep(const uint32_t *d_ext, uint32_t n_pairs, uint32_t *d_scratch, uint32_t *d_kept, uint32_t *d_total, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipErrorInvalidValue;
+    const dim3 blocks((n_pairs + 1u + 255u) / 256u);
+    hipLaunchKernelGGL(refset_keep_flag_kernel, blocks, dim3(256), 0, stream, d_ext, n_pairs, d_scratch);
+    const hipError_t e = launch_scan(d_scratch, n_pairs + 1u, d_scratch + n_pairs + 1u, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(refset_keep_kernel, blocks, dim3(256), 0, stream, d_ext, n_pairs, d_scratch, d_scratch + n_pairs + 1u, d_kept, d_total);
+    return hipGetLastError();
+}
 
 hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units, hipStream_t stream)
 {

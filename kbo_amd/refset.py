@@ -14,6 +14,11 @@ REF_RUN = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32
                     ("matches", np.uint32), ("mismatches", np.uint32), ("jumps", np.uint32), ("gap_bases", np.uint32),
                     ("gap_opens", np.uint32)])
 
+# kbo_ref_summary (36 bytes): the pair + kbo_aln_extent - the numbers of 'M', 'X' and 'R', the maximal stretches without '-', and
+# where the first one starts and the last one ends
+REF_SUMMARY = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32), ("n_match", np.uint32), ("n_mismatch", np.uint32),
+                        ("n_jump", np.uint32), ("n_runs", np.uint32), ("start", np.uint32), ("end", np.uint32)])
+
 
 class RefSet:
     """kbo_refset_t: index r is what kbo::build (lib.rs:501-506) makes of reference r alone"""
@@ -78,9 +83,29 @@ def find_refset(query_seqs, refset, find_opts=None, strands=STRAND_BOTH):
         lib().kbo_free(p)
 
 
+def summary_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH):
+    """The summary of kbo::matches of every query sequence, on the strands asked for, against every reference of the set: one
+    REF_SUMMARY record per (ref, seq, strand) pair with a hit, ordered by (ref, seq, strand); a pair without a hit has none.  The
+    pairs, thresholds and coordinates are find_refset's, and n_runs is its number of records for the pair with max_gap_len = 0."""
+    raw = [_u8(s) for s in query_seqs]
+    concat = np.ascontiguousarray(np.concatenate(raw) if raw else np.zeros(0, dtype=np.uint8))
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in raw], dtype=np.uint64)
+    p, n = C.c_void_p(), C.c_uint64()
+    check(lib().kbo_summary_refset(refset._h, concat.ctypes.data, offsets.ctypes.data, len(raw), float(max_error_prob), int(strands),
+                                   C.byref(p), C.byref(n)))
+    try:
+        if n.value == 0:
+            return np.zeros(0, dtype=REF_SUMMARY)
+        buf = (C.c_uint8 * (n.value * REF_SUMMARY.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=REF_SUMMARY).copy()
+    finally:
+        lib().kbo_free(p)
+
+
 def last_routes():
     """(references walked by the LDS kernel, references through the single-index pipeline, pairs walked, slabs) of the calling
-    thread's last find_refset"""
+    thread's last find_refset or summary_refset"""
     out = (C.c_uint64 * 4)()
     check(lib().kbo_refset_last_routes(out))
     return tuple(int(v) for v in out)

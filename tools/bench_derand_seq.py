@@ -3,6 +3,9 @@
 (one threshold a call) on the same bytes.  16 MiB of walk-like MS bytes - k, with ramps 0, 1, 2, ... behind a mismatch every about
 100 bases - as 256 sequences of 64 KiB and as 16 sequences of 1 MiB, k = 31, t = 14.  Timed with device events over CALLS calls
 behind WARMUP calls; prints one JSON line per shape with the milliseconds a call and whether the two stages' characters are equal.
+The summary form of the stage (kbo_derand_summary_seq_dev: counts, runs and extent per sequence, no characters) is timed in the same
+run, next to the composition it replaces - kbo_derand_translate_seq_dev followed by kbo_summary_dev on its output - and its counts are
+compared with that composition's.
 Usage: tools/bench_derand_seq.py   (environment: CALLS=20 WARMUP=3)"""
 import json
 import os
@@ -61,7 +64,22 @@ for n_seqs in (256, 16):
     def one():
         kbo_amd.check(L.kbo_derand_translate_dev(d_ms.data_ptr(), d_off.data_ptr(), n_seqs, TOTAL, K, T, None, out_one.data_ptr(), length,
                                                  w_one.data_ptr(), wb_one, s))
+    wb_sum = int(L.kbo_derand_summary_seq_work_bytes(n_seqs, TOTAL, K, T))
+    w_sum = torch.zeros(wb_sum // 8 + 2, dtype=torch.int64, device=dev)
+    ext = torch.zeros((n_seqs, 6), dtype=torch.int32, device=dev)
+    summ = torch.zeros((n_seqs, 4), dtype=torch.int32, device=dev)
+
+    def summary():
+        kbo_amd.check(L.kbo_derand_summary_seq_dev(d_ms.data_ptr(), d_off.data_ptr(), n_seqs, TOTAL, K, d_thr.data_ptr(), T, ext.data_ptr(),
+                                                   w_sum.data_ptr(), wb_sum, s))
+
+    def composed():
+        seq()
+        kbo_amd.check(L.kbo_summary_dev(out_seq.data_ptr(), d_off.data_ptr(), n_seqs, length, summ.data_ptr(), s))
     ms_seq, ms_one = timed(seq), timed(one)
+    ms_sum, ms_comp = timed(summary), timed(composed)
     print(json.dumps({"n_seqs": n_seqs, "seq_len": length, "k": K, "t": T, "calls": CALLS, "derand_translate_seq_ms": round(ms_seq, 4),
                       "derand_translate_ms": round(ms_one, 4), "seq_scratch_bytes": wb_seq,
+                      "derand_summary_seq_ms": round(ms_sum, 4), "derand_translate_seq_then_summary_ms": round(ms_comp, 4),
+                      "summary_counts_equal": bool(torch.equal(ext[:, :4], summ)),
                       "equal": bool(torch.equal(out_seq[:TOTAL], out_one[:TOTAL]))}))

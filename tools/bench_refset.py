@@ -8,6 +8,9 @@ Workload: REFS random references of REF_BP bases at k = 31 against a query of QU
 copy of every 40th reference with 1 % substitutions lies in the query, so that there are runs to report.
 Usage: tools/bench_refset.py   (environment: REFS=2000 REF_BP=1000 QUERY_BP=5000000 CONTIGS=50 LOOP=50 REPEATS=3; CONTIGS=100 makes
 the contigs 50 kbp, below the 65 536 bases at which the single-index stage changes kernels; records_crc32 compares two builds)
+SUMMARY=1 times kbo_summary_refset on the same workload instead (one record per pair with a hit; the CRC is of those records) and
+checks, for the references the loop takes - or, with LOOP=0, for all of them against one kbo_find_refset(max_gap_len = 0) call that
+is not timed - that every pair's n_runs is its number of run records.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -22,8 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kbo_amd  # noqa: E402
 from kbo_amd import batch, refset  # noqa: E402
 
-REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS = (int(os.environ.get(n, d)) for n, d in (
-    ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3)))
+REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS, SUMMARY = (int(os.environ.get(n, d)) for n, d in (
+    ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3), ("SUMMARY", 0)))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -52,19 +55,53 @@ t1 = time.perf_counter()
 rs.to_device()
 torch.cuda.synchronize()
 t2 = time.perf_counter()
-got = refset.find_refset(contigs, rs, fopts, strands=3)  # warm-up: code objects, the call's buffers
+
+
+def runs_per_pair(records):
+    """{(ref, seq, strand): number of records} of find_refset's records"""
+    keys, counts = np.unique(np.stack([records["ref"], records["seq"], records["strand"]], axis=1), axis=0, return_counts=True) \
+        if len(records) else (np.zeros((0, 3), dtype=np.uint32), np.zeros(0, dtype=np.int64))
+    return {tuple(int(v) for v in key): int(c) for key, c in zip(keys, counts)}
+
+
+if SUMMARY:
+    def call():
+        return refset.summary_refset(contigs, rs, fopts.max_error_prob, strands=3)
+    name = "summary_refset"
+else:
+    def call():
+        return refset.find_refset(contigs, rs, fopts, strands=3)
+    name = "find_refset"
+got = call()  # warm-up: code objects, the call's buffers
 times = []
 for _ in range(REPEATS):
     t = time.perf_counter()
-    got = refset.find_refset(contigs, rs, fopts, strands=3)
+    got = call()
     times.append(time.perf_counter() - t)
 find_s = statistics.median(times)
 res = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
-       "refset_build_s": round(t1 - t0, 4), "refset_to_device_s": round(t2 - t1, 4), "find_refset_s": round(find_s, 4),
-       "find_refset_s_all": [round(t, 4) for t in times], "find_refset_gbp_per_s": round(pair_bases / find_s / 1e9, 2),
+       "refset_build_s": round(t1 - t0, 4), "refset_to_device_s": round(t2 - t1, 4), name + "_s": round(find_s, 4),
+       name + "_s_all": [round(t, 4) for t in times], name + "_gbp_per_s": round(pair_bases / find_s / 1e9, 2),
        "records": int(len(got)), "records_crc32": zlib.crc32(got.tobytes()), "routes": refset.last_routes()}
 
-if LOOP > 0:
+if SUMMARY:
+    mine = {(int(r), int(s), int(st)): int(n) for r, s, st, n in zip(got["ref"], got["seq"], got["strand"], got["n_runs"])}
+    if LOOP > 0:  # against the single-index loop, for the references it takes
+        picks = list(range(0, REFS, max(1, REFS // LOOP)))[:LOOP]
+        want = {}
+        for r in picks:
+            sbwt, _ = kbo_amd.build([refs[r]], kbo_amd.BuildOpts(k=K))
+            rles, ro = batch.find_batch_strands(sbwt, concat, offsets, kbo_amd.FindOpts(max_gap_len=0), strands=3)
+            for x in range(2 * CONTIGS):
+                if ro[x + 1] > ro[x]:
+                    want[r, x // 2, x % 2 + 1] = int(ro[x + 1] - ro[x])
+        mine = {key: n for key, n in mine.items() if key[0] in set(picks)}
+        res["runs_checked_refs"] = len(picks)
+    else:  # against kbo_find_refset without gap filling, every reference
+        want = runs_per_pair(refset.find_refset(contigs, rs, kbo_amd.FindOpts(max_gap_len=0), strands=3))
+        res["runs_checked_refs"] = REFS
+    res["n_runs_equal_find"] = mine == want
+elif LOOP > 0:
     def one(r):
         """(seconds of build, of to_device, of find) for reference r alone, and its records"""
         a = time.perf_counter()
