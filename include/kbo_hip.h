@@ -524,6 +524,50 @@ typedef struct {
 } kbo_ref_summary; /* 36 bytes */
 int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
                        int strands, kbo_ref_summary **records, uint64_t *n_records);
+/* The two calls for a batch that is already in the HBM of the current device: the same records, in the same order, written to the
+ * caller's device buffer; everything is enqueued on `stream` (a hipStream_t) and the call returns.  No hipStreamSynchronize, no
+ * device-to-host copy, no allocation: all scratch is d_work, and the one host-to-device upload of a call is the references' thresholds
+ * (n_refs uint32_t - only the host can compute them, from n_kmers and max_error_prob).  Launches: 6 a call (7 with the '-' strand, and
+ * a device-to-device copy of the batch when both strands are asked for) + 34 a slab (find) or 22 a slab (summary), whatever the batch
+ * and the set hold.
+ * Inputs: the set has a copy on the current device (kbo_refset_to_device; KBO_E_BAD_ARG when it has none); d_concat holds
+ * total_bases + 16 readable bytes and is 16-byte aligned; d_offsets holds n_seqs + 1 uint64_t on the device, 8-byte aligned, ascending
+ * from 0 to total_bases, which the caller knows: nothing about the batch is read back, so nothing about it is checked.
+ * Records: exactly those kbo_find_refset / kbo_summary_refset return for the same set, batch, options and strands - fields, the
+ * coordinates of the '-' strand and the order (ref, seq, strand with '+' first, start) - from d_runs[0] / d_records[0] on (4-byte
+ * aligned).  *d_n_runs / *d_n_records (on the device, 8-byte aligned; the call writes it and does not require it to be zero) receives
+ * the number of records, those beyond `capacity` included: they are counted and not written, nothing is written at or behind element
+ * `capacity`, and the output pointer may be NULL when capacity == 0.
+ * A sequence of fewer than 3 bases, an empty one included, contributes no record and disturbs no other pair: the device form cannot
+ * refuse the batch with KBO_E_LEN_LE_2 as the host form does, because it does not know the lengths.  A reference with a status
+ * contributes nothing, as there.  A set that holds a reference of the single-index route (more than KBO_REFSET_MAX_ROWS rows) is refused
+ * with KBO_E_UNSUPPORTED - that route is a host pipeline; kbo_refset_lds_only() is 1 when the set holds none, else 0.
+ * Slabs: a slab is a range of consecutive queryable references against the WHOLE batch on the strands asked for, refs x n_strands x
+ * total_bases bytes, planned on the device (kbo_amd/csrc/refset_plan_kernels.hip).  *_work_bytes(..., refs_per_slab) is the exact figure
+ * for slabs of that many references - 0: as many as one slab may hold (all queryable ones unless 2^32 - 16 bytes or 2^28 pairs come
+ * first), larger values count as that - and grows with refs_per_slab and with capacity; 0 for arguments the call refuses.  The call
+ * uses the largest refs_per_slab whose figure fits work_bytes and touches no byte of d_work (16-byte aligned) behind that figure.
+ * d_work holds, per call, the '-' strand of the batch (behind a copy of the '+' strand when both are asked for: the walk addresses one
+ * buffer), the chunks of every sequence with their scan, the thresholds and the list of the queryable references; per slab, pair
+ * offsets and thresholds, the walk's items and tasks, the MS bytes, the characters (find), the scratch of
+ * kbo_derand_translate_seq_dev's stage - for the lowest threshold there is, 2: the figure does not know max_error_prob - and of
+ * kbo_run_lengths_seq_dev's (find) or the extents and the kept list (summary), and a slab-local buffer of min(capacity, the most runs
+ * a slab can have) seven-word records (find).
+ * Errors, all before anything is enqueued: KBO_E_BAD_ARG for null arguments, misaligned ones, strands outside 1 .. 3, a max_error_prob
+ * outside (0, 1] and a work_bytes below the figure for one reference a slab; KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_THRESHOLD_LE_1 as
+ * the host calls; KBO_E_UNSUPPORTED for a reference of the single-index route, a slab of one reference of 2^32 - 16 bytes or more, and
+ * n_seqs x n_strands >= 2^28.  kbo_refset_last_routes is not touched by these calls. */
+int kbo_refset_lds_only(const kbo_refset_t *set);
+size_t kbo_find_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                      size_t refs_per_slab);
+int kbo_find_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        const kbo_find_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_run *d_runs, size_t capacity,
+                        uint64_t *d_n_runs, void *stream);
+size_t kbo_summary_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                         size_t refs_per_slab);
+int kbo_summary_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                           double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_summary *d_records, size_t capacity,
+                           uint64_t *d_n_records, void *stream);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

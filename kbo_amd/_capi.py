@@ -119,6 +119,8 @@ SYMBOLS = [
     "kbo_summary_words_work_bytes", "kbo_summary_words_dev", "kbo_map_stream_submit_summary",
     "kbo_refset_build", "kbo_refset_free", "kbo_refset_size", "kbo_refset_k", "kbo_refset_n_kmers", "kbo_refset_status",
     "kbo_refset_to_device", "kbo_find_refset", "kbo_summary_refset",
+    "kbo_refset_lds_only", "kbo_find_refset_dev_work_bytes", "kbo_find_refset_dev", "kbo_summary_refset_dev_work_bytes",
+    "kbo_summary_refset_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -325,6 +327,11 @@ def lib():
     L.kbo_refset_to_device.argtypes = [vp, C.c_int]
     L.kbo_find_refset.argtypes = [vp, vp, vp, sz, C.POINTER(FindOpts), C.c_int, C.POINTER(vp), C.POINTER(u64)]
     L.kbo_summary_refset.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(u64)]
+    L.kbo_refset_lds_only.argtypes = [vp]
+    L.kbo_find_refset_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz]; L.kbo_find_refset_dev_work_bytes.restype = sz
+    L.kbo_find_refset_dev.argtypes = [vp, vp, vp, sz, u64, C.POINTER(FindOpts), C.c_int, vp, sz, vp, sz, vp, vp]
+    L.kbo_summary_refset_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz]; L.kbo_summary_refset_dev_work_bytes.restype = sz
+    L.kbo_summary_refset_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, sz, vp, vp]
     L.kbo_set_refset_record_capacity.argtypes = [sz]
     L.kbo_refset_last_routes.argtypes = [vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]

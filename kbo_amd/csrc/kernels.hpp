@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "refset_plan.hpp"
+
 namespace kbo {
 
 // Device-resident index (32-bit positions).  Layout: sbwt_index.hpp.
@@ -578,6 +580,30 @@ hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units /* the
 // order, as records of seven u32 { pair, extent } at d_kept (room for n_pairs of them) and their number at d_total;
 // d_scratch: chunk_items_scratch_words(n_pairs) u32.  Nothing read back.
 hipError_t launch_refset_keep(const uint32_t *d_ext, uint32_t n_pairs, uint32_t *d_scratch, uint32_t *d_kept, uint32_t *d_total, hipStream_t stream);
+// ---- the slab planner and the record stage of the device-resident reference-set calls (refset_plan_kernels.hip; the arithmetic:
+// refset_plan.hpp).  Everything the planner reads is on the device: the batch's offsets, the references' thresholds (0: the
+// reference cannot be queried), the scanned chunk counts and the list of the queryable references that launch_refset_plan_call makes
+struct RefsetPlan {
+    refplan::Geometry g;
+    const uint64_t *off;                // n_seqs + 1
+    const uint32_t *thr;                // per reference of the set
+    const uint32_t *nch, *nch_sums;     // chunks of every sequence, scanned (n_seqs + 1 values, two levels)
+    const uint32_t *qref;               // the queryable references, ascending
+};
+// once per call, 6 launches: d_nch and d_qflag take chunk_items_scratch_words(n_seqs) / (n_refs) u32, d_qref n_refs u32; *d_count = 0
+hipError_t launch_refset_plan_call(const RefsetPlan &a, uint32_t n_refs, uint32_t *d_nch, uint32_t *d_qflag, uint32_t *d_qref, uint64_t *d_count,
+                                   hipStream_t stream);
+// a slab of `refs` queryable references from the first_q-th on, 2 launches: pair offsets (pairs + 1) and thresholds, the '-' of the
+// pairs of fewer than 3 bases (d_chars, or nullptr), refs * g.item_slots item slots and refs * g.tasks_per_ref tasks of the walk
+hipError_t launch_refset_plan_slab(const RefsetPlan &a, uint32_t first_q, uint32_t refs, uint64_t *d_poff, uint32_t *d_pthr, uint8_t *d_chars,
+                                   uint4 *d_items, uint4 *d_tasks, hipStream_t stream);
+// the slab's records into the call's list, 2 launches: record x becomes { ref, seq, strand, record } at element *d_count + x of d_out when
+// that is in front of `capacity`; then *d_count grows by the slab's records, written or not.  Runs: d_first / d_local are the
+// segmented run-length stage's prefix and its first local_cap records of seven u32; summaries: launch_refset_keep's list and count
+hipError_t launch_refset_tag_runs(const RefsetPlan &a, uint32_t first_q, uint32_t n_pairs, const uint32_t *d_first, const uint32_t *d_local,
+                                  uint32_t local_cap, uint64_t *d_count, uint64_t capacity, uint32_t *d_out, hipStream_t stream);
+hipError_t launch_refset_tag_summaries(const RefsetPlan &a, uint32_t first_q, uint32_t n_pairs, const uint32_t *d_kept, const uint32_t *d_n_kept,
+                                       uint64_t *d_count, uint64_t capacity, uint32_t *d_out, hipStream_t stream);
 
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256

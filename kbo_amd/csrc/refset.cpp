@@ -396,6 +396,183 @@ kbo_aln_extent extent_of_chars(const uint8_t *c, uint64_t len)
     return e;
 }
 
+// ---- the device-resident form (kbo_find_refset_dev / kbo_summary_refset_dev): the same stages enqueued on the caller's stream over
+// the caller's work buffer.  A slab is a range of queryable references against the whole batch, planned on the device
+// (refset_plan_kernels.hip); nothing comes back to the host.
+struct DevForm {
+    kbo::refplan::Geometry g;
+    uint32_t n_refs = 0, n_q = 0, max_refs = 0, refs = 0; // references of the set, queryable ones, the most a slab may hold, a slab's
+    uint64_t local_cap = 0;                               // records of the slab-local buffer (find)
+    // per call ...
+    size_t q = 0, nch = 0, qflag = 0, qref = 0, thr = 0;
+    // ... and per slab
+    size_t poff = 0, pthr = 0, items = 0, tasks = 0, ms = 0, chars = 0, derand = 0, stage = 0, first = 0, local = 0, total = 0, end = 0;
+    bool ok = false; // false: a limit of the kernels is exceeded even with one reference per slab
+};
+
+size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+
+// the layout of d_work for slabs of refs_per_slab references (0: as many as a slab may hold; more than that: that many)
+DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int strands, size_t capacity, size_t refs_per_slab, bool find)
+{
+    DevForm F;
+    if (!set || n_seqs == 0 || strands < 1 || strands > 3) return F;
+    const uint64_t ns = strands == 3 ? 2 : 1;
+    if (n_seqs * ns >= (1ull << 28) || n_seqs >= (1ull << 28) || ns * total >= (1ull << 32) - 16) return F;
+    if (ns * kbo::refplan::chunks_bound(total, n_seqs, kbo::refplan::chunk_of(set->k)) > 0xFFFFFF00ull) return F;
+    F.g = kbo::refplan::geometry(n_seqs, total, strands, set->k);
+    F.n_refs = (uint32_t)set->descs.size();
+    for (const kbo::RefsetDesc &d : set->descs) F.n_q += !d.status;
+    // what a slab may hold: its bytes and item slots index with 32 bits, its pairs are the sequences of the stages behind the walk
+    uint64_t most = std::max<uint32_t>(F.n_q, 1);
+    if (total) most = std::min<uint64_t>(most, ((1ull << 32) - 17) / (ns * total));
+    most = std::min<uint64_t>(most, ((1ull << 28) - 1) / (n_seqs * ns));
+    most = std::min<uint64_t>(most, 0xFFFFFF00ull / F.g.item_slots);
+    F.max_refs = (uint32_t)most;
+    const uint64_t R = F.refs = (uint32_t)(refs_per_slab == 0 ? most : std::min<uint64_t>(refs_per_slab, most));
+    const uint64_t B = R * ns * total, np = R * n_seqs * ns;
+    const size_t rev = (size_t)(total + 15) / 16 * 16;
+    size_t w = 0;
+    F.q = w;      w += strands == 1 ? 0 : (strands == 3 ? 2 * rev : rev) + 64;
+    F.nch = w;    w += up16(kbo::chunk_items_scratch_words((uint32_t)n_seqs) * sizeof(uint32_t));
+    F.qflag = w;  w += up16(kbo::chunk_items_scratch_words(F.n_refs) * sizeof(uint32_t));
+    F.qref = w;   w += up16((size_t)F.n_refs * sizeof(uint32_t));
+    F.thr = w;    w += up16((size_t)F.n_refs * sizeof(uint32_t));
+    F.total = w;  w += 16;
+    F.poff = w;   w += up16((size_t)(np + 1) * sizeof(uint64_t));
+    F.pthr = w;   w += up16((size_t)np * sizeof(uint32_t));
+    F.items = w;  w += (size_t)R * F.g.item_slots * sizeof(uint4);
+    F.tasks = w;  w += (size_t)R * F.g.tasks_per_ref * sizeof(uint4);
+    F.ms = w;     w += up16((size_t)B) + 64;
+    // (the thresholds depend on max_error_prob, which the figure does not know: room for the lowest one there is)
+    F.derand = w; w += up16(kbo::derand_seq_work_bytes((uint32_t)np, B, set->k, 2));
+    if (find) {
+        F.local_cap = std::min<uint64_t>(capacity, B / 2 + np); // (a run holds a character other than '-' and ends at one)
+        F.chars = w; w += up16((size_t)B) + 64;
+        F.stage = w; w += up16(kbo::rle_seg_work_bytes((uint32_t)np, B));
+        F.first = w; w += up16((size_t)(np + 1) * sizeof(uint32_t));
+        F.local = w; w += up16((size_t)F.local_cap * kRleWords * sizeof(uint32_t));
+    } else {
+        F.chars = w; w += up16((size_t)np * sizeof(kbo_aln_extent));                                     // the extents
+        F.stage = w; w += up16(kbo::chunk_items_scratch_words((uint32_t)np) * sizeof(uint32_t));          // launch_refset_keep's scan
+        F.local = w; w += up16((size_t)np * 7 * sizeof(uint32_t));                                       // the kept list
+    }
+    F.end = w;
+    F.ok = true;
+    return F;
+}
+
+struct DevCall {
+    kbo_refset *set;
+    const uint8_t *d_concat;
+    const uint64_t *d_offsets;
+    size_t n_seqs;
+    uint64_t total_bases;
+    double max_error_prob;
+    uint32_t gap;
+    int strands;
+    void *d_work;
+    size_t work_bytes;
+    void *d_out;
+    size_t capacity;
+    uint64_t *d_n;
+    hipStream_t stream;
+};
+
+DevSet *device_set_if_any(kbo_refset *set, int device)
+{
+    std::lock_guard<std::mutex> g(set->mu);
+    auto it = set->dev.find(device);
+    return it == set->dev.end() ? nullptr : it->second;
+}
+
+void run_dev_form(const DevCall &c, bool find)
+{
+    KBO_REQUIRE(c.strands >= 1 && c.strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && c.d_n && (c.d_out || c.capacity == 0), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(((uintptr_t)c.d_concat & 15) == 0 && ((uintptr_t)c.d_work & 15) == 0 && ((uintptr_t)c.d_offsets & 7) == 0 &&
+                    ((uintptr_t)c.d_n & 7) == 0 && ((uintptr_t)c.d_out & 3) == 0,
+                KBO_E_BAD_ARG, "d_concat and d_work 16-byte, d_offsets and the count 8-byte, the records 4-byte aligned");
+    KBO_REQUIRE(c.n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+    kbo_refset *set = c.set;
+    const std::vector<uint32_t> thr = refset_thresholds(set, c.max_error_prob);
+    for (const kbo::RefsetDesc &d : set->descs)
+        KBO_REQUIRE(d.status || !d.route, KBO_E_UNSUPPORTED, "a reference of more than KBO_REFSET_MAX_ROWS rows: the host calls take it (kbo_refset_lds_only)");
+    DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, 1, find);
+    KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a slab of one reference of 2^32 - 16 bytes or more, or 2^28 (sequence, strand) pairs or more");
+    KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes too small for one reference a slab");
+    uint32_t lo = 1, hi = F.max_refs; // the largest refs_per_slab whose figure fits: the figure is monotonic
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, mid, find).end <= c.work_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, lo, find);
+    DevSet *ds = device_set_if_any(set, current_device());
+    KBO_REQUIRE(ds, KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
+
+    uint32_t min_thr = set->k;
+    std::vector<uint32_t> qrefs;
+    for (size_t r = 0; r < thr.size(); r++)
+        if (!set->descs[r].status) {
+            min_thr = std::min(min_thr, thr[r]);
+            qrefs.push_back((uint32_t)r);
+        }
+    hipStream_t st = c.stream;
+    uint8_t *w = static_cast<uint8_t *>(c.d_work);
+    auto at = [&](size_t o) { return reinterpret_cast<uint32_t *>(w + o); };
+    // the walk addresses ONE query buffer: the caller's for '+' alone, the '-' strand made here, or a copy of '+' with '-' behind it
+    const uint8_t *q = c.strands == 1 ? c.d_concat : w + F.q;
+    HIP_OK(hipMemcpyAsync(w + F.thr, thr.data(), thr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (c.strands == 3 && c.total_bases) HIP_OK(hipMemcpyAsync(w + F.q, c.d_concat, c.total_bases, hipMemcpyDeviceToDevice, st));
+    if (c.strands & KBO_STRAND_REV)
+        HIP_OK(kbo::launch_revcomp_bytes(c.d_concat, c.d_offsets, (uint32_t)c.n_seqs, c.total_bases, w + F.q + F.g.rev_base, st));
+    kbo::RefsetPlan P;
+    P.g = F.g;
+    P.off = c.d_offsets;
+    P.thr = at(F.thr);
+    P.nch = at(F.nch);
+    P.nch_sums = at(F.nch) + c.n_seqs + 1;
+    P.qref = at(F.qref);
+    HIP_OK(kbo::launch_refset_plan_call(P, F.n_refs, at(F.nch), at(F.qflag), at(F.qref), c.d_n, st));
+    if (c.total_bases == 0) return; // (no base, no record)
+
+    uint64_t *poff = reinterpret_cast<uint64_t *>(w + F.poff);
+    uint8_t *ms = w + F.ms;
+    for (size_t q0 = 0; q0 < qrefs.size(); q0 += F.refs) {
+        const uint32_t refs = (uint32_t)std::min<size_t>(F.refs, qrefs.size() - q0);
+        const uint32_t np = refs * (uint32_t)c.n_seqs * F.g.n_strands;
+        const uint64_t bytes = kbo::refplan::slab_bytes(F.g, refs);
+        uint32_t lds_units = 0;
+        for (uint32_t j = 0; j < refs; j++) lds_units = std::max(lds_units, kbo::refset_units(set->descs[qrefs[q0 + j]].n_sets));
+        HIP_OK(kbo::launch_refset_plan_slab(P, (uint32_t)q0, refs, poff, at(F.pthr), find ? w + F.chars : nullptr,
+                                            reinterpret_cast<uint4 *>(w + F.items), reinterpret_cast<uint4 *>(w + F.tasks), st));
+        kbo::RefsetWalkArgs a;
+        a.descs = ds->descs.as<kbo::RefsetDesc>();
+        a.arena = ds->arena.as<uint4>();
+        a.tasks = reinterpret_cast<const uint4 *>(w + F.tasks);
+        a.items = reinterpret_cast<const uint4 *>(w + F.items);
+        a.n_tasks = refs * F.g.tasks_per_ref;
+        a.k = set->k;
+        a.q = q;
+        a.ms = ms;
+        HIP_OK(kbo::launch_refset_walk(a, lds_units, st));
+        if (find) {
+            HIP_OK(kbo::launch_derand_translate_seq(ms, poff, np, bytes, set->k, at(F.pthr), min_thr, nullptr, w + F.chars, w + F.derand, st));
+            HIP_OK(kbo::launch_rle_seg_count(w + F.chars, poff, np, bytes, c.gap, 0u, w + F.stage, at(F.first), st));
+            if (F.local_cap)
+                HIP_OK(kbo::launch_rle_seg_emit(w + F.chars, np, bytes, c.gap, w + F.stage, at(F.local), (uint32_t)F.local_cap, st));
+            HIP_OK(kbo::launch_refset_tag_runs(P, (uint32_t)q0, np, at(F.first), at(F.local), (uint32_t)F.local_cap, c.d_n, c.capacity,
+                                               static_cast<uint32_t *>(c.d_out), st));
+        } else {
+            HIP_OK(kbo::launch_derand_summary_seq(ms, poff, np, bytes, set->k, at(F.pthr), min_thr, at(F.chars), w + F.derand, st));
+            HIP_OK(kbo::launch_refset_keep(at(F.chars), np, at(F.stage), at(F.local), at(F.total), st));
+            HIP_OK(kbo::launch_refset_tag_summaries(P, (uint32_t)q0, np, at(F.local), at(F.total), c.d_n, c.capacity,
+                                                    static_cast<uint32_t *>(c.d_out), st));
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -583,6 +760,50 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
         MallocPtr<kbo_ref_summary> res(gather_by_ref(F, F.out, &n));
         *n_records = n;
         if (n) *records = res.release(); // (none: *records stays NULL)
+    });
+}
+
+int kbo_refset_lds_only(const kbo_refset_t *set)
+{
+    if (!set) return 0;
+    for (const kbo::RefsetDesc &d : set->descs)
+        if (!d.status && d.route) return 0;
+    return 1;
+}
+
+size_t kbo_find_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                      size_t refs_per_slab)
+{
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, true).end;
+}
+
+size_t kbo_summary_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                         size_t refs_per_slab)
+{
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, false).end;
+}
+
+int kbo_find_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        const kbo_find_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_run *d_runs, size_t capacity,
+                        uint64_t *d_n_runs, void *stream)
+{
+    return guarded([&] {
+        kbo_find_opts o;
+        if (opts) o = *opts; else kbo_find_opts_default(&o);
+        run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, o.max_error_prob, (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu),
+                             strands, d_work, work_bytes, d_runs, capacity, d_n_runs, static_cast<hipStream_t>(stream)},
+                     true);
+    });
+}
+
+int kbo_summary_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                           double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_summary *d_records, size_t capacity,
+                           uint64_t *d_n_records, void *stream)
+{
+    return guarded([&] {
+        run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_records, capacity,
+                             d_n_records, static_cast<hipStream_t>(stream)},
+                     false);
     });
 }
 

@@ -55,6 +55,10 @@ class RefSet:
         check(lib().kbo_refset_to_device(self._h, device))
         return self
 
+    def lds_only(self):
+        """True when no reference takes the single-index route: what find_refset_dev / summary_refset_dev ask of a set"""
+        return bool(lib().kbo_refset_lds_only(self._h))
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().kbo_refset_free(self._h)
@@ -101,6 +105,59 @@ def summary_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH)
         return np.frombuffer(buf, dtype=REF_SUMMARY).copy()
     finally:
         lib().kbo_free(p)
+
+
+def _refset_dev(find, concat, offsets, refset, arg, strands, capacity, refs_per_slab, stream):
+    import torch
+    device = concat.device
+    n_seqs = int(offsets.numel()) - 1
+    assert concat.dtype == torch.uint8 and offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+    L = lib()
+    words = 10 if find else 9
+    work_bytes = L.kbo_find_refset_dev_work_bytes if find else L.kbo_summary_refset_dev_work_bytes
+    ns = 2 if int(strands) == STRAND_BOTH else 1
+    if refs_per_slab is None:  # slabs of about 256 MiB; 0: as many references as a slab may hold
+        refs_per_slab = max(1, (1 << 28) // max(1, ns * total))
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.device(device), torch.cuda.stream(s):
+        q = concat.contiguous()
+        if int(q.numel()) < total + 16 or q.data_ptr() % 16:  # the 16 bytes of slack behind a per-base buffer
+            p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+            p[:total].copy_(q[:total])
+            q = p
+        off = offsets.contiguous()
+        wb = int(work_bytes(refset._h, n_seqs, total, int(strands), capacity, refs_per_slab))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=device)
+        records = torch.empty((capacity, words), dtype=torch.int32, device=device)
+        count = torch.empty(1, dtype=torch.int64, device=device)
+        out = records.data_ptr() if capacity else None
+        if find:
+            check(L.kbo_find_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, C.byref(arg), int(strands), work.data_ptr(), wb,
+                                        out, capacity, count.data_ptr(), s.cuda_stream))
+        else:
+            check(L.kbo_summary_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, float(arg), int(strands), work.data_ptr(), wb,
+                                           out, capacity, count.data_ptr(), s.cuda_stream))
+    return records, count  # (the scratch was allocated on `s`: the allocator reuses it in that stream's order)
+
+
+def find_refset_dev(concat, offsets, refset, find_opts=None, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
+    """kbo_find_refset_dev over torch tensors on the device: find_refset's records for a batch that is already there.  concat: uint8
+    (the sequences back to back); offsets: int64 or uint64 (n_seqs + 1); the set has a copy on that device (RefSet.to_device) and is
+    lds_only().  Returns (records, count): records a (capacity, 10) int32 tensor that holds the u32 words of REF_RUN, the first
+    min(count, capacity) rows written, and count an int64 tensor of one element, the number of records there are - beyond `capacity`
+    they are counted only.  Sequences of fewer than 3 bases contribute nothing.  refs_per_slab: references of a slab (None: about
+    256 MiB a slab, 0: as many as a slab may hold); it sizes the scratch.  Enqueued on `stream` (default: the current one); nothing is
+    synchronised."""
+    from . import FindOpts
+    o = find_opts if find_opts is not None else FindOpts()
+    return _refset_dev(True, concat, offsets, refset, _capi.FindOpts(o.max_error_prob, o.max_gap_len), strands, int(capacity), refs_per_slab, stream)
+
+
+def summary_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
+    """kbo_summary_refset_dev over torch tensors on the device: summary_refset's records, as find_refset_dev returns find_refset's -
+    (records, count) with records a (capacity, 9) int32 tensor that holds the u32 words of REF_SUMMARY."""
+    return _refset_dev(False, concat, offsets, refset, max_error_prob, strands, int(capacity), refs_per_slab, stream)
 
 
 def last_routes():

@@ -11,6 +11,9 @@ the contigs 50 kbp, below the 65 536 bases at which the single-index stage chang
 SUMMARY=1 times kbo_summary_refset on the same workload instead (one record per pair with a hit; the CRC is of those records) and
 checks, for the references the loop takes - or, with LOOP=0, for all of them against one kbo_find_refset(max_gap_len = 0) call that
 is not timed - that every pair's n_runs is its number of run records.
+DEV=1 adds the device-resident form on the same workload - refset.find_refset_dev, with SUMMARY=1 refset.summary_refset_dev: the batch
+is uploaded once outside the timed region, a timed call ends when its records are on the host (REFS_PER_SLAB=64 references a slab,
+DEV_CAPACITY=1048576 records of room), and its records_crc32 is printed next to the host call's.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -27,6 +30,7 @@ from kbo_amd import batch, refset  # noqa: E402
 
 REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS, SUMMARY = (int(os.environ.get(n, d)) for n, d in (
     ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3), ("SUMMARY", 0)))
+DEV, REFS_PER_SLAB, DEV_CAPACITY = (int(os.environ.get(n, d)) for n, d in (("DEV", 0), ("REFS_PER_SLAB", 64), ("DEV_CAPACITY", 1 << 20)))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -83,6 +87,34 @@ res = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1])
        "refset_build_s": round(t1 - t0, 4), "refset_to_device_s": round(t2 - t1, 4), name + "_s": round(find_s, 4),
        name + "_s_all": [round(t, 4) for t in times], name + "_gbp_per_s": round(pair_bases / find_s / 1e9, 2),
        "records": int(len(got)), "records_crc32": zlib.crc32(got.tobytes()), "routes": refset.last_routes()}
+
+if DEV:
+    d_q = torch.zeros(int(offsets[-1]) + 16, dtype=torch.uint8, device="cuda")
+    d_q[:int(offsets[-1])].copy_(torch.from_numpy(concat))
+    d_off = torch.from_numpy(offsets.astype(np.int64)).cuda()
+    torch.cuda.synchronize()
+
+    def dev_call():
+        if SUMMARY:
+            rec, count = refset.summary_refset_dev(d_q, d_off, rs, fopts.max_error_prob, strands=3, capacity=DEV_CAPACITY, refs_per_slab=REFS_PER_SLAB)
+        else:
+            rec, count = refset.find_refset_dev(d_q, d_off, rs, fopts, strands=3, capacity=DEV_CAPACITY, refs_per_slab=REFS_PER_SLAB)
+        n = int(count.item())  # (waits for the stream: the only synchronisation of the call)
+        return n, rec[:min(n, DEV_CAPACITY)].cpu().numpy()
+    dev_call()  # warm-up: code objects, the allocator's blocks
+    dev_times = []
+    for _ in range(REPEATS):
+        t = time.perf_counter()
+        n_dev, dev_rec = dev_call()
+        dev_times.append(time.perf_counter() - t)
+    dev_s = statistics.median(dev_times)
+    queryable = sum(rs.status(r) == 0 for r in range(REFS))
+    res.update({name + "_dev_s": round(dev_s, 4), name + "_dev_s_all": [round(t, 4) for t in dev_times],
+                name + "_dev_gbp_per_s": round(pair_bases / dev_s / 1e9, 2), "dev_refs_per_slab": REFS_PER_SLAB,
+                "dev_slabs": -(-queryable // REFS_PER_SLAB), "dev_records": n_dev,
+                "dev_records_crc32": zlib.crc32(np.ascontiguousarray(dev_rec).view(np.uint32).tobytes()),
+                "dev_over_host": round(dev_s / find_s, 3)})
+    res["dev_records_equal_host"] = res["dev_records_crc32"] == res["records_crc32"] and n_dev == len(got)
 
 if SUMMARY:
     mine = {(int(r), int(s), int(st)): int(n) for r, s, st, n in zip(got["ref"], got["seq"], got["strand"], got["n_runs"])}
