@@ -160,6 +160,12 @@ pub mod ffi {
         // the summary of every (reference, sequence, strand) pair of a reference set with a hit (the set: kbo_refset_build, kbo_hip.h)
         pub fn kbo_summary_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
                                   records: *mut *mut super::RefSummary, n_records: *mut u64) -> c_int;
+        // a set whose references of up to max_wide_rows rows (16 384 ..= 2^20) keep their packed form and are walked from memory; the
+        // route of reference r (-1 status, 0 LDS, 1 single-index, 2 wide); 1 when the device-resident calls take the set
+        pub fn kbo_refset_build_wide(seqs: *const *const u8, lens: *const usize, n_refs: usize, opts: *const KboBuildOpts,
+                                     max_wide_rows: usize, out: *mut *mut KboRefset) -> c_int;
+        pub fn kbo_refset_route(set: *const KboRefset, r: usize) -> c_int;
+        pub fn kbo_refset_packed_only(set: *const KboRefset) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,

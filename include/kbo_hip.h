@@ -478,7 +478,8 @@ int kbo_revcomp_packed_dev(const uint32_t *d_words, const uint64_t *d_offsets, s
  * queries all of them in one call: the query batch is uploaded once, its '-' strand is made on the device, and a kernel that keeps a
  * whole reference in a compute unit's LDS walks (reference, query chunk) pairs (kbo_amd/csrc/refset_kernels.hip).  A reference of
  * more than 16 384 rows does not fit that form; the set keeps an ordinary index handle for it and the call takes it through the
- * single-index pipeline, one such reference at a time, with the same results.
+ * single-index pipeline, one such reference at a time, with the same results (kbo_refset_build_wide, below, keeps references of up
+ * to 2^20 rows in the packed layout instead).
  * A reference without a k-mer - shorter than k, or without a run of k bases A, C, G, T - cannot be queried (kbo_find on its own
  * handle fails in random_match_threshold, derandomize.rs:134); the set still builds, kbo_refset_status says so (KBO_E_BAD_ARG, the
  * code that call returns) and the reference contributes no runs.  Whole-call errors of the build (null arguments, n_refs == 0, k
@@ -491,6 +492,28 @@ size_t kbo_refset_k(const kbo_refset_t *set);
 uint64_t kbo_refset_n_kmers(const kbo_refset_t *set, size_t r); /* 0 for r >= N */
 int kbo_refset_status(const kbo_refset_t *set, size_t r);       /* 0, or the KBO_E_* of building / querying r alone */
 int kbo_refset_to_device(kbo_refset_t *set, int device);        /* idempotent, -1 = current */
+/* The same set with references of more than 16 384 rows kept in the packed layout too.  kbo_refset_build_wide behaves as
+ * kbo_refset_build does, with one difference in routing: a reference of more than KBO_REFSET_MAX_ROWS (16 384) and at most
+ * max_wide_rows rows keeps its packed form - the same 2 bytes a row - in the set's arena and takes the WIDE route: a kernel that reads
+ * the form from memory where the LDS kernel reads it from LDS (kbo_amd/csrc/refset_wide_kernels.hip), in the same slabs as the small
+ * references.  It gets no index handle and no plan structures.  A reference of at most KBO_REFSET_MAX_ROWS rows keeps the LDS route, one of
+ * more than max_wide_rows rows the single-index route.  max_wide_rows must lie in [KBO_REFSET_MAX_ROWS, KBO_REFSET_WIDE_MAX_ROWS]
+ * (KBO_E_BAD_ARG otherwise, checked before any work); max_wide_rows == KBO_REFSET_MAX_ROWS gives exactly kbo_refset_build's set.
+ * The cap is 2^20 rows because the form is then 2 MiB, half of one XCD's 4 MiB L2: the workgroups of a reference's tasks re-read it
+ * from L2 while the query and the MS bytes stream through the other half; above it the single-index pipeline with its plan
+ * structures is the tool.  A contraction scans LCS bytes linearly, as in the LDS form: a reference that is mostly one long repeat
+ * makes the walk slow, never wrong.  That, and that the route is measured on one workload only, is why it is chosen per set and kbo_refset_build
+ * does not take it.  Results do not depend on the route: fields, order, '-' strand coordinates and the thresholds from each
+ * reference's own n_kmers are the same. */
+#define KBO_REFSET_WIDE_MAX_ROWS (1u << 20)
+#define KBO_REFSET_ROUTE_NONE (-1)   /* the reference has a status */
+#define KBO_REFSET_ROUTE_LDS 0
+#define KBO_REFSET_ROUTE_INDEX 1     /* the single-index pipeline */
+#define KBO_REFSET_ROUTE_WIDE 2      /* packed form, walked from memory */
+int kbo_refset_build_wide(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, size_t max_wide_rows,
+                          kbo_refset_t **out);
+int kbo_refset_route(const kbo_refset_t *set, size_t r);   /* KBO_REFSET_ROUTE_*; KBO_E_BAD_ARG for r >= N or a null set */
+int kbo_refset_packed_only(const kbo_refset_t *set);       /* 1: no reference takes the single-index route */
 /* The records with (ref = r, seq = s, strand) are, in order, exactly the runs kbo_find returns for sequence s - strand
  * KBO_STRAND_REV: for its reverse complement, in the coordinates of the reverse-complemented sequence as for kbo_find_batch_strands -
  * against reference r's own index: derandomised with the threshold of that index's n_kmers and opts->max_error_prob, run lengths
@@ -529,7 +552,7 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
  * device-to-host copy, no allocation: all scratch is d_work, and the one host-to-device upload of a call is the references' thresholds
  * (n_refs uint32_t - only the host can compute them, from n_kmers and max_error_prob).  Launches: 6 a call (7 with the '-' strand, and
  * a device-to-device copy of the batch when both strands are asked for) + 34 a slab (find) or 22 a slab (summary), whatever the batch
- * and the set hold.
+ * holds; one more for a slab that holds both LDS and wide references (a walk kernel each).
  * Inputs: the set has a copy on the current device (kbo_refset_to_device; KBO_E_BAD_ARG when it has none); d_concat holds
  * total_bases + 16 readable bytes and is 16-byte aligned; d_offsets holds n_seqs + 1 uint64_t on the device, 8-byte aligned, ascending
  * from 0 to total_bases, which the caller knows: nothing about the batch is read back, so nothing about it is checked.
@@ -540,8 +563,11 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
  * `capacity`, and the output pointer may be NULL when capacity == 0.
  * A sequence of fewer than 3 bases, an empty one included, contributes no record and disturbs no other pair: the device form cannot
  * refuse the batch with KBO_E_LEN_LE_2 as the host form does, because it does not know the lengths.  A reference with a status
- * contributes nothing, as there.  A set that holds a reference of the single-index route (more than KBO_REFSET_MAX_ROWS rows) is refused
- * with KBO_E_UNSUPPORTED - that route is a host pipeline; kbo_refset_lds_only() is 1 when the set holds none, else 0.
+ * contributes nothing, as there.  A set that holds a reference of the single-index route (more than KBO_REFSET_MAX_ROWS rows in a set of
+ * kbo_refset_build, more than max_wide_rows in one of kbo_refset_build_wide) is refused with KBO_E_UNSUPPORTED - that route is a host
+ * pipeline; kbo_refset_packed_only() is 1 when the set holds none, else 0, and the *_work_bytes of a refused set are 0.  Wide references
+ * lie in the slabs next to LDS ones and need no scratch of their own: the figures do not depend on the routes.  kbo_refset_lds_only()
+ * is 1 when every reference that can be queried takes the LDS route.
  * Slabs: a slab is a range of consecutive queryable references against the WHOLE batch on the strands asked for, refs x n_strands x
  * total_bases bytes, planned on the device (kbo_amd/csrc/refset_plan_kernels.hip).  *_work_bytes(..., refs_per_slab) is the exact figure
  * for slabs of that many references - 0: as many as one slab may hold (all queryable ones unless 2^32 - 16 bytes or 2^28 pairs come

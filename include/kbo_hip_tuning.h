@@ -210,6 +210,17 @@ int kbo_set_refset_record_capacity(size_t records);
 /* test hook: what the calling thread's last kbo_find_refset did: out[0] references walked by the LDS kernel, out[1] references taken
  * through the single-index pipeline, out[2] (reference, sequence, strand) pairs walked over both routes, out[3] slabs */
 int kbo_refset_last_routes(uint64_t out[4]);
+/* test hook: the wide route (kbo_refset_build_wide) in the calling thread's last kbo_find_refset / kbo_summary_refset: out[0] references
+ * walked by the wide kernel, out[1] the tasks (workgroups) it was launched with, over all slabs.  out[0] of kbo_refset_last_routes
+ * counts the references of the LDS kernel only; its out[2], the pairs, includes the wide references' */
+int kbo_refset_last_wide(uint64_t out[2]);
+/* test hook: the packed form of reference r (kernels.hpp: rank blocks, LCS bytes with the sentinel), *n_bytes of it, a multiple of
+ * 16; out == NULL asks for the size only.  KBO_E_BAD_ARG for a reference with a status or of the single-index route */
+int kbo_refset_form(const kbo_refset_t *set, size_t r, uint8_t *out, size_t *n_bytes);
+/* test hook: the matching statistics of seq (len bytes, any values) against reference r, one depth a base, made on the CPU by the
+ * step the wide kernel runs (kbo_amd/csrc/refset_step.hpp) over the set's host arena, unchunked.  No HIP call; not a fallback.
+ * KBO_E_BAD_ARG as kbo_refset_form */
+int kbo_refset_ms_host(const kbo_refset_t *set, size_t r, const uint8_t *seq, size_t len, uint8_t *ms_out);
 
 /* ------------------------------------------------------------------ kbo_derand_translate_seq_dev */
 /* positions of a chunk and of a group (64 chunks) of derand_seq_kernels.hip; neither spans two sequences.  A sequence of more than

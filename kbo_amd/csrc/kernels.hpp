@@ -562,7 +562,7 @@ struct RefsetDesc { // one per reference of the set, on the device
     uint32_t n_sets;
     uint32_t C[4];
     int32_t status;   // 0, or why the reference cannot be queried (then it has no units)
-    uint32_t route;   // 0: this kernel, 1: an ordinary index of its own
+    uint32_t route;   // 0: this kernel, 1: an ordinary index of its own, 2: the same form, walked from memory (refset_wide_kernels.hip)
     uint64_t n_kmers;
 };
 struct RefsetWalkArgs {
@@ -575,7 +575,13 @@ struct RefsetWalkArgs {
     const uint8_t *q;    // the query batch, both strands
     uint8_t *ms;         // the slab: one byte per (pair, base)
 };
-hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units /* the largest refset_units() among the tasks' references */, hipStream_t stream);
+// (a task whose reference has another route than kRefsetRouteLds is skipped: the task list of a slab is shared by both walks)
+hipError_t launch_refset_walk(const RefsetWalkArgs &a, uint32_t lds_units /* the largest refset_units() among the tasks' LDS references */, hipStream_t stream);
+// ---- the same walk with the form read from the arena (refset_wide_kernels.hip): references of more than kRefsetMaxRows and at most
+// kRefsetWideMaxRows rows (a form of 2 MiB, half of an XCD's L2).  It takes the tasks of the references of kRefsetRouteWide and skips the rest
+constexpr uint32_t kRefsetWideMaxRows = 1u << 20;
+constexpr uint32_t kRefsetRouteLds = 0, kRefsetRouteIndex = 1, kRefsetRouteWide = 2; // RefsetDesc::route
+hipError_t launch_refset_wide_walk(const RefsetWalkArgs &a, hipStream_t stream);
 // kbo_summary_refset: of the n_pairs extents of a slab (six u32 a pair, launch_derand_summary_seq's) those with n_runs > 0, in pair
 // order, as records of seven u32 { pair, extent } at d_kept (room for n_pairs of them) and their number at d_total;
 // d_scratch: chunk_items_scratch_words(n_pairs) u32.  Nothing read back.

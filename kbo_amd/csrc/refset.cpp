@@ -6,6 +6,7 @@
 // derandomize / translate stage and keeps the pairs with a hit on the device: no characters, no run-length stage.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
+#include "refset_step.hpp"
 
 #include <algorithm>
 #include <thread>
@@ -13,10 +14,14 @@
 using namespace kbo_host;
 
 static_assert(kbo::kRefsetChunk == KBO_REFSET_CHUNK && kbo::kRefsetMaxRows == KBO_REFSET_MAX_ROWS, "kbo_hip_tuning.h states the kernel's constants");
+static_assert(kbo::kRefsetWideMaxRows == KBO_REFSET_WIDE_MAX_ROWS && kbo::kRefsetRouteLds == KBO_REFSET_ROUTE_LDS &&
+                  kbo::kRefsetRouteIndex == KBO_REFSET_ROUTE_INDEX && kbo::kRefsetRouteWide == KBO_REFSET_ROUTE_WIDE,
+              "kbo_hip.h states the wide walk's constants");
 
 namespace {
 std::atomic<size_t> g_record_capacity{1u << 16};
 thread_local uint64_t t_routes[4] = {0, 0, 0, 0};
+thread_local uint64_t t_wide[2] = {0, 0}; // references walked by the wide kernel, the tasks it was launched with
 
 struct DevSet {
     DevBuf arena, descs;
@@ -55,8 +60,8 @@ struct StreamScope {
 struct kbo_refset {
     uint32_t k = 0;
     std::vector<kbo::RefsetDesc> descs;
-    std::vector<uint32_t> arena;                  // the LDS forms back to back, four words a unit
-    std::vector<std::unique_ptr<kbo_index>> own;  // per reference: its ordinary index when it does not fit the LDS form, else null
+    std::vector<uint32_t> arena;                  // the packed forms (LDS and wide references) back to back, four words a unit
+    std::vector<std::unique_ptr<kbo_index>> own;  // per reference: its ordinary index when it takes the single-index route, else null
     std::mutex mu;
     std::map<int, DevSet *> dev;
     ~kbo_refset()
@@ -67,7 +72,7 @@ struct kbo_refset {
 
 namespace {
 
-// the LDS form of an index (kernels.hpp), appended to `arena`
+// the packed form of an index of any number of rows below 2^32 - 32 (kernels.hpp "LDS form"), appended to `arena`
 void append_lds_form(const kbo::HostIndex &h, std::vector<uint32_t> &arena)
 {
     const uint32_t n = (uint32_t)h.n_sets, nb = n / 32u + 1u;
@@ -109,13 +114,15 @@ struct SlabPlan {
     std::vector<uint32_t> ref, seq, strand, thr; // per pair; thr: its reference's threshold
     std::vector<uint64_t> off;              // per pair + 1: its first byte in the slab
     std::vector<uint32_t> items, tasks;     // four words a record (kernels.hpp RefsetWalkArgs)
-    uint32_t longest = 0, lds_units = 0;
+    uint32_t longest = 0, lds_units = 0; // lds_units: the largest form among the slab's LDS references
+    bool has_lds = false, has_wide = false; // the kinds of reference the slab's tasks name
     void clear()
     {
         ref.clear(); seq.clear(); strand.clear(); thr.clear(); items.clear(); tasks.clear();
         off.assign(1, 0);
         longest = 0;
         lds_units = 0;
+        has_lds = has_wide = false;
     }
     size_t pairs() const { return ref.size(); }
     uint64_t bytes() const { return off.back(); }
@@ -125,13 +132,13 @@ struct SlabPlan {
 struct SlabWalker {
     kbo_refset *set;
     const uint64_t *offsets;
-    uint32_t k, chunk, min_thr; // min_thr: the smallest threshold of the references that take the LDS kernel
+    uint32_t k, chunk, min_thr; // min_thr: the smallest threshold of the references that take a walk of the packed form
     uint64_t rev_base; // where the '-' strand of the batch begins in d_q
     hipStream_t st;
     DevSet *ds;
     DevBuf d_q, d_off, d_ms, d_poff, d_pthr, d_items, d_tasks, d_derand;
     std::vector<uint64_t> ref_begin, ref_end; // where every reference's records lie in the call's list
-    std::vector<uint8_t> walked;              // per reference: a launch of the LDS kernel has held it (the route counters)
+    std::vector<uint8_t> walked;              // per reference: a launch of its walk kernel has held it (the route counters)
 
     void add_pair(SlabPlan &P, uint32_t r, uint32_t s, uint32_t strand, uint32_t threshold)
     {
@@ -154,7 +161,11 @@ struct SlabWalker {
         P.thr.push_back(threshold);
         P.off.push_back(o0 + len);
         P.longest = std::max<uint32_t>(P.longest, (uint32_t)len);
-        P.lds_units = std::max(P.lds_units, kbo::refset_units(set->descs[r].n_sets));
+        if (set->descs[r].route == kbo::kRefsetRouteWide) P.has_wide = true;
+        else {
+            P.has_lds = true;
+            P.lds_units = std::max(P.lds_units, kbo::refset_units(set->descs[r].n_sets));
+        }
     }
 
     // the slab's pairs, thresholds and tasks to the device, and the walk: the MS bytes of every pair in d_ms
@@ -180,11 +191,16 @@ struct SlabWalker {
         a.k = k;
         a.q = d_q.as<uint8_t>();
         a.ms = d_ms.as<uint8_t>();
-        HIP_OK(kbo::launch_refset_walk(a, P.lds_units, st));
+        if (P.has_lds) HIP_OK(kbo::launch_refset_walk(a, P.lds_units, st)); // (each kernel skips the other's tasks)
+        if (P.has_wide) {
+            HIP_OK(kbo::launch_refset_wide_walk(a, st));
+            t_wide[1] += a.n_tasks;
+        }
         for (size_t p = 0; p < np; p++)
             if (!walked[P.ref[p]]) {
                 walked[P.ref[p]] = 1;
-                t_routes[0]++;
+                if (set->descs[P.ref[p]].route == kbo::kRefsetRouteWide) t_wide[0]++;
+                else t_routes[0]++;
             }
         t_routes[2] += np;
     }
@@ -335,7 +351,7 @@ void upload_batch(SlabWalker &F, kbo_refset *set, const uint8_t *concat, const u
         HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
 }
 
-// the references of the LDS kernel: every pair carries its reference's threshold, so a slab is cut by the budget alone
+// the references of the packed form, LDS and wide: every pair carries its reference's threshold, so a slab is cut by the budget alone
 template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, size_t n_seqs, int strands)
 {
     const kbo_refset *set = f.set;
@@ -343,11 +359,11 @@ template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, siz
     const uint64_t budget = slab_bytes_for(nullptr);
     f.min_thr = set->k;
     for (size_t r = 0; r < n_refs; r++)
-        if (!set->descs[r].status && !set->descs[r].route) f.min_thr = std::min(f.min_thr, thr[r]);
+        if (!set->descs[r].status && set->descs[r].route != kbo::kRefsetRouteIndex) f.min_thr = std::min(f.min_thr, thr[r]);
     SlabPlan P;
     P.clear();
     for (size_t r = 0; r < n_refs; r++) {
-        if (set->descs[r].status || set->descs[r].route) continue;
+        if (set->descs[r].status || set->descs[r].route == kbo::kRefsetRouteIndex) continue;
         for (size_t s = 0; s < n_seqs; s++)
             for (uint32_t strand = 1; strand <= 2; strand++) {
                 if (!(strands & strand)) continue;
@@ -417,6 +433,8 @@ DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int stran
 {
     DevForm F;
     if (!set || n_seqs == 0 || strands < 1 || strands > 3) return F;
+    for (const kbo::RefsetDesc &d : set->descs)
+        if (!d.status && d.route == kbo::kRefsetRouteIndex) return F; // (the call refuses the set)
     const uint64_t ns = strands == 3 ? 2 : 1;
     if (n_seqs * ns >= (1ull << 28) || n_seqs >= (1ull << 28) || ns * total >= (1ull << 32) - 16) return F;
     if (ns * kbo::refplan::chunks_bound(total, n_seqs, kbo::refplan::chunk_of(set->k)) > 0xFFFFFF00ull) return F;
@@ -497,7 +515,8 @@ void run_dev_form(const DevCall &c, bool find)
     kbo_refset *set = c.set;
     const std::vector<uint32_t> thr = refset_thresholds(set, c.max_error_prob);
     for (const kbo::RefsetDesc &d : set->descs)
-        KBO_REQUIRE(d.status || !d.route, KBO_E_UNSUPPORTED, "a reference of more than KBO_REFSET_MAX_ROWS rows: the host calls take it (kbo_refset_lds_only)");
+        KBO_REQUIRE(d.status || d.route != kbo::kRefsetRouteIndex, KBO_E_UNSUPPORTED,
+                    "a reference of the single-index route: the host calls take it (kbo_refset_packed_only)");
     DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, 1, find);
     KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a slab of one reference of 2^32 - 16 bytes or more, or 2^28 (sequence, strand) pairs or more");
     KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes too small for one reference a slab");
@@ -543,8 +562,16 @@ void run_dev_form(const DevCall &c, bool find)
         const uint32_t refs = (uint32_t)std::min<size_t>(F.refs, qrefs.size() - q0);
         const uint32_t np = refs * (uint32_t)c.n_seqs * F.g.n_strands;
         const uint64_t bytes = kbo::refplan::slab_bytes(F.g, refs);
-        uint32_t lds_units = 0;
-        for (uint32_t j = 0; j < refs; j++) lds_units = std::max(lds_units, kbo::refset_units(set->descs[qrefs[q0 + j]].n_sets));
+        uint32_t lds_units = 0; // the kinds of reference the slab holds: only their kernels are launched
+        bool has_lds = false, has_wide = false;
+        for (uint32_t j = 0; j < refs; j++) {
+            const kbo::RefsetDesc &d = set->descs[qrefs[q0 + j]];
+            if (d.route == kbo::kRefsetRouteWide) has_wide = true;
+            else {
+                has_lds = true;
+                lds_units = std::max(lds_units, kbo::refset_units(d.n_sets));
+            }
+        }
         HIP_OK(kbo::launch_refset_plan_slab(P, (uint32_t)q0, refs, poff, at(F.pthr), find ? w + F.chars : nullptr,
                                             reinterpret_cast<uint4 *>(w + F.items), reinterpret_cast<uint4 *>(w + F.tasks), st));
         kbo::RefsetWalkArgs a;
@@ -556,7 +583,8 @@ void run_dev_form(const DevCall &c, bool find)
         a.k = set->k;
         a.q = q;
         a.ms = ms;
-        HIP_OK(kbo::launch_refset_walk(a, lds_units, st));
+        if (has_lds) HIP_OK(kbo::launch_refset_walk(a, lds_units, st));
+        if (has_wide) HIP_OK(kbo::launch_refset_wide_walk(a, st));
         if (find) {
             HIP_OK(kbo::launch_derand_translate_seq(ms, poff, np, bytes, set->k, at(F.pthr), min_thr, nullptr, w + F.chars, w + F.derand, st));
             HIP_OK(kbo::launch_rle_seg_count(w + F.chars, poff, np, bytes, c.gap, 0u, w + F.stage, at(F.first), st));
@@ -579,9 +607,17 @@ extern "C" {
 
 int kbo_refset_build(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, kbo_refset_t **out)
 {
+    return kbo_refset_build_wide(seqs, lens, n_refs, opts, KBO_REFSET_MAX_ROWS, out);
+}
+
+int kbo_refset_build_wide(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, size_t max_wide_rows,
+                          kbo_refset_t **out)
+{
     return guarded([&] {
         KBO_REQUIRE(out, KBO_E_BAD_ARG, "null out");
         *out = nullptr;
+        KBO_REQUIRE(max_wide_rows >= KBO_REFSET_MAX_ROWS && max_wide_rows <= KBO_REFSET_WIDE_MAX_ROWS, KBO_E_BAD_ARG,
+                    "max_wide_rows in KBO_REFSET_MAX_ROWS .. KBO_REFSET_WIDE_MAX_ROWS");
         KBO_REQUIRE(seqs && lens && n_refs > 0, KBO_E_BAD_ARG, "assert!(!slices.is_empty()) (index.rs:60)");
         KBO_REQUIRE(n_refs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 references");
         for (size_t r = 0; r < n_refs; r++) KBO_REQUIRE(seqs[r] || lens[r] == 0, KBO_E_BAD_ARG, "null reference sequence");
@@ -613,10 +649,13 @@ int kbo_refset_build(const uint8_t *const *seqs, const size_t *lens, size_t n_re
                 d.n_kmers = h.n_kmers;
                 for (int c = 0; c < 4; c++) d.C[c] = (uint32_t)h.C[c];
                 if (h.n_kmers == 0) d.status = KBO_E_BAD_ARG; // n_kmers > 0 (derandomize.rs:134)
-                else if (h.n_sets > kbo::kRefsetMaxRows) {
-                    d.route = 1;
+                else if (h.n_sets > max_wide_rows) {
+                    d.route = kbo::kRefsetRouteIndex;
                     set->own[r] = std::move(idx);
-                } else append_lds_form(h, forms[r]);
+                } else { // its packed form in the arena, and no index of its own: no plan structures
+                    d.route = h.n_sets > kbo::kRefsetMaxRows ? kbo::kRefsetRouteWide : kbo::kRefsetRouteLds;
+                    append_lds_form(h, forms[r]);
+                }
             }
         };
         std::vector<std::thread> team;
@@ -659,6 +698,70 @@ int kbo_set_refset_record_capacity(size_t records)
     return KBO_OK;
 }
 
+int kbo_refset_last_wide(uint64_t out[2])
+{
+    if (!out) return KBO_E_BAD_ARG;
+    std::copy(t_wide, t_wide + 2, out);
+    return KBO_OK;
+}
+
+int kbo_refset_route(const kbo_refset_t *set, size_t r)
+{
+    if (!set || r >= set->descs.size()) return KBO_E_BAD_ARG;
+    return set->descs[r].status ? KBO_REFSET_ROUTE_NONE : (int)set->descs[r].route;
+}
+
+int kbo_refset_packed_only(const kbo_refset_t *set)
+{
+    if (!set) return 0;
+    for (const kbo::RefsetDesc &d : set->descs)
+        if (!d.status && d.route == kbo::kRefsetRouteIndex) return 0;
+    return 1;
+}
+
+namespace {
+struct HostForm { // refset_step.hpp's accessor over the host arena
+    const uint32_t *rank_;
+    const uint8_t *lcs_;
+    kbo::refstep::Entry rank(uint32_t block, uint32_t c) const
+    {
+        const uint32_t *e = rank_ + ((size_t)block * 4u + c) * 2u;
+        return kbo::refstep::Entry{e[0], e[1]};
+    }
+    uint32_t lcs(uint32_t i) const { return lcs_[i]; }
+};
+const kbo::RefsetDesc *packed_desc(const kbo_refset_t *set, size_t r)
+{
+    if (!set || r >= set->descs.size()) return nullptr;
+    const kbo::RefsetDesc &d = set->descs[r];
+    return d.status || d.route == kbo::kRefsetRouteIndex ? nullptr : &d;
+}
+} // namespace
+
+int kbo_refset_form(const kbo_refset_t *set, size_t r, uint8_t *out, size_t *n_bytes)
+{
+    const kbo::RefsetDesc *d = packed_desc(set, r);
+    if (!d || !n_bytes) return KBO_E_BAD_ARG;
+    *n_bytes = (size_t)kbo::refset_units(d->n_sets) * 16u;
+    if (out) std::memcpy(out, set->arena.data() + (size_t)d->off * 4u, *n_bytes);
+    return KBO_OK;
+}
+
+int kbo_refset_ms_host(const kbo_refset_t *set, size_t r, const uint8_t *seq, size_t len, uint8_t *ms_out)
+{
+    const kbo::RefsetDesc *d = packed_desc(set, r);
+    if (!d || ((!seq || !ms_out) && len)) return KBO_E_BAD_ARG;
+    const uint32_t n = d->n_sets;
+    const uint32_t *form = set->arena.data() + (size_t)d->off * 4u;
+    const HostForm x{form, reinterpret_cast<const uint8_t *>(form + 4u * (size_t)kbo::refset_rank_units(n))};
+    uint32_t lo = 0, hi = n, depth = 0;
+    for (size_t i = 0; i < len; i++) {
+        kbo::refstep::step(x, n, set->k, seq[i], lo, hi, depth);
+        ms_out[i] = (uint8_t)depth;
+    }
+    return KBO_OK;
+}
+
 int kbo_refset_last_routes(uint64_t out[4])
 {
     if (!out) return KBO_E_BAD_ARG;
@@ -680,6 +783,7 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
         const std::vector<uint32_t> thr = refset_thresholds(set, o.max_error_prob);
         const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
         std::fill(t_routes, t_routes + 4, 0);
+        std::fill(t_wide, t_wide + 2, 0);
 
         const size_t n_refs = set->descs.size();
         const uint32_t n_strands = strands == 3 ? 2 : 1;
@@ -689,10 +793,10 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
         upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
         run_slabs(F, thr, n_seqs, strands);
 
-        // the references that do not fit the LDS form: their own index through the single-index pipeline, one at a time
+        // the references of the single-index route: their own index through that pipeline, one at a time
         std::vector<uint64_t> rle_off(2 * n_seqs + 1);
         for (size_t r = 0; r < n_refs; r++) {
-            if (set->descs[r].status || !set->descs[r].route) continue;
+            if (set->descs[r].status || set->descs[r].route != kbo::kRefsetRouteIndex) continue;
             RleSink<kbo_rle> sink;
             sink.max_gap_len = o.max_gap_len;
             sink.rle_offsets = rle_off.data();
@@ -729,6 +833,7 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
         const std::vector<uint32_t> thr = refset_thresholds(set, max_error_prob);
         const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
         std::fill(t_routes, t_routes + 4, 0);
+        std::fill(t_wide, t_wide + 2, 0);
 
         const size_t n_refs = set->descs.size();
         const uint32_t n_strands = strands == 3 ? 2 : 1;
@@ -737,10 +842,10 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
         upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
         run_slabs(F, thr, n_seqs, strands);
 
-        // the references that do not fit the LDS form: the characters of the single-index pipeline, counted here
+        // the references of the single-index route: the characters of that pipeline, counted here
         std::vector<uint8_t> fwd, rev;
         for (size_t r = 0; r < n_refs; r++) {
-            if (set->descs[r].status || !set->descs[r].route) continue;
+            if (set->descs[r].status || set->descs[r].route != kbo::kRefsetRouteIndex) continue;
             if (strands & KBO_STRAND_FWD) fwd.resize(total);
             if (strands & KBO_STRAND_REV) rev.resize(total);
             matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, max_error_prob, false, fwd.data(), nullptr, strands, rev.data());
@@ -767,7 +872,7 @@ int kbo_refset_lds_only(const kbo_refset_t *set)
 {
     if (!set) return 0;
     for (const kbo::RefsetDesc &d : set->descs)
-        if (!d.status && d.route) return 0;
+        if (!d.status && d.route != kbo::kRefsetRouteLds) return 0;
     return 1;
 }
 

@@ -11,105 +11,23 @@
 // The scans are linear in the LCS bytes: contracting to level m passes about n / 4^m rows and happens when a string of m + 2
 // bases is absent from the reference, which for the levels that are wide is rare.  Rows are random from one base to the next, so
 // the lanes' LDS addresses are: bank conflicts are those of 64 random addresses and no layout avoids them.
-#include "device_util.hpp"
+#include "refset_walk.hpp"
 
 namespace kbo {
 namespace {
-
-struct RefsetLds {
-    const uint2 *rank;
-    const uint8_t *lcs;
-    uint32_t n, k;
-};
-
-__device__ __forceinline__ uint32_t refset_rank(const RefsetLds &x, uint32_t c, uint32_t i)
-{
-    const uint2 e = x.rank[(i >> 5) * 4u + c];
-    return e.x + __popc(e.y & ((1u << (i & 31u)) - 1u));
-}
-
-// one base: the interval [l, r) and depth d of the longest suffix of the bases so far that is a suffix of a row
-__device__ __forceinline__ void refset_step(const RefsetLds &x, uint32_t ch, uint32_t &l, uint32_t &r, uint32_t &d)
-{
-    const uint32_t c = decode_base(ch);
-    if (c > 3u) { // no row continues with a byte that is no base: every level fails
-        l = 0;
-        r = x.n;
-        d = 0;
-        return;
-    }
-    for (;;) {
-        const uint32_t nl = refset_rank(x, c, l), nr = refset_rank(x, c, r);
-        if (nl < nr) {
-            l = nl;
-            r = nr;
-            d = min(d + 1u, x.k);
-            return;
-        }
-        if (d == 0) return;
-        const uint32_t m = min(max((uint32_t)x.lcs[l], (uint32_t)x.lcs[r]), d - 1u); // (LCS[0] = LCS[n] = 0)
-        if (m == 0) {
-            l = 0;
-            r = x.n;
-        } else {
-            while (x.lcs[l] >= m) l--;
-            while (x.lcs[r] >= m) r++;
-        }
-        d = m;
-    }
-}
 
 __global__ __launch_bounds__(kRefsetThreads) void refset_walk_kernel(RefsetWalkArgs a)
 {
     extern __shared__ uint4 smem[];
     const uint4 task = a.tasks[blockIdx.x];
     const RefsetDesc desc = a.descs[task.x];
+    if (desc.route != kRefsetRouteLds) return; // (the whole workgroup, before anything is staged: refset_wide_kernels.hip has this task)
     const uint32_t n = desc.n_sets, units = refset_units(n);
     const uint4 *src = a.arena + desc.off;
     for (uint32_t i = threadIdx.x; i < units; i += kRefsetThreads) smem[i] = src[i];
     __syncthreads();
     if (threadIdx.x >= task.z) return;
-    RefsetLds x;
-    x.rank = reinterpret_cast<const uint2 *>(smem);
-    x.lcs = reinterpret_cast<const uint8_t *>(smem + refset_rank_units(n));
-    x.n = n;
-    x.k = a.k;
-
-    const uint4 item = a.items[task.y + threadIdx.x];
-    const uint32_t len = item.z & 0xFFFFu, warm = item.z >> 16;
-    const uint8_t *q = a.q + item.x;
-    uint32_t l = 0, r = n, d = 0;
-    for (uint32_t p = 0; p < warm; p += 16u) { // k - 1 bases in front of the chunk: state only
-        const uint4 v = ld16u(q, p);
-        uint64_t lo = (uint64_t)v.x | (uint64_t)v.y << 32, hi = (uint64_t)v.z | (uint64_t)v.w << 32;
-        const uint32_t nb = min(16u, warm - p);
-        for (uint32_t j = 0; j < nb; j++) {
-            refset_step(x, (uint32_t)lo & 0xFFu, l, r, d);
-            lo = lo >> 8 | hi << 56;
-            hi >>= 8;
-        }
-    }
-    uint8_t *out = a.ms + item.y;
-    for (uint32_t p = warm; p < len; p += 16u) {
-        const uint4 v = ld16u(q, p);
-        uint64_t lo = (uint64_t)v.x | (uint64_t)v.y << 32, hi = (uint64_t)v.z | (uint64_t)v.w << 32;
-        uint64_t olo = 0, ohi = 0; // the depths enter at the top byte and move down
-        const uint32_t nb = min(16u, len - p);
-        for (uint32_t j = 0; j < nb; j++) {
-            refset_step(x, (uint32_t)lo & 0xFFu, l, r, d);
-            lo = lo >> 8 | hi << 56;
-            hi >>= 8;
-            olo = olo >> 8 | ohi << 56;
-            ohi = ohi >> 8 | (uint64_t)d << 56;
-        }
-        for (uint32_t j = nb; j < 16u; j++) {
-            olo = olo >> 8 | ohi << 56;
-            ohi >>= 8;
-        }
-        const uint4 o = make_uint4((uint32_t)olo, (uint32_t)(olo >> 32), (uint32_t)ohi, (uint32_t)(ohi >> 32));
-        if (nb == 16u) st16u(out, p - warm, o);
-        else st_partial(out + (p - warm), o, nb);
-    }
+    refset_walk_chunk(PackedForm(smem, n), n, a.k, a.items[task.y + threadIdx.x], a.q, a.ms);
 }
 
 // kbo_summary_refset: the pairs of a slab with a hit (n_runs > 0), kept in pair order.  ext: six words a pair (kbo_aln_extent)

@@ -8,6 +8,9 @@ from ._capi import check, lib
 from .index import _u8
 
 STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
+# kbo_refset_route: the reference has a status / the LDS kernel / the single-index pipeline / the packed form walked from memory
+ROUTE_NONE, ROUTE_LDS, ROUTE_INDEX, ROUTE_WIDE = -1, 0, 1, 2
+MAX_ROWS, WIDE_MAX_ROWS = 16384, 1 << 20  # KBO_REFSET_MAX_ROWS, KBO_REFSET_WIDE_MAX_ROWS
 
 # kbo_ref_run (40 bytes): which (reference, sequence, strand) a run belongs to + the fields of format::RLE (format.rs:18-33)
 REF_RUN = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32), ("start", np.uint32), ("end", np.uint32),
@@ -27,7 +30,10 @@ class RefSet:
         self._h = handle
 
     @classmethod
-    def build(cls, seqs, build_opts=None):
+    def build(cls, seqs, build_opts=None, wide_rows=None):
+        """wide_rows: None - kbo_refset_build: a reference of more than MAX_ROWS rows takes the single-index route; a number in
+        MAX_ROWS .. WIDE_MAX_ROWS - kbo_refset_build_wide: references of up to that many rows keep their packed form in the set and
+        take the wide route, in the same slabs as the small ones, and a set without a larger one can go to find_refset_dev"""
         from . import BuildOpts
         o = build_opts if build_opts is not None else BuildOpts()
         raw = [bytes(_u8(s)) for s in seqs]
@@ -35,7 +41,10 @@ class RefSet:
         lens = (C.c_size_t * max(1, len(raw)))(*[len(s) for s in raw])
         co = o._to_c()
         h = C.c_void_p()
-        check(lib().kbo_refset_build(arr, lens, len(raw), C.byref(co), C.byref(h)))
+        if wide_rows is None:
+            check(lib().kbo_refset_build(arr, lens, len(raw), C.byref(co), C.byref(h)))
+        else:
+            check(lib().kbo_refset_build_wide(arr, lens, len(raw), C.byref(co), int(wide_rows), C.byref(h)))
         return cls(h)
 
     def __len__(self):
@@ -56,8 +65,34 @@ class RefSet:
         return self
 
     def lds_only(self):
-        """True when no reference takes the single-index route: what find_refset_dev / summary_refset_dev ask of a set"""
+        """True when every reference that can be queried takes the LDS route"""
         return bool(lib().kbo_refset_lds_only(self._h))
+
+    def packed_only(self):
+        """True when no reference takes the single-index route: what find_refset_dev / summary_refset_dev ask of a set"""
+        return bool(lib().kbo_refset_packed_only(self._h))
+
+    def route(self, r):
+        """ROUTE_LDS, ROUTE_INDEX or ROUTE_WIDE; ROUTE_NONE for a reference with a status"""
+        v = lib().kbo_refset_route(self._h, r)
+        if v < ROUTE_NONE:
+            check(v)
+        return v
+
+    def form(self, r):
+        """test hook: the packed form of an LDS or wide reference, as bytes in a uint8 array"""
+        n = C.c_size_t()
+        check(lib().kbo_refset_form(self._h, r, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        check(lib().kbo_refset_form(self._h, r, out.ctypes.data, C.byref(n)))
+        return out
+
+    def ms_host(self, r, seq):
+        """test hook: the matching statistics of seq against reference r, by the wide kernel's step on the CPU"""
+        q = np.ascontiguousarray(_u8(seq))
+        out = np.zeros(len(q), dtype=np.uint8)
+        check(lib().kbo_refset_ms_host(self._h, r, q.ctypes.data, len(q), out.ctypes.data))
+        return out
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -144,7 +179,7 @@ def _refset_dev(find, concat, offsets, refset, arg, strands, capacity, refs_per_
 def find_refset_dev(concat, offsets, refset, find_opts=None, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
     """kbo_find_refset_dev over torch tensors on the device: find_refset's records for a batch that is already there.  concat: uint8
     (the sequences back to back); offsets: int64 or uint64 (n_seqs + 1); the set has a copy on that device (RefSet.to_device) and is
-    lds_only().  Returns (records, count): records a (capacity, 10) int32 tensor that holds the u32 words of REF_RUN, the first
+    packed_only(): LDS and wide references (RefSet.build(wide_rows=...)), none of the single-index route.  Returns (records, count): records a (capacity, 10) int32 tensor that holds the u32 words of REF_RUN, the first
     min(count, capacity) rows written, and count an int64 tensor of one element, the number of records there are - beyond `capacity`
     they are counted only.  Sequences of fewer than 3 bases contribute nothing.  refs_per_slab: references of a slab (None: about
     256 MiB a slab, 0: as many as a slab may hold); it sizes the scratch.  Enqueued on `stream` (default: the current one); nothing is
@@ -156,8 +191,16 @@ def find_refset_dev(concat, offsets, refset, find_opts=None, strands=STRAND_BOTH
 
 def summary_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
     """kbo_summary_refset_dev over torch tensors on the device: summary_refset's records, as find_refset_dev returns find_refset's -
-    (records, count) with records a (capacity, 9) int32 tensor that holds the u32 words of REF_SUMMARY."""
+    (records, count) with records a (capacity, 9) int32 tensor that holds the u32 words of REF_SUMMARY.  The set is packed_only(), as
+    there."""
     return _refset_dev(False, concat, offsets, refset, max_error_prob, strands, int(capacity), refs_per_slab, stream)
+
+
+def last_wide():
+    """(references walked by the wide kernel, tasks it was launched with) of the calling thread's last find_refset or summary_refset"""
+    out = (C.c_uint64 * 2)()
+    check(lib().kbo_refset_last_wide(out))
+    return tuple(int(v) for v in out)
 
 
 def last_routes():

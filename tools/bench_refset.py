@@ -14,6 +14,11 @@ is not timed - that every pair's n_runs is its number of run records.
 DEV=1 adds the device-resident form on the same workload - refset.find_refset_dev, with SUMMARY=1 refset.summary_refset_dev: the batch
 is uploaded once outside the timed region, a timed call ends when its records are on the host (REFS_PER_SLAB=64 references a slab,
 DEV_CAPACITY=1048576 records of room), and its records_crc32 is printed next to the host call's.
+WIDE=1 is a leg of its own: WIDE_REFS=300 references of WIDE_BP=50000 bases - plasmid-sized, over KBO_REFSET_MAX_ROWS rows each - built
+twice in one process, by kbo_refset_build (every reference through the single-index pipeline, one at a time) and by
+kbo_refset_build_wide (the packed form walked from memory, refset_wide_kernels.hip), and run against the same contigs on both strands:
+both builds' and both calls' seconds, records_crc32 of both (they must be equal) and the wide kernel's share of the references and
+pairs of its call.  SUMMARY=1 and REPEATS apply; nothing else of the above runs.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -31,6 +36,7 @@ from kbo_amd import batch, refset  # noqa: E402
 REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS, SUMMARY = (int(os.environ.get(n, d)) for n, d in (
     ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3), ("SUMMARY", 0)))
 DEV, REFS_PER_SLAB, DEV_CAPACITY = (int(os.environ.get(n, d)) for n, d in (("DEV", 0), ("REFS_PER_SLAB", 64), ("DEV_CAPACITY", 1 << 20)))
+WIDE, WIDE_REFS, WIDE_BP = (int(os.environ.get(n, d)) for n, d in (("WIDE", 0), ("WIDE_REFS", 300), ("WIDE_BP", 50_000)))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -52,6 +58,54 @@ pair_bases = REFS * 2 * int(offsets[-1])
 
 import torch  # noqa: E402
 assert torch.cuda.is_available(), "this measures the GPU path: no device, no number"
+
+
+def wide_leg():
+    """the same large references as a set of the single-index route and as a set of the wide route, one process.  (It plants its copies in
+    the module's `contigs` AFTER `concat` was made of them: the leg passes `contigs` to its calls and exits, no other leg runs behind it)"""
+    big = [ACGT[rng.integers(0, 4, WIDE_BP)] for _ in range(WIDE_REFS)]
+    for i, r in enumerate(range(0, WIDE_REFS, 10)):  # a stretch of every 10th reference with 1 % substitutions lies in the query
+        c = contigs[i % CONTIGS]
+        n = min(5000, WIDE_BP, per)
+        at = int(rng.integers(0, per - n + 1))
+        copy = big[r][:n].copy()
+        pos = np.flatnonzero(rng.random(n) < 0.01)
+        copy[pos] = ACGT[(np.searchsorted(ACGT, copy[pos]) + 1) % 4]
+        c[at:at + n] = copy
+    out = {"workload": {"refs": WIDE_REFS, "ref_bp": WIDE_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2,
+                        "pair_bases": WIDE_REFS * 2 * int(offsets[-1])}, "form": "summary_refset" if SUMMARY else "find_refset"}
+    for label, rows in (("index_route", None), ("wide_route", refset.WIDE_MAX_ROWS)):
+        a = time.perf_counter()
+        s = refset.RefSet.build(big, opts, wide_rows=rows)
+        b = time.perf_counter()
+        s.to_device()
+        torch.cuda.synchronize()
+        c = time.perf_counter()
+
+        def call():
+            if SUMMARY:
+                return refset.summary_refset(contigs, s, fopts.max_error_prob, strands=3)
+            return refset.find_refset(contigs, s, fopts, strands=3)
+        got = call()  # warm-up: code objects, the call's buffers, the plan structures of the single-index route
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = call()
+            ts.append(time.perf_counter() - t)
+        routes, wide = refset.last_routes(), refset.last_wide()
+        out[label] = {"build_s": round(b - a, 4), "to_device_s": round(c - b, 4), "call_s": round(statistics.median(ts), 4),
+                      "call_s_all": [round(t, 4) for t in ts], "gbp_per_s": round(out["workload"]["pair_bases"] / statistics.median(ts) / 1e9, 2),
+                      "records": int(len(got)), "records_crc32": zlib.crc32(got.tobytes()), "routes": routes, "wide": wide,
+                      "wide_share_of_refs": round(wide[0] / max(1, routes[0] + routes[1] + wide[0]), 3)}
+        del s
+    out["records_equal"] = out["index_route"]["records_crc32"] == out["wide_route"]["records_crc32"]
+    out["index_over_wide"] = round(out["index_route"]["call_s"] / out["wide_route"]["call_s"], 2)
+    print(json.dumps(out))
+
+
+if WIDE:
+    wide_leg()
+    sys.exit(0)
 
 t0 = time.perf_counter()
 rs = refset.RefSet.build(refs, opts)
