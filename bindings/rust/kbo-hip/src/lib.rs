@@ -160,6 +160,15 @@ pub mod ffi {
         // the summary of every (reference, sequence, strand) pair of a reference set with a hit (the set: kbo_refset_build, kbo_hip.h)
         pub fn kbo_summary_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
                                   records: *mut *mut super::RefSummary, n_records: *mut u64) -> c_int;
+        // the best reference of every sequence, reduced on the device: one record per sequence; and its device-resident form, whose
+        // d_out is the running table of n_seqs records
+        pub fn kbo_best_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
+                               out: *mut *mut super::RefBest) -> c_int;
+        pub fn kbo_best_refset_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int,
+                                              refs_per_slab: usize) -> usize;
+        pub fn kbo_best_refset_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                   p: f64, strands: c_int, d_work: *mut c_void, work_bytes: usize, d_out: *mut super::RefBest,
+                                   stream: *mut c_void) -> c_int;
         // a set whose references of up to max_wide_rows rows (16 384 ..= 2^20) keep their packed form and are walked from memory; the
         // route of reference r (-1 status, 0 LDS, 1 single-index, 2 wide); 1 when the device-resident calls take the set
         pub fn kbo_refset_build_wide(seqs: *const *const u8, lens: *const usize, n_refs: usize, opts: *const KboBuildOpts,
@@ -231,6 +240,22 @@ pub struct RefSummary {
     pub aln: AlnExtent,
 }
 
+/// `kbo_ref_best` (48 bytes): what `kbo_best_refset` returns per query sequence - the first (reference, strand) pair by (larger
+/// `aln.n_match`, smaller `ref_`, '+' first), the number of pairs with a hit, and the runner-up among the other references.
+/// `ref_` / `second_ref` are `REF_NONE` where there is none.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefBest {
+    pub seq: u32,
+    pub ref_: u32,
+    pub strand: u32,
+    pub aln: AlnExtent,
+    pub n_hits: u32,
+    pub second_ref: u32,
+    pub second_match: u32,
+}
+pub const REF_NONE: u32 = 0xFFFF_FFFF;
+
 /// The summary form of `derand_translate_seq_dev`: the same inputs and contract, one `AlnExtent` per sequence at `d_out` (every one
 /// written; sequences of fewer than 3 bases get zeros) and no character buffer.  `d_work`: `derand_summary_seq_work_bytes` bytes.
 ///
@@ -260,6 +285,21 @@ pub unsafe fn summary_refset(set: *mut ffi::KboRefset, seqs: &[Vec<u8>], max_err
     check(ffi::kbo_summary_refset(set, concat.as_ptr(), offsets.as_ptr(), seqs.len(), max_error_prob, strands, &mut p, &mut n));
     if n == 0 { return Vec::new(); }
     let out = std::slice::from_raw_parts(p, n as usize).to_vec();
+    ffi::kbo_free(p as *mut c_void);
+    out
+}
+
+/// `kbo_best_refset` over a set handle a caller built with `kbo_refset_build`: one record per sequence, in sequence order.
+///
+/// # Safety
+/// `set` is a live `kbo_refset_t`.
+pub unsafe fn best_refset(set: *mut ffi::KboRefset, seqs: &[Vec<u8>], max_error_prob: f64, strands: c_int) -> Vec<RefBest> {
+    let mut offsets = vec![0u64; seqs.len() + 1];
+    for (i, r) in seqs.iter().enumerate() { offsets[i + 1] = offsets[i] + r.len() as u64; }
+    let concat: Vec<u8> = seqs.concat();
+    let mut p = std::ptr::null_mut::<RefBest>();
+    check(ffi::kbo_best_refset(set, concat.as_ptr(), offsets.as_ptr(), seqs.len(), max_error_prob, strands, &mut p));
+    let out = std::slice::from_raw_parts(p, seqs.len()).to_vec();
     ffi::kbo_free(p as *mut c_void);
     out
 }

@@ -594,6 +594,49 @@ size_t kbo_summary_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs,
 int kbo_summary_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                            double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_summary *d_records, size_t capacity,
                            uint64_t *d_n_records, void *stream);
+/* Which reference does each sequence belong to, and how clear is that choice: ONE record per query sequence, always, in sequence
+ * order (seq == its index) - typing a contig against an allele database, assigning a plasmid to its closest relative, binning reads by
+ * gene.  It is the reduction over references of kbo_summary_refset's pairs, made on the device: n_seqs records leave it per call where
+ * the summary sends up to N x n_seqs x 2.
+ * A pair (ref, strand) of a sequence has a HIT when its aln.n_runs > 0 - the pairs kbo_summary_refset has a record for.  Pairs with a
+ * hit are ordered by: larger aln.n_match first, then smaller ref, then '+' (KBO_STRAND_FWD) before '-'.
+ *   ref, strand, aln         the first pair in that order, aln as kbo_summary_refset's record of it has it ('-': in the coordinates
+ *                            of the reverse-complemented sequence)
+ *   n_hits                   the pairs of this sequence with a hit (kbo_summary_refset's records with this seq)
+ *   second_ref, second_match ref and aln.n_match of the first pair in that order among the pairs of ANOTHER reference than ref: the
+ *                            runner-up; the winner's own other strand is never it
+ * A sequence without a hit: ref = second_ref = KBO_REF_NONE, strand = 0, aln and the counts 0.  Only one reference hit: second_ref =
+ * KBO_REF_NONE, second_match = 0.  second_match == aln.n_match says that another reference ties (two identical references: the lower
+ * one is ref, the other second_ref).
+ * kbo_best_refset: *out is library-allocated (kbo_free), n_seqs records.  The slabs, the upload, the '-' strand, the walk and the
+ * summary stage are kbo_summary_refset's; behind them a slab runs ONE kernel that merges its extents into a table of n_seqs records on
+ * the device (kbo_amd/csrc/refset_best_kernels.hip) - no compaction, no record stage, nothing read back and nothing waited for per
+ * slab; the table comes back in one copy behind the last slab, the call's one synchronisation.  References of the single-index route
+ * go through that pipeline as in kbo_summary_refset and are merged into the table on the host, by the same merge
+ * (kbo_amd/csrc/refset_best.hpp).  Errors, all checked before the first HIP call: those of kbo_summary_refset, and KBO_E_UNSUPPORTED
+ * for 2^28 sequences or more.  References with a status contribute nothing.  kbo_refset_last_routes / kbo_refset_last_wide report this
+ * call as they do the summary's.
+ * kbo_best_refset_dev: kbo_summary_refset_dev's contract - the set is kbo_refset_packed_only() and has a copy on the current device,
+ * the inputs, alignments and slack of the batch, d_work (16-byte aligned) of kbo_best_refset_dev_work_bytes(..., refs_per_slab) bytes
+ * with the same meaning of refs_per_slab, everything enqueued on `stream`, nothing synchronised, read back or allocated, the same
+ * errors before anything is enqueued.  d_out (4-byte aligned, n_seqs records) IS the running table: the call sets it to the empty
+ * records and every slab merges into it, so it is complete when the stream reaches the end of the call; there is no capacity and no
+ * count.  Sequences of fewer than 3 bases get the record without a hit (the host form refuses the batch, as kbo_summary_refset does).
+ * Launches: 7 a call (8 with the '-' strand, and the device-to-device copy when both strands are asked for) - the summary form's 6 and
+ * the table's fill - + 17 a slab where the summary form has 22: its compaction (4) and its record append (2) are not launched, the merge (1) is;
+ * one more for a slab with both LDS and wide references.  d_work holds what kbo_summary_refset_dev's does without the scan and the kept
+ * list. */
+#define KBO_REF_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t seq, ref, strand; /* strand: KBO_STRAND_FWD or KBO_STRAND_REV; 0 without a hit */
+    kbo_aln_extent aln;
+    uint32_t n_hits, second_ref, second_match;
+} kbo_ref_best; /* 48 bytes */
+int kbo_best_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob, int strands,
+                    kbo_ref_best **out);
+size_t kbo_best_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t refs_per_slab);
+int kbo_best_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, void *stream);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

@@ -214,6 +214,10 @@ int kbo_refset_last_routes(uint64_t out[4]);
  * walked by the wide kernel, out[1] the tasks (workgroups) it was launched with, over all slabs.  out[0] of kbo_refset_last_routes
  * counts the references of the LDS kernel only; its out[2], the pairs, includes the wide references' */
 int kbo_refset_last_wide(uint64_t out[2]);
+/* test hook: the launches of refset_best_kernel (kbo_amd/csrc/refset_best_kernels.hip) in the calling thread's last kbo_best_refset or
+ * kbo_best_refset_dev, one a slab: out[0] with a wave per sequence, out[1] with a workgroup of four waves per sequence (batches of
+ * fewer than 64 sequences) */
+int kbo_refset_last_best(uint64_t out[2]);
 /* test hook: the packed form of reference r (kernels.hpp: rank blocks, LCS bytes with the sentinel), *n_bytes of it, a multiple of
  * 16; out == NULL asks for the size only.  KBO_E_BAD_ARG for a reference with a status or of the single-index route */
 int kbo_refset_form(const kbo_refset_t *set, size_t r, uint8_t *out, size_t *n_bytes);

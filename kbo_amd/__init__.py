@@ -24,7 +24,7 @@ if os.environ.get("KBO_HW_QUEUES"):
 from . import _capi, derandomize, format, gap_filling, index, translate, variant_calling  # noqa: F401
 from ._capi import KboError, check, lib  # noqa: F401
 from .index import LcsArray, SbwtIndexVariant, _u8  # noqa: F401
-from .refset import RefSet, find_refset, find_refset_dev, summary_refset, summary_refset_dev  # noqa: F401,E402
+from .refset import RefSet, best_refset, best_refset_dev, find_refset, find_refset_dev, summary_refset, summary_refset_dev  # noqa: F401,E402
 
 
 @dataclass

@@ -122,6 +122,7 @@ SYMBOLS = [
     "kbo_refset_lds_only", "kbo_find_refset_dev_work_bytes", "kbo_find_refset_dev", "kbo_summary_refset_dev_work_bytes",
     "kbo_summary_refset_dev",
     "kbo_refset_build_wide", "kbo_refset_route", "kbo_refset_packed_only",
+    "kbo_best_refset", "kbo_best_refset_dev_work_bytes", "kbo_best_refset_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -132,7 +133,7 @@ TUNING_SYMBOLS = [
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
     "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
     "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
-    "kbo_refset_last_wide", "kbo_refset_form", "kbo_refset_ms_host",
+    "kbo_refset_last_wide", "kbo_refset_form", "kbo_refset_ms_host", "kbo_refset_last_best",
 ]
 
 _lib = None
@@ -342,6 +343,10 @@ def lib():
     L.kbo_refset_last_wide.argtypes = [vp]
     L.kbo_refset_form.argtypes = [vp, sz, vp, C.POINTER(sz)]
     L.kbo_refset_ms_host.argtypes = [vp, sz, vp, sz, vp]
+    L.kbo_best_refset.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, C.POINTER(vp)]
+    L.kbo_best_refset_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz]; L.kbo_best_refset_dev_work_bytes.restype = sz
+    L.kbo_best_refset_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, vp]
+    L.kbo_refset_last_best.argtypes = [vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

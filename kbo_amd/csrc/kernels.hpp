@@ -610,6 +610,22 @@ hipError_t launch_refset_tag_runs(const RefsetPlan &a, uint32_t first_q, uint32_
                                   uint32_t local_cap, uint64_t *d_count, uint64_t capacity, uint32_t *d_out, hipStream_t stream);
 hipError_t launch_refset_tag_summaries(const RefsetPlan &a, uint32_t first_q, uint32_t n_pairs, const uint32_t *d_kept, const uint32_t *d_n_kept,
                                        uint64_t *d_count, uint64_t capacity, uint32_t *d_out, hipStream_t stream);
+// ---- the best reference per sequence (refset_best_kernels.hip; the record and its merge: refset_best.hpp).  The table is n_seqs
+// records of twelve u32 (kbo_ref_best), set to the empty records once per call; behind the summary stage of every slab its extents
+// are merged in.  The slab's n_pairs pairs are numbers [lead, lead + n_pairs) of (reference of the slab, sequence, strand index) in
+// that order, counted from the slab's first reference on: lead < n_seqs * n_strands is where the slab begins within that reference.
+struct RefsetBestArgs {
+    const uint32_t *ext;   // six u32 a pair of the slab (launch_derand_summary_seq's), 8-byte aligned
+    const uint32_t *refs;  // the slab_refs references the slab's pairs belong to, in order
+    uint32_t *table;       // n_seqs records, 4-byte aligned
+    uint32_t n_pairs, lead, slab_refs;
+    uint32_t n_seqs, n_strands, strands; // strands: KBO_STRAND_FWD, KBO_STRAND_REV or both (then n_strands = 2)
+};
+// below this many sequences a workgroup of four waves shares one sequence's pairs, from it on a wave has a sequence to itself
+constexpr uint32_t kRefsetBestSplitBelow = 64;
+bool refset_best_splits(uint32_t n_seqs);
+hipError_t launch_refset_best_init(uint32_t *d_table, uint32_t n_seqs, hipStream_t stream); // n_seqs < 2^28
+hipError_t launch_refset_best(const RefsetBestArgs &a, hipStream_t stream);                 // one launch; none for n_pairs == 0
 
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256

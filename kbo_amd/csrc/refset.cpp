@@ -4,8 +4,11 @@
 // (derand_seq_kernels.hip: the pair's reference's), then the single-index pipeline's run_lengths_gapped kernels as they are.
 // kbo_summary_refset shares the slabs, the upload, the '-' strand and the walk; behind the walk it runs the counting form of the
 // derandomize / translate stage and keeps the pairs with a hit on the device: no characters, no run-length stage.
+// kbo_best_refset shares all of that up to the extents and merges them, slab by slab, into a table of one record per sequence on the
+// device (refset_best_kernels.hip): no record stage, nothing read back until the last slab is enqueued.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
+#include "refset_best.hpp"
 #include "refset_step.hpp"
 
 #include <algorithm>
@@ -22,6 +25,7 @@ namespace {
 std::atomic<size_t> g_record_capacity{1u << 16};
 thread_local uint64_t t_routes[4] = {0, 0, 0, 0};
 thread_local uint64_t t_wide[2] = {0, 0}; // references walked by the wide kernel, the tasks it was launched with
+thread_local uint64_t t_best[2] = {0, 0}; // launches of refset_best_kernel: a wave per sequence, a workgroup per sequence
 
 struct DevSet {
     DevBuf arena, descs;
@@ -128,9 +132,48 @@ struct SlabPlan {
     uint64_t bytes() const { return off.back(); }
 };
 
-// what kbo_find_refset and kbo_summary_refset share: the batch on the device, slabs of pairs and their walk
+// A slab's uploads through pinned memory, two sets in turn: a walker that synchronises nothing per slab (Bester) plans the next
+// slab while the device runs this one, and the slab's host arrays are free to change as soon as run_slab returns.  A set is taken
+// again only when the copies out of it have run (its event).
+struct SlabStage {
+    PinBuf pin[2];
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool used[2] = {false, false};
+    size_t at = 0;
+    int cur = 1;
+    static size_t room(size_t bytes) { return (bytes + 15) / 16 * 16; }
+    void begin(size_t bytes)
+    {
+        cur ^= 1;
+        if (!ev[cur]) HIP_OK(hipEventCreateWithFlags(&ev[cur], hipEventDisableTiming));
+        if (used[cur]) HIP_OK(hipEventSynchronize(ev[cur]));
+        pin[cur].ensure(bytes);
+        at = 0;
+    }
+    const void *put(const void *src, size_t bytes)
+    {
+        KBO_REQUIRE(at + bytes <= pin[cur].cap, KBO_E_HIP, "slab stage overrun");
+        uint8_t *dst = pin[cur].as<uint8_t>() + at;
+        if (bytes) std::memcpy(dst, src, bytes);
+        at += room(bytes);
+        return dst;
+    }
+    void end(hipStream_t st)
+    {
+        HIP_OK(hipEventRecord(ev[cur], st));
+        used[cur] = true;
+    }
+    ~SlabStage()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// what kbo_find_refset, kbo_summary_refset and kbo_best_refset share: the batch on the device, slabs of pairs and their walk
 struct SlabWalker {
     kbo_refset *set;
+    SlabStage *stage = nullptr; // where the slab's arrays are copied from when they may change before the copies have run
     const uint64_t *offsets;
     uint32_t k, chunk, min_thr; // min_thr: the smallest threshold of the references that take a walk of the packed form
     uint64_t rev_base; // where the '-' strand of the batch begins in d_q
@@ -178,10 +221,10 @@ struct SlabWalker {
         d_derand.ensure(kbo::derand_seq_work_bytes((uint32_t)np, P.bytes(), k, min_thr));
         d_items.ensure(P.items.size() * sizeof(uint32_t));
         d_tasks.ensure(P.tasks.size() * sizeof(uint32_t));
-        HIP_OK(hipMemcpyAsync(d_poff.p, P.off.data(), (np + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_pthr.p, P.thr.data(), np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_items.p, P.items.data(), P.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_tasks.p, P.tasks.data(), P.tasks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        upload(d_poff.p, P.off.data(), (np + 1) * sizeof(uint64_t));
+        upload(d_pthr.p, P.thr.data(), np * sizeof(uint32_t));
+        upload(d_items.p, P.items.data(), P.items.size() * sizeof(uint32_t));
+        upload(d_tasks.p, P.tasks.data(), P.tasks.size() * sizeof(uint32_t));
         kbo::RefsetWalkArgs a;
         a.descs = ds->descs.as<kbo::RefsetDesc>();
         a.arena = ds->arena.as<uint4>();
@@ -205,6 +248,16 @@ struct SlabWalker {
         t_routes[2] += np;
     }
     static size_t slab_buffer_bytes(const SlabPlan &P) { return ((size_t)P.bytes() + 15) / 16 * 16 + 64; }
+    void upload(void *dst, const void *src, size_t bytes)
+    {
+        HIP_OK(hipMemcpyAsync(dst, stage ? stage->put(src, bytes) : src, bytes, hipMemcpyHostToDevice, st));
+    }
+    // what walk_slab puts into the stage
+    static size_t stage_bytes(const SlabPlan &P)
+    {
+        return SlabStage::room((P.pairs() + 1) * sizeof(uint64_t)) + SlabStage::room(P.pairs() * sizeof(uint32_t)) +
+               SlabStage::room(P.items.size() * sizeof(uint32_t)) + SlabStage::room(P.tasks.size() * sizeof(uint32_t));
+    }
 };
 
 struct Finder : SlabWalker {
@@ -300,6 +353,48 @@ struct Summarizer : SlabWalker {
             }
             ref_end[r] = out.size();
         }
+        t_routes[3]++;
+    }
+};
+
+// kbo_best_refset: the extents of a slab merged into the call's table where they are.  Nothing is read back and nothing waited for:
+// the slab's arrays go through the stage, the device buffers are the stream's in order (one that grows is freed by hipFree, which
+// waits for the device's work), and the table comes back once, behind the last slab.
+struct Bester : SlabWalker {
+    SlabStage pinned;
+    DevBuf d_ext, d_refs, d_table;
+    std::vector<uint32_t> refs; // the slab's references, in order
+    uint32_t n_seqs = 0, n_strands = 0, strands = 0;
+
+    void run_slab(const SlabPlan &P)
+    {
+        const size_t np = P.pairs();
+        if (!np) return;
+        refs.clear();
+        for (size_t p = 0; p < np; p++)
+            if (refs.empty() || refs.back() != P.ref[p]) refs.push_back(P.ref[p]);
+        d_ext.ensure(np * sizeof(kbo_aln_extent));
+        d_refs.ensure(refs.size() * sizeof(uint32_t));
+        stage = &pinned;
+        pinned.begin(stage_bytes(P) + SlabStage::room(refs.size() * sizeof(uint32_t)));
+        walk_slab(P);
+        upload(d_refs.p, refs.data(), refs.size() * sizeof(uint32_t));
+        pinned.end(st);
+        HIP_OK(kbo::launch_derand_summary_seq(d_ms.as<uint8_t>(), d_poff.as<uint64_t>(), (uint32_t)np, P.bytes(), k, d_pthr.as<uint32_t>(), min_thr,
+                                              d_ext.as<uint32_t>(), d_derand.p, st));
+        kbo::RefsetBestArgs a;
+        a.ext = d_ext.as<uint32_t>();
+        a.refs = d_refs.as<uint32_t>();
+        a.table = d_table.as<uint32_t>();
+        a.n_pairs = (uint32_t)np;
+        // run_slabs adds the pairs in (reference, sequence, strand) order: the slab begins this far into its first reference
+        a.lead = P.seq[0] * n_strands + (strands == 3 ? P.strand[0] - 1u : 0u);
+        a.slab_refs = (uint32_t)refs.size();
+        a.n_seqs = n_seqs;
+        a.n_strands = n_strands;
+        a.strands = strands;
+        HIP_OK(kbo::launch_refset_best(a, st));
+        t_best[kbo::refset_best_splits(n_seqs) ? 1 : 0]++;
         t_routes[3]++;
     }
 };
@@ -412,9 +507,10 @@ kbo_aln_extent extent_of_chars(const uint8_t *c, uint64_t len)
     return e;
 }
 
-// ---- the device-resident form (kbo_find_refset_dev / kbo_summary_refset_dev): the same stages enqueued on the caller's stream over
-// the caller's work buffer.  A slab is a range of queryable references against the whole batch, planned on the device
-// (refset_plan_kernels.hip); nothing comes back to the host.
+// ---- the device-resident form (kbo_find_refset_dev / kbo_summary_refset_dev / kbo_best_refset_dev): the same stages enqueued on the
+// caller's stream over the caller's work buffer.  A slab is a range of queryable references against the whole batch, planned on the
+// device (refset_plan_kernels.hip); nothing comes back to the host.
+enum DevKind { kDevSummary, kDevFind, kDevBest };
 struct DevForm {
     kbo::refplan::Geometry g;
     uint32_t n_refs = 0, n_q = 0, max_refs = 0, refs = 0; // references of the set, queryable ones, the most a slab may hold, a slab's
@@ -429,8 +525,9 @@ struct DevForm {
 size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 // the layout of d_work for slabs of refs_per_slab references (0: as many as a slab may hold; more than that: that many)
-DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int strands, size_t capacity, size_t refs_per_slab, bool find)
+DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int strands, size_t capacity, size_t refs_per_slab, DevKind kind)
 {
+    const bool find = kind == kDevFind;
     DevForm F;
     if (!set || n_seqs == 0 || strands < 1 || strands > 3) return F;
     for (const kbo::RefsetDesc &d : set->descs)
@@ -472,8 +569,10 @@ DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int stran
         F.local = w; w += up16((size_t)F.local_cap * kRleWords * sizeof(uint32_t));
     } else {
         F.chars = w; w += up16((size_t)np * sizeof(kbo_aln_extent));                                     // the extents
-        F.stage = w; w += up16(kbo::chunk_items_scratch_words((uint32_t)np) * sizeof(uint32_t));          // launch_refset_keep's scan
-        F.local = w; w += up16((size_t)np * 7 * sizeof(uint32_t));                                       // the kept list
+        if (kind == kDevSummary) { // (best: the extents are merged into the caller's table where they are)
+            F.stage = w; w += up16(kbo::chunk_items_scratch_words((uint32_t)np) * sizeof(uint32_t));      // launch_refset_keep's scan
+            F.local = w; w += up16((size_t)np * 7 * sizeof(uint32_t));                                   // the kept list
+        }
     }
     F.end = w;
     F.ok = true;
@@ -504,10 +603,13 @@ DevSet *device_set_if_any(kbo_refset *set, int device)
     return it == set->dev.end() ? nullptr : it->second;
 }
 
-void run_dev_form(const DevCall &c, bool find)
+// (best: c.d_out is the table of n_seqs records, there is no capacity and the count the planner zeroes lies in d_work)
+void run_dev_form(const DevCall &c, DevKind kind)
 {
+    const bool find = kind == kDevFind, best = kind == kDevBest;
     KBO_REQUIRE(c.strands >= 1 && c.strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
-    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && c.d_n && (c.d_out || c.capacity == 0), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && (c.d_n || best) && (c.d_out || (c.capacity == 0 && !best)), KBO_E_BAD_ARG,
+                "null argument");
     KBO_REQUIRE(((uintptr_t)c.d_concat & 15) == 0 && ((uintptr_t)c.d_work & 15) == 0 && ((uintptr_t)c.d_offsets & 7) == 0 &&
                     ((uintptr_t)c.d_n & 7) == 0 && ((uintptr_t)c.d_out & 3) == 0,
                 KBO_E_BAD_ARG, "d_concat and d_work 16-byte, d_offsets and the count 8-byte, the records 4-byte aligned");
@@ -517,16 +619,16 @@ void run_dev_form(const DevCall &c, bool find)
     for (const kbo::RefsetDesc &d : set->descs)
         KBO_REQUIRE(d.status || d.route != kbo::kRefsetRouteIndex, KBO_E_UNSUPPORTED,
                     "a reference of the single-index route: the host calls take it (kbo_refset_packed_only)");
-    DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, 1, find);
+    DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, 1, kind);
     KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a slab of one reference of 2^32 - 16 bytes or more, or 2^28 (sequence, strand) pairs or more");
     KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes too small for one reference a slab");
     uint32_t lo = 1, hi = F.max_refs; // the largest refs_per_slab whose figure fits: the figure is monotonic
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, mid, find).end <= c.work_bytes) lo = mid;
+        if (dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, mid, kind).end <= c.work_bytes) lo = mid;
         else hi = mid - 1;
     }
-    F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, lo, find);
+    F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, lo, kind);
     DevSet *ds = device_set_if_any(set, current_device());
     KBO_REQUIRE(ds, KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
 
@@ -553,7 +655,12 @@ void run_dev_form(const DevCall &c, bool find)
     P.nch = at(F.nch);
     P.nch_sums = at(F.nch) + c.n_seqs + 1;
     P.qref = at(F.qref);
-    HIP_OK(kbo::launch_refset_plan_call(P, F.n_refs, at(F.nch), at(F.qflag), at(F.qref), c.d_n, st));
+    uint64_t *d_n = best ? reinterpret_cast<uint64_t *>(w + F.total) : c.d_n;
+    HIP_OK(kbo::launch_refset_plan_call(P, F.n_refs, at(F.nch), at(F.qflag), at(F.qref), d_n, st));
+    if (best) {
+        HIP_OK(kbo::launch_refset_best_init(static_cast<uint32_t *>(c.d_out), (uint32_t)c.n_seqs, st));
+        std::fill(t_best, t_best + 2, 0);
+    }
     if (c.total_bases == 0) return; // (no base, no record)
 
     uint64_t *poff = reinterpret_cast<uint64_t *>(w + F.poff);
@@ -592,6 +699,20 @@ void run_dev_form(const DevCall &c, bool find)
                 HIP_OK(kbo::launch_rle_seg_emit(w + F.chars, np, bytes, c.gap, w + F.stage, at(F.local), (uint32_t)F.local_cap, st));
             HIP_OK(kbo::launch_refset_tag_runs(P, (uint32_t)q0, np, at(F.first), at(F.local), (uint32_t)F.local_cap, c.d_n, c.capacity,
                                                static_cast<uint32_t *>(c.d_out), st));
+        } else if (best) {
+            HIP_OK(kbo::launch_derand_summary_seq(ms, poff, np, bytes, set->k, at(F.pthr), min_thr, at(F.chars), w + F.derand, st));
+            kbo::RefsetBestArgs b;
+            b.ext = at(F.chars);
+            b.refs = at(F.qref) + q0;
+            b.table = static_cast<uint32_t *>(c.d_out);
+            b.n_pairs = np;
+            b.lead = 0;
+            b.slab_refs = refs;
+            b.n_seqs = (uint32_t)c.n_seqs;
+            b.n_strands = F.g.n_strands;
+            b.strands = (uint32_t)c.strands;
+            HIP_OK(kbo::launch_refset_best(b, st));
+            t_best[kbo::refset_best_splits(b.n_seqs) ? 1 : 0]++;
         } else {
             HIP_OK(kbo::launch_derand_summary_seq(ms, poff, np, bytes, set->k, at(F.pthr), min_thr, at(F.chars), w + F.derand, st));
             HIP_OK(kbo::launch_refset_keep(at(F.chars), np, at(F.stage), at(F.local), at(F.total), st));
@@ -879,13 +1000,13 @@ int kbo_refset_lds_only(const kbo_refset_t *set)
 size_t kbo_find_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
                                       size_t refs_per_slab)
 {
-    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, true).end;
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kDevFind).end;
 }
 
 size_t kbo_summary_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
                                          size_t refs_per_slab)
 {
-    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, false).end;
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kDevSummary).end;
 }
 
 int kbo_find_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
@@ -897,7 +1018,7 @@ int kbo_find_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64
         if (opts) o = *opts; else kbo_find_opts_default(&o);
         run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, o.max_error_prob, (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu),
                              strands, d_work, work_bytes, d_runs, capacity, d_n_runs, static_cast<hipStream_t>(stream)},
-                     true);
+                     kDevFind);
     });
 }
 
@@ -908,7 +1029,86 @@ int kbo_summary_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uin
     return guarded([&] {
         run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_records, capacity,
                              d_n_records, static_cast<hipStream_t>(stream)},
-                     false);
+                     kDevSummary);
+    });
+}
+
+int kbo_refset_last_best(uint64_t out[2])
+{
+    if (!out) return KBO_E_BAD_ARG;
+    std::copy(t_best, t_best + 2, out);
+    return KBO_OK;
+}
+
+int kbo_best_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob, int strands,
+                    kbo_ref_best **out)
+{
+    return guarded([&] {
+        namespace rb = kbo::refbest;
+        static_assert(sizeof(kbo_ref_best) == 48 && sizeof(kbo_ref_best) == sizeof(rb::Best) && rb::kWords * 4 == sizeof(kbo_ref_best),
+                      "kbo_ref_best is the twelve words of refset_best.hpp");
+        KBO_REQUIRE(strands >= 1 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+        KBO_REQUIRE(set && out, KBO_E_BAD_ARG, "null argument");
+        *out = nullptr;
+        const std::vector<uint32_t> thr = refset_thresholds(set, max_error_prob);
+        const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
+        KBO_REQUIRE(n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "2^28 sequences or more");
+        std::fill(t_routes, t_routes + 4, 0);
+        std::fill(t_wide, t_wide + 2, 0);
+        std::fill(t_best, t_best + 2, 0);
+
+        const size_t n_refs = set->descs.size();
+        const uint32_t n_strands = strands == 3 ? 2 : 1;
+        Bester F;
+        F.n_seqs = (uint32_t)n_seqs;
+        F.n_strands = n_strands;
+        F.strands = (uint32_t)strands;
+        StreamScope stream;
+        upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+        F.d_table.alloc(n_seqs * sizeof(kbo_ref_best));
+        HIP_OK(kbo::launch_refset_best_init(F.d_table.as<uint32_t>(), (uint32_t)n_seqs, stream.s));
+        run_slabs(F, thr, n_seqs, strands);
+        MallocPtr<kbo_ref_best> res = malloc_array<kbo_ref_best>(n_seqs);
+        HIP_OK(hipMemcpyAsync(res.get(), F.d_table.p, n_seqs * sizeof(kbo_ref_best), hipMemcpyDeviceToHost, stream.s));
+        HIP_OK(hipStreamSynchronize(stream.s)); // the call's one wait
+
+        // the references of the single-index route: the characters of that pipeline, counted and merged here
+        std::vector<uint8_t> fwd, rev;
+        for (size_t r = 0; r < n_refs; r++) {
+            if (set->descs[r].status || set->descs[r].route != kbo::kRefsetRouteIndex) continue;
+            if (strands & KBO_STRAND_FWD) fwd.resize(total);
+            if (strands & KBO_STRAND_REV) rev.resize(total);
+            matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, max_error_prob, false, fwd.data(), nullptr, strands, rev.data());
+            for (size_t s = 0; s < n_seqs; s++)
+                for (uint32_t strand = 1; strand <= 2; strand++) {
+                    if (!(strands & strand)) continue;
+                    const uint8_t *c = (strand == KBO_STRAND_FWD ? fwd.data() : rev.data()) + offsets[s];
+                    const kbo_aln_extent e = extent_of_chars(c, offsets[s + 1] - offsets[s]);
+                    const uint32_t ext[6] = {e.n_match, e.n_mismatch, e.n_jump, e.n_runs, e.start, e.end};
+                    rb::Best b;
+                    std::memcpy(&b, &res[s], sizeof b);
+                    b = rb::merge(b, rb::from_pair((uint32_t)s, (uint32_t)r, strand, ext));
+                    std::memcpy(&res[s], &b, sizeof b);
+                }
+            t_routes[1]++;
+            t_routes[2] += n_seqs * n_strands;
+        }
+        *out = res.release();
+    });
+}
+
+size_t kbo_best_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t refs_per_slab)
+{
+    return dev_form(set, n_seqs, total_bases, strands, 0, refs_per_slab, kDevBest).end;
+}
+
+int kbo_best_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, void *stream)
+{
+    return guarded([&] {
+        run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_out, 0, nullptr,
+                             static_cast<hipStream_t>(stream)},
+                     kDevBest);
     });
 }
 

@@ -22,6 +22,13 @@ REF_RUN = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32
 REF_SUMMARY = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32), ("n_match", np.uint32), ("n_mismatch", np.uint32),
                         ("n_jump", np.uint32), ("n_runs", np.uint32), ("start", np.uint32), ("end", np.uint32)])
 
+# kbo_ref_best (48 bytes): one per query sequence - the first (ref, strand) pair by (larger n_match, smaller ref, '+' first) with its
+# kbo_aln_extent, the pairs with a hit, and ref / n_match of the runner-up among the OTHER references; REF_NONE where there is none
+REF_NONE = 0xFFFFFFFF
+REF_BEST = np.dtype([("seq", np.uint32), ("ref", np.uint32), ("strand", np.uint32), ("n_match", np.uint32), ("n_mismatch", np.uint32),
+                     ("n_jump", np.uint32), ("n_runs", np.uint32), ("start", np.uint32), ("end", np.uint32), ("n_hits", np.uint32),
+                     ("second_ref", np.uint32), ("second_match", np.uint32)])
+
 
 class RefSet:
     """kbo_refset_t: index r is what kbo::build (lib.rs:501-506) makes of reference r alone"""
@@ -142,6 +149,54 @@ def summary_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH)
         lib().kbo_free(p)
 
 
+def best_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH):
+    """The best reference of every query sequence, reduced on the device: a structured array of len(query_seqs) REF_BEST records in
+    sequence order.  The pairs are summary_refset's; a sequence's record names the pair with the most matches (ties: the smaller
+    ref, then '+'), how many pairs had a hit, and the runner-up among the other references.  A sequence without a hit has ref ==
+    second_ref == REF_NONE and strand == 0."""
+    raw = [_u8(s) for s in query_seqs]
+    concat = np.ascontiguousarray(np.concatenate(raw) if raw else np.zeros(0, dtype=np.uint8))
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in raw], dtype=np.uint64)
+    p = C.c_void_p()
+    check(lib().kbo_best_refset(refset._h, concat.ctypes.data, offsets.ctypes.data, len(raw), float(max_error_prob), int(strands), C.byref(p)))
+    try:
+        buf = (C.c_uint8 * (len(raw) * REF_BEST.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=REF_BEST).copy()
+    finally:
+        lib().kbo_free(p)
+
+
+def best_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, refs_per_slab=None, stream=None):
+    """kbo_best_refset_dev over torch tensors on the device: best_refset's records as an (n_seqs, 12) int32 tensor that holds the u32
+    words of REF_BEST, complete when `stream` reaches the end of the call.  The conventions are summary_refset_dev's: the batch, the
+    set (on that device, packed_only()), refs_per_slab, the stream, and nothing synchronised.  Sequences of fewer than 3 bases get
+    the record without a hit."""
+    import torch
+    device = concat.device
+    n_seqs = int(offsets.numel()) - 1
+    assert concat.dtype == torch.uint8 and offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+    L = lib()
+    ns = 2 if int(strands) == STRAND_BOTH else 1
+    if refs_per_slab is None:  # slabs of about 256 MiB; 0: as many references as a slab may hold
+        refs_per_slab = max(1, (1 << 28) // max(1, ns * total))
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.device(device), torch.cuda.stream(s):
+        q = concat.contiguous()
+        if int(q.numel()) < total + 16 or q.data_ptr() % 16:  # the 16 bytes of slack behind a per-base buffer
+            p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+            p[:total].copy_(q[:total])
+            q = p
+        off = offsets.contiguous()
+        wb = int(L.kbo_best_refset_dev_work_bytes(refset._h, n_seqs, total, int(strands), refs_per_slab))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=device)
+        table = torch.empty((n_seqs, 12), dtype=torch.int32, device=device)
+        check(L.kbo_best_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, float(max_error_prob), int(strands),
+                                    work.data_ptr(), wb, table.data_ptr(), s.cuda_stream))
+    return table  # (the scratch was allocated on `s`: the allocator reuses it in that stream's order)
+
+
 def _refset_dev(find, concat, offsets, refset, arg, strands, capacity, refs_per_slab, stream):
     import torch
     device = concat.device
@@ -203,9 +258,17 @@ def last_wide():
     return tuple(int(v) for v in out)
 
 
+def last_best():
+    """(launches with a wave per sequence, launches with a workgroup per sequence) of refset_best_kernel in the calling thread's last
+    best_refset or best_refset_dev"""
+    out = (C.c_uint64 * 2)()
+    check(lib().kbo_refset_last_best(out))
+    return tuple(int(v) for v in out)
+
+
 def last_routes():
     """(references walked by the LDS kernel, references through the single-index pipeline, pairs walked, slabs) of the calling
-    thread's last find_refset or summary_refset"""
+    thread's last find_refset, summary_refset or best_refset"""
     out = (C.c_uint64 * 4)()
     check(lib().kbo_refset_last_routes(out))
     return tuple(int(v) for v in out)

@@ -19,6 +19,11 @@ twice in one process, by kbo_refset_build (every reference through the single-in
 kbo_refset_build_wide (the packed form walked from memory, refset_wide_kernels.hip), and run against the same contigs on both strands:
 both builds' and both calls' seconds, records_crc32 of both (they must be equal) and the wide kernel's share of the references and
 pairs of its call.  SUMMARY=1 and REPEATS apply; nothing else of the above runs.
+BEST=1 is a leg of its own on the first workload: kbo_best_refset - one record per contig, reduced on the device - against what a
+caller did before it: kbo_summary_refset plus the fold of its records in numpy (sort by (seq, most matches, ref, strand), the first
+record of every contig, the first of another reference).  Both in one session, median of REPEATS behind a warm-up; the seconds of
+each, of the fold alone, the records the summary sent, and the CRC of the best records next to the CRC of the folded summary records
+(they must be equal).  LOOP, SUMMARY and DEV do not apply.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -37,6 +42,7 @@ REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS, SUMMARY = (int(os.environ.get(n,
     ("REFS", 2000), ("REF_BP", 1000), ("QUERY_BP", 5_000_000), ("CONTIGS", 50), ("LOOP", 50), ("REPEATS", 3), ("SUMMARY", 0)))
 DEV, REFS_PER_SLAB, DEV_CAPACITY = (int(os.environ.get(n, d)) for n, d in (("DEV", 0), ("REFS_PER_SLAB", 64), ("DEV_CAPACITY", 1 << 20)))
 WIDE, WIDE_REFS, WIDE_BP = (int(os.environ.get(n, d)) for n, d in (("WIDE", 0), ("WIDE_REFS", 300), ("WIDE_BP", 50_000)))
+BEST = int(os.environ.get("BEST", 0))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -121,6 +127,59 @@ def runs_per_pair(records):
         if len(records) else (np.zeros((0, 3), dtype=np.uint32), np.zeros(0, dtype=np.int64))
     return {tuple(int(v) for v in key): int(c) for key, c in zip(keys, counts)}
 
+
+def fold_best(summ, n_seqs):
+    """REF_BEST of every sequence from summary_refset's records, in numpy"""
+    out = np.zeros(n_seqs, dtype=refset.REF_BEST)
+    out["seq"] = np.arange(n_seqs, dtype=np.uint32)
+    out["ref"] = out["second_ref"] = refset.REF_NONE
+    if not len(summ):
+        return out
+
+    def firsts(rec):
+        """the first record of every sequence that has one, by (most matches, ref, strand)"""
+        order = np.lexsort((rec["strand"], rec["ref"], -rec["n_match"].astype(np.int64), rec["seq"]))
+        rec = rec[order]
+        return rec[np.concatenate([[True], rec["seq"][1:] != rec["seq"][:-1]])]
+    top = firsts(summ)
+    at = top["seq"]
+    for f in ("ref", "strand", "n_match", "n_mismatch", "n_jump", "n_runs", "start", "end"):
+        out[f][at] = top[f]
+    out["n_hits"] = np.bincount(summ["seq"], minlength=n_seqs).astype(np.uint32)
+    rest = summ[summ["ref"] != out["ref"][summ["seq"]]]
+    if len(rest):
+        second = firsts(rest)
+        out["second_ref"][second["seq"]] = second["ref"]
+        out["second_match"][second["seq"]] = second["n_match"]
+    return out
+
+
+def best_leg():
+    def timed(fn):
+        fn()  # warm-up: code objects, the call's buffers
+        ts, got = [], None
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return statistics.median(ts), [round(t, 4) for t in ts], got
+    best_s, best_all, best = timed(lambda: refset.best_refset(contigs, rs, fopts.max_error_prob, strands=3))
+    routes, launches = refset.last_routes(), refset.last_best()
+    summ_s, summ_all, summ = timed(lambda: refset.summary_refset(contigs, rs, fopts.max_error_prob, strands=3))
+    fold_s, fold_all, folded = timed(lambda: fold_best(summ, CONTIGS))
+    print(json.dumps({
+        "workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+        "best_refset_s": round(best_s, 4), "best_refset_s_all": best_all, "best_refset_gbp_per_s": round(pair_bases / best_s / 1e9, 2),
+        "summary_refset_s": round(summ_s, 4), "summary_refset_s_all": summ_all, "numpy_fold_s": round(fold_s, 4), "numpy_fold_s_all": fold_all,
+        "summary_plus_fold_s": round(summ_s + fold_s, 4), "summary_plus_fold_over_best": round((summ_s + fold_s) / best_s, 3),
+        "summary_records": int(len(summ)), "best_records": int(len(best)), "best_with_a_hit": int((best["ref"] != refset.REF_NONE).sum()),
+        "best_records_crc32": zlib.crc32(best.tobytes()), "folded_summary_crc32": zlib.crc32(folded.tobytes()),
+        "best_equals_folded_summary": best.tobytes() == folded.tobytes(), "routes": routes, "best_launches": launches}))
+
+
+if BEST:
+    best_leg()
+    sys.exit(0)
 
 if SUMMARY:
     def call():
