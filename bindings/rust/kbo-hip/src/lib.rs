@@ -175,6 +175,16 @@ pub mod ffi {
                                      max_wide_rows: usize, out: *mut *mut KboRefset) -> c_int;
         pub fn kbo_refset_route(set: *const KboRefset, r: usize) -> c_int;
         pub fn kbo_refset_packed_only(set: *const KboRefset) -> c_int;
+        // a set with a prefilter (a seed table over the packed references): the host forms of find / summary / best then walk only the
+        // (reference, sequence, strand) pairs that share a seed; kbo_refset_candidates is the screen alone - bit
+        // (r * n_seqs + s) * 2 + strand - 1 of ceil(n_refs * n_seqs * 2 / 32) words
+        pub fn kbo_refset_opts_default(o: *mut super::RefsetOpts);
+        pub fn kbo_refset_build_opts(seqs: *const *const u8, lens: *const usize, n_refs: usize, opts: *const KboBuildOpts,
+                                     refset_opts: *const super::RefsetOpts, out: *mut *mut KboRefset) -> c_int;
+        pub fn kbo_refset_has_prefilter(set: *const KboRefset) -> c_int;
+        pub fn kbo_refset_prefilter_bytes(set: *const KboRefset) -> u64;
+        pub fn kbo_refset_candidates(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
+                                     bits_out: *mut u32, n_candidates: *mut u64) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -287,6 +297,30 @@ pub unsafe fn summary_refset(set: *mut ffi::KboRefset, seqs: &[Vec<u8>], max_err
     let out = std::slice::from_raw_parts(p, n as usize).to_vec();
     ffi::kbo_free(p as *mut c_void);
     out
+}
+
+/// `kbo_refset_opts`: `max_wide_rows` (16 384 ..= 2^20) and `prefilter` (0 or 1) of `kbo_refset_build_opts`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct RefsetOpts {
+    pub max_wide_rows: usize,
+    pub prefilter: i32,
+}
+
+/// `kbo_refset_candidates` over a set built with a prefilter: `out[(r * n_seqs + s) * 2 + strand - 1]` says whether sequence `s` on
+/// that strand shares a seed with reference `r` - every pair with a record is among them.
+///
+/// # Safety
+/// `set` is a live `kbo_refset_t`.
+pub unsafe fn refset_candidates(set: *mut ffi::KboRefset, n_refs: usize, seqs: &[Vec<u8>], max_error_prob: f64, strands: c_int) -> Vec<bool> {
+    let mut offsets = vec![0u64; seqs.len() + 1];
+    for (i, r) in seqs.iter().enumerate() { offsets[i + 1] = offsets[i] + r.len() as u64; }
+    let concat: Vec<u8> = seqs.concat();
+    let n_bits = n_refs * seqs.len() * 2;
+    let mut words = vec![0u32; (n_bits + 31) / 32];
+    check(ffi::kbo_refset_candidates(set, concat.as_ptr(), offsets.as_ptr(), seqs.len(), max_error_prob, strands, words.as_mut_ptr(),
+                                     std::ptr::null_mut()));
+    (0..n_bits).map(|b| words[b / 32] >> (b % 32) & 1 == 1).collect()
 }
 
 /// `kbo_best_refset` over a set handle a caller built with `kbo_refset_build`: one record per sequence, in sequence order.

@@ -514,6 +514,55 @@ int kbo_refset_build_wide(const uint8_t *const *seqs, const size_t *lens, size_t
                           kbo_refset_t **out);
 int kbo_refset_route(const kbo_refset_t *set, size_t r);   /* KBO_REFSET_ROUTE_*; KBO_E_BAD_ARG for r >= N or a null set */
 int kbo_refset_packed_only(const kbo_refset_t *set);       /* 1: no reference takes the single-index route */
+/* A set with a PREFILTER: an opt-in screen of the (reference, sequence, strand) pairs by shared seeds, for the packed routes (LDS
+ * and wide).  More than 99 % of the pairs of a gene database against an assembly produce nothing, and the walk of all of them is the
+ * cost of a call; the screen is exact.  From derandomize_ms_vec (derandomize.rs:221-247, 282-285) and translate_ms_val
+ * (translate.rs:190-213): when no noisy matching statistic of a sequence is > threshold or == k, every derandomised value is below 1
+ * and every character '-' - the pair has no run and no summary record.  So a pair can have a record only if, with t_r the threshold
+ * of reference r at this call's max_error_prob and w_r = min(t_r + 1, k), some w_r consecutive bases of the sequence on that strand
+ * occur in an indexed stretch of r.  The screen tests that with m_r = min(w_r, KBO_REFSET_SEED_MAX) bases.
+ * kbo_refset_build_opts(..., refset_opts, out) with refset_opts->prefilter = 0 is exactly kbo_refset_build_wide(max_wide_rows); with
+ * prefilter = 1 the set also carries a seed table, made on the host while the sequences are at hand: one entry for every start
+ * position of every indexed stretch - a maximal run of A, C, G, T of at least k bases, and its reverse complement when
+ * opts->add_revcomp is set - of every reference of a packed route that can be queried.  An entry holds the 2-bit code of the next
+ * KBO_REFSET_SEED_MAX bases (fewer at the stretch's end, and then how many) and the reference; entries are sorted by code, and an
+ * array of 4^KBO_REFSET_SEED_MIN + 1 offsets addresses them by their first KBO_REFSET_SEED_MIN bases.  Entries carry their reference
+ * and their length, so one table serves every max_error_prob.  12 bytes an entry + 16 MiB (kbo_refset_prefilter_bytes);
+ * kbo_refset_to_device uploads it with the arena.  References of the single-index route and references with a status have no entries.
+ *   KBO_REFSET_SEED_MAX = 24: the default thresholds (max_error_prob 1e-7) are 15 .. 18 for references of 0.3 .. 16 kbp and reach 21
+ *     at 2^20 rows, so m_r = w_r there; a stricter max_error_prob than the cap covers is screened with 24 bases - weaker, never
+ *     wrong.  The figure is reasoning, not measurement.
+ *   KBO_REFSET_SEED_MIN = 11: a reference with m_r below it cannot be screened at that max_error_prob - all its pairs are candidates
+ *     - so it should not exceed the m_r in use (max_error_prob 1e-4 gives m_r = 11 for a reference of 300 bases), and the offsets should stay
+ *     small against the 256 MiB Infinity Cache next to the entries: 16 MiB, where 12 bases would take 64 MiB and buy a bucket a
+ *     quarter as long - 0.5 entries a look-up instead of 0.12 for 2 x 10^6 entries, either of which is one cache line.
+ * kbo_find_refset, kbo_summary_refset and kbo_best_refset on such a set run ONE more kernel behind the upload
+ * (kbo_amd/csrc/refset_screen_kernels.hip) that marks the pairs sharing a seed of m_r bases, read the bitmap back (one more copy and
+ * one more synchronisation per call), and plan, upload and walk only the marked pairs.  Records are byte-identical with and without
+ * the prefilter.  References of the single-index route go through their pipeline unscreened.  A call whose bitmap would exceed 2^31
+ * bits (n_refs x n_seqs x 2) runs unscreened, with the same records.  kbo_best_refset's merge kernel finds a slab's pairs by
+ * arithmetic and cannot skip any: on a set with a prefilter the call runs kbo_summary_refset's slabs over the candidate pairs -
+ * their per-slab waits come back - and folds the kept records into the table on the host, by the merge of refset_best.hpp; the table
+ * is the same.  The device forms (kbo_*_refset_dev) IGNORE the prefilter: they plan on the device from closed forms over all pairs.
+ * kbo_refset_candidates runs the screen alone: bits_out receives ceil(n_refs x n_seqs x 2 / 32) words, bit
+ * (r x n_seqs + s) x 2 + (strand - 1); *n_candidates (may be NULL) the bits set.  For a reference that can be screened the bit is 1 if
+ * and only if sequence s on that strand holds m_r consecutive bytes that lie within the sequence, are all bases and occur as m_r
+ * consecutive bases of an indexed stretch of r - so every pair with a record has its bit set; a reference that cannot be screened at
+ * this max_error_prob has the bits of all its pairs set.  Bits of strands not asked for, and of references without entries, are 0.
+ * Errors: those of kbo_summary_refset; KBO_E_BAD_ARG for a set without a prefilter; KBO_E_UNSUPPORTED above 2^31 bits. */
+#define KBO_REFSET_SEED_MAX 24
+#define KBO_REFSET_SEED_MIN 11
+typedef struct {
+    size_t max_wide_rows; /* KBO_REFSET_MAX_ROWS: as kbo_refset_build; up to KBO_REFSET_WIDE_MAX_ROWS: as kbo_refset_build_wide */
+    int32_t prefilter;    /* 0 */
+} kbo_refset_opts;
+void kbo_refset_opts_default(kbo_refset_opts *o);
+int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts,
+                          const kbo_refset_opts *refset_opts, kbo_refset_t **out);
+int kbo_refset_has_prefilter(const kbo_refset_t *set);        /* 1 or 0 */
+uint64_t kbo_refset_prefilter_bytes(const kbo_refset_t *set); /* the seed table's bytes; 0 without one */
+int kbo_refset_candidates(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                          int strands, uint32_t *bits_out, uint64_t *n_candidates);
 /* The records with (ref = r, seq = s, strand) are, in order, exactly the runs kbo_find returns for sequence s - strand
  * KBO_STRAND_REV: for its reverse complement, in the coordinates of the reverse-complemented sequence as for kbo_find_batch_strands -
  * against reference r's own index: derandomised with the threshold of that index's n_kmers and opts->max_error_prob, run lengths

@@ -225,6 +225,22 @@ int kbo_refset_form(const kbo_refset_t *set, size_t r, uint8_t *out, size_t *n_b
  * step the wide kernel runs (kbo_amd/csrc/refset_step.hpp) over the set's host arena, unchunked.  No HIP call; not a fallback.
  * KBO_E_BAD_ARG as kbo_refset_form */
 int kbo_refset_ms_host(const kbo_refset_t *set, size_t r, const uint8_t *seq, size_t len, uint8_t *ms_out);
+/* start positions a lane of refset_screen_kernels.hip owns, lanes of its workgroups: lane boundaries lie at the multiples of
+ * KBO_REFSET_SCREEN_RUN bases of the concatenated batch, workgroup boundaries at those of RUN x THREADS */
+#define KBO_REFSET_SCREEN_RUN 64
+#define KBO_REFSET_SCREEN_THREADS 256
+/* test hook: kbo_refset_candidates restated on the CPU over the set's host table, by the seed, the shared prefix and the bucket scan
+ * the kernel runs (kbo_amd/csrc/refset_screen.hpp), a sequence at a time, unchunked.  Same arguments, bitmap and errors.  No HIP
+ * call; not a fallback */
+int kbo_refset_candidates_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                               double max_error_prob, int strands, uint32_t *bits_out, uint64_t *n_candidates);
+/* test hook: the bits of a call's bitmap (n_refs x n_seqs x 2) above which kbo_find_refset / kbo_summary_refset / kbo_best_refset on
+ * a set with a prefilter run unscreened (default and most 2^31; 0 restores the default) */
+int kbo_set_refset_prefilter_max_bits(uint64_t bits);
+/* what the calling thread's last kbo_find_refset / kbo_summary_refset / kbo_best_refset did with the prefilter: out[0] the
+ * (reference, sequence, strand) pairs of packed references, out[1] how many had their bit set (0 when the screen did not run),
+ * out[2] how many were walked, out[3] 1 if the screen ran, else 0 (no prefilter, or the bitmap above the cap) */
+int kbo_refset_last_prefilter(uint64_t out[4]);
 
 /* ------------------------------------------------------------------ kbo_derand_translate_seq_dev */
 /* positions of a chunk and of a group (64 chunks) of derand_seq_kernels.hip; neither spans two sequences.  A sequence of more than

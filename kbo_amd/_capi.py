@@ -38,6 +38,11 @@ class FindOpts(C.Structure):
     _fields_ = [("max_error_prob", C.c_double), ("max_gap_len", C.c_size_t)]
 
 
+class RefsetOpts(C.Structure):
+    """kbo_hip.h kbo_refset_opts"""
+    _fields_ = [("max_wide_rows", C.c_size_t), ("prefilter", C.c_int32)]
+
+
 class MapOpts(C.Structure):
     """kbo::MapOpts (lib.rs:412-466)."""
     _fields_ = [("max_error_prob", C.c_double), ("fill_gaps", C.c_int32), ("call_variants", C.c_int32),
@@ -123,6 +128,7 @@ SYMBOLS = [
     "kbo_summary_refset_dev",
     "kbo_refset_build_wide", "kbo_refset_route", "kbo_refset_packed_only",
     "kbo_best_refset", "kbo_best_refset_dev_work_bytes", "kbo_best_refset_dev",
+    "kbo_refset_opts_default", "kbo_refset_build_opts", "kbo_refset_has_prefilter", "kbo_refset_prefilter_bytes", "kbo_refset_candidates",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -134,6 +140,7 @@ TUNING_SYMBOLS = [
     "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
     "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
     "kbo_refset_last_wide", "kbo_refset_form", "kbo_refset_ms_host", "kbo_refset_last_best",
+    "kbo_refset_candidates_host", "kbo_set_refset_prefilter_max_bits", "kbo_refset_last_prefilter",
 ]
 
 _lib = None
@@ -347,6 +354,14 @@ def lib():
     L.kbo_best_refset_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz]; L.kbo_best_refset_dev_work_bytes.restype = sz
     L.kbo_best_refset_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, vp]
     L.kbo_refset_last_best.argtypes = [vp]
+    L.kbo_refset_opts_default.argtypes = [C.POINTER(RefsetOpts)]; L.kbo_refset_opts_default.restype = None
+    L.kbo_refset_build_opts.argtypes = [C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.POINTER(BuildOpts), C.POINTER(RefsetOpts), C.POINTER(vp)]
+    L.kbo_refset_has_prefilter.argtypes = [vp]
+    L.kbo_refset_prefilter_bytes.argtypes = [vp]; L.kbo_refset_prefilter_bytes.restype = u64
+    L.kbo_refset_candidates.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, vp, C.POINTER(u64)]
+    L.kbo_refset_candidates_host.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, vp, C.POINTER(u64)]
+    L.kbo_set_refset_prefilter_max_bits.argtypes = [u64]
+    L.kbo_refset_last_prefilter.argtypes = [vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

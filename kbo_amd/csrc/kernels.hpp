@@ -627,6 +627,26 @@ bool refset_best_splits(uint32_t n_seqs);
 hipError_t launch_refset_best_init(uint32_t *d_table, uint32_t n_seqs, hipStream_t stream); // n_seqs < 2^28
 hipError_t launch_refset_best(const RefsetBestArgs &a, hipStream_t stream);                 // one launch; none for n_pairs == 0
 
+// ---- the seed screen of a reference set (refset_screen_kernels.hip; the seed and the bucket scan: refset_screen.hpp).  The table is
+// the set's: kBuckets + 1 offsets, then per entry a key (code << 16 | valid bases) and its reference, sorted by key.  A lane owns
+// kRefsetScreenRun consecutive start positions of one strand of the batch, a workgroup kRefsetScreenThreads lanes; m: per reference,
+// the shared bases that mark a pair (refscreen::kUnfilterable: never).  Bit (r * n_seqs + s) * 2 + strand - 1 of `bits` is set with
+// atomicOr; the caller zeroes the bitmap.  n_refs * n_seqs * 2 <= 2^31 and total < 2^31.
+constexpr uint32_t kRefsetScreenRun = 64;
+constexpr uint32_t kRefsetScreenThreads = 256;
+struct RefsetScreenArgs {
+    const uint32_t *bucket;
+    const uint64_t *keys;
+    const uint32_t *refs;
+    const uint8_t *m;       // n_refs bytes
+    const uint8_t *q;       // the batch, 16-byte aligned: '+' at q, '-' at q + rev_base
+    const uint64_t *off;    // n_seqs + 1, from 0
+    uint32_t *bits;
+    uint64_t total, rev_base; // rev_base: a multiple of 16, >= total
+    uint32_t n_seqs, strands, first_strand; // strands: 1, 2 or 3; first_strand: 2 for strands == 2, else 1
+};
+hipError_t launch_refset_screen(const RefsetScreenArgs &a, hipStream_t stream); // one launch; none for total == 0
+
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256
 void set_walk_experiment(int lane_limit, int dummy_lds_bytes); // experiments behind DESIGN.md section 6

@@ -6,9 +6,13 @@
 // derandomize / translate stage and keeps the pairs with a hit on the device: no characters, no run-length stage.
 // kbo_best_refset shares all of that up to the extents and merges them, slab by slab, into a table of one record per sequence on the
 // device (refset_best_kernels.hip): no record stage, nothing read back until the last slab is enqueued.
+// A set built with a prefilter (kbo_refset_build_opts) carries a seed table (refset_screen.hpp); the host forms then mark the pairs
+// that share a seed with one kernel over the uploaded batch (refset_screen_kernels.hip), read the bitmap back, and plan, upload and
+// walk only the marked pairs.  kbo_refset_candidates is that screen alone, kbo_refset_candidates_host its restatement on the CPU.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 #include "refset_best.hpp"
+#include "refset_screen.hpp"
 #include "refset_step.hpp"
 
 #include <algorithm>
@@ -21,14 +25,22 @@ static_assert(kbo::kRefsetWideMaxRows == KBO_REFSET_WIDE_MAX_ROWS && kbo::kRefse
                   kbo::kRefsetRouteIndex == KBO_REFSET_ROUTE_INDEX && kbo::kRefsetRouteWide == KBO_REFSET_ROUTE_WIDE,
               "kbo_hip.h states the wide walk's constants");
 
+static_assert(kbo::refscreen::kSeedMax == KBO_REFSET_SEED_MAX && kbo::refscreen::kSeedMin == KBO_REFSET_SEED_MIN &&
+                  kbo::kRefsetScreenRun == KBO_REFSET_SCREEN_RUN && kbo::kRefsetScreenThreads == KBO_REFSET_SCREEN_THREADS,
+              "the headers state the screen's constants");
+
 namespace {
+constexpr uint64_t kPrefilterMaxBits = 1ull << 31; // the bitmap is read back: above this many bits a call runs unscreened
 std::atomic<size_t> g_record_capacity{1u << 16};
+std::atomic<uint64_t> g_prefilter_max_bits{kPrefilterMaxBits};
+thread_local uint64_t t_pre[4] = {0, 0, 0, 0}; // pairs of packed references, with their bit set, walked; the screen ran
 thread_local uint64_t t_routes[4] = {0, 0, 0, 0};
 thread_local uint64_t t_wide[2] = {0, 0}; // references walked by the wide kernel, the tasks it was launched with
 thread_local uint64_t t_best[2] = {0, 0}; // launches of refset_best_kernel: a wave per sequence, a workgroup per sequence
 
 struct DevSet {
     DevBuf arena, descs;
+    DevBuf pre_bucket, pre_keys, pre_refs; // the seed table of a set with a prefilter
 };
 
 struct DeviceScope { // the calling thread on `device` until the scope ends
@@ -66,6 +78,10 @@ struct kbo_refset {
     std::vector<kbo::RefsetDesc> descs;
     std::vector<uint32_t> arena;                  // the packed forms (LDS and wide references) back to back, four words a unit
     std::vector<std::unique_ptr<kbo_index>> own;  // per reference: its ordinary index when it takes the single-index route, else null
+    // the seed table of a set built with a prefilter (refset_screen.hpp): bucket offsets, then the entries sorted by key
+    bool prefilter = false;
+    std::vector<uint32_t> pre_bucket, pre_refs;
+    std::vector<uint64_t> pre_keys;
     std::mutex mu;
     std::map<int, DevSet *> dev;
     ~kbo_refset()
@@ -109,6 +125,17 @@ DevSet *device_set(kbo_refset *set, int device)
     d->descs.alloc(set->descs.size() * sizeof(kbo::RefsetDesc));
     if (!set->arena.empty()) HIP_OK(hipMemcpy(d->arena.p, set->arena.data(), set->arena.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d->descs.p, set->descs.data(), set->descs.size() * sizeof(kbo::RefsetDesc), hipMemcpyHostToDevice));
+    if (set->prefilter) {
+        const size_t n = set->pre_keys.size();
+        d->pre_bucket.alloc(set->pre_bucket.size() * sizeof(uint32_t));
+        d->pre_keys.alloc(n * sizeof(uint64_t));
+        d->pre_refs.alloc(n * sizeof(uint32_t));
+        HIP_OK(hipMemcpy(d->pre_bucket.p, set->pre_bucket.data(), set->pre_bucket.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (n) {
+            HIP_OK(hipMemcpy(d->pre_keys.p, set->pre_keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d->pre_refs.p, set->pre_refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+    }
     set->dev[device] = d.get();
     return d.release();
 }
@@ -446,8 +473,175 @@ void upload_batch(SlabWalker &F, kbo_refset *set, const uint8_t *concat, const u
         HIP_OK(kbo::launch_revcomp_bytes(F.d_q.as<uint8_t>(), F.d_off.as<uint64_t>(), (uint32_t)n_seqs, total, F.d_q.as<uint8_t>() + F.rev_base, F.st));
 }
 
+
+// ---- the seed screen (refset_screen.hpp; refset_screen_kernels.hip)
+struct HostTable { // refset_screen.hpp's accessor over the set's host table
+    const kbo_refset *set;
+    uint32_t bucket(uint32_t b) const { return set->pre_bucket[b]; }
+    uint64_t key(uint32_t x) const { return set->pre_keys[x]; }
+    uint32_t ref(uint32_t x) const { return set->pre_refs[x]; }
+};
+
+bool packed_ok(const kbo::RefsetDesc &d) { return !d.status && d.route != kbo::kRefsetRouteIndex; }
+
+// One entry per start position of every indexed stretch (a maximal run of bases of at least k, as build_host_index sees them; its
+// reverse complement too with add_revcomp) of every packed reference that can be queried, sorted by key, and the bucket offsets
+void build_prefilter(kbo_refset *set, const uint8_t *const *seqs, const size_t *lens, bool add_revcomp)
+{
+    namespace sc = kbo::refscreen;
+    std::vector<std::pair<uint64_t, uint32_t>> entries;
+    std::vector<uint8_t> rc;
+    auto add_stretch = [&](const uint8_t *b, size_t n, uint32_t r) { // right to left: the seed at i is base i in front of the one at i + 1
+        sc::Seed seed{0u, 0u};
+        for (size_t i = n; i-- > 0;) {
+            seed = sc::step_left(seed, b[i]);
+            entries.emplace_back(sc::key_of(seed), r);
+        }
+    };
+    for (size_t r = 0; r < set->descs.size(); r++) {
+        if (!packed_ok(set->descs[r])) continue;
+        const uint8_t *q = seqs[r];
+        for (size_t i = 0, n = lens[r]; i < n;) {
+            if (kbo::refstep::base_code(q[i]) > 3u) {
+                i++;
+                continue;
+            }
+            size_t j = i;
+            while (j < n && kbo::refstep::base_code(q[j]) <= 3u) j++;
+            if (j - i >= set->k) {
+                add_stretch(q + i, j - i, (uint32_t)r);
+                if (add_revcomp) {
+                    rc.resize(j - i);
+                    for (size_t x = 0; x < j - i; x++) rc[x] = (uint8_t)"TGCA"[kbo::refstep::base_code(q[j - 1 - x])];
+                    add_stretch(rc.data(), rc.size(), (uint32_t)r);
+                }
+            }
+            i = j;
+        }
+    }
+    KBO_REQUIRE(entries.size() < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "the set's seed table exceeds 2^32 - 1 entries");
+    std::sort(entries.begin(), entries.end());
+    set->pre_bucket.assign((size_t)sc::kBuckets + 1, 0u);
+    set->pre_keys.resize(entries.size());
+    set->pre_refs.resize(entries.size());
+    for (size_t x = 0; x < entries.size(); x++) {
+        set->pre_keys[x] = entries[x].first;
+        set->pre_refs[x] = entries[x].second;
+        set->pre_bucket[(size_t)sc::bucket_of(entries[x].first >> 16) + 1]++;
+    }
+    for (size_t b = 0; b < sc::kBuckets; b++) set->pre_bucket[b + 1] += set->pre_bucket[b];
+    set->prefilter = true;
+}
+
+// the bitmap of a call: bit (r * n_seqs + s) * 2 + strand - 1
+struct Screen {
+    size_t n_seqs = 0;
+    std::vector<uint32_t> bits;
+    bool test(size_t r, size_t s, uint32_t strand) const
+    {
+        const uint64_t b = ((uint64_t)r * n_seqs + s) * 2u + (strand - 1u);
+        return bits[b >> 5] >> (b & 31u) & 1u;
+    }
+    void set_bit(size_t r, size_t s, uint32_t strand)
+    {
+        const uint64_t b = ((uint64_t)r * n_seqs + s) * 2u + (strand - 1u);
+        bits[b >> 5] |= 1u << (b & 31u);
+    }
+    uint64_t count() const
+    {
+        uint64_t n = 0;
+        for (uint32_t w : bits) n += (uint64_t)__builtin_popcount(w);
+        return n;
+    }
+};
+
+uint64_t screen_bits(const kbo_refset *set, size_t n_seqs) { return (uint64_t)set->descs.size() * n_seqs * 2u; }
+
+// m_r of every reference for this call's thresholds; 0: the reference is not packed or cannot be queried (it has no entries)
+std::vector<uint8_t> seed_lens(const kbo_refset *set, const std::vector<uint32_t> &thr)
+{
+    std::vector<uint8_t> m(set->descs.size(), 0);
+    for (size_t r = 0; r < m.size(); r++)
+        if (packed_ok(set->descs[r])) m[r] = (uint8_t)kbo::refscreen::seed_len(thr[r], set->k);
+    return m;
+}
+
+// a packed reference whose m_r does not reach a bucket's bases cannot be screened: all its pairs of the strands asked for are candidates
+void mark_unfilterable(const std::vector<uint8_t> &m, int strands, Screen &scr)
+{
+    for (size_t r = 0; r < m.size(); r++) {
+        if (m[r] == 0 || m[r] >= kbo::refscreen::kSeedMin) continue;
+        for (size_t s = 0; s < scr.n_seqs; s++)
+            for (uint32_t strand = 1; strand <= 2; strand++)
+                if (strands & strand) scr.set_bit(r, s, strand);
+    }
+}
+
+// the screen kernel over the batch upload_batch put on the device; the bitmap comes back (one copy, one wait)
+void run_screen(SlabWalker &F, const std::vector<uint32_t> &thr, size_t n_seqs, uint64_t total, int strands, Screen &scr)
+{
+    const kbo_refset *set = F.set;
+    const size_t n_refs = set->descs.size(), words = (size_t)((screen_bits(set, n_seqs) + 31) / 32);
+    const std::vector<uint8_t> m = seed_lens(set, thr);
+    std::vector<uint8_t> dev_m(n_refs);
+    for (size_t r = 0; r < n_refs; r++) dev_m[r] = m[r] >= kbo::refscreen::kSeedMin ? m[r] : (uint8_t)kbo::refscreen::kUnfilterable;
+    DevBuf d_bits(words * sizeof(uint32_t)), d_m(n_refs);
+    HIP_OK(hipMemsetAsync(d_bits.p, 0, words * sizeof(uint32_t), F.st));
+    HIP_OK(hipMemcpyAsync(d_m.p, dev_m.data(), n_refs, hipMemcpyHostToDevice, F.st));
+    kbo::RefsetScreenArgs a;
+    a.bucket = F.ds->pre_bucket.as<uint32_t>();
+    a.keys = F.ds->pre_keys.as<uint64_t>();
+    a.refs = F.ds->pre_refs.as<uint32_t>();
+    a.m = d_m.as<uint8_t>();
+    a.q = F.d_q.as<uint8_t>();
+    a.off = F.d_off.as<uint64_t>();
+    a.bits = d_bits.as<uint32_t>();
+    a.total = total;
+    a.rev_base = F.rev_base;
+    a.n_seqs = (uint32_t)n_seqs;
+    a.strands = (uint32_t)strands;
+    a.first_strand = strands == 2 ? 2u : 1u;
+    HIP_OK(kbo::launch_refset_screen(a, F.st));
+    scr.n_seqs = n_seqs;
+    scr.bits.assign(words, 0u);
+    HIP_OK(hipMemcpyAsync(scr.bits.data(), d_bits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, F.st));
+    HIP_OK(hipStreamSynchronize(F.st));
+    mark_unfilterable(m, strands, scr);
+}
+
+// what a host call does behind upload_batch: the counters of kbo_refset_last_prefilter, and the screen when the set has a prefilter
+// and the bitmap is within the cap.  Returns the screen run_slabs goes by, or null: every pair.
+const Screen *screen_call(SlabWalker &F, const std::vector<uint32_t> &thr, size_t n_seqs, uint64_t total, int strands, Screen &scr)
+{
+    const kbo_refset *set = F.set;
+    uint64_t packed = 0;
+    for (const kbo::RefsetDesc &d : set->descs) packed += packed_ok(d);
+    std::fill(t_pre, t_pre + 4, 0);
+    t_pre[0] = packed * n_seqs * (strands == 3 ? 2u : 1u);
+    if (!set->prefilter || screen_bits(set, n_seqs) > g_prefilter_max_bits.load()) return nullptr;
+    run_screen(F, thr, n_seqs, total, strands, scr);
+    t_pre[1] = scr.count();
+    t_pre[3] = 1;
+    return &scr;
+}
+
+// the checks kbo_refset_candidates and its host form share, all before any work; the thresholds
+std::vector<uint32_t> check_candidates(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                                       double max_error_prob, int strands, const uint32_t *bits_out, uint64_t *total)
+{
+    KBO_REQUIRE(strands >= 1 && strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(set && bits_out, KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(set->prefilter, KBO_E_BAD_ARG, "the set has no prefilter (kbo_refset_build_opts)");
+    std::vector<uint32_t> thr = refset_thresholds(set, max_error_prob);
+    *total = check_refset_batch(set, concat, offsets, n_seqs);
+    KBO_REQUIRE(screen_bits(set, n_seqs) <= kPrefilterMaxBits, KBO_E_UNSUPPORTED, "a bitmap of more than 2^31 bits");
+    return thr;
+}
+
 // the references of the packed form, LDS and wide: every pair carries its reference's threshold, so a slab is cut by the budget alone
-template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, size_t n_seqs, int strands)
+// With a screen (a set with a prefilter), only the pairs whose bit is set: the slabs are cut by the candidates alone, a reference
+// none of whose pairs is one appears in no slab, and a call without a candidate runs no slab at all.
+template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, size_t n_seqs, int strands, const Screen *screen)
 {
     const kbo_refset *set = f.set;
     const size_t n_refs = set->descs.size();
@@ -462,6 +656,8 @@ template <typename F> void run_slabs(F &f, const std::vector<uint32_t> &thr, siz
         for (size_t s = 0; s < n_seqs; s++)
             for (uint32_t strand = 1; strand <= 2; strand++) {
                 if (!(strands & strand)) continue;
+                if (screen && !screen->test(r, s, strand)) continue;
+                t_pre[2]++;
                 const uint64_t len = f.offsets[s + 1] - f.offsets[s];
                 if (P.pairs() && P.bytes() + len > budget) {
                     f.run_slab(P);
@@ -734,9 +930,29 @@ int kbo_refset_build(const uint8_t *const *seqs, const size_t *lens, size_t n_re
 int kbo_refset_build_wide(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts, size_t max_wide_rows,
                           kbo_refset_t **out)
 {
+    kbo_refset_opts ro;
+    kbo_refset_opts_default(&ro);
+    ro.max_wide_rows = max_wide_rows;
+    return kbo_refset_build_opts(seqs, lens, n_refs, opts, &ro, out);
+}
+
+void kbo_refset_opts_default(kbo_refset_opts *o)
+{
+    if (!o) return;
+    o->max_wide_rows = KBO_REFSET_MAX_ROWS;
+    o->prefilter = 0;
+}
+
+int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts,
+                          const kbo_refset_opts *refset_opts, kbo_refset_t **out)
+{
     return guarded([&] {
         KBO_REQUIRE(out, KBO_E_BAD_ARG, "null out");
         *out = nullptr;
+        kbo_refset_opts ro;
+        if (refset_opts) ro = *refset_opts; else kbo_refset_opts_default(&ro);
+        const size_t max_wide_rows = ro.max_wide_rows;
+        KBO_REQUIRE(ro.prefilter == 0 || ro.prefilter == 1, KBO_E_BAD_ARG, "prefilter: 0 or 1");
         KBO_REQUIRE(max_wide_rows >= KBO_REFSET_MAX_ROWS && max_wide_rows <= KBO_REFSET_WIDE_MAX_ROWS, KBO_E_BAD_ARG,
                     "max_wide_rows in KBO_REFSET_MAX_ROWS .. KBO_REFSET_WIDE_MAX_ROWS");
         KBO_REQUIRE(seqs && lens && n_refs > 0, KBO_E_BAD_ARG, "assert!(!slices.is_empty()) (index.rs:60)");
@@ -792,6 +1008,7 @@ int kbo_refset_build_wide(const uint8_t *const *seqs, const size_t *lens, size_t
             set->arena.insert(set->arena.end(), forms[r].begin(), forms[r].end());
             std::vector<uint32_t>().swap(forms[r]);
         }
+        if (ro.prefilter) build_prefilter(set.get(), seqs, lens, o.add_revcomp != 0); // (the sequences are at hand here only)
         *out = set.release();
     });
 }
@@ -883,6 +1100,85 @@ int kbo_refset_ms_host(const kbo_refset_t *set, size_t r, const uint8_t *seq, si
     return KBO_OK;
 }
 
+int kbo_refset_has_prefilter(const kbo_refset_t *set) { return set && set->prefilter ? 1 : 0; }
+
+uint64_t kbo_refset_prefilter_bytes(const kbo_refset_t *set)
+{
+    if (!set || !set->prefilter) return 0;
+    return (uint64_t)set->pre_bucket.size() * sizeof(uint32_t) + (uint64_t)set->pre_keys.size() * (sizeof(uint64_t) + sizeof(uint32_t));
+}
+
+int kbo_set_refset_prefilter_max_bits(uint64_t bits)
+{
+    g_prefilter_max_bits = bits == 0 || bits > kPrefilterMaxBits ? kPrefilterMaxBits : bits;
+    return KBO_OK;
+}
+
+int kbo_refset_last_prefilter(uint64_t out[4])
+{
+    if (!out) return KBO_E_BAD_ARG;
+    std::copy(t_pre, t_pre + 4, out);
+    return KBO_OK;
+}
+
+int kbo_refset_candidates(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                          int strands, uint32_t *bits_out, uint64_t *n_candidates)
+{
+    return guarded([&] {
+        uint64_t total = 0;
+        const std::vector<uint32_t> thr = check_candidates(set, concat, offsets, n_seqs, max_error_prob, strands, bits_out, &total);
+        SlabWalker F;
+        StreamScope stream;
+        upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+        Screen scr;
+        run_screen(F, thr, n_seqs, total, strands, scr);
+        std::copy(scr.bits.begin(), scr.bits.end(), bits_out);
+        if (n_candidates) *n_candidates = scr.count();
+    });
+}
+
+int kbo_refset_candidates_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                               double max_error_prob, int strands, uint32_t *bits_out, uint64_t *n_candidates)
+{
+    return guarded([&] {
+        namespace sc = kbo::refscreen;
+        uint64_t total = 0;
+        const std::vector<uint32_t> thr = check_candidates(set, concat, offsets, n_seqs, max_error_prob, strands, bits_out, &total);
+        const std::vector<uint8_t> m = seed_lens(set, thr);
+        Screen scr;
+        scr.n_seqs = n_seqs;
+        scr.bits.assign((size_t)((screen_bits(set, n_seqs) + 31) / 32), 0u);
+        const HostTable table{set};
+        std::vector<uint8_t> rc;
+        for (size_t s = 0; s < n_seqs; s++) {
+            const uint8_t *fwd = concat + offsets[s];
+            const size_t len = (size_t)(offsets[s + 1] - offsets[s]);
+            for (uint32_t strand = 1; strand <= 2; strand++) {
+                if (!(strands & strand)) continue;
+                const uint8_t *q = fwd;
+                if (strand == KBO_STRAND_REV) { // (revcomp_kernels.hip: A <-> T, C <-> G in either case, any other byte as it is)
+                    rc.resize(len);
+                    for (size_t i = 0; i < len; i++) {
+                        const uint8_t b = fwd[len - 1 - i], u = b & 0xDFu;
+                        rc[i] = u == 'A' || u == 'T' ? b ^ ('A' ^ 'T') : (u == 'C' || u == 'G' ? b ^ ('C' ^ 'G') : b);
+                    }
+                    q = rc.data();
+                }
+                sc::Seed seed{0u, 0u};
+                for (size_t i = len; i-- > 0;) {
+                    seed = sc::step_left(seed, q[i]);
+                    sc::scan(table, seed, [&](uint32_t r, uint32_t shared) {
+                        if (m[r] >= sc::kSeedMin && shared >= m[r]) scr.set_bit(r, s, strand);
+                    });
+                }
+            }
+        }
+        mark_unfilterable(m, strands, scr);
+        std::copy(scr.bits.begin(), scr.bits.end(), bits_out);
+        if (n_candidates) *n_candidates = scr.count();
+    });
+}
+
 int kbo_refset_last_routes(uint64_t out[4])
 {
     if (!out) return KBO_E_BAD_ARG;
@@ -912,7 +1208,8 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
         F.gap = (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu);
         StreamScope stream;
         upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
-        run_slabs(F, thr, n_seqs, strands);
+        Screen scr;
+        run_slabs(F, thr, n_seqs, strands, screen_call(F, thr, n_seqs, total, strands, scr));
 
         // the references of the single-index route: their own index through that pipeline, one at a time
         std::vector<uint64_t> rle_off(2 * n_seqs + 1);
@@ -961,7 +1258,8 @@ int kbo_summary_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t 
         Summarizer F;
         StreamScope stream;
         upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
-        run_slabs(F, thr, n_seqs, strands);
+        Screen scr;
+        run_slabs(F, thr, n_seqs, strands, screen_call(F, thr, n_seqs, total, strands, scr));
 
         // the references of the single-index route: the characters of that pipeline, counted here
         std::vector<uint8_t> fwd, rev;
@@ -1059,18 +1357,35 @@ int kbo_best_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
 
         const size_t n_refs = set->descs.size();
         const uint32_t n_strands = strands == 3 ? 2 : 1;
-        Bester F;
-        F.n_seqs = (uint32_t)n_seqs;
-        F.n_strands = n_strands;
-        F.strands = (uint32_t)strands;
-        StreamScope stream;
-        upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
-        F.d_table.alloc(n_seqs * sizeof(kbo_ref_best));
-        HIP_OK(kbo::launch_refset_best_init(F.d_table.as<uint32_t>(), (uint32_t)n_seqs, stream.s));
-        run_slabs(F, thr, n_seqs, strands);
         MallocPtr<kbo_ref_best> res = malloc_array<kbo_ref_best>(n_seqs);
-        HIP_OK(hipMemcpyAsync(res.get(), F.d_table.p, n_seqs * sizeof(kbo_ref_best), hipMemcpyDeviceToHost, stream.s));
-        HIP_OK(hipStreamSynchronize(stream.s)); // the call's one wait
+        StreamScope stream;
+        if (set->prefilter) {
+            // refset_best_kernel finds a slab's pairs by arithmetic and cannot skip any: the summary's slabs over the candidate pairs,
+            // and the kept records folded into the table here, by the merge the single-index references go through below
+            Summarizer F;
+            upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+            Screen scr;
+            run_slabs(F, thr, n_seqs, strands, screen_call(F, thr, n_seqs, total, strands, scr));
+            std::vector<rb::Best> table(n_seqs);
+            for (size_t s = 0; s < n_seqs; s++) table[s] = rb::empty((uint32_t)s);
+            for (const kbo_ref_summary &w : F.out) {
+                const uint32_t ext[6] = {w.aln.n_match, w.aln.n_mismatch, w.aln.n_jump, w.aln.n_runs, w.aln.start, w.aln.end};
+                table[w.seq] = rb::merge(table[w.seq], rb::from_pair(w.seq, w.ref, w.strand, ext));
+            }
+            std::memcpy(res.get(), table.data(), n_seqs * sizeof(kbo_ref_best));
+        } else {
+            Bester F;
+            F.n_seqs = (uint32_t)n_seqs;
+            F.n_strands = n_strands;
+            F.strands = (uint32_t)strands;
+            upload_batch(F, set, concat, offsets, n_seqs, total, strands, stream.s);
+            F.d_table.alloc(n_seqs * sizeof(kbo_ref_best));
+            HIP_OK(kbo::launch_refset_best_init(F.d_table.as<uint32_t>(), (uint32_t)n_seqs, stream.s));
+            Screen scr;
+            run_slabs(F, thr, n_seqs, strands, screen_call(F, thr, n_seqs, total, strands, scr));
+            HIP_OK(hipMemcpyAsync(res.get(), F.d_table.p, n_seqs * sizeof(kbo_ref_best), hipMemcpyDeviceToHost, stream.s));
+            HIP_OK(hipStreamSynchronize(stream.s)); // the call's one wait
+        }
 
         // the references of the single-index route: the characters of that pipeline, counted and merged here
         std::vector<uint8_t> fwd, rev;

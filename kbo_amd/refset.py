@@ -11,6 +11,7 @@ STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
 # kbo_refset_route: the reference has a status / the LDS kernel / the single-index pipeline / the packed form walked from memory
 ROUTE_NONE, ROUTE_LDS, ROUTE_INDEX, ROUTE_WIDE = -1, 0, 1, 2
 MAX_ROWS, WIDE_MAX_ROWS = 16384, 1 << 20  # KBO_REFSET_MAX_ROWS, KBO_REFSET_WIDE_MAX_ROWS
+SEED_MAX, SEED_MIN = 24, 11  # KBO_REFSET_SEED_MAX, KBO_REFSET_SEED_MIN: bases of a seed's code, bases that address a bucket
 
 # kbo_ref_run (40 bytes): which (reference, sequence, strand) a run belongs to + the fields of format::RLE (format.rs:18-33)
 REF_RUN = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32), ("start", np.uint32), ("end", np.uint32),
@@ -37,10 +38,12 @@ class RefSet:
         self._h = handle
 
     @classmethod
-    def build(cls, seqs, build_opts=None, wide_rows=None):
+    def build(cls, seqs, build_opts=None, wide_rows=None, prefilter=False):
         """wide_rows: None - kbo_refset_build: a reference of more than MAX_ROWS rows takes the single-index route; a number in
         MAX_ROWS .. WIDE_MAX_ROWS - kbo_refset_build_wide: references of up to that many rows keep their packed form in the set and
-        take the wide route, in the same slabs as the small ones, and a set without a larger one can go to find_refset_dev"""
+        take the wide route, in the same slabs as the small ones, and a set without a larger one can go to find_refset_dev.
+        prefilter: kbo_refset_build_opts with a seed table - find_refset, summary_refset and best_refset then screen the (reference,
+        sequence, strand) pairs on the device and walk only those that share a seed; the records are the same"""
         from . import BuildOpts
         o = build_opts if build_opts is not None else BuildOpts()
         raw = [bytes(_u8(s)) for s in seqs]
@@ -48,7 +51,10 @@ class RefSet:
         lens = (C.c_size_t * max(1, len(raw)))(*[len(s) for s in raw])
         co = o._to_c()
         h = C.c_void_p()
-        if wide_rows is None:
+        if prefilter:
+            ro = _capi.RefsetOpts(MAX_ROWS if wide_rows is None else int(wide_rows), 1)
+            check(lib().kbo_refset_build_opts(arr, lens, len(raw), C.byref(co), C.byref(ro), C.byref(h)))
+        elif wide_rows is None:
             check(lib().kbo_refset_build(arr, lens, len(raw), C.byref(co), C.byref(h)))
         else:
             check(lib().kbo_refset_build_wide(arr, lens, len(raw), C.byref(co), int(wide_rows), C.byref(h)))
@@ -86,6 +92,29 @@ class RefSet:
             check(v)
         return v
 
+    @property
+    def has_prefilter(self):
+        """True for a set built with prefilter=True"""
+        return bool(lib().kbo_refset_has_prefilter(self._h))
+
+    def prefilter_bytes(self):
+        """bytes of the seed table (bucket offsets + 12 an entry); 0 without a prefilter"""
+        return int(lib().kbo_refset_prefilter_bytes(self._h))
+
+    def candidates(self, query_seqs, max_error_prob=1e-7, strands=STRAND_BOTH, host=False):
+        """kbo_refset_candidates: the screen alone - a boolean array [n_refs, n_seqs, 2], True where sequence s on strand '+' (0) or
+        '-' (1) shares a seed of the length this max_error_prob needs with reference r: every pair with a record is among them.
+        host=True: the restatement on the CPU (kbo_refset_candidates_host, a test hook)"""
+        concat, offsets, n = _batch(query_seqs)
+        n_bits = len(self) * n * 2
+        words = np.zeros((n_bits + 31) // 32, dtype=np.uint32)
+        cnt = C.c_uint64()
+        f = lib().kbo_refset_candidates_host if host else lib().kbo_refset_candidates
+        check(f(self._h, concat.ctypes.data, offsets.ctypes.data, n, float(max_error_prob), int(strands), words.ctypes.data, C.byref(cnt)))
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_bits].astype(bool)
+        assert int(bits.sum()) == cnt.value
+        return bits.reshape(len(self), n, 2)
+
     def form(self, r):
         """test hook: the packed form of an LDS or wide reference, as bytes in a uint8 array"""
         n = C.c_size_t()
@@ -105,6 +134,14 @@ class RefSet:
         if getattr(self, "_h", None):
             lib().kbo_refset_free(self._h)
             self._h = None
+
+
+def _batch(query_seqs):
+    raw = [_u8(s) for s in query_seqs]
+    concat = np.ascontiguousarray(np.concatenate(raw) if raw else np.zeros(0, dtype=np.uint8))
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(s) for s in raw], dtype=np.uint64)
+    return concat, offsets, len(raw)
 
 
 def find_refset(query_seqs, refset, find_opts=None, strands=STRAND_BOTH):
@@ -264,6 +301,19 @@ def last_best():
     out = (C.c_uint64 * 2)()
     check(lib().kbo_refset_last_best(out))
     return tuple(int(v) for v in out)
+
+
+def last_prefilter():
+    """(pairs of packed references, pairs with their bit set, pairs walked, 1 if the screen ran) of the calling thread's last
+    find_refset, summary_refset or best_refset"""
+    out = (C.c_uint64 * 4)()
+    check(lib().kbo_refset_last_prefilter(out))
+    return tuple(int(v) for v in out)
+
+
+def set_prefilter_max_bits(bits):
+    """test hook: the bitmap size (n_refs x n_seqs x 2 bits) above which a call on a set with a prefilter runs unscreened; 0: 2^31"""
+    check(lib().kbo_set_refset_prefilter_max_bits(int(bits)))
 
 
 def last_routes():

@@ -24,6 +24,12 @@ caller did before it: kbo_summary_refset plus the fold of its records in numpy (
 record of every contig, the first of another reference).  Both in one session, median of REPEATS behind a warm-up; the seconds of
 each, of the fold alone, the records the summary sent, and the CRC of the best records next to the CRC of the folded summary records
 (they must be equal).  LOOP, SUMMARY and DEV do not apply.
+PREFILTER=1 is a leg of its own: the same call on the same references built without and with the seed table (RefSet.build(...,
+prefilter=True)), in one session: kbo_find_refset, with SUMMARY=1 kbo_summary_refset, with BEST=1 kbo_best_refset, on the first
+workload or, with WIDE=1, on the wide leg's references as a set of the wide route.  Median of REPEATS behind a warm-up for both sets;
+the seconds of both, whether the records' CRCs are equal, kbo_refset_last_prefilter's counters (pairs of packed references, with
+their bit set, walked, whether the screen ran), and the table's bytes and the seconds its build added.  LOOP and DEV do not apply.
+The screen kernel's own time: run this under a kernel trace and read refset_screen_kernel's row.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -43,6 +49,7 @@ REFS, REF_BP, QUERY_BP, CONTIGS, LOOP, REPEATS, SUMMARY = (int(os.environ.get(n,
 DEV, REFS_PER_SLAB, DEV_CAPACITY = (int(os.environ.get(n, d)) for n, d in (("DEV", 0), ("REFS_PER_SLAB", 64), ("DEV_CAPACITY", 1 << 20)))
 WIDE, WIDE_REFS, WIDE_BP = (int(os.environ.get(n, d)) for n, d in (("WIDE", 0), ("WIDE_REFS", 300), ("WIDE_BP", 50_000)))
 BEST = int(os.environ.get("BEST", 0))
+PREFILTER = int(os.environ.get("PREFILTER", 0))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -66,9 +73,9 @@ import torch  # noqa: E402
 assert torch.cuda.is_available(), "this measures the GPU path: no device, no number"
 
 
-def wide_leg():
-    """the same large references as a set of the single-index route and as a set of the wide route, one process.  (It plants its copies in
-    the module's `contigs` AFTER `concat` was made of them: the leg passes `contigs` to its calls and exits, no other leg runs behind it)"""
+def wide_refs():
+    """the wide leg's references.  (It plants its copies in the module's `contigs` AFTER `concat` was made of them: a leg that takes
+    them passes `contigs` to its calls and exits, no other leg runs behind it)"""
     big = [ACGT[rng.integers(0, 4, WIDE_BP)] for _ in range(WIDE_REFS)]
     for i, r in enumerate(range(0, WIDE_REFS, 10)):  # a stretch of every 10th reference with 1 % substitutions lies in the query
         c = contigs[i % CONTIGS]
@@ -78,6 +85,50 @@ def wide_leg():
         pos = np.flatnonzero(rng.random(n) < 0.01)
         copy[pos] = ACGT[(np.searchsorted(ACGT, copy[pos]) + 1) % 4]
         c[at:at + n] = copy
+    return big
+
+
+def prefilter_leg():
+    """the same call on the same references, built without and with the prefilter"""
+    the_refs, rows = (wide_refs(), refset.WIDE_MAX_ROWS) if WIDE else (refs, None)
+    form = "best_refset" if BEST else "summary_refset" if SUMMARY else "find_refset"
+    total = len(the_refs) * 2 * int(offsets[-1])
+    out = {"workload": {"refs": len(the_refs), "ref_bp": len(the_refs[0]), "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2,
+                        "pair_bases": total}, "form": form}
+    for label, pre in (("plain", False), ("prefilter", True)):
+        a = time.perf_counter()
+        s = refset.RefSet.build(the_refs, opts, wide_rows=rows, prefilter=pre)
+        b = time.perf_counter()
+        s.to_device()
+        torch.cuda.synchronize()
+        c = time.perf_counter()
+
+        def call():
+            if BEST:
+                return refset.best_refset(contigs, s, fopts.max_error_prob, strands=3)
+            if SUMMARY:
+                return refset.summary_refset(contigs, s, fopts.max_error_prob, strands=3)
+            return refset.find_refset(contigs, s, fopts, strands=3)
+        got = call()  # warm-up: code objects, the call's buffers
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = call()
+            ts.append(time.perf_counter() - t)
+        out[label] = {"build_s": round(b - a, 4), "to_device_s": round(c - b, 4), "call_s": round(statistics.median(ts), 4),
+                      "call_s_all": [round(t, 4) for t in ts], "gbp_per_s": round(total / statistics.median(ts) / 1e9, 2),
+                      "records": int(len(got)), "records_crc32": zlib.crc32(got.tobytes()), "routes": refset.last_routes(),
+                      "prefilter_counters": refset.last_prefilter(), "prefilter_bytes": s.prefilter_bytes()}
+        del s
+    out["records_equal"] = out["plain"]["records_crc32"] == out["prefilter"]["records_crc32"]
+    out["table_build_s"] = round(out["prefilter"]["build_s"] - out["plain"]["build_s"], 4)
+    out["plain_over_prefilter"] = round(out["plain"]["call_s"] / out["prefilter"]["call_s"], 2)
+    print(json.dumps(out))
+
+
+def wide_leg():
+    """the same large references as a set of the single-index route and as a set of the wide route, one process"""
+    big = wide_refs()
     out = {"workload": {"refs": WIDE_REFS, "ref_bp": WIDE_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2,
                         "pair_bases": WIDE_REFS * 2 * int(offsets[-1])}, "form": "summary_refset" if SUMMARY else "find_refset"}
     for label, rows in (("index_route", None), ("wide_route", refset.WIDE_MAX_ROWS)):
@@ -108,6 +159,10 @@ def wide_leg():
     out["index_over_wide"] = round(out["index_route"]["call_s"] / out["wide_route"]["call_s"], 2)
     print(json.dumps(out))
 
+
+if PREFILTER:
+    prefilter_leg()
+    sys.exit(0)
 
 if WIDE:
     wide_leg()
