@@ -185,6 +185,31 @@ pub mod ffi {
         pub fn kbo_refset_prefilter_bytes(set: *const KboRefset) -> u64;
         pub fn kbo_refset_candidates(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, p: f64, strands: c_int,
                                      bits_out: *mut u32, n_candidates: *mut u64) -> c_int;
+        // the screened device-resident forms: the screen for a batch on the device (d_bits: that bitmap, d_stats: the four figures), and
+        // find / summary / best over ONE slab of the candidate list's longest prefix within max_pairs pairs and max_pair_bases bases;
+        // d_runs: kbo_ref_run records of ten u32
+        pub fn kbo_refset_candidates_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int) -> usize;
+        pub fn kbo_refset_candidates_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                         p: f64, strands: c_int, d_work: *mut c_void, work_bytes: usize, d_bits: *mut u32,
+                                         d_stats: *mut super::RefsetScreenStats, stream: *mut c_void) -> c_int;
+        pub fn kbo_find_refset_screened_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int,
+                                                       capacity: usize, max_pairs: usize, max_pair_bases: u64) -> usize;
+        pub fn kbo_find_refset_screened_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                            opts: *const KboFindOpts, strands: c_int, d_work: *mut c_void, work_bytes: usize,
+                                            d_runs: *mut c_void, capacity: usize, d_n_runs: *mut u64, max_pairs: usize, max_pair_bases: u64,
+                                            d_stats: *mut super::RefsetScreenStats, stream: *mut c_void) -> c_int;
+        pub fn kbo_summary_refset_screened_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int,
+                                                          capacity: usize, max_pairs: usize, max_pair_bases: u64) -> usize;
+        pub fn kbo_summary_refset_screened_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize,
+                                               total_bases: u64, p: f64, strands: c_int, d_work: *mut c_void, work_bytes: usize,
+                                               d_records: *mut super::RefSummary, capacity: usize, d_n_records: *mut u64, max_pairs: usize,
+                                               max_pair_bases: u64, d_stats: *mut super::RefsetScreenStats, stream: *mut c_void) -> c_int;
+        pub fn kbo_best_refset_screened_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int,
+                                                       max_pairs: usize, max_pair_bases: u64) -> usize;
+        pub fn kbo_best_refset_screened_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                            p: f64, strands: c_int, d_work: *mut c_void, work_bytes: usize, d_out: *mut super::RefBest,
+                                            max_pairs: usize, max_pair_bases: u64, d_stats: *mut super::RefsetScreenStats,
+                                            stream: *mut c_void) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -238,6 +263,17 @@ pub struct AlnExtent {
     pub n_runs: u32,
     pub start: u32,
     pub end: u32,
+}
+
+/// `kbo_refset_screen_stats` (32 bytes, on the device): what the screened device-resident reference-set calls report - the candidate
+/// pairs and their bases, and the pairs and bases of the one slab that was walked; `n_walked == n_candidates`: the call is complete.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefsetScreenStats {
+    pub n_candidates: u64,
+    pub candidate_bases: u64,
+    pub n_walked: u64,
+    pub walked_bases: u64,
 }
 
 /// `kbo_ref_summary` (36 bytes): what `kbo_summary_refset` returns per (reference, sequence, strand) pair with a hit.

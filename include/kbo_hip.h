@@ -543,7 +543,8 @@ int kbo_refset_packed_only(const kbo_refset_t *set);       /* 1: no reference ta
  * bits (n_refs x n_seqs x 2) runs unscreened, with the same records.  kbo_best_refset's merge kernel finds a slab's pairs by
  * arithmetic and cannot skip any: on a set with a prefilter the call runs kbo_summary_refset's slabs over the candidate pairs -
  * their per-slab waits come back - and folds the kept records into the table on the host, by the merge of refset_best.hpp; the table
- * is the same.  The device forms (kbo_*_refset_dev) IGNORE the prefilter: they plan on the device from closed forms over all pairs.
+ * is the same.  The device forms (kbo_*_refset_dev) IGNORE the prefilter: they plan on the device from closed forms over all pairs;
+ * kbo_*_refset_screened_dev, below them, plan from the bitmap.
  * kbo_refset_candidates runs the screen alone: bits_out receives ceil(n_refs x n_seqs x 2 / 32) words, bit
  * (r x n_seqs + s) x 2 + (strand - 1); *n_candidates (may be NULL) the bits set.  For a reference that can be screened the bit is 1 if
  * and only if sequence s on that strand holds m_r consecutive bytes that lie within the sequence, are all bases and occur as m_r
@@ -686,6 +687,53 @@ int kbo_best_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
 size_t kbo_best_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t refs_per_slab);
 int kbo_best_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                         double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, void *stream);
+/* The SCREENED device forms: the device-resident calls above over a set built with a prefilter, walking only the pairs the seed screen
+ * marks.  They are opt-in; kbo_*_refset_dev keep ignoring the prefilter.  Everything those promise holds: all work is enqueued on
+ * `stream`, no synchronisation, no device-to-host copy, no allocation, all scratch in d_work (16-byte aligned) and nothing written
+ * behind the figure of *_work_bytes, the same inputs, alignments and 16 bytes of slack behind d_concat.  The call's ONE host-to-device
+ * upload is 5 bytes a reference: the thresholds and the seed lengths m_r, which only the host can compute.
+ * kbo_refset_candidates_dev is kbo_refset_candidates for a batch on the device: d_bits (4-byte aligned, ceil(n_refs x n_seqs x 2 / 32)
+ * words, zeroed by the call) receives the same bitmap bit for bit - a reference that cannot be screened at this max_error_prob has
+ * all its pairs on the strands asked for set - and d_stats (8-byte aligned) n_candidates and candidate_bases (the bases of the
+ * candidate pairs, a pair counting its sequence's length), n_walked = walked_bases = 0.  5 launches, 6 with the '-' strand.
+ * kbo_find / summary / best_refset_screened_dev run that screen into d_work, list the set bits in ascending order - the records' own
+ * order (ref, seq, strand with '+' first) - and walk ONE slab: the longest prefix of that list with at most max_pairs pairs and at
+ * most max_pair_bases bases.  d_stats receives the four figures; the caller reads it when it likes, and n_walked == n_candidates says
+ * that the call is complete.  A caller that sizes the caps from kbo_refset_candidates_dev's figures always is.  Records: byte for byte
+ * those of the host forms restricted to the walked pairs, in the same order; capacity and *d_n_runs / *d_n_records as in the
+ * unscreened forms; for best, d_out is the complete table of n_seqs records over the walked pairs.  Several slabs are out of scope:
+ * ONE slab holds at most 2^28 - 1 pairs and 2^32 - 17 bytes, and a caller with more candidates than that uses the unscreened form.
+ * Launches, whatever the batch and the bitmap hold: find 46, summary 34, best 31; one more with the '-' strand (and a device-to-device
+ * copy of the batch when both strands are asked for), one more for a set with both LDS and wide references.  Grids are sized by the
+ * caps - max_pair_bases / chunk + max_pairs item slots, that / 256 + min(queryable references, max_pairs) + 1 workgroups of the walk -
+ * and lanes behind the device-side counts return, so generous caps cost time as well as scratch.
+ * *_work_bytes are exact, grow with max_pairs, max_pair_bases and capacity, and are 0 for arguments the call refuses.
+ * Errors, all before anything is enqueued: those of the unscreened device forms; KBO_E_BAD_ARG for a set without a prefilter, for
+ * max_pairs == 0 and for a work_bytes below the figure; KBO_E_UNSUPPORTED for a bitmap of more than 2^31 bits, a reference of the
+ * single-index route, a batch of 2^31 bases or more, and caps beyond what one slab may hold. */
+typedef struct {
+    uint64_t n_candidates, candidate_bases, n_walked, walked_bases;
+} kbo_refset_screen_stats; /* 32 bytes, on the device */
+size_t kbo_refset_candidates_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands);
+int kbo_refset_candidates_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                              double max_error_prob, int strands, void *d_work, size_t work_bytes, uint32_t *d_bits,
+                              kbo_refset_screen_stats *d_stats, void *stream);
+size_t kbo_find_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                               size_t max_pairs, uint64_t max_pair_bases);
+int kbo_find_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 const kbo_find_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_run *d_runs, size_t capacity,
+                                 uint64_t *d_n_runs, size_t max_pairs, uint64_t max_pair_bases, kbo_refset_screen_stats *d_stats, void *stream);
+size_t kbo_summary_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                                  size_t max_pairs, uint64_t max_pair_bases);
+int kbo_summary_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                    double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_summary *d_records,
+                                    size_t capacity, uint64_t *d_n_records, size_t max_pairs, uint64_t max_pair_bases,
+                                    kbo_refset_screen_stats *d_stats, void *stream);
+size_t kbo_best_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_pairs,
+                                               uint64_t max_pair_bases);
+int kbo_best_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, size_t max_pairs,
+                                 uint64_t max_pair_bases, kbo_refset_screen_stats *d_stats, void *stream);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

@@ -129,6 +129,9 @@ SYMBOLS = [
     "kbo_refset_build_wide", "kbo_refset_route", "kbo_refset_packed_only",
     "kbo_best_refset", "kbo_best_refset_dev_work_bytes", "kbo_best_refset_dev",
     "kbo_refset_opts_default", "kbo_refset_build_opts", "kbo_refset_has_prefilter", "kbo_refset_prefilter_bytes", "kbo_refset_candidates",
+    "kbo_refset_candidates_dev_work_bytes", "kbo_refset_candidates_dev", "kbo_find_refset_screened_dev_work_bytes",
+    "kbo_find_refset_screened_dev", "kbo_summary_refset_screened_dev_work_bytes", "kbo_summary_refset_screened_dev",
+    "kbo_best_refset_screened_dev_work_bytes", "kbo_best_refset_screened_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -362,6 +365,17 @@ def lib():
     L.kbo_refset_candidates_host.argtypes = [vp, vp, vp, sz, C.c_double, C.c_int, vp, C.POINTER(u64)]
     L.kbo_set_refset_prefilter_max_bits.argtypes = [u64]
     L.kbo_refset_last_prefilter.argtypes = [vp]
+    L.kbo_refset_candidates_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int]; L.kbo_refset_candidates_dev_work_bytes.restype = sz
+    L.kbo_refset_candidates_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, vp, vp]
+    L.kbo_find_refset_screened_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz, u64]
+    L.kbo_find_refset_screened_dev_work_bytes.restype = sz
+    L.kbo_find_refset_screened_dev.argtypes = [vp, vp, vp, sz, u64, C.POINTER(FindOpts), C.c_int, vp, sz, vp, sz, vp, sz, u64, vp, vp]
+    L.kbo_summary_refset_screened_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz, u64]
+    L.kbo_summary_refset_screened_dev_work_bytes.restype = sz
+    L.kbo_summary_refset_screened_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, sz, vp, sz, u64, vp, vp]
+    L.kbo_best_refset_screened_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, u64]
+    L.kbo_best_refset_screened_dev_work_bytes.restype = sz
+    L.kbo_best_refset_screened_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, sz, u64, vp, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

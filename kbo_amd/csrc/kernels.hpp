@@ -647,6 +647,45 @@ struct RefsetScreenArgs {
 };
 hipError_t launch_refset_screen(const RefsetScreenArgs &a, hipStream_t stream); // one launch; none for total == 0
 
+// ---- the screened device forms (refset_cand_kernels.hip; the arithmetic: refset_cand.hpp): the bitmap of the screen to the list of
+// its set bits, ONE slab of the list's longest prefix within the caps planned from it, and the record and merge stages that name a
+// pair by the list.  Everything is read on the device; stream order is the only synchronisation.
+struct RefsetCandArgs {
+    const uint64_t *off;   // the batch's offsets, n_seqs + 1
+    const uint32_t *thr;   // per reference of the set (0: it cannot be queried)
+    const uint8_t *m;      // per reference: what the screen kernel takes, refcand::kMarkAll for a packed reference that cannot be screened
+    uint32_t *bits;        // the bitmap, `words` words
+    uint32_t *pc;          // chunk_items_scratch_words(words) u32: the words' popcounts, scanned (two levels)
+    uint64_t *hdr;         // { candidates, pairs walked, bases walked, 0 }: the call's own copy of the figures
+    uint64_t *stats;       // kbo_refset_screen_stats: { n_candidates, candidate_bases, n_walked, walked_bases }, zeroed by the caller
+    uint32_t *list;        // max_pairs u32: the bit of the pair at every rank, refcand::kNoPair behind the candidates
+    uint64_t *poff;        // max_pairs + 1: the pairs' lengths, then their prefix, then the pairs' first bytes (in place)
+    uint64_t *bsum;        // (max_pairs + 1) / 1024 + 2 u64: the block sums of that prefix
+    uint32_t *pthr;        // max_pairs
+    uint32_t *nch;         // chunk_items_scratch_words(max_pairs) u32: the pairs' chunk counts, scanned
+    uint32_t *rfirst;      // n_refs + 1: the first item of every reference
+    uint32_t *ntask;       // chunk_items_scratch_words(n_refs) u32: the references' task counts, scanned
+    uint64_t n_bits, max_bases, rev_off; // rev_off: where the '-' strand begins in the walk's query buffer
+    uint32_t words, n_refs, n_seqs, strands, k, chunk, max_pairs, item_slots, task_slots, safe_ref; // safe_ref: names the empty tasks
+};
+// 3 launches: the pairs of the references that cannot be screened set in the bitmap, the words' popcounts and their scan;
+// stats[1] += the candidates' bases
+hipError_t launch_refset_cand_count(const RefsetCandArgs &a, hipStream_t stream);
+// 1 launch: stats[0] = the candidates (kbo_refset_candidates_dev: nothing is walked)
+hipError_t launch_refset_cand_stats(const RefsetCandArgs &a, hipStream_t stream);
+// 4 launches behind launch_refset_cand_count: the list, the 64-bit scan of the lengths, the cut; hdr and stats written
+hipError_t launch_refset_cand_list(const RefsetCandArgs &a, hipStream_t stream);
+// 7 launches: pair offsets and thresholds (the '-' of pairs of fewer than 3 bases in d_chars, or nullptr), chunk counts and their scan,
+// the references' items and tasks and their scan, a.item_slots item slots and a.task_slots tasks of the walk
+hipError_t launch_refset_cand_plan(const RefsetCandArgs &a, uint8_t *d_chars, uint4 *d_items, uint4 *d_tasks, hipStream_t stream);
+// 1 launch each: launch_refset_tag_runs / _summaries with (ref, seq, strand) from the list; *d_count = the records there are
+hipError_t launch_refset_cand_tag_runs(const RefsetCandArgs &a, const uint32_t *d_first, const uint32_t *d_local, uint32_t local_cap, uint64_t *d_count,
+                                       uint64_t capacity, uint32_t *d_out, hipStream_t stream);
+hipError_t launch_refset_cand_tag_summaries(const RefsetCandArgs &a, const uint32_t *d_kept, const uint32_t *d_n_kept, uint64_t *d_count,
+                                            uint64_t capacity, uint32_t *d_out, hipStream_t stream);
+// 1 launch: the extents of the walked pairs (six u32 at the pair's rank) merged into the table, a sequence's pairs found by its bits
+hipError_t launch_refset_cand_best(const RefsetCandArgs &a, const uint32_t *d_ext, uint32_t *d_table, hipStream_t stream);
+
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256
 void set_walk_experiment(int lane_limit, int dummy_lds_bytes); // experiments behind DESIGN.md section 6

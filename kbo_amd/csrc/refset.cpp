@@ -12,6 +12,7 @@
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 #include "refset_best.hpp"
+#include "refset_cand.hpp"
 #include "refset_screen.hpp"
 #include "refset_step.hpp"
 
@@ -918,6 +919,246 @@ void run_dev_form(const DevCall &c, DevKind kind)
     }
 }
 
+// ---- the screened device-resident form (kbo_refset_candidates_dev, kbo_*_refset_screened_dev): the screen kernel over the batch
+// where it is, the bitmap to the list of its set bits, and ONE slab of the list's longest prefix within the caller's caps planned
+// from it (refset_cand_kernels.hip).  The stages behind the walk see the slab as max_pairs sequences over max_pair_bases bytes, of
+// which those behind the walked pairs are empty: their total_bases only bounds their chunk lists (derand_seq_kernels.hip seq_layout,
+// rle_seg_kernels.hip seg_layout), and walked_bases / 128 + n_walked chunks are within max_pair_bases / 128 + max_pairs.
+enum CandKind { kCandSummary, kCandFind, kCandBest, kCandOnly };
+constexpr uint64_t kCandMaxPairs = (1ull << 28) - 1, kCandMaxBases = (1ull << 32) - 17; // what ONE slab may hold
+struct CandForm {
+    uint32_t n_refs = 0, n_q = 0, words = 0, chunk = 0;
+    uint64_t n_bits = 0, item_slots = 0, task_slots = 0, local_cap = 0;
+    size_t rev = 0; // bytes of one strand of the batch in the query buffer
+    size_t q = 0, thr = 0, pc = 0, hdr = 0, bits = 0, list = 0, poff = 0, bsum = 0, pthr = 0, nch = 0, rfirst = 0, ntask = 0, items = 0, tasks = 0, ms = 0,
+           derand = 0, chars = 0, stage = 0, first = 0, local = 0, total = 0, end = 0;
+    bool ok = false;
+};
+
+// why a call with these arguments is refused, in the order the calls report it; KBO_OK: it is not
+int cand_refusal(const kbo_refset *set, size_t n_seqs, uint64_t total, int strands, size_t max_pairs, uint64_t max_bases, CandKind kind)
+{
+    if (!set || strands < 1 || strands > 3) return KBO_E_BAD_ARG;
+    if (n_seqs == 0) return KBO_E_EMPTY_QUERY;
+    if (!set->prefilter) return KBO_E_BAD_ARG;
+    if (kind != kCandOnly && max_pairs == 0) return KBO_E_BAD_ARG;
+    for (const kbo::RefsetDesc &d : set->descs)
+        if (!d.status && d.route == kbo::kRefsetRouteIndex) return KBO_E_UNSUPPORTED;
+    if (screen_bits(set, n_seqs) > kPrefilterMaxBits) return KBO_E_UNSUPPORTED;
+    const uint64_t ns = strands == 3 ? 2 : 1;
+    if (n_seqs * ns >= (1ull << 28) || total >= (1ull << 31) || ns * total >= (1ull << 32) - 16) return KBO_E_UNSUPPORTED;
+    if (kind != kCandOnly && (max_pairs > kCandMaxPairs || max_bases > kCandMaxBases)) return KBO_E_UNSUPPORTED;
+    return KBO_OK;
+}
+
+CandForm cand_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int strands, size_t capacity, size_t max_pairs, uint64_t max_bases,
+                   CandKind kind)
+{
+    CandForm F;
+    if (cand_refusal(set, n_seqs, total, strands, max_pairs, max_bases, kind) != KBO_OK) return F;
+    const uint64_t MP = max_pairs, MB = max_bases;
+    F.n_refs = (uint32_t)set->descs.size();
+    for (const kbo::RefsetDesc &d : set->descs) F.n_q += !d.status;
+    F.n_bits = screen_bits(set, n_seqs);
+    F.words = (uint32_t)((F.n_bits + 31) / 32);
+    F.chunk = kbo::refplan::chunk_of(set->k);
+    F.rev = (size_t)(total + 15) / 16 * 16;
+    size_t w = 0;
+    if (strands == 3) { // '+' copied to q, '-' made at q + rev: one buffer for the screen and the walk
+        F.q = w;
+        w += 2 * F.rev + 64;
+    }
+    F.thr = w;    w += up16((size_t)F.n_refs * 5);                                                 // the thresholds, then the m bytes
+    F.pc = w;     w += up16(kbo::chunk_items_scratch_words(F.words) * sizeof(uint32_t));
+    F.hdr = w;    w += 32;
+    if (kind != kCandOnly) {
+        F.item_slots = kbo::refcand::item_slots(MP, MB, F.chunk);
+        F.task_slots = kbo::refcand::task_slots(F.item_slots, F.n_q, MP);
+        F.bits = w;   w += up16((size_t)F.words * sizeof(uint32_t));
+        F.list = w;   w += up16((size_t)MP * sizeof(uint32_t));
+        F.poff = w;   w += up16((size_t)(MP + 1) * sizeof(uint64_t));
+        F.bsum = w;   w += up16((size_t)((MP + 1) / kbo::refcand::kScan64Block + 2) * sizeof(uint64_t));
+        F.pthr = w;   w += up16((size_t)MP * sizeof(uint32_t));
+        F.nch = w;    w += up16(kbo::chunk_items_scratch_words((uint32_t)MP) * sizeof(uint32_t));
+        F.rfirst = w; w += up16((size_t)(F.n_refs + 1) * sizeof(uint32_t));
+        F.ntask = w;  w += up16(kbo::chunk_items_scratch_words(F.n_refs) * sizeof(uint32_t));
+        F.items = w;  w += (size_t)F.item_slots * sizeof(uint4);
+        F.tasks = w;  w += (size_t)F.task_slots * sizeof(uint4);
+        F.ms = w;     w += up16((size_t)MB) + 64;
+        F.derand = w; w += up16(kbo::derand_seq_work_bytes((uint32_t)MP, MB, set->k, 2));
+        if (kind == kCandFind) {
+            F.local_cap = std::min<uint64_t>(capacity, MB / 2 + MP); // (a run holds a character other than '-' and ends at one)
+            F.chars = w; w += up16((size_t)MB) + 64;
+            F.stage = w; w += up16(kbo::rle_seg_work_bytes((uint32_t)MP, MB));
+            F.first = w; w += up16((size_t)(MP + 1) * sizeof(uint32_t));
+            F.local = w; w += up16((size_t)F.local_cap * kRleWords * sizeof(uint32_t));
+        } else {
+            F.chars = w; w += up16((size_t)MP * sizeof(kbo_aln_extent)); // the extents
+            if (kind == kCandSummary) {
+                F.stage = w; w += up16(kbo::chunk_items_scratch_words((uint32_t)MP) * sizeof(uint32_t));
+                F.local = w; w += up16((size_t)MP * 7 * sizeof(uint32_t));
+                F.total = w; w += 16;
+            }
+        }
+    }
+    if (strands == 2) { // '-' alone: the screen kernel reads it at q + rev, so it lies at least rev bytes into d_work and q inside it
+        F.q = std::max(w, F.rev);
+        w = F.q + F.rev + 64;
+    }
+    F.end = w;
+    F.ok = true;
+    return F;
+}
+
+struct CandCall {
+    DevCall c;
+    size_t max_pairs;
+    uint64_t max_bases;
+    uint32_t *d_bits; // kCandOnly: the caller's bitmap
+    kbo_refset_screen_stats *d_stats;
+};
+
+void run_cand_form(const CandCall &cc, CandKind kind)
+{
+    namespace sc = kbo::refscreen;
+    const DevCall &c = cc.c;
+    const bool find = kind == kCandFind, best = kind == kCandBest, only = kind == kCandOnly;
+    KBO_REQUIRE(c.strands >= 1 && c.strands <= 3, KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
+    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && cc.d_stats && (only ? cc.d_bits != nullptr : (c.d_n || best)) &&
+                    (only || c.d_out || (c.capacity == 0 && !best)),
+                KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(((uintptr_t)c.d_concat & 15) == 0 && ((uintptr_t)c.d_work & 15) == 0 && ((uintptr_t)c.d_offsets & 7) == 0 &&
+                    ((uintptr_t)c.d_n & 7) == 0 && ((uintptr_t)c.d_out & 3) == 0 && ((uintptr_t)cc.d_stats & 7) == 0 && ((uintptr_t)cc.d_bits & 3) == 0,
+                KBO_E_BAD_ARG, "d_concat and d_work 16-byte, d_offsets, the count and d_stats 8-byte, the records and d_bits 4-byte aligned");
+    KBO_REQUIRE(c.n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+    kbo_refset *set = c.set;
+    KBO_REQUIRE(set->prefilter, KBO_E_BAD_ARG, "the set has no prefilter (kbo_refset_build_opts)");
+    KBO_REQUIRE(only || cc.max_pairs > 0, KBO_E_BAD_ARG, "max_pairs == 0");
+    const std::vector<uint32_t> thr = refset_thresholds(set, c.max_error_prob);
+    for (const kbo::RefsetDesc &d : set->descs)
+        KBO_REQUIRE(d.status || d.route != kbo::kRefsetRouteIndex, KBO_E_UNSUPPORTED,
+                    "a reference of the single-index route: the host calls take it (kbo_refset_packed_only)");
+    KBO_REQUIRE(screen_bits(set, c.n_seqs) <= kPrefilterMaxBits, KBO_E_UNSUPPORTED, "a bitmap of more than 2^31 bits");
+    KBO_REQUIRE(only || (cc.max_pairs <= kCandMaxPairs && cc.max_bases <= kCandMaxBases), KBO_E_UNSUPPORTED,
+                "caps beyond one slab: 2^28 pairs or more, or more than 2^32 - 17 bases (the unscreened form cuts several slabs)");
+    const CandForm F = cand_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, cc.max_pairs, cc.max_bases, kind);
+    KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a batch of 2^31 bases or more, or 2^28 (sequence, strand) pairs or more");
+    KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes below the figure of *_work_bytes");
+    DevSet *ds = device_set_if_any(set, current_device());
+    KBO_REQUIRE(ds, KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
+
+    // the call's one upload: the thresholds and, behind them, the seed lengths as the kernels take them
+    const std::vector<uint8_t> m = seed_lens(set, thr);
+    std::vector<uint32_t> up(((size_t)F.n_refs * 5 + 3) / 4, 0u);
+    std::copy(thr.begin(), thr.end(), up.begin());
+    uint8_t *up_m = reinterpret_cast<uint8_t *>(up.data() + F.n_refs);
+    uint32_t min_thr = set->k, safe_ref = 0, lds_units = 0;
+    bool has_lds = false, has_wide = false, any = false;
+    for (size_t r = 0; r < F.n_refs; r++) {
+        up_m[r] = m[r] >= sc::kSeedMin ? m[r] : (uint8_t)(m[r] ? kbo::refcand::kMarkAll : sc::kUnfilterable);
+        const kbo::RefsetDesc &d = set->descs[r];
+        if (d.status) continue;
+        if (!any) safe_ref = (uint32_t)r;
+        any = true;
+        min_thr = std::min(min_thr, thr[r]);
+        if (d.route == kbo::kRefsetRouteWide) has_wide = true;
+        else {
+            has_lds = true;
+            lds_units = std::max(lds_units, kbo::refset_units(d.n_sets));
+        }
+    }
+    hipStream_t st = c.stream;
+    uint8_t *w = static_cast<uint8_t *>(c.d_work);
+    auto at = [&](size_t o) { return reinterpret_cast<uint32_t *>(w + o); };
+    HIP_OK(hipMemcpyAsync(w + F.thr, up.data(), (size_t)F.n_refs * 5, hipMemcpyHostToDevice, st));
+    // ONE query buffer for the screen and the walk: the caller's for '+' alone; '+' copied and '-' behind it; or '-' alone, which the
+    // walk reads at its first byte and the screen at q + rev
+    const uint8_t *walk_q = c.strands == 1 ? c.d_concat : w + F.q;
+    if (c.strands == 3 && c.total_bases) HIP_OK(hipMemcpyAsync(w + F.q, c.d_concat, c.total_bases, hipMemcpyDeviceToDevice, st));
+    if (c.strands & KBO_STRAND_REV)
+        HIP_OK(kbo::launch_revcomp_bytes(c.d_concat, c.d_offsets, (uint32_t)c.n_seqs, c.total_bases, w + F.q + (c.strands == 3 ? F.rev : 0), st));
+    uint32_t *bits = only ? cc.d_bits : at(F.bits);
+    HIP_OK(hipMemsetAsync(bits, 0, (size_t)F.words * sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(cc.d_stats, 0, sizeof(kbo_refset_screen_stats), st));
+    kbo::RefsetScreenArgs s;
+    s.bucket = ds->pre_bucket.as<uint32_t>();
+    s.keys = ds->pre_keys.as<uint64_t>();
+    s.refs = ds->pre_refs.as<uint32_t>();
+    s.m = w + F.thr + (size_t)F.n_refs * 4;
+    s.q = c.strands == 2 ? w + F.q - F.rev : walk_q;
+    s.off = c.d_offsets;
+    s.bits = bits;
+    s.total = c.total_bases;
+    s.rev_base = F.rev;
+    s.n_seqs = (uint32_t)c.n_seqs;
+    s.strands = (uint32_t)c.strands;
+    s.first_strand = c.strands == 2 ? 2u : 1u;
+    HIP_OK(kbo::launch_refset_screen(s, st));
+    kbo::RefsetCandArgs a{};
+    a.off = c.d_offsets;
+    a.thr = at(F.thr);
+    a.m = s.m;
+    a.bits = bits;
+    a.pc = at(F.pc);
+    a.hdr = reinterpret_cast<uint64_t *>(w + F.hdr);
+    a.stats = reinterpret_cast<uint64_t *>(cc.d_stats);
+    a.n_bits = F.n_bits;
+    a.words = F.words;
+    a.n_refs = F.n_refs;
+    a.n_seqs = (uint32_t)c.n_seqs;
+    a.strands = (uint32_t)c.strands;
+    a.k = set->k;
+    a.chunk = F.chunk;
+    HIP_OK(kbo::launch_refset_cand_count(a, st));
+    if (only) {
+        HIP_OK(kbo::launch_refset_cand_stats(a, st));
+        return;
+    }
+    a.list = at(F.list);
+    a.poff = reinterpret_cast<uint64_t *>(w + F.poff);
+    a.bsum = reinterpret_cast<uint64_t *>(w + F.bsum);
+    a.pthr = at(F.pthr);
+    a.nch = at(F.nch);
+    a.rfirst = at(F.rfirst);
+    a.ntask = at(F.ntask);
+    a.max_bases = cc.max_bases;
+    a.rev_off = c.strands == 3 ? F.rev : 0;
+    a.max_pairs = (uint32_t)cc.max_pairs;
+    a.item_slots = (uint32_t)F.item_slots;
+    a.task_slots = (uint32_t)F.task_slots;
+    a.safe_ref = safe_ref;
+    const uint32_t np = a.max_pairs;
+    const uint64_t bytes = cc.max_bases;
+    HIP_OK(kbo::launch_refset_cand_list(a, st));
+    HIP_OK(kbo::launch_refset_cand_plan(a, find ? w + F.chars : nullptr, reinterpret_cast<uint4 *>(w + F.items), reinterpret_cast<uint4 *>(w + F.tasks), st));
+    kbo::RefsetWalkArgs wa;
+    wa.descs = ds->descs.as<kbo::RefsetDesc>();
+    wa.arena = ds->arena.as<uint4>();
+    wa.tasks = reinterpret_cast<const uint4 *>(w + F.tasks);
+    wa.items = reinterpret_cast<const uint4 *>(w + F.items);
+    wa.n_tasks = a.task_slots;
+    wa.k = set->k;
+    wa.q = walk_q;
+    wa.ms = w + F.ms;
+    if (has_lds) HIP_OK(kbo::launch_refset_walk(wa, lds_units, st));
+    if (has_wide) HIP_OK(kbo::launch_refset_wide_walk(wa, st));
+    uint8_t *ms = w + F.ms;
+    if (find) {
+        HIP_OK(kbo::launch_derand_translate_seq(ms, a.poff, np, bytes, set->k, a.pthr, min_thr, nullptr, w + F.chars, w + F.derand, st));
+        HIP_OK(kbo::launch_rle_seg_count(w + F.chars, a.poff, np, bytes, c.gap, 0u, w + F.stage, at(F.first), st));
+        if (F.local_cap) HIP_OK(kbo::launch_rle_seg_emit(w + F.chars, np, bytes, c.gap, w + F.stage, at(F.local), (uint32_t)F.local_cap, st));
+        HIP_OK(kbo::launch_refset_cand_tag_runs(a, at(F.first), at(F.local), (uint32_t)F.local_cap, c.d_n, c.capacity, static_cast<uint32_t *>(c.d_out), st));
+    } else if (best) {
+        HIP_OK(kbo::launch_derand_summary_seq(ms, a.poff, np, bytes, set->k, a.pthr, min_thr, at(F.chars), w + F.derand, st));
+        HIP_OK(kbo::launch_refset_best_init(static_cast<uint32_t *>(c.d_out), (uint32_t)c.n_seqs, st));
+        HIP_OK(kbo::launch_refset_cand_best(a, at(F.chars), static_cast<uint32_t *>(c.d_out), st));
+    } else {
+        HIP_OK(kbo::launch_derand_summary_seq(ms, a.poff, np, bytes, set->k, a.pthr, min_thr, at(F.chars), w + F.derand, st));
+        HIP_OK(kbo::launch_refset_keep(at(F.chars), np, at(F.stage), at(F.local), at(F.total), st));
+        HIP_OK(kbo::launch_refset_cand_tag_summaries(a, at(F.local), at(F.total), c.d_n, c.capacity, static_cast<uint32_t *>(c.d_out), st));
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -1424,6 +1665,82 @@ int kbo_best_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64
         run_dev_form(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_out, 0, nullptr,
                              static_cast<hipStream_t>(stream)},
                      kDevBest);
+    });
+}
+
+size_t kbo_refset_candidates_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands)
+{
+    return cand_form(set, n_seqs, total_bases, strands, 0, 0, 0, kCandOnly).end;
+}
+
+int kbo_refset_candidates_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                              double max_error_prob, int strands, void *d_work, size_t work_bytes, uint32_t *d_bits,
+                              kbo_refset_screen_stats *d_stats, void *stream)
+{
+    return guarded([&] {
+        static_assert(sizeof(kbo_refset_screen_stats) == 32, "kbo_refset_screen_stats is 32 bytes");
+        run_cand_form(CandCall{DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, nullptr, 0, nullptr,
+                                       static_cast<hipStream_t>(stream)},
+                               0, 0, d_bits, d_stats},
+                      kCandOnly);
+    });
+}
+
+size_t kbo_find_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                               size_t max_pairs, uint64_t max_pair_bases)
+{
+    return cand_form(set, n_seqs, total_bases, strands, capacity, max_pairs, max_pair_bases, kCandFind).end;
+}
+
+int kbo_find_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 const kbo_find_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_run *d_runs, size_t capacity,
+                                 uint64_t *d_n_runs, size_t max_pairs, uint64_t max_pair_bases, kbo_refset_screen_stats *d_stats, void *stream)
+{
+    return guarded([&] {
+        kbo_find_opts o;
+        if (opts) o = *opts; else kbo_find_opts_default(&o);
+        run_cand_form(CandCall{DevCall{set, d_concat, d_offsets, n_seqs, total_bases, o.max_error_prob,
+                                       (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu), strands, d_work, work_bytes, d_runs, capacity, d_n_runs,
+                                       static_cast<hipStream_t>(stream)},
+                               max_pairs, max_pair_bases, nullptr, d_stats},
+                      kCandFind);
+    });
+}
+
+size_t kbo_summary_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
+                                                  size_t max_pairs, uint64_t max_pair_bases)
+{
+    return cand_form(set, n_seqs, total_bases, strands, capacity, max_pairs, max_pair_bases, kCandSummary).end;
+}
+
+int kbo_summary_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                    double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_summary *d_records,
+                                    size_t capacity, uint64_t *d_n_records, size_t max_pairs, uint64_t max_pair_bases,
+                                    kbo_refset_screen_stats *d_stats, void *stream)
+{
+    return guarded([&] {
+        run_cand_form(CandCall{DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_records, capacity,
+                                       d_n_records, static_cast<hipStream_t>(stream)},
+                               max_pairs, max_pair_bases, nullptr, d_stats},
+                      kCandSummary);
+    });
+}
+
+size_t kbo_best_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_pairs,
+                                               uint64_t max_pair_bases)
+{
+    return cand_form(set, n_seqs, total_bases, strands, 0, max_pairs, max_pair_bases, kCandBest).end;
+}
+
+int kbo_best_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, size_t max_pairs,
+                                 uint64_t max_pair_bases, kbo_refset_screen_stats *d_stats, void *stream)
+{
+    return guarded([&] {
+        run_cand_form(CandCall{DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_out, 0, nullptr,
+                                       static_cast<hipStream_t>(stream)},
+                               max_pairs, max_pair_bases, nullptr, d_stats},
+                      kCandBest);
     });
 }
 

@@ -115,6 +115,23 @@ class RefSet:
         assert int(bits.sum()) == cnt.value
         return bits.reshape(len(self), n, 2)
 
+    def candidates_dev(self, concat, offsets, max_error_prob=1e-7, strands=STRAND_BOTH, stream=None):
+        """kbo_refset_candidates_dev over torch tensors on the device: the screen alone for a batch that is already there (the
+        conventions are find_refset_dev's).  Returns (bits, stats): bits an int32 tensor of ceil(n_refs x n_seqs x 2 / 32) words,
+        bit (r * n_seqs + s) * 2 + strand - 1 as candidates() has it; stats an int64 tensor of the four words of
+        kbo_refset_screen_stats (n_candidates, candidate_bases, n_walked = 0, walked_bases = 0).  Nothing is synchronised."""
+        import torch
+        q, off, n_seqs, total, s = _dev_batch(concat, offsets, stream)
+        L = lib()
+        with torch.cuda.device(q.device), torch.cuda.stream(s):
+            wb = int(L.kbo_refset_candidates_dev_work_bytes(self._h, n_seqs, total, int(strands)))
+            work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+            bits = torch.empty((len(self) * n_seqs * 2 + 31) // 32, dtype=torch.int32, device=q.device)
+            stats = torch.empty(4, dtype=torch.int64, device=q.device)
+            check(L.kbo_refset_candidates_dev(self._h, q.data_ptr(), off.data_ptr(), n_seqs, total, float(max_error_prob), int(strands),
+                                              work.data_ptr(), wb, bits.data_ptr(), stats.data_ptr(), s.cuda_stream))
+        return bits, stats
+
     def form(self, r):
         """test hook: the packed form of an LDS or wide reference, as bytes in a uint8 array"""
         n = C.c_size_t()
@@ -204,12 +221,74 @@ def best_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH):
         lib().kbo_free(p)
 
 
-def best_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, refs_per_slab=None, stream=None):
+def _dev_batch(concat, offsets, stream):
+    """the batch as the device-resident calls take it: (concat with 16 bytes of slack, 16-byte aligned; offsets; n_seqs; total; stream)"""
+    import torch
+    device = concat.device
+    n_seqs = int(offsets.numel()) - 1
+    assert concat.dtype == torch.uint8 and offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+    total = int(offsets[-1].item()) if n_seqs > 0 else 0
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.device(device), torch.cuda.stream(s):
+        q = concat.contiguous()
+        if int(q.numel()) < total + 16 or q.data_ptr() % 16:  # the 16 bytes of slack behind a per-base buffer
+            p = torch.zeros(total + 16, dtype=torch.uint8, device=device)
+            p[:total].copy_(q[:total])
+            q = p
+        off = offsets.contiguous()
+    return q, off, n_seqs, total, s
+
+
+def _screened_dev(kind, concat, offsets, refset, arg, strands, capacity, max_pairs, max_pair_bases, stream):
+    """kbo_find / summary / best_refset_screened_dev; max_pairs / max_pair_bases None: one read-back of candidates_dev's figures"""
+    import torch
+    q, off, n_seqs, total, s = _dev_batch(concat, offsets, stream)
+    L = lib()
+    if max_pairs is None or max_pair_bases is None:
+        p = arg.max_error_prob if kind == "find" else arg
+        st = refset.candidates_dev(q, off, p, strands, s)[1].cpu()  # (the one synchronisation of a call without caps)
+        max_pairs = max(1, int(st[0])) if max_pairs is None else max_pairs
+        max_pair_bases = int(st[1]) if max_pair_bases is None else max_pair_bases
+    max_pairs, max_pair_bases = int(max_pairs), int(max_pair_bases)
+    with torch.cuda.device(q.device), torch.cuda.stream(s):
+        stats = torch.empty(4, dtype=torch.int64, device=q.device)
+        if kind == "best":
+            wb = int(L.kbo_best_refset_screened_dev_work_bytes(refset._h, n_seqs, total, int(strands), max_pairs, max_pair_bases))
+            work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+            table = torch.empty((n_seqs, 12), dtype=torch.int32, device=q.device)
+            check(L.kbo_best_refset_screened_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, float(arg), int(strands),
+                                                 work.data_ptr(), wb, table.data_ptr(), max_pairs, max_pair_bases, stats.data_ptr(),
+                                                 s.cuda_stream))
+            return table, stats
+        find = kind == "find"
+        work_bytes = L.kbo_find_refset_screened_dev_work_bytes if find else L.kbo_summary_refset_screened_dev_work_bytes
+        wb = int(work_bytes(refset._h, n_seqs, total, int(strands), capacity, max_pairs, max_pair_bases))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+        records = torch.empty((capacity, 10 if find else 9), dtype=torch.int32, device=q.device)
+        count = torch.empty(1, dtype=torch.int64, device=q.device)
+        out = records.data_ptr() if capacity else None
+        if find:
+            check(L.kbo_find_refset_screened_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, C.byref(arg), int(strands),
+                                                 work.data_ptr(), wb, out, capacity, count.data_ptr(), max_pairs, max_pair_bases,
+                                                 stats.data_ptr(), s.cuda_stream))
+        else:
+            check(L.kbo_summary_refset_screened_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, float(arg), int(strands),
+                                                    work.data_ptr(), wb, out, capacity, count.data_ptr(), max_pairs, max_pair_bases,
+                                                    stats.data_ptr(), s.cuda_stream))
+    return records, count, stats
+
+
+def best_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, refs_per_slab=None, stream=None, screened=False,
+                    max_pairs=None, max_pair_bases=None):
     """kbo_best_refset_dev over torch tensors on the device: best_refset's records as an (n_seqs, 12) int32 tensor that holds the u32
     words of REF_BEST, complete when `stream` reaches the end of the call.  The conventions are summary_refset_dev's: the batch, the
     set (on that device, packed_only()), refs_per_slab, the stream, and nothing synchronised.  Sequences of fewer than 3 bases get
-    the record without a hit."""
+    the record without a hit.
+    screened=True: kbo_best_refset_screened_dev over a set with a prefilter - the table over the pairs of ONE slab of candidates (see
+    find_refset_dev); returns (table, stats)."""
     import torch
+    if screened:
+        return _screened_dev("best", concat, offsets, refset, max_error_prob, strands, 0, max_pairs, max_pair_bases, stream)
     device = concat.device
     n_seqs = int(offsets.numel()) - 1
     assert concat.dtype == torch.uint8 and offsets.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
@@ -268,23 +347,35 @@ def _refset_dev(find, concat, offsets, refset, arg, strands, capacity, refs_per_
     return records, count  # (the scratch was allocated on `s`: the allocator reuses it in that stream's order)
 
 
-def find_refset_dev(concat, offsets, refset, find_opts=None, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
+def find_refset_dev(concat, offsets, refset, find_opts=None, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None,
+                    screened=False, max_pairs=None, max_pair_bases=None):
     """kbo_find_refset_dev over torch tensors on the device: find_refset's records for a batch that is already there.  concat: uint8
     (the sequences back to back); offsets: int64 or uint64 (n_seqs + 1); the set has a copy on that device (RefSet.to_device) and is
     packed_only(): LDS and wide references (RefSet.build(wide_rows=...)), none of the single-index route.  Returns (records, count): records a (capacity, 10) int32 tensor that holds the u32 words of REF_RUN, the first
     min(count, capacity) rows written, and count an int64 tensor of one element, the number of records there are - beyond `capacity`
     they are counted only.  Sequences of fewer than 3 bases contribute nothing.  refs_per_slab: references of a slab (None: about
     256 MiB a slab, 0: as many as a slab may hold); it sizes the scratch.  Enqueued on `stream` (default: the current one); nothing is
-    synchronised."""
+    synchronised.
+    screened=True: kbo_find_refset_screened_dev over a set built with prefilter=True - the screen runs on the device and ONE slab is
+    walked, the longest prefix of the candidate pairs (in the records' order) with at most max_pairs pairs and max_pair_bases bases;
+    refs_per_slab is not used.  Returns (records, count, stats): stats an int64 tensor (n_candidates, candidate_bases, n_walked,
+    walked_bases), and n_walked == n_candidates says the records are complete.  A cap left None is taken from one read-back of
+    RefSet.candidates_dev's figures (the only synchronisation; with both caps given there is none)."""
     from . import FindOpts
     o = find_opts if find_opts is not None else FindOpts()
+    if screened:
+        return _screened_dev("find", concat, offsets, refset, _capi.FindOpts(o.max_error_prob, o.max_gap_len), strands, int(capacity), max_pairs,
+                             max_pair_bases, stream)
     return _refset_dev(True, concat, offsets, refset, _capi.FindOpts(o.max_error_prob, o.max_gap_len), strands, int(capacity), refs_per_slab, stream)
 
 
-def summary_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None):
+def summary_refset_dev(concat, offsets, refset, max_error_prob=1e-7, strands=STRAND_BOTH, capacity=1 << 16, refs_per_slab=None, stream=None,
+                       screened=False, max_pairs=None, max_pair_bases=None):
     """kbo_summary_refset_dev over torch tensors on the device: summary_refset's records, as find_refset_dev returns find_refset's -
     (records, count) with records a (capacity, 9) int32 tensor that holds the u32 words of REF_SUMMARY.  The set is packed_only(), as
-    there."""
+    there.  screened=True: kbo_summary_refset_screened_dev, as find_refset_dev's; returns (records, count, stats)."""
+    if screened:
+        return _screened_dev("summary", concat, offsets, refset, max_error_prob, strands, int(capacity), max_pairs, max_pair_bases, stream)
     return _refset_dev(False, concat, offsets, refset, max_error_prob, strands, int(capacity), refs_per_slab, stream)
 
 

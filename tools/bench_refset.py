@@ -30,6 +30,12 @@ workload or, with WIDE=1, on the wide leg's references as a set of the wide rout
 the seconds of both, whether the records' CRCs are equal, kbo_refset_last_prefilter's counters (pairs of packed references, with
 their bit set, walked, whether the screen ran), and the table's bytes and the seconds its build added.  LOOP and DEV do not apply.
 The screen kernel's own time: run this under a kernel trace and read refset_screen_kernel's row.
+DEV=1 PREFILTER=1 is a leg of its own on the first workload, one set built with the seed table, one session: the screened
+device-resident form (refset.find_refset_dev(..., screened=True), with SUMMARY=1 / BEST=1 the summary / best form; the caps come from
+one read-back of RefSet.candidates_dev's figures outside the timed region), next to the unscreened device-resident form on the same
+set (REFS_PER_SLAB, DEV_CAPACITY as above) and next to the host form, which screens.  The batch is uploaded once outside the timed
+regions; a timed device call ends when its records are on the host.  Median of REPEATS behind a warm-up for each; records_crc32 of
+each, the statistics the screened call left on the device, and the ratios.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -159,6 +165,69 @@ def wide_leg():
     out["index_over_wide"] = round(out["index_route"]["call_s"] / out["wide_route"]["call_s"], 2)
     print(json.dumps(out))
 
+
+def screened_dev_leg():
+    """the screened device form next to the unscreened one and to the host form with the prefilter: one set, one session"""
+    form = "best_refset" if BEST else "summary_refset" if SUMMARY else "find_refset"
+    s = refset.RefSet.build(refs, opts, prefilter=True).to_device()
+    d_q = torch.zeros(int(offsets[-1]) + 16, dtype=torch.uint8, device="cuda")
+    d_q[:int(offsets[-1])].copy_(torch.from_numpy(concat))
+    d_off = torch.from_numpy(offsets.astype(np.int64)).cuda()
+    cand = [int(v) for v in s.candidates_dev(d_q, d_off, fopts.max_error_prob, strands=3)[1].cpu().numpy()]
+    max_pairs, max_bases = max(1, cand[0]), cand[1]
+    torch.cuda.synchronize()
+    stats = {}
+
+    def host_call():
+        if BEST:
+            return refset.best_refset(contigs, s, fopts.max_error_prob, strands=3)
+        if SUMMARY:
+            return refset.summary_refset(contigs, s, fopts.max_error_prob, strands=3)
+        return refset.find_refset(contigs, s, fopts, strands=3)
+
+    def dev_call(screened):
+        kw = dict(screened=True, max_pairs=max_pairs, max_pair_bases=max_bases) if screened else dict(refs_per_slab=REFS_PER_SLAB)
+        if BEST:
+            got = refset.best_refset_dev(d_q, d_off, s, fopts.max_error_prob, strands=3, **kw)
+            table = (got[0] if screened else got).cpu().numpy()  # (waits for the stream: the only synchronisation of the call)
+            if screened:
+                stats["stats"] = [int(v) for v in got[1].cpu().numpy()]
+            return np.ascontiguousarray(table).view(np.uint32)
+        if SUMMARY:
+            got = refset.summary_refset_dev(d_q, d_off, s, fopts.max_error_prob, strands=3, capacity=DEV_CAPACITY, **kw)
+        else:
+            got = refset.find_refset_dev(d_q, d_off, s, fopts, strands=3, capacity=DEV_CAPACITY, **kw)
+        n = int(got[1].item())  # (waits for the stream: the only synchronisation of the call)
+        if screened:
+            stats["stats"] = [int(v) for v in got[2].cpu().numpy()]
+        return np.ascontiguousarray(got[0][:min(n, DEV_CAPACITY)].cpu().numpy()).view(np.uint32)
+
+    def timed(fn):
+        got = fn()  # warm-up: code objects, the allocator's blocks
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return {"call_s": round(statistics.median(ts), 5), "call_s_all": [round(t, 5) for t in ts], "records": int(len(got)),
+                "records_crc32": zlib.crc32(got.tobytes())}
+    out = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+           "form": form, "max_pairs": max_pairs, "max_pair_bases": max_bases}
+    out["screened_dev"] = timed(lambda: dev_call(True))
+    out["screened_dev"]["stats"] = dict(zip(("n_candidates", "candidate_bases", "n_walked", "walked_bases"), stats["stats"]))
+    out["host_prefilter"] = timed(host_call)
+    out["host_prefilter"]["prefilter_counters"] = refset.last_prefilter()
+    out["unscreened_dev"] = timed(lambda: dev_call(False))
+    out["unscreened_dev"]["refs_per_slab"] = REFS_PER_SLAB
+    out["records_equal"] = out["screened_dev"]["records_crc32"] == out["host_prefilter"]["records_crc32"] == out["unscreened_dev"]["records_crc32"]
+    out["unscreened_over_screened"] = round(out["unscreened_dev"]["call_s"] / out["screened_dev"]["call_s"], 2)
+    out["host_over_screened"] = round(out["host_prefilter"]["call_s"] / out["screened_dev"]["call_s"], 2)
+    print(json.dumps(out))
+
+
+if PREFILTER and DEV:
+    screened_dev_leg()
+    sys.exit(0)
 
 if PREFILTER:
     prefilter_leg()
