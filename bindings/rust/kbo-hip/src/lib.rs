@@ -210,6 +210,19 @@ pub mod ffi {
                                             p: f64, strands: c_int, d_work: *mut c_void, work_bytes: usize, d_out: *mut super::RefBest,
                                             max_pairs: usize, max_pair_bases: u64, d_stats: *mut super::RefsetScreenStats,
                                             stream: *mut c_void) -> c_int;
+        // the locus of a run: a set built with `RefsetOpts::positions` = 1 carries one entry per row; runs: kbo_ref_run records of ten
+        // u32 ({ ref, seq, strand, start, end, ... }), loci: one RefLocus per run, same index
+        pub fn kbo_refset_has_positions(set: *const KboRefset) -> c_int;
+        pub fn kbo_refset_positions_bytes(set: *const KboRefset) -> u64;
+        pub fn kbo_refset_positions(set: *const KboRefset, r: usize, out: *mut u32, n_rows: *mut usize) -> c_int;
+        pub fn kbo_refset_ref_len(set: *const KboRefset, r: usize) -> u64;
+        pub fn kbo_locate_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, runs: *const u32, n_runs: u64,
+                                 loci_out: *mut super::RefLocus) -> c_int;
+        pub fn kbo_locate_refset_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                     d_runs: *const u32, d_n_runs: *const u64, capacity: usize, d_loci: *mut super::RefLocus,
+                                     stream: *mut c_void) -> c_int;
+        pub fn kbo_locate_refset_host(set: *const KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, runs: *const u32,
+                                      n_runs: u64, loci_out: *mut super::RefLocus) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -335,12 +348,31 @@ pub unsafe fn summary_refset(set: *mut ffi::KboRefset, seqs: &[Vec<u8>], max_err
     out
 }
 
-/// `kbo_refset_opts`: `max_wide_rows` (16 384 ..= 2^20) and `prefilter` (0 or 1) of `kbo_refset_build_opts`.
+/// `kbo_refset_opts`: `max_wide_rows` (16 384 ..= 2^20), `prefilter` and `positions` (0 or 1) of `kbo_refset_build_opts`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct RefsetOpts {
     pub max_wide_rows: usize,
     pub prefilter: i32,
+    pub positions: i32,
+}
+
+/// `KBO_LOCUS_NONE` / `KBO_POS_NONE`, and `KBO_LOCUS_MULTI` (bit 31 of a table entry; bit 30: a REV occurrence).
+pub const LOCUS_NONE: u32 = 0xFFFF_FFFF;
+pub const LOCUS_MULTI: u32 = 0x8000_0000;
+
+/// `kbo_ref_locus` (24 bytes), one per `kbo_ref_run`: the run's first and last anchor as (position in the sequence on the run's
+/// strand, position on the reference), `LOCUS_NONE` without one.  `flags`: bit 0 / 1 the first / last anchor is a REV occurrence,
+/// bit 2 / 3 it is MULTI, bit 4 the record was not usable.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefLocus {
+    pub q_first: u32,
+    pub ref_first: u32,
+    pub q_last: u32,
+    pub ref_last: u32,
+    pub flags: u32,
+    pub n_tested: u32,
 }
 
 /// `kbo_refset_candidates` over a set built with a prefilter: `out[(r * n_seqs + s) * 2 + strand - 1]` says whether sequence `s` on

@@ -556,6 +556,8 @@ int kbo_refset_packed_only(const kbo_refset_t *set);       /* 1: no reference ta
 typedef struct {
     size_t max_wide_rows; /* KBO_REFSET_MAX_ROWS: as kbo_refset_build; up to KBO_REFSET_WIDE_MAX_ROWS: as kbo_refset_build_wide */
     int32_t prefilter;    /* 0 */
+    int32_t positions;    /* 0; 1: the set also carries a position table ("the locus of a run", below).  In what was tail padding:
+                           * sizeof(kbo_refset_opts) is unchanged */
 } kbo_refset_opts;
 void kbo_refset_opts_default(kbo_refset_opts *o);
 int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts,
@@ -734,6 +736,70 @@ size_t kbo_best_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n
 int kbo_best_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                                  double max_error_prob, int strands, void *d_work, size_t work_bytes, kbo_ref_best *d_out, size_t max_pairs,
                                  uint64_t max_pair_bases, kbo_refset_screen_stats *d_stats, void *stream);
+/* The LOCUS of a run: which part of its reference a kbo_ref_run covers.  Every coordinate of a run is one of the query sequence; a
+ * set built with kbo_refset_opts.positions = 1 also answers where on the reference the run lies - which half of the gene, forward or
+ * reverse - exactly and without a second alignment.  With positions = 0 (the default) the set is byte for byte what it is without the
+ * field: arena, descs, device copy and every *_work_bytes figure; values other than 0 and 1 give KBO_E_BAD_ARG.
+ * The table: one uint32_t per row of every reference of a packed route (LDS or wide) that can be queried, made on the host at build
+ * time by walking every indexed stretch - a maximal run of A, C, G, T of at least k bases, as for the seed table - and, with
+ * opts->add_revcomp, its reverse complement through the reference's own packed form.  An OCCURRENCE of a k-mer x in reference r is
+ * (p, FWD) when x equals ref[p, p + k) and (p, REV) when the reverse complement of x does (REV only with add_revcomp), the window
+ * inside an indexed stretch, p 0-based on the reference as given.  The entry of x's row holds, of x's occurrences, the one with FWD
+ * before REV and then the smallest p: bits 0 .. 29 p, bit 30 set for REV, bit 31 (KBO_LOCUS_MULTI) set when x has more than one
+ * occurrence; a row that is no full k-mer (a dummy row) holds KBO_POS_NONE.  References of the single-index route and references
+ * with a status have no entries.  A reference of 2^30 bases or more makes the build fail with KBO_E_UNSUPPORTED, before any work.
+ * (KBO_E_UNSUPPORTED too, behind the walk, should an indexed k-mer ever lack a row of its own in the packed form: the table cannot be made.)
+ * kbo_refset_to_device uploads the table with the arena (4 bytes a row + 8 a reference: kbo_refset_positions_bytes).
+ * kbo_refset_positions copies the entries of reference r (out may be NULL: *n_rows alone; 0 rows for a reference without entries;
+ * KBO_E_BAD_ARG for a set without positions or r >= N); kbo_refset_ref_len is a reference's length as given, kept for every set.
+ *
+ * A run covers the half-open 0-based range [run.start, run.end) of the sequence on its strand (format.rs:154,175: start is the index
+ * of the run's first character and end one past its last character that is no gap - as oracle/kbo_oracle.c's
+ * ora_run_lengths_gapped states it and the find tests compare it).  An ANCHOR of the run is a position i with run.start <= i and
+ * i + k <= run.end whose k bytes [i, i + k) of the strand's sequence are all A, C, G, T and are a k-mer of reference run.ref.  For
+ * strand == KBO_STRAND_REV the strand's sequence is the reverse complement as kbo_revcomp_batch defines it: byte j is the complement
+ * of byte len - 1 - j as given, and lower case is no base.  The first anchor is the smallest such i, the last anchor the largest;
+ * they may be the same.  A run without one - a run shorter than k included - has all four positions KBO_LOCUS_NONE and flags 0.
+ * Bit 4 of flags, with all positions KBO_LOCUS_NONE and n_tested 0, marks a record the call cannot use: ref >= N, a reference with a
+ * status or of the single-index route, seq >= n_seqs, a strand that is not 1 or 2, start > end, or end beyond the sequence.
+ *
+ * kbo_locate_refset: the batch is kbo_find_refset's ('+' as given), runs any n_runs records with (ref, seq, strand, run.start,
+ * run.end) set - kbo_find_refset's, on either or both strands - and loci_out receives n_runs records, same index.  It uploads the
+ * batch and the runs, launches ONE kernel (kbo_amd/csrc/refset_locate_kernels.hip: a wave per run, 64 windows a step, the packed form
+ * read from the arena) and downloads the loci: one synchronisation.  Errors, all before the first HIP call and in this order:
+ * KBO_E_BAD_ARG for null arguments (runs and loci_out may be NULL when n_runs == 0) and for a set without positions; the offsets as
+ * kbo_find_refset checks them; KBO_E_BAD_ARG for a record that bit 4 describes.  n_runs == 0 succeeds and touches no device.
+ * kbo_locate_refset_host is the same call restated on the CPU (no device; a test hook and a yardstick): byte-identical records.
+ * kbo_locate_refset_dev: kbo_find_refset_dev's contract for the batch (d_concat 16-byte aligned with 16 readable bytes behind
+ * total_bases, d_offsets 8-byte aligned) and d_runs / d_n_runs (4- / 8-byte aligned) exactly as kbo_find_refset_dev and
+ * kbo_find_refset_screened_dev leave them, so the calls compose on one stream with nothing read back.  It writes
+ * min(*d_n_runs, capacity) records to d_loci (4-byte aligned) and nothing at or behind element `capacity` (d_runs and d_loci may be
+ * NULL when capacity == 0); one launch, no synchronisation, no allocation, no scratch.  The kernel checks every record itself from
+ * the descs and the offsets and reads nothing outside the batch, the arena and the table: a record that bit 4 describes - or an
+ * offset pair that is descending or beyond total_bases - gets bit 4, never a fault.  KBO_E_BAD_ARG before anything is enqueued for
+ * null or misaligned pointers, a set without positions and a set without a copy on the current device; KBO_E_EMPTY_QUERY for
+ * n_seqs == 0.
+ * n_tested counts the k-mer windows handed to lanes for this run, 64 at a time from the front until a group holds an anchor and
+ * then from the back (both directions; the last group of a direction counts the windows that are left): a work count. */
+#define KBO_POS_NONE 0xFFFFFFFFu
+#define KBO_LOCUS_MULTI 0x80000000u
+#define KBO_LOCUS_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t q_first, ref_first; /* first anchor: position in the sequence on the run's strand of the k-mer's first base; the table's p */
+    uint32_t q_last, ref_last;   /* last anchor */
+    uint32_t flags;              /* bit 0 / 1: first / last anchor is a REV occurrence; bit 2 / 3: it is MULTI; bit 4: the record was not usable */
+    uint32_t n_tested;           /* k-mer windows looked up for this run (both directions) */
+} kbo_ref_locus; /* 24 bytes, one per kbo_ref_run, same index */
+int kbo_refset_has_positions(const kbo_refset_t *set);        /* 1 or 0 */
+uint64_t kbo_refset_positions_bytes(const kbo_refset_t *set); /* the position table's bytes; 0 without one */
+int kbo_refset_positions(const kbo_refset_t *set, size_t r, uint32_t *out, size_t *n_rows);
+uint64_t kbo_refset_ref_len(const kbo_refset_t *set, size_t r); /* 0 for r >= N */
+int kbo_locate_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                      uint64_t n_runs, kbo_ref_locus *loci_out);
+int kbo_locate_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                          const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_locus *d_loci, void *stream);
+int kbo_locate_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                           uint64_t n_runs, kbo_ref_locus *loci_out);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

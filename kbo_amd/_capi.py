@@ -40,7 +40,12 @@ class FindOpts(C.Structure):
 
 class RefsetOpts(C.Structure):
     """kbo_hip.h kbo_refset_opts"""
-    _fields_ = [("max_wide_rows", C.c_size_t), ("prefilter", C.c_int32)]
+    _fields_ = [("max_wide_rows", C.c_size_t), ("prefilter", C.c_int32), ("positions", C.c_int32)]
+
+
+class RefLocus(C.Structure):
+    """kbo_hip.h kbo_ref_locus"""
+    _fields_ = [(n, C.c_uint32) for n in ("q_first", "ref_first", "q_last", "ref_last", "flags", "n_tested")]
 
 
 class MapOpts(C.Structure):
@@ -132,6 +137,8 @@ SYMBOLS = [
     "kbo_refset_candidates_dev_work_bytes", "kbo_refset_candidates_dev", "kbo_find_refset_screened_dev_work_bytes",
     "kbo_find_refset_screened_dev", "kbo_summary_refset_screened_dev_work_bytes", "kbo_summary_refset_screened_dev",
     "kbo_best_refset_screened_dev_work_bytes", "kbo_best_refset_screened_dev",
+    "kbo_refset_has_positions", "kbo_refset_positions_bytes", "kbo_refset_positions", "kbo_refset_ref_len",
+    "kbo_locate_refset", "kbo_locate_refset_dev", "kbo_locate_refset_host",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -376,6 +383,13 @@ def lib():
     L.kbo_best_refset_screened_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, u64]
     L.kbo_best_refset_screened_dev_work_bytes.restype = sz
     L.kbo_best_refset_screened_dev.argtypes = [vp, vp, vp, sz, u64, C.c_double, C.c_int, vp, sz, vp, sz, u64, vp, vp]
+    L.kbo_refset_has_positions.argtypes = [vp]
+    L.kbo_refset_positions_bytes.argtypes = [vp]; L.kbo_refset_positions_bytes.restype = u64
+    L.kbo_refset_positions.argtypes = [vp, sz, vp, C.POINTER(sz)]
+    L.kbo_refset_ref_len.argtypes = [vp, sz]; L.kbo_refset_ref_len.restype = u64
+    L.kbo_locate_refset.argtypes = [vp, vp, vp, sz, vp, u64, vp]
+    L.kbo_locate_refset_host.argtypes = [vp, vp, vp, sz, vp, u64, vp]
+    L.kbo_locate_refset_dev.argtypes = [vp, vp, vp, sz, u64, vp, vp, sz, vp, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

@@ -647,6 +647,25 @@ struct RefsetScreenArgs {
 };
 hipError_t launch_refset_screen(const RefsetScreenArgs &a, hipStream_t stream); // one launch; none for total == 0
 
+// ---- the locus of a run (refset_locate_kernels.hip; the look-up and the record: refset_locate.hpp).  One wave per record of d_runs,
+// grid-strided over min(*n_runs, capacity); the kernel checks every record against the descs and the offsets itself and reads nothing
+// outside the batch, the arena and the table.  positions: the set's entries, reference r's rows from pos_off[r] on
+struct RefsetLocateArgs {
+    const RefsetDesc *descs;
+    const uint4 *arena;
+    const uint32_t *positions;
+    const uint64_t *pos_off;
+    const uint8_t *q;        // the '+' batch
+    const uint64_t *off;     // n_seqs + 1
+    const uint32_t *runs;    // kbo_ref_run: ten u32 a record
+    const uint64_t *n_runs;  // on the device
+    uint32_t *loci;          // kbo_ref_locus: six u32 a record
+    uint64_t capacity, total;
+    uint32_t n_refs, n_seqs, k;
+};
+constexpr uint32_t kRefsetLocateThreads = 256;
+hipError_t launch_refset_locate(const RefsetLocateArgs &a, hipStream_t stream); // one launch; none for capacity == 0
+
 // ---- the screened device forms (refset_cand_kernels.hip; the arithmetic: refset_cand.hpp): the bitmap of the screen to the list of
 // its set bits, ONE slab of the list's longest prefix within the caps planned from it, and the record and merge stages that name a
 // pair by the list.  Everything is read on the device; stream order is the only synchronisation.

@@ -9,10 +9,13 @@
 // A set built with a prefilter (kbo_refset_build_opts) carries a seed table (refset_screen.hpp); the host forms then mark the pairs
 // that share a seed with one kernel over the uploaded batch (refset_screen_kernels.hip), read the bitmap back, and plan, upload and
 // walk only the marked pairs.  kbo_refset_candidates is that screen alone, kbo_refset_candidates_host its restatement on the CPU.
+// A set built with positions carries one entry per row of every packed reference (refset_locate.hpp); kbo_locate_refset turns the
+// runs of a find into anchors on the references with one kernel (refset_locate_kernels.hip), kbo_locate_refset_host on the CPU.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 #include "refset_best.hpp"
 #include "refset_cand.hpp"
+#include "refset_locate.hpp"
 #include "refset_screen.hpp"
 #include "refset_step.hpp"
 
@@ -29,6 +32,10 @@ static_assert(kbo::kRefsetWideMaxRows == KBO_REFSET_WIDE_MAX_ROWS && kbo::kRefse
 static_assert(kbo::refscreen::kSeedMax == KBO_REFSET_SEED_MAX && kbo::refscreen::kSeedMin == KBO_REFSET_SEED_MIN &&
                   kbo::kRefsetScreenRun == KBO_REFSET_SCREEN_RUN && kbo::kRefsetScreenThreads == KBO_REFSET_SCREEN_THREADS,
               "the headers state the screen's constants");
+static_assert(kbo::reflocate::kPosNone == KBO_POS_NONE && kbo::reflocate::kPosNone == KBO_LOCUS_NONE && kbo::reflocate::kMulti == KBO_LOCUS_MULTI &&
+                  sizeof(kbo_ref_locus) == 24 && sizeof(kbo_ref_locus) == sizeof(kbo::reflocate::Locus),
+              "kbo_hip.h states the position table's constants and the six words of a locus");
+static_assert(sizeof(kbo_refset_opts) == sizeof(size_t) + 8, "kbo_refset_opts: positions lies in what was the struct's tail padding");
 
 namespace {
 constexpr uint64_t kPrefilterMaxBits = 1ull << 31; // the bitmap is read back: above this many bits a call runs unscreened
@@ -42,6 +49,7 @@ thread_local uint64_t t_best[2] = {0, 0}; // launches of refset_best_kernel: a w
 struct DevSet {
     DevBuf arena, descs;
     DevBuf pre_bucket, pre_keys, pre_refs; // the seed table of a set with a prefilter
+    DevBuf pos, pos_off;                   // the position table of a set with positions, and where each reference's entries begin
 };
 
 struct DeviceScope { // the calling thread on `device` until the scope ends
@@ -83,6 +91,12 @@ struct kbo_refset {
     bool prefilter = false;
     std::vector<uint32_t> pre_bucket, pre_refs;
     std::vector<uint64_t> pre_keys;
+    // the position table of a set built with positions (refset_locate.hpp): one entry per row of every packed reference that can be
+    // queried, reference r's from pos_off[r] on (n_refs + 1 offsets)
+    bool positions = false;
+    std::vector<uint32_t> pos;
+    std::vector<uint64_t> pos_off;
+    std::vector<uint64_t> ref_len; // every reference's length as given
     std::mutex mu;
     std::map<int, DevSet *> dev;
     ~kbo_refset()
@@ -136,6 +150,12 @@ DevSet *device_set(kbo_refset *set, int device)
             HIP_OK(hipMemcpy(d->pre_keys.p, set->pre_keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
             HIP_OK(hipMemcpy(d->pre_refs.p, set->pre_refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
+    }
+    if (set->positions) {
+        d->pos.alloc(set->pos.size() * sizeof(uint32_t) + 16);
+        d->pos_off.alloc(set->pos_off.size() * sizeof(uint64_t));
+        if (!set->pos.empty()) HIP_OK(hipMemcpy(d->pos.p, set->pos.data(), set->pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d->pos_off.p, set->pos_off.data(), set->pos_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     set->dev[device] = d.get();
     return d.release();
@@ -484,6 +504,85 @@ struct HostTable { // refset_screen.hpp's accessor over the set's host table
 };
 
 bool packed_ok(const kbo::RefsetDesc &d) { return !d.status && d.route != kbo::kRefsetRouteIndex; }
+
+struct HostForm { // refset_step.hpp's accessor over the host arena
+    const uint32_t *rank_;
+    const uint8_t *lcs_;
+    kbo::refstep::Entry rank(uint32_t block, uint32_t c) const
+    {
+        const uint32_t *e = rank_ + ((size_t)block * 4u + c) * 2u;
+        return kbo::refstep::Entry{e[0], e[1]};
+    }
+    uint32_t lcs(uint32_t i) const { return lcs_[i]; }
+};
+HostForm host_form(const kbo_refset *set, const kbo::RefsetDesc &d)
+{
+    const uint32_t *form = set->arena.data() + (size_t)d.off * 4u;
+    return HostForm{form, reinterpret_cast<const uint8_t *>(form + 4u * (size_t)kbo::refset_rank_units(d.n_sets))};
+}
+
+// ---- the position table (refset_locate.hpp): every indexed stretch of every packed reference that can be queried - the stretches
+// build_prefilter enumerates - walked through the reference's own packed form with the walk's step; at depth k the interval is the
+// one row of the k-mer that ends there.  With add_revcomp the stretch's reverse complement too: its k-mers are REV occurrences
+void build_positions(kbo_refset *set, const uint8_t *const *seqs, const size_t *lens, bool add_revcomp, uint32_t num_threads)
+{
+    namespace lc = kbo::reflocate;
+    const size_t n_refs = set->descs.size();
+    const uint32_t k = set->k;
+    set->pos_off.assign(n_refs + 1, 0);
+    for (size_t r = 0; r < n_refs; r++) set->pos_off[r + 1] = set->pos_off[r] + (packed_ok(set->descs[r]) ? set->descs[r].n_sets : 0u);
+    set->pos.assign((size_t)set->pos_off[n_refs], lc::kPosNone);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> bad{false};
+    auto work = [&] {
+        std::vector<uint8_t> rc;
+        for (size_t r; (r = next.fetch_add(1)) < n_refs;) {
+            const kbo::RefsetDesc &d = set->descs[r];
+            if (!packed_ok(d)) continue;
+            const HostForm x = host_form(set, d);
+            uint32_t *entries = set->pos.data() + set->pos_off[r];
+            // b: a stretch (or its reverse complement) of n bases; the window [s, s + k) of it is the occurrence at p0 + s / p0 - s
+            auto add_stretch = [&](const uint8_t *b, size_t n, size_t p0, bool rev) {
+                uint32_t lo = 0, hi = d.n_sets, depth = 0;
+                for (size_t i = 0; i < n; i++) {
+                    kbo::refstep::step(x, d.n_sets, k, b[i], lo, hi, depth);
+                    if (i + 1 < k) continue;
+                    if (depth != k || hi - lo != 1u) { // (an indexed k-mer has exactly one row)
+                        bad = true;
+                        return;
+                    }
+                    const size_t s = i + 1 - k;
+                    entries[lo] = lc::entry_merge(entries[lo], lc::entry_of((uint32_t)(rev ? p0 - s : p0 + s), rev));
+                }
+            };
+            const uint8_t *q = seqs[r];
+            for (size_t i = 0, n = lens[r]; i < n;) {
+                if (kbo::refstep::base_code(q[i]) > 3u) {
+                    i++;
+                    continue;
+                }
+                size_t j = i;
+                while (j < n && kbo::refstep::base_code(q[j]) <= 3u) j++;
+                if (j - i >= k) {
+                    add_stretch(q + i, j - i, i, false);
+                    if (add_revcomp) { // window s of the reverse complement covers [j - s - k, j - s) of the reference
+                        rc.resize(j - i);
+                        for (size_t y = 0; y < j - i; y++) rc[y] = (uint8_t)"TGCA"[kbo::refstep::base_code(q[j - 1 - y])];
+                        add_stretch(rc.data(), rc.size(), j - k, true);
+                    }
+                }
+                i = j;
+            }
+        }
+    };
+    std::vector<std::thread> team;
+    for (uint32_t t = 1; t < std::min<size_t>(num_threads, n_refs); t++) team.emplace_back(work);
+    work();
+    for (auto &t : team) t.join();
+    // (the walk contradicts the index it walks: what building or querying such a reference alone cannot do either)
+    KBO_REQUIRE(!bad.load(), KBO_E_UNSUPPORTED, "positions: an indexed k-mer without a row of its own in the reference's packed form");
+    set->positions = true;
+}
 
 // One entry per start position of every indexed stretch (a maximal run of bases of at least k, as build_host_index sees them; its
 // reverse complement too with add_revcomp) of every packed reference that can be queried, sorted by key, and the bucket offsets
@@ -1182,6 +1281,7 @@ void kbo_refset_opts_default(kbo_refset_opts *o)
     if (!o) return;
     o->max_wide_rows = KBO_REFSET_MAX_ROWS;
     o->prefilter = 0;
+    o->positions = 0;
 }
 
 int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t n_refs, const kbo_build_opts *opts,
@@ -1194,11 +1294,15 @@ int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t
         if (refset_opts) ro = *refset_opts; else kbo_refset_opts_default(&ro);
         const size_t max_wide_rows = ro.max_wide_rows;
         KBO_REQUIRE(ro.prefilter == 0 || ro.prefilter == 1, KBO_E_BAD_ARG, "prefilter: 0 or 1");
+        KBO_REQUIRE(ro.positions == 0 || ro.positions == 1, KBO_E_BAD_ARG, "positions: 0 or 1");
         KBO_REQUIRE(max_wide_rows >= KBO_REFSET_MAX_ROWS && max_wide_rows <= KBO_REFSET_WIDE_MAX_ROWS, KBO_E_BAD_ARG,
                     "max_wide_rows in KBO_REFSET_MAX_ROWS .. KBO_REFSET_WIDE_MAX_ROWS");
         KBO_REQUIRE(seqs && lens && n_refs > 0, KBO_E_BAD_ARG, "assert!(!slices.is_empty()) (index.rs:60)");
         KBO_REQUIRE(n_refs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 references");
         for (size_t r = 0; r < n_refs; r++) KBO_REQUIRE(seqs[r] || lens[r] == 0, KBO_E_BAD_ARG, "null reference sequence");
+        if (ro.positions)
+            for (size_t r = 0; r < n_refs; r++)
+                KBO_REQUIRE(lens[r] < kbo::reflocate::kMaxRefLen, KBO_E_UNSUPPORTED, "positions: a reference of 2^30 bases or more");
         kbo_build_opts o;
         if (opts) o = *opts; else kbo_build_opts_default(&o);
         KBO_REQUIRE(o.k > 0 && o.k <= 255, KBO_E_BAD_ARG, "k must be in 1..255");
@@ -1206,6 +1310,7 @@ int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t
         set->k = o.k;
         set->descs.assign(n_refs, kbo::RefsetDesc{});
         set->own.resize(n_refs);
+        set->ref_len.assign(lens, lens + n_refs);
         std::vector<std::vector<uint32_t>> forms(n_refs);
         std::atomic<size_t> next{0};
         auto work = [&] {
@@ -1250,6 +1355,7 @@ int kbo_refset_build_opts(const uint8_t *const *seqs, const size_t *lens, size_t
             std::vector<uint32_t>().swap(forms[r]);
         }
         if (ro.prefilter) build_prefilter(set.get(), seqs, lens, o.add_revcomp != 0); // (the sequences are at hand here only)
+        if (ro.positions) build_positions(set.get(), seqs, lens, o.add_revcomp != 0, std::max(1u, o.num_threads));
         *out = set.release();
     });
 }
@@ -1299,16 +1405,6 @@ int kbo_refset_packed_only(const kbo_refset_t *set)
 }
 
 namespace {
-struct HostForm { // refset_step.hpp's accessor over the host arena
-    const uint32_t *rank_;
-    const uint8_t *lcs_;
-    kbo::refstep::Entry rank(uint32_t block, uint32_t c) const
-    {
-        const uint32_t *e = rank_ + ((size_t)block * 4u + c) * 2u;
-        return kbo::refstep::Entry{e[0], e[1]};
-    }
-    uint32_t lcs(uint32_t i) const { return lcs_[i]; }
-};
 const kbo::RefsetDesc *packed_desc(const kbo_refset_t *set, size_t r)
 {
     if (!set || r >= set->descs.size()) return nullptr;
@@ -1741,6 +1837,155 @@ int kbo_best_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, con
                                        static_cast<hipStream_t>(stream)},
                                max_pairs, max_pair_bases, nullptr, d_stats},
                       kCandBest);
+    });
+}
+
+// ---- the locus of a run (refset_locate.hpp; refset_locate_kernels.hip)
+} // extern "C"
+
+namespace {
+namespace lc = kbo::reflocate;
+
+struct HostSeq { // refset_locate.hpp's accessors over the '+' batch and a reference's entries on the host
+    const uint8_t *q_;
+    uint32_t byte(uint64_t i) const { return q_[i]; }
+};
+struct HostPos {
+    const uint32_t *pos_;
+    uint32_t entry(uint32_t row) const { return pos_[row]; }
+};
+
+// the checks of kbo_locate_refset and its host form, all before any work; the batch's bases
+uint64_t check_locate(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                      uint64_t n_runs, const kbo_ref_locus *loci_out)
+{
+    KBO_REQUIRE(set && concat && offsets && (n_runs == 0 || (runs && loci_out)), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(set->positions, KBO_E_BAD_ARG, "the set has no positions (kbo_refset_build_opts)");
+    const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
+    for (uint64_t x = 0; x < n_runs; x++) {
+        const kbo_ref_run &w = runs[x];
+        KBO_REQUIRE(w.ref < set->descs.size() && packed_ok(set->descs[w.ref]), KBO_E_BAD_ARG,
+                    "a run of a reference that is not in the set, has a status or takes the single-index route");
+        KBO_REQUIRE(w.seq < n_seqs && (w.strand == KBO_STRAND_FWD || w.strand == KBO_STRAND_REV), KBO_E_BAD_ARG,
+                    "a run of a sequence that is not in the batch, or of no strand");
+        KBO_REQUIRE(lc::span_ok(offsets[w.seq], offsets[w.seq + 1], total, w.run.start, w.run.end), KBO_E_BAD_ARG,
+                    "a run with start > end, or end beyond its sequence");
+    }
+    return total;
+}
+
+kbo::RefsetLocateArgs locate_args(const kbo_refset *set, const DevSet *ds)
+{
+    kbo::RefsetLocateArgs a{};
+    a.descs = ds->descs.as<kbo::RefsetDesc>();
+    a.arena = ds->arena.as<uint4>();
+    a.positions = ds->pos.as<uint32_t>();
+    a.pos_off = ds->pos_off.as<uint64_t>();
+    a.n_refs = (uint32_t)set->descs.size();
+    a.k = set->k;
+    return a;
+}
+} // namespace
+
+extern "C" {
+
+int kbo_refset_has_positions(const kbo_refset_t *set) { return set && set->positions ? 1 : 0; }
+
+uint64_t kbo_refset_positions_bytes(const kbo_refset_t *set)
+{
+    if (!set || !set->positions) return 0;
+    return (uint64_t)set->pos.size() * sizeof(uint32_t) + (uint64_t)set->pos_off.size() * sizeof(uint64_t);
+}
+
+int kbo_refset_positions(const kbo_refset_t *set, size_t r, uint32_t *out, size_t *n_rows)
+{
+    if (!set || !set->positions || r >= set->descs.size() || !n_rows) return KBO_E_BAD_ARG;
+    *n_rows = (size_t)(set->pos_off[r + 1] - set->pos_off[r]);
+    if (out && *n_rows) std::memcpy(out, set->pos.data() + set->pos_off[r], *n_rows * sizeof(uint32_t));
+    return KBO_OK;
+}
+
+uint64_t kbo_refset_ref_len(const kbo_refset_t *set, size_t r) { return set && r < set->ref_len.size() ? set->ref_len[r] : 0; }
+
+int kbo_locate_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                           uint64_t n_runs, kbo_ref_locus *loci_out)
+{
+    return guarded([&] {
+        (void)check_locate(set, concat, offsets, n_seqs, runs, n_runs, loci_out);
+        const HostSeq q{concat};
+        for (uint64_t x = 0; x < n_runs; x++) {
+            const kbo_ref_run &w = runs[x];
+            const kbo::RefsetDesc &d = set->descs[w.ref];
+            const HostForm form = host_form(set, d);
+            const HostPos pos{set->pos.data() + set->pos_off[w.ref]};
+            const uint64_t begin = offsets[w.seq], len = offsets[w.seq + 1] - begin;
+            const bool rev = w.strand == KBO_STRAND_REV;
+            const lc::Locus L = lc::locate_serial(w.run.start, w.run.end, set->k, [&](uint32_t i) {
+                return lc::kmer_entry(form, d.n_sets, set->k, q, begin, len, rev, pos, i);
+            });
+            std::memcpy(&loci_out[x], &L, sizeof L);
+        }
+    });
+}
+
+int kbo_locate_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                      uint64_t n_runs, kbo_ref_locus *loci_out)
+{
+    return guarded([&] {
+        const uint64_t total = check_locate(set, concat, offsets, n_seqs, runs, n_runs, loci_out);
+        if (n_runs == 0) return;
+        DevSet *ds = device_set(set, current_device());
+        StreamScope stream;
+        DevBuf d_q((size_t)(total + 15) / 16 * 16 + 16), d_off((n_seqs + 1) * sizeof(uint64_t)), d_runs((size_t)n_runs * sizeof(kbo_ref_run)), d_n(16),
+            d_loci((size_t)n_runs * sizeof(kbo_ref_locus));
+        HIP_OK(hipMemcpyAsync(d_q.p, concat, total, hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_runs.p, runs, (size_t)n_runs * sizeof(kbo_ref_run), hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_n.p, &n_runs, sizeof(uint64_t), hipMemcpyHostToDevice, stream.s));
+        kbo::RefsetLocateArgs a = locate_args(set, ds);
+        a.q = d_q.as<uint8_t>();
+        a.off = d_off.as<uint64_t>();
+        a.runs = d_runs.as<uint32_t>();
+        a.n_runs = d_n.as<uint64_t>();
+        a.loci = d_loci.as<uint32_t>();
+        a.capacity = n_runs;
+        a.total = total;
+        a.n_seqs = (uint32_t)n_seqs;
+        HIP_OK(kbo::launch_refset_locate(a, stream.s));
+        HIP_OK(hipMemcpyAsync(loci_out, d_loci.p, (size_t)n_runs * sizeof(kbo_ref_locus), hipMemcpyDeviceToHost, stream.s));
+        HIP_OK(hipStreamSynchronize(stream.s)); // the call's one wait
+    });
+}
+
+int kbo_locate_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                          const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_locus *d_loci, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(set && d_concat && d_offsets && d_n_runs && (capacity == 0 || (d_runs && d_loci)), KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(((uintptr_t)d_concat & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_n_runs & 7) == 0 &&
+                        ((uintptr_t)d_runs & 3) == 0 && ((uintptr_t)d_loci & 3) == 0,
+                    KBO_E_BAD_ARG, "d_concat 16-byte, d_offsets and the count 8-byte, the records 4-byte aligned");
+        KBO_REQUIRE(set->positions, KBO_E_BAD_ARG, "the set has no positions (kbo_refset_build_opts)");
+        KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+        KBO_REQUIRE(n_seqs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 sequences per call");
+        bool any_copy;
+        {
+            std::lock_guard<std::mutex> g(set->mu);
+            any_copy = !set->dev.empty();
+        }
+        KBO_REQUIRE(any_copy, KBO_E_BAD_ARG, "the set has no copy on any device (kbo_refset_to_device)"); // (no device is asked)
+        DevSet *ds = device_set_if_any(set, current_device());
+        KBO_REQUIRE(ds, KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
+        kbo::RefsetLocateArgs a = locate_args(set, ds);
+        a.q = d_concat;
+        a.off = d_offsets;
+        a.runs = reinterpret_cast<const uint32_t *>(d_runs);
+        a.n_runs = d_n_runs;
+        a.loci = reinterpret_cast<uint32_t *>(d_loci);
+        a.capacity = capacity;
+        a.total = total_bases;
+        a.n_seqs = (uint32_t)n_seqs;
+        HIP_OK(kbo::launch_refset_locate(a, static_cast<hipStream_t>(stream)));
     });
 }
 

@@ -30,6 +30,14 @@ REF_BEST = np.dtype([("seq", np.uint32), ("ref", np.uint32), ("strand", np.uint3
                      ("n_jump", np.uint32), ("n_runs", np.uint32), ("start", np.uint32), ("end", np.uint32), ("n_hits", np.uint32),
                      ("second_ref", np.uint32), ("second_match", np.uint32)])
 
+# kbo_ref_locus (24 bytes), one per REF_RUN record: the run's first and last anchor - a k-mer window of the run that is a k-mer of
+# the reference - as (position in the sequence on the run's strand, position on the reference); LOCUS_NONE where there is none
+LOCUS_NONE = POS_NONE = 0xFFFFFFFF
+LOCUS_MULTI = 0x80000000  # bit 31 of a table entry: the k-mer has more than one occurrence; bit 30: the entry is a REV occurrence
+LOCUS_FIRST_REV, LOCUS_LAST_REV, LOCUS_FIRST_MULTI, LOCUS_LAST_MULTI, LOCUS_UNUSABLE = 1, 2, 4, 8, 16  # flags
+REF_LOCUS = np.dtype([("q_first", np.uint32), ("ref_first", np.uint32), ("q_last", np.uint32), ("ref_last", np.uint32),
+                      ("flags", np.uint32), ("n_tested", np.uint32)])
+
 
 class RefSet:
     """kbo_refset_t: index r is what kbo::build (lib.rs:501-506) makes of reference r alone"""
@@ -38,12 +46,14 @@ class RefSet:
         self._h = handle
 
     @classmethod
-    def build(cls, seqs, build_opts=None, wide_rows=None, prefilter=False):
+    def build(cls, seqs, build_opts=None, wide_rows=None, prefilter=False, positions=False):
         """wide_rows: None - kbo_refset_build: a reference of more than MAX_ROWS rows takes the single-index route; a number in
         MAX_ROWS .. WIDE_MAX_ROWS - kbo_refset_build_wide: references of up to that many rows keep their packed form in the set and
         take the wide route, in the same slabs as the small ones, and a set without a larger one can go to find_refset_dev.
         prefilter: kbo_refset_build_opts with a seed table - find_refset, summary_refset and best_refset then screen the (reference,
-        sequence, strand) pairs on the device and walk only those that share a seed; the records are the same"""
+        sequence, strand) pairs on the device and walk only those that share a seed; the records are the same.
+        positions: kbo_refset_build_opts with a position table - one entry per row of every packed reference, what locate_refset
+        needs to say where on its reference a run lies"""
         from . import BuildOpts
         o = build_opts if build_opts is not None else BuildOpts()
         raw = [bytes(_u8(s)) for s in seqs]
@@ -51,8 +61,8 @@ class RefSet:
         lens = (C.c_size_t * max(1, len(raw)))(*[len(s) for s in raw])
         co = o._to_c()
         h = C.c_void_p()
-        if prefilter:
-            ro = _capi.RefsetOpts(MAX_ROWS if wide_rows is None else int(wide_rows), 1)
+        if prefilter or positions:
+            ro = _capi.RefsetOpts(MAX_ROWS if wide_rows is None else int(wide_rows), 1 if prefilter else 0, 1 if positions else 0)
             check(lib().kbo_refset_build_opts(arr, lens, len(raw), C.byref(co), C.byref(ro), C.byref(h)))
         elif wide_rows is None:
             check(lib().kbo_refset_build(arr, lens, len(raw), C.byref(co), C.byref(h)))
@@ -132,6 +142,27 @@ class RefSet:
                                               work.data_ptr(), wb, bits.data_ptr(), stats.data_ptr(), s.cuda_stream))
         return bits, stats
 
+    def has_positions(self):
+        """True for a set built with positions=True"""
+        return bool(lib().kbo_refset_has_positions(self._h))
+
+    def positions_bytes(self):
+        """bytes of the position table (4 a row + 8 a reference); 0 without one"""
+        return int(lib().kbo_refset_positions_bytes(self._h))
+
+    def positions(self, r):
+        """test hook: the table's entries of reference r, one uint32 per row of its index (none for a reference without a packed
+        form): bits 0 .. 29 p, bit 30 REV, bit 31 LOCUS_MULTI; POS_NONE for a row that is no full k-mer"""
+        n = C.c_size_t()
+        check(lib().kbo_refset_positions(self._h, r, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        check(lib().kbo_refset_positions(self._h, r, out.ctypes.data, C.byref(n)))
+        return out
+
+    def ref_len(self, r):
+        """the length of reference r as it was given"""
+        return int(lib().kbo_refset_ref_len(self._h, r))
+
     def form(self, r):
         """test hook: the packed form of an LDS or wide reference, as bytes in a uint8 array"""
         n = C.c_size_t()
@@ -161,10 +192,13 @@ def _batch(query_seqs):
     return concat, offsets, len(raw)
 
 
-def find_refset(query_seqs, refset, find_opts=None, strands=STRAND_BOTH):
+def find_refset(query_seqs, refset, find_opts=None, strands=STRAND_BOTH, locate=False):
     """kbo::find (lib.rs:808-821) of every query sequence, on the strands asked for, against every reference of the set ->
     structured array of REF_RUN records ordered by (ref, seq, strand, start); '-' runs in the coordinates of the
-    reverse-complemented sequence"""
+    reverse-complemented sequence.  locate=True (a set built with positions=True): (runs, loci), loci as locate_refset's"""
+    if locate:
+        runs = find_refset(query_seqs, refset, find_opts, strands)
+        return runs, locate_refset(query_seqs, refset, runs)
     from . import FindOpts
     o = find_opts if find_opts is not None else FindOpts()
     co = _capi.FindOpts(o.max_error_prob, o.max_gap_len)
@@ -181,6 +215,62 @@ def find_refset(query_seqs, refset, find_opts=None, strands=STRAND_BOTH):
         return np.frombuffer(buf, dtype=REF_RUN).copy()
     finally:
         lib().kbo_free(p)
+
+
+def locate_refset(query_seqs, refset, runs, host=False):
+    """kbo_locate_refset: where the runs of find_refset (REF_RUN records of the same query_seqs and set; the set built with
+    positions=True) lie on their references -> a structured array of REF_LOCUS records, one per run, same index.
+    host=True: the restatement on the CPU (kbo_locate_refset_host), byte-identical"""
+    concat, offsets, n = _batch(query_seqs)
+    runs = np.ascontiguousarray(runs, dtype=REF_RUN)
+    loci = np.zeros(len(runs), dtype=REF_LOCUS)
+    f = lib().kbo_locate_refset_host if host else lib().kbo_locate_refset
+    check(f(refset._h, concat.ctypes.data, offsets.ctypes.data, n, runs.ctypes.data, len(runs), loci.ctypes.data))
+    return loci
+
+
+def locate_refset_dev(concat, offsets, refset, d_runs, d_n_runs, capacity, stream=None):
+    """kbo_locate_refset_dev over torch tensors on the device: d_runs / d_n_runs as find_refset_dev returns them (records, count), the
+    batch by find_refset_dev's conventions -> a (capacity, 6) int32 tensor that holds the u32 words of REF_LOCUS, the first
+    min(count, capacity) rows written.  One launch on `stream` (default: the current one).  kbo_locate_refset_dev itself synchronises
+    nothing; this wrapper, like find_refset_dev, reads offsets[-1] back once for the batch's bases, which waits for the device."""
+    import torch
+    q, off, n_seqs, total, s = _dev_batch(concat, offsets, stream)
+    capacity = int(capacity)
+    with torch.cuda.device(q.device), torch.cuda.stream(s):
+        loci = torch.empty((capacity, 6), dtype=torch.int32, device=q.device)
+        check(lib().kbo_locate_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, d_runs.data_ptr() if capacity else None,
+                                          d_n_runs.data_ptr(), capacity, loci.data_ptr() if capacity else None, s.cuda_stream))
+    return loci
+
+
+def locus_interval(runs, loci, k, ref_lens):
+    """Where each run lies on its reference, from its two anchors: (ref_lo, ref_hi, orientation), three int64 arrays.  The run's
+    first base is projected along the diagonal of the first anchor and its last base along that of the last anchor - forward for a
+    FWD anchor (query i <-> reference ref + (i - q)), antiparallel for a REV one (query i <-> reference ref + k - 1 - (i - q)) - and
+    [ref_lo, ref_hi) is the range between the two images, both ends clipped to 0 .. ref_len (a projection that falls wholly
+    outside the reference - possible only with indels - gives an empty range, ref_lo == ref_hi).  orientation: 1 when both anchors are FWD (the
+    run's strand of the sequence reads along the reference), 2 when both are REV; 3 when they differ - an inverted repeat
+    or a MULTI k-mer whose first occurrence lies on the other strand: neither forward nor reverse can be claimed, so neither is.  An ESTIMATE that is exact when
+    the run holds no insertion or deletion: substitutions keep a diagonal, indels shift it.  A run without an anchor gets -1 in all
+    three.  ref_lens: the references' lengths, indexed by runs["ref"] (RefSet.ref_len)."""
+    runs = np.asarray(runs)
+    loci = np.asarray(loci)
+    ref_lens = np.asarray(ref_lens, dtype=np.int64)
+    k = int(k)
+    start, end = runs["start"].astype(np.int64), runs["end"].astype(np.int64)
+    qf, rf = loci["q_first"].astype(np.int64), loci["ref_first"].astype(np.int64)
+    ql, rl = loci["q_last"].astype(np.int64), loci["ref_last"].astype(np.int64)
+    flags = loci["flags"].astype(np.int64)
+    none = loci["q_first"] == LOCUS_NONE
+    first_rev, last_rev = (flags & LOCUS_FIRST_REV) != 0, (flags & LOCUS_LAST_REV) != 0
+    a = np.where(first_rev, rf + k - 1 + (qf - start), rf - (qf - start))            # the image of the run's first base
+    b = np.where(last_rev, rl + k - 1 - (end - 1 - ql), rl + (end - 1 - ql))          # ... and of its last base
+    n = ref_lens[np.where(none, 0, runs["ref"].astype(np.int64))] if len(runs) else np.zeros(0, dtype=np.int64)
+    lo = np.clip(np.minimum(a, b), 0, n)
+    hi = np.clip(np.maximum(a, b) + 1, 0, n)
+    orient = np.where(first_rev & last_rev, 2, np.where(first_rev | last_rev, 3, 1))
+    return np.where(none, -1, lo), np.where(none, -1, hi), np.where(none, -1, orient)
 
 
 def summary_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH):

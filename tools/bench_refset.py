@@ -36,6 +36,12 @@ one read-back of RefSet.candidates_dev's figures outside the timed region), next
 set (REFS_PER_SLAB, DEV_CAPACITY as above) and next to the host form, which screens.  The batch is uploaded once outside the timed
 regions; a timed device call ends when its records are on the host.  Median of REPEATS behind a warm-up for each; records_crc32 of
 each, the statistics the screened call left on the device, and the ratios.
+LOCATE=1 is a leg of its own on the first workload, one session: two sets, without and with the position table
+(RefSet.build(..., positions=True); with PREFILTER=1 both carry the seed table, so the find in front of the locate screens), and on
+the second one kbo_find_refset, kbo_find_refset followed by kbo_locate_refset (find_refset(..., locate=True)), and kbo_locate_refset
+alone over the runs of the find.  Median of REPEATS behind a warm-up for each; the seconds of the three, the table's bytes and both
+sets' build seconds, the sum of n_tested and a CRC of the loci (it compares two builds; the host form's CRC, made once outside the
+timed regions, stands next to it).  LOOP, SUMMARY, DEV, WIDE and BEST do not apply.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -56,6 +62,7 @@ DEV, REFS_PER_SLAB, DEV_CAPACITY = (int(os.environ.get(n, d)) for n, d in (("DEV
 WIDE, WIDE_REFS, WIDE_BP = (int(os.environ.get(n, d)) for n, d in (("WIDE", 0), ("WIDE_REFS", 300), ("WIDE_BP", 50_000)))
 BEST = int(os.environ.get("BEST", 0))
 PREFILTER = int(os.environ.get("PREFILTER", 0))
+LOCATE = int(os.environ.get("LOCATE", 0))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -224,6 +231,51 @@ def screened_dev_leg():
     out["host_over_screened"] = round(out["host_prefilter"]["call_s"] / out["screened_dev"]["call_s"], 2)
     print(json.dumps(out))
 
+
+def locate_leg():
+    """find, find + locate and locate alone on a set with the position table; its build next to the set without"""
+    out = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+           "prefilter": bool(PREFILTER)}
+    sets = {}
+    for label, pos in (("plain", False), ("positions", True)):
+        a = time.perf_counter()
+        s = refset.RefSet.build(refs, opts, prefilter=bool(PREFILTER), positions=pos)
+        b = time.perf_counter()
+        s.to_device()
+        torch.cuda.synchronize()
+        c = time.perf_counter()
+        out[label] = {"build_s": round(b - a, 4), "to_device_s": round(c - b, 4), "positions_bytes": s.positions_bytes(),
+                      "prefilter_bytes": s.prefilter_bytes()}
+        sets[label] = s
+    s = sets["positions"]
+
+    def timed(fn):
+        got = fn()  # warm-up: code objects, the call's buffers
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return statistics.median(ts), [round(t, 5) for t in ts], got
+    find_s, find_all, runs = timed(lambda: refset.find_refset(contigs, s, fopts, strands=3))
+    both_s, both_all, (runs2, loci2) = timed(lambda: refset.find_refset(contigs, s, fopts, strands=3, locate=True))
+    loc_s, loc_all, loci = timed(lambda: refset.locate_refset(contigs, s, runs))
+    host = refset.locate_refset(contigs, s, runs, host=True)
+    plain_runs = refset.find_refset(contigs, sets["plain"], fopts, strands=3)
+    out.update({"find_refset_s": round(find_s, 5), "find_refset_s_all": find_all, "find_plus_locate_s": round(both_s, 5),
+                "find_plus_locate_s_all": both_all, "locate_refset_s": round(loc_s, 5), "locate_refset_s_all": loc_all,
+                "locate_over_find": round(loc_s / find_s, 4), "runs": int(len(runs)), "runs_crc32": zlib.crc32(runs.tobytes()),
+                "runs_equal_plain_set": runs.tobytes() == plain_runs.tobytes() == runs2.tobytes(),
+                "table_build_s": round(out["positions"]["build_s"] - out["plain"]["build_s"], 4),
+                "n_tested_sum": int(loci["n_tested"].astype(np.int64).sum()), "with_anchor": int((loci["q_first"] != refset.LOCUS_NONE).sum()),
+                "loci_crc32": zlib.crc32(loci.tobytes()), "host_loci_crc32": zlib.crc32(host.tobytes()),
+                "loci_equal_host": loci.tobytes() == host.tobytes() == loci2.tobytes(), "prefilter_counters": refset.last_prefilter()})
+    print(json.dumps(out))
+
+
+if LOCATE:
+    locate_leg()
+    sys.exit(0)
 
 if PREFILTER and DEV:
     screened_dev_leg()
