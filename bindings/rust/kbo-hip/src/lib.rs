@@ -223,6 +223,18 @@ pub mod ffi {
                                      stream: *mut c_void) -> c_int;
         pub fn kbo_locate_refset_host(set: *const KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, runs: *const u32,
                                       n_runs: u64, loci_out: *mut super::RefLocus) -> c_int;
+        // the cover of a reference: depth and breadth of every reference over the runs; covers: one RefCover per reference, depth (or
+        // null): the profile of kbo_refset_cover_bases u32, laid out by kbo_refset_cover_offsets
+        pub fn kbo_refset_cover_bases(set: *const KboRefset) -> u64;
+        pub fn kbo_refset_cover_offsets(set: *const KboRefset, out: *mut u64) -> c_int;
+        pub fn kbo_cover_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, runs: *const u32, n_runs: u64,
+                                covers_out: *mut super::RefCover, depth_out: *mut u32) -> c_int;
+        pub fn kbo_cover_refset_host(set: *const KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, runs: *const u32,
+                                     n_runs: u64, covers_out: *mut super::RefCover, depth_out: *mut u32) -> c_int;
+        pub fn kbo_cover_refset_dev_work_bytes(set: *const KboRefset) -> usize;
+        pub fn kbo_cover_refset_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                    d_runs: *const u32, d_n_runs: *const u64, capacity: usize, d_covers: *mut super::RefCover,
+                                    d_depth: *mut u32, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -373,6 +385,27 @@ pub struct RefLocus {
     pub ref_last: u32,
     pub flags: u32,
     pub n_tested: u32,
+}
+
+/// `KBO_COVER_NO_ENTRIES` / `KBO_COVER_OVERFLOW`: bits 0 and 1 of `RefCover::flags`.
+pub const COVER_NO_ENTRIES: u32 = 1;
+pub const COVER_OVERFLOW: u32 = 2;
+
+/// `kbo_ref_cover` (48 bytes), one per reference of the set: how much of the reference the runs' anchors cover (`covered` bases in
+/// `n_segments` pieces between `first` and `last`, `LOCUS_NONE` without one), how deep (`max_depth`), from how many runs and anchors.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefCover {
+    pub ref_len: u32,
+    pub covered: u32,
+    pub n_segments: u32,
+    pub first: u32,
+    pub last: u32,
+    pub max_depth: u32,
+    pub n_runs: u32,
+    pub flags: u32,
+    pub n_anchors: u64,
+    pub n_multi: u64,
 }
 
 /// `kbo_refset_candidates` over a set built with a prefilter: `out[(r * n_seqs + s) * 2 + strand - 1]` says whether sequence `s` on

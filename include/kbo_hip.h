@@ -800,6 +800,71 @@ int kbo_locate_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint
                           const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_locus *d_loci, void *stream);
 int kbo_locate_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
                            uint64_t n_runs, kbo_ref_locus *loci_out);
+/* The COVER of a reference: how much of reference r the whole batch covers, how deep and in how many pieces - the one reduction
+ * along REFERENCE coordinates; every other record is keyed by a query sequence.  The set is built with positions = 1.  Reference r
+ * HAS ENTRIES when it is of a packed route (LDS or wide) and its status is 0; anchors and usable records are those of "The LOCUS of a
+ * run" above.  For a reference with entries of L_r bases (kbo_refset_ref_len):
+ *   H_r[p], 0 <= p < L_r: the number of (record, anchor) pairs with the record one of the usable records given to the call with
+ *     ref == r and the entry of the anchor's k-mer holding position p (its low 30 bits; FWD and REV alike: both say that
+ *     ref[p, p + k) is matched).  A record given twice counts twice.  A MULTI k-mer counts at its one stored occurrence (FWD before
+ *     REV, then the smallest p) and nowhere else: an exact repeat of k or more bases inside a reference leaves its second copy
+ *     uncovered - n_multi says how many anchors that concerns.  Marking every occurrence needs an occurrence list that the set does
+ *     not keep; it is out of scope.
+ *   D_r[j] = sum of H_r[p] over max(0, j - k + 1) <= p <= j, 0 <= j < L_r: the DEPTH at base j.
+ * kbo_ref_cover holds, per reference, index = reference: ref_len = L_r as given (set for every reference); covered = the number of j
+ * with D[j] > 0; n_segments = the maximal intervals of such j; first / last = the smallest / largest such j (KBO_LOCUS_NONE when
+ * covered == 0); max_depth = the largest D[j]; n_runs = the usable records with ref == r; n_anchors = the sum of H; n_multi = the
+ * anchors among them whose entry has MULTI.  flags bit 0 (KBO_COVER_NO_ENTRIES): the reference has no entries (the single-index
+ * route, or a status) - every field but ref_len is 0 and first / last are KBO_LOCUS_NONE.  Bit 1 (KBO_COVER_OVERFLOW): n_anchors >=
+ * 2^32; H and D are 32-bit, so every field but ref_len, n_runs, n_anchors and n_multi is unspecified.  With bit 1 clear the sum of D
+ * is k * n_anchors, covered <= ref_len, and covered == 0 exactly when n_anchors == 0.
+ * The DEPTH PROFILE (optional) is D_r as uint32_t for every reference with entries, concatenated in reference order:
+ * kbo_refset_cover_offsets copies the N + 1 offsets (made at build time; a reference without entries owns no element; KBO_E_BAD_ARG
+ * for a set without positions), kbo_refset_cover_bases is their last, B (0 without positions).  kbo_refset_to_device uploads the
+ * offsets as a small allocation of their own; kbo_refset_positions_bytes does not count them.
+ *
+ * kbo_cover_refset: batch and runs as for kbo_locate_refset; covers_out receives N records, depth_out (or NULL) B words.  It uploads
+ * the batch and the runs, clears its scratch, launches three kernels (kbo_amd/csrc/refset_cover_kernels.hip: count - a wave per run,
+ * every window looked up, an integer atomic add per anchor; scan - a prefix sum per reference; reduce - D, the record, the profile)
+ * and downloads the records, and the profile when asked: one synchronisation.  The result does not depend on the order of the runs.
+ * Errors, all before the first HIP call and in this order: KBO_E_BAD_ARG for null arguments (runs may be NULL when n_runs == 0,
+ * depth_out always) and for a set without positions; the offsets as kbo_find_refset checks them; KBO_E_BAD_ARG for a record that
+ * bit 4 of a locus describes.  n_runs == 0 succeeds and touches no device: records with ref_len, bit 0 where due and zeros, and a
+ * profile of zeros.
+ * kbo_cover_refset_host is the same call restated on the CPU (no device; a test hook and a yardstick): byte-identical records and
+ * profile.
+ * kbo_cover_refset_dev: kbo_locate_refset_dev's contract for the batch and for d_runs / d_n_runs, so it composes on one stream
+ * behind kbo_find_refset_dev and kbo_find_refset_screened_dev with nothing read back.  It reads min(*d_n_runs, capacity) records
+ * (d_runs may be NULL when capacity == 0) and checks every one itself as the locate kernel does; an unusable record is skipped: it
+ * contributes nothing and cannot fault.  It writes N records to d_covers (4-byte aligned) and, when d_depth is given (4-byte
+ * aligned), B words there; nothing outside them and d_work[0, work_bytes).  No synchronisation, no allocation, no scratch memory.
+ * d_work: 16-byte aligned, work_bytes at least kbo_cover_refset_dev_work_bytes(set) - 24 bytes a reference for the counters and 4
+ * bytes a base of B for H, each part rounded up to 16; it does not depend on the batch and is 0 for a set the call refuses.
+ * KBO_E_BAD_ARG before anything is enqueued for null or misaligned pointers, a set without positions, a short d_work and a set
+ * without a copy on the current device; KBO_E_EMPTY_QUERY for n_seqs == 0. */
+#define KBO_COVER_NO_ENTRIES 1u
+#define KBO_COVER_OVERFLOW 2u
+typedef struct {
+    uint32_t ref_len;     /* L_r as given */
+    uint32_t covered;     /* bases with D > 0 */
+    uint32_t n_segments;  /* maximal intervals of them */
+    uint32_t first, last; /* the smallest and the largest covered base; KBO_LOCUS_NONE without one */
+    uint32_t max_depth;
+    uint32_t n_runs;      /* usable records of this reference */
+    uint32_t flags;       /* KBO_COVER_NO_ENTRIES, KBO_COVER_OVERFLOW */
+    uint64_t n_anchors;   /* the sum of H */
+    uint64_t n_multi;     /* the anchors among them whose entry has MULTI */
+} kbo_ref_cover; /* 48 bytes, one per reference of the set, index = reference */
+uint64_t kbo_refset_cover_bases(const kbo_refset_t *set);
+int kbo_refset_cover_offsets(const kbo_refset_t *set, uint64_t *out /* N + 1 */);
+int kbo_cover_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                     uint64_t n_runs, kbo_ref_cover *covers_out, uint32_t *depth_out);
+int kbo_cover_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                          uint64_t n_runs, kbo_ref_cover *covers_out, uint32_t *depth_out);
+size_t kbo_cover_refset_dev_work_bytes(const kbo_refset_t *set);
+int kbo_cover_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                         const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_cover *d_covers, uint32_t *d_depth,
+                         void *d_work, size_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

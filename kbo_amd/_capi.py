@@ -48,6 +48,12 @@ class RefLocus(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("q_first", "ref_first", "q_last", "ref_last", "flags", "n_tested")]
 
 
+class RefCover(C.Structure):
+    """kbo_hip.h kbo_ref_cover"""
+    _fields_ = [(n, C.c_uint32) for n in ("ref_len", "covered", "n_segments", "first", "last", "max_depth", "n_runs", "flags")] + [
+        ("n_anchors", C.c_uint64), ("n_multi", C.c_uint64)]
+
+
 class MapOpts(C.Structure):
     """kbo::MapOpts (lib.rs:412-466)."""
     _fields_ = [("max_error_prob", C.c_double), ("fill_gaps", C.c_int32), ("call_variants", C.c_int32),
@@ -139,6 +145,8 @@ SYMBOLS = [
     "kbo_best_refset_screened_dev_work_bytes", "kbo_best_refset_screened_dev",
     "kbo_refset_has_positions", "kbo_refset_positions_bytes", "kbo_refset_positions", "kbo_refset_ref_len",
     "kbo_locate_refset", "kbo_locate_refset_dev", "kbo_locate_refset_host",
+    "kbo_refset_cover_bases", "kbo_refset_cover_offsets", "kbo_cover_refset", "kbo_cover_refset_host",
+    "kbo_cover_refset_dev_work_bytes", "kbo_cover_refset_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -390,6 +398,12 @@ def lib():
     L.kbo_locate_refset.argtypes = [vp, vp, vp, sz, vp, u64, vp]
     L.kbo_locate_refset_host.argtypes = [vp, vp, vp, sz, vp, u64, vp]
     L.kbo_locate_refset_dev.argtypes = [vp, vp, vp, sz, u64, vp, vp, sz, vp, vp]
+    L.kbo_refset_cover_bases.argtypes = [vp]; L.kbo_refset_cover_bases.restype = u64
+    L.kbo_refset_cover_offsets.argtypes = [vp, vp]
+    L.kbo_cover_refset.argtypes = [vp, vp, vp, sz, vp, u64, vp, vp]
+    L.kbo_cover_refset_host.argtypes = [vp, vp, vp, sz, vp, u64, vp, vp]
+    L.kbo_cover_refset_dev_work_bytes.argtypes = [vp]; L.kbo_cover_refset_dev_work_bytes.restype = sz
+    L.kbo_cover_refset_dev.argtypes = [vp, vp, vp, sz, u64, vp, vp, sz, vp, vp, vp, sz, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

@@ -666,6 +666,31 @@ struct RefsetLocateArgs {
 constexpr uint32_t kRefsetLocateThreads = 256;
 hipError_t launch_refset_locate(const RefsetLocateArgs &a, hipStream_t stream); // one launch; none for capacity == 0
 
+// ---- depth and breadth of every reference over a list of runs (refset_cover_kernels.hip; the arithmetic and the layout of `work`:
+// refset_cover.hpp).  The records of d_runs are read and checked as the locate kernel does; an unusable one is skipped.  work: the
+// references' counters, then one word per base of every reference with entries, reference r's from base_off[r] on - cleared by the
+// launch; depth (or null): the profile, `bases` words laid out by base_off too
+struct RefsetCoverArgs {
+    const RefsetDesc *descs;
+    const uint4 *arena;
+    const uint32_t *positions;
+    const uint64_t *pos_off;
+    const uint64_t *base_off; // n_refs + 1
+    const uint32_t *ref_len;  // n_refs: every reference's length as given
+    const uint8_t *q;         // the '+' batch
+    const uint64_t *off;      // n_seqs + 1
+    const uint32_t *runs;     // kbo_ref_run: ten u32 a record
+    const uint64_t *n_runs;   // on the device
+    uint32_t *covers;         // kbo_ref_cover: twelve u32 a record, n_refs records
+    uint32_t *depth;
+    uint8_t *work;            // refcover::work_bytes(n_refs, bases) bytes, 16-byte aligned
+    uint64_t capacity, total, bases;
+    uint32_t n_refs, n_seqs, k;
+};
+constexpr uint32_t kRefsetCoverThreads = 256;
+// the clear and refset_cover_count_kernel, refset_cover_scan_kernel, refset_cover_reduce_kernel; for capacity == 0 the clear and the last
+hipError_t launch_refset_cover(const RefsetCoverArgs &a, hipStream_t stream);
+
 // ---- the screened device forms (refset_cand_kernels.hip; the arithmetic: refset_cand.hpp): the bitmap of the screen to the list of
 // its set bits, ONE slab of the list's longest prefix within the caps planned from it, and the record and merge stages that name a
 // pair by the list.  Everything is read on the device; stream order is the only synchronisation.

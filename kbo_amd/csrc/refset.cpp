@@ -11,10 +11,14 @@
 // walk only the marked pairs.  kbo_refset_candidates is that screen alone, kbo_refset_candidates_host its restatement on the CPU.
 // A set built with positions carries one entry per row of every packed reference (refset_locate.hpp); kbo_locate_refset turns the
 // runs of a find into anchors on the references with one kernel (refset_locate_kernels.hip), kbo_locate_refset_host on the CPU.
+// Such a set also carries one base offset per reference (refset_cover.hpp); kbo_cover_refset counts every anchor of the runs on the
+// base its entry names and reduces along each reference to its depth and breadth (refset_cover_kernels.hip), kbo_cover_refset_host
+// on the CPU.
 #include "../../include/kbo_hip_tuning.h"
 #include "capi_internal.hpp"
 #include "refset_best.hpp"
 #include "refset_cand.hpp"
+#include "refset_cover.hpp"
 #include "refset_locate.hpp"
 #include "refset_screen.hpp"
 #include "refset_step.hpp"
@@ -35,6 +39,9 @@ static_assert(kbo::refscreen::kSeedMax == KBO_REFSET_SEED_MAX && kbo::refscreen:
 static_assert(kbo::reflocate::kPosNone == KBO_POS_NONE && kbo::reflocate::kPosNone == KBO_LOCUS_NONE && kbo::reflocate::kMulti == KBO_LOCUS_MULTI &&
                   sizeof(kbo_ref_locus) == 24 && sizeof(kbo_ref_locus) == sizeof(kbo::reflocate::Locus),
               "kbo_hip.h states the position table's constants and the six words of a locus");
+static_assert(sizeof(kbo_ref_cover) == 48 && sizeof(kbo_ref_cover) == sizeof(kbo::refcover::Cover) && KBO_COVER_NO_ENTRIES == kbo::refcover::kFlagNoEntries &&
+                  KBO_COVER_OVERFLOW == kbo::refcover::kFlagOverflow,
+              "kbo_hip.h states the twelve words of a cover and its flags");
 static_assert(sizeof(kbo_refset_opts) == sizeof(size_t) + 8, "kbo_refset_opts: positions lies in what was the struct's tail padding");
 
 namespace {
@@ -50,6 +57,7 @@ struct DevSet {
     DevBuf arena, descs;
     DevBuf pre_bucket, pre_keys, pre_refs; // the seed table of a set with a prefilter
     DevBuf pos, pos_off;                   // the position table of a set with positions, and where each reference's entries begin
+    DevBuf cov;                            // ... and its base offsets (n_refs + 1 u64), then every reference's length (n_refs u32)
 };
 
 struct DeviceScope { // the calling thread on `device` until the scope ends
@@ -97,6 +105,9 @@ struct kbo_refset {
     std::vector<uint32_t> pos;
     std::vector<uint64_t> pos_off;
     std::vector<uint64_t> ref_len; // every reference's length as given
+    // the base offsets of a set built with positions (refset_cover.hpp): reference r's bases of the depth profile from cov_off[r] on,
+    // none for a reference without entries (n_refs + 1 offsets)
+    std::vector<uint64_t> cov_off;
     std::mutex mu;
     std::map<int, DevSet *> dev;
     ~kbo_refset()
@@ -156,6 +167,11 @@ DevSet *device_set(kbo_refset *set, int device)
         d->pos_off.alloc(set->pos_off.size() * sizeof(uint64_t));
         if (!set->pos.empty()) HIP_OK(hipMemcpy(d->pos.p, set->pos.data(), set->pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d->pos_off.p, set->pos_off.data(), set->pos_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        const size_t n_refs = set->descs.size();
+        std::vector<uint32_t> lens(set->ref_len.begin(), set->ref_len.end()); // (below 2^30 each: kbo_refset_build_opts)
+        d->cov.alloc((n_refs + 1) * sizeof(uint64_t) + n_refs * sizeof(uint32_t));
+        HIP_OK(hipMemcpy(d->cov.p, set->cov_off.data(), (n_refs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d->cov.as<uint8_t>() + (n_refs + 1) * sizeof(uint64_t), lens.data(), n_refs * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     set->dev[device] = d.get();
     return d.release();
@@ -532,6 +548,8 @@ void build_positions(kbo_refset *set, const uint8_t *const *seqs, const size_t *
     set->pos_off.assign(n_refs + 1, 0);
     for (size_t r = 0; r < n_refs; r++) set->pos_off[r + 1] = set->pos_off[r] + (packed_ok(set->descs[r]) ? set->descs[r].n_sets : 0u);
     set->pos.assign((size_t)set->pos_off[n_refs], lc::kPosNone);
+    set->cov_off.assign(n_refs + 1, 0);
+    for (size_t r = 0; r < n_refs; r++) set->cov_off[r + 1] = set->cov_off[r] + (packed_ok(set->descs[r]) ? lens[r] : 0u);
     std::atomic<size_t> next{0};
     std::atomic<bool> bad{false};
     auto work = [&] {
@@ -1855,11 +1873,11 @@ struct HostPos {
     uint32_t entry(uint32_t row) const { return pos_[row]; }
 };
 
-// the checks of kbo_locate_refset and its host form, all before any work; the batch's bases
-uint64_t check_locate(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
-                      uint64_t n_runs, const kbo_ref_locus *loci_out)
+// what kbo_locate_refset, kbo_cover_refset and their host forms check behind their null arguments, all before any work: the set has
+// positions, the batch, then every record; the batch's bases
+uint64_t check_positions_batch_runs(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                                    uint64_t n_runs)
 {
-    KBO_REQUIRE(set && concat && offsets && (n_runs == 0 || (runs && loci_out)), KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(set->positions, KBO_E_BAD_ARG, "the set has no positions (kbo_refset_build_opts)");
     const uint64_t total = check_refset_batch(set, concat, offsets, n_seqs);
     for (uint64_t x = 0; x < n_runs; x++) {
@@ -1872,6 +1890,13 @@ uint64_t check_locate(const kbo_refset *set, const uint8_t *concat, const uint64
                     "a run with start > end, or end beyond its sequence");
     }
     return total;
+}
+
+uint64_t check_locate(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                      uint64_t n_runs, const kbo_ref_locus *loci_out)
+{
+    KBO_REQUIRE(set && concat && offsets && (n_runs == 0 || (runs && loci_out)), KBO_E_BAD_ARG, "null argument");
+    return check_positions_batch_runs(set, concat, offsets, n_seqs, runs, n_runs);
 }
 
 kbo::RefsetLocateArgs locate_args(const kbo_refset *set, const DevSet *ds)
@@ -1986,6 +2011,180 @@ int kbo_locate_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint
         a.total = total_bases;
         a.n_seqs = (uint32_t)n_seqs;
         HIP_OK(kbo::launch_refset_locate(a, static_cast<hipStream_t>(stream)));
+    });
+}
+
+// ---- depth and breadth of every reference (refset_cover.hpp; refset_cover_kernels.hip)
+} // extern "C"
+
+namespace {
+namespace cv = kbo::refcover;
+
+struct HostWords { // refset_cover.hpp's accessors over H and the profile on the host
+    uint32_t *h_;
+    uint32_t get(uint64_t i) const { return h_[i]; }
+    void set(uint64_t i, uint32_t v) { h_[i] = v; }
+    void add(uint64_t i) { h_[i]++; }
+};
+struct HostDepth {
+    uint32_t *d_;
+    void put(uint64_t i, uint32_t v) { d_[i] = v; }
+};
+
+// the checks of kbo_cover_refset and its host form, all before any work; the batch's bases
+uint64_t check_cover(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs, uint64_t n_runs,
+                     const kbo_ref_cover *covers_out)
+{
+    KBO_REQUIRE(set && concat && offsets && covers_out && (n_runs == 0 || runs), KBO_E_BAD_ARG, "null argument");
+    return check_positions_batch_runs(set, concat, offsets, n_seqs, runs, n_runs);
+}
+
+// the call on the CPU: count, scan and reduce as refset_cover.hpp's serial forms have them
+void cover_host(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, const kbo_ref_run *runs, uint64_t n_runs,
+                kbo_ref_cover *covers_out, uint32_t *depth_out)
+{
+    const size_t n_refs = set->descs.size();
+    std::vector<uint32_t> h((size_t)set->cov_off[n_refs], 0u), ref_runs(n_refs, 0u);
+    std::vector<uint64_t> anchors(n_refs, 0), multi(n_refs, 0);
+    HostWords H{h.data()};
+    const HostSeq q{concat};
+    for (uint64_t x = 0; x < n_runs; x++) {
+        const kbo_ref_run &w = runs[x];
+        const kbo::RefsetDesc &d = set->descs[w.ref];
+        const HostForm form = host_form(set, d);
+        const HostPos pos{set->pos.data() + set->pos_off[w.ref]};
+        const uint64_t begin = offsets[w.seq], len = offsets[w.seq + 1] - begin;
+        const bool rev = w.strand == KBO_STRAND_REV;
+        cv::count_serial(
+            H, set->cov_off[w.ref], (uint32_t)set->ref_len[w.ref], w.run.start, w.run.end, set->k,
+            [&](uint32_t i) { return lc::kmer_entry(form, d.n_sets, set->k, q, begin, len, rev, pos, i); }, anchors[w.ref], multi[w.ref]);
+        ref_runs[w.ref]++;
+    }
+    HostDepth depth{depth_out};
+    for (size_t r = 0; r < n_refs; r++) {
+        const uint32_t len = (uint32_t)set->ref_len[r];
+        cv::Cover c = cv::no_entries(len);
+        if (packed_ok(set->descs[r])) {
+            cv::scan_serial(H, set->cov_off[r], len);
+            c = cv::finish(len, cv::reduce_serial(H, set->cov_off[r], len, set->k, depth_out ? &depth : nullptr, set->cov_off[r]), ref_runs[r], anchors[r],
+                           multi[r]);
+        }
+        std::memcpy(&covers_out[r], &c, sizeof c);
+    }
+}
+
+kbo::RefsetCoverArgs cover_args(const kbo_refset *set, const DevSet *ds)
+{
+    kbo::RefsetCoverArgs a{};
+    const size_t n_refs = set->descs.size();
+    a.descs = ds->descs.as<kbo::RefsetDesc>();
+    a.arena = ds->arena.as<uint4>();
+    a.positions = ds->pos.as<uint32_t>();
+    a.pos_off = ds->pos_off.as<uint64_t>();
+    a.base_off = ds->cov.as<uint64_t>();
+    a.ref_len = reinterpret_cast<const uint32_t *>(ds->cov.as<uint64_t>() + n_refs + 1);
+    a.n_refs = (uint32_t)n_refs;
+    a.bases = set->cov_off[n_refs];
+    a.k = set->k;
+    return a;
+}
+} // namespace
+
+extern "C" {
+
+uint64_t kbo_refset_cover_bases(const kbo_refset_t *set) { return set && set->positions ? set->cov_off.back() : 0; }
+
+int kbo_refset_cover_offsets(const kbo_refset_t *set, uint64_t *out)
+{
+    if (!set || !set->positions || !out) return KBO_E_BAD_ARG;
+    std::memcpy(out, set->cov_off.data(), set->cov_off.size() * sizeof(uint64_t));
+    return KBO_OK;
+}
+
+size_t kbo_cover_refset_dev_work_bytes(const kbo_refset_t *set)
+{
+    if (!set || !set->positions) return 0;
+    return (size_t)cv::work_bytes(set->descs.size(), set->cov_off.back());
+}
+
+int kbo_cover_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs,
+                          uint64_t n_runs, kbo_ref_cover *covers_out, uint32_t *depth_out)
+{
+    return guarded([&] {
+        (void)check_cover(set, concat, offsets, n_seqs, runs, n_runs, covers_out);
+        cover_host(set, concat, offsets, runs, n_runs, covers_out, depth_out);
+    });
+}
+
+int kbo_cover_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_ref_run *runs, uint64_t n_runs,
+                     kbo_ref_cover *covers_out, uint32_t *depth_out)
+{
+    return guarded([&] {
+        const uint64_t total = check_cover(set, concat, offsets, n_seqs, runs, n_runs, covers_out);
+        if (n_runs == 0) { // (no device: the records of references nothing was found on, and a profile of zeros)
+            cover_host(set, concat, offsets, runs, 0, covers_out, depth_out);
+            return;
+        }
+        DevSet *ds = device_set(set, current_device());
+        StreamScope stream;
+        const size_t n_refs = set->descs.size(), bases = (size_t)set->cov_off[n_refs], work_bytes = (size_t)cv::work_bytes(n_refs, bases);
+        DevBuf d_q((size_t)(total + 15) / 16 * 16 + 16), d_off((n_seqs + 1) * sizeof(uint64_t)), d_runs((size_t)n_runs * sizeof(kbo_ref_run)), d_n(16),
+            d_covers(n_refs * sizeof(kbo_ref_cover)), d_work(work_bytes), d_depth(depth_out ? bases * sizeof(uint32_t) + 16 : 0);
+        HIP_OK(hipMemcpyAsync(d_q.p, concat, total, hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_off.p, offsets, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_runs.p, runs, (size_t)n_runs * sizeof(kbo_ref_run), hipMemcpyHostToDevice, stream.s));
+        HIP_OK(hipMemcpyAsync(d_n.p, &n_runs, sizeof(uint64_t), hipMemcpyHostToDevice, stream.s));
+        kbo::RefsetCoverArgs a = cover_args(set, ds);
+        a.q = d_q.as<uint8_t>();
+        a.off = d_off.as<uint64_t>();
+        a.runs = d_runs.as<uint32_t>();
+        a.n_runs = d_n.as<uint64_t>();
+        a.covers = d_covers.as<uint32_t>();
+        a.depth = depth_out ? d_depth.as<uint32_t>() : nullptr;
+        a.work = d_work.as<uint8_t>();
+        a.capacity = n_runs;
+        a.total = total;
+        a.n_seqs = (uint32_t)n_seqs;
+        HIP_OK(kbo::launch_refset_cover(a, stream.s));
+        HIP_OK(hipMemcpyAsync(covers_out, d_covers.p, n_refs * sizeof(kbo_ref_cover), hipMemcpyDeviceToHost, stream.s));
+        if (depth_out && bases) HIP_OK(hipMemcpyAsync(depth_out, d_depth.p, bases * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.s));
+        HIP_OK(hipStreamSynchronize(stream.s)); // the call's one wait
+    });
+}
+
+int kbo_cover_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                         const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_cover *d_covers, uint32_t *d_depth,
+                         void *d_work, size_t work_bytes, void *stream)
+{
+    return guarded([&] {
+        KBO_REQUIRE(set && d_concat && d_offsets && d_n_runs && d_covers && d_work && (capacity == 0 || d_runs), KBO_E_BAD_ARG, "null argument");
+        KBO_REQUIRE(((uintptr_t)d_concat & 15) == 0 && ((uintptr_t)d_work & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 &&
+                        ((uintptr_t)d_n_runs & 7) == 0 && ((uintptr_t)d_runs & 3) == 0 && ((uintptr_t)d_covers & 3) == 0 && ((uintptr_t)d_depth & 3) == 0,
+                    KBO_E_BAD_ARG, "d_concat and d_work 16-byte, d_offsets and the count 8-byte, the records and d_depth 4-byte aligned");
+        KBO_REQUIRE(set->positions, KBO_E_BAD_ARG, "the set has no positions (kbo_refset_build_opts)");
+        KBO_REQUIRE(n_seqs > 0, KBO_E_EMPTY_QUERY, "empty batch");
+        KBO_REQUIRE(n_seqs < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "more than 2^32-1 sequences per call");
+        KBO_REQUIRE(work_bytes >= kbo_cover_refset_dev_work_bytes(set), KBO_E_BAD_ARG, "work_bytes below the figure of kbo_cover_refset_dev_work_bytes");
+        bool any_copy;
+        {
+            std::lock_guard<std::mutex> g(set->mu);
+            any_copy = !set->dev.empty();
+        }
+        KBO_REQUIRE(any_copy, KBO_E_BAD_ARG, "the set has no copy on any device (kbo_refset_to_device)"); // (no device is asked)
+        DevSet *ds = device_set_if_any(set, current_device());
+        KBO_REQUIRE(ds, KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
+        kbo::RefsetCoverArgs a = cover_args(set, ds);
+        a.q = d_concat;
+        a.off = d_offsets;
+        a.runs = reinterpret_cast<const uint32_t *>(d_runs);
+        a.n_runs = d_n_runs;
+        a.covers = reinterpret_cast<uint32_t *>(d_covers);
+        a.depth = d_depth;
+        a.work = static_cast<uint8_t *>(d_work);
+        a.capacity = capacity;
+        a.total = total_bases;
+        a.n_seqs = (uint32_t)n_seqs;
+        HIP_OK(kbo::launch_refset_cover(a, static_cast<hipStream_t>(stream)));
     });
 }
 

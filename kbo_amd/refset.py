@@ -38,6 +38,12 @@ LOCUS_FIRST_REV, LOCUS_LAST_REV, LOCUS_FIRST_MULTI, LOCUS_LAST_MULTI, LOCUS_UNUS
 REF_LOCUS = np.dtype([("q_first", np.uint32), ("ref_first", np.uint32), ("q_last", np.uint32), ("ref_last", np.uint32),
                       ("flags", np.uint32), ("n_tested", np.uint32)])
 
+# kbo_ref_cover (48 bytes), one per reference of the set: the bases of the reference that the anchors of the runs given cover, in how
+# many pieces, between which bases (LOCUS_NONE without one) and how deep, from how many runs and anchors
+COVER_NO_ENTRIES, COVER_OVERFLOW = 1, 2  # flags
+REF_COVER = np.dtype([("ref_len", np.uint32), ("covered", np.uint32), ("n_segments", np.uint32), ("first", np.uint32), ("last", np.uint32),
+                      ("max_depth", np.uint32), ("n_runs", np.uint32), ("flags", np.uint32), ("n_anchors", np.uint64), ("n_multi", np.uint64)])
+
 
 class RefSet:
     """kbo_refset_t: index r is what kbo::build (lib.rs:501-506) makes of reference r alone"""
@@ -163,6 +169,20 @@ class RefSet:
         """the length of reference r as it was given"""
         return int(lib().kbo_refset_ref_len(self._h, r))
 
+    def cover_bases(self):
+        """words of the depth profile: the bases of every reference with entries; 0 without positions"""
+        return int(lib().kbo_refset_cover_bases(self._h))
+
+    def cover_offsets(self):
+        """where each reference's bases lie in the depth profile: len(self) + 1 uint64 offsets, a reference without entries owns none"""
+        out = np.zeros(len(self) + 1, dtype=np.uint64)
+        check(lib().kbo_refset_cover_offsets(self._h, out.ctypes.data))
+        return out
+
+    def cover_work_bytes(self):
+        """kbo_cover_refset_dev_work_bytes: the d_work of cover_refset_dev; 0 without positions"""
+        return int(lib().kbo_cover_refset_dev_work_bytes(self._h))
+
     def form(self, r):
         """test hook: the packed form of an LDS or wide reference, as bytes in a uint8 array"""
         n = C.c_size_t()
@@ -242,6 +262,41 @@ def locate_refset_dev(concat, offsets, refset, d_runs, d_n_runs, capacity, strea
         check(lib().kbo_locate_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, d_runs.data_ptr() if capacity else None,
                                           d_n_runs.data_ptr(), capacity, loci.data_ptr() if capacity else None, s.cuda_stream))
     return loci
+
+
+def cover_refset(query_seqs, refset, runs, depth=False, host=False):
+    """kbo_cover_refset: depth and breadth of every reference of the set (built with positions=True) over the runs of find_refset
+    (REF_RUN records of the same query_seqs and set) -> a structured array of REF_COVER records, one per reference.  depth=True:
+    (covers, profile, offsets) - the depth of every base of every reference with entries as uint32, reference r's at
+    profile[offsets[r]:offsets[r + 1]].  host=True: the restatement on the CPU (kbo_cover_refset_host), byte-identical"""
+    concat, offsets, n = _batch(query_seqs)
+    runs = np.ascontiguousarray(runs, dtype=REF_RUN)
+    covers = np.zeros(len(refset), dtype=REF_COVER)
+    profile = np.zeros(refset.cover_bases(), dtype=np.uint32) if depth else None
+    f = lib().kbo_cover_refset_host if host else lib().kbo_cover_refset
+    check(f(refset._h, concat.ctypes.data, offsets.ctypes.data, n, runs.ctypes.data if len(runs) else None, len(runs), covers.ctypes.data,
+            profile.ctypes.data if depth else None))
+    return (covers, profile, refset.cover_offsets()) if depth else covers
+
+
+def cover_refset_dev(concat, offsets, refset, d_runs, d_n_runs, capacity, depth=False, stream=None):
+    """kbo_cover_refset_dev over torch tensors on the device: d_runs / d_n_runs as find_refset_dev returns them (records, count), the
+    batch by find_refset_dev's conventions -> (covers, profile): covers an (n_refs, 12) int32 tensor that holds the u32 words of
+    REF_COVER, profile an int32 tensor of RefSet.cover_bases() words with depth=True, else None.  Everything on `stream` (default: the
+    current one).  kbo_cover_refset_dev itself synchronises nothing; this wrapper, like find_refset_dev, reads offsets[-1] back once
+    for the batch's bases, which waits for the device."""
+    import torch
+    q, off, n_seqs, total, s = _dev_batch(concat, offsets, stream)
+    capacity = int(capacity)
+    with torch.cuda.device(q.device), torch.cuda.stream(s):
+        wb = refset.cover_work_bytes()
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+        covers = torch.empty((len(refset), 12), dtype=torch.int32, device=q.device)
+        profile = torch.empty(refset.cover_bases(), dtype=torch.int32, device=q.device) if depth else None
+        check(lib().kbo_cover_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, d_runs.data_ptr() if capacity else None,
+                                         d_n_runs.data_ptr(), capacity, covers.data_ptr(), profile.data_ptr() if depth else None,
+                                         work.data_ptr(), wb, s.cuda_stream))
+    return covers, profile  # (the scratch was allocated on `s`: the allocator reuses it in that stream's order)
 
 
 def locus_interval(runs, loci, k, ref_lens):

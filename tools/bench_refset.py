@@ -42,6 +42,11 @@ the second one kbo_find_refset, kbo_find_refset followed by kbo_locate_refset (f
 alone over the runs of the find.  Median of REPEATS behind a warm-up for each; the seconds of the three, the table's bytes and both
 sets' build seconds, the sum of n_tested and a CRC of the loci (it compares two builds; the host form's CRC, made once outside the
 timed regions, stands next to it).  LOOP, SUMMARY, DEV, WIDE and BEST do not apply.
+COVER=1 is a leg of its own next to LOCATE=1, on the same set with the position table, one session: kbo_find_refset, kbo_locate_refset
+and kbo_cover_refset (with and without the depth profile) over the runs of the find, median of REPEATS behind a warm-up for each; a
+CRC of the records and of the profile, the host form's next to them (made once outside the timed regions), and the sums of the
+records' fields.  For breadth alone on an assembly there is an older way with another definition - an index of the QUERY
+(kbo_index_build_device) and kbo_summary_batch with the references as the batch: its seconds stand next to the cover's, the time only.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -63,6 +68,7 @@ WIDE, WIDE_REFS, WIDE_BP = (int(os.environ.get(n, d)) for n, d in (("WIDE", 0), 
 BEST = int(os.environ.get("BEST", 0))
 PREFILTER = int(os.environ.get("PREFILTER", 0))
 LOCATE = int(os.environ.get("LOCATE", 0))
+COVER = int(os.environ.get("COVER", 0))
 K, THREADS = 31, 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
@@ -273,8 +279,61 @@ def locate_leg():
     print(json.dumps(out))
 
 
+def cover_leg():
+    """find, locate and cover over the runs of the find on a set with the position table; breadth by an index of the query next to it"""
+    out = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+           "prefilter": bool(PREFILTER)}
+    a = time.perf_counter()
+    s = refset.RefSet.build(refs, opts, prefilter=bool(PREFILTER), positions=True)
+    b = time.perf_counter()
+    s.to_device()
+    torch.cuda.synchronize()
+    out["set"] = {"build_s": round(b - a, 4), "to_device_s": round(time.perf_counter() - b, 4), "positions_bytes": s.positions_bytes(),
+                  "cover_bases": s.cover_bases(), "cover_work_bytes": s.cover_work_bytes()}
+
+    def timed(fn):
+        got = fn()  # warm-up: code objects, the call's buffers
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return statistics.median(ts), [round(t, 5) for t in ts], got
+    find_s, find_all, runs = timed(lambda: refset.find_refset(contigs, s, fopts, strands=3))
+    loc_s, loc_all, loci = timed(lambda: refset.locate_refset(contigs, s, runs))
+    cov_s, cov_all, covers = timed(lambda: refset.cover_refset(contigs, s, runs))
+    dep_s, dep_all, (covers2, depth, _) = timed(lambda: refset.cover_refset(contigs, s, runs, depth=True))
+    t = time.perf_counter()
+    host, host_depth, _ = refset.cover_refset(contigs, s, runs, depth=True, host=True)
+    host_s = time.perf_counter() - t
+
+    def by_query_index():  # another definition of breadth: the references' bases that match an index of the query
+        sbwt, _ = kbo_amd.build(contigs, kbo_amd.BuildOpts(k=K, add_revcomp=True, num_threads=THREADS), device=-1)
+        return batch.summary_batch(sbwt, refs, fopts.max_error_prob)
+    alt_s, alt_all, alt = timed(by_query_index)
+    windows = np.maximum(0, runs["end"].astype(np.int64) - runs["start"].astype(np.int64) - K + 1)
+    out.update({"find_refset_s": round(find_s, 5), "find_refset_s_all": find_all, "locate_refset_s": round(loc_s, 5), "locate_refset_s_all": loc_all,
+                "cover_refset_s": round(cov_s, 5), "cover_refset_s_all": cov_all, "cover_refset_depth_s": round(dep_s, 5),
+                "cover_refset_depth_s_all": dep_all, "cover_over_find": round(cov_s / find_s, 4), "cover_host_s": round(host_s, 4),
+                "index_of_query_plus_summary_s": round(alt_s, 5), "index_of_query_plus_summary_s_all": alt_all,
+                "index_of_query_refs_with_a_match": int((alt[:, 0] > 0).sum()),
+                "runs": int(len(runs)), "runs_crc32": zlib.crc32(runs.tobytes()), "windows": int(windows.sum()),
+                "refs_covered": int((covers["covered"] > 0).sum()), "covered_sum": int(covers["covered"].astype(np.int64).sum()),
+                "segments_sum": int(covers["n_segments"].astype(np.int64).sum()), "n_anchors_sum": int(covers["n_anchors"].sum()),
+                "n_multi_sum": int(covers["n_multi"].sum()), "max_depth": int(covers["max_depth"].max()),
+                "covers_crc32": zlib.crc32(covers.tobytes()), "host_covers_crc32": zlib.crc32(host.tobytes()),
+                "depth_crc32": zlib.crc32(depth.tobytes()), "host_depth_crc32": zlib.crc32(host_depth.tobytes()),
+                "covers_equal_host": covers.tobytes() == host.tobytes() == covers2.tobytes(), "depth_equal_host": depth.tobytes() == host_depth.tobytes(),
+                "loci_crc32": zlib.crc32(loci.tobytes()), "prefilter_counters": refset.last_prefilter()})
+    print(json.dumps(out))
+
+
 if LOCATE:
     locate_leg()
+    sys.exit(0)
+
+if COVER:
+    cover_leg()
     sys.exit(0)
 
 if PREFILTER and DEV:
