@@ -235,6 +235,15 @@ pub mod ffi {
         pub fn kbo_cover_refset_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
                                     d_runs: *const u32, d_n_runs: *const u64, capacity: usize, d_covers: *mut super::RefCover,
                                     d_depth: *mut u32, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+        // the variants of a pair: kbo::call against every reference with a hit; out: records and their characters, released by
+        // kbo_ref_calls_free.  opts.sbwt_build_opts.k is the set's k; useful calls need k of about twice the threshold or more
+        pub fn kbo_call_refset(set: *mut KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboCallOpts,
+                               strands: c_int, out: *mut super::RefCalls) -> c_int;
+        pub fn kbo_call_refset_host(set: *const KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboCallOpts,
+                                    strands: c_int, out: *mut super::RefCalls) -> c_int;
+        pub fn kbo_ref_calls_free(calls: *mut super::RefCalls);
+        pub fn kbo_refset_last_call(out: *mut u64) -> c_int;
+        pub fn kbo_refset_spell_row(set: *const KboRefset, r: usize, row: u32, out: *mut u8) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -406,6 +415,31 @@ pub struct RefCover {
     pub flags: u32,
     pub n_anchors: u64,
     pub n_multi: u64,
+}
+
+/// `kbo_ref_variant` (24 bytes): a variant of `kbo::call` between reference `ref_` and sequence `seq` on `strand` - `Variant::query_pos`
+/// on that strand, and where its characters lie in `RefCalls::chars`: `query_len` of the sequence, then `ref_len` of the reference.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefVariant {
+    pub ref_: u32,
+    pub seq: u32,
+    pub strand: u32,
+    pub pos: u32,
+    pub chars: u32,
+    pub query_len: u16,
+    pub ref_len: u16,
+}
+
+/// `kbo_ref_calls`: what `kbo_call_refset` returns - `n_variants` records ordered by (ref, seq, strand, pos) and their `n_chars`
+/// characters; both null without a variant.  `kbo_ref_calls_free` releases them.
+#[repr(C)]
+#[derive(Debug)]
+pub struct RefCalls {
+    pub n_variants: u64,
+    pub n_chars: u64,
+    pub variants: *mut RefVariant,
+    pub chars: *mut u8,
 }
 
 /// `kbo_refset_candidates` over a set built with a prefilter: `out[(r * n_seqs + s) * 2 + strand - 1]` says whether sequence `s` on

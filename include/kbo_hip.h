@@ -865,6 +865,58 @@ size_t kbo_cover_refset_dev_work_bytes(const kbo_refset_t *set);
 int kbo_cover_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
                          const kbo_ref_run *d_runs, const uint64_t *d_n_runs, size_t capacity, kbo_ref_cover *d_covers, uint32_t *d_depth,
                          void *d_work, size_t work_bytes, void *stream);
+/* The VARIANTS of a pair: what differs between reference r and its copy in sequence s - kbo::call (lib.rs:547-573) against every
+ * reference of the set that has a hit, in one call.  kbo_call_refset returns records for every (reference r, sequence s, strand) pair
+ * that kbo_summary_refset has a record for with the same set, batch, strands and max_error_prob, and for no other: a pair without a
+ * summary record contributes nothing, by definition.  (That is what makes the prefilter exact for this call: a site needs a depth of
+ * at least the threshold, the screen proves the absence of one above it, and a pair whose depths only reach the threshold has no
+ * summary record.)  The records of a pair are exactly the variants kbo_call(an index of reference r alone, sequence s, opts)
+ * returns - for KBO_STRAND_REV with the reverse complement of s as kbo_revcomp_batch makes it, in the coordinates of the reverse
+ * complement, as everywhere in this family.  The threshold is that of reference r's own n_kmers (lib.rs:620).  Field roles are the
+ * reference crate's: query_chars are characters of the walked sequence s, ref_chars those of the matched row of reference r's index,
+ * so a contig with 'A' where the gene has 'G' gives (pos, "A", "G").  An insertion in s has ref_len 0, a deletion query_len 0.
+ * Useful calls need k of about twice the threshold or more: resolve_variant (variant_calling.rs:139-201) needs a significant match
+ * on either side of the site inside one k-mer, so with thresholds of 15 - 18 (references of 300 - 20 000 bases) k = 41 and above
+ * resolve substitutions, insertions and deletions alike and k = 31 resolves little but deletions.
+ * Records are in the order (ref, seq, strand with KBO_STRAND_FWD first, pos).  `chars` of a record is the offset of its characters
+ * in kbo_ref_calls.chars: query_len characters of the sequence, then ref_len of the reference.  Without a variant n_variants is 0
+ * and both pointers are NULL.  kbo_ref_calls_free releases both arrays (malloc'ed) and clears the struct; NULL is allowed.
+ *
+ * opts->sbwt_build_opts.k must equal the set's k.  opts->sbwt_build_opts.add_revcomp applies to the index of the sequence itself
+ * (lib.rs:553), as in kbo_call_batch, and is independent of how the set was built; the other build options are not used.  NULL opts:
+ * the defaults.  The set must be kbo_refset_packed_only(); references with a status contribute nothing.
+ * Errors, all before the first HIP call and in this order: KBO_E_BAD_ARG for strands outside 1 .. 3 and for a null set or out (out
+ * is cleared from here on); KBO_E_K_MISMATCH, as kbo_call_batch; KBO_E_UNSUPPORTED for a set with a reference of the single-index
+ * route, as the device forms; then kbo_summary_refset's for max_error_prob, the thresholds and the batch, in its order and with its
+ * codes; KBO_E_UNSUPPORTED for a sequence of 2^29 bases or more (2^28 with add_revcomp), as kbo_call_batch.
+ *
+ * kbo_call_refset runs kbo_summary_refset's slabs - on a set with a prefilter over the candidate pairs alone, with the same bytes
+ * returned - and behind the walk and the counting derandomize of every slab three more kernels
+ * (kbo_amd/csrc/refset_call_kernels.hip): scan, a lane per byte of the slab's matching statistics, finds the positions i >= 1 of
+ * kept pairs with d[i] < d[i-1], d[i-1] >= t and d[i] < t (variant_calling.rs:269); match, a wave per candidate, finds the first j
+ * in i + 1 .. min(i + k + 1, len) with d[j] >= t whose interval is one row, the interval recomputed by d[j] rank steps over the
+ * packed form; spell, a lane per site, reads the row's k-mer off the packed form by k inverse steps and gathers the k depths that
+ * end at j.  Two counts, the site records and the windows come back per slab.  The host then resolves every site as kbo_call_batch
+ * resolves a site left to it (variant_calling.rs:275-284), with one suffix automaton per (sequence, strand) that has a site.
+ * kbo_call_refset_host is the same call restated on the CPU (no HIP call; a test hook and a yardstick): byte-identical records and
+ * characters.  Open: the second pass on the device with a threshold per site, a device-resident form, and references of the
+ * single-index route. */
+typedef struct {
+    uint32_t ref, seq, strand;   /* as kbo_ref_run */
+    uint32_t pos;                /* Variant::query_pos: in sequence s on that strand */
+    uint32_t chars;              /* offset into kbo_ref_calls.chars: query_len characters of the sequence, then ref_len of reference r */
+    uint16_t query_len, ref_len; /* 0 = none: an insertion has ref_len 0, a deletion query_len 0 */
+} kbo_ref_variant;               /* 24 bytes */
+typedef struct {
+    uint64_t n_variants, n_chars;
+    kbo_ref_variant *variants;
+    uint8_t *chars;
+} kbo_ref_calls;
+int kbo_call_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_call_opts *opts, int strands,
+                    kbo_ref_calls *out);
+int kbo_call_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_call_opts *opts,
+                         int strands, kbo_ref_calls *out);
+void kbo_ref_calls_free(kbo_ref_calls *calls);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

@@ -241,6 +241,15 @@ int kbo_set_refset_prefilter_max_bits(uint64_t bits);
  * (reference, sequence, strand) pairs of packed references, out[1] how many had their bit set (0 when the screen did not run),
  * out[2] how many were walked, out[3] 1 if the screen ran, else 0 (no prefilter, or the bitmap above the cap) */
 int kbo_refset_last_prefilter(uint64_t out[4]);
+/* what the calling thread's last kbo_call_refset / kbo_call_refset_host did: out[0] the (reference, sequence, strand) pairs handed to
+ * the scan (the pairs walked; the host form walks every pair of a packed reference), out[1] candidate positions i, out[2] sites -
+ * candidates with a match j -, out[3] variants.  The lists of a slab's candidates, sites and windows on the device have room for
+ * kbo_set_refset_record_capacity records at first; a slab with more candidates is scanned again with room for its count */
+int kbo_refset_last_call(uint64_t out[4]);
+/* test hook: the k characters of row `row` of reference r's index ('$' in front of a row that is no full k-mer), read off the packed
+ * form on the CPU by the inverse steps refset_call_kernels.hip spells a site's row with (kbo_amd/csrc/refset_call.hpp) -> out, k
+ * bytes.  KBO_E_BAD_ARG as kbo_refset_form, and for a row that the reference does not have */
+int kbo_refset_spell_row(const kbo_refset_t *set, size_t r, uint32_t row, uint8_t *out);
 
 /* ------------------------------------------------------------------ kbo_derand_translate_seq_dev */
 /* positions of a chunk and of a group (64 chunks) of derand_seq_kernels.hip; neither spans two sequences.  A sequence of more than

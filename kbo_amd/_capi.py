@@ -77,6 +77,11 @@ class CallFlat(C.Structure):
                 ("query_len", C.POINTER(C.c_uint16)), ("ref_len", C.POINTER(C.c_uint16)), ("chars", C.POINTER(C.c_uint8))]
 
 
+class RefCalls(C.Structure):
+    """kbo_ref_calls (kbo_hip.h): the variants of kbo_call_refset, records of 24 bytes and their characters"""
+    _fields_ = [("n_variants", C.c_uint64), ("n_chars", C.c_uint64), ("variants", C.c_void_p), ("chars", C.c_void_p)]
+
+
 OPT_INHERIT = -2147483648
 
 
@@ -146,7 +151,7 @@ SYMBOLS = [
     "kbo_refset_has_positions", "kbo_refset_positions_bytes", "kbo_refset_positions", "kbo_refset_ref_len",
     "kbo_locate_refset", "kbo_locate_refset_dev", "kbo_locate_refset_host",
     "kbo_refset_cover_bases", "kbo_refset_cover_offsets", "kbo_cover_refset", "kbo_cover_refset_host",
-    "kbo_cover_refset_dev_work_bytes", "kbo_cover_refset_dev",
+    "kbo_cover_refset_dev_work_bytes", "kbo_cover_refset_dev", "kbo_call_refset", "kbo_call_refset_host", "kbo_ref_calls_free",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -159,6 +164,7 @@ TUNING_SYMBOLS = [
     "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
     "kbo_refset_last_wide", "kbo_refset_form", "kbo_refset_ms_host", "kbo_refset_last_best",
     "kbo_refset_candidates_host", "kbo_set_refset_prefilter_max_bits", "kbo_refset_last_prefilter",
+    "kbo_refset_last_call", "kbo_refset_spell_row",
 ]
 
 _lib = None
@@ -404,6 +410,11 @@ def lib():
     L.kbo_cover_refset_host.argtypes = [vp, vp, vp, sz, vp, u64, vp, vp]
     L.kbo_cover_refset_dev_work_bytes.argtypes = [vp]; L.kbo_cover_refset_dev_work_bytes.restype = sz
     L.kbo_cover_refset_dev.argtypes = [vp, vp, vp, sz, u64, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.kbo_call_refset.argtypes = [vp, vp, vp, sz, C.POINTER(CallOpts), C.c_int, C.POINTER(RefCalls)]
+    L.kbo_call_refset_host.argtypes = [vp, vp, vp, sz, C.POINTER(CallOpts), C.c_int, C.POINTER(RefCalls)]
+    L.kbo_ref_calls_free.argtypes = [C.POINTER(RefCalls)]; L.kbo_ref_calls_free.restype = None
+    L.kbo_refset_last_call.argtypes = [vp]
+    L.kbo_refset_spell_row.argtypes = [vp, sz, C.c_uint32, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     _lib = L
     return L

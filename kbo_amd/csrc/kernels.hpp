@@ -691,6 +691,31 @@ constexpr uint32_t kRefsetCoverThreads = 256;
 // the clear and refset_cover_count_kernel, refset_cover_scan_kernel, refset_cover_reduce_kernel; for capacity == 0 the clear and the last
 hipError_t launch_refset_cover(const RefsetCoverArgs &a, hipStream_t stream);
 
+// ---- the first pass of kbo::call over a slab of pairs (refset_call_kernels.hip; the arithmetic: refset_call.hpp), behind the walk and
+// launch_derand_summary_seq of the slab: the candidates of the kept pairs, their sites {pair, i, j, row} and a window record per site
+// (refcall::window_stride(k) bytes: the k depths that end at j, then at refcall::window_pad(k) the k characters of the row)
+struct RefsetCallArgs {
+    const RefsetDesc *descs;
+    const uint4 *arena;
+    const uint8_t *q;     // the walk's query buffer
+    const uint8_t *ms;    // the slab's matching statistics, `bytes` of them
+    const uint64_t *poff; // n_pairs + 1: the pairs' first bytes
+    const uint32_t *pthr; // n_pairs: the pairs' thresholds
+    const uint32_t *ext;  // n_pairs extents, six u32 each (launch_derand_summary_seq): a pair with n_runs == 0 is not scanned
+    const uint32_t *pref; // n_pairs: the pairs' references
+    const uint32_t *pq;   // n_pairs: the first base of the pair's sequence on its strand in q
+    uint32_t *counts;     // kRefsetCallCountBytes: [0] candidates, [16] sites; zeroed by the launch
+    uint2 *cands;         // cap records {pair, i}
+    uint4 *sites;         // cap records {pair, i, j, row}, in no order
+    uint8_t *win;         // cap window records, same index as sites
+    uint64_t bytes;
+    uint32_t n_pairs, k, min_thr, cap; // min_thr: no pair's threshold is below it
+};
+constexpr uint32_t kRefsetCallThreads = 256;
+constexpr size_t kRefsetCallCountBytes = 128;
+// a clear of the counts and three launches.  counts[0] > cap afterwards: candidates were dropped, repeat with cap >= counts[0]
+hipError_t launch_refset_call(const RefsetCallArgs &a, hipStream_t stream);
+
 // ---- the screened device forms (refset_cand_kernels.hip; the arithmetic: refset_cand.hpp): the bitmap of the screen to the list of
 // its set bits, ONE slab of the list's longest prefix within the caps planned from it, and the record and merge stages that name a
 // pair by the list.  Everything is read on the device; stream order is the only synchronisation.

@@ -44,6 +44,12 @@ COVER_NO_ENTRIES, COVER_OVERFLOW = 1, 2  # flags
 REF_COVER = np.dtype([("ref_len", np.uint32), ("covered", np.uint32), ("n_segments", np.uint32), ("first", np.uint32), ("last", np.uint32),
                       ("max_depth", np.uint32), ("n_runs", np.uint32), ("flags", np.uint32), ("n_anchors", np.uint64), ("n_multi", np.uint64)])
 
+# kbo_ref_variant (24 bytes): a variant of kbo::call between reference `ref` and sequence `seq` on `strand` - Variant::query_pos on
+# that strand of the sequence, and where its characters lie in the call's `chars`: query_len of the sequence, then ref_len of the
+# reference (an insertion in the sequence has ref_len 0, a deletion query_len 0)
+REF_VARIANT = np.dtype([("ref", np.uint32), ("seq", np.uint32), ("strand", np.uint32), ("pos", np.uint32), ("chars", np.uint32),
+                        ("query_len", np.uint16), ("ref_len", np.uint16)])
+
 
 class RefSet:
     """kbo_refset_t: index r is what kbo::build (lib.rs:501-506) makes of reference r alone"""
@@ -198,6 +204,13 @@ class RefSet:
         check(lib().kbo_refset_ms_host(self._h, r, q.ctypes.data, len(q), out.ctypes.data))
         return out
 
+    def spell_row(self, r, row):
+        """test hook: the k characters of row `row` of reference r's index, read off the packed form on the CPU ('$' in front of a
+        row that is no full k-mer)"""
+        out = np.zeros(self.k(), dtype=np.uint8)
+        check(lib().kbo_refset_spell_row(self._h, r, int(row), out.ctypes.data))
+        return out.tobytes()
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().kbo_refset_free(self._h)
@@ -326,6 +339,48 @@ def locus_interval(runs, loci, k, ref_lens):
     hi = np.clip(np.maximum(a, b) + 1, 0, n)
     orient = np.where(first_rev & last_rev, 2, np.where(first_rev | last_rev, 3, 1))
     return np.where(none, -1, lo), np.where(none, -1, hi), np.where(none, -1, orient)
+
+
+def call_refset(query_seqs, refset, opts=None, strands=STRAND_BOTH, host=False):
+    """kbo::call (lib.rs:547-573) of every query sequence, on the strands asked for, against every reference of the set that
+    summary_refset has a record for with it: (variants, chars) - a structured array of REF_VARIANT records ordered by (ref, seq,
+    strand, pos) and the uint8 array their `chars` offsets point into (variant_chars slices it).  query characters are the
+    sequence's, ref characters the reference's; '-' positions are those of the reverse-complemented sequence.  opts: CallOpts whose
+    sbwt_build_opts.k is the set's k (None: the defaults with that k); its add_revcomp is the sequence's own index's, as in
+    call_batch.  The set is packed_only().  Useful calls need k of about twice the threshold or more.
+    host=True: the restatement on the CPU (kbo_call_refset_host), byte-identical"""
+    from . import BuildOpts, CallOpts
+    o = opts if opts is not None else CallOpts(sbwt_build_opts=BuildOpts(k=refset.k(), build_select=True))
+    co = _capi.CallOpts(o.max_error_prob, o.sbwt_build_opts._to_c())
+    concat, offsets, n = _batch(query_seqs)
+    res = _capi.RefCalls()
+    f = lib().kbo_call_refset_host if host else lib().kbo_call_refset
+    check(f(refset._h, concat.ctypes.data, offsets.ctypes.data, n, C.byref(co), int(strands), C.byref(res)))
+    try:
+        if res.n_variants == 0:
+            assert not res.variants and not res.chars
+            return np.zeros(0, dtype=REF_VARIANT), np.zeros(0, dtype=np.uint8)
+        buf = (C.c_uint8 * (res.n_variants * REF_VARIANT.itemsize)).from_address(res.variants)
+        variants = np.frombuffer(buf, dtype=REF_VARIANT).copy()
+        chars = np.zeros(res.n_chars, dtype=np.uint8)
+        if res.n_chars:
+            chars[:] = np.frombuffer((C.c_uint8 * res.n_chars).from_address(res.chars), dtype=np.uint8)
+        return variants, chars
+    finally:
+        lib().kbo_ref_calls_free(C.byref(res))
+
+
+def variant_chars(variant, chars):
+    """(query_chars, ref_chars) of one REF_VARIANT record as bytes"""
+    at, ql, rl = int(variant["chars"]), int(variant["query_len"]), int(variant["ref_len"])
+    return chars[at:at + ql].tobytes(), chars[at + ql:at + ql + rl].tobytes()
+
+
+def last_call():
+    """(pairs handed to the scan, candidate positions, sites with a match, variants) of the calling thread's last call_refset"""
+    out = (C.c_uint64 * 4)()
+    check(lib().kbo_refset_last_call(out))
+    return tuple(int(v) for v in out)
 
 
 def summary_refset(query_seqs, refset, max_error_prob=1e-7, strands=STRAND_BOTH):

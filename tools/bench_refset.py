@@ -47,6 +47,13 @@ and kbo_cover_refset (with and without the depth profile) over the runs of the f
 CRC of the records and of the profile, the host form's next to them (made once outside the timed regions), and the sums of the
 records' fields.  For breadth alone on an assembly there is an older way with another definition - an index of the QUERY
 (kbo_index_build_device) and kbo_summary_batch with the references as the batch: its seconds stand next to the cover's, the time only.
+CALL=1 is a leg of its own on the first workload, one session (K=63 for it: useful calls need k of about twice the threshold or more;
+PREFILTER=1 builds the set with the seed table): kbo_call_refset next to kbo_summary_refset on the same set - the floor: the same
+walk - and next to the only way there was before, one kbo_index_build + kbo_index_to_device + kbo_call_batch per reference over the
+contigs and their reverse complements, for LOOP references (LOOP=0: every reference), scaled to all of them.  Median of REPEATS
+behind a warm-up for the set's calls; the seconds, kbo_refset_last_call's counters (pairs, candidates, sites, variants), and a CRC of
+the variants of the references the loop took from both routes - the loop's filtered to the pairs with a summary record, as the call
+is defined - which must be equal.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -69,7 +76,8 @@ BEST = int(os.environ.get("BEST", 0))
 PREFILTER = int(os.environ.get("PREFILTER", 0))
 LOCATE = int(os.environ.get("LOCATE", 0))
 COVER = int(os.environ.get("COVER", 0))
-K, THREADS = 31, 16
+CALL = int(os.environ.get("CALL", 0))
+K, THREADS = int(os.environ.get("K", 31)), 16
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 rng = np.random.default_rng(2024)
 refs = [ACGT[rng.integers(0, 4, REF_BP)] for _ in range(REFS)]
@@ -327,6 +335,83 @@ def cover_leg():
                 "loci_crc32": zlib.crc32(loci.tobytes()), "prefilter_counters": refset.last_prefilter()})
     print(json.dumps(out))
 
+
+def call_leg():
+    """kbo_call_refset next to kbo_summary_refset on the same set, and next to one index + kbo_call_batch per reference"""
+    out = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+           "prefilter": bool(PREFILTER)}
+    copts = kbo_amd.CallOpts(max_error_prob=fopts.max_error_prob, sbwt_build_opts=kbo_amd.BuildOpts(k=K, build_select=True))
+    a = time.perf_counter()
+    s = refset.RefSet.build(refs, opts, prefilter=bool(PREFILTER))
+    b = time.perf_counter()
+    s.to_device()
+    torch.cuda.synchronize()
+    out["set"] = {"build_s": round(b - a, 4), "to_device_s": round(time.perf_counter() - b, 4)}
+
+    def timed(fn):
+        got = fn()  # warm-up: code objects, the call's buffers
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return statistics.median(ts), [round(t, 5) for t in ts], got
+    sum_s, sum_all, summ = timed(lambda: refset.summary_refset(contigs, s, fopts.max_error_prob, strands=3))
+    call_s, call_all, (variants, chars) = timed(lambda: refset.call_refset(contigs, s, copts, strands=3))
+    counters, pre = refset.last_call(), refset.last_prefilter()
+    # the loop: the contigs and their reverse complements as one batch of 2 x CONTIGS sequences per reference
+    comp = np.arange(256, dtype=np.uint8)
+    for x, y in zip(b"ACGT", b"TGCA"):
+        comp[x] = y
+    both = np.concatenate([concat] + [comp[c[::-1]] for c in contigs])
+    both_off = np.concatenate([offsets, offsets[1:] + offsets[-1]])
+    picks = list(range(REFS)) if LOOP <= 0 else list(range(0, REFS, max(1, REFS // LOOP)))[:LOOP]
+    kept = {(int(r), int(q), int(st)) for r, q, st in zip(summ["ref"], summ["seq"], summ["strand"])}
+
+    def one(r):
+        t0_ = time.perf_counter()
+        sbwt, _ = kbo_amd.build([refs[r]], kbo_amd.BuildOpts(k=K))
+        t1_ = time.perf_counter()
+        sbwt.to_device()
+        torch.cuda.synchronize()
+        t2_ = time.perf_counter()
+        res = batch.call_batch_arrays(sbwt, both, both_off, copts)
+        t3_ = time.perf_counter()
+        return (t1_ - t0_, t2_ - t1_, t3_ - t2_), res
+    for r in (REFS - 1, REFS - 2):
+        one(r)
+    sums, loop_recs = np.zeros(3), []
+    for r in picks:
+        t, res = one(r)
+        sums += t
+        if int(res["var_offsets"][-1]) == 0:
+            continue
+        for x in range(2 * CONTIGS):
+            key = (r, x % CONTIGS, x // CONTIGS + 1)
+            if key in kept:
+                loop_recs += [key + v for v in batch.variants_of(res, x)]
+    loop_recs.sort(key=lambda v: v[:4])
+    mine = [(int(v["ref"]), int(v["seq"]), int(v["strand"]), int(v["pos"])) + refset.variant_chars(v, chars)
+            for v in variants[np.isin(variants["ref"], picks)]]
+    crc = lambda recs: zlib.crc32(repr(recs).encode())
+    per_ref = sums / max(1, len(picks))
+    loop_all = float(per_ref.sum()) * REFS
+    out.update({"summary_refset_s": round(sum_s, 5), "summary_refset_s_all": sum_all, "summary_records": int(len(summ)),
+                "call_refset_s": round(call_s, 5), "call_refset_s_all": call_all, "call_over_summary": round(call_s / sum_s, 3),
+                "pairs_scanned": counters[0], "candidates": counters[1], "sites": counters[2], "variants": counters[3],
+                "n_chars": int(len(chars)), "prefilter_counters": pre, "variants_crc32": zlib.crc32(variants.tobytes() + chars.tobytes()),
+                "loop_refs_timed": len(picks),
+                "loop_per_ref_s": {"build": round(per_ref[0], 5), "to_device": round(per_ref[1], 5), "call_batch": round(per_ref[2], 5)},
+                "loop_scaled_s": round(loop_all, 2), "ratio_loop_over_call": round(loop_all / call_s, 1),
+                "loop_variants": len(loop_recs), "set_variants_of_loop_refs": len(mine),
+                "loop_records_crc32": crc(loop_recs), "set_records_crc32": crc(mine), "records_equal_loop": loop_recs == mine})
+    print(json.dumps(out))
+    assert loop_recs == mine, "kbo_call_refset and the loop over single indexes differ"
+
+
+if CALL:
+    call_leg()
+    sys.exit(0)
 
 if LOCATE:
     locate_leg()
