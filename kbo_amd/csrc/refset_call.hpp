@@ -1,5 +1,5 @@
 // refset_call.hpp — the first pass of kbo::call against a set of references (kbo_hip.h "The VARIANTS of a pair"), for
-// host and device alike: refset_call_kernels.hip runs it over a slab of (reference, sequence, strand) pairs, refset.cpp restates it on
+// host and device alike: refset_call_kernels.hip runs it over a slab of (reference, sequence, strand) pairs, refset_calls.cpp restates it on
 // the CPU (kbo_call_refset_host), tools/refset_call_check.cpp runs it through accessors that check every index.
 //
 // A slab holds the matching statistics of its pairs back to back: pair x owns the bytes [off(x), off(x + 1)) and has the threshold

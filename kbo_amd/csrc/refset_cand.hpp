@@ -1,5 +1,5 @@
 // refset_cand.hpp — the index arithmetic of a SCREENED reference-set slab, for host and device alike (kbo_refset_candidates_dev,
-// kbo_*_refset_screened_dev): what refset.cpp's run_slabs / SlabWalker::add_pair do pair by pair on the host over the
+// kbo_*_refset_screened_dev): what the host's run_slabs / add_pair (refset_slab.hpp) do pair by pair on the host over the
 // pairs whose bit is set, as steps that need only the bitmap, the batch's offsets and prefix sums.  refset_cand_kernels.hip runs them
 // a lane per word, pair, reference, item slot and task slot; tools/refset_cand_check.cpp runs them on the CPU next to add_pair's loop.
 //

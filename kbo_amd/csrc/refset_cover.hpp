@@ -1,6 +1,6 @@
 // refset_cover.hpp — depth and breadth of every reference of a set over a list of runs (kbo_hip.h "The COVER of a reference";
 // DESIGN.md 4.12), for host and device alike: refset_cover_kernels.hip runs it a wave per run and a wave per reference, refset.cpp
-// makes the base offsets, restates the call on the CPU (kbo_cover_refset_host) and writes the records of a call without runs,
+// makes the base offsets, refset_runs.cpp restates the call on the CPU (kbo_cover_refset_host) and writes a call without runs,
 // tools/refset_cover_check.cpp runs it through accessors that check every index.
 //
 // Three steps over one array of 32-bit words, H, that holds L_r words for every reference r with entries, reference r's from

@@ -1,6 +1,6 @@
 // refset_locate.hpp — where a run of kbo_find_refset lies on its reference (kbo_hip.h "the locus of a run"), for host
-// and device alike: refset_locate_kernels.hip runs it a wave per run, refset.cpp fills the position table with its encoding and
-// restates the call on the CPU (kbo_locate_refset_host), tools/refset_locate_check.cpp runs it through accessors that check every
+// and device alike: refset_locate_kernels.hip runs it a wave per run, refset.cpp fills the position table with its encoding,
+// refset_runs.cpp restates the call on the CPU (kbo_locate_refset_host), tools/refset_locate_check.cpp runs it through accessors that check every
 // index.
 //
 // A noisy matching statistic equals k at query position i exactly when the k-mer that ends there is a row of the reference's SBWT,

@@ -1,5 +1,5 @@
 // refset_plan.hpp — the index arithmetic of a reference-set slab, for host and device alike (kbo_find_refset_dev /
-// kbo_summary_refset_dev): what refset.cpp's SlabWalker::add_pair does pair by pair on the host, as closed forms
+// kbo_summary_refset_dev): what refset_slab.hpp's add_pair does pair by pair on the host, as closed forms
 // that need only the batch's offsets.  refset_plan_kernels.hip runs them a lane per pair and per item; tools/refset_plan_check.cpp
 // runs them on the CPU next to add_pair's loop.
 //

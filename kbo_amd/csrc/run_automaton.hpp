@@ -1,5 +1,5 @@
 // run_automaton.hpp — the reference-side walk of a call site without the index the reference builds of the sequence: what
-// call_batch.cpp (kbo_call_batch) and refset.cpp (kbo_call_refset) answer variant_calling.rs:280 with.  Host code only.
+// call_batch.cpp (kbo_call_batch) and refset_calls.cpp (kbo_call_refset) answer variant_calling.rs:280 with.  Host code only.
 #pragma once
 #include <cstddef>
 #include <cstdint>

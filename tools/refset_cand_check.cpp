@@ -1,11 +1,12 @@
 // refset_cand_check.cpp — the screened slab planner's arithmetic (kbo_amd/csrc/refset_cand.hpp) on the CPU, next to the loops it
 // replaces: the candidate list, the cut by the caps, pairs, items and tasks of the ONE slab of the screened device-resident
 // reference-set calls, built the way refset_cand_kernels.hip builds them (a step per bitmap word, pair slot, reference, item slot and
-// task slot, from the bitmap, the offsets and prefix sums) and compared with brute force and with what refset.cpp's run_slabs /
-// SlabWalker::add_pair append pair by pair over the pairs whose bit is set, restated below.  Every array is read through at(): an index
+// task slot, from the bitmap, the offsets and prefix sums) and compared with brute force and with what the host's own planner (add_pair,
+// refset_slab.hpp, in refset.cpp's run_slabs order) appends pair by pair over the pairs whose bit is set.  Every array is read through at(): an index
 // outside it ends the program.  No GPU, no library: a stand-alone program, meant to run under sanitizers.
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I kbo_amd/csrc tools/refset_cand_check.cpp -o refset_cand_check && ./refset_cand_check
 #include "refset_cand.hpp"
+#include "refset_slab.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -18,33 +19,6 @@ using kbo::refplan::chunks_of;
 using kbo::refplan::record_owner;
 
 namespace {
-
-struct HostPlan { // refset.cpp SlabPlan, the fields the device needs
-    std::vector<uint64_t> off{0};
-    std::vector<uint32_t> ref, seq, strand, items, tasks;
-};
-
-// refset.cpp SlabWalker::add_pair
-void add_pair(HostPlan &P, const std::vector<uint64_t> &offsets, uint32_t k, uint32_t chunk, uint64_t rev_base, uint32_t r, uint32_t s, uint32_t strand)
-{
-    const uint64_t len = offsets.at(s + 1) - offsets.at(s), q0 = (strand == 2 ? rev_base : 0) + offsets.at(s), o0 = P.off.back();
-    bool fresh = P.tasks.empty() || P.tasks[P.tasks.size() - 4] != r;
-    for (uint64_t c0 = 0; c0 < len; c0 += chunk) {
-        const uint64_t c1 = std::min(len, c0 + chunk), warm = std::min<uint64_t>(c0, k - 1);
-        if (fresh || P.tasks[P.tasks.size() - 2] == kTaskItems) {
-            const uint32_t t[4] = {r, (uint32_t)(P.items.size() / 4), 0u, 0u};
-            P.tasks.insert(P.tasks.end(), t, t + 4);
-            fresh = false;
-        }
-        const uint32_t it[4] = {(uint32_t)(q0 + c0 - warm), (uint32_t)(o0 + c0), (uint32_t)(c1 - c0 + warm) | (uint32_t)warm << 16, 0u};
-        P.items.insert(P.items.end(), it, it + 4);
-        P.tasks[P.tasks.size() - 2]++;
-    }
-    P.ref.push_back(r);
-    P.seq.push_back(s);
-    P.strand.push_back(strand);
-    P.off.push_back(o0 + len);
-}
 
 int g_bad = 0;
 #define CHECK(cond, ...)                                                                                                                     \
@@ -151,10 +125,10 @@ void check_call(const std::vector<uint64_t> &offsets, uint32_t n_refs, uint32_t 
     CHECK(walked_bases <= max_bases && walked <= max_pairs && cand_bases >= walked_bases, "the caps");
 
     // the host's plan over the walked pairs
-    HostPlan H;
+    kbo_host::SlabPlan H;
     for (uint32_t p = 0; p < walked; p++) {
         const PairId id = pair_of_bit(order.at(p), n_seqs);
-        add_pair(H, offsets, k, chunk, rev_off, id.ref, id.seq, id.strand);
+        kbo_host::add_pair(H, kbo_host::SlabBatch{offsets.data(), k, chunk, rev_off}, id.ref, id.seq, id.strand, 0u);
     }
 
     // rc_pairs_kernel

@@ -1,9 +1,10 @@
 // refset_plan_check.cpp — the slab planner's arithmetic (kbo_amd/csrc/refset_plan.hpp) on the CPU, next to the loop it replaces:
 // pairs, items and tasks of slabs of the device-resident reference-set calls, built the way refset_plan_kernels.hip builds them
-// (a closed form per pair and per item slot, from the offsets alone) and compared with what refset.cpp's SlabWalker::add_pair
-// appends pair by pair, restated below.  No GPU, no library: a stand-alone program, meant to run under sanitizers.
+// (a closed form per pair and per item slot, from the offsets alone) and compared with what the host's own planner (add_pair,
+// refset_slab.hpp) appends pair by pair.  No GPU, no library: a stand-alone program, meant to run under sanitizers.
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I kbo_amd/csrc tools/refset_plan_check.cpp -o refset_plan_check && ./refset_plan_check
 #include "refset_plan.hpp"
+#include "refset_slab.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -13,33 +14,6 @@
 using namespace kbo::refplan;
 
 namespace {
-
-struct HostPlan { // refset.cpp SlabPlan, the fields the device needs
-    std::vector<uint64_t> off{0};
-    std::vector<uint32_t> ref, seq, strand, items, tasks;
-};
-
-// refset.cpp SlabWalker::add_pair
-void add_pair(HostPlan &P, const std::vector<uint64_t> &offsets, uint32_t k, uint32_t chunk, uint64_t rev_base, uint32_t r, uint32_t s, uint32_t strand)
-{
-    const uint64_t len = offsets[s + 1] - offsets[s], q0 = (strand == 2 ? rev_base : 0) + offsets[s], o0 = P.off.back();
-    bool fresh = P.tasks.empty() || P.tasks[P.tasks.size() - 4] != r;
-    for (uint64_t c0 = 0; c0 < len; c0 += chunk) {
-        const uint64_t c1 = std::min(len, c0 + chunk), warm = std::min<uint64_t>(c0, k - 1);
-        if (fresh || P.tasks[P.tasks.size() - 2] == kTaskItems) {
-            const uint32_t t[4] = {r, (uint32_t)(P.items.size() / 4), 0u, 0u};
-            P.tasks.insert(P.tasks.end(), t, t + 4);
-            fresh = false;
-        }
-        const uint32_t it[4] = {(uint32_t)(q0 + c0 - warm), (uint32_t)(o0 + c0), (uint32_t)(c1 - c0 + warm) | (uint32_t)warm << 16, 0u};
-        P.items.insert(P.items.end(), it, it + 4);
-        P.tasks[P.tasks.size() - 2]++;
-    }
-    P.ref.push_back(r);
-    P.seq.push_back(s);
-    P.strand.push_back(strand);
-    P.off.push_back(o0 + len);
-}
 
 int g_bad = 0;
 #define CHECK(cond, ...)                                                                                                                     \
@@ -58,11 +32,11 @@ void check_slab(const std::vector<uint64_t> &offsets, uint32_t k, int strands, c
 {
     const uint32_t n_seqs = (uint32_t)offsets.size() - 1, refs = (uint32_t)ref_ids.size();
     const Geometry g = geometry(n_seqs, offsets.back(), strands, k);
-    HostPlan H;
+    kbo_host::SlabPlan H;
     for (uint32_t r : ref_ids)
         for (uint32_t s = 0; s < n_seqs; s++)
             for (uint32_t strand = 1; strand <= 2; strand++)
-                if (strands & strand) add_pair(H, offsets, k, g.chunk, g.rev_base, r, s, strand);
+                if (strands & strand) kbo_host::add_pair(H, kbo_host::SlabBatch{offsets.data(), k, g.chunk, g.rev_base}, r, s, strand, 0u);
 
     // the device's inputs: chunks per sequence, scanned
     std::vector<uint32_t> first(n_seqs + 1, 0);
