@@ -242,6 +242,21 @@ pub mod ffi {
         pub fn kbo_call_refset_host(set: *const KboRefset, concat: *const u8, offsets: *const u64, n_seqs: usize, opts: *const KboCallOpts,
                                     strands: c_int, out: *mut super::RefCalls) -> c_int;
         pub fn kbo_ref_calls_free(calls: *mut super::RefCalls);
+        // the device-resident forms: the same records and characters within max_variants / max_chars, the totals and what the lists
+        // of max_sites could not hold in d_stats; nothing synchronised or read back
+        pub fn kbo_call_refset_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int, max_sites: usize,
+                                              refs_per_slab: usize) -> usize;
+        pub fn kbo_call_refset_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                   opts: *const KboCallOpts, strands: c_int, d_work: *mut c_void, work_bytes: usize,
+                                   d_variants: *mut super::RefVariant, max_variants: usize, d_chars: *mut u8, max_chars: usize,
+                                   max_sites: usize, d_stats: *mut super::RefCallsStats, stream: *mut c_void) -> c_int;
+        pub fn kbo_call_refset_screened_dev_work_bytes(set: *const KboRefset, n_seqs: usize, total_bases: u64, strands: c_int,
+                                                       max_sites: usize, max_pairs: usize, max_pair_bases: u64) -> usize;
+        pub fn kbo_call_refset_screened_dev(set: *mut KboRefset, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                            opts: *const KboCallOpts, strands: c_int, d_work: *mut c_void, work_bytes: usize,
+                                            d_variants: *mut super::RefVariant, max_variants: usize, d_chars: *mut u8, max_chars: usize,
+                                            max_sites: usize, d_stats: *mut super::RefCallsStats, max_pairs: usize, max_pair_bases: u64,
+                                            d_screen_stats: *mut super::RefsetScreenStats, stream: *mut c_void) -> c_int;
         pub fn kbo_refset_last_call(out: *mut u64) -> c_int;
         pub fn kbo_refset_spell_row(set: *const KboRefset, r: usize, row: u32, out: *mut u8) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
@@ -440,6 +455,20 @@ pub struct RefCalls {
     pub n_chars: u64,
     pub variants: *mut RefVariant,
     pub chars: *mut u8,
+}
+
+/// `kbo_ref_calls_stats` (64 bytes, on the device): what `kbo_call_refset_dev` found - the totals, whether or not they fitted the
+/// capacities - and what its lists of `max_sites` records could not hold: the call is complete iff `max_slab_candidates` and `n_sites`
+/// are both at most `max_sites`.  `n_panics`: sites at which the reference would panic; nothing is emitted for them.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct RefCallsStats {
+    pub n_variants: u64,
+    pub n_chars: u64,
+    pub n_sites: u64,
+    pub max_slab_candidates: u64,
+    pub n_panics: u64,
+    pub reserved: [u64; 3],
 }
 
 /// `kbo_refset_candidates` over a set built with a prefilter: `out[(r * n_seqs + s) * 2 + strand - 1]` says whether sequence `s` on

@@ -899,8 +899,51 @@ int kbo_cover_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint6
  * end at j.  Two counts, the site records and the windows come back per slab.  The host then resolves every site as kbo_call_batch
  * resolves a site left to it (variant_calling.rs:275-284), with one suffix automaton per (sequence, strand) that has a site.
  * kbo_call_refset_host is the same call restated on the CPU (no HIP call; a test hook and a yardstick): byte-identical records and
- * characters.  Open: the second pass on the device with a threshold per site, a device-resident form, and references of the
- * single-index route. */
+ * characters.  Open: references of the single-index route.
+ *
+ * kbo_call_refset_dev and kbo_call_refset_screened_dev are the device-resident forms.  Everything kbo_summary_refset_dev and
+ * kbo_summary_refset_screened_dev promise holds: the inputs, alignments and 16 bytes of slack of the batch, a set that is
+ * kbo_refset_packed_only() with a copy on the current device, everything enqueued on `stream`, nothing synchronised, read back or
+ * allocated, all scratch in d_work (16-byte aligned) and nothing written behind the figure of *_work_bytes; refs_per_slab, max_pairs
+ * and max_pair_bases mean what they mean there (the screened form walks ONE slab; n_walked == n_candidates of d_screen_stats says
+ * that it held every candidate).  The call's only upload is the thresholds (and, screened, the seed lengths).  opts as in
+ * kbo_call_refset, add_revcomp included.
+ * Records: byte for byte the kbo_ref_variant records and characters of kbo_call_refset for the same set, batch, options and strands,
+ * in its order; the screened form returns those of the walked pairs.  Record x is written iff x < max_variants, its characters iff
+ * chars + query_len + ref_len <= max_chars; d_stats->n_variants and n_chars are the full totals, and nothing at or behind either
+ * capacity is touched (d_variants may be NULL when max_variants == 0, d_chars when max_chars == 0).  d_variants is 4-byte, d_stats
+ * 8-byte aligned.
+ * max_sites bounds three lists in d_work: a slab's candidates, a slab's sites, and the sites of the whole call.  The host form enlarges
+ * its lists and repeats a slab; the device form cannot, so it counts what it could not store: the call is COMPLETE iff
+ * max_slab_candidates <= max_sites and n_sites <= max_sites.  The records of the stored sites are exact either way.
+ * A site at which the reference would panic (resolve_variant: common suffix 0, a slice beyond the k-mer) makes kbo_call_refset fail
+ * with KBO_E_REF_PANIC; the device forms count it in n_panics and emit nothing for it.  Sequences of fewer than 3 bases contribute
+ * nothing.  Limits: those of the device forms (strands x bases below 2^32 - 16; 2^31 bases screened) and max_sites <= 2^23; the host
+ * form's 2^29 bases a sequence do not apply, and a sequence may be as long as the batch.
+ * The second pass (kbo_amd/csrc/refset_resolve_kernels.hip; the arithmetic: refset_resolve.hpp) runs behind the last slab: ONE
+ * index of the '+' strand of the batch - a word { q-mer code, start } per base whose q-mer, q = min(12, the smallest threshold), lies
+ * inside a run of at least k bases, every other base a word with a code that no q-mer has, radix-sorted by code in four passes, in
+ * time linear in the batch whatever repeats it holds - then a wave per
+ * site that probes it for the depths of the row's k-mer (forwards, as reverse complements, or both: the site's strand and
+ * add_revcomp), the resolve word, a radix sort of the sites' keys (ref, seq, strand, pos), two scans and one write.  d_work holds
+ * 16 bytes a base for the index and its sort, 1/4 byte a base for the sort's histograms, 4 k + 100 bytes (k rounded up to 16) a
+ * site of max_sites and 12 bytes a pair of a slab, behind what the best form holds; the figure is never below the summary form's.
+ * Launches, whatever the batch holds: per slab the summary form's without its compaction and record append, + 1 (the pairs' words) +
+ * 3 and a clear (the first pass) + 1 (the append); per call 25 + 4 P behind the last slab, P = ceil(bits(total_bases + 1) / 8) +
+ * ceil((bits(N) + bits(n_seqs) + 1) / 8) the passes over the sites' keys (bits(v): the bits that hold 0 .. v - 1), and the clear of
+ * d_stats.
+ * Errors, all before anything is enqueued and in this order: those of kbo_summary_refset_dev / _screened_dev for the same arguments
+ * (d_stats null or misaligned among them); KBO_E_K_MISMATCH; KBO_E_BAD_ARG for max_sites == 0, KBO_E_UNSUPPORTED for max_sites above
+ * 2^23; then a short work_bytes and a set without a copy on the current device, as there.  *_work_bytes are exact, grow with
+ * max_sites and refs_per_slab (max_pairs, max_pair_bases), are at least the summary form's, and are 0 for arguments the call refuses. */
+typedef struct {
+    uint64_t n_variants, n_chars; /* what there is, those beyond the capacities included */
+    uint64_t n_sites;             /* sites found in the whole call, those beyond max_sites included; the sites of candidates that a
+                                     slab could not store are never found, so not counted: max_slab_candidates says that there are such */
+    uint64_t max_slab_candidates; /* the most candidates one slab had */
+    uint64_t n_panics;            /* sites at which the reference panics */
+    uint64_t reserved[3];
+} kbo_ref_calls_stats;            /* 64 bytes, on the device */
 typedef struct {
     uint32_t ref, seq, strand;   /* as kbo_ref_run */
     uint32_t pos;                /* Variant::query_pos: in sequence s on that strand */
@@ -917,6 +960,17 @@ int kbo_call_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
 int kbo_call_refset_host(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_call_opts *opts,
                          int strands, kbo_ref_calls *out);
 void kbo_ref_calls_free(kbo_ref_calls *calls);
+size_t kbo_call_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_sites,
+                                      size_t refs_per_slab);
+int kbo_call_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        const kbo_call_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_variant *d_variants, size_t max_variants,
+                        uint8_t *d_chars, size_t max_chars, size_t max_sites, kbo_ref_calls_stats *d_stats, void *stream);
+size_t kbo_call_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_sites,
+                                               size_t max_pairs, uint64_t max_pair_bases);
+int kbo_call_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 const kbo_call_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_variant *d_variants,
+                                 size_t max_variants, uint8_t *d_chars, size_t max_chars, size_t max_sites, kbo_ref_calls_stats *d_stats,
+                                 size_t max_pairs, uint64_t max_pair_bases, kbo_refset_screen_stats *d_screen_stats, void *stream);
 
 /* ------------------------------------------------------------------ device-resident path
  * Everything already in the HBM of the current device; kernels are enqueued on `stream`

@@ -250,6 +250,29 @@ int kbo_refset_last_call(uint64_t out[4]);
  * form on the CPU by the inverse steps refset_call_kernels.hip spells a site's row with (kbo_amd/csrc/refset_call.hpp) -> out, k
  * bytes.  KBO_E_BAD_ARG as kbo_refset_form, and for a row that the reference does not have */
 int kbo_refset_spell_row(const kbo_refset_t *set, size_t r, uint32_t row, uint8_t *out);
+/* test hooks of the second pass the device-resident calls run (kbo_amd/csrc/refset_resolve.hpp), restated on the CPU over the same
+ * arithmetic.  No HIP call; not a fallback.
+ * kbo_call_refset_host_indexed: kbo_call_refset_host's pipeline with the second pass done as the device does it - the index of the
+ * '+' batch, the probes, the three values, the resolve word, the order by keys - instead of an automaton per sequence.  Same
+ * arguments, records, errors and counters; KBO_E_REF_PANIC for a site at which the reference would panic.
+ * kbo_refset_kmer_depths_host: the depths of the k characters of `kmer` against the runs of at least k bases of seq[0, len):
+ * mode 1 forwards, 2 against their reverse complements, 3 both; out[t] is the depth at t if it is at least q (1 <= q <= 12,
+ * q <= k <= 255), else 0.
+ * kbo_refset_resolve_word_host: resolve_variant's case analysis as the device states it, next to the host's copy
+ * (resolve_variant_peaks): qpeak / rpeak 0xFF for none.  out[0] the device's word ({ q_from | q_len << 8 | r_from << 16 |
+ * r_len << 24 }, 0xFFFFFFFF no variant, 0xFFFFFFFE a panic), out[1] the host's verdict (0 no variant, 1 a variant, 2 a panic),
+ * out[2 .. 5] its q_from, q_to, r_from, r_to.  kbo_refset_resolve_words_check runs every (csl 0 .. k, qpeak, rpeak in none,
+ * 0 .. k - 2) through both: out[0] cases, out[1] cases in which they differ, out[2] panics, out[3] variants.
+ * kbo_refset_order_sites_host: the order of n sites by their keys (ref, seq, strand, i), by the radix passes the device runs over
+ * the same key words: order_out[p] is the site at place p.  KBO_E_BAD_ARG for a site outside n_refs, n_seqs, strand 1 .. 2 or
+ * i >= total_bases. */
+int kbo_call_refset_host_indexed(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                                 const kbo_call_opts *opts, int strands, kbo_ref_calls *out);
+int kbo_refset_kmer_depths_host(const uint8_t *seq, size_t len, uint32_t k, uint32_t q, int mode, const uint8_t *kmer, uint32_t *out);
+int kbo_refset_resolve_word_host(uint32_t k, uint32_t csl, uint32_t qpeak, uint32_t rpeak, uint32_t out[6]);
+int kbo_refset_resolve_words_check(uint32_t k, uint64_t out[4]);
+int kbo_refset_order_sites_host(size_t n, const uint32_t *refs, const uint32_t *seqs, const uint32_t *strands, const uint32_t *is,
+                                uint64_t n_refs, uint64_t n_seqs, uint64_t total_bases, uint32_t *order_out);
 
 /* ------------------------------------------------------------------ kbo_derand_translate_seq_dev */
 /* positions of a chunk and of a group (64 chunks) of derand_seq_kernels.hip; neither spans two sequences.  A sequence of more than

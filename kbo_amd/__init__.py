@@ -27,7 +27,7 @@ from .index import LcsArray, SbwtIndexVariant, _u8  # noqa: F401
 from .refset import RefSet, best_refset, best_refset_dev, find_refset, find_refset_dev, summary_refset, summary_refset_dev  # noqa: F401,E402
 from .refset import locate_refset, locate_refset_dev, locus_interval  # noqa: F401,E402
 from .refset import cover_refset, cover_refset_dev  # noqa: F401,E402
-from .refset import call_refset, variant_chars  # noqa: F401,E402
+from .refset import call_refset, call_refset_dev, variant_chars  # noqa: F401,E402
 
 
 @dataclass

@@ -152,6 +152,7 @@ SYMBOLS = [
     "kbo_locate_refset", "kbo_locate_refset_dev", "kbo_locate_refset_host",
     "kbo_refset_cover_bases", "kbo_refset_cover_offsets", "kbo_cover_refset", "kbo_cover_refset_host",
     "kbo_cover_refset_dev_work_bytes", "kbo_cover_refset_dev", "kbo_call_refset", "kbo_call_refset_host", "kbo_ref_calls_free",
+    "kbo_call_refset_dev_work_bytes", "kbo_call_refset_dev", "kbo_call_refset_screened_dev_work_bytes", "kbo_call_refset_screened_dev",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -164,7 +165,8 @@ TUNING_SYMBOLS = [
     "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
     "kbo_refset_last_wide", "kbo_refset_form", "kbo_refset_ms_host", "kbo_refset_last_best",
     "kbo_refset_candidates_host", "kbo_set_refset_prefilter_max_bits", "kbo_refset_last_prefilter",
-    "kbo_refset_last_call", "kbo_refset_spell_row",
+    "kbo_refset_last_call", "kbo_refset_spell_row", "kbo_call_refset_host_indexed", "kbo_refset_kmer_depths_host",
+    "kbo_refset_resolve_word_host", "kbo_refset_resolve_words_check", "kbo_refset_order_sites_host",
 ]
 
 _lib = None
@@ -413,6 +415,17 @@ def lib():
     L.kbo_call_refset.argtypes = [vp, vp, vp, sz, C.POINTER(CallOpts), C.c_int, C.POINTER(RefCalls)]
     L.kbo_call_refset_host.argtypes = [vp, vp, vp, sz, C.POINTER(CallOpts), C.c_int, C.POINTER(RefCalls)]
     L.kbo_ref_calls_free.argtypes = [C.POINTER(RefCalls)]; L.kbo_ref_calls_free.restype = None
+    L.kbo_call_refset_host_indexed.argtypes = [vp, vp, vp, sz, C.POINTER(CallOpts), C.c_int, C.POINTER(RefCalls)]
+    L.kbo_call_refset_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz]
+    L.kbo_call_refset_dev_work_bytes.restype = sz
+    L.kbo_call_refset_dev.argtypes = [vp, vp, vp, sz, u64, C.POINTER(CallOpts), C.c_int, vp, sz, vp, sz, vp, sz, sz, vp, vp]
+    L.kbo_call_refset_screened_dev_work_bytes.argtypes = [vp, sz, u64, C.c_int, sz, sz, u64]
+    L.kbo_call_refset_screened_dev_work_bytes.restype = sz
+    L.kbo_call_refset_screened_dev.argtypes = [vp, vp, vp, sz, u64, C.POINTER(CallOpts), C.c_int, vp, sz, vp, sz, vp, sz, sz, vp, sz, u64, vp, vp]
+    L.kbo_refset_kmer_depths_host.argtypes = [vp, sz, C.c_uint32, C.c_uint32, C.c_int, vp, vp]
+    L.kbo_refset_resolve_word_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.kbo_refset_resolve_words_check.argtypes = [C.c_uint32, vp]
+    L.kbo_refset_order_sites_host.argtypes = [sz, vp, vp, vp, vp, u64, u64, u64, vp]
     L.kbo_refset_last_call.argtypes = [vp]
     L.kbo_refset_spell_row.argtypes = [vp, sz, C.c_uint32, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]

@@ -755,6 +755,46 @@ hipError_t launch_refset_cand_tag_summaries(const RefsetCandArgs &a, const uint3
 // 1 launch: the extents of the walked pairs (six u32 at the pair's rank) merged into the table, a sequence's pairs found by its bits
 hipError_t launch_refset_cand_best(const RefsetCandArgs &a, const uint32_t *d_ext, uint32_t *d_table, hipStream_t stream);
 
+// ---- the second pass of kbo::call on the device (refset_resolve_kernels.hip; the arithmetic: refset_resolve.hpp), for the
+// device-resident calls kbo_call_refset_dev / kbo_call_refset_screened_dev.  Per slab: what launch_refset_call reads of a pair that
+// only the slab's plan knows, made on the device, and the slab's sites appended to the call's list.  Per call: launch_refset_resolve.
+struct RefsetSitePairs { // n_pairs words each
+    uint32_t *pref; // the pair's reference
+    uint32_t *pq;   // the first base of its sequence on its strand in the walk's query buffer
+    uint32_t *pseq; // sequence << 1 | strand - 1
+};
+// 1 launch each: the pairs of a slab of the unscreened form (launch_refset_plan_slab's), of the ONE slab of the screened form
+hipError_t launch_refset_site_pairs_plan(const RefsetPlan &a, uint32_t first_q, uint32_t n_pairs, const RefsetSitePairs &out, hipStream_t stream);
+hipError_t launch_refset_site_pairs_cand(const RefsetCandArgs &a, const RefsetSitePairs &out, hipStream_t stream);
+constexpr uint32_t kRefsetSiteTagWords = 8; // { ref, seq, strand, threshold, i, j, first base of the sequence on its strand, 0 }
+struct RefsetResolveArgs {
+    const uint8_t *concat; // the '+' batch: what the index is made of
+    const uint8_t *q;      // the walk's query buffer: the query-side k-mers
+    const uint64_t *off;   // n_seqs + 1
+    uint64_t total;
+    uint32_t n_seqs, k, qlen, add_revcomp;
+    uint32_t max_sites;
+    uint32_t *tags;        // max_sites records of kRefsetSiteTagWords words, 16-byte aligned
+    uint8_t *wins;         // max_sites window records of refcall::window_stride(k) bytes
+    uint64_t *ix[2];       // `total` words each: the index and the sort's other buffer
+    uint64_t *keys[2];     // 2 * max_sites words each: the sites' key words (hi, then lo) and the sort's other buffer
+    uint32_t *hist, *sums; // the radix passes': 256 * build_tiles(max(total, max_sites)) words, that / kScanBlock + 2 words
+    uint32_t *words;       // max_sites: the sites' resolve words
+    uint32_t *vcnt, *ccnt; // max_sites + 1 each: variants and characters in front of every place of the order ...
+    uint32_t *vsums, *csums; // ... and their block sums, (max_sites + 1) / kScanBlock + 1 each
+    uint32_t key_seq_bits, key_hi_bits, key_i_bits; // refresolve::key_shape
+    uint32_t *variants;    // kbo_ref_variant: six u32 a record
+    uint8_t *chars;
+    uint64_t max_variants, max_chars;
+    uint64_t *stats;       // kbo_ref_calls_stats: { n_variants, n_chars, n_sites, max_slab_candidates, n_panics, 0, 0, 0 }
+};
+// 1 launch behind launch_refset_call of a slab: site x of the slab becomes record stats[2] + x of the call's list when that is in
+// front of max_sites, tagged by its pair; stats[2] grows by the slab's sites, stats[3] becomes the most candidates a slab had
+hipError_t launch_refset_sites_append(const RefsetCallArgs &slab, const RefsetSitePairs &pairs, const RefsetResolveArgs &a, hipStream_t stream);
+// behind the last slab, 25 + 4 refresolve::key_passes() launches whatever the batch holds: the index (1 + 4 x 4), the sites' words
+// (1), their keys (1) and the sort (4 a pass), the counts (1), two scans (2 x 2), the records and characters (1)
+hipError_t launch_refset_resolve(const RefsetResolveArgs &a, hipStream_t stream);
+
 constexpr int kWalkThreads = 64; // default workgroup size (waves are independent: no LDS, no barriers)
 void set_walk_threads(int threads); // tuning: 64, 128 or 256
 void set_walk_experiment(int lane_limit, int dummy_lds_bytes); // experiments behind DESIGN.md section 6

@@ -76,6 +76,7 @@ template <typename Slab> KBO_ST_FN bool scan_byte(const Slab &s, uint32_t pairs,
     const uint32_t x = pair_of(s, pairs, p);
     const uint64_t begin = s.off(x);
     if (p <= begin || !s.kept(x) || !is_candidate(a, b, s.thr(x))) return false; // (i >= 1: p - 1 is the same pair's)
+    if (p >= s.off(x + 1u)) return false; // (a slab cut on the device may end in front of `bytes`: a byte behind the last pair is no pair's)
     c.pair = x;
     c.i = (uint32_t)(p - begin);
     return true;

@@ -1,9 +1,12 @@
 // refset_calls.cpp — the variants of a pair (kbo_hip.h "The VARIANTS of a pair"): kbo_call_refset runs the first
 // pass of kbo::call behind the summary's stages of every slab of refset_internal.hpp's host pipeline (refset_call.hpp;
 // refset_call_kernels.hip): the sites and their windows come back, and the host resolves them as call_batch.cpp resolves a site left
-// to it - one suffix automaton per (sequence, strand) with a site.  kbo_call_refset_host is the same pipeline on the CPU.
+// to it - one suffix automaton per (sequence, strand) with a site.  kbo_call_refset_host is the same pipeline on the CPU, and
+// kbo_call_refset_host_indexed that with the second pass as the device-resident forms run it (refset_resolve.hpp).
 #include "refset_internal.hpp"
+#include "refine.hpp"
 #include "refset_call.hpp"
+#include "refset_resolve.hpp"
 #include "run_automaton.hpp"
 
 #include <thread>
@@ -256,6 +259,183 @@ struct HostBytes {
     uint8_t *w_;
     void put(uint32_t t, uint32_t v) { w_[t] = (uint8_t)v; }
 };
+
+// the first pass on the CPU, a pair at a time (refset_call.hpp): the sites and their windows, the counters of kbo_refset_last_call
+void host_first_pass(const kbo_refset *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, int strands, const CallCheck &c, CallSites &S)
+{
+    std::fill(t_call, t_call + 4, 0);
+    const uint32_t k = set->k;
+    S.init(k);
+    std::vector<uint8_t> rev, ms;
+    for (size_t s = 0; s < n_seqs; s++) {
+        const size_t len = (size_t)(offsets[s + 1] - offsets[s]);
+        ms.resize(len);
+        for (uint32_t strand = 1; strand <= 2; strand++) {
+            if (!(strands & strand)) continue;
+            const uint8_t *q = concat + offsets[s];
+            if (strand == KBO_STRAND_REV) {
+                revcomp_host(q, len, rev);
+                q = rev.data();
+            }
+            const HostStrandSeq seq{q};
+            for (size_t r = 0; r < set->descs.size(); r++) {
+                const kbo::RefsetDesc &d = set->descs[r];
+                if (!packed_ok(d)) continue;
+                KBO_REQUIRE(kbo_refset_ms_host(set, r, q, len, ms.data()) == KBO_OK, KBO_E_BAD_ARG, "kbo_refset_ms_host");
+                t_call[0]++;
+                const uint32_t t = c.thr[r];
+                if (!rc::has_hit([&](uint64_t i) { return (uint32_t)ms[i]; }, len, k, t)) continue; // (no summary record: nothing)
+                const HostPairSlab slab{ms.data(), len, t};
+                const HostForm form = host_form(set, d);
+                for (uint64_t p = 1; p < len; p++) {
+                    rc::Cand cand{0, 0};
+                    if (!rc::scan_byte(slab, 1u, len, t, p, cand)) continue;
+                    t_call[1]++;
+                    uint32_t j = 0, row = 0;
+                    if (!rc::match_serial(slab, form, d.n_sets, seq, 0u, len, k, t, cand.i, j, row)) continue;
+                    t_call[2]++;
+                    S.sites.push_back(CallSite{(uint32_t)r, (uint32_t)s, strand, t, cand.i, j});
+                    S.wins.resize(S.wins.size() + S.stride, 0);
+                    uint8_t *w = S.wins.data() + S.wins.size() - S.stride;
+                    HostBytes depths{w}, kmer{w + S.pad};
+                    rc::gather_depths(slab, 0u, j, k, depths);
+                    rc::spell_row(form, d.n_sets, k, row, kmer);
+                }
+            }
+        }
+    }
+}
+
+// ---- the second pass as the device-resident forms run it (refset_resolve.hpp; refset_resolve_kernels.hip), on the CPU
+namespace rs = kbo::refresolve;
+struct HostWords {
+    const uint64_t *w_;
+    uint64_t word(uint64_t x) const { return w_[x]; }
+};
+struct HostKmer {
+    const uint8_t *p_;
+    uint32_t byte(uint32_t t) const { return p_[t]; }
+};
+
+// the index of a batch on its '+' strand: a word per base, sorted by code (the positions of a code ascend: the sort is stable)
+std::vector<uint64_t> batch_index(const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t k, uint32_t q)
+{
+    std::vector<uint64_t> ix((size_t)offsets[n_seqs]);
+    const HostSeq s{concat};
+    for (size_t x = 0; x < n_seqs; x++)
+        for (uint64_t p = offsets[x]; p < offsets[x + 1]; p++) ix[(size_t)p] = rs::index_word(s, offsets[x], offsets[x + 1], p, k, q);
+    std::stable_sort(ix.begin(), ix.end(), [](uint64_t a, uint64_t b) { return (a >> 32) < (b >> 32); });
+    return ix;
+}
+
+// the sites' places by their keys: LSD passes over the digits the device's radix passes read, each a stable counting sort
+std::vector<uint32_t> order_by_keys(const std::vector<CallSite> &sites, uint64_t n_refs, uint64_t n_seqs, uint64_t total)
+{
+    const rs::KeyShape shape = rs::key_shape(n_refs, n_seqs, total);
+    const size_t n = sites.size();
+    std::vector<uint64_t> hi(n), lo(n), hi2(n), lo2(n);
+    for (size_t x = 0; x < n; x++) {
+        hi[x] = rs::key_hi(shape, sites[x].ref, sites[x].seq, sites[x].strand);
+        lo[x] = rs::key_lo(sites[x].i, (uint32_t)x);
+    }
+    for (uint32_t p = 0; p < rs::key_passes(shape); p++) {
+        uint32_t a = 0, nb = 0;
+        rs::key_pass(shape, p, a, nb);
+        size_t first[257] = {0};
+        for (size_t x = 0; x < n; x++) first[rs::key_digit(hi[x], lo[x], a, nb) + 1u]++;
+        for (size_t d = 0; d < 256; d++) first[d + 1] += first[d];
+        for (size_t x = 0; x < n; x++) {
+            const size_t to = first[rs::key_digit(hi[x], lo[x], a, nb)]++;
+            hi2[to] = hi[x];
+            lo2[to] = lo[x];
+        }
+        hi.swap(hi2);
+        lo.swap(lo2);
+    }
+    std::vector<uint32_t> order(n);
+    for (size_t x = 0; x < n; x++) order[x] = (uint32_t)lo[x];
+    return order;
+}
+
+// resolve_variant_peaks on a site's three values: 0 no variant, 1 a variant (its ranges in r), 2 a panic
+uint32_t host_verdict(uint32_t k, uint32_t csl, uint32_t qpeak, uint32_t rpeak, size_t r[4])
+{
+    try {
+        return kbo::resolve_variant_peaks(k, csl, qpeak != rs::kNoPeak, qpeak, rpeak != rs::kNoPeak, rpeak, r[0], r[1], r[2], r[3]) ? 1u : 0u;
+    } catch (const kbo::RefPanic &) {
+        return 2u;
+    }
+}
+
+void resolve_sites_indexed(const CallSites &S, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, size_t n_refs, uint32_t min_thr,
+                           bool add_revcomp, kbo_ref_calls *out)
+{
+    const uint32_t k = S.k, q = rs::qmer_len(min_thr, k);
+    const size_t n = S.sites.size();
+    if (!n) return;
+    const uint64_t total = offsets[n_seqs];
+    const std::vector<uint64_t> ix = batch_index(concat, offsets, n_seqs, k, q);
+    const HostSeq plus{concat};
+    const HostWords words{ix.data()};
+    std::vector<uint8_t> minus(total), rev; // the '-' strand, a sequence at a time, where a site needs it
+    std::vector<uint8_t> have(n_seqs, 0);
+    std::vector<uint32_t> word(n), dq(k), dr(k);
+    std::vector<uint8_t> qk(k);
+    for (size_t x = 0; x < n; x++) {
+        const CallSite &w = S.sites[x];
+        const uint64_t begin = offsets[w.seq], end = offsets[w.seq + 1];
+        if (w.strand == KBO_STRAND_REV && !have[w.seq]) {
+            revcomp_host(concat + begin, (size_t)(end - begin), rev);
+            std::copy(rev.begin(), rev.end(), minus.begin() + begin);
+            have[w.seq] = 1;
+        }
+        const uint8_t *seq = (w.strand == KBO_STRAND_REV ? minus.data() : concat) + begin;
+        const uint8_t *win = S.wins.data() + x * S.stride, *rk = win + S.pad;
+        const HostKmer km{rk};
+        const uint32_t mode = rs::probe_mode(w.strand, add_revcomp);
+        uint32_t csl = 0;
+        for (uint32_t t = 0; t < k; t++) {
+            qk[t] = rs::in_front(t, w.j, k) ? (uint8_t)'$' : seq[(size_t)w.j + t - (k - 1u)];
+            dr[t] = rs::query_depth(win[t], t, w.j, k);
+            dq[t] = rs::depth_at(km, t, q, mode, plus, begin, end, words, ix.size());
+        }
+        while (csl < k && qk[k - 1u - csl] == rk[k - 1u - csl]) csl++;
+        const uint32_t qpeak = rs::rightmost_peak([&](uint32_t i) { return dr[i]; }, k, w.thr);
+        const uint32_t rpeak = rs::rightmost_peak([&](uint32_t i) { return dq[i]; }, k, w.thr);
+        word[x] = rs::resolve_word(rs::site_code(csl, qpeak, rpeak), k);
+        KBO_REQUIRE(word[x] != rs::kPanic, KBO_E_REF_PANIC, "resolve_variant panics at a site (common suffix 0, or a slice beyond the k-mer)");
+    }
+    const std::vector<uint32_t> order = order_by_keys(S.sites, n_refs, n_seqs, total);
+    uint64_t n_vars = 0, n_chars = 0;
+    for (size_t x = 0; x < n; x++)
+        if (rs::is_variant(word[x])) {
+            n_vars++;
+            n_chars += rs::word_chars(word[x]);
+        }
+    KBO_REQUIRE(n_chars < 0xFFFFFFFFull, KBO_E_UNSUPPORTED, "2^32 - 1 characters of variants or more");
+    t_call[3] = n_vars;
+    if (!n_vars) return;
+    MallocPtr<kbo_ref_variant> vars = malloc_array<kbo_ref_variant>((size_t)n_vars);
+    MallocPtr<uint8_t> bytes = malloc_array<uint8_t>((size_t)std::max<uint64_t>(n_chars, 1));
+    uint32_t at = 0;
+    size_t v = 0;
+    for (size_t p = 0; p < n; p++) {
+        const uint32_t x = order[p], wd = word[x];
+        if (!rs::is_variant(wd)) continue;
+        const CallSite &w = S.sites[x];
+        const uint32_t qf = wd & 0xFFu, ql = (wd >> 8) & 0xFFu, rf = (wd >> 16) & 0xFFu, rl = wd >> 24;
+        vars.get()[v++] = kbo_ref_variant{w.ref, w.seq, w.strand, w.i, at, (uint16_t)ql, (uint16_t)rl};
+        const uint8_t *seq = (w.strand == KBO_STRAND_REV ? minus.data() : concat) + offsets[w.seq];
+        const uint8_t *rk = S.wins.data() + (size_t)x * S.stride + S.pad;
+        for (uint32_t t = 0; t < ql; t++) bytes.get()[at + t] = rs::in_front(qf + t, w.j, k) ? (uint8_t)'$' : seq[(size_t)w.j + qf + t - (k - 1u)];
+        for (uint32_t t = 0; t < rl; t++) bytes.get()[at + ql + t] = rk[rf + t];
+        at += ql + rl;
+    }
+    out->n_variants = n_vars;
+    out->n_chars = n_chars;
+    out->variants = vars.release();
+    if (n_chars) out->chars = bytes.release();
+}
 } // namespace
 
 extern "C" {
@@ -301,49 +481,88 @@ int kbo_call_refset_host(const kbo_refset_t *set, const uint8_t *concat, const u
 {
     return guarded([&] {
         const CallCheck c = check_call(set, concat, offsets, n_seqs, opts, strands, out);
-        std::fill(t_call, t_call + 4, 0);
-        const uint32_t k = set->k;
         CallSites S;
-        S.init(k);
-        std::vector<uint8_t> rev, ms;
-        for (size_t s = 0; s < n_seqs; s++) {
-            const size_t len = (size_t)(offsets[s + 1] - offsets[s]);
-            ms.resize(len);
-            for (uint32_t strand = 1; strand <= 2; strand++) {
-                if (!(strands & strand)) continue;
-                const uint8_t *q = concat + offsets[s];
-                if (strand == KBO_STRAND_REV) {
-                    revcomp_host(q, len, rev);
-                    q = rev.data();
-                }
-                const HostStrandSeq seq{q};
-                for (size_t r = 0; r < set->descs.size(); r++) {
-                    const kbo::RefsetDesc &d = set->descs[r];
-                    if (!packed_ok(d)) continue;
-                    KBO_REQUIRE(kbo_refset_ms_host(set, r, q, len, ms.data()) == KBO_OK, KBO_E_BAD_ARG, "kbo_refset_ms_host");
-                    t_call[0]++;
-                    const uint32_t t = c.thr[r];
-                    if (!rc::has_hit([&](uint64_t i) { return (uint32_t)ms[i]; }, len, k, t)) continue; // (no summary record: nothing)
-                    const HostPairSlab slab{ms.data(), len, t};
-                    const HostForm form = host_form(set, d);
-                    for (uint64_t p = 1; p < len; p++) {
-                        rc::Cand cand{0, 0};
-                        if (!rc::scan_byte(slab, 1u, len, t, p, cand)) continue;
-                        t_call[1]++;
-                        uint32_t j = 0, row = 0;
-                        if (!rc::match_serial(slab, form, d.n_sets, seq, 0u, len, k, t, cand.i, j, row)) continue;
-                        t_call[2]++;
-                        S.sites.push_back(CallSite{(uint32_t)r, (uint32_t)s, strand, t, cand.i, j});
-                        S.wins.resize(S.wins.size() + S.stride, 0);
-                        uint8_t *w = S.wins.data() + S.wins.size() - S.stride;
-                        HostBytes depths{w}, kmer{w + S.pad};
-                        rc::gather_depths(slab, 0u, j, k, depths);
-                        rc::spell_row(form, d.n_sets, k, row, kmer);
-                    }
-                }
-            }
-        }
+        host_first_pass(set, concat, offsets, n_seqs, strands, c, S);
         resolve_sites(S, concat, offsets, c.o.sbwt_build_opts.add_revcomp != 0, call_threads(), out);
+    });
+}
+
+int kbo_call_refset_host_indexed(const kbo_refset_t *set, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                                 const kbo_call_opts *opts, int strands, kbo_ref_calls *out)
+{
+    return guarded([&] {
+        const CallCheck c = check_call(set, concat, offsets, n_seqs, opts, strands, out);
+        CallSites S;
+        host_first_pass(set, concat, offsets, n_seqs, strands, c, S);
+        uint32_t min_thr = set->k;
+        for (size_t r = 0; r < set->descs.size(); r++)
+            if (packed_ok(set->descs[r])) min_thr = std::min(min_thr, c.thr[r]);
+        resolve_sites_indexed(S, concat, offsets, n_seqs, set->descs.size(), min_thr, c.o.sbwt_build_opts.add_revcomp != 0, out);
+    });
+}
+
+int kbo_refset_kmer_depths_host(const uint8_t *seq, size_t len, uint32_t k, uint32_t q, int mode, const uint8_t *kmer, uint32_t *out)
+{
+    return guarded([&] {
+        KBO_REQUIRE(seq && kmer && out && mode >= 1 && mode <= 3 && q >= 1 && q <= rs::kQMax && q <= k && k <= 255 && len < 0xFFFFFFFFull,
+                    KBO_E_BAD_ARG, "kbo_refset_kmer_depths_host: arguments");
+        const uint64_t off[2] = {0, len};
+        const std::vector<uint64_t> ix = batch_index(seq, off, 1, k, q);
+        const HostSeq s{seq};
+        const HostWords words{ix.data()};
+        const HostKmer km{kmer};
+        for (uint32_t t = 0; t < k; t++) out[t] = rs::depth_at(km, t, q, (uint32_t)mode, s, 0u, len, words, ix.size());
+    });
+}
+
+int kbo_refset_resolve_word_host(uint32_t k, uint32_t csl, uint32_t qpeak, uint32_t rpeak, uint32_t out[6])
+{
+    if (!out || k < 2 || k > 255 || csl > k || (qpeak != rs::kNoPeak && qpeak + 2 > k) || (rpeak != rs::kNoPeak && rpeak + 2 > k)) return KBO_E_BAD_ARG;
+    out[0] = rs::resolve_word(rs::site_code(csl, qpeak, rpeak), k);
+    size_t r[4] = {0, 0, 0, 0};
+    out[1] = host_verdict(k, csl, qpeak, rpeak, r);
+    for (int x = 0; x < 4; x++) out[2 + x] = (uint32_t)r[x];
+    return KBO_OK;
+}
+
+int kbo_refset_resolve_words_check(uint32_t k, uint64_t out[4])
+{
+    if (!out || k < 2 || k > 255) return KBO_E_BAD_ARG;
+    std::fill(out, out + 4, 0);
+    auto peak = [&](uint32_t x) { return x + 1u < k ? x : rs::kNoPeak; }; // (x = k - 1: none)
+    for (uint32_t csl = 0; csl <= k; csl++)
+        for (uint32_t qx = 0; qx < k; qx++)
+            for (uint32_t rx = 0; rx < k; rx++) {
+                const uint32_t qp = peak(qx), rp = peak(rx), word = rs::resolve_word(rs::site_code(csl, qp, rp), k);
+                size_t r[4] = {0, 0, 0, 0};
+                const uint32_t verdict = host_verdict(k, csl, qp, rp, r);
+                bool same = verdict == (word == rs::kPanic ? 2u : word == rs::kNoVariant ? 0u : 1u);
+                if (same && verdict == 1u)
+                    same = (word & 0xFFu) == (r[1] > r[0] ? r[0] : 0u) && ((word >> 8) & 0xFFu) == r[1] - r[0] &&
+                           ((word >> 16) & 0xFFu) == (r[3] > r[2] ? r[2] : 0u) && (word >> 24) == r[3] - r[2];
+                out[0]++;
+                out[1] += !same;
+                out[2] += verdict == 2u;
+                out[3] += verdict == 1u;
+            }
+    return KBO_OK;
+}
+
+int kbo_refset_order_sites_host(size_t n, const uint32_t *refs, const uint32_t *seqs, const uint32_t *strands, const uint32_t *is,
+                                uint64_t n_refs, uint64_t n_seqs, uint64_t total_bases, uint32_t *order_out)
+{
+    return guarded([&] {
+        KBO_REQUIRE((n == 0 || (refs && seqs && strands && is && order_out)) && n < 0xFFFFFFFFull && n_refs >= 1 && n_refs <= 0xFFFFFFFFull &&
+                        n_seqs >= 1 && n_seqs < (1ull << 28) && total_bases < (1ull << 32),
+                    KBO_E_BAD_ARG, "kbo_refset_order_sites_host: arguments");
+        std::vector<CallSite> sites(n);
+        for (size_t x = 0; x < n; x++) {
+            KBO_REQUIRE(refs[x] < n_refs && seqs[x] < n_seqs && strands[x] >= 1 && strands[x] <= 2 && is[x] < total_bases, KBO_E_BAD_ARG,
+                        "kbo_refset_order_sites_host: a site outside the shape");
+            sites[x] = CallSite{refs[x], seqs[x], strands[x], 0u, is[x], 0u};
+        }
+        const std::vector<uint32_t> order = order_by_keys(sites, n_refs, n_seqs, total_bases);
+        std::copy(order.begin(), order.end(), order_out);
     });
 }
 

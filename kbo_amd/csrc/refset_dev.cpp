@@ -1,19 +1,21 @@
 // refset_dev.cpp — the device-resident reference-set calls (kbo_hip.h): the stages of refset.cpp's host calls
 // enqueued on the caller's stream over the caller's work buffer, nothing read back.  Two forms share their checks, the strand
 // buffer, the walk and the stages behind it:
-//   unscreened  kbo_find_refset_dev, kbo_summary_refset_dev, kbo_best_refset_dev: slabs of queryable references against the whole
-//               batch, planned on the device (refset_plan_kernels.hip)
+//   unscreened  kbo_find_refset_dev, kbo_summary_refset_dev, kbo_best_refset_dev, kbo_call_refset_dev: slabs of queryable references
+//               against the whole batch, planned on the device (refset_plan_kernels.hip)
 //   screened    kbo_refset_candidates_dev, kbo_*_refset_screened_dev: the screen kernel, and ONE slab of the candidate pairs within the
 //               caller's caps (refset_cand_kernels.hip)
 // Every *_work_bytes figure is the end of a layout below; the calls run at exactly that figure.
 #include "refset_internal.hpp"
+#include "refset_call.hpp"
 #include "refset_cand.hpp"
+#include "refset_resolve.hpp"
 #include "refset_screen.hpp"
 
 using namespace kbo_host;
 
 namespace {
-enum Kind { kSummary, kFind, kBest, kCandidatesOnly }; // (the last: the screen alone, which only the screened form has)
+enum Kind { kSummary, kFind, kBest, kCandidatesOnly, kCall }; // (kCandidatesOnly: the screen alone, which only the screened form has)
 
 // ---- what the two forms share
 // the regions of d_work a slab's walk and the stages behind it take: `pairs` sequences over `bytes` bytes to those stages
@@ -43,10 +45,45 @@ Tail tail_layout(size_t w, uint32_t k, uint64_t pairs, uint64_t bytes, uint64_t 
         if (kind == kSummary) { // (best: the extents are merged into the caller's table where they are)
             t.stage = w; w += up16(kbo::chunk_items_scratch_words((uint32_t)pairs) * sizeof(uint32_t));   // launch_refset_keep's scan
             t.local = w; w += up16((size_t)pairs * 7 * sizeof(uint32_t));                                // the kept list
+        } else if (kind == kCall) {
+            t.local = w; w += up16((size_t)pairs * 3 * sizeof(uint32_t));                                // RefsetSitePairs: three words a pair
         }
     }
     t.end = w;
     return t;
+}
+
+// ---- call: the regions behind everything else, so that no other figure moves.  A slab's candidates, sites and windows (max_sites of
+// each); the call's list of tagged sites and their windows; the index of the '+' batch and its sort's other buffer (16 bytes a
+// base), the radix passes' histograms; a resolve word, two key words twice, two counts a site
+constexpr uint64_t kCallMaxSites = 1ull << 23; // (a site has at most 510 characters, and a record's `chars` is 32 bits)
+constexpr size_t kScanValuesPerBlock = 1024;   // (values per block of launch_scan: device_util.hpp kScanBlock)
+struct CallStage {
+    size_t counts = 0, cands = 0, sites = 0, win = 0;
+    size_t tags = 0, wins = 0, ix[2] = {0, 0}, hist = 0, sums = 0, words = 0, keys[2] = {0, 0}, vcnt = 0, ccnt = 0, vsums = 0, csums = 0, end = 0;
+};
+CallStage call_stage_layout(size_t w, uint32_t k, uint64_t total, uint64_t max_sites)
+{
+    CallStage s;
+    const size_t stride = kbo::refcall::window_stride(k), tiles = kbo::build_tiles(std::max<uint64_t>(total, max_sites));
+    const size_t scan_sums = up16(((size_t)(max_sites + 1) / kScanValuesPerBlock + 1) * sizeof(uint32_t));
+    s.counts = w;  w += kbo::kRefsetCallCountBytes;
+    s.cands = w;   w += up16((size_t)max_sites * sizeof(uint2));
+    s.sites = w;   w += (size_t)max_sites * sizeof(uint4);
+    s.win = w;     w += (size_t)max_sites * stride;
+    s.tags = w;    w += (size_t)max_sites * kbo::kRefsetSiteTagWords * sizeof(uint32_t);
+    s.wins = w;    w += (size_t)max_sites * stride;
+    for (size_t &o : s.ix) { o = w; w += up16((size_t)total * sizeof(uint64_t)); }
+    s.hist = w;    w += up16(256 * tiles * sizeof(uint32_t));
+    s.sums = w;    w += up16((256 * tiles / kScanValuesPerBlock + 2) * sizeof(uint32_t));
+    s.words = w;   w += up16((size_t)max_sites * sizeof(uint32_t));
+    for (size_t &o : s.keys) { o = w; w += (size_t)max_sites * 2 * sizeof(uint64_t); }
+    s.vcnt = w;    w += up16((size_t)(max_sites + 1) * sizeof(uint32_t));
+    s.ccnt = w;    w += up16((size_t)(max_sites + 1) * sizeof(uint32_t));
+    s.vsums = w;   w += scan_sums;
+    s.csums = w;   w += scan_sums;
+    s.end = w;
+    return s;
 }
 
 // a walked slab as the stages behind the walk take it; total: the count launch_refset_keep leaves (summary)
@@ -101,7 +138,14 @@ struct DevCall {
     uint64_t max_bases = 0;
     uint32_t *d_bits = nullptr; // kCandidatesOnly: the caller's bitmap
     kbo_refset_screen_stats *d_stats = nullptr;
+    // kCall: d_out / capacity are the variants and max_variants, there is no d_n
+    uint32_t opts_k = 0, add_revcomp = 0;
+    size_t max_sites = 0, max_chars = 0;
+    uint8_t *d_chars = nullptr;
+    kbo_ref_calls_stats *d_calls = nullptr;
 };
+// what sizes a layout besides the batch: the records' capacity, or the sites of a call
+size_t layout_capacity(const DevCall &c, Kind kind) { return kind == kCall ? c.max_sites : c.capacity; }
 
 constexpr uint64_t kCandMaxPairs = (1ull << 28) - 1, kCandMaxBases = (1ull << 32) - 17; // what the ONE slab of the screened form may hold
 
@@ -109,13 +153,14 @@ constexpr uint64_t kCandMaxPairs = (1ull << 28) - 1, kCandMaxBases = (1ull << 32
 // own layout and asks for the set's copy on the current device
 std::vector<uint32_t> check_dev_call(const DevCall &c, Kind kind, bool screened)
 {
-    const bool best = kind == kBest, only = kind == kCandidatesOnly;
+    const bool best = kind == kBest, only = kind == kCandidatesOnly, call = kind == kCall;
     require_strands(c.strands);
-    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && (c.d_stats || !screened) && (only ? c.d_bits != nullptr : (c.d_n || best)) &&
-                    (only || c.d_out || (c.capacity == 0 && !best)),
+    KBO_REQUIRE(c.set && c.d_concat && c.d_offsets && c.d_work && (c.d_stats || !screened) && (only ? c.d_bits != nullptr : (c.d_n || best || call)) &&
+                    (only || c.d_out || (c.capacity == 0 && !best)) && (!call || (c.d_calls && (c.d_chars || c.max_chars == 0))),
                 KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(((uintptr_t)c.d_concat & 15) == 0 && ((uintptr_t)c.d_work & 15) == 0 && ((uintptr_t)c.d_offsets & 7) == 0 &&
-                    ((uintptr_t)c.d_n & 7) == 0 && ((uintptr_t)c.d_out & 3) == 0 && ((uintptr_t)c.d_stats & 7) == 0 && ((uintptr_t)c.d_bits & 3) == 0,
+                    ((uintptr_t)c.d_n & 7) == 0 && ((uintptr_t)c.d_out & 3) == 0 && ((uintptr_t)c.d_stats & 7) == 0 && ((uintptr_t)c.d_bits & 3) == 0 &&
+                    ((uintptr_t)c.d_calls & 7) == 0,
                 KBO_E_BAD_ARG,
                 screened ? "d_concat and d_work 16-byte, d_offsets, the count and d_stats 8-byte, the records and d_bits 4-byte aligned"
                          : "d_concat and d_work 16-byte, d_offsets and the count 8-byte, the records 4-byte aligned");
@@ -131,6 +176,11 @@ std::vector<uint32_t> check_dev_call(const DevCall &c, Kind kind, bool screened)
         KBO_REQUIRE(only || (c.max_pairs <= kCandMaxPairs && c.max_bases <= kCandMaxBases), KBO_E_UNSUPPORTED,
                     "caps beyond one slab: 2^28 pairs or more, or more than 2^32 - 17 bases (the unscreened form cuts several slabs)");
     }
+    if (call) { // (behind the device forms' checks: the call's own)
+        KBO_REQUIRE(c.opts_k == c.set->k, KBO_E_K_MISMATCH, "assert!(sbwt_ref.k() == sbwt_query.k()) (lib.rs:559)");
+        KBO_REQUIRE(c.max_sites > 0, KBO_E_BAD_ARG, "max_sites == 0");
+        KBO_REQUIRE(c.max_sites <= kCallMaxSites, KBO_E_UNSUPPORTED, "max_sites above 2^23");
+    }
     return thr;
 }
 
@@ -144,12 +194,88 @@ const uint8_t *prepare_strands(const DevCall &c, uint8_t *q)
     return q;
 }
 
+// ---- call: what the two forms share behind the extents of a slab, and behind the last slab
+struct CallRun {
+    kbo::RefsetSitePairs pairs;
+    kbo::RefsetResolveArgs r;
+};
+CallRun call_run(const DevCall &c, uint8_t *w, const Tail &t, const CallStage &s, uint64_t pairs, const uint8_t *walk_q, uint32_t min_thr)
+{
+    namespace rr = kbo::refresolve;
+    auto at = [&](size_t o) { return reinterpret_cast<uint32_t *>(w + o); };
+    auto at64 = [&](size_t o) { return reinterpret_cast<uint64_t *>(w + o); };
+    CallRun R{};
+    R.pairs = kbo::RefsetSitePairs{at(t.local), at(t.local) + pairs, at(t.local) + 2 * pairs};
+    kbo::RefsetResolveArgs &r = R.r;
+    r.concat = c.d_concat;
+    r.q = walk_q;
+    r.off = c.d_offsets;
+    r.total = c.total_bases;
+    r.n_seqs = (uint32_t)c.n_seqs;
+    r.k = c.set->k;
+    r.qlen = rr::qmer_len(min_thr, c.set->k);
+    r.add_revcomp = c.add_revcomp;
+    r.max_sites = (uint32_t)c.max_sites;
+    r.tags = at(s.tags);
+    r.wins = w + s.wins;
+    r.ix[0] = at64(s.ix[0]);
+    r.ix[1] = at64(s.ix[1]);
+    r.keys[0] = at64(s.keys[0]);
+    r.keys[1] = at64(s.keys[1]);
+    r.hist = at(s.hist);
+    r.sums = at(s.sums);
+    r.words = at(s.words);
+    r.vcnt = at(s.vcnt);
+    r.ccnt = at(s.ccnt);
+    r.vsums = at(s.vsums);
+    r.csums = at(s.csums);
+    const rr::KeyShape shape = rr::key_shape(c.set->descs.size(), c.n_seqs, c.total_bases);
+    r.key_seq_bits = shape.seq_bits;
+    r.key_hi_bits = shape.hi_bits;
+    r.key_i_bits = shape.i_bits;
+    r.variants = static_cast<uint32_t *>(c.d_out);
+    r.chars = c.d_chars;
+    r.max_variants = c.capacity;
+    r.max_chars = c.max_chars;
+    r.stats = reinterpret_cast<uint64_t *>(c.d_calls);
+    return R;
+}
+// behind the extents of a slab whose RefsetSitePairs the form has made: Caller::run_slab's launch_refset_call, and the sites appended
+void enqueue_call_slab(const DevSet *ds, const CallRun &R, uint8_t *w, const Tail &t, const CallStage &s, uint32_t pairs, uint64_t bytes, uint32_t min_thr,
+                       hipStream_t st)
+{
+    if (!pairs || !bytes) return;
+    kbo::RefsetCallArgs a{};
+    a.descs = ds->descs.as<kbo::RefsetDesc>();
+    a.arena = ds->arena.as<uint4>();
+    a.q = R.r.q;
+    a.ms = w + t.ms;
+    a.poff = reinterpret_cast<const uint64_t *>(w + t.poff);
+    a.pthr = reinterpret_cast<const uint32_t *>(w + t.pthr);
+    a.ext = reinterpret_cast<const uint32_t *>(w + t.chars);
+    a.pref = R.pairs.pref;
+    a.pq = R.pairs.pq;
+    a.counts = reinterpret_cast<uint32_t *>(w + s.counts);
+    a.cands = reinterpret_cast<uint2 *>(w + s.cands);
+    a.sites = reinterpret_cast<uint4 *>(w + s.sites);
+    a.win = w + s.win;
+    a.bytes = bytes;
+    a.n_pairs = pairs;
+    a.k = R.r.k;
+    a.min_thr = min_thr;
+    a.cap = R.r.max_sites;
+    HIP_OK(kbo::launch_refset_call(a, st));
+    HIP_OK(kbo::launch_refset_sites_append(a, R.pairs, R.r, st));
+}
+
 // ---- the unscreened form: a slab is a range of queryable references against the whole batch
 struct DevForm {
     kbo::refplan::Geometry g;
     uint32_t n_refs = 0, n_q = 0, max_refs = 0, refs = 0; // references of the set, queryable ones, the most a slab may hold, a slab's
     size_t q = 0, nch = 0, qflag = 0, qref = 0, thr = 0, total = 0; // per call ...
     Tail t;                                                         // ... and per slab
+    CallStage cs;                                                   // (call)
+    size_t end = 0;  // the figure
     bool ok = false; // false: a limit of the kernels is exceeded even with one reference per slab
 };
 
@@ -158,6 +284,7 @@ DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int stran
 {
     DevForm F;
     if (!set || n_seqs == 0 || strands < 1 || strands > 3 || !packed_only(set)) return F; // (the call refuses them)
+    if (kind == kCall && (capacity == 0 || capacity > kCallMaxSites)) return F;              // (call: capacity is max_sites)
     const uint64_t ns = strands == 3 ? 2 : 1;
     if (n_seqs * ns >= (1ull << 28) || n_seqs >= (1ull << 28) || ns * total >= (1ull << 32) - 16) return F;
     if (ns * kbo::refplan::chunks_bound(total, n_seqs, kbo::refplan::chunk_of(set->k)) > 0xFFFFFF00ull) return F;
@@ -180,25 +307,31 @@ DevForm dev_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int stran
     F.thr = w;    w += up16((size_t)F.n_refs * sizeof(uint32_t));
     F.total = w;  w += 16;
     F.t = tail_layout(w, set->k, R * n_seqs * ns, R * ns * total, R * F.g.item_slots, R * F.g.tasks_per_ref, capacity, kind);
+    F.end = F.t.end;
+    if (kind == kCall) { // (the figure is never below the summary's: many pairs and few sites would put it there)
+        F.cs = call_stage_layout(F.t.end, set->k, total, capacity);
+        F.end = std::max(F.cs.end, tail_layout(w, set->k, R * n_seqs * ns, R * ns * total, R * F.g.item_slots, R * F.g.tasks_per_ref, 0, kSummary).end);
+    }
     F.ok = true;
     return F;
 }
 
 void run_dev_form(const DevCall &c, Kind kind)
 {
-    const bool find = kind == kFind, best = kind == kBest;
+    const bool find = kind == kFind, best = kind == kBest, call = kind == kCall;
     const std::vector<uint32_t> thr = check_dev_call(c, kind, false);
     kbo_refset *set = c.set;
-    DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, 1, kind);
+    const size_t cap = layout_capacity(c, kind);
+    DevForm F = dev_form(set, c.n_seqs, c.total_bases, c.strands, cap, 1, kind);
     KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a slab of one reference of 2^32 - 16 bytes or more, or 2^28 (sequence, strand) pairs or more");
-    KBO_REQUIRE(c.work_bytes >= F.t.end, KBO_E_BAD_ARG, "work_bytes too small for one reference a slab");
+    KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes too small for one reference a slab");
     uint32_t lo = 1, hi = F.max_refs; // the largest refs_per_slab whose figure fits: the figure is monotonic
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, mid, kind).t.end <= c.work_bytes) lo = mid;
+        if (dev_form(set, c.n_seqs, c.total_bases, c.strands, cap, mid, kind).end <= c.work_bytes) lo = mid;
         else hi = mid - 1;
     }
-    F = dev_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, lo, kind);
+    F = dev_form(set, c.n_seqs, c.total_bases, c.strands, cap, lo, kind);
     DevSet *ds = require_device_set(set);
 
     uint32_t min_thr = set->k;
@@ -220,8 +353,9 @@ void run_dev_form(const DevCall &c, Kind kind)
     P.nch = at(F.nch);
     P.nch_sums = at(F.nch) + c.n_seqs + 1;
     P.qref = at(F.qref);
-    uint64_t *d_n = best ? reinterpret_cast<uint64_t *>(w + F.total) : c.d_n; // (best: the count the planner zeroes lies in d_work)
+    uint64_t *d_n = best || call ? reinterpret_cast<uint64_t *>(w + F.total) : c.d_n; // (best, call: the count the planner zeroes lies in d_work)
     HIP_OK(kbo::launch_refset_plan_call(P, F.n_refs, at(F.nch), at(F.qflag), at(F.qref), d_n, st));
+    if (call) HIP_OK(hipMemsetAsync(c.d_calls, 0, sizeof(kbo_ref_calls_stats), st));
     if (best) {
         HIP_OK(kbo::launch_refset_best_init(static_cast<uint32_t *>(c.d_out), (uint32_t)c.n_seqs, st));
         std::fill(t_best, t_best + 2, 0);
@@ -230,6 +364,8 @@ void run_dev_form(const DevCall &c, Kind kind)
 
     const Tail &t = F.t;
     uint32_t *out = static_cast<uint32_t *>(c.d_out);
+    CallRun R{};
+    if (call) R = call_run(c, w, t, F.cs, (uint64_t)F.refs * c.n_seqs * F.g.n_strands, q, min_thr);
     for (size_t q0 = 0; q0 < qrefs.size(); q0 += F.refs) {
         const uint32_t refs = (uint32_t)std::min<size_t>(F.refs, qrefs.size() - q0);
         const uint32_t np = refs * (uint32_t)c.n_seqs * F.g.n_strands;
@@ -242,6 +378,9 @@ void run_dev_form(const DevCall &c, Kind kind)
         enqueue_tail(kind, run, [&] {
             if (find) {
                 HIP_OK(kbo::launch_refset_tag_runs(P, (uint32_t)q0, np, at(t.first), at(t.local), (uint32_t)t.local_cap, c.d_n, c.capacity, out, st));
+            } else if (call) {
+                HIP_OK(kbo::launch_refset_site_pairs_plan(P, (uint32_t)q0, np, R.pairs, st));
+                enqueue_call_slab(ds, R, w, t, F.cs, np, run.bytes, min_thr, st);
             } else if (best) {
                 kbo::RefsetBestArgs b;
                 b.ext = at(t.chars);
@@ -260,6 +399,7 @@ void run_dev_form(const DevCall &c, Kind kind)
             }
         });
     }
+    if (call) HIP_OK(kbo::launch_refset_resolve(R.r, st));
 }
 
 // ---- the screened form: the screen kernel over the batch where it is, the bitmap to the list of its set bits, and ONE slab of the
@@ -273,6 +413,7 @@ struct CandForm {
     size_t rev = 0; // bytes of one strand of the batch in the query buffer
     size_t q = 0, thr = 0, pc = 0, hdr = 0, bits = 0, list = 0, bsum = 0, nch = 0, rfirst = 0, ntask = 0, total = 0, end = 0;
     Tail t;
+    CallStage cs; // (call)
     bool ok = false;
 };
 
@@ -284,6 +425,7 @@ CandForm cand_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int str
     if (!set || strands < 1 || strands > 3 || n_seqs == 0 || !set->prefilter || !packed_only(set) || screen_bits(set, n_seqs) > kPrefilterMaxBits) return F;
     if (n_seqs * ns >= (1ull << 28) || total >= (1ull << 31) || ns * total >= (1ull << 32) - 16) return F;
     if (kind != kCandidatesOnly && (MP == 0 || MP > kCandMaxPairs || max_bases > kCandMaxBases)) return F;
+    if (kind == kCall && (capacity == 0 || capacity > kCallMaxSites)) return F; // (call: capacity is max_sites)
     F.n_refs = (uint32_t)set->descs.size();
     for (const kbo::RefsetDesc &d : set->descs) F.n_q += !d.status;
     F.n_bits = screen_bits(set, n_seqs);
@@ -308,11 +450,13 @@ CandForm cand_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int str
         F.rfirst = w; w += up16((size_t)(F.n_refs + 1) * sizeof(uint32_t));
         F.ntask = w;  w += up16(kbo::chunk_items_scratch_words(F.n_refs) * sizeof(uint32_t));
         F.t = tail_layout(w, set->k, MP, max_bases, F.item_slots, F.task_slots, capacity, kind);
+        const size_t summary_end = kind == kCall ? tail_layout(w, set->k, MP, max_bases, F.item_slots, F.task_slots, 0, kSummary).end + 16 : 0;
         w = F.t.end;
         if (kind == kSummary) {
             F.total = w;
             w += 16;
         }
+        if (kind == kCall) w = std::max((F.cs = call_stage_layout(w, set->k, total, capacity)).end, summary_end); // (never below the summary's)
     }
     if (strands == 2) { // '-' alone: the screen kernel reads it at q + rev, so it lies at least rev bytes into d_work and q inside it
         F.q = std::max(w, F.rev);
@@ -326,10 +470,10 @@ CandForm cand_form(const kbo_refset *set, size_t n_seqs, uint64_t total, int str
 void run_cand_form(const DevCall &c, Kind kind)
 {
     namespace sc = kbo::refscreen;
-    const bool find = kind == kFind, best = kind == kBest, only = kind == kCandidatesOnly;
+    const bool find = kind == kFind, best = kind == kBest, only = kind == kCandidatesOnly, call = kind == kCall;
     const std::vector<uint32_t> thr = check_dev_call(c, kind, true);
     kbo_refset *set = c.set;
-    const CandForm F = cand_form(set, c.n_seqs, c.total_bases, c.strands, c.capacity, c.max_pairs, c.max_bases, kind);
+    const CandForm F = cand_form(set, c.n_seqs, c.total_bases, c.strands, layout_capacity(c, kind), c.max_pairs, c.max_bases, kind);
     KBO_REQUIRE(F.ok, KBO_E_UNSUPPORTED, "a batch of 2^31 bases or more, or 2^28 (sequence, strand) pairs or more");
     KBO_REQUIRE(c.work_bytes >= F.end, KBO_E_BAD_ARG, "work_bytes below the figure of *_work_bytes");
     DevSet *ds = require_device_set(set);
@@ -357,6 +501,7 @@ void run_cand_form(const DevCall &c, Kind kind)
     uint32_t *bits = only ? c.d_bits : at(F.bits);
     HIP_OK(hipMemsetAsync(bits, 0, (size_t)F.words * sizeof(uint32_t), st));
     HIP_OK(hipMemsetAsync(c.d_stats, 0, sizeof(kbo_refset_screen_stats), st));
+    if (call) HIP_OK(hipMemsetAsync(c.d_calls, 0, sizeof(kbo_ref_calls_stats), st));
     kbo::RefsetScreenArgs s = screen_args(ds, c.n_seqs, c.total_bases, c.strands);
     s.m = w + F.thr + (size_t)F.n_refs * 4;
     s.q = c.strands == 2 ? w + F.q - F.rev : walk_q;
@@ -404,9 +549,15 @@ void run_cand_form(const DevCall &c, Kind kind)
     launch_walks(ds, tasks, items, a.task_slots, set->k, walk_q, w + t.ms, walk_kinds(set, 0, F.n_refs), st);
     uint32_t *out = static_cast<uint32_t *>(c.d_out);
     const TailRun run{w, t, a.max_pairs, c.max_bases, set->k, min_thr, c.gap, at(F.total), st};
+    CallRun R{};
+    if (call) R = call_run(c, w, t, F.cs, a.max_pairs, walk_q, min_thr);
     enqueue_tail(kind, run, [&] {
         if (find) {
             HIP_OK(kbo::launch_refset_cand_tag_runs(a, at(t.first), at(t.local), (uint32_t)t.local_cap, c.d_n, c.capacity, out, st));
+        } else if (call) {
+            HIP_OK(kbo::launch_refset_site_pairs_cand(a, R.pairs, st));
+            enqueue_call_slab(ds, R, w, t, F.cs, a.max_pairs, c.max_bases, min_thr, st);
+            if (c.total_bases) HIP_OK(kbo::launch_refset_resolve(R.r, st));
         } else if (best) { // (the table is initialised here, behind the extents; the unscreened form does it once per call, up front)
             HIP_OK(kbo::launch_refset_best_init(out, (uint32_t)c.n_seqs, st));
             HIP_OK(kbo::launch_refset_cand_best(a, at(t.chars), out, st));
@@ -417,7 +568,7 @@ void run_cand_form(const DevCall &c, Kind kind)
 }
 
 // an entry point's call in either form; find takes its error probability and gap from the options
-int run_call(DevCall c, Kind kind, bool screened, const kbo_find_opts *opts = nullptr)
+int run_call(DevCall c, Kind kind, bool screened, const kbo_find_opts *opts = nullptr, const kbo_call_opts *copts = nullptr)
 {
     return guarded([&] {
         if (kind == kFind) {
@@ -426,11 +577,32 @@ int run_call(DevCall c, Kind kind, bool screened, const kbo_find_opts *opts = nu
             c.max_error_prob = o.max_error_prob;
             c.gap = (uint32_t)std::min<size_t>(o.max_gap_len, 0xFFFFFFFFu);
         }
+        if (kind == kCall) {
+            kbo_call_opts o;
+            if (copts) o = *copts; else kbo_call_opts_default(&o);
+            c.max_error_prob = o.max_error_prob;
+            c.opts_k = o.sbwt_build_opts.k;
+            c.add_revcomp = o.sbwt_build_opts.add_revcomp ? 1u : 0u;
+        }
         if (screened) run_cand_form(c, kind);
         else run_dev_form(c, kind);
     });
 }
 static_assert(sizeof(kbo_refset_screen_stats) == 32, "kbo_refset_screen_stats is 32 bytes");
+static_assert(sizeof(kbo_ref_calls_stats) == 64 && sizeof(kbo_ref_variant) == 24, "kbo_ref_calls_stats is 64 bytes, kbo_ref_variant six words");
+
+DevCall call_args(kbo_refset *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases, int strands, void *d_work,
+                  size_t work_bytes, kbo_ref_variant *d_variants, size_t max_variants, uint8_t *d_chars, size_t max_chars, size_t max_sites,
+                  kbo_ref_calls_stats *d_stats, void *stream)
+{
+    DevCall c{set, d_concat, d_offsets, n_seqs, total_bases, /* from opts: */ 0, 0u, strands, d_work, work_bytes, d_variants, max_variants, nullptr,
+              static_cast<hipStream_t>(stream)};
+    c.max_sites = max_sites;
+    c.max_chars = max_chars;
+    c.d_chars = d_chars;
+    c.d_calls = d_stats;
+    return c;
+}
 
 } // namespace
 
@@ -439,18 +611,18 @@ extern "C" {
 size_t kbo_find_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
                                       size_t refs_per_slab)
 {
-    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kFind).t.end;
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kFind).end;
 }
 
 size_t kbo_summary_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t capacity,
                                          size_t refs_per_slab)
 {
-    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kSummary).t.end;
+    return dev_form(set, n_seqs, total_bases, strands, capacity, refs_per_slab, kSummary).end;
 }
 
 size_t kbo_best_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t refs_per_slab)
 {
-    return dev_form(set, n_seqs, total_bases, strands, 0, refs_per_slab, kBest).t.end;
+    return dev_form(set, n_seqs, total_bases, strands, 0, refs_per_slab, kBest).end;
 }
 
 int kbo_find_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
@@ -530,6 +702,39 @@ int kbo_best_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, con
 {
     return run_call(DevCall{set, d_concat, d_offsets, n_seqs, total_bases, max_error_prob, 0u, strands, d_work, work_bytes, d_out, 0, nullptr,
                             static_cast<hipStream_t>(stream), max_pairs, max_pair_bases, nullptr, d_stats}, kBest, true);
+}
+
+size_t kbo_call_refset_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_sites,
+                                      size_t refs_per_slab)
+{
+    return dev_form(set, n_seqs, total_bases, strands, max_sites, refs_per_slab, kCall).end;
+}
+
+int kbo_call_refset_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                        const kbo_call_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_variant *d_variants, size_t max_variants,
+                        uint8_t *d_chars, size_t max_chars, size_t max_sites, kbo_ref_calls_stats *d_stats, void *stream)
+{
+    return run_call(call_args(set, d_concat, d_offsets, n_seqs, total_bases, strands, d_work, work_bytes, d_variants, max_variants, d_chars, max_chars,
+                              max_sites, d_stats, stream), kCall, false, nullptr, opts);
+}
+
+size_t kbo_call_refset_screened_dev_work_bytes(const kbo_refset_t *set, size_t n_seqs, uint64_t total_bases, int strands, size_t max_sites,
+                                               size_t max_pairs, uint64_t max_pair_bases)
+{
+    return cand_form(set, n_seqs, total_bases, strands, max_sites, max_pairs, max_pair_bases, kCall).end;
+}
+
+int kbo_call_refset_screened_dev(kbo_refset_t *set, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                                 const kbo_call_opts *opts, int strands, void *d_work, size_t work_bytes, kbo_ref_variant *d_variants,
+                                 size_t max_variants, uint8_t *d_chars, size_t max_chars, size_t max_sites, kbo_ref_calls_stats *d_stats,
+                                 size_t max_pairs, uint64_t max_pair_bases, kbo_refset_screen_stats *d_screen_stats, void *stream)
+{
+    DevCall c = call_args(set, d_concat, d_offsets, n_seqs, total_bases, strands, d_work, work_bytes, d_variants, max_variants, d_chars, max_chars,
+                          max_sites, d_stats, stream);
+    c.max_pairs = max_pairs;
+    c.max_bases = max_pair_bases;
+    c.d_stats = d_screen_stats;
+    return run_call(c, kCall, true, nullptr, opts);
 }
 
 } // extern "C"

@@ -348,13 +348,14 @@ def call_refset(query_seqs, refset, opts=None, strands=STRAND_BOTH, host=False):
     sequence's, ref characters the reference's; '-' positions are those of the reverse-complemented sequence.  opts: CallOpts whose
     sbwt_build_opts.k is the set's k (None: the defaults with that k); its add_revcomp is the sequence's own index's, as in
     call_batch.  The set is packed_only().  Useful calls need k of about twice the threshold or more.
-    host=True: the restatement on the CPU (kbo_call_refset_host), byte-identical"""
+    host=True: the restatement on the CPU (kbo_call_refset_host), byte-identical; host="indexed": that with the second pass as the
+    device-resident forms run it (kbo_call_refset_host_indexed), byte-identical too"""
     from . import BuildOpts, CallOpts
     o = opts if opts is not None else CallOpts(sbwt_build_opts=BuildOpts(k=refset.k(), build_select=True))
     co = _capi.CallOpts(o.max_error_prob, o.sbwt_build_opts._to_c())
     concat, offsets, n = _batch(query_seqs)
     res = _capi.RefCalls()
-    f = lib().kbo_call_refset_host if host else lib().kbo_call_refset
+    f = lib().kbo_call_refset_host_indexed if host == "indexed" else lib().kbo_call_refset_host if host else lib().kbo_call_refset
     check(f(refset._h, concat.ctypes.data, offsets.ctypes.data, n, C.byref(co), int(strands), C.byref(res)))
     try:
         if res.n_variants == 0:
@@ -374,6 +375,50 @@ def variant_chars(variant, chars):
     """(query_chars, ref_chars) of one REF_VARIANT record as bytes"""
     at, ql, rl = int(variant["chars"]), int(variant["query_len"]), int(variant["ref_len"])
     return chars[at:at + ql].tobytes(), chars[at + ql:at + ql + rl].tobytes()
+
+
+def call_refset_dev(concat, offsets, refset, opts=None, strands=STRAND_BOTH, max_variants=1 << 16, max_chars=1 << 20, max_sites=1 << 16,
+                    refs_per_slab=None, stream=None, screened=False, max_pairs=None, max_pair_bases=None):
+    """kbo_call_refset_dev over torch tensors on the device: call_refset's records, nothing synchronised.  Returns (variants, chars,
+    stats): an (max_variants, 6) int32 tensor that holds the u32 words of REF_VARIANT, a uint8 tensor of max_chars characters and an
+    int64 tensor of 8 words (n_variants, n_chars, n_sites, max_slab_candidates, n_panics, 0, 0, 0), complete when `stream` reaches
+    the end of the call.  Record x is there iff x < max_variants, its characters iff chars + query_len + ref_len <= max_chars; the
+    call is complete iff max_slab_candidates <= max_sites and n_sites <= max_sites.  The batch, refs_per_slab and stream as in
+    summary_refset_dev.  screened=True: kbo_call_refset_screened_dev, the caps as find_refset_dev's; returns (variants, chars,
+    stats, screen_stats)."""
+    import torch
+    from . import BuildOpts, CallOpts
+    o = opts if opts is not None else CallOpts(sbwt_build_opts=BuildOpts(k=refset.k(), build_select=True))
+    co = _capi.CallOpts(o.max_error_prob, o.sbwt_build_opts._to_c())
+    q, off, n_seqs, total, s = _dev_batch(concat, offsets, stream)
+    L = lib()
+    max_variants, max_chars, max_sites = int(max_variants), int(max_chars), int(max_sites)
+    if screened and (max_pairs is None or max_pair_bases is None):
+        st = refset.candidates_dev(q, off, o.max_error_prob, strands, s)[1].cpu()  # (the one synchronisation of a call without caps)
+        max_pairs = max(1, int(st[0])) if max_pairs is None else max_pairs
+        max_pair_bases = int(st[1]) if max_pair_bases is None else max_pair_bases
+    with torch.cuda.device(q.device), torch.cuda.stream(s):
+        variants = torch.empty((max_variants, 6), dtype=torch.int32, device=q.device)
+        chars = torch.empty(max_chars, dtype=torch.uint8, device=q.device)
+        stats = torch.empty(8, dtype=torch.int64, device=q.device)
+        vp = variants.data_ptr() if max_variants else None
+        cp = chars.data_ptr() if max_chars else None
+        if screened:
+            max_pairs, max_pair_bases = int(max_pairs), int(max_pair_bases)
+            wb = int(L.kbo_call_refset_screened_dev_work_bytes(refset._h, n_seqs, total, int(strands), max_sites, max_pairs, max_pair_bases))
+            work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+            screen_stats = torch.empty(4, dtype=torch.int64, device=q.device)
+            check(L.kbo_call_refset_screened_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, C.byref(co), int(strands),
+                                                 work.data_ptr(), wb, vp, max_variants, cp, max_chars, max_sites, stats.data_ptr(),
+                                                 max_pairs, max_pair_bases, screen_stats.data_ptr(), s.cuda_stream))
+            return variants, chars, stats, screen_stats
+        ns = 2 if int(strands) == STRAND_BOTH else 1  # (None: slabs of about 256 MiB, as summary_refset_dev)
+        rps = max(1, (1 << 28) // max(1, ns * total)) if refs_per_slab is None else int(refs_per_slab)
+        wb = int(L.kbo_call_refset_dev_work_bytes(refset._h, n_seqs, total, int(strands), max_sites, rps))
+        work = torch.empty(wb // 8 + 2, dtype=torch.int64, device=q.device)
+        check(L.kbo_call_refset_dev(refset._h, q.data_ptr(), off.data_ptr(), n_seqs, total, C.byref(co), int(strands), work.data_ptr(), wb,
+                                    vp, max_variants, cp, max_chars, max_sites, stats.data_ptr(), s.cuda_stream))
+    return variants, chars, stats
 
 
 def last_call():

@@ -54,6 +54,11 @@ contigs and their reverse complements, for LOOP references (LOOP=0: every refere
 behind a warm-up for the set's calls; the seconds, kbo_refset_last_call's counters (pairs, candidates, sites, variants), and a CRC of
 the variants of the references the loop took from both routes - the loop's filtered to the pairs with a summary record, as the call
 is defined - which must be equal.
+CALL=1 DEV=1 is a leg of its own on the same workload, one set, one session: kbo_call_refset next to the device-resident form - with
+PREFILTER=1 kbo_call_refset_screened_dev with caps from kbo_refset_candidates_dev's figures, else kbo_call_refset_dev (REFS_PER_SLAB) -
+and next to the floor, the summary's device form on the same set.  The batch is uploaded once outside the timed regions; a timed
+device call ends when its records, characters and stats are on the host.  Median of REPEATS behind a warm-up for each; variants_crc32
+of both calls (they must be equal) and the device form's stats.  MAX_SITES=65536 sizes its lists.  LOOP does not apply.
 The LDS kernel's own rate: run this under a kernel trace with LOOP=0 REPEATS=1 and divide the pair-bases by refset_walk_kernel's time."""
 import json
 import os
@@ -408,6 +413,68 @@ def call_leg():
     print(json.dumps(out))
     assert loop_recs == mine, "kbo_call_refset and the loop over single indexes differ"
 
+
+def call_dev_leg():
+    """kbo_call_refset next to its device-resident form and to the summary's device form, the floor: one set, one session"""
+    max_sites = int(os.environ.get("MAX_SITES", 1 << 16))
+    copts = kbo_amd.CallOpts(max_error_prob=fopts.max_error_prob, sbwt_build_opts=kbo_amd.BuildOpts(k=K, build_select=True))
+    s = refset.RefSet.build(refs, opts, prefilter=bool(PREFILTER)).to_device()
+    d_q = torch.zeros(int(offsets[-1]) + 16, dtype=torch.uint8, device="cuda")
+    d_q[:int(offsets[-1])].copy_(torch.from_numpy(concat))
+    d_off = torch.from_numpy(offsets.astype(np.int64)).cuda()
+    kw = dict(refs_per_slab=REFS_PER_SLAB)
+    if PREFILTER:
+        cand = [int(v) for v in s.candidates_dev(d_q, d_off, fopts.max_error_prob, strands=3)[1].cpu().numpy()]
+        kw = dict(screened=True, max_pairs=max(1, cand[0]), max_pair_bases=cand[1])
+    torch.cuda.synchronize()
+    stats = {}
+
+    def host_call():
+        variants, chars = refset.call_refset(contigs, s, copts, strands=3)
+        return variants.tobytes() + chars.tobytes(), len(variants)
+
+    def dev_call():
+        got = refset.call_refset_dev(d_q, d_off, s, copts, strands=3, max_variants=DEV_CAPACITY, max_chars=4 * DEV_CAPACITY, max_sites=max_sites, **kw)
+        st = [int(v) for v in got[2].cpu().numpy()]  # (waits for the stream: the only synchronisation of the call)
+        stats["stats"] = dict(zip(("n_variants", "n_chars", "n_sites", "max_slab_candidates", "n_panics"), st))
+        if PREFILTER:
+            stats["screen"] = dict(zip(("n_candidates", "candidate_bases", "n_walked", "walked_bases"), (int(v) for v in got[3].cpu().numpy())))
+        n, nc = min(st[0], DEV_CAPACITY), min(st[1], 4 * DEV_CAPACITY)
+        return np.ascontiguousarray(got[0][:n].cpu().numpy()).tobytes() + got[1][:nc].cpu().numpy().tobytes(), n
+
+    def floor_call():
+        got = refset.summary_refset_dev(d_q, d_off, s, fopts.max_error_prob, strands=3, capacity=DEV_CAPACITY, **kw)
+        n = int(got[1].item())
+        return np.ascontiguousarray(got[0][:min(n, DEV_CAPACITY)].cpu().numpy()).tobytes(), n
+
+    def timed(fn, what):
+        got = fn()  # warm-up: code objects, the allocator's blocks
+        ts = []
+        for _ in range(REPEATS):
+            t = time.perf_counter()
+            got = fn()
+            ts.append(time.perf_counter() - t)
+        return {"call_s": round(statistics.median(ts), 5), "call_s_all": [round(t, 5) for t in ts], what: got[1], what + "_crc32": zlib.crc32(got[0])}
+    out = {"workload": {"refs": REFS, "ref_bp": REF_BP, "query_bp": int(offsets[-1]), "contigs": CONTIGS, "k": K, "strands": 2, "pair_bases": pair_bases},
+           "prefilter": bool(PREFILTER), "max_sites": max_sites}
+    out["call_refset_dev"] = timed(dev_call, "variants")
+    out["call_refset_dev"].update(stats)
+    out["call_refset_dev"].update({k_: v for k_, v in kw.items() if k_ != "screened"})
+    out["call_refset"] = timed(host_call, "variants")
+    out["call_refset"]["counters"] = refset.last_call()
+    out["summary_refset_dev"] = timed(floor_call, "records")
+    st = stats["stats"]
+    out["complete"] = st["max_slab_candidates"] <= max_sites and st["n_sites"] <= max_sites
+    out["variants_equal"] = out["call_refset_dev"]["variants_crc32"] == out["call_refset"]["variants_crc32"]
+    out["host_over_dev"] = round(out["call_refset"]["call_s"] / out["call_refset_dev"]["call_s"], 2)
+    out["dev_over_floor"] = round(out["call_refset_dev"]["call_s"] / out["summary_refset_dev"]["call_s"], 2)
+    print(json.dumps(out))
+    assert out["variants_equal"], "kbo_call_refset and its device-resident form differ"
+
+
+if CALL and DEV:
+    call_dev_leg()
+    sys.exit(0)
 
 if CALL:
     call_leg()
