@@ -3,6 +3,7 @@
 //   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline with one output stage per mode,
 //   kbo_capi.cpp      the extern "C" entry points,
 //   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
+//   batch_route.cpp   the kernel route of a batch, for host slabs and device calls alike (batch_route.hpp),
 //   build_device.cpp  kbo_index_build_device (the index built by the device).
 #pragma once
 #include <atomic>
@@ -443,6 +444,7 @@ struct FusedMap {
     uint8_t *d_chars;   // >= total + 16 bytes
     uint32_t threshold;
     bool format;        // + format::relative_to_ref
+    bool want_ms = false; // the MS values go to memory as well (the device calls)
     bool done = false;
     // a packed batch whose characters leave packed as well: where their words go (nw words + 16 bytes); packed_done = the kernel
     // wrote them there itself (its packed-native form), else the characters are in d_chars as for any batch
@@ -456,6 +458,7 @@ struct FusedMap {
     // its second pass wrote them and no character was made, else the characters are in d_chars for the reducer (summary_kernels.hip)
     uint4 *d_summary = nullptr;
     bool summarized = false;
+    hipStream_t ts = nullptr; // done: where the route left the result complete (batch_route.hpp route_map)
 };
 // Strands of a host batch (kbo_*_batch_strands) and the count of what it uploads.  strands = KBO_STRAND_FWD: the slab as it is;
 // KBO_STRAND_REV: its reverse complement, made on the device from the uploaded slab; both: the slab DOUBLED on the device -

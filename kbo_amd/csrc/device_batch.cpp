@@ -10,12 +10,11 @@
 #include <atomic>
 #include <cstdlib>
 #include <deque>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
 
-#include "capi_internal.hpp"
+#include "batch_route.hpp"
 
 using namespace kbo_host;
 
@@ -104,54 +103,37 @@ void require_batch(bool args, size_t n_seqs, uint64_t total_bases, std::initiali
     KBO_REQUIRE(low == 0, KBO_E_BAD_ARG, alignment);
 }
 
-// one index's copy on the current device, asked for once per call: device_view() counts the batch's bases for the copy's lazy plan
-// structures
-struct CopyView {
-    kbo::DevIndexView ix{};
-    DevCopy::PlanState *plan = nullptr;
-};
-CopyView copy_view(kbo_index *idx, uint64_t total_bases)
+// a batch of bytes in HBM with its d_work as the routes see it (batch_route.hpp): one item per sequence or chunks, made by walk_ms
+// for the walk alone - map_reads_kernel and its second pass read the offsets themselves
+BatchView batch_view(const DevWork &w, void *d_work, const uint8_t *q, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                     uint32_t longest, uint8_t *d_ms)
 {
-    CopyView c;
-    c.ix = device_view(idx, current_device(), &c.plan, total_bases);
-    return c;
-}
-
-// map_reads_kernel's arguments over a batch of reads (one item per read; the kernel and its second pass read the offsets themselves:
-// no item list is made)
-kbo::WalkArgs reads_args(const CopyView &c, const DevWork &w, void *d_work, const uint8_t *q, const uint64_t *d_offsets,
-                         uint64_t total_bases, uint32_t longest, uint8_t *d_ms, uint8_t *chars_out, uint32_t thr, bool format, bool want_ms,
-                         bool whatever_the_holdoff = false /* planned even while the copy's plan is held off (summary batches) */)
-{
-    kbo::WalkArgs a{};
-    a.ix = c.ix;
-    a.q = q;
-    a.q_bytes = total_bases;
-    a.items = static_cast<kbo::WalkItem *>(d_work);
-    a.n_items = w.n_slots;
-    a.d_out = d_ms;
-    a.max_item_len = longest;
-    attach_plan(a, static_cast<uint8_t *>(d_work) + w.plan_off, whatever_the_holdoff ? nullptr : c.plan);
-    a.chars_out = chars_out;
-    a.map_thr = thr;
-    a.map_fmt = format ? 1u : 0u;
-    a.map_want_ms = want_ms ? 1u : 0u;
-    a.seq_off = d_offsets;
-    return a;
-}
-
-// the MS values of a batch (kbo_ms_batch_dev, kbo_call_walk_dev, and the first of map / find's two kernels) into d_ms_out.  `given`:
-// the caller's view of an unsharded index, or null (asked for here); a sharded index has every shard walked, the maximum kept
-void walk_ms(kbo_index *idx, const CopyView *given, const DevWork &w, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs,
-             uint64_t total_bases, uint32_t longest, uint8_t *d_ms_out, uint32_t *d_lo_out, uint32_t *d_hi_out, void *d_work,
-             hipStream_t s, const CallSink *call)
-{
-    KBO_REQUIRE(total_bases / w.chunk + n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
-    if (call) HIP_OK(hipMemsetAsync(call->d_counts, 0, kbo::kCallSegs * 64 + 64, s)); // (kbo_call_walk_dev's counters: once the call is accepted)
     uint8_t *work = static_cast<uint8_t *>(d_work);
+    BatchView v;
+    v.q = q;
+    v.offsets = v.reads_seq_off = d_offsets;
+    v.n_seqs = (uint32_t)n_seqs;
+    v.total = total_bases;
+    v.longest = longest;
+    v.items = static_cast<kbo::WalkItem *>(d_work);
+    v.n_items = w.n_slots;
+    v.chunk = w.chunked ? w.chunk : 0;
+    v.plan.p = work + w.plan_off;
+    v.ms = d_ms;
+    v.ms_shard = work + w.shard_off;
+    v.long_work.p = work + w.long_off;
+    return v;
+}
+
+// the MS values of a batch (kbo_ms_batch_dev, kbo_call_walk_dev, and the first of map / find's two kernels) into v.ms.  `given`:
+// the caller's view of an unsharded index, or null (asked for here); a sharded index has every shard walked, the maximum kept
+void walk_ms(kbo_index *idx, const CopyView *given, const DevWork &w, BatchView &v, void *d_work, const WalkAsk &ask, hipStream_t s)
+{
+    KBO_REQUIRE(v.total / w.chunk + v.n_seqs < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
+    if (ask.call) HIP_OK(hipMemsetAsync(ask.call->d_counts, 0, kbo::kCallSegs * 64 + 64, s)); // (kbo_call_walk_dev's counters: once the call is accepted)
     CopyView own;
     if (!given && !idx->sharded()) {
-        own = copy_view(idx, total_bases);
+        own = copy_view(idx, v.total);
         given = &own;
     }
     // a batch of reads over a copy with a depth table, nothing but the MS values asked for: map_reads_kernel in the form that puts
@@ -159,48 +141,21 @@ void walk_ms(kbo_index *idx, const CopyView *given, const DevWork &w, const uint
     // stopping there - no characters are made - and the plain walk for the reads it leaves (C2: 0.33 against 0.61 ms per
     // 1 M reads for the plan-guided walk below, which stays what larger batches' chunks, the intervals, the call mode and the
     // work counters take)
-    if (!idx->sharded() && !d_lo_out && !call && !w.chunked && g_ms_one_kernel.load() != 0 && !g_plan_stats.load()) {
-        kbo::WalkArgs a = reads_args(*given, w, d_work, d_concat, d_offsets, total_bases, longest, d_ms_out, nullptr, idx->host.k /* (no value is derandomised here) */,
-                                     false, true);
+    if (!idx->sharded() && !ask.lo && !ask.call && !w.chunked && g_ms_one_kernel.load() != 0 && !g_plan_stats.load()) {
+        const FusedMap values{nullptr, (uint32_t)idx->host.k /* (no value is derandomised here) */, false, true};
+        kbo::WalkArgs a = walk_args(v, *given, v.ms, WalkAsk{}, &values);
         if (a.gitems && kbo::map_reads_applies(a)) {
             a.host_bailed = given->plan ? given->plan->bailed : nullptr;
-            HIP_OK(kbo::launch_map_reads(a, s));
-            if (kbo::map_reads_finish_applies(a)) HIP_OK(kbo::launch_map_reads_finish(a, s)); // (the reads it left: their values by one kernel)
-            else HIP_OK(kbo::launch_redo_pass(a, s));
-            if (!a.host_bailed) plan_after_launch(a, s, given->plan);
+            run_reads(v, a, given->plan, ReadsLaunch{s, s}); // (the reads it left: their values by one kernel, or by the plain walk)
             return;
         }
     }
-    kbo::WalkItem *items = static_cast<kbo::WalkItem *>(d_work);
     if (w.chunked)
-        HIP_OK(kbo::launch_make_chunk_items(d_offsets, (uint32_t)n_seqs, w.chunk, idx->host.k, w.n_slots, items,
-                                            reinterpret_cast<uint32_t *>(work + w.scan_off), s, call != nullptr));
+        HIP_OK(kbo::launch_make_chunk_items(v.offsets, v.n_seqs, w.chunk, idx->host.k, w.n_slots, v.items,
+                                            reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_work) + w.scan_off), s, ask.call != nullptr));
     else
-        HIP_OK(kbo::launch_make_items(d_offsets, (uint32_t)n_seqs, items, s));
-    const std::vector<kbo_index *> shards = shards_of(idx);
-    uint8_t *ms_shard = work + w.shard_off;
-    for (size_t sh = 0; sh < shards.size(); sh++) {
-        const CopyView c = idx->sharded() ? copy_view(shards[sh], total_bases) : *given;
-        kbo::WalkArgs a{};
-        a.ix = c.ix;
-        a.q = d_concat;
-        a.q_bytes = total_bases;
-        a.items = items;
-        a.n_items = w.n_slots;
-        a.rounds = 0;
-        a.d_out = sh == 0 ? d_ms_out : ms_shard;
-        a.lo_out = d_lo_out;
-        a.hi_out = d_hi_out;
-        a.call_sites = call ? static_cast<uint4 *>(call->d_sites) : nullptr;
-        a.call_counts = call ? call->d_counts : nullptr;
-        a.call_cap = call ? call->cap_per_list : 0;
-        a.call_thr = call ? call->threshold : 0;
-        a.max_item_len = w.chunked ? w.chunk + (call ? 2u : 1u) * idx->host.k : longest;
-        attach_plan(a, work + w.plan_off, c.plan);
-        HIP_OK(kbo::launch_ms_walk(a, walk_max_waves(), s));
-        plan_after_launch(a, s, c.plan);
-        if (sh > 0) HIP_OK(kbo::launch_max_bytes(d_ms_out, ms_shard, total_bases, s)); // depth against the union = maximum
-    }
+        HIP_OK(kbo::launch_make_items(v.offsets, v.n_seqs, v.items, s));
+    walk_shards(v, idx, given, ask, s);
 }
 
 int ms_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs,
@@ -218,8 +173,8 @@ int ms_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t 
         const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k, idx->sharded());
         KBO_REQUIRE(work_bytes >= w.walk_min, KBO_E_BAD_ARG,
                     "d_work is smaller than kbo_ms_work_bytes() (+ one shard's MS values for a sharded index: kbo_index_work_bytes()) for this batch");
-        walk_ms(idx, nullptr, w, d_concat, d_offsets, n_seqs, total_bases, (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu), d_ms_out,
-                d_lo_out, d_hi_out, d_work, static_cast<hipStream_t>(stream), call);
+        BatchView v = batch_view(w, d_work, d_concat, d_offsets, n_seqs, total_bases, (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu), d_ms_out);
+        walk_ms(idx, nullptr, w, v, d_work, WalkAsk{d_lo_out, d_hi_out, call}, static_cast<hipStream_t>(stream));
     });
 }
 } // namespace
@@ -469,34 +424,12 @@ int kbo_stage_timing_read(double *kernel_ms_sum, double *redo_ms_sum, int *n_cal
 }
 
 namespace {
-// one fence event per host thread and device: hipStreamWaitEvent takes the event's state at the time of the call, so recording it
-// again for the next batch does not disturb a wait that is already queued
-hipEvent_t tail_fence()
+// map_reads_kernel on L.s, then the second pass over the reads it leaves on the stream fork_tail gives; returns that stream
+// (ReadsLaunch::then of every call of this file but the MS values alone).  kbo_set_stage_timing: the kernel and the second pass each
+// between two events
+hipStream_t map_reads_then(const BatchView &v, kbo::WalkArgs &a, const ReadsLaunch &L)
 {
-    thread_local std::map<int, hipEvent_t> evs;
-    hipEvent_t &ev = evs[current_device()];
-    if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    return ev;
-}
-
-// the second pass on the caller's other stream, behind what `s` holds so far; returns the stream it goes to.  `a`: a batch of reads'
-// second pass, whose pieces grow to 32 bases there (beside another batch's kernel the pass costs by the look-ups it takes away from
-// that kernel rather than by its longest chain: longer pieces, fewer warm-up bases.  Pieces of 16 / 24 / 32 / 48 / 64 bases at C2,
-// two batches in flight: 0.341 / 0.324 / 0.316 / 0.343 / 0.337 ms per batch)
-hipStream_t fork_tail(hipStream_t s, hipStream_t tail, kbo::WalkArgs *a)
-{
-    if (tail == s) return s;
-    hipEvent_t fence = tail_fence();
-    HIP_OK(hipEventRecord(fence, s));
-    HIP_OK(hipStreamWaitEvent(tail, fence, 0));
-    if (a) a->redo_piece = 32u;
-    return tail;
-}
-
-// map_reads_kernel on `s`, then `pass(ts)`, the second pass over the reads it leaves, on the stream fork_tail gives; returns that
-// stream.  kbo_set_stage_timing: the kernel and the second pass each between two events
-template <class Pass> hipStream_t map_reads_then(kbo::WalkArgs &a, hipStream_t s, hipStream_t tail, Pass pass)
-{
+    const hipStream_t s = L.s;
     const bool timing = g_stage_timing.load() != 0;
     StageEvents ev{};
     if (timing) {
@@ -505,9 +438,9 @@ template <class Pass> hipStream_t map_reads_then(kbo::WalkArgs &a, hipStream_t s
     }
     HIP_OK(kbo::launch_map_reads(a, s));
     if (timing) HIP_OK(hipEventRecord(ev.e1, s));
-    const hipStream_t ts = fork_tail(s, tail, &a);
+    const hipStream_t ts = fork_tail(s, L.tail, &a);
     if (timing) HIP_OK(hipEventRecord(ev.e1t, ts)); // (when the second pass starts: behind the kernel and behind what `ts` held)
-    pass(ts);
+    second_pass(v, a, ts, L.one_wave_tail && ts != s);
     if (timing) {
         HIP_OK(hipEventRecord(ev.e2, ts));
         std::lock_guard<std::mutex> g(g_timing_mu);
@@ -554,53 +487,28 @@ int map_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t
                                    : "d_work is smaller than kbo_work_bytes() for this batch");
         const hipStream_t s = static_cast<hipStream_t>(stream);
         const uint32_t n = (uint32_t)n_seqs, thr = (uint32_t)threshold, longest = (uint32_t)std::min<size_t>(max_seq_len, 0xFFFFFFFFu);
-        uint8_t *work = static_cast<uint8_t *>(d_work);
-        const bool long_seqs = max_seq_len == 0 || max_seq_len > 160;
+        BatchView v = batch_view(w, d_work, d_concat, d_offsets, n_seqs, total_bases, longest, d_ms);
+        FusedMap m{d_chars_out, thr, format != 0, want_ms != 0};
+        if (find && find->max_gap_len == 0) m.run_counts = static_cast<uint32_t *>(find->d_rle_work);
+        m.ts = s;
         CopyView c; // (a sharded index takes the two-kernel route: the walk asks for its shards' views)
-        if (!idx->sharded()) c = copy_view(idx, total_bases);
-        kbo::WalkArgs a{};
-        if (!idx->sharded() && !long_seqs && !w.chunked) a = reads_args(c, w, d_work, d_concat, d_offsets, total_bases, longest, d_ms, d_chars_out, thr, format, want_ms);
-        hipStream_t ts = s; // (where the characters are complete)
-        bool one_kernel = true, counted = false;
-        if (!idx->sharded() && long_seqs && !want_ms && w.long_bytes && kbo::map_long_applies(c.ix, thr)) {
-            // sequences of any length: one wave per piece of a sequence (long_kernels.hip), the pieces whose proof fails by the
-            // plain walk + the literal recurrences behind it (on the tail stream when the caller gave one)
-            kbo::LongArgs la{};
-            HIP_OK(kbo::launch_map_long(c.ix, d_concat, d_offsets, n, total_bases, thr, format != 0, d_chars_out, work + w.long_off, s, la,
-                                        g_plan_stats.load()));
-            ts = fork_tail(s, static_cast<hipStream_t>(tail_stream), nullptr);
-            HIP_OK(kbo::launch_map_long_redo(la, d_ms, ts));
-        } else if (a.gitems && kbo::map_reads_applies(a)) { // (else no plan structures, or the copy is held off: two kernels)
+        if (!idx->sharded()) {
+            c = copy_view(idx, total_bases);
+            kbo::WalkArgs a = !long_seqs(v) && !v.chunk ? walk_args(v, c, d_ms, WalkAsk{}, &m) : kbo::WalkArgs{};
             a.host_bailed = c.plan ? c.plan->bailed : nullptr; // (set by redo_collect_kernel itself: no 8-byte copy behind the launch)
-            // kbo::find with max_gap_len = 0: the kernel counts the runs of the reads it finishes (their characters are in LDS anyway), so
-            // that format::run_lengths_gapped is one pass over the characters instead of two
-            uint32_t *rle_scratch = find ? static_cast<uint32_t *>(find->d_rle_work) : nullptr;
-            counted = find && find->max_gap_len == 0 && !format && !want_ms && kbo::map_reads_direct(a);
-            if (counted) a.run_counts = rle_scratch;
-            ts = map_reads_then(a, s, static_cast<hipStream_t>(tail_stream), [&](hipStream_t t) {
-                if (kbo::map_reads_finish_applies(a)) {
-                    // the reads the kernel listed, finished by one kernel: walk, derandomize + translate, characters (and their runs)
-                    HIP_OK(kbo::launch_map_reads_finish(a, t, urgent_tail && t != s));
-                } else {
-                    HIP_OK(kbo::launch_redo_pass(a, t)); // (redo_collect_kernel reads the offsets as well: no item list at all)
-                    HIP_OK(kbo::launch_derand_flagged(d_ms, d_offsets, n, idx->host.k, thr, format ? d_concat : nullptr, d_chars_out, a.redo,
-                                                      longest, t, counted ? rle_scratch : nullptr)); // (the flagged reads' run counts)
-                }
-            });
-            if (!a.host_bailed) plan_after_launch(a, ts, c.plan);
-        } else {
-            one_kernel = false;
-            walk_ms(idx, idx->sharded() ? nullptr : &c, w, d_concat, d_offsets, n_seqs, total_bases, longest, d_ms, nullptr, nullptr, d_work, s,
-                    nullptr);
+            route_map(v, c, a, m, ReadsLaunch{s, static_cast<hipStream_t>(tail_stream), urgent_tail, map_reads_then});
+        }
+        if (!m.done) {
+            walk_ms(idx, idx->sharded() ? nullptr : &c, w, v, d_work, WalkAsk{}, s);
             HIP_OK(kbo::launch_derand_translate(d_ms, d_offsets, n, idx->host.k, thr, format ? d_concat : nullptr, d_chars_out, nullptr, longest,
-                                                0xFFFFFFFFu, s, total_bases, w.derand_bytes ? work + w.derand_off : nullptr, w.derand_bytes));
+                                                0xFFFFFFFFu, s, total_bases, w.derand_bytes ? static_cast<uint8_t *>(d_work) + w.derand_off : nullptr, w.derand_bytes));
         }
         // the run lengths of the kernels' own characters: on the two-kernel route no run for a sequence of fewer than 3 bases, whose bytes
         // of d_chars_out it leaves unwritten (kbo_run_lengths_dev would count runs in whatever the caller's buffer held there)
-        if (find) run_lengths(*find, d_chars_out, d_offsets, n, longest, ts, true, counted);
+        if (find) run_lengths(*find, d_chars_out, d_offsets, n, longest, m.ts, true, m.counted);
         // kbo_summary_batch_dev's batches that do not take map_reads_kernel's summary form: the records off the characters, behind them
-        if (summary_of_chars) HIP_OK(kbo::launch_summary_bytes(d_chars_out, d_offsets, n, total_bases, summary_of_chars, ts));
-        if (fused) *fused = one_kernel ? 1 : 0;
+        if (summary_of_chars) HIP_OK(kbo::launch_summary_bytes(d_chars_out, d_offsets, n, total_bases, summary_of_chars, m.ts));
+        if (fused) *fused = m.done ? 1 : 0;
     });
 }
 } // namespace
@@ -688,18 +596,15 @@ int summary_batch_dev_impl(kbo_index_t *idx, const uint8_t *d_concat, const uint
             }
             return;
         }
-        const hipStream_t s = static_cast<hipStream_t>(stream);
         // (planned whatever the copy's hold-off says - summary_work: the route is the copy's and the batch's alone -, and a batch that
         // leaves most of its reads to the second pass still reports it: the character batches behind it honour the hold-off)
-        kbo::WalkArgs a = reads_args(c, w, d_work, d_concat, d_offsets, total_bases, (uint32_t)max_seq_len, nullptr, nullptr, (uint32_t)threshold,
-                                     false, false, true);
+        const BatchView v = batch_view(w, d_work, d_concat, d_offsets, n_seqs, total_bases, (uint32_t)max_seq_len, nullptr);
+        const FusedMap ask{nullptr, (uint32_t)threshold, false};
+        kbo::WalkArgs a = walk_args(v, CopyView{c.ix, nullptr}, nullptr, WalkAsk{}, &ask);
         a.summary_out = reinterpret_cast<uint4 *>(d_summary_out);
         KBO_REQUIRE(a.gitems && kbo::map_reads_applies(a) && kbo::map_reads_finish_applies(a), KBO_E_UNSUPPORTED, "the summary form of map_reads_kernel does not apply");
         a.host_bailed = c.plan ? c.plan->bailed : nullptr;
-        const hipStream_t ts = map_reads_then(a, s, static_cast<hipStream_t>(tail_stream), [&](hipStream_t t) {
-            HIP_OK(kbo::launch_map_reads_finish(a, t, urgent_tail && t != s));
-        });
-        if (!a.host_bailed) plan_after_launch(a, ts, c.plan);
+        run_reads(v, a, c.plan, ReadsLaunch{static_cast<hipStream_t>(stream), static_cast<hipStream_t>(tail_stream), urgent_tail, map_reads_then});
         if (fused) *fused = 1;
     });
     if (rc != KBO_OK || !generic) return rc;
@@ -1058,39 +963,33 @@ int kbo_matches_packed_dev(kbo_index_t *idx, const uint32_t *d_words, const uint
                     "kbo_matches_packed_dev: reads of at most 160 bases over an unsharded index (else: kbo_matches_batch_packed)");
         const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob);
         KBO_REQUIRE(threshold > 1, KBO_E_THRESHOLD_LE_1, "threshold > 1 (derandomize.rs:275)");
-        hipStream_t s = static_cast<hipStream_t>(stream), ts = static_cast<hipStream_t>(tail_stream);
+        hipStream_t s = static_cast<hipStream_t>(stream);
         const DevWork w = dev_work(n_seqs, total_bases, max_seq_len, idx->host.k, false);
         KBO_REQUIRE(!w.chunked, KBO_E_UNSUPPORTED, "reads only");
         KBO_REQUIRE(work_bytes >= w.bytes, KBO_E_BAD_ARG, "d_work is smaller than kbo_work_bytes() for this batch");
         const PackedScratch L = packed_scratch(n_seqs, total_bases);
         uint8_t *sc = static_cast<uint8_t *>(d_scratch);
-        uint8_t *q = sc + L.q, *ms = sc + L.ms, *chars = sc + L.chars, *exc = sc + L.exc;
         uint32_t *pscr = uniform_len ? nullptr : reinterpret_cast<uint32_t *>(sc + L.pscr);
-        const uint32_t wps = uniform_len ? (uint32_t)((uniform_len + 15) / 16) : 0u;
+        // (the second pass's bytes, MS values and characters go to the scratch; none of the batch's bytes is there before it)
+        BatchView v = batch_view(w, d_work, sc + L.q, d_offsets, n_seqs, total_bases, (uint32_t)max_seq_len, sc + L.ms);
+        v.bytes_out = sc + L.q;
+        v.have_bytes = false; // (and the number of words is not known here: this view takes run_reads alone)
+        v.qp = d_words;
+        v.wps = uniform_len ? (uint32_t)((uniform_len + 15) / 16) : 0u;
+        v.pscr = pscr;
+        v.exc_pos = d_exc_pos;
+        v.exc_byte = d_exc_byte;
+        v.n_exc = (uint32_t)n_exc;
+        v.exc_flag.p = sc + L.exc;
         const CopyView c = copy_view(idx, total_bases);
-        kbo::WalkArgs a = reads_args(c, w, d_work, q, d_offsets, total_bases, (uint32_t)max_seq_len, ms, chars, (uint32_t)threshold, false, false);
+        const FusedMap ask{sc + L.chars, (uint32_t)threshold, false};
+        kbo::WalkArgs a = walk_args(v, c, v.ms, WalkAsk{}, &ask);
         KBO_REQUIRE(a.gitems && kbo::map_reads_packed_applies(a, true), KBO_E_UNSUPPORTED,
                     "this copy of the index cannot take the packed-native kernel (no depth table, a held-off copy, a threshold below the "
                     "table's order): kbo_matches_batch_packed takes any batch");
         if (pscr) HIP_OK(kbo::launch_packed_prefix(d_offsets, (uint32_t)n_seqs, pscr, s));
-        a.qp = d_words;
-        a.qp_wps = wps;
-        a.qp_data = pscr;
-        a.qp_sums = pscr ? pscr + n_seqs + 1u : nullptr;
-        a.packed_out = d_words_out;
-        if (n_exc) {
-            HIP_OK(hipMemsetAsync(exc, 0, n_seqs, s));
-            HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, 0, d_offsets, (uint32_t)n_seqs, exc, s));
-            a.qp_exc = exc;
-        }
-        const hipStream_t done = map_reads_then(a, s, ts, [&](hipStream_t t) {
-            HIP_OK(kbo::launch_unpack_flagged(d_words, d_offsets, (uint32_t)n_seqs, wps, pscr, a.redo, q, t));
-            HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, 0, q, t));
-            HIP_OK(kbo::launch_redo_pass(a, t));
-            HIP_OK(kbo::launch_derand_flagged(ms, d_offsets, (uint32_t)n_seqs, idx->host.k, (uint32_t)threshold, nullptr, chars, a.redo, (uint32_t)max_seq_len, t));
-            HIP_OK(kbo::launch_pack_flagged(chars, d_offsets, (uint32_t)n_seqs, wps, pscr, a.redo, d_words_out, t));
-        });
-        plan_after_launch(a, done, c.plan);
+        packed_native_args(v, a, d_words_out, s);
+        run_reads(v, a, c.plan, ReadsLaunch{s, static_cast<hipStream_t>(tail_stream), false, map_reads_then});
     });
 }
 

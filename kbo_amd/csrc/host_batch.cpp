@@ -1,7 +1,7 @@
 // host_batch.cpp — host batches: work decomposition, slabs, pinned staging with helper threads, the
 // three-stage (upload / kernels / download) pipeline with pooled per-device scratch and one output
 // stage per mode.  No compute here: kernels live in the *_kernels.hip files.
-#include "capi_internal.hpp"
+#include "batch_route.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -110,48 +110,40 @@ struct PhaseClock {
 };
 
 
-// upload + A1 over a host batch (asynchronous on `stream`); leaves ms (and lo/hi) on the device.
-// `items_keep` must stay alive until the stream has been synchronised.
-void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                       bool want_ival, BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
-                       uint32_t longest, hipStream_t copy_stream, hipEvent_t copied, const CallSink *call, const PackedIn *packed, FusedMap *map,
-                       const HostStage *hs)
+// The upload of a host batch (on `copy_stream` where given, `stream` waiting for it) and what is made of it on the device: the
+// other strand, the offsets, the work items, a packed batch's scanned words.  Returns the queries, offsets and items of the batch's
+// view (batch_route.hpp); the bytes of a packed batch are unpacked only when a route needs them
+static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, BatchOnDevice &B,
+                                 std::vector<kbo::WalkItem> &items_keep, hipStream_t stream, uint32_t longest, hipStream_t copy_stream,
+                                 hipEvent_t copied, bool call, const PackedIn *packed, const HostStage *hs)
 {
-    KBO_REQUIRE(idx->host.k <= 255, KBO_E_UNSUPPORTED, "k > 255");
     // strands (HostStage): what is uploaded is the first n_up sequences' up_total bases; `rev` = a reverse complement is made of it
     const int strands = hs ? hs->strands : 1;
     const bool both = strands == 3, rev = (strands & 2) != 0;
-    KBO_REQUIRE(!both || n_seqs % 2 == 0, KBO_E_BAD_ARG, "both strands: a doubled slab");
     const size_t n_up = both ? n_seqs / 2 : n_seqs;
     const uint64_t up_total = both ? offsets[n_up] : offsets[n_seqs];
-    const int dev = current_device();
-    const std::vector<kbo_index *> shards = shards_of(idx); // (a sharded index: every shard is walked, the maximum kept)
-    KBO_REQUIRE(shards.size() == 1 || (!want_ival && !call), KBO_E_UNSUPPORTED,
-                "intervals and the call mode need the rows of one index; this handle is a sharded index");
-    const uint64_t total = offsets[n_seqs];
-    B.total = total;
+    BatchView v;
+    v.n_seqs = (uint32_t)n_seqs;
+    v.total = B.total = offsets[n_seqs];
     // reads (nothing to chunk): the item list is derived from the offsets on the device;
     // otherwise it is built here (chunks with k-1 warm-up bases) and uploaded
-    const uint64_t chunk = walk_chunk(total, n_seqs, idx->host.k);
-    const uint32_t longest_seq = longest ? longest : max_len(offsets, n_seqs);
-    const bool device_items = longest_seq <= chunk;
-    size_t n_items = n_seqs;
-    if (!device_items) {
-        make_items_host(offsets, n_seqs, idx->host.k, items_keep, call != nullptr);
-        n_items = items_keep.size();
-    }
+    v.longest = longest ? longest : max_len(offsets, n_seqs);
+    const uint64_t chunk = walk_chunk(v.total, n_seqs, idx->host.k);
+    if (v.longest > chunk) v.chunk = (uint32_t)chunk;
+    if (v.chunk) make_items_host(offsets, n_seqs, idx->host.k, items_keep, call);
+    const size_t n_items = v.chunk ? items_keep.size() : n_seqs;
     KBO_REQUIRE(n_items < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
-    KBO_REQUIRE(total < 0xFFFFFF00ull, KBO_E_UNSUPPORTED, "4 GiB or more of query in one launch");
+    KBO_REQUIRE(v.total < 0xFFFFFF00ull, KBO_E_UNSUPPORTED, "4 GiB or more of query in one launch");
+    v.n_items = (uint32_t)n_items;
 
-    const size_t padded = ((total + 15) / 16) * 16 + 16;
+    const size_t padded = ((v.total + 15) / 16) * 16 + 16;
     B.q.ensure(padded);
     B.off.ensure((n_seqs + 1) * sizeof(uint64_t));
     B.items.ensure(n_items * sizeof(kbo::WalkItem));
     B.ms.ensure(padded);
-    if (want_ival) {
-        B.lo.ensure(total * sizeof(uint32_t));
-        B.hi.ensure(total * sizeof(uint32_t));
-    }
+    v.q = v.bytes_out = B.q.as<uint8_t>();
+    v.offsets = B.off.as<uint64_t>();
+    v.items = B.items.as<kbo::WalkItem>();
     hipStream_t up = copy_stream ? copy_stream : stream;
     auto upload = [&](void *dst, const void *src, size_t n) {
         HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, up));
@@ -175,13 +167,13 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
         upload(strands == 2 ? B.raw.p : B.q.p, concat, up_total);
     }
     if (!uniform) upload(B.off.p, offsets, (n_up + 1) * sizeof(uint64_t));
-    if (!device_items) upload(B.items.p, items_keep.data(), items_keep.size() / (both ? 2 : 1) * sizeof(kbo::WalkItem));
+    if (v.chunk) upload(B.items.p, items_keep.data(), items_keep.size() / (both ? 2 : 1) * sizeof(kbo::WalkItem));
     if (copy_stream) {
         HIP_OK(hipEventRecord(copied, copy_stream));
         HIP_OK(hipStreamWaitEvent(stream, copied, 0));
     }
     if (both && !uniform) HIP_OK(kbo::launch_double_offsets(B.off.as<uint64_t>(), (uint32_t)n_up, stream));
-    if (both && !device_items) // (a sequence's chunks depend on its length alone: the second half's items are the first's, up_total on)
+    if (both && v.chunk) // (a sequence's chunks depend on its length alone: the second half's items are the first's, up_total on)
         HIP_OK(kbo::launch_double_items(B.items.as<kbo::WalkItem>(), (uint32_t)(items_keep.size() / 2), up_total, stream));
     if (packed) {
         if (uniform) HIP_OK(kbo::launch_uniform_offsets(B.off.as<uint64_t>(), (uint32_t)n_seqs, packed->uniform_len, stream));
@@ -190,15 +182,20 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
             HIP_OK(kbo::launch_packed_prefix(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.pscr.as<uint32_t>(), stream));
         }
     }
-    const uint32_t wps = uniform ? (packed->uniform_len + 15u) / 16u : 0u;
-    // what the kernels below see of a packed slab: its words and its list, with the '-' strand where asked for
-    const size_t n_words = (both ? 2 : 1) * up_words, n_exc = (both ? 2 : 1) * up_exc;
-    const uint64_t *d_exc_pos = B.exc_pos.as<uint64_t>() + (strands == 2 ? up_exc : 0);
-    const uint8_t *d_exc_byte = B.exc_byte.as<uint8_t>() + (strands == 2 ? up_exc : 0);
+    if (packed) { // what the kernels see of a packed slab: its words and its list, with the '-' strand where asked for
+        v.have_bytes = false;
+        v.qp = B.packed.as<uint32_t>();
+        v.n_words = (both ? 2 : 1) * up_words;
+        v.wps = uniform ? (packed->uniform_len + 15u) / 16u : 0u;
+        v.pscr = uniform ? nullptr : B.pscr.as<uint32_t>();
+        v.exc_pos = B.exc_pos.as<uint64_t>() + (strands == 2 ? up_exc : 0);
+        v.exc_byte = B.exc_byte.as<uint8_t>() + (strands == 2 ? up_exc : 0);
+        v.n_exc = (uint32_t)((both ? 2 : 1) * up_exc);
+        v.exc_base = packed->base;
+    }
     if (rev && packed) {
-        const uint32_t *pre = uniform ? nullptr : B.pscr.as<uint32_t>();
         HIP_OK(kbo::launch_revcomp_packed(strands == 2 ? B.raw.as<uint32_t>() : B.packed.as<uint32_t>(), (uint32_t)up_words, B.off.as<uint64_t>(),
-                                          (uint32_t)n_up, wps, pre, pre ? pre + n_seqs + 1u : nullptr,
+                                          (uint32_t)n_up, v.wps, v.pscr, v.pscr ? v.pscr + n_seqs + 1u : nullptr,
                                           B.packed.as<uint32_t>() + (both ? up_words : 0), stream));
         HIP_OK(kbo::launch_revcomp_exceptions(B.exc_pos.as<uint64_t>(), B.exc_byte.as<uint8_t>(), (uint32_t)up_exc, packed->base, B.off.as<uint64_t>(),
                                               (uint32_t)n_up, packed->base + (both ? up_total : 0), B.exc_pos.as<uint64_t>() + up_exc,
@@ -207,160 +204,38 @@ void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *of
         HIP_OK(kbo::launch_revcomp_bytes(strands == 2 ? B.raw.as<uint8_t>() : B.q.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_up, up_total,
                                          B.q.as<uint8_t>() + (both ? up_total : 0), stream));
     }
-    // the bytes of a packed batch: only when something needs them (the one kernel takes the words as they are)
-    bool have_bytes = !packed;
-    auto need_bytes = [&] {
-        if (have_bytes) return;
-        have_bytes = true;
-        HIP_OK(kbo::launch_unpack2(B.packed.as<uint32_t>(), (uint32_t)n_words, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps,
-                                   uniform ? nullptr : B.pscr.as<uint32_t>(), B.q.as<uint8_t>(), stream));
-        HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
-    };
-    static const int env_native = std::getenv("KBO_PACKED_NATIVE") ? std::atoi(std::getenv("KBO_PACKED_NATIVE")) : 1; // experiments
-    if (device_items) HIP_OK(kbo::launch_make_items(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.items.as<kbo::WalkItem>(), stream));
-    for (size_t sh = 0; sh < shards.size(); sh++) {
-        DevCopy::PlanState *plan_state = nullptr;
-        const kbo::DevIndexView view = device_view(shards[sh], dev, &plan_state, total);
-        if (sh > 0) B.ms_shard.ensure(padded);
-        kbo::WalkArgs a{};
-        a.ix = view;
-        a.q = B.q.as<uint8_t>();
-        a.q_bytes = total;
-        a.items = B.items.as<kbo::WalkItem>();
-        a.n_items = (uint32_t)n_items;
-        a.rounds = 0;
-        a.d_out = sh == 0 ? B.ms.as<uint8_t>() : B.ms_shard.as<uint8_t>();
-        a.lo_out = want_ival ? B.lo.as<uint32_t>() : nullptr;
-        a.hi_out = want_ival ? B.hi.as<uint32_t>() : nullptr;
-        a.call_sites = call ? static_cast<uint4 *>(call->d_sites) : nullptr;
-        a.call_counts = call ? call->d_counts : nullptr;
-        a.call_cap = call ? call->cap_per_list : 0;
-        a.call_thr = call ? call->threshold : 0;
-        // (no item is longer than this: chunk + k - 1 warm-up bases; call mode: k warm-up + up to k borrowed bases)
-        a.max_item_len = device_items ? longest_seq : (uint32_t)std::min<uint64_t>(chunk + (call ? 2ull * idx->host.k : idx->host.k), 0xFFFFFFFFu);
-        if (view.pc_text && !want_ival) B.plan.ensure(kbo::plan_work_bytes(n_items, total));
-        attach_plan(a, view.pc_text && !want_ival ? B.plan.p : nullptr, plan_state);
-        if (map && shards.size() == 1 && device_items && !call) { // kbo::matches / map over reads: the one kernel where it applies
-            a.chars_out = map->d_chars;
-            a.map_thr = map->threshold;
-            a.map_fmt = map->format ? 1u : 0u;
-            a.map_want_ms = 0;
-            // kbo_summary_batch[_packed]: the kernel's summary form - reads as bytes, or (packed-native, direct form) as words - and
-            // finish_reads_kernel's behind it, over the bytes of the reads the kernel listed: records, no characters, no MS values
-            if (map->d_summary && !map->format && a.gitems && !a.pstats) {
-                kbo::WalkArgs sa = a;
-                sa.chars_out = nullptr;
-                sa.d_out = nullptr;
-                sa.summary_out = map->d_summary;
-                const bool native = packed && env_native && kbo::map_reads_packed_applies(sa, false);
-                if (native) {
-                    sa.qp = B.packed.as<uint32_t>();
-                    sa.qp_wps = wps;
-                    sa.qp_data = uniform ? nullptr : B.pscr.as<uint32_t>();
-                    sa.qp_sums = uniform ? nullptr : B.pscr.as<uint32_t>() + n_seqs + 1u;
-                    if (n_exc) {
-                        B.exc_flag.ensure(n_seqs + 16);
-                        HIP_OK(hipMemsetAsync(B.exc_flag.p, 0, n_seqs, stream));
-                        HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, packed->base, B.off.as<uint64_t>(),
-                                                           (uint32_t)n_seqs, B.exc_flag.as<uint8_t>(), stream));
-                        sa.qp_exc = B.exc_flag.as<uint8_t>();
-                    }
-                } else {
-                    need_bytes();
-                }
-                kbo::WalkArgs fa = sa; // (the second pass reads bytes: those of the listed reads are unpacked for it)
-                fa.qp = nullptr;
-                fa.seq_off = B.off.as<uint64_t>();
-                if (kbo::map_reads_applies(sa) && kbo::map_reads_finish_applies(fa)) {
-                    HIP_OK(kbo::launch_map_reads(sa, stream));
-                    if (native) {
-                        HIP_OK(kbo::launch_unpack_flagged(sa.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, sa.qp_data, sa.redo, B.q.as<uint8_t>(), stream));
-                        HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
-                    }
-                    fa = sa;
-                    fa.qp = nullptr;
-                    fa.seq_off = B.off.as<uint64_t>();
-                    HIP_OK(kbo::launch_map_reads_finish(fa, stream));
-                    plan_after_launch(sa, stream, plan_state);
-                    map->done = map->summarized = true;
-                    return;
-                }
-            }
-            if (packed && env_native && a.gitems && kbo::map_reads_packed_applies(a, map->d_packed_out != nullptr)) {
-                // packed-native: the words go into the kernel as they are and (kbo_matches_batch_packed) the characters leave it
-                // as words; only the reads it leaves to the plain walk get their bytes, and their characters are packed behind it
-                a.qp = B.packed.as<uint32_t>();
-                a.qp_wps = wps;
-                a.qp_data = uniform ? nullptr : B.pscr.as<uint32_t>();
-                a.qp_sums = uniform ? nullptr : B.pscr.as<uint32_t>() + n_seqs + 1u;
-                a.packed_out = map->d_packed_out;
-                if (n_exc) {
-                    B.exc_flag.ensure(n_seqs + 16);
-                    HIP_OK(hipMemsetAsync(B.exc_flag.p, 0, n_seqs, stream));
-                    HIP_OK(kbo::launch_flag_exceptions(d_exc_pos, (uint32_t)n_exc, packed->base, B.off.as<uint64_t>(),
-                                                       (uint32_t)n_seqs, B.exc_flag.as<uint8_t>(), stream));
-                    a.qp_exc = B.exc_flag.as<uint8_t>();
-                }
-                const bool count_runs = map->run_counts && !map->format && !map->d_packed_out;
-                if (count_runs) a.run_counts = map->run_counts;
-                HIP_OK(kbo::launch_map_reads(a, stream));
-                HIP_OK(kbo::launch_unpack_flagged(a.qp, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, B.q.as<uint8_t>(), stream));
-                HIP_OK(kbo::launch_exceptions(d_exc_pos, d_exc_byte, (uint32_t)n_exc, packed->base, B.q.as<uint8_t>(), stream));
-                HIP_OK(kbo::launch_redo_pass(a, stream));
-                HIP_OK(kbo::launch_derand_flagged(B.ms.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, idx->host.k, map->threshold,
-                                                  map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, stream,
-                                                  count_runs ? map->run_counts : nullptr));
-                if (map->d_packed_out) {
-                    HIP_OK(kbo::launch_pack_flagged(map->d_chars, B.off.as<uint64_t>(), (uint32_t)n_seqs, wps, a.qp_data, a.redo, map->d_packed_out, stream));
-                    map->packed_done = true;
-                }
-                if (count_runs) map->counted = true;
-                plan_after_launch(a, stream, plan_state);
-                map->done = true;
-                return;
-            }
-            need_bytes();
-            if (a.gitems && kbo::map_reads_applies(a)) {
-                const bool count_runs = map->run_counts && !map->format && kbo::map_reads_direct(a);
-                if (count_runs) a.run_counts = map->run_counts;
-                HIP_OK(kbo::launch_map_reads(a, stream));
-                a.seq_off = B.off.as<uint64_t>(); // (item s is sequence s, whole: finish_reads_kernel reads the offsets)
-                if (kbo::map_reads_finish_applies(a)) {
-                    HIP_OK(kbo::launch_map_reads_finish(a, stream)); // the reads the kernel listed: walk, derandomize + translate, characters, runs
-                } else {
-                    a.seq_off = nullptr;
-                    HIP_OK(kbo::launch_redo_pass(a, stream));
-                    HIP_OK(kbo::launch_derand_flagged(B.ms.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, idx->host.k, map->threshold,
-                                                      map->format ? B.q.as<uint8_t>() : nullptr, map->d_chars, a.redo, longest_seq, stream,
-                                                      count_runs ? map->run_counts : nullptr)); // (the flagged reads' runs counted on the way)
-                }
-                if (count_runs) map->counted = true;
-                plan_after_launch(a, stream, plan_state);
-                map->done = true;
-                return;
-            }
-        }
-        if (map && shards.size() == 1 && !call && !want_ival && longest_seq > 160u && kbo::map_long_applies(view, map->threshold)) {
-            // kbo::matches / map / find over sequences of more than 160 bases - contigs, whole reference sequences, long reads:
-            // one wave per piece of a sequence (long_kernels.hip), its flagged pieces by the plain walk + the literal recurrences
-            const size_t wb = kbo::long_work_bytes(n_seqs, total, idx->host.k);
-            if (wb) {
-                need_bytes();
-                B.longw.ensure(wb);
-                kbo::LongArgs la{};
-                HIP_OK(kbo::launch_map_long(view, B.q.as<uint8_t>(), B.off.as<uint64_t>(), (uint32_t)n_seqs, total, map->threshold, map->format,
-                                            map->d_chars, B.longw.p, stream, la, g_plan_stats.load()));
-                HIP_OK(kbo::launch_map_long_redo(la, B.ms.as<uint8_t>(), stream));
-                map->done = true;
-                return;
-            }
-        }
-        need_bytes();
-        HIP_OK(kbo::launch_ms_walk(a, walk_max_waves(), stream));
-        plan_after_launch(a, stream, plan_state);
-        // the depth against the union of the shards is the maximum of the depths against each (capi_internal.hpp)
-        if (sh > 0) HIP_OK(kbo::launch_max_bytes(B.ms.as<uint8_t>(), B.ms_shard.as<uint8_t>(), total, stream));
-    }
+    if (!v.chunk) HIP_OK(kbo::launch_make_items(B.off.as<uint64_t>(), (uint32_t)n_seqs, B.items.as<kbo::WalkItem>(), stream));
+    return v;
+}
+
+// upload + A1 over a host batch (asynchronous on `stream`); leaves ms (and lo/hi) on the device.
+// `items_keep` must stay alive until the stream has been synchronised.
+void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                       bool want_ival, BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
+                       uint32_t longest, hipStream_t copy_stream, hipEvent_t copied, const CallSink *call, const PackedIn *packed, FusedMap *map,
+                       const HostStage *hs)
+{
+    KBO_REQUIRE(idx->host.k <= 255, KBO_E_UNSUPPORTED, "k > 255");
+    KBO_REQUIRE(!hs || hs->strands != 3 || n_seqs % 2 == 0, KBO_E_BAD_ARG, "both strands: a doubled slab");
+    const std::vector<kbo_index *> shards = shards_of(idx);
+    KBO_REQUIRE(shards.size() == 1 || (!want_ival && !call), KBO_E_UNSUPPORTED,
+                "intervals and the call mode need the rows of one index; this handle is a sharded index");
+    BatchView v = stage_walk_host(idx, concat, offsets, n_seqs, B, items_keep, stream, longest, copy_stream, copied, call != nullptr, packed, hs);
+    // the slab's own buffers for what the routes leave or need on the way; those not every route takes grow when one does
+    for (DevBuf *b : {&B.lo, &B.hi})
+        if (want_ival) b->ensure(v.total * sizeof(uint32_t));
+    if (shards.size() > 1) B.ms_shard.ensure(((v.total + 15) / 16) * 16 + 16);
+    v.exc_flag.grow = &B.exc_flag;
+    v.plan.grow = &B.plan;
+    v.ms = B.ms.as<uint8_t>();
+    v.ms_shard = B.ms_shard.as<uint8_t>();
+    v.long_work.grow = &B.longw;
+    const WalkAsk wask{want_ival ? B.lo.as<uint32_t>() : nullptr, want_ival ? B.hi.as<uint32_t>() : nullptr, call};
+    if (shards.size() > 1) return walk_shards(v, idx, nullptr, wask, stream); // (every shard is walked, the maximum kept)
+    const CopyView c = copy_view(shards[0], v.total);
+    kbo::WalkArgs a = walk_args(v, c, v.ms, wask, !v.chunk && !call ? map : nullptr);
+    if (map && !call && !want_ival) route_map(v, c, a, *map, ReadsLaunch{stream, stream}); // kbo::matches / map: the one kernel where it applies
+    if (!map || !map->done) walk_shards(v, idx, &c, wask, stream, &a); // (A1 alone: the caller runs A5 / A6)
 }
 
 void run_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
