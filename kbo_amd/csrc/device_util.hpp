@@ -31,6 +31,12 @@ __device__ __forceinline__ void st16u(uint8_t *base, uint32_t byte_off, const ui
     __builtin_memcpy(base + byte_off, &v, 16);
 #endif
 }
+// the load to match: 16 bytes at any byte address that are read ONCE (a batch's bases), marked as the first to leave the caches again
+__device__ __forceinline__ uint4 ld16u_nt(const uint8_t *base, uint32_t byte_off)
+{
+    const u32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(base + byte_off));
+    return make_uint4(t.x, t.y, t.z, t.w);
+}
 __device__ __forceinline__ void st4u(uint8_t *p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 
 // store the first nb (1..15) bytes of a 16-byte block: whole words, then the trailing bytes

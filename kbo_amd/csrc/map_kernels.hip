@@ -7,7 +7,7 @@
 //
 //   map_reads_kernel   0. the wave's stretch of the query buffer (its 64 reads lie back to back) is loaded once, in whole
 //                         lines, and turned into 2-bit digits on the way into LDS (a quarter of the bytes; a byte that is no
-//                         base sends its read to the plain walk);
+//                         base sends its read to the plain walk); streaming loads: a batch's bases are read once;
 //                      1. seed: the first D bases of a read - D = what a seed must be deep, log4(rows) + 3 - are looked up in
 //                         a table of text positions (DevIndexView::seed_pos): one load gives the read's diagonal of the
 //                         path-cover text (plan_kernels.hip has the idea; there it took a table of intervals and a second,
@@ -25,7 +25,7 @@
 //                         bytes by the lane that resolved the mismatch;
 //                      4. derandomize + translate, right to left, one lane per read, in place over those bytes;
 //                      5. the characters leave in whole lines, relative_to_ref applied on the way out (the bases come from the
-//                         2-bit copy).
+//                         2-bit copy), whole 16-byte blocks as streaming stores (the wave's first and last block byte by byte).
 //                      (direct form, round 5: a window that is in the index and that neither the anchors nor its place settle is
 //                      asked of the windows AROUND it - six entries, judged at the kernel's end; a diagonal on which every third
 //                      base mismatches is a chance seed, and its read is judged like one without a seed.)
@@ -303,7 +303,9 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         for (uint32_t u = 0; u < kStageUnroll; u++) {
             const uint32_t c = c00 + 64u * u + lane;
             vv[u] = make_uint4(0, 0, 0, 0);
-            if (c < nblk) vv[u] = ld16u(qb, base16 + 16u * c); // (reads <= 15 bytes past the last read)
+            // (reads <= 15 bytes past the last read.  A streaming load: the batch's bases are read once, and as plain loads their 150 MB
+            // pushed the 2-bit text and the filter, which every wave comes back to, out of the L2 - LABNOTES round 7)
+            if (c < nblk) vv[u] = ld16u_nt(qb, base16 + 16u * c);
         }
 #pragma unroll
         for (uint32_t u = 0; u < kStageUnroll; u++) {
@@ -376,7 +378,9 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     const uint32_t dmask = D >= 16u ? 0xFFFFFFFFu : ((1u << (2u * D)) - 1u);
     auto seed_at = [&](uint32_t e_) -> uint32_t { // text position of the base e_ of the read by the window that ends there, or ~0
         const uint64_t win = ending_at(soff + e_);
-        if (!by_anchor) return a.ix.seed_pos[(uint32_t)win & dmask];
+        // (a streaming load: 4^D entries, a gigabyte at D = 14 - no line of it is asked for twice while it is cached, and each one it
+        // leaves in the L2 is one of the text's or the filter's less)
+        if (!by_anchor) return __builtin_nontemporal_load(a.ix.seed_pos + ((uint32_t)win & dmask));
         const uint64_t key = win & ((1ull << (2u * D)) - 1ull), amask = ((uint64_t)1 << a.ix.anchor_bits) - 1ull;
         uint64_t h = (key * 0x9E3779B97F4A7C15ull) >> (64u - a.ix.anchor_bits);
         const uint32_t tag = (uint32_t)key + 1u;
@@ -1176,8 +1180,10 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
             v.y = four((w_ >> 8) & 0xFFu, (dg >> 16) & 0xFFu);
             v.z = four((w_ >> 16) & 0xFFu, (dg >> 8) & 0xFFu);
             v.w = four(w_ >> 24, dg & 0xFFu);
+            // (whole blocks as streaming stores: nothing on the device reads the characters back before the kernel ends, and the lines
+            // they would take in the L2 are the text's and the filter's)
             const uint32_t g0 = base16 + 16u * c;
-            if (g0 >= lo && g0 + 16u <= wave_hi) __builtin_memcpy(a.chars_out + g0, &v, 16);
+            if (g0 >= lo && g0 + 16u <= wave_hi) st16u(a.chars_out, g0, v);
             else st_range16(a.chars_out + g0, v, lo > g0 ? min(lo - g0, 16u) : 0u, min(wave_hi - g0, 16u));
         }
     } else if (a.chars_out != nullptr)
