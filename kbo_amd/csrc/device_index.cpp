@@ -1,6 +1,7 @@
 // device_index.cpp — the per-device copies of an index handle (rank blocks, contraction entries,
 // two-base blocks) and the knobs that shape them.
 #include "capi_internal.hpp"
+#include "map_text.hpp"
 
 #include <cmath>
 
@@ -312,13 +313,23 @@ void build_plan_structures(kbo_index *idx, DevCopy *dc)
         t0 = clk::now();
         const uint64_t units = kbo::pack_text_units(idx->host.n_sets);
         dc->pc_tm.alloc(units * 8 + 64);
-        HIP_OK(kbo::launch_pack_text(dc->pc_text.as<uint8_t>(), pc.text.size(), dc->pc_tm.as<uint2>(), units, bs));
+        // ... and the digits alone with a bit per unit that says whether it has a mark: what the kernel's common path reads, half the
+        // bytes.  Their slack (a window's last 16-byte load, the four bytes of summary bits from any unit on) reads as no digits / all
+        // marked; pc_tm's slack is never read
+        const uint64_t mu_bytes = kbo::pack_text_mu_bytes(units);
+        dc->pc_t.alloc(units * 4 + 64);
+        dc->pc_mu.alloc(mu_bytes + 64);
+        dc->pc_mc.alloc(kbo::maptext::kCells / 8u);
+        HIP_OK(hipMemsetAsync(dc->pc_t.as<uint8_t>() + units * 4, 0, 64, bs));
+        HIP_OK(hipMemsetAsync(dc->pc_mu.as<uint8_t>() + mu_bytes, 0xFF, 64, bs));
+        HIP_OK(kbo::launch_pack_text(dc->pc_text.as<uint8_t>(), pc.text.size(), dc->pc_tm.as<uint2>(), dc->pc_t.as<uint32_t>(), dc->pc_mu.as<uint32_t>(), dc->pc_mc.as<uint32_t>(), units,
+                                     bs));
         dc->seed_pos.alloc(((size_t)4 << (2u * dc->seed_d)) + 64);
         HIP_OK(kbo::launch_seed_pos(dc->seed_tab.as<uint2>(), dc->pc_pos.as<uint32_t>(), dc->seed_pos.as<uint32_t>(), dc->seed_d, bs));
         HIP_OK(hipStreamSynchronize(bs));
-        dc->setup.cover_bytes += units * 8;
+        dc->setup.cover_bytes += units * 12 + mu_bytes + kbo::maptext::kCells / 8u;
         dc->setup.seed_bytes += (uint64_t)4 << (2u * dc->seed_d);
-        idx->plan_bytes += units * 8 + ((size_t)4 << (2u * dc->seed_d));
+        idx->plan_bytes += units * 12 + mu_bytes + kbo::maptext::kCells / 8u + ((size_t)4 << (2u * dc->seed_d));
         dc->setup.seed_s += since(t0);
     }
     dc->plan_built = true;
@@ -461,7 +472,7 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
                 // table's depth without its table, a text without its positions - must not reach a launch), the copy is marked so
                 // that the build is not paid again by every later call, and it walks plainly - with the same results.  An explicit
                 // kbo_index_to_device still reports the failure.
-                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->seed_pos})
+                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->pc_t, &dc->pc_mu, &dc->pc_mc, &dc->seed_pos})
                     b->release();
                 dc->seed_d = dc->dtab_order = dc->anchor_bits = dc->dfilt_bases = 0;
                 dc->dtab_grouped = false;
@@ -502,6 +513,10 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
     v.fat_null = dc->fat_null;
     v.pc_node = dc->pc_node.as<uint32_t>();
     v.pc_tm = (use_tab && dc->pc_tm.p) ? dc->pc_tm.as<uint2>() : nullptr;
+    v.pc_t = (v.pc_tm && dc->pc_t.p && dc->pc_mu.p && dc->pc_mc.p) ? dc->pc_t.as<uint32_t>() : nullptr;
+    v.pc_mu = v.pc_t ? dc->pc_mu.as<uint8_t>() : nullptr;
+    v.pc_mc = v.pc_t ? dc->pc_mc.as<uint32_t>() : nullptr;
+    v.pc_mc_shift = kbo::maptext::cell_shift(kbo::pack_text_units(idx->host.n_sets));
     v.dfilt = (use_tab && dc->dfilt_bases) ? dc->dfilt.as<uint32_t>() : nullptr;
     v.dfilt_bases = v.dfilt ? dc->dfilt_bases : 0u;
     v.seed_pos = (use_tab && dc->seed_pos.p) ? dc->seed_pos.as<uint32_t>() : nullptr;

@@ -48,6 +48,13 @@ struct DevIndexView {
     // whose k-mer ends with them, 0xFFFFFFFF when there is none
     const uint2 *pc_tm;
     const uint32_t *seed_pos;
+    // the same text without its marks, which is what map_reads_kernel's common path reads (map_text.hpp): pc_t[u] = pc_tm[u].x, and
+    // pc_mu = one bit per unit, set where pc_tm[u].y != 0 (and behind the last unit) - half the bytes of pc_tm and 1 / 256 of them
+    // pc_mc: maptext::kCells bits, bit c set where a window that starts in cell c - 2^pc_mc_shift units - can see a marked unit
+    const uint32_t *pc_t;
+    const uint8_t *pc_mu;
+    const uint32_t *pc_mc;
+    uint32_t pc_mc_shift;
     // ... and its filter in front of the depth table (small indexes): bit [key of dfilt_bases bases] set where that string is a
     // suffix of a row - 4^dfilt_bases / 8 bytes (2 MB for 12 bases: stays in L2), nullptr when the copy has none
     const uint32_t *dfilt;
@@ -219,10 +226,14 @@ hipError_t launch_dtab_resolve(const WalkArgs &a, hipStream_t stream);
 // ---- kbo::map / matches for a batch of reads in one launch (map_kernels.hip)
 // the 2-bit text with its path-start marks from the padded byte text (n_bytes = kPlanPad + n_sets + kPlanPad), n_units of
 // 16 positions; the text positions of the seed table's intervals
-hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint2 *d_out, uint64_t n_units, hipStream_t stream);
+// (d_t: n_units words; d_mu: pack_text_mu_bytes(n_units) bytes, all of them written, and 4 bytes behind them readable; d_mc:
+// maptext::kCells bits, cells of 2^maptext::cell_shift(n_units) units)
+hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint2 *d_out, uint32_t *d_t, uint32_t *d_mu, uint32_t *d_mc, uint64_t n_units,
+                            hipStream_t stream);
 // (a read's diagonal may start up to 160 bases in front of the text - it is seeded from its last bases too - and end 176 behind it)
 constexpr uint32_t kMapPad = 192;
 inline uint64_t pack_text_units(uint64_t n_sets) { return (n_sets + kMapPad + 256u) / 16u + 2u; }
+inline uint64_t pack_text_mu_bytes(uint64_t n_units) { return (n_units + 255u) / 256u * 32u; } // (a bit per unit, whole workgroups of pack_text_kernel)
 hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, uint32_t *d_out, uint32_t seed_d, hipStream_t stream);
 // true when the launch described by `a` (plan work attached, chars_out set) can take map_reads_kernel: reads of at most 160
 // bases, MS values / characters only, an index copy with a depth table, the 2-bit text and the position table

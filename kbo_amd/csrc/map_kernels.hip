@@ -12,8 +12,9 @@
 //                         a table of text positions (DevIndexView::seed_pos): one load gives the read's diagonal of the
 //                         path-cover text (plan_kernels.hip has the idea; there it took a table of intervals and a second,
 //                         dependent load of the row's position);
-//                      2. compare: 16 bases per XOR against the 2-bit text (DevIndexView::pc_tm: text and path-start marks
-//                         interleaved, 0.5 B per row: 2.5 MB on a 5 Mbp index, L2-resident where the byte text was not);
+//                      2. compare: 16 bases per XOR against the 2-bit text (DevIndexView::pc_t: 0.25 B per row, 1.25 MB on a 5 Mbp
+//                         index, which an XCD's L2 keeps next to the filter; the path-start marks come from pc_tm only for a window
+//                         that pc_mu says has one - map_text.hpp);
 //                      2b. (direct form) a read that leaves its diagonal - an insertion, a deletion, a chimera, a first seed that
 //                         sat elsewhere - gets a SECOND diagonal seeded from its last bases and is cut where the two together
 //                         mismatch least, behind the stretch both match (the cut is a break like a mismatch, with the second
@@ -36,10 +37,11 @@
 //   (IO = 1, 2)        packed-native: the reads come as 2-bit words (kbo_matches_batch_packed's layout) and go into the digit
 //                      string as they are; with IO = 2 the characters leave as 2-bit words as well.
 //
-//   pack_text_kernel / seed_pos_kernel   build pc_tm and seed_pos on the device from the byte text and the interval table.
+//   pack_text_kernel / seed_pos_kernel   build pc_tm (with pc_t, pc_mu) and seed_pos on the device from the byte text and the interval table.
 //
 // Integer / byte work only: no MFMA.  One 64-lane wave per workgroup (the LDS of a CU then holds twelve of them).
 #include "device_util.hpp"
+#include "map_text.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -80,24 +82,35 @@ __device__ __forceinline__ uint32_t spread_marks(uint32_t x)
 // pc_tm[u] = { 2-bit digits of text positions [16 u - kMapPad, 16 u - kMapPad + 16), first one most significant;
 //              01 at every position that matches nothing: a path start, the padding, in front of / beyond the text }
 // (text_padded holds positions -kPlanPad .. : kMapPad - kPlanPad is a multiple of 16)
+// out_t[u] = the digits alone; out_mu: bit u set where unit u has a mark, and for every unit behind the last up to the grid's end
+// (map_text.hpp: the split layout)
 __global__ __launch_bounds__(256) void pack_text_kernel(const uint8_t *__restrict__ text_padded, uint64_t n_bytes, uint2 *__restrict__ out,
-                                                        uint64_t n_units)
+                                                        uint32_t *__restrict__ out_t, uint32_t *__restrict__ out_mu, uint64_t n_units)
 {
     static_assert(kMapPad >= kPlanPad && (kMapPad - kPlanPad) % 16u == 0, "padding of the 2-bit text");
     const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_units) return;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    const uint64_t b = 16ull * u - (kMapPad - kPlanPad); // (wraps for the units in front of the byte text: they stay all marks)
-    if (16ull * u < kMapPad - kPlanPad) {
-    } else if (b + 16u <= n_bytes) v = *reinterpret_cast<const uint4 *>(text_padded + b);
-    else if (b < n_bytes) {
-        uint8_t tmp[16];
-        for (uint32_t t = 0; t < 16; t++) tmp[t] = b + t < n_bytes ? text_padded[b + t] : (uint8_t)0;
-        __builtin_memcpy(&v, tmp, 16);
+    uint32_t marks = 0x55555555u;
+    if (u < n_units) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        const uint64_t b = 16ull * u - (kMapPad - kPlanPad); // (wraps for the units in front of the byte text: they stay all marks)
+        if (16ull * u < kMapPad - kPlanPad) {
+        } else if (b + 16u <= n_bytes) v = *reinterpret_cast<const uint4 *>(text_padded + b);
+        else if (b < n_bytes) {
+            uint8_t tmp[16];
+            for (uint32_t t = 0; t < 16; t++) tmp[t] = b + t < n_bytes ? text_padded[b + t] : (uint8_t)0;
+            __builtin_memcpy(&v, tmp, 16);
+        }
+        uint32_t code, valid;
+        pack16(v, code, valid);
+        marks = spread_marks(~valid & 0xFFFFu);
+        out[u] = make_uint2(code, marks);
+        out_t[u] = code;
     }
-    uint32_t code, valid;
-    pack16(v, code, valid);
-    out[u] = make_uint2(code, spread_marks(~valid & 0xFFFFu));
+    const uint64_t any = __ballot(marks != 0u); // (a wave's 64 units: two words of the summary)
+    if ((threadIdx.x & 63u) == 0u) {
+        out_mu[u >> 5] = (uint32_t)any;
+        out_mu[(u >> 5) + 1u] = (uint32_t)(any >> 32);
+    }
 }
 
 __global__ __launch_bounds__(256) void seed_pos_kernel(const uint2 *__restrict__ seed_tab, const uint32_t *__restrict__ pc_pos,
@@ -111,8 +124,51 @@ __global__ __launch_bounds__(256) void seed_pos_kernel(const uint2 *__restrict__
     out[w] = iv.x < iv.y ? (pc_pos[iv.x] | (iv.y - iv.x > 1u ? 0x80000000u : 0u)) : 0xFFFFFFFFu;
 }
 
+// map_text.hpp's accessors over the index copy's arrays: plain loads (the hot set, which every wave comes back to)
+struct TextDigits {
+    const uint32_t *p;
+    __device__ __forceinline__ void quad(uint64_t u, uint32_t (&d)[4]) const
+    {
+        uint4 v;
+        __builtin_memcpy(&v, p + u, 16);
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+        d[3] = v.w;
+    }
+    __device__ __forceinline__ uint32_t word(uint64_t u) const { return p[u]; }
+};
+struct TextMarkBits {
+    const uint8_t *p;
+    __device__ __forceinline__ uint32_t from(uint64_t u) const
+    {
+        uint32_t w;
+        __builtin_memcpy(&w, p + (u >> 3), 4);
+        return w >> (uint32_t)(u & 7u);
+    }
+};
+struct TextUnits {
+    const uint2 *p;
+    __device__ __forceinline__ uint32_t marks(uint64_t u) const { return p[u].y; }
+};
+struct WaveAny {
+    __device__ __forceinline__ bool operator()(bool b) const { return __ballot(b) != 0; }
+};
+
+// the coarse summary of the marks (map_text.hpp): a thread per cell
+__global__ __launch_bounds__(64) void mark_cells_kernel(const uint8_t *__restrict__ mu, uint32_t *__restrict__ out, uint32_t shift, uint64_t n_units)
+{
+    const uint32_t c = blockIdx.x * 64u + threadIdx.x;
+    const uint64_t any = __ballot(maptext::cell_marked(TextMarkBits{mu}, c, shift, n_units));
+    if (threadIdx.x == 0u) {
+        out[c >> 5] = (uint32_t)any;
+        out[(c >> 5) + 1u] = (uint32_t)(any >> 32);
+    }
+}
+
 __device__ __forceinline__ bool thr_gt(uint32_t thr, uint32_t order) { return thr > order; } // (windows order .. thr apart exist)
 constexpr uint32_t kMapWords = 10;       // 16-base words per read: reads of up to 160 bases
+static_assert(kMapWords == maptext::kWords, "map_text.hpp's window is a read's");
 // experiments of earlier rounds (KBO_MAP_X bits 0 - 4: ambiguous seeds as they come, a second filter stretch, half-window seed
 // retries, no search beside the diagonal, no look at the window one base on): compiled in only with -DKBO_MAP_EXPERIMENTS - the second
 // filter stretch alone is two more words per window live through the proof's loop.  Bits 5 and 6 (this round's rules off) stay: they sit
@@ -392,6 +448,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         }
         return 0xFFFFFFFFu;
     };
+    const uint32_t mark_cells = a.ix.pc_mc[lane]; // (the coarse summary of the text's marks: near_mark below)
     const uint32_t jmax = min(len, cap);
     uint32_t e = D - 1u, p0 = 0, st_lookups = 0, p_amb = 0;
     bool seeded = false, have_amb = false;
@@ -423,36 +480,19 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
 
     // ---- 2. compare with the text on the diagonal: mm[g] has bit 2 (15 - j) set where base 16 g + j differs from the text (or the
     // text has a mark there: a path start, the padding)
-    auto compare = [&](uint32_t pd, uint32_t (&mm)[kMapWords]) -> uint32_t {
-        const uint32_t q0 = pd + kMapPad, r = q0 & 15u;
-        const uint8_t *tp = reinterpret_cast<const uint8_t *>(a.ix.pc_tm) + (size_t)(q0 >> 4) * 8u;
-        uint4 L[6];
-#pragma unroll
-        for (int i = 0; i < 6; i++) __builtin_memcpy(&L[i], tp + 16 * i, 16);
-        uint32_t T[12], M[12];
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-            T[2 * i] = L[i].x;
-            M[2 * i] = L[i].y;
-            T[2 * i + 1] = L[i].z;
-            M[2 * i + 1] = L[i].w;
-        }
-        uint32_t c = 0;
-#pragma unroll
-        for (uint32_t g = 0; g < kMapWords; g++) {
-            mm[g] = 0;
-            if (16u * g < len) {
-                const uint32_t tw = (uint32_t)((((uint64_t)T[g] << 32) | T[g + 1]) >> (32u - 2u * r));
-                const uint32_t mk = (uint32_t)((((uint64_t)M[g] << 32) | M[g + 1]) >> (32u - 2u * r));
-                const uint32_t x = qw[g] ^ tw;
-                uint32_t m1 = (x | (x >> 1) | mk) & 0x55555555u;
-                const uint32_t nb = len - 16u * g;
-                if (nb < 16u) m1 &= ~0u << (32u - 2u * nb);
-                mm[g] = m1;
-                c += (uint32_t)__popc(m1);
-            }
-        }
-        return c;
+    // The text comes without its marks (pc_t: 48 bytes a window, three loads).  Whether a mark is in sight the wave knows without a
+    // load: the coarse summary, a word a lane (mark_cells above).  Only a window near a path start or the padding asks pc_mu which
+    // of its units have marks, and takes those from pc_tm (map_text.hpp).
+    // near_mark is a shuffle: EVERY lane of the wave calls it - outside the `if` on the lanes that compare
+    const TextDigits text_d{a.ix.pc_t};
+    const TextMarkBits text_mu{a.ix.pc_mu};
+    const TextUnits text_tm{a.ix.pc_tm};
+    auto near_mark = [&](uint32_t q) -> bool { // q: pd + kMapPad of a window
+        const uint32_t c = maptext::cell_of(q >> 4, a.ix.pc_mc_shift);
+        return (__shfl(mark_cells, (int)((c >> 5) & 63u)) >> (c & 31u)) & 1u;
+    };
+    auto compare = [&](uint32_t pd, bool near, uint32_t (&mm)[kMapWords]) -> uint32_t {
+        return maptext::compare_split(text_d, text_mu, text_tm, WaveAny{}, near, qw, pd + kMapPad, len, mm);
     };
     uint32_t cnt = 0;
     uint32_t junction = 0xFFu; // DIRECT: index in the read's list of the entry that is no mismatch but the last base of its first diagonal
@@ -461,7 +501,8 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
 #pragma unroll
     for (uint32_t g = 0; g < kMapWords; g++) mmw[g] = 0;
     if (__ballot(seeded)) {
-        if (seeded) cnt = compare(p0, mmw);
+        const bool nm = near_mark(p0 + kMapPad);
+        if (seeded) cnt = compare(p0, nm, mmw);
     }
     // ---- 2b. (DIRECT) a SECOND diagonal for a read that leaves its first - an insertion or a deletion, a chimera, or a first seed
     // that sat on a substitution and matched elsewhere (3 reads in 1000; all their bases mismatch from there on) -, and for a read
@@ -495,44 +536,17 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
             bool front = false;
             uint32_t pA = 0;
             if (__ballot(near)) {
+                const bool nm_t = near_mark(p0 + kMapPad + len - 19u), nm_h = near_mark(p0 + kMapPad - 3u);
                 if (near) {
                     // qb: the text base three in front of the 16 bases on p0; -> fewest mismatches over the six shifts, j = shift + 3
                     const uint32_t qt = p0 + kMapPad + len - 19u, qh = p0 + kMapPad - 3u;
-                    const uint8_t *tt = reinterpret_cast<const uint8_t *>(a.ix.pc_tm) + (size_t)(qt >> 4) * 8u;
-                    const uint8_t *th = reinterpret_cast<const uint8_t *>(a.ix.pc_tm) + (size_t)(qh >> 4) * 8u;
-                    uint2 U[3], H[3];
-#pragma unroll
-                    for (int i = 0; i < 3; i++) {
-                        __builtin_memcpy(&U[i], tt + 8 * i, 8);
-                        __builtin_memcpy(&H[i], th + 8 * i, 8);
-                    }
+                    uint32_t Ud[maptext::kBeside], Um[maptext::kBeside], Hd[maptext::kBeside], Hm[maptext::kBeside];
+                    maptext::beside_split(text_d, text_mu, text_tm, WaveAny{}, nm_t, qt >> 4, Ud, Um);
+                    maptext::beside_split(text_d, text_mu, text_tm, WaveAny{}, nm_h, qh >> 4, Hd, Hm);
                     // (a break within 16 bases of that end: the 8 bases at the end, all of them - 6 / 4^8 by chance)
-                    auto beside = [&](const uint2 (&X)[3], uint32_t qb, uint32_t word, uint32_t end8, uint32_t &best_j) -> uint32_t {
-                        uint32_t best = 99u, j8 = 3u;
-                        best_j = 3u;
-#pragma unroll
-                        for (uint32_t j = 0; j < 7u; j++) {
-                            if (j == 3u) continue;
-                            const uint32_t rel = (qb & 15u) + j, r = rel & 15u;
-                            const uint2 hi = rel < 16u ? X[0] : X[1], lo = rel < 16u ? X[1] : X[2];
-                            const uint32_t tw = (uint32_t)((((uint64_t)hi.x << 32) | lo.x) >> (32u - 2u * r));
-                            const uint32_t mk = (uint32_t)((((uint64_t)hi.y << 32) | lo.y) >> (32u - 2u * r));
-                            const uint32_t x = word ^ tw;
-                            const uint32_t mb = (x | (x >> 1) | mk) & 0x55555555u, c = (uint32_t)__popc(mb);
-                            if (c < best) {
-                                best = c;
-                                best_j = j;
-                            }
-                            if ((mb & end8) == 0u) j8 = j;
-                        }
-                        if (best > 2u && j8 != 3u) {
-                            best = 0u;
-                            best_j = j8;
-                        }
-                        return best;
-                    };
                     uint32_t jt, jh;
-                    const uint32_t ct = beside(U, qt, from_base(soff + len - 16u), 0x0000FFFFu, jt), ch = beside(H, qh, qw[0], 0xFFFF0000u, jh);
+                    const uint32_t ct = maptext::beside_best(Ud, Um, qt, from_base(soff + len - 16u), 0x0000FFFFu, jt),
+                                   ch = maptext::beside_best(Hd, Hm, qh, qw[0], 0xFFFF0000u, jh);
                     // (by chance: 6 * 1129 / 4^16 = 1.6e-6 - and then it costs a flag, not a wrong character)
                     if (ct <= 2u) {
                         seedB = true;
@@ -544,10 +558,11 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                 }
             }
             if (__ballot(front)) {
+                const bool nm = near_mark(pA + kMapPad);
                 if (front) { // the seed's diagonal is the second one
                     pB = p0;
                     p0 = pA;
-                    cnt = compare(p0, mmw);
+                    cnt = compare(p0, nm, mmw);
                     seedB = true;
                 }
             }
@@ -571,7 +586,8 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
 #pragma unroll
                 for (uint32_t g = 0; g < kMapWords; g++) mmB[g] = 0;
                 uint32_t cB = 0;
-                if (two) cB = compare(pB, mmB);
+                const bool nm = near_mark(pB + kMapPad);
+                if (two) cB = compare(pB, nm, mmB);
                 if (two && !seeded) { // no first diagonal: the whole read on the second
 #pragma unroll
                     for (uint32_t g = 0; g < kMapWords; g++) mmw[g] = mmB[g];
@@ -1465,9 +1481,12 @@ __global__ __launch_bounds__(256) void finish_reads_kernel(WalkArgs a, uint32_t 
 
 } // namespace
 
-hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint2 *d_out, uint64_t n_units, hipStream_t stream)
+hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint2 *d_out, uint32_t *d_t, uint32_t *d_mu, uint32_t *d_mc, uint64_t n_units,
+                            hipStream_t stream)
 {
-    hipLaunchKernelGGL(pack_text_kernel, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, stream, d_text_padded, n_bytes, d_out, n_units);
+    hipLaunchKernelGGL(pack_text_kernel, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, stream, d_text_padded, n_bytes, d_out, d_t, d_mu, n_units);
+    hipLaunchKernelGGL(mark_cells_kernel, dim3(maptext::kCells / 64u), dim3(64), 0, stream, reinterpret_cast<const uint8_t *>(d_mu), d_mc,
+                       maptext::cell_shift(n_units), n_units);
     return hipGetLastError();
 }
 
@@ -1481,7 +1500,7 @@ hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, ui
 // what the index copy and the batch's longest read have to be like ...
 static bool map_reads_index_applies(const DevIndexView &ix, uint32_t longest)
 {
-    return ix.dtab && ix.pc_tm && ix.seed_pos && ix.seed_d >= 4u && ix.seed_d <= 14u && ix.dtab_order >= 4u && ix.dtab_order <= 17u &&
+    return ix.dtab && ix.pc_tm && ix.pc_t && ix.pc_mu && ix.pc_mc && ix.seed_pos && ix.seed_d >= 4u && ix.seed_d <= 14u && ix.dtab_order >= 4u && ix.dtab_order <= 17u &&
            ix.dtab_order <= ix.k && longest != 0 && longest <= 16u * kMapWords;
 }
 // ... and the launch: its plan work attached (attach_plan: not while the copy's plan is held off), no intervals, no call mode
