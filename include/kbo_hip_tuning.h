@@ -126,7 +126,9 @@ int kbo_set_plan_stats(int on);
  * [9]: entries of the redo list, [10]: 1 = the plan was given up, [11]: 1 = a walk left through its guard;  depth-table form
  * (kbo_set_depth_table) out[12]: table look-ups, [13]: values written from the table, [14] = [15]: items the table could not
  * resolve (counted by the lanes / by the launch's control word; out[8] is meaningless in that form), [16]: bases read off the
- * path-cover text (anchors), [17]: items resolved without a plan.  Meaningless
+ * path-cover text (anchors), [17]: items resolved without a plan;  map_reads_kernel's direct form (kbo_map_batch_dev) [18]:
+ * words looked up of the copy's bit per text position for lone substitutions, [19]: mismatches those bits settled without a
+ * filter word or a table byte (out[6] and out[12] count the filter words and table bytes actually looked up).  Meaningless
  * (stale or zero) when that launch did not plan (plain walk, hold-off, intervals requested) or did not count. */
 #define KBO_PLAN_STATS 20
 int kbo_plan_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k, const void *d_work,

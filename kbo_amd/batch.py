@@ -492,7 +492,7 @@ class DeviceBatch:
                                        s.cuda_stream))
         names = ("units_walked", "accepted", "failed", "levels", "entry_levels", "seed_lookups", "seed_extensions",
                  "mismatches", "units", "redo_entries", "gave_up", "guard", "tab_lookups", "tab_written", "tab_flagged",
-                 "tab_unresolved", "tab_anchored", "items_noplan")
+                 "tab_unresolved", "tab_anchored", "items_noplan", "subst_bits", "subst_clean")
         return {n: int(v) for n, v in zip(names, out)}
 
     def plan_flags(self, stream=None):

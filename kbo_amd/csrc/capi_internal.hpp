@@ -49,6 +49,9 @@ struct DevCopy {
     uint32_t dfilt_bases = 0;
     DevBuf pc_tm, seed_pos;          // map_reads_kernel's 2-bit text + marks and its table of seed positions (copies with a depth table)
     DevBuf pc_t, pc_mu, pc_mc;       // ... the text's digits alone, a bit per unit with a mark and the coarse summary of those (map_text.hpp)
+    DevBuf sub_clean;                // ... and a bit per text position: a lone substitution there needs no table (map_subst.hpp), for the
+    uint32_t sub_thr = 0;            // proof's windows at this threshold - what a call with default options gets on this index -
+    bool sub_anch = false;           // with or without anchors
     // what making this copy cost (kbo_index_device_layout): seconds of host work / device builds / uploads, by part
     bool plan_built = false;         // path cover, recovery lines, tables: made by the first use that pays for them (device_index.cpp)
     bool plan_failed = false;        // ... or could not be made (no memory): not tried again on every call; the copy walks plainly

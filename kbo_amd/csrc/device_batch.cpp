@@ -221,6 +221,8 @@ int kbo_plan_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, 
             for (uint32_t i = 0; i < 8; i++) out[i] += st[sl * kbo::kPlanStatWords + i];
             for (uint32_t i = 0; i < 3; i++) out[12 + i] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabLookups + i];
             out[16] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabAnchored];
+            out[18] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSubstBits];
+            out[19] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSubstClean];
         }
         out[15] = ctl[4];
         out[17] = ctl[5];

@@ -1,6 +1,7 @@
 // device_index.cpp — the per-device copies of an index handle (rank blocks, contraction entries,
 // two-base blocks) and the knobs that shape them.
 #include "capi_internal.hpp"
+#include "map_subst.hpp"
 #include "map_text.hpp"
 
 #include <cmath>
@@ -331,6 +332,34 @@ void build_plan_structures(kbo_index *idx, DevCopy *dc)
         dc->setup.seed_bytes += (uint64_t)4 << (2u * dc->seed_d);
         idx->plan_bytes += units * 12 + mu_bytes + kbo::maptext::kCells / 8u + ((size_t)4 << (2u * dc->seed_d));
         dc->setup.seed_s += since(t0);
+        // a bit per text position that settles a lone substitution there without the filter or the table (map_subst.hpp), from the
+        // text and the table just made, for the threshold a call with default options gets on this index (any other threshold's
+        // launches run without it).  KBO_SUBST_BITS=0: none - read for every copy, so that a process can hold one of either kind
+        const char *env_sub = std::getenv("KBO_SUBST_BITS");
+        kbo_map_opts dflt;
+        kbo_map_opts_default(&dflt);
+        // (an index without a k-mer - sequences shorter than k - has no threshold: no bits)
+        const size_t thr = idx->host.n_kmers > 0 ? random_match_threshold(idx->host.k, idx->host.n_kmers, 4, dflt.max_error_prob) : 0;
+        const bool anch = dc->anchor_bits != 0 && thr > dc->dtab_order;
+        const uint32_t step = thr >= dc->dtab_order ? kbo::mapsubst::window_step(dc->dtab_order, (uint32_t)thr, anch) : 0u;
+        if (!(env_sub && std::atoi(env_sub) == 0) && thr >= dc->dtab_order && thr < idx->host.k && !kbo::mapsubst::window_used(kbo::mapsubst::kWindows, step, dc->dtab_order, 0u)) {
+            t0 = clk::now();
+            const uint64_t sub_bytes = kbo::mapsubst::bitmap_words(units) * 4;
+            dc->sub_clean.alloc(sub_bytes + 64);
+            HIP_OK(hipMemsetAsync(dc->sub_clean.as<uint8_t>() + sub_bytes, 0, 64, bs));
+            kbo::DevIndexView sv{};
+            sv.pc_tm = dc->pc_tm.as<uint2>();
+            sv.dtab = dc->dtab.as<uint8_t>();
+            sv.dtab_order = dc->dtab_order;
+            sv.dtab_grouped = dc->dtab_grouped ? 1u : 0u;
+            HIP_OK(kbo::launch_subst_bits(sv, units, (uint32_t)thr, anch, dc->sub_clean.as<uint32_t>(), bs));
+            HIP_OK(hipStreamSynchronize(bs));
+            dc->sub_thr = (uint32_t)thr;
+            dc->sub_anch = anch;
+            dc->setup.cover_bytes += sub_bytes;
+            idx->plan_bytes += sub_bytes;
+            dc->setup.cover_s += since(t0);
+        }
     }
     dc->plan_built = true;
 }
@@ -472,7 +501,7 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
                 // table's depth without its table, a text without its positions - must not reach a launch), the copy is marked so
                 // that the build is not paid again by every later call, and it walks plainly - with the same results.  An explicit
                 // kbo_index_to_device still reports the failure.
-                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->pc_t, &dc->pc_mu, &dc->pc_mc, &dc->seed_pos})
+                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->pc_t, &dc->pc_mu, &dc->pc_mc, &dc->sub_clean, &dc->seed_pos})
                     b->release();
                 dc->seed_d = dc->dtab_order = dc->anchor_bits = dc->dfilt_bases = 0;
                 dc->dtab_grouped = false;
@@ -519,6 +548,9 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
     v.pc_mc_shift = kbo::maptext::cell_shift(kbo::pack_text_units(idx->host.n_sets));
     v.dfilt = (use_tab && dc->dfilt_bases) ? dc->dfilt.as<uint32_t>() : nullptr;
     v.dfilt_bases = v.dfilt ? dc->dfilt_bases : 0u;
+    v.sub_clean = (v.pc_t && dc->sub_clean.p) ? dc->sub_clean.as<uint32_t>() : nullptr;
+    v.sub_thr = dc->sub_thr;
+    v.sub_anch = dc->sub_anch ? 1u : 0u;
     v.seed_pos = (use_tab && dc->seed_pos.p) ? dc->seed_pos.as<uint32_t>() : nullptr;
     for (int c = 0; c < 4; c++) v.C[c] = (uint32_t)idx->host.C[c];
     v.C[4] = v.n;

@@ -59,6 +59,12 @@ struct DevIndexView {
     // suffix of a row - 4^dfilt_bases / 8 bytes (2 MB for 12 bases: stays in L2), nullptr when the copy has none
     const uint32_t *dfilt;
     uint32_t dfilt_bases;
+    // ... and what settles a lone substitution without the table (map_subst.hpp): a bit per position of the 2-bit text (bit q of
+    // word q / 32, q counted from the first unit's first position), set where no one-base neighbour of the text's windows around
+    // it is in the index - for the proof's windows at threshold sub_thr with (sub_anch = 1) or without anchors.  nullptr when the
+    // copy has none; launch_map_reads hands the kernel nullptr when the launch's threshold is another
+    const uint32_t *sub_clean;
+    uint32_t sub_thr, sub_anch;
 };
 
 // One unit of walk work: `len` bases starting at absolute offset `start` of the
@@ -137,7 +143,7 @@ struct WalkArgs {
     uint32_t unit_bail;    // more units than this in a launch: the plan is given up, every item takes the plain walk
     uint32_t *qctl;        // [0] queue head of the guided walk, [1] entries of the redo list, [2] plan given up, [3] a walk left through its guard,
                            // [4] (table mode) items the table could not resolve, [5] items without a plan, [6] entries of map_reads_kernel's list of the reads it left (finish_reads_kernel)
-    uint32_t *pstats;      // work counters of the launch (kPlanStat*): kPlanStatSlots slots of 8 u32, summed by the host
+    uint32_t *pstats;      // work counters of the launch (kPlanStat*): kPlanStatSlots slots of kPlanStatWords u32, summed by the host
     uint32_t plan_dmin;    // plan_kernel: a seed must be this deep (capped at k) before its row is trusted
     uint32_t plan_cap;     // plan_kernel: seed iterations before an item is given up as unplanned
     uint32_t plan_gap;     // plan_emit_kernel: mismatches closer than this share a unit (>= 2)
@@ -182,7 +188,9 @@ struct WalkArgs {
 // what the CPU model of the stage (oracle/plan_model.c) is pinned to, tests/test_gpu_model.py
 enum : uint32_t { kPlanStatUnits = 0, kPlanStatAccepted, kPlanStatFailed, kPlanStatLevels, kPlanStatEntryLevels,
                   kPlanStatSeedLookups, kPlanStatSeedExtensions, kPlanStatMismatches,
-                  kPlanStatTabLookups, kPlanStatTabWritten, kPlanStatTabFlagged, kPlanStatTabAnchored, kPlanStatWords };
+                  kPlanStatTabLookups, kPlanStatTabWritten, kPlanStatTabFlagged, kPlanStatTabAnchored,
+                  kPlanStatSubstBits, kPlanStatSubstClean, // (map_reads_kernel: words of sub_clean looked up, mismatches they settled)
+                  kPlanStatWords };
 constexpr uint32_t kPlanStatSlots = 8;
 // where the pieces of a launch's plan work live inside its work buffer (attach_plan)
 struct PlanLayout {
@@ -234,6 +242,9 @@ hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint
 constexpr uint32_t kMapPad = 192;
 inline uint64_t pack_text_units(uint64_t n_sets) { return (n_sets + kMapPad + 256u) / 16u + 2u; }
 inline uint64_t pack_text_mu_bytes(uint64_t n_units) { return (n_units + 255u) / 256u * 32u; } // (a bit per unit, whole workgroups of pack_text_kernel)
+// the bit per text position of map_subst.hpp from the copy's own text and depth table (ix.pc_tm, ix.pc_t, ix.dtab), for the proof's
+// windows at threshold thr: d_bits gets mapsubst::bitmap_words(n_units) words
+hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, hipStream_t stream);
 hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, uint32_t *d_out, uint32_t seed_d, hipStream_t stream);
 // true when the launch described by `a` (plan work attached, chars_out set) can take map_reads_kernel: reads of at most 160
 // bases, MS values / characters only, an index copy with a depth table, the 2-bit text and the position table

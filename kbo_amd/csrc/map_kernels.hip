@@ -41,6 +41,7 @@
 //
 // Integer / byte work only: no MFMA.  One 64-lane wave per workgroup (the LDS of a CU then holds twelve of them).
 #include "device_util.hpp"
+#include "map_subst.hpp"
 #include "map_text.hpp"
 
 #include <algorithm>
@@ -154,6 +155,40 @@ struct TextUnits {
 struct WaveAny {
     __device__ __forceinline__ bool operator()(bool b) const { return __ballot(b) != 0; }
 };
+
+// map_subst.hpp's accessors: the kernel's one gathered word, and what the bitmap is built from
+static_assert(mapsubst::kPad == kMapPad, "map_subst.hpp keys its bits by the 2-bit text's positions");
+struct SubstBits {
+    const uint32_t *p;
+    __device__ __forceinline__ uint32_t word(uint64_t w) const { return p[w]; }
+};
+struct SubstText {
+    const uint2 *tm;
+    uint64_t n_units;
+    __device__ __forceinline__ uint64_t positions() const { return 16ull * n_units; }
+    __device__ __forceinline__ bool marked(uint64_t q) const { return (tm[q >> 4].y >> (2u * (15u - (uint32_t)(q & 15u)))) & 1u; }
+    __device__ __forceinline__ uint32_t base(uint64_t q) const { return (tm[q >> 4].x >> (2u * (15u - (uint32_t)(q & 15u)))) & 3u; }
+};
+struct SubstTable {
+    const uint8_t *dtab;
+    uint32_t order, grouped;
+    __device__ __forceinline__ bool present(uint64_t key) const
+    {
+        return (dtab[grouped ? dtab_grouped_addr(key, 0u, order) : key] & 0x80u) != 0u; // (any of the three groups holds every entry)
+    }
+};
+// a thread per position, a word per 32 of them
+__global__ __launch_bounds__(256) void subst_bits_kernel(SubstText tx, SubstTable tab, uint32_t thr, uint32_t have_anch, uint32_t *__restrict__ out,
+                                                         uint64_t n_words)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool c = q < tx.positions() && mapsubst::clean(tx, tab, q, tab.order, thr, have_anch != 0u);
+    const uint64_t any = __ballot(c);
+    if ((threadIdx.x & 63u) == 0u) {
+        if ((q >> 5) < n_words) out[q >> 5] = (uint32_t)any;
+        if ((q >> 5) + 1u < n_words) out[(q >> 5) + 1u] = (uint32_t)(any >> 32);
+    }
+}
 
 // the coarse summary of the marks (map_text.hpp): a thread per cell
 __global__ __launch_bounds__(64) void mark_cells_kernel(const uint8_t *__restrict__ mu, uint32_t *__restrict__ out, uint32_t shift, uint64_t n_units)
@@ -497,6 +532,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     uint32_t cnt = 0;
     uint32_t junction = 0xFFu; // DIRECT: index in the read's list of the entry that is no mismatch but the last base of its first diagonal
     uint32_t jov = 0;          // ... and the bases in front of the cut that lie on both diagonals
+    bool cut = false;          // DIRECT: the read's bases lie on two diagonals (also where the cut merged with a mismatch and left no junction)
     uint32_t mmw[kMapWords];
 #pragma unroll
     for (uint32_t g = 0; g < kMapWords; g++) mmw[g] = 0;
@@ -638,6 +674,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                         uint32_t jm = 0xFFu, before = 0;
                         int32_t lastA = -1; // the first diagonal's last mismatch in front of the cut
                         cnt = 0;
+                        cut = true;
 #pragma unroll
                         for (uint32_t g = 0; g < kMapWords; g++) {
                             const uint32_t lo_b = 16u * g; // bases of this word: [lo_b, lo_b + 16)
@@ -730,6 +767,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     uint32_t w_e = 0, w_owner = 0, w_at = 0, w_len = 0, w_pre[6] = {0, 0, 0, 0, 0, 0};
     // ---- 3. the stretches behind the mismatches from the depth table (rule: dtab_kernels.hip), dealt out to the lanes
     uint32_t st_look = 0, st_written = 0, st_anch = 0, st_filt = 0; // (direct form: st_written = windows the filter settled)
+    uint32_t st_bits = 0, st_clean = 0;                             // (direct form: words of sub_clean looked up, mismatches they settled)
     {
         const uint32_t order = a.ix.dtab_order;
         // DIRECT: cov = bases between two windows of the proof (header), n_e = windows per mismatch (<= 4: launch_map_reads);
@@ -738,7 +776,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         // closer, so that one of them may be present as long as its exact depth, read off the path-cover text, is at most
         // order + 1: header)
         const bool have_anch = DIRECT && a.ix.anchor != nullptr && thr_gt(a.map_thr, order);
-        const uint32_t thr = a.map_thr, covb = DIRECT ? thr - order + 2u : 1u, cov = have_anch ? thr - order : covb;
+        const uint32_t thr = a.map_thr, covb = DIRECT ? mapsubst::window_step(order, thr, false) : 1u, cov = DIRECT ? mapsubst::window_step(order, thr, have_anch) : 1u;
         const uint32_t n_blockwin = (DIRECT && len > thr) ? (len - order + covb - 1u) / covb + 1u : 0u;
         const uint32_t my_n = !plannable || flag ? 0u : DIRECT ? (no_plan ? (n_blockwin + 3u) / 4u : (len > thr ? cnt : 0u))
                                                                : (no_plan ? (len + 15u) / 16u : cnt);
@@ -770,6 +808,8 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
             const uint32_t owner = work ? lo_l : lane;
             const uint32_t o_incl = __shfl(incl, (int)owner), o_n = __shfl(my_n, (int)owner), o_soff = __shfl(soff, (int)owner),
                            o_len = __shfl(len, (int)owner), o_np = __shfl(no_plan ? 1u : 0u, (int)owner), o_junc = __shfl(junction, (int)owner), o_jov = __shfl(jov, (int)owner);
+            // (what the bit of a lone substitution is keyed by, map_subst.hpp: the owner's diagonal, and whether it has only one)
+            const uint32_t o_p0 = __shfl(p0, (int)owner), o_cut = __shfl(cut ? 1u : 0u, (int)owner);
             const bool blockmode = o_np != 0;
             if (DIRECT) {
                 if (work) {
@@ -777,6 +817,22 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                     const uint32_t m = blockmode ? 0u : (uint32_t)spw[owner * 16u + t];
                     uint32_t bytes[4], ee[4];
                     bool use[4], lastw[4], look[4];
+                    // a lone substitution on the read's one diagonal (map_subst.hpp): one bit of the copy's sub_clean says whether any
+                    // of its windows can be in the index.  Set: all of them are absent - no filter word, no table byte, nothing
+                    // pending.  Clear: the table, as before (not the filter first: the chain stays one L2-resident gather, then the
+                    // table).  The word is gathered in the round in which the other items gather their filter words
+                    bool lone = false, settled = false;
+                    if (a.ix.sub_clean && !blockmode) {
+                        const uint8_t *osp = spw + owner * 16u;
+                        const bool has_prev = t > 0u, has_next = t + 1u < o_n;
+                        lone = mapsubst::eligible(false, o_cut != 0u, t == o_junc, has_prev, has_prev ? (uint32_t)osp[t - 1u] : 0u, m, has_next,
+                                                  has_next ? (uint32_t)osp[t + 1u] : 0u, order);
+                        if (lone) {
+                            settled = mapsubst::clean_bit(SubstBits{a.ix.sub_clean}, mapsubst::bit_of(o_p0, m));
+                            if (STATS) st_bits++;
+                            if (STATS && settled) st_clean++;
+                        }
+                    }
 #pragma unroll
                     for (uint32_t i = 0; i < 4u; i++) {
                         // the base the window ends at, and whether the window counts: inside the read, `order` bases long, and not the
@@ -790,19 +846,19 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                             // (the junction of two diagonals: the windows that hold both its bases, m and m + 1)
                             // (and the bases in front of m that lie on the second diagonal too: the windows reach back over them)
                             const uint32_t jn = t == o_junc ? 1u + o_jov : 0u, j1 = t == o_junc ? 1u : 0u;
-                            ee[i] = m + j1 + min(i * cov, order - 1u - jn);
-                            use[i] = ee[i] < o_len && ee[i] + 1u >= order && (i == 0u || (i - 1u) * cov < order - 1u - jn);
-                            lastw[i] = i * cov >= order - 1u - jn; // the window that starts at the break: nothing stands behind it
+                            ee[i] = m + j1 + mapsubst::window_offset(i, cov, order, jn);
+                            use[i] = ee[i] < o_len && ee[i] + 1u >= order && mapsubst::window_used(i, cov, order, jn);
+                            lastw[i] = mapsubst::window_last(i, cov, order, jn); // the window that starts at the break: nothing stands behind it
                         }
                         bytes[i] = 0;
-                        look[i] = use[i];
+                        look[i] = use[i] && !settled;
                     }
                     // the filter in front of the table (small indexes: DevIndexView::dfilt, 2 MB the L2 keeps): a window is absent as
                     // soon as F of its bases are - F bases that hold the whole break (the mismatch; the junction's bases and what
                     // lies on both diagonals in front of it), or the window would only repeat what the text says.  Two of them
                     // where two differ: the rightmost and the leftmost such stretch inside the window.  Three windows in four
                     // never reach the table (a line fill each) at C2
-                    if (a.ix.dfilt) {
+                    if (a.ix.dfilt && !lone) {
                         const uint32_t F = a.ix.dfilt_bases, fmask = (1u << (2u * F)) - 1u;
                         uint32_t zlo, zhi; // the break inside the read (a read without a seed: any stretch will do)
                         if (blockmode) zlo = zhi = 0xFFFFFFFFu;
@@ -1337,6 +1393,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     if (STATS) plan_stats_add(a.pstats, kPlanStatSeedLookups, st_lookups, kPlanStatSeedExtensions, st_filt /* (this kernel: filter look-ups) */, kPlanStatMismatches, seeded ? cnt : 0u, 0, 0);
     if (STATS) plan_stats_add(a.pstats, kPlanStatTabLookups, st_look, kPlanStatTabWritten, st_written, kPlanStatTabFlagged, flag ? 1u : 0u,
                    kPlanStatTabAnchored, st_anch);
+    if (STATS) plan_stats_add(a.pstats, kPlanStatSubstBits, st_bits, kPlanStatSubstClean, st_clean, 0, 0, 0, 0);
     const uint64_t fm = __ballot(flag), nm = __ballot(no_plan);
     if (lane == 0) {
         if (fm) atomicAdd(a.qctl + 4, (uint32_t)__popcll(fm));
@@ -1490,6 +1547,14 @@ hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint
     return hipGetLastError();
 }
 
+hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, hipStream_t stream)
+{
+    const uint64_t n_words = mapsubst::bitmap_words(n_units);
+    hipLaunchKernelGGL(subst_bits_kernel, dim3((unsigned)((32u * n_words + 255u) / 256u)), dim3(256), 0, stream, SubstText{ix.pc_tm, n_units},
+                       SubstTable{ix.dtab, ix.dtab_order, ix.dtab_grouped}, thr, have_anch ? 1u : 0u, d_bits, n_words);
+    return hipGetLastError();
+}
+
 hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, uint32_t *d_out, uint32_t seed_d, hipStream_t stream)
 {
     const uint64_t n = 1ull << (2u * seed_d);
@@ -1539,6 +1604,8 @@ hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream)
     hipError_t e = hipMemsetAsync(a.qctl, 0, 64 + kPlanStatSlots * kPlanStatWords * 4, stream);
     if (e != hipSuccess) return e;
     const bool direct = map_reads_direct(a);
+    // (the bits of lone substitutions speak for the windows of one threshold: another one's launch runs without them)
+    if (!direct || a.map_thr != a.ix.sub_thr || (a.ix.sub_anch != 0u) != (a.ix.anchor != nullptr && a.map_thr > a.ix.dtab_order)) a.ix.sub_clean = nullptr;
     static const bool env_nouni = std::getenv("KBO_MAP_NO_UNIFORM") != nullptr; // experiments
     a.uniform_len = (a.seq_off && !env_nouni && a.max_item_len != 0 && (uint64_t)a.n_items * a.max_item_len == a.q_bytes) ? a.max_item_len : 0u;
     const int io = a.qp ? (a.packed_out ? 2 : 1) : 0;
