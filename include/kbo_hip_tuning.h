@@ -89,6 +89,35 @@ int kbo_set_plan_lazy(int64_t bases);
  * copy to hand back, in key order (ignored for tables too small to be grouped).  table == NULL only asks for *n_bytes and
  * *order; tables of more than 14 bases are not handed back (KBO_E_UNSUPPORTED). */
 int kbo_index_depth_table(kbo_index_t *idx, int device, int view, uint8_t *table, size_t *n_bytes, int *order);
+/* inspection / tests: one of the plan structures that the copy of `idx` on `device` (-1 = current; the copy and its plan
+ * structures are made if there are none: as kbo_index_depth_table) built for itself on the device, handed back byte for byte as
+ * it lies there - a plain download under the handle's lock; nothing on the device changes and no kernel runs.
+ * out == NULL only asks for *n_bytes and info; a part the copy does not have gives 0 bytes, info all zero and KBO_OK (no depth
+ * table: everything but a host-built seed table; KBO_SUBST_BITS=0, a default threshold below the table's order or an index without
+ * a k-mer: no sub_clean).  KBO_E_BAD_ARG: a NULL idx / n_bytes / info, a part outside 0 .. KBO_PLAN_PARTS - 1, a buffer of fewer
+ * than the part's bytes; a sharded index is refused as by the other hooks that need the rows of one index.
+ * With U = info[0] units of 16 text positions (unit u = positions [16 u - 192, + 16) of the path-cover text):
+ *   PC_TM     U x { digits, marks } (kbo_amd/csrc/map_text.hpp), 8 U bytes                      info = { U, cell shift }
+ *   PC_T      U digit words and the 16 bytes of slack a window's last load may read              info = { U, cell shift }
+ *   PC_MU     a bit per unit, whole workgroups of 256 units, and the 4 bytes of slack behind     info = { U, cell shift }
+ *   PC_MC     2048 bits, a cell of 2^shift units each                                            info = { U, cell shift }
+ *   SEED_TAB  { l, r } per string of seed_d bases, 8 * 4^seed_d bytes           info = { seed_d, 1 if built on the device else 0 }
+ *   SEED_POS  a text position per string of seed_d bases, 4 * 4^seed_d bytes    info = { seed_d, as SEED_TAB }
+ *   DFILT     a bit per string of F bases, 4^F / 8 bytes                        info = { F, order of the depth table }
+ *   ANCHOR    2^bits slots of { text position, (uint32_t)key + 1 }, 8 bytes     info = { bits, order of the depth table }
+ *   SUB_CLEAN a bit per text position (kbo_amd/csrc/map_subst.hpp), 4 * ((U + 1) / 2) bytes
+ *                                                      info = { U, order of the depth table, threshold, 1 with anchors else 0 } */
+#define KBO_PLAN_PART_PC_TM 0
+#define KBO_PLAN_PART_PC_T 1
+#define KBO_PLAN_PART_PC_MU 2
+#define KBO_PLAN_PART_PC_MC 3
+#define KBO_PLAN_PART_SEED_TAB 4
+#define KBO_PLAN_PART_SEED_POS 5
+#define KBO_PLAN_PART_DFILT 6
+#define KBO_PLAN_PART_ANCHOR 7
+#define KBO_PLAN_PART_SUB_CLEAN 8
+#define KBO_PLAN_PARTS 9
+int kbo_index_plan_part(kbo_index_t *idx, int device, int part, void *out, size_t *n_bytes, uint32_t info[4]);
 /* tests: depth of the seed table of device copies made after the call (0 = by index size: 8 / 10 / 12 / 13 bases;
  * 1 .. 13 = that many, capped at k).  Large tables are what large indexes get: 12 bases = 128 MiB, 13 = 512 MiB. */
 int kbo_set_seed_table_depth(int bases);

@@ -83,6 +83,9 @@ class RefCalls(C.Structure):
 
 
 OPT_INHERIT = -2147483648
+# kbo_hip_tuning.h KBO_PLAN_PART_*: name -> (part, numpy dtype of its entries)
+PLAN_PARTS = {"pc_tm": (0, "<u4"), "pc_t": (1, "<u4"), "pc_mu": (2, "u1"), "pc_mc": (3, "<u4"), "seed_tab": (4, "<u4"),
+              "seed_pos": (5, "<u4"), "dfilt": (6, "<u4"), "anchor": (7, "<u8"), "sub_clean": (8, "<u4")}
 
 
 class IndexOpts(C.Structure):
@@ -159,7 +162,7 @@ TUNING_SYMBOLS = [
     "kbo_walk_geometry", "kbo_set_walk_waves_per_cu", "kbo_set_walk_threads", "kbo_set_walk_rare", "kbo_set_guided_walk",
     "kbo_set_pair_steps", "kbo_set_force_big_layout", "kbo_set_seed_table_depth", "kbo_set_plan", "kbo_set_plan_tuning",
     "kbo_set_plan_unit_cap_divisor", "kbo_index_plan_holdoff", "kbo_set_walk_experiment", "kbo_plan_stats_dev", "kbo_set_plan_stats", "kbo_set_index_shards", "kbo_index_shard", "kbo_set_depth_table", "kbo_set_depth_table_anchors", "kbo_index_depth_table", "kbo_run_automaton_depths",
-    "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check",
+    "kbo_set_stage_timing", "kbo_stage_timing_read", "kbo_set_plan_table_budget", "kbo_set_plan_lazy", "kbo_plan_flags_dev", "kbo_long_stats_dev", "kbo_set_map_long", "kbo_set_ms_one_kernel", "kbo_set_call_device_emit", "kbo_index_layout_check", "kbo_index_cover_check", "kbo_index_plan_part",
     "kbo_set_host_in_place", "kbo_fill_gaps_stats", "kbo_map_batch_opts_phases", "kbo_index_build_device_phases", "kbo_sparse_runs_blocks",
     "kbo_last_batch_staged_bytes", "kbo_summary_slab_routes", "kbo_set_refset_record_capacity", "kbo_refset_last_routes",
     "kbo_derand_translate_host", "kbo_run_lengths_seg_calls", "kbo_run_lengths_seq_host", "kbo_run_lengths_seq_host_each",
@@ -300,6 +303,7 @@ def lib():
     L.kbo_set_depth_table.argtypes = [C.c_int]
     L.kbo_set_depth_table_anchors.argtypes = [C.c_int]
     L.kbo_index_depth_table.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.kbo_index_plan_part.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     L.kbo_index_shards.argtypes = [vp]
     L.kbo_index_shard.argtypes = [vp, C.c_int]; L.kbo_index_shard.restype = vp
     L.kbo_index_work_bytes.argtypes = [vp, sz, u64, sz]; L.kbo_index_work_bytes.restype = sz

@@ -28,6 +28,8 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "map_subst.hpp"
+#include "map_text.hpp"
 #include "../../include/kbo_hip_tuning.h"
 
 using namespace kbo_host;
@@ -1227,6 +1229,48 @@ int kbo_index_depth_table(kbo_index_t *idx, int device, int view, uint8_t *table
         }
         *n_bytes = need;
         *order = (int)v.dtab_order;
+    });
+}
+
+// test hook (kbo_hip_tuning.h): one of the plan structures the copy on `device` made for itself, as it lies there, slack included
+int kbo_index_plan_part(kbo_index_t *idx, int device, int part, void *out, size_t *n_bytes, uint32_t info[4])
+{
+    return guarded([&] {
+        KBO_REQUIRE(idx && n_bytes && info && part >= 0 && part < KBO_PLAN_PARTS, KBO_E_BAD_ARG, "null argument / part not in 0 .. KBO_PLAN_PARTS - 1");
+        const int dev = device < 0 ? current_device() : device;
+        (void)device_view(idx, dev, nullptr, 0, true); // (makes the copy and its plan structures if there are none yet)
+        std::lock_guard<std::mutex> g(idx->mu);
+        auto it = idx->dev.find(dev);
+        KBO_REQUIRE(it != idx->dev.end(), KBO_E_BAD_ARG, "the index has no copy on that device");
+        const DevCopy &dc = *it->second;
+        const uint64_t units = kbo::pack_text_units(idx->host.n_sets);
+        const uint32_t shift = kbo::maptext::cell_shift(units);
+        const bool seed_on_device = dc.dtab_order != 0 && dc.seed_d != 0 && dc.seed_d <= dc.dtab_order; // (build_plan_structures' rule)
+        const DevBuf *buf = nullptr;
+        size_t need = 0;
+        uint32_t inf[4] = {0, 0, 0, 0};
+        switch (part) {
+        case KBO_PLAN_PART_PC_TM: buf = &dc.pc_tm, need = units * 8, inf[0] = (uint32_t)units, inf[1] = shift; break;
+        case KBO_PLAN_PART_PC_T: buf = &dc.pc_t, need = units * 4 + 16, inf[0] = (uint32_t)units, inf[1] = shift; break;
+        case KBO_PLAN_PART_PC_MU: buf = &dc.pc_mu, need = kbo::pack_text_mu_bytes(units) + 4, inf[0] = (uint32_t)units, inf[1] = shift; break;
+        case KBO_PLAN_PART_PC_MC: buf = &dc.pc_mc, need = kbo::maptext::kCells / 8u, inf[0] = (uint32_t)units, inf[1] = shift; break;
+        case KBO_PLAN_PART_SEED_TAB: buf = &dc.seed_tab, need = dc.seed_d ? (size_t)8 << (2u * dc.seed_d) : 0, inf[0] = dc.seed_d, inf[1] = seed_on_device; break;
+        case KBO_PLAN_PART_SEED_POS: buf = &dc.seed_pos, need = (size_t)4 << (2u * dc.seed_d), inf[0] = dc.seed_d, inf[1] = seed_on_device; break;
+        case KBO_PLAN_PART_DFILT: buf = &dc.dfilt, need = dc.dfilt_bases ? ((size_t)1 << (2u * dc.dfilt_bases)) / 8u : 0, inf[0] = dc.dfilt_bases, inf[1] = dc.dtab_order; break;
+        case KBO_PLAN_PART_ANCHOR: buf = &dc.anchor, need = dc.anchor_bits ? (size_t)8 << dc.anchor_bits : 0, inf[0] = dc.anchor_bits, inf[1] = dc.dtab_order; break;
+        default: buf = &dc.sub_clean, need = kbo::mapsubst::bitmap_words(units) * 4, inf[0] = (uint32_t)units, inf[1] = dc.dtab_order, inf[2] = dc.sub_thr, inf[3] = dc.sub_anch ? 1u : 0u; break;
+        }
+        if (!buf->p) need = 0; // (a part this copy does not have)
+        if (out && need) {
+            KBO_REQUIRE(*n_bytes >= need, KBO_E_BAD_ARG, "buffer smaller than the part");
+            int prev = current_device();
+            if (prev != dev) HIP_OK(hipSetDevice(dev));
+            const hipError_t e = hipMemcpy(out, buf->p, need, hipMemcpyDeviceToHost);
+            if (prev != dev) (void)hipSetDevice(prev);
+            HIP_OK(e);
+        }
+        *n_bytes = need;
+        for (int i = 0; i < 4; i++) info[i] = need ? inf[i] : 0u;
     });
 }
 

@@ -134,6 +134,21 @@ class SbwtIndexVariant:
         check(lib().kbo_index_depth_table(self._h, device, 0, None, C.byref(nb), C.byref(order)))
         return int(order.value)
 
+    def plan_part(self, name, device=-1):
+        """(array, info[4]) - one of the plan structures the device copy built for itself, as it lies on the device, slack included
+        (kbo_hip_tuning.h kbo_index_plan_part): name in _capi.PLAN_PARTS; pc_tm as uint32[n_units, 2] {digits, marks}, seed_tab as
+        uint32[4^seed_d, 2] {l, r}, anchor as uint64 slots, pc_mu as bytes, the others as uint32 words.  An empty array: no such part."""
+        part, dtype = _capi.PLAN_PARTS[name]
+        nb, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        check(lib().kbo_index_plan_part(self._h, device, part, None, C.byref(nb), info))
+        out = np.zeros(nb.value, dtype=np.uint8)
+        if nb.value:
+            check(lib().kbo_index_plan_part(self._h, device, part, out.ctypes.data, C.byref(nb), info))
+        out = out.view(dtype)
+        if name in ("pc_tm", "seed_tab"):
+            out = out.reshape(-1, 2)
+        return out, [int(v) for v in info]
+
     def recovery_lines(self):
         """uint8[n_lines, 128] - the recovery lines of the guided walk (kbo_hip.h: kbo_index_recovery_lines)."""
         nb = C.c_size_t(0)

@@ -168,6 +168,25 @@ def test_index_opts_round_trip_and_checks(tmp_path):
     assert L.kbo_index_set_opts(None, C.byref(o)) == -4 and L.kbo_index_get_opts(sbwt._h, None) == -4
 
 
+def test_plan_part_argument_checks_need_no_gpu():
+    """kbo_index_plan_part (kbo_hip_tuning.h) refuses a NULL index, a NULL n_bytes or info and a part out of range before it touches a
+    device, and the binding knows every part by the header's number"""
+    L = kbo_amd.lib()
+    sbwt, _ = kbo_amd.build([b"ACGTTGCATGCATGCAAGTCGATCGATTTGACCATG" * 3], kbo_amd.BuildOpts(k=7))
+    nb, info = C.c_size_t(0), (C.c_uint32 * 4)()
+    assert L.kbo_index_plan_part(None, -1, 0, None, C.byref(nb), info) == -4
+    assert L.kbo_index_plan_part(sbwt._h, -1, 0, None, None, info) == -4
+    assert L.kbo_index_plan_part(sbwt._h, -1, 0, None, C.byref(nb), None) == -4
+    hdr = open(os.path.join(ROOT, "include", "kbo_hip_tuning.h")).read()
+    parts = {m[0].lower(): int(m[1]) for m in re.findall(r"#define KBO_PLAN_PART_([A-Z_]+) (\d+)", hdr)}
+    n_parts = int(re.search(r"#define KBO_PLAN_PARTS (\d+)", hdr).group(1))
+    assert parts == {name: part for name, (part, _) in _capi.PLAN_PARTS.items()} and sorted(parts.values()) == list(range(n_parts))
+    for part in (-1, n_parts, 1 << 20):
+        assert L.kbo_index_plan_part(sbwt._h, -1, part, None, C.byref(nb), info) == -4
+    with pytest.raises(KeyError):
+        sbwt.plan_part("depth_table")
+
+
 def test_compute_fails_loudly_without_gpu():
     """No CPU fallback: on a machine without a HIP device every compute call is an error."""
     import torch
