@@ -259,6 +259,31 @@ pub mod ffi {
                                             d_screen_stats: *mut super::RefsetScreenStats, stream: *mut c_void) -> c_int;
         pub fn kbo_refset_last_call(out: *mut u64) -> c_int;
         pub fn kbo_refset_spell_row(set: *const KboRefset, r: usize, row: u32, out: *mut u8) -> c_int;
+        // positions, segments, depth: the single-index path in SOURCE coordinates (kbo_hip.h).  add_positions makes the table on
+        // `device` from the sequences the index was built from; segments_dev / depth_finish_dev compose behind kbo_ms_batch_dev with
+        // intervals on one stream; segments_batch is the host form (segs released by kbo_free)
+        pub fn kbo_index_add_positions(idx: *mut KboIndex, seqs: *const *const u8, lens: *const usize, n_seqs: usize, add_revcomp: c_int,
+                                       device: c_int) -> c_int;
+        pub fn kbo_index_has_positions(idx: *const KboIndex) -> c_int;
+        pub fn kbo_index_positions_bytes(idx: *const KboIndex) -> u64;
+        pub fn kbo_index_positions(idx: *const KboIndex, out: *mut u32, n_rows: *mut usize) -> c_int;
+        pub fn kbo_index_source_offsets(idx: *const KboIndex, out: *mut u64, n: *mut usize) -> c_int;
+        pub fn kbo_index_source_bases(idx: *const KboIndex) -> u64;
+        pub fn kbo_index_positions_to_device(idx: *mut KboIndex, device: c_int) -> c_int;
+        pub fn kbo_positions_from_ms_host(k: u32, n_sets: u64, d: *const u8, lo: *const u32, offsets: *const u64, n_seqs: usize,
+                                          src_off: *const u64, rev: c_int, entries_inout: *mut u32, n_not_full: *mut u64) -> c_int;
+        pub fn kbo_segments_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
+        pub fn kbo_segments_dev(idx: *mut KboIndex, d_ms: *const u8, d_lo: *const u32, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                                bridge: u32, strand: u32, d_segs: *mut super::SeqSegment, capacity: usize, d_n_segs: *mut u64,
+                                d_delta: *mut u32, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+        pub fn kbo_segments_from_ms_host(entries: *const u32, n_rows: u64, k: u32, d: *const u8, lo: *const u32, offsets: *const u64,
+                                         n_seqs: usize, bridge: u32, strand: u32, segs: *mut super::SeqSegment, capacity: usize,
+                                         n_segs: *mut u64, delta: *mut u32, source_bases: u64) -> c_int;
+        pub fn kbo_depth_work_bytes(idx: *const KboIndex) -> usize;
+        pub fn kbo_depth_finish_dev(idx: *mut KboIndex, d_delta: *const u32, d_depth: *mut u32, d_work: *mut c_void, work_bytes: usize,
+                                    stream: *mut c_void) -> c_int;
+        pub fn kbo_segments_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
+                                  segs: *mut *mut super::SeqSegment, n_segs: *mut u64, depth_out: *mut u32) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -409,6 +434,21 @@ pub struct RefLocus {
     pub ref_last: u32,
     pub flags: u32,
     pub n_tested: u32,
+}
+
+/// `kbo_seq_segment` (28 bytes): a collinear block of exact k-mer matches of sequence `seq` in source coordinates.  `q_first` /
+/// `q_last`: the first base of the first / last anchor's k-mer in the sequence; `pos_first` / `pos_last`: their positions on the
+/// sources.  `flags`: bit 0 REV, bit 2 / 3 the first / last anchor's k-mer occurs more than once.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct SeqSegment {
+    pub seq: u32,
+    pub strand: u32,
+    pub q_first: u32,
+    pub q_last: u32,
+    pub pos_first: u32,
+    pub pos_last: u32,
+    pub flags: u32,
 }
 
 /// `KBO_COVER_NO_ENTRIES` / `KBO_COVER_OVERFLOW`: bits 0 and 1 of `RefCover::flags`.

@@ -1185,6 +1185,99 @@ int kbo_run_lengths_seq_dev(const uint8_t *d_chars, const uint64_t *d_offsets, s
 size_t kbo_sparse_runs_work_bytes(size_t n_seqs, uint64_t total_words);
 int kbo_sparse_runs_dev(const uint32_t *d_words, const uint64_t *d_offsets, size_t n_seqs, size_t max_seq_len, void *d_work,
                         kbo_aln_run *d_runs, size_t capacity, uint32_t *d_n_runs, void *stream);
+/* ------------------------------------------------------------------ Positions, segments, depth: a batch in SOURCE coordinates
+ * Where on the sequences an index was built from a walked sequence lies, and how deep a batch piles up on every base of them - for
+ * the single-index path, at any index size (the arithmetic: kbo_amd/csrc/index_locate.hpp, the kernels:
+ * kbo_amd/csrc/locate_kernels.hip).  A handle without positions behaves byte for byte as it does without this section.
+ *
+ * THE POSITION TABLE.  The SOURCE coordinates are those of `seqs` concatenated in order with no separator: base j of sequence s is
+ * src_off[s] + j.  An OCCURRENCE of a k-mer x is (p, FWD) when x equals source[p, p + k) and (p, REV) when the reverse complement of x
+ * does (REV only with add_revcomp != 0), the window inside one sequence and inside a maximal run of A, C, G, T of at least k bases.
+ * The entry of x's row is the reference sets' (above): of x's occurrences the one with FWD before REV and then the smallest p, bits
+ * 0 .. 29 p, bit 30 REV, bit 31 (KBO_LOCUS_MULTI) set when x has more than one occurrence; a row that is no full k-mer holds
+ * KBO_POS_NONE.
+ * kbo_index_add_positions makes the table on `device` (-1: the current one) from the sequences the index was built from, on any
+ * unsharded handle - built, loaded, or adopted through kbo_index_from_parts: it uploads them in slabs, reverses and complements each
+ * slab on the device when add_revcomp is set (kbo_revcomp_batch_dev), walks them with kbo_ms_batch_dev's interval walk - at depth k an
+ * interval is one row, the row of the window that ends there - and lets a lane per base keep the smallest and the largest occurrence of
+ * its row (integer atomics: the same table whatever the arrival order).  It is a build step: it allocates, synchronises and reads two
+ * counters back.  Every window of every indexed stretch must reach depth k, and the rows with an entry must number
+ * kbo_index_n_kmers: otherwise the sequences are not the index's (or add_revcomp is not what it was built with) and the call fails
+ * with KBO_E_BAD_ARG.  A second call replaces the table; a failed one leaves the handle without positions.  Before any HIP call:
+ * KBO_E_BAD_ARG for null arguments or n_seqs == 0, KBO_E_UNSUPPORTED for a sharded handle and for sources of 2^30 bases or more (p has
+ * 30 bits).  The handle keeps a host copy (kbo_index_positions: out may be NULL for *n_rows alone), the copy on `device`, and src_off
+ * (kbo_index_source_offsets: n_seqs + 1 values, out may be NULL for *n alone; kbo_index_source_bases is the last);
+ * kbo_index_positions_bytes is what the host copy and src_off take, 0 without positions.  kbo_index_positions_to_device is idempotent
+ * and the one place a further device's copy is made.  The getters give KBO_E_BAD_ARG for a handle without positions.
+ * kbo_index_save and kbo_index_load do NOT carry the table: a loaded handle has none until kbo_index_add_positions is called on it.
+ * kbo_positions_from_ms_host restates the table's rule on the CPU (no HIP call; a test hook and a yardstick): d and lo are the MS bytes
+ * and interval starts of one strand of the sources walked sequence by sequence (`offsets`; rev != 0: of every sequence's reverse
+ * complement as kbo_revcomp_batch makes it), src_off where each begins in source coordinates; every base at depth k is merged into
+ * entries_inout (n_sets words, KBO_POS_NONE before the first call), one strand a call.  *n_not_full (or NULL) counts the windows of
+ * the sequences that did not reach depth k.
+ *
+ * SEGMENTS.  An ANCHOR of a walked sequence is a position q whose window [q, q + k) has depth k at its last base; its entry is the
+ * table's word for that base's row.  Of a sequence's anchors by ascending q, two neighbours a < b are JOINED when b.q - a.q <= 1 +
+ * bridge, both have the same REV bit and both lie on one diagonal (FWD: p - q equal; REV: p + q equal); MULTI does not matter.  A
+ * SEGMENT is a maximal chain of joined neighbours: a collinear block of exact k-mer matches.  bridge = 0 joins only adjacent windows,
+ * bridge = k carries a segment across a lone substitution, bridge > 255 is KBO_E_BAD_ARG.  An insertion or deletion changes the
+ * diagonal and never joins.  A MULTI k-mer is placed at its stored occurrence only, so a read inside the second copy of an exact
+ * repeat is reported at the first, and a read that leaves the repeat there changes its diagonal and starts a new segment; every
+ * occurrence of a MULTI k-mer needs an occurrence list the handle does not keep and is out of scope, as for the reference sets.
+ * kbo_segments_dev takes what kbo_ms_batch_dev wrote with intervals (d_ms, d_lo: total_bases values; d_offsets: n_seqs + 1) and is a
+ * device-resident call like the others: everything is enqueued on `stream`, nothing is synchronised, read back or allocated, and no
+ * byte of d_work (16-byte aligned) beyond kbo_segments_work_bytes() - exact: a byte per base, 8 bytes per 2048 bases, 8 per 2048 of
+ * those, each rounded up to 16 - is touched.  Records are in (seq, q_first) order; record x is written iff x < capacity, *d_n_segs
+ * (8-byte aligned) is the full count, and nothing at or behind element `capacity` is written (d_segs may be NULL when capacity == 0).
+ * `strand` is copied into the records as given.  Sequences shorter than k, or empty, contribute nothing.  Errors, before anything is
+ * enqueued and in this order: KBO_E_BAD_ARG for null or misaligned pointers and for bridge > 255; KBO_E_EMPTY_QUERY for n_seqs == 0;
+ * KBO_E_UNSUPPORTED for total_bases + 16 > 2^32 or n_seqs >= 2^28 and for a sharded handle; KBO_E_BAD_ARG for a handle without
+ * positions, a short work_bytes, and a handle without positions on the current device.
+ * kbo_segments_from_ms_host is the same call restated on the CPU (host arrays; entries: n_rows words; delta, or NULL: source_bases + 1
+ * words): byte-identical records, count and delta.
+ *
+ * DEPTH.  Base j of the sources is covered by a FWD segment when j lies in [pos_first, pos_last + k) and by a REV segment when it lies
+ * in [pos_last, pos_first + k); DEPTH[j] is the number of segments that cover j, over every call that added to the same delta array -
+ * a read counts once per base however many of its k-mers cover it, which is what tells it from kbo_cover_refset's D.  With d_delta !=
+ * NULL (kbo_index_source_bases + 1 words, zeroed once by the caller, shared by any number of batches and strands) the anchor that
+ * starts a segment and the anchor that ends it do one integer atomic add each: +1 where the covered range begins and -1 behind it.
+ * kbo_depth_finish_dev writes the inclusive prefix sums of delta to d_depth (source_bases words): exact modulo 2^32 and independent
+ * of the order of the batches.  d_work: kbo_depth_work_bytes(idx), 4 bytes per 2048 bases rounded up to 16; 0 for a handle without
+ * positions.  KBO_E_BAD_ARG for null or misaligned pointers, a handle without positions and a short work_bytes.
+ *
+ * kbo_segments_batch is the host form: upload, the '-' strand made on the device (in the coordinates of the reverse-complemented
+ * sequence, as everywhere), the interval walk, kbo_segments_dev's kernels per strand - once to count, once to write - the depth
+ * finish, one download.  *segs is malloc'ed (kbo_free), in (seq, strand with KBO_STRAND_FWD first, q_first) order; depth_out (or
+ * NULL) receives source_bases words, written, not added to.  Errors: KBO_E_BAD_ARG for strands outside 1 .. 3, null arguments and
+ * bridge > 255, KBO_E_UNSUPPORTED for a sharded handle, KBO_E_BAD_ARG for a handle without positions, then the batch as
+ * kbo_find_batch_strands checks it. */
+typedef struct {
+    uint32_t seq, strand;         /* index in the batch; the strand argument as given */
+    uint32_t q_first, q_last;     /* first base of the first / last anchor's k-mer in the sequence */
+    uint32_t pos_first, pos_last; /* their entries' p, source coordinates */
+    uint32_t flags;               /* bit 0: REV; bit 2 / 3: the first / last anchor's entry is MULTI */
+} kbo_seq_segment;                /* 28 bytes */
+int kbo_index_add_positions(kbo_index_t *idx, const uint8_t *const *seqs, const size_t *lens, size_t n_seqs, int add_revcomp, int device);
+int kbo_index_has_positions(const kbo_index_t *idx);        /* 1 or 0 */
+uint64_t kbo_index_positions_bytes(const kbo_index_t *idx);
+int kbo_index_positions(const kbo_index_t *idx, uint32_t *out, size_t *n_rows);
+int kbo_index_source_offsets(const kbo_index_t *idx, uint64_t *out, size_t *n);
+uint64_t kbo_index_source_bases(const kbo_index_t *idx);
+int kbo_index_positions_to_device(kbo_index_t *idx, int device);
+int kbo_positions_from_ms_host(uint32_t k, uint64_t n_sets, const uint8_t *d, const uint32_t *lo, const uint64_t *offsets, size_t n_seqs,
+                               const uint64_t *src_off, int rev, uint32_t *entries_inout, uint64_t *n_not_full);
+size_t kbo_segments_work_bytes(size_t n_seqs, uint64_t total_bases);
+int kbo_segments_dev(kbo_index_t *idx, const uint8_t *d_ms, const uint32_t *d_lo, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                     uint32_t bridge, uint32_t strand, kbo_seq_segment *d_segs, size_t capacity, uint64_t *d_n_segs, uint32_t *d_delta,
+                     void *d_work, size_t work_bytes, void *stream);
+int kbo_segments_from_ms_host(const uint32_t *entries, uint64_t n_rows, uint32_t k, const uint8_t *d, const uint32_t *lo,
+                              const uint64_t *offsets, size_t n_seqs, uint32_t bridge, uint32_t strand, kbo_seq_segment *segs, size_t capacity,
+                              uint64_t *n_segs, uint32_t *delta, uint64_t source_bases);
+size_t kbo_depth_work_bytes(const kbo_index_t *idx);
+int kbo_depth_finish_dev(kbo_index_t *idx, const uint32_t *d_delta, uint32_t *d_depth, void *d_work, size_t work_bytes, void *stream);
+int kbo_segments_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands,
+                       kbo_seq_segment **segs, uint64_t *n_segs, uint32_t *depth_out);
+
 /* ---- alignment summaries (kbo_aln_summary, above) of device-resident batches; asynchronous, the library never synchronises.
  * kbo_summary_batch_dev: kbo::matches over the batch as kbo_map_batch_dev_tail runs it (format = 0: the same routes, streams and
  * second pass on `tail_stream`; the records are complete when BOTH streams have reached this point), with d_summary_out - n_seqs records,

@@ -330,6 +330,17 @@ int kbo_run_lengths_seq_host(const uint8_t *aln, const uint64_t *offsets, size_t
 int kbo_run_lengths_seq_host_each(const uint8_t *aln, const uint64_t *offsets, size_t n_seqs, size_t max_gap_len, size_t chunk, size_t group,
                                   size_t min_len, uint32_t *records, size_t capacity, uint32_t *first);
 
+/* ------------------------------------------------------------------ kbo_index_add_positions, kbo_segments_dev */
+/* positions of a tile of locate_kernels.hip and of the halo it reads on either side (the largest bridge + 1), and the values a
+ * workgroup of the three-pass scan takes; the getter returns what the kernels were compiled with (any pointer may be NULL) */
+#define KBO_SEGMENTS_TILE 2048
+#define KBO_SEGMENTS_HALO 256
+#define KBO_SEGMENTS_MAX_BRIDGE 255
+int kbo_segments_geometry(uint32_t *tile, uint32_t *halo, uint32_t *scan_chunk);
+/* test hook: source bases a slab of kbo_index_add_positions adds to the table (each slab is walked with the k - 1 bases in front of
+ * it); 0 = the default, 32 Mi.  Any value gives the same table. */
+int kbo_set_positions_slab_bases(uint64_t bases);
+
 /* ------------------------------------------------------------------ kbo_derand_translate_dev and the host batches' stage behind the walk */
 /* test hook: the derandomize + translate stage of kbo_matches_batch / kbo_map_batch / kbo_find_batch / kbo_map_batch_opts over MS bytes
  * of the caller's making instead of a walk's.  ms (offsets[n_seqs] bytes, any values <= k), offsets (n_seqs + 1 values from 0, ascending)

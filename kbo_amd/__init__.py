@@ -28,6 +28,8 @@ from .refset import RefSet, best_refset, best_refset_dev, find_refset, find_refs
 from .refset import locate_refset, locate_refset_dev, locus_interval  # noqa: F401,E402
 from .refset import cover_refset, cover_refset_dev  # noqa: F401,E402
 from .refset import call_refset, call_refset_dev, variant_chars  # noqa: F401,E402
+from . import locate  # noqa: F401,E402
+from .locate import add_positions, depth_finish_dev, segment_source, segments, segments_dev  # noqa: F401,E402
 
 
 @dataclass

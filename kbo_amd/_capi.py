@@ -156,6 +156,9 @@ SYMBOLS = [
     "kbo_refset_cover_bases", "kbo_refset_cover_offsets", "kbo_cover_refset", "kbo_cover_refset_host",
     "kbo_cover_refset_dev_work_bytes", "kbo_cover_refset_dev", "kbo_call_refset", "kbo_call_refset_host", "kbo_ref_calls_free",
     "kbo_call_refset_dev_work_bytes", "kbo_call_refset_dev", "kbo_call_refset_screened_dev_work_bytes", "kbo_call_refset_screened_dev",
+    "kbo_index_add_positions", "kbo_index_has_positions", "kbo_index_positions_bytes", "kbo_index_positions", "kbo_index_source_offsets",
+    "kbo_index_source_bases", "kbo_index_positions_to_device", "kbo_positions_from_ms_host", "kbo_segments_work_bytes", "kbo_segments_dev",
+    "kbo_segments_from_ms_host", "kbo_depth_work_bytes", "kbo_depth_finish_dev", "kbo_segments_batch",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -170,6 +173,7 @@ TUNING_SYMBOLS = [
     "kbo_refset_candidates_host", "kbo_set_refset_prefilter_max_bits", "kbo_refset_last_prefilter",
     "kbo_refset_last_call", "kbo_refset_spell_row", "kbo_call_refset_host_indexed", "kbo_refset_kmer_depths_host",
     "kbo_refset_resolve_word_host", "kbo_refset_resolve_words_check", "kbo_refset_order_sites_host",
+    "kbo_segments_geometry", "kbo_set_positions_slab_bases",
 ]
 
 _lib = None
@@ -433,6 +437,22 @@ def lib():
     L.kbo_refset_last_call.argtypes = [vp]
     L.kbo_refset_spell_row.argtypes = [vp, sz, C.c_uint32, vp]
     L.kbo_derand_translate_host.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+    L.kbo_index_add_positions.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_int, C.c_int]
+    L.kbo_index_has_positions.argtypes = [vp]
+    L.kbo_index_positions_bytes.argtypes = [vp]; L.kbo_index_positions_bytes.restype = u64
+    L.kbo_index_positions.argtypes = [vp, vp, C.POINTER(sz)]
+    L.kbo_index_source_offsets.argtypes = [vp, vp, C.POINTER(sz)]
+    L.kbo_index_source_bases.argtypes = [vp]; L.kbo_index_source_bases.restype = u64
+    L.kbo_index_positions_to_device.argtypes = [vp, C.c_int]
+    L.kbo_positions_from_ms_host.argtypes = [u32, u64, vp, vp, vp, sz, vp, C.c_int, vp, C.POINTER(u64)]
+    L.kbo_segments_work_bytes.argtypes = [sz, u64]; L.kbo_segments_work_bytes.restype = sz
+    L.kbo_segments_dev.argtypes = [vp, vp, vp, vp, sz, u64, u32, u32, vp, sz, vp, vp, vp, sz, vp]
+    L.kbo_segments_from_ms_host.argtypes = [vp, u64, u32, vp, vp, vp, sz, u32, u32, vp, sz, C.POINTER(u64), vp, u64]
+    L.kbo_depth_work_bytes.argtypes = [vp]; L.kbo_depth_work_bytes.restype = sz
+    L.kbo_depth_finish_dev.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.kbo_segments_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, C.POINTER(vp), C.POINTER(u64), vp]
+    L.kbo_segments_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.kbo_set_positions_slab_bases.argtypes = [u64]
     _lib = L
     return L
 

@@ -4,7 +4,8 @@
 //   kbo_capi.cpp      the extern "C" entry points,
 //   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
 //   batch_route.cpp   the kernel route of a batch, for host slabs and device calls alike (batch_route.hpp),
-//   build_device.cpp  kbo_index_build_device (the index built by the device).
+//   build_device.cpp  kbo_index_build_device (the index built by the device),
+//   index_locate.cpp  the position table of an index, the segments of a batch and the depth of the sources.
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -52,6 +53,7 @@ struct DevCopy {
     DevBuf sub_clean;                // ... and a bit per text position: a lone substitution there needs no table (map_subst.hpp), for the
     uint32_t sub_thr = 0;            // proof's windows at this threshold - what a call with default options gets on this index -
     bool sub_anch = false;           // with or without anchors
+    DevBuf positions;                // the position table (index_locate.cpp): a word per row, empty without one
     // what making this copy cost (kbo_index_device_layout): seconds of host work / device builds / uploads, by part
     bool plan_built = false;         // path cover, recovery lines, tables: made by the first use that pays for them (device_index.cpp)
     bool plan_failed = false;        // ... or could not be made (no memory): not tried again on every call; the copy walks plainly
@@ -112,6 +114,10 @@ struct kbo_index {
     // the path cover of the plan-guided walk once it has been computed (or read from an index file), guarded by `mu`:
     // every device copy uploads it from here, kbo_index_save writes it (laying it out is a 26 s pointer chase per 10^8 rows)
     std::unique_ptr<kbo::PathCover> cover;
+    // the position table (kbo_index_add_positions, index_locate.cpp), guarded by `mu`: a word per row, and where every source sequence
+    // begins in source coordinates (+ their end); both empty without one.  Device copies keep theirs in DevCopy::positions
+    std::vector<uint32_t> positions;
+    std::vector<uint64_t> src_off;
     // A SHARDED index (kbo_capi.cpp build_sharded): an index whose rows would not fit 32-bit row numbers (a human genome
     // with its reverse complements: 6.2 * 10^9 rows) is built as several ordinary indexes over disjoint parts of the input -
     // groups of sequences, forward and reverse-complement strands apart - and this handle only holds them: host.k,

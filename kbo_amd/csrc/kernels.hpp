@@ -821,6 +821,28 @@ constexpr int kWalkThreads = 64; // default workgroup size (waves are independen
 void set_walk_threads(int threads); // tuning: 64, 128 or 256
 void set_walk_experiment(int lane_limit, int dummy_lds_bytes); // experiments behind DESIGN.md section 6
 void set_walk_rare(int period);            // tuning: hot-loop iterations between rare-block visits
+// ---- locate_kernels.hip (the arithmetic, the tile and the d_work layout: index_locate.hpp)
+// a walked slab of the sources into the rows' smallest / largest occurrence (d_min cleared to ones, d_max to zeros beforehand) and the
+// bases with a full depth counted; then d_min turned into the entries and the rows that have one counted
+hipError_t launch_locate_mark(const uint8_t *d_ms, const uint32_t *d_lo, uint32_t len, uint32_t k, uint32_t n_rows, uint32_t base, bool rev,
+                              uint32_t *d_min, uint32_t *d_max, uint64_t *d_n_full, hipStream_t stream);
+hipError_t launch_locate_entries(uint32_t *d_min, const uint32_t *d_max, uint32_t n_rows, uint64_t *d_n_entries, hipStream_t stream);
+struct SegmentArgs {
+    const uint8_t *ms;       // a batch as the interval walk left it
+    const uint32_t *lo;
+    const uint64_t *off;
+    const uint32_t *entries; // n_rows words
+    uint32_t n_seqs, n_rows, k, bridge, strand, n_delta;
+    uint64_t total, capacity;
+    uint32_t *segs;          // capacity records of 7 words
+    uint64_t *n_segs;
+    uint32_t *delta;         // n_delta words, or null
+    void *work;              // idxlocate::seg_work(total).bytes
+};
+hipError_t launch_segments(const SegmentArgs &a, hipStream_t stream);
+// d_depth = the inclusive prefix sums of n words of d_delta; d_work: idxlocate::depth_work(n) bytes
+hipError_t launch_depth_finish(const uint32_t *d_delta, uint32_t *d_depth, uint64_t n, void *d_work, hipStream_t stream);
+
 void set_pair_min_depth(int d);            // tuning: depth from which two-base steps are tried
 constexpr uint32_t kRankRows = 96; // rows per 16-byte rank block (== kRankRowsPerBlock)
 

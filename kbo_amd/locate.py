@@ -1,0 +1,149 @@
+"""Positions, segments, depth (kbo_hip.h): where a batch lies on the sequences an index was built from.
+
+add_positions() gives an index its position table; segments() turns a batch into collinear blocks of exact k-mer matches in source
+coordinates and, when asked, the depth of every source base; segments_dev() / depth_finish_dev() are the same over device buffers.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._capi import check, lib
+from .index import SbwtIndexVariant, _u8
+
+STRAND_FWD, STRAND_REV = 1, 2
+POS_NONE, MULTI, REV, POS_MASK = 0xFFFFFFFF, 1 << 31, 1 << 30, (1 << 30) - 1
+SEG_REV, SEG_FIRST_MULTI, SEG_LAST_MULTI = 1, 4, 8
+
+# kbo_seq_segment
+SEGMENT_DTYPE = np.dtype([(n, "<u4") for n in ("seq", "strand", "q_first", "q_last", "pos_first", "pos_last", "flags")])
+
+
+def _batch(query_seqs):
+    """(concat uint8, offsets uint64) of a list of sequences, or the pair itself"""
+    if isinstance(query_seqs, tuple) and len(query_seqs) == 2 and isinstance(query_seqs[1], np.ndarray):
+        return np.ascontiguousarray(query_seqs[0], dtype=np.uint8), np.ascontiguousarray(query_seqs[1], dtype=np.uint64)
+    seqs = [_u8(s) for s in query_seqs]
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if seqs:
+        offsets[1:] = np.cumsum([len(s) for s in seqs])
+    concat = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint8)
+    return np.ascontiguousarray(concat, dtype=np.uint8), offsets
+
+
+def add_positions(sbwt, seqs, add_revcomp=False, device=-1):
+    """kbo_index_add_positions: the position table of `sbwt`, made on `device` from the sequences it was built from"""
+    seqs = [bytes(_u8(s)) for s in seqs]
+    arr = (C.c_char_p * max(1, len(seqs)))(*seqs)
+    lens = (C.c_size_t * max(1, len(seqs)))(*[len(s) for s in seqs])
+    check(lib().kbo_index_add_positions(sbwt._h, arr, lens, len(seqs), int(bool(add_revcomp)), int(device)))
+    return sbwt
+
+
+def has_positions(sbwt):
+    return bool(lib().kbo_index_has_positions(sbwt._h))
+
+
+def positions(sbwt):
+    """uint32[n_sets]: the entry of every row (kbo_index_positions)"""
+    n = C.c_size_t(0)
+    check(lib().kbo_index_positions(sbwt._h, None, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.uint32)
+    check(lib().kbo_index_positions(sbwt._h, out.ctypes.data, C.byref(n)))
+    return out
+
+
+def source_offsets(sbwt):
+    """uint64[n_seqs + 1]: where every source sequence begins in source coordinates (kbo_index_source_offsets)"""
+    n = C.c_size_t(0)
+    check(lib().kbo_index_source_offsets(sbwt._h, None, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.uint64)
+    check(lib().kbo_index_source_offsets(sbwt._h, out.ctypes.data, C.byref(n)))
+    return out
+
+
+SbwtIndexVariant.positions = positions
+SbwtIndexVariant.source_offsets = source_offsets
+SbwtIndexVariant.has_positions = has_positions
+
+
+def segments(query_seqs, sbwt, bridge=None, strands=STRAND_FWD, depth=False):
+    """kbo_segments_batch -> records (SEGMENT_DTYPE) in (seq, strand, q_first) order, or (records, depth uint32[source bases]).
+    query_seqs: a list of sequences or (concat, offsets); bridge: None = k"""
+    concat, offsets = _batch(query_seqs)
+    b = sbwt.k() if bridge is None else int(bridge)
+    p, n = C.c_void_p(), C.c_uint64(0)
+    d = np.zeros(int(lib().kbo_index_source_bases(sbwt._h)), dtype=np.uint32) if depth else None
+    check(lib().kbo_segments_batch(sbwt._h, concat.ctypes.data if len(concat) else None, offsets.ctypes.data, len(offsets) - 1, min(b, 0xFFFFFFFF), int(strands),
+                                   C.byref(p), C.byref(n), d.ctypes.data if depth else None))
+    try:
+        recs = np.frombuffer(C.string_at(p.value, n.value * SEGMENT_DTYPE.itemsize), dtype=SEGMENT_DTYPE).copy()
+    finally:
+        lib().kbo_free(p)
+    return (recs, d) if depth else recs
+
+
+def segments_work_bytes(n_seqs, total_bases):
+    return int(lib().kbo_segments_work_bytes(n_seqs, total_bases))
+
+
+def segments_dev(sbwt, ms, lo, offsets, n_seqs, total_bases, segs, capacity, n_segs, work, work_bytes=None, bridge=None, strand=STRAND_FWD,
+                 delta=None, stream=None):
+    """kbo_segments_dev over torch tensors (or raw device pointers) as kbo_ms_batch_dev left them; everything on `stream`"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    b = sbwt.k() if bridge is None else int(bridge)
+    wb = segments_work_bytes(n_seqs, total_bases) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_segments_dev(sbwt._h, ptr(ms), ptr(lo), ptr(offsets), n_seqs, total_bases, b, int(strand), ptr(segs), int(capacity), ptr(n_segs),
+                                 ptr(delta), ptr(work), wb, s))
+
+
+def depth_work_bytes(sbwt):
+    return int(lib().kbo_depth_work_bytes(sbwt._h))
+
+
+def depth_finish_dev(sbwt, delta, depth, work, work_bytes=None, stream=None):
+    """kbo_depth_finish_dev: depth = the inclusive prefix sums of delta"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    wb = depth_work_bytes(sbwt) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_depth_finish_dev(sbwt._h, ptr(delta), ptr(depth), ptr(work), wb, s))
+
+
+def segment_source(segs, src_off):
+    """(source sequence, offset of the segment's lowest base within it, orientation 0 = FWD / 1 = REV) of every record; src_off: the
+    index's source_offsets()"""
+    off = np.asarray(src_off, dtype=np.uint64)
+    low = np.where(segs["flags"] & SEG_REV, segs["pos_last"], segs["pos_first"]).astype(np.uint64)
+    src = np.searchsorted(off, low, side="right") - 1
+    return src, low - off[src], (segs["flags"] & SEG_REV).astype(np.uint8)
+
+
+def positions_from_ms_host(k, n_sets, d, lo, offsets, src_off, rev, entries):
+    """kbo_positions_from_ms_host: one strand's walk of the sources merged into `entries` (uint32[n_sets], in place); returns n_not_full"""
+    d = np.ascontiguousarray(d, dtype=np.uint8)
+    lo = np.ascontiguousarray(lo, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    src_off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    assert entries.dtype == np.uint32 and entries.flags.c_contiguous and len(entries) == n_sets
+    miss = C.c_uint64(0)
+    check(lib().kbo_positions_from_ms_host(k, n_sets, d.ctypes.data, lo.ctypes.data, offsets.ctypes.data, len(offsets) - 1, src_off.ctypes.data, int(rev),
+                                           entries.ctypes.data, C.byref(miss)))
+    return int(miss.value)
+
+
+def segments_from_ms_host(entries, k, d, lo, offsets, bridge, strand, capacity, source_bases, delta=None):
+    """kbo_segments_from_ms_host -> (records written, count); delta (uint32[source_bases + 1]) is added to in place"""
+    entries = np.ascontiguousarray(entries, dtype=np.uint32)
+    d = np.ascontiguousarray(d, dtype=np.uint8)
+    lo = np.ascontiguousarray(lo, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    segs = np.zeros(capacity, dtype=SEGMENT_DTYPE)
+    n = C.c_uint64(0)
+    if delta is not None:
+        assert delta.dtype == np.uint32 and delta.flags.c_contiguous and len(delta) == source_bases + 1
+    check(lib().kbo_segments_from_ms_host(entries.ctypes.data, len(entries), k, d.ctypes.data, lo.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                          bridge, strand, segs.ctypes.data if capacity else None, capacity, C.byref(n),
+                                          delta.ctypes.data if delta is not None else None, source_bases))
+    return segs[:min(capacity, n.value)], int(n.value)
