@@ -284,6 +284,16 @@ pub mod ffi {
                                     stream: *mut c_void) -> c_int;
         pub fn kbo_segments_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
                                   segs: *mut *mut super::SeqSegment, n_segs: *mut u64, depth_out: *mut u32) -> c_int;
+        // placement: the segments of every sequence chained to one record, behind kbo_segments_dev on the same stream (merge != 0:
+        // into what d_place holds - the second strand's call); place_from_segments_host is the CPU restatement, place_batch the host form
+        pub fn kbo_place_work_bytes(n_seqs: usize, n_segs_capacity: usize) -> usize;
+        pub fn kbo_place_dev(idx: *mut KboIndex, d_segs: *const super::SeqSegment, d_n_segs: *const u64, capacity: usize, n_seqs: usize,
+                             max_gap: u32, max_indel: u32, merge: c_int, d_place: *mut super::SeqPlace, d_work: *mut c_void,
+                             work_bytes: usize, stream: *mut c_void) -> c_int;
+        pub fn kbo_place_from_segments_host(segs: *const super::SeqSegment, n_segs: u64, n_seqs: usize, src_off: *const u64, n_src: usize,
+                                            k: u32, max_gap: u32, max_indel: u32, merge: c_int, place: *mut super::SeqPlace) -> c_int;
+        pub fn kbo_place_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
+                               max_gap: u32, max_indel: u32, place_out: *mut super::SeqPlace) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -449,6 +459,33 @@ pub struct SeqSegment {
     pub pos_first: u32,
     pub pos_last: u32,
     pub flags: u32,
+}
+
+/// `KBO_PLACE_NONE`: `SeqPlace::source` of a sequence without a segment; `KBO_PLACE_REV` / `KBO_PLACE_SPILLS`: bits 0 and 1 of its flags.
+pub const PLACE_NONE: u32 = 0xFFFF_FFFF;
+pub const PLACE_REV: u16 = 1;
+pub const PLACE_SPILLS: u16 = 2;
+
+/// `kbo_seq_place` (48 bytes), one per sequence: the best chain of the sequence's segments.  `source`: the source sequence it lies on;
+/// `q_start .. q_end` in the sequence and `pos_start .. pos_end` in source coordinates, half open; `score`: the query bases the chain's
+/// segments cover; `n_segs`, `indel`, `n_multi`: segments, indel bases and segments with a repeated k-mer at an end along the chain;
+/// `second`: the score of the best chain with another first segment, 0 without one.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct SeqPlace {
+    pub source: u32,
+    pub strand: u16,
+    pub flags: u16,
+    pub q_start: u32,
+    pub q_end: u32,
+    pub pos_start: u32,
+    pub pos_end: u32,
+    pub score: u32,
+    pub n_segs: u32,
+    pub indel: u32,
+    pub n_multi: u32,
+    pub second: u32,
+    pub reserved: u32,
 }
 
 /// `KBO_COVER_NO_ENTRIES` / `KBO_COVER_OVERFLOW`: bits 0 and 1 of `RefCover::flags`.

@@ -1277,6 +1277,80 @@ size_t kbo_depth_work_bytes(const kbo_index_t *idx);
 int kbo_depth_finish_dev(kbo_index_t *idx, const uint32_t *d_delta, uint32_t *d_depth, void *d_work, size_t work_bytes, void *stream);
 int kbo_segments_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands,
                        kbo_seq_segment **segs, uint64_t *n_segs, uint32_t *depth_out);
+/* ------------------------------------------------------------------ Placement: the segments of a sequence chained to ONE record
+ * Where a sequence lies: on which source and strand, how much of it, and how clear that is (the arithmetic:
+ * kbo_amd/csrc/index_place.hpp, the kernels: kbo_amd/csrc/place_kernels.hip).  A read with a substitution is two segments at bridge 0,
+ * a read with an insertion or deletion two at any bridge, a 10 kbp read a few hundred; this step chains them on the device.
+ *
+ * DEFINITIONS.  Take the segments of one sequence from one kbo_segments_dev call (one strand argument), s_0 .. s_{n-1} in list order;
+ * they are disjoint stretches of the anchor list, so q_last of s_j is below q_first of s_i for j < i.  For a segment: len = q_last -
+ * q_first + k (the query bases it covers); rev = flag bit 0; diag = pos_first - q_first (FWD) or pos_first + q_first (REV) as a 64-bit
+ * signed value, constant over the segment; src = the last source s with src_off[s] <= pos_first.
+ * s_j MAY PRECEDE s_i iff all of: i - W <= j < i with W = KBO_PLACE_WINDOW = 64; the same rev and the same src; g = q_first_i -
+ * q_last_j <= max_gap; and with shift = diag_i - diag_j (FWD) or diag_j - diag_i (REV) - the bases the source advances beyond the query:
+ * > 0 a deletion in the sequence, < 0 an insertion - |shift| <= max_indel and g + shift >= 1 (the source advances).
+ * gain(j, i) = min(len_i, q_last_i - q_last_j).
+ * CHAINS.  f_i = max(len_i, max over the j that may precede i of f_j + gain(j, i)).  The predecessor taken is the one with the largest
+ * value, ties to the larger j; there is none when len_i is at least that value.  Every segment carries along its chain the chain's
+ * first segment (its ROOT), the number of segments, the sum of |shift| and the number of its segments with a MULTI flag at either end.
+ * With at most W segments the recurrence is the exact maximum over all chains the rule allows; beyond, predecessors further back
+ * than W are not looked at.
+ * THE PLACEMENT of the sequence is the chain that ends at the i with the largest f, ties to the smaller i.  `second` is the largest f_i
+ * over all i whose root differs from the best chain's root, 0 when there is none: chains of one root share a prefix with the best one
+ * and are not a second placement.  A MULTI k-mer is placed at its stored occurrence only (SEGMENTS, above), so `second` does not see
+ * the other copy of an exact repeat: n_multi is there to say that the chain rests on k-mers that occur elsewhere too.
+ * MERGE.  Two records of one sequence merge to the one with the larger score, ties to the smaller strand value (then, for two calls
+ * with one strand value, to the smaller of the remaining fields in their order); its `second` becomes the largest of both `second`s and
+ * the loser's score.  A KBO_PLACE_NONE record loses to anything.  The merge is associative and commutative: the record is its own
+ * reduction state, as kbo_ref_best is.
+ *
+ * kbo_place_dev takes d_segs, d_n_segs and capacity exactly as kbo_segments_dev leaves them and uses min(*d_n_segs, capacity) records,
+ * read on the device.  It is a device-resident call like the others: at most four launches on `stream` - the ranges cleared; a lane per record
+ * for its source (a bisection of the device copy of src_off that kbo_index_add_positions / kbo_index_positions_to_device make beside the
+ * table) and the range of its sequence; a lane per sequence that chains a list of at most KBO_PLACE_LANE_MAX = 4 segments in registers;
+ * a wave per sequence with a longer list, the up to 64 predecessors of a step one to a lane - nothing is synchronised, read back or
+ * allocated, and the route is chosen per sequence on the device.  Both routes write the same bytes.  No byte of d_work (16-byte aligned)
+ * beyond kbo_place_work_bytes(n_seqs, capacity) - exact: three times 4 bytes per sequence and 4 bytes per record of capacity, each
+ * rounded up to 16, and 16 - or of d_place (16-byte aligned) beyond n_seqs records is touched.  merge != 0: every record is merged into
+ * what d_place holds (the second strand's call); merge == 0: d_place is written, not read.  Whatever the records hold, no load or store
+ * leaves the caller's buffers and the handle's table: a record whose seq is not its range's, or is at least n_seqs, is skipped, and the
+ * result for a list that is not in (seq, q_first) order is unspecified but in bounds.  d_segs may be NULL when capacity == 0 (every
+ * record is then KBO_PLACE_NONE).  Errors, before anything is enqueued and in this order: KBO_E_BAD_ARG for null or misaligned
+ * pointers (d_segs 4-byte, d_n_segs 8-byte, d_place and d_work 16-byte); KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_UNSUPPORTED for
+ * n_seqs >= 2^28 or capacity >= 2^32 - 1 and for a sharded handle; KBO_E_BAD_ARG for a handle without positions, for one without
+ * positions on the current device, and for a short work_bytes.  kbo_place_work_bytes is 0 for n_seqs == 0 and beyond those limits.
+ * kbo_place_from_segments_host is the same call restated on the CPU (no HIP call; src_off: n_src + 1 values as
+ * kbo_index_source_offsets gives them): byte-identical records, for any list.  KBO_E_BAD_ARG for null arguments (segs may be NULL when
+ * n_segs == 0), k == 0, n_src == 0 and src_off that does not start at 0 or descends; KBO_E_EMPTY_QUERY for n_seqs == 0;
+ * KBO_E_UNSUPPORTED beyond the limits above.
+ * kbo_place_batch is the host form: upload, the '-' strand made on the device, the interval walk, kbo_segments_dev (once to count,
+ * once to write) and kbo_place_dev per strand - the second with merge - and one download of n_seqs records to place_out.  Errors as
+ * kbo_segments_batch. */
+#define KBO_PLACE_NONE 0xFFFFFFFFu
+#define KBO_PLACE_WINDOW 64
+#define KBO_PLACE_LANE_MAX 4
+#define KBO_PLACE_REV 1u
+#define KBO_PLACE_SPILLS 2u
+typedef struct {
+    uint32_t source;             /* the root's src; KBO_PLACE_NONE when the sequence has no segment: every other field is then 0 */
+    uint16_t strand;             /* the strand argument of the call that won (its low 16 bits), as the best chain's last record holds it */
+    uint16_t flags;              /* bit 0 REV; bit 1 SPILLS: pos_end > src_off[source + 1], the chain runs across a junction of adjacent
+                                    sources, which the segments' definition allows */
+    uint32_t q_start, q_end;     /* the root's q_first; the end's q_last + k */
+    uint32_t pos_start, pos_end; /* source coordinates, half open.  FWD: the root's pos_first, the end's pos_last + k; REV: the end's
+                                    pos_last, the root's pos_first + k */
+    uint32_t score;              /* f */
+    uint32_t n_segs, indel, n_multi; /* as the chain carried them */
+    uint32_t second;
+    uint32_t reserved;           /* 0 */
+} kbo_seq_place;                 /* 48 bytes */
+size_t kbo_place_work_bytes(size_t n_seqs, size_t n_segs_capacity);
+int kbo_place_dev(kbo_index_t *idx, const kbo_seq_segment *d_segs, const uint64_t *d_n_segs, size_t capacity, size_t n_seqs, uint32_t max_gap,
+                  uint32_t max_indel, int merge, kbo_seq_place *d_place, void *d_work, size_t work_bytes, void *stream);
+int kbo_place_from_segments_host(const kbo_seq_segment *segs, uint64_t n_segs, size_t n_seqs, const uint64_t *src_off, size_t n_src, uint32_t k,
+                                 uint32_t max_gap, uint32_t max_indel, int merge, kbo_seq_place *place);
+int kbo_place_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands,
+                    uint32_t max_gap, uint32_t max_indel, kbo_seq_place *place_out);
 
 /* ---- alignment summaries (kbo_aln_summary, above) of device-resident batches; asynchronous, the library never synchronises.
  * kbo_summary_batch_dev: kbo::matches over the batch as kbo_map_batch_dev_tail runs it (format = 0: the same routes, streams and

@@ -30,6 +30,7 @@ from .refset import cover_refset, cover_refset_dev  # noqa: F401,E402
 from .refset import call_refset, call_refset_dev, variant_chars  # noqa: F401,E402
 from . import locate  # noqa: F401,E402
 from .locate import add_positions, depth_finish_dev, segment_source, segments, segments_dev  # noqa: F401,E402
+from .locate import place, place_dev, place_from_segments_host, place_local, place_work_bytes  # noqa: F401,E402
 
 
 @dataclass

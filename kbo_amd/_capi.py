@@ -159,6 +159,7 @@ SYMBOLS = [
     "kbo_index_add_positions", "kbo_index_has_positions", "kbo_index_positions_bytes", "kbo_index_positions", "kbo_index_source_offsets",
     "kbo_index_source_bases", "kbo_index_positions_to_device", "kbo_positions_from_ms_host", "kbo_segments_work_bytes", "kbo_segments_dev",
     "kbo_segments_from_ms_host", "kbo_depth_work_bytes", "kbo_depth_finish_dev", "kbo_segments_batch",
+    "kbo_place_work_bytes", "kbo_place_dev", "kbo_place_from_segments_host", "kbo_place_batch",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -451,6 +452,10 @@ def lib():
     L.kbo_depth_work_bytes.argtypes = [vp]; L.kbo_depth_work_bytes.restype = sz
     L.kbo_depth_finish_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     L.kbo_segments_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, C.POINTER(vp), C.POINTER(u64), vp]
+    L.kbo_place_work_bytes.argtypes = [sz, sz]; L.kbo_place_work_bytes.restype = sz
+    L.kbo_place_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, C.c_int, vp, vp, sz, vp]
+    L.kbo_place_from_segments_host.argtypes = [vp, u64, sz, vp, sz, u32, u32, u32, C.c_int, vp]
+    L.kbo_place_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, u32, u32, vp]
     L.kbo_segments_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.kbo_set_positions_slab_bases.argtypes = [u64]
     _lib = L

@@ -5,7 +5,8 @@
 //   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
 //   batch_route.cpp   the kernel route of a batch, for host slabs and device calls alike (batch_route.hpp),
 //   build_device.cpp  kbo_index_build_device (the index built by the device),
-//   index_locate.cpp  the position table of an index, the segments of a batch and the depth of the sources.
+//   index_locate.cpp  the position table of an index, the segments of a batch and the depth of the sources,
+//   index_place.cpp   one placement per sequence from those segments.
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -54,6 +55,7 @@ struct DevCopy {
     uint32_t sub_thr = 0;            // proof's windows at this threshold - what a call with default options gets on this index -
     bool sub_anch = false;           // with or without anchors
     DevBuf positions;                // the position table (index_locate.cpp): a word per row, empty without one
+    DevBuf src_off;                  // ... and where every source begins (kbo_index::src_off), made with it: what kbo_place_dev bisects
     // what making this copy cost (kbo_index_device_layout): seconds of host work / device builds / uploads, by part
     bool plan_built = false;         // path cover, recovery lines, tables: made by the first use that pays for them (device_index.cpp)
     bool plan_failed = false;        // ... or could not be made (no memory): not tried again on every call; the copy walks plainly
@@ -190,6 +192,10 @@ void attach_plan(kbo::WalkArgs &a, void *plan_work, DevCopy::PlanState *ps);
 void plan_reset_holdoff(); // every copy plans its next launch again
 // after launch_ms_walk: lets the host learn whether the plan paid (and whether a walk was cut short by its guard)
 void plan_after_launch(const kbo::WalkArgs &a, hipStream_t stream, DevCopy::PlanState *ps);
+
+// ---- index_locate.cpp: the source offsets of the copy on `dev` as kbo_index_add_positions / kbo_index_positions_to_device left them
+// (*n_src: the sources; n_src + 1 values), or null: no positions, or none on that device
+const uint64_t *source_offsets_on(kbo_index *idx, int dev, uint32_t *n_src);
 
 // ---- kbo_capi.cpp: shards kbo_index_build makes of `bases` bases (one per 3.76 * 10^9 rows, or kbo_set_index_shards); > 1 = sharded
 size_t shards_wanted(uint64_t bases, bool add_revcomp);

@@ -63,7 +63,18 @@ void drop_positions(kbo_index *idx)
     std::lock_guard<std::mutex> g(idx->mu);
     idx->positions.clear();
     idx->src_off.clear();
-    for (auto &kv : idx->dev) kv.second->positions.release();
+    for (auto &kv : idx->dev) {
+        kv.second->positions.release();
+        kv.second->src_off.release();
+    }
+}
+
+// the source offsets beside a copy's table (mu held, the copy's device current)
+void upload_src_off(kbo_index *idx, DevCopy *copy)
+{
+    if (copy->src_off.p) return;
+    copy->src_off.alloc(idx->src_off.size() * sizeof(uint64_t));
+    HIP_OK(hipMemcpy(copy->src_off.p, idx->src_off.data(), idx->src_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
 }
 
 // the table of the copy on `dev`, or null; make: uploaded when the copy has none (the device current)
@@ -79,6 +90,7 @@ const uint32_t *positions_on(kbo_index *idx, int dev, bool make)
         if (!idx->positions.empty())
             HIP_OK(hipMemcpy(b.p, idx->positions.data(), idx->positions.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
+    if (make) upload_src_off(idx, it->second);
     return b.as<uint32_t>();
 }
 
@@ -170,6 +182,7 @@ void add_positions(kbo_index *idx, const uint8_t *const *seqs, const size_t *len
     std::swap(keep.p, mn.p);
     std::swap(keep.cap, mn.cap);
     std::swap(keep.dev, mn.dev);
+    upload_src_off(idx, idx->dev.at(dev));
 }
 
 struct HostIn {
@@ -229,6 +242,15 @@ void segments_enqueue(const uint32_t *d_entries, uint32_t n_rows, uint32_t k, ui
 }
 
 } // namespace
+
+const uint64_t *kbo_host::source_offsets_on(kbo_index *idx, int dev, uint32_t *n_src)
+{
+    std::lock_guard<std::mutex> g(idx->mu);
+    auto it = idx->dev.find(dev);
+    if (it == idx->dev.end() || idx->src_off.empty() || !it->second->positions.p || !it->second->src_off.p) return nullptr;
+    *n_src = (uint32_t)(idx->src_off.size() - 1);
+    return it->second->src_off.as<uint64_t>();
+}
 
 int kbo_set_positions_slab_bases(uint64_t bases)
 {

@@ -842,6 +842,20 @@ struct SegmentArgs {
 hipError_t launch_segments(const SegmentArgs &a, hipStream_t stream);
 // d_depth = the inclusive prefix sums of n words of d_delta; d_work: idxlocate::depth_work(n) bytes
 hipError_t launch_depth_finish(const uint32_t *d_delta, uint32_t *d_depth, uint64_t n, void *d_work, hipStream_t stream);
+// ---- place_kernels.hip (the arithmetic, the ring and the d_work layout: index_place.hpp)
+struct PlaceArgs {
+    const uint32_t *segs;    // records of 7 words as launch_segments left them: min(*n_segs, capacity) are looked at
+    const uint64_t *n_segs;
+    uint64_t capacity;
+    const uint64_t *src_off; // n_src + 1 values
+    uint32_t n_seqs, n_src, k, max_gap, max_indel;
+    bool merge;              // into what `place` holds
+    void *place;             // n_seqs records of 48 bytes, 16-byte aligned
+    void *work;              // idxplace::place_work(n_seqs, capacity).bytes
+};
+// at most four launches, sized by n_seqs and capacity alone: the ranges cleared, a lane per record, a lane per sequence, a wave per
+// sequence with a long list (the second and the fourth only when capacity can hold such records)
+hipError_t launch_place(const PlaceArgs &a, hipStream_t stream);
 
 void set_pair_min_depth(int d);            // tuning: depth from which two-base steps are tried
 constexpr uint32_t kRankRows = 96; // rows per 16-byte rank block (== kRankRowsPerBlock)

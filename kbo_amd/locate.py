@@ -1,7 +1,9 @@
-"""Positions, segments, depth (kbo_hip.h): where a batch lies on the sequences an index was built from.
+"""Positions, segments, depth, placement (kbo_hip.h): where a batch lies on the sequences an index was built from.
 
 add_positions() gives an index its position table; segments() turns a batch into collinear blocks of exact k-mer matches in source
 coordinates and, when asked, the depth of every source base; segments_dev() / depth_finish_dev() are the same over device buffers.
+place() chains the segments of every sequence to one record - source, strand, extent, score, runner-up; place_dev() is the same over
+device buffers behind segments_dev(), place_from_segments_host() its restatement on the CPU.
 """
 import ctypes as C
 
@@ -16,6 +18,11 @@ SEG_REV, SEG_FIRST_MULTI, SEG_LAST_MULTI = 1, 4, 8
 
 # kbo_seq_segment
 SEGMENT_DTYPE = np.dtype([(n, "<u4") for n in ("seq", "strand", "q_first", "q_last", "pos_first", "pos_last", "flags")])
+# kbo_seq_place
+PLACE_NONE, PLACE_REV, PLACE_SPILLS, PLACE_WINDOW, PLACE_LANE_MAX = 0xFFFFFFFF, 1, 2, 64, 4
+PLACE_DTYPE = np.dtype([("source", "<u4"), ("strand", "<u2"), ("flags", "<u2")] + [(n, "<u4") for n in (
+    "q_start", "q_end", "pos_start", "pos_end", "score", "n_segs", "indel", "n_multi", "second", "reserved")])
+assert PLACE_DTYPE.itemsize == 48
 
 
 def _batch(query_seqs):
@@ -147,3 +154,55 @@ def segments_from_ms_host(entries, k, d, lo, offsets, bridge, strand, capacity, 
                                           bridge, strand, segs.ctypes.data if capacity else None, capacity, C.byref(n),
                                           delta.ctypes.data if delta is not None else None, source_bases))
     return segs[:min(capacity, n.value)], int(n.value)
+
+
+def place(query_seqs, sbwt, bridge=None, strands=STRAND_FWD, max_gap=1000, max_indel=100):
+    """kbo_place_batch -> one record (PLACE_DTYPE) per sequence: the best chain of its segments over the strands asked for; source ==
+    PLACE_NONE for a sequence without a segment.  query_seqs: a list of sequences or (concat, offsets); bridge: None = k.
+    max_gap (query bases between two segments of a chain) and max_indel (bases the diagonal may move between them) default to 1000 and
+    100: choices that suit reads up to a few 10 kbp with small indels, not derived figures"""
+    concat, offsets = _batch(query_seqs)
+    b = sbwt.k() if bridge is None else int(bridge)
+    out = np.zeros(len(offsets) - 1, dtype=PLACE_DTYPE)
+    check(lib().kbo_place_batch(sbwt._h, concat.ctypes.data if len(concat) else None, offsets.ctypes.data, len(offsets) - 1, min(b, 0xFFFFFFFF), int(strands),
+                                int(max_gap), int(max_indel), out.ctypes.data if len(out) else None))
+    return out
+
+
+def place_work_bytes(n_seqs, capacity):
+    return int(lib().kbo_place_work_bytes(n_seqs, capacity))
+
+
+def place_dev(sbwt, segs, n_segs, capacity, n_seqs, place_out, work, work_bytes=None, max_gap=1000, max_indel=100, merge=False, stream=None):
+    """kbo_place_dev over torch tensors (or raw device pointers): segs, n_segs and capacity as segments_dev() left them; everything on
+    `stream`.  merge: into what place_out holds (the second strand's call)"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    wb = place_work_bytes(n_seqs, capacity) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_place_dev(sbwt._h, ptr(segs), ptr(n_segs), int(capacity), n_seqs, int(max_gap), int(max_indel), int(bool(merge)), ptr(place_out),
+                              ptr(work), wb, s))
+
+
+def place_from_segments_host(segs, n_seqs, src_off, k, max_gap=1000, max_indel=100, merge_into=None):
+    """kbo_place_from_segments_host -> PLACE_DTYPE[n_seqs]; merge_into: records of an earlier call (another strand) to merge with"""
+    segs = np.ascontiguousarray(segs, dtype=SEGMENT_DTYPE)
+    src_off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    out = np.zeros(n_seqs, dtype=PLACE_DTYPE) if merge_into is None else np.ascontiguousarray(merge_into, dtype=PLACE_DTYPE).copy()
+    assert len(out) == n_seqs
+    check(lib().kbo_place_from_segments_host(segs.ctypes.data if len(segs) else None, len(segs), n_seqs, src_off.ctypes.data, len(src_off) - 1, k,
+                                             int(max_gap), int(max_indel), int(merge_into is not None), out.ctypes.data if n_seqs else None))
+    return out
+
+
+def place_local(rec, src_off):
+    """(source, start, end, orientation 0 = FWD / 1 = REV) of one record or an array of them, start and end in the source's own
+    coordinates (end may lie beyond the source: PLACE_SPILLS); src_off: the index's source_offsets().  A PLACE_NONE record gives
+    (PLACE_NONE, 0, 0, 0)"""
+    off = np.asarray(src_off, dtype=np.uint64)
+    src = np.asarray(rec["source"], dtype=np.int64)
+    none = src == PLACE_NONE
+    base = off[np.where(none, 0, src)].astype(np.int64)
+    start = np.where(none, 0, np.asarray(rec["pos_start"], dtype=np.int64) - base)
+    end = np.where(none, 0, np.asarray(rec["pos_end"], dtype=np.int64) - base)
+    return src, start, end, np.where(none, 0, np.asarray(rec["flags"]) & PLACE_REV).astype(np.uint8)
