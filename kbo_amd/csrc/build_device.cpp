@@ -255,14 +255,6 @@ void build_on_device(const uint8_t *const *seqs, const size_t *lens, size_t n_se
     HIP_OK(hipStreamSynchronize(s));
 }
 
-struct RestoreDevice {
-    int prev;
-    ~RestoreDevice()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 } // namespace
 
 extern "C" int kbo_index_build_device(const uint8_t *const *seqs, const size_t *lens, size_t n_seqs, const kbo_build_opts *opts, int device,
@@ -287,11 +279,8 @@ extern "C" int kbo_index_build_device(const uint8_t *const *seqs, const size_t *
         KBO_REQUIRE(bases * (rc ? 2u : 1u) < 0xFFFFFFF0ull, KBO_E_UNSUPPORTED,
                     "kbo_index_build_device: 2^32 or more k-mers; build it with kbo_index_build");
         for (double &t : t_phase) t = 0;
-        int prev = -1;
-        HIP_OK(hipGetDevice(&prev));
-        RestoreDevice restore{prev};
-        const int dev = device < 0 ? prev : device;
-        if (dev != prev) HIP_OK(hipSetDevice(dev));
+        DeviceScope scope(device);
+        const int dev = device < 0 ? scope.prev : device;
         size_t free_b = 0, total_b = 0;
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
         const uint64_t need = peak_bytes(bases, n_seqs, o.k, rc);

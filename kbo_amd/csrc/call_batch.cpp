@@ -26,18 +26,7 @@ using namespace kbo_host;
 
 namespace {
 
-// KBO_TIMING=1 in the environment: phases of kbo_call_batch on stderr
-struct CallClock {
-    bool on = std::getenv("KBO_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what)
-    {
-        if (!on) return;
-        const auto n = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[kbo timing] call: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
-};
+constexpr const char *kCallClock = "[kbo timing] call:"; // KBO_TIMING=1 in the environment: phases of kbo_call_batch on stderr
 
 struct SiteRec {
     uint32_t seq, i, j, lo;
@@ -187,7 +176,9 @@ void find_sites(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, 
             std::vector<kbo::WalkItem> items;
             if (by_walk) {
                 const CallSink sink{d_sites.p, d_count.as<uint32_t>(), cap / kbo::kCallSegs, threshold};
-                enqueue_walk_host(idx, concat + sl.b0, off.data(), ns, false, B, items, stream, 0, nullptr, nullptr, &sink);
+                WalkHostAsk ask;
+                ask.call = &sink;
+                enqueue_walk_host(idx, concat + sl.b0, off.data(), ns, B, items, stream, ask);
             } else {
                 run_walk_host(idx, concat + sl.b0, off.data(), ns, true, B, stream);
                 HIP_OK(kbo::launch_call_sites(B.ms.as<uint8_t>(), B.lo.as<uint32_t>(), B.hi.as<uint32_t>(), B.off.as<uint64_t>(),
@@ -474,7 +465,7 @@ struct CallSlot {
 };
 
 void call_fast(kbo_index *query_idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, const kbo_call_opts &o, size_t d,
-               uint32_t second_q, FlatCalls &out, uint64_t *var_offsets, CallClock &clk)
+               uint32_t second_q, FlatCalls &out, uint64_t *var_offsets, PhaseClock &clk)
 {
     const uint32_t k = query_idx->host.k;
     const bool revcomp = o.sbwt_build_opts.add_revcomp != 0;
@@ -549,7 +540,9 @@ void call_fast(kbo_index *query_idx, const uint8_t *concat, const uint64_t *offs
         HIP_OK(hipMemsetAsync(S.d_count.p, 0, count_bytes, st));
         HIP_OK(hipMemsetAsync(S.d_meta.p, 0, kbo::kCallMetaWords * 4, st));
         const CallSink sink{S.d_sites.p, S.d_count.as<uint32_t>(), seg_cap, (uint32_t)d};
-        enqueue_walk_host(query_idx, S.in.as<uint8_t>(), off, ns, false, S.B, S.items, st, 0, nullptr, nullptr, &sink);
+        WalkHostAsk ask;
+        ask.call = &sink;
+        enqueue_walk_host(query_idx, S.in.as<uint8_t>(), off, ns, S.B, S.items, st, ask);
         HIP_OK(kbo::launch_call_prefix(S.d_count.as<uint32_t>(), seg_cap, S.d_prefix.as<uint32_t>(), S.d_meta.as<uint32_t>(), st));
         HIP_OK(kbo::launch_call_finalize(S.d_sites.p, S.d_count.as<uint32_t>(), S.d_prefix.as<uint32_t>(), seg_cap, seg_cap, true,
                                          S.B.off.as<uint64_t>(), (uint32_t)ns, k, S.B.ms.as<uint8_t>(), view, S.d_recs.p, S.d_win.as<uint8_t>(), stride, st));
@@ -773,7 +766,7 @@ void call_batch_flat_impl(kbo_index_t *query_idx, const uint8_t *concat, const u
                 "intervals and the call mode need the rows of one index; this handle is a sharded index");
     const uint32_t k = query_idx->host.k;
     const size_t d = random_match_threshold(k, query_idx->host.n_kmers, 4, o.max_error_prob); // variant_calling.rs:260
-    CallClock clk;
+    PhaseClock clk{kCallClock};
     // the second pass's values per site from the device (call_second_kernels.hip), where its q-mers can be at most as long as the
     // threshold and positions fit its tables - and then the variants themselves (call_emit_kernels.hip)
     static const int env_second = std::getenv("KBO_CALL_DEVICE_SECOND") ? std::atoi(std::getenv("KBO_CALL_DEVICE_SECOND")) : 1; // experiments
@@ -838,7 +831,7 @@ extern "C" int kbo_call_batch(kbo_index_t *query_idx, const uint8_t *concat, con
         *out = nullptr;
         FlatCalls fc;
         call_batch_flat_impl(query_idx, concat, offsets, n_seqs, opts, fc, var_offsets);
-        CallClock clk;
+        PhaseClock clk{kCallClock};
         // ---- the reference's records (variant_calling.rs:8-26): one allocation, the records, then the characters
         const size_t nv = fc.pos.size(), nc = fc.chars.size();
         const size_t head = std::max<size_t>(1, nv) * sizeof(kbo_variant);

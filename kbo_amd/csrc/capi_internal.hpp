@@ -2,6 +2,7 @@
 //   device_index.cpp  the index handle and its per-device copies,
 //   host_batch.cpp    host batches: slabs, staging, the three-stage pipeline with one output stage per mode,
 //   kbo_capi.cpp      the extern "C" entry points,
+//   kbo_tuning.cpp    ... those of include/kbo_hip_tuning.h: knobs, experiment setters, test hooks,
 //   device_batch.cpp  ... those over batches already on the device (d_work, kbo_*_dev, kbo_map_stream_*),
 //   batch_route.cpp   the kernel route of a batch, for host slabs and device calls alike (batch_route.hpp),
 //   build_device.cpp  kbo_index_build_device (the index built by the device),
@@ -110,7 +111,7 @@ struct kbo_index {
     kbo::HostIndex host;
     std::mutex mu;
     HandleOpts opts;
-    std::map<int, kbo_host::DevCopy *> dev;
+    std::map<int, std::unique_ptr<kbo_host::DevCopy>> dev;
     uint64_t rank_bytes = 0, lcs_bytes = 0, plan_bytes = 0;
     bool transient = false; // an index that serves one small batch (kbo::call builds one per sequence): no path cover
     // the path cover of the plan-guided walk once it has been computed (or read from an index file), guarded by `mu`:
@@ -129,10 +130,6 @@ struct kbo_index {
     // walks every shard and keeps the maximum; what needs rows of the union (intervals, call, fill_gaps, export) is refused.
     std::vector<std::unique_ptr<kbo_index>> shards;
     bool sharded() const { return !shards.empty(); }
-    ~kbo_index()
-    {
-        for (auto &kv : dev) delete kv.second;
-    }
 };
 
 namespace kbo_host {
@@ -165,6 +162,9 @@ extern std::atomic<int64_t> g_plan_lazy_bases;    // bases through a copy before
 
 // ---- device_index.cpp
 int current_device();
+inline int resolve_device(int device) { return device < 0 ? current_device() : device; } // (< 0: the calling thread's)
+// the copy of the index on `device` (resolved), which must exist; called with idx->mu held
+DevCopy &copy_on(kbo_index *idx, int device);
 // the indexes a walk goes over: the shards of a sharded handle, else the handle itself
 inline std::vector<kbo_index *> shards_of(kbo_index *idx)
 {
@@ -485,15 +485,19 @@ struct HostStage {
     int strands = 1;
     std::atomic<uint64_t> *staged = nullptr; // += bytes of every host -> device copy
 };
-void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, bool want_ival,
-                       BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
-                       uint32_t longest = 0 /* longest sequence if the caller knows it */,
-                       hipStream_t copy_stream = nullptr /* uploads go here when given ... */,
-                       hipEvent_t copied = nullptr /* ... and `stream` waits for this event */,
-                       const CallSink *call = nullptr /* call mode: MS values + sites, no intervals */,
-                       const PackedIn *packed = nullptr /* the queries arrive 2-bit packed (concat is not read) */,
-                       FusedMap *map = nullptr /* kbo::matches / map: the one kernel where it applies */,
-                       const HostStage *hs = nullptr /* strands, upload count */);
+// what a caller of enqueue_walk_host asks for beyond the walk of the batch as it is; each sets the fields it means
+struct WalkHostAsk {
+    bool want_ival = false;            // the intervals as well (B.lo, B.hi)
+    uint32_t longest = 0;              // longest sequence if the caller knows it
+    hipStream_t copy_stream = nullptr; // uploads go here when given ...
+    hipEvent_t copied = nullptr;       // ... and `stream` waits for this event
+    const CallSink *call = nullptr;    // call mode: MS values + sites, no intervals
+    const PackedIn *packed = nullptr;  // the queries arrive 2-bit packed (concat is not read)
+    FusedMap *map = nullptr;           // kbo::matches / map: the one kernel where it applies
+    const HostStage *stage = nullptr;  // strands, upload count
+};
+void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, BatchOnDevice &B,
+                       std::vector<kbo::WalkItem> &items_keep, hipStream_t stream, const WalkHostAsk &ask = {});
 void run_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, bool want_ival,
                    BatchOnDevice &B, hipStream_t stream);
 // A5+A6 over a batch whose offsets are known on the host
@@ -501,14 +505,52 @@ void derand_translate_host_offsets(const uint8_t *d_ms, const uint64_t *d_off, c
                                    uint32_t k, uint32_t threshold, const uint8_t *d_ref, uint8_t *d_chars,
                                    int32_t *d_derand, hipStream_t stream, uint32_t longest = 0,
                                    DevBuf *piece_work = nullptr /* lets long reads / contigs be split into pieces */);
-// kbo::matches over a batch (lib.rs:618-627); optional relative_to_ref (lib.rs:756-757); with a sink the
-// characters are turned into run lengths on the device instead of being downloaded (lib.rs:816-820)
-void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink = nullptr,
-                        int strands = 0 /* 0: one strand as given; else KBO_STRAND_*: chars_out '+', rev_out '-' */, uint8_t *rev_out = nullptr,
-                        kbo_aln_summary *summary_out = nullptr /* kbo_summary_batch: n_seqs records instead of the characters */);
-// the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list; the characters come
-// back 2-bit packed as well (M, -, X, R = 0 .. 3) or, with a sink, as run lengths, or, with a sparse sink, as their runs other than 'M'
+// what leaves the device for a slab of a host batch ...
+enum class OutMode {
+    Ms,     // kbo_ms_batch: the MS values (and the intervals, when lo / hi are given)
+    Chars,  // kbo_matches_batch, kbo_map_batch: one character per base
+    Words,  // kbo_matches_batch_packed: the characters as 2-bit words
+    Rle,    // kbo_find_batch, kbo_find_batch_into: run-length records, widened to kbo_rle
+    Rle32,  // kbo_find_batch_packed: run-length records as the device writes them
+    Sparse, // kbo_matches_batch_sparse: the runs of characters other than 'M'
+    Summary, // kbo_summary_batch, kbo_summary_batch_packed: one kbo_aln_summary per sequence, the characters stay on the device
+};
+// ... and where it goes: made by the maker of its mode, which sets that mode's destination and no other
+struct HostOut {
+    OutMode mode;
+    uint8_t *ms_out = nullptr;                      // Ms ...
+    uint32_t *lo_out = nullptr, *hi_out = nullptr;  // ... with the intervals when these are given
+    uint8_t *chars_out = nullptr, *chars_rev = nullptr;    // Chars: the '+' strand (or the one strand as given) and the '-' strand ...
+    bool format = false;                                   // ... with format::relative_to_ref applied
+    uint32_t *packed_out = nullptr, *packed_rev = nullptr; // Words: the same
+    RleSink<kbo_rle> *rle = nullptr;                // Rle
+    RleSink<kbo_rle32> *rle32 = nullptr;            // Rle32
+    RecordSink<kbo_aln_run> *sparse_runs = nullptr; // Sparse
+    kbo_aln_summary *summary_out = nullptr;         // Summary: n_seqs records
+
+    static HostOut ms(uint8_t *d, uint32_t *lo, uint32_t *hi) { HostOut o{OutMode::Ms}; o.ms_out = d; o.lo_out = lo; o.hi_out = hi; return o; }
+    static HostOut chars(uint8_t *fwd, uint8_t *rev, bool format) { HostOut o{OutMode::Chars}; o.chars_out = fwd; o.chars_rev = rev; o.format = format; return o; }
+    static HostOut words(uint32_t *fwd, uint32_t *rev) { HostOut o{OutMode::Words}; o.packed_out = fwd; o.packed_rev = rev; return o; }
+    static HostOut runs(RleSink<kbo_rle> *sink) { HostOut o{OutMode::Rle}; o.rle = sink; return o; }
+    static HostOut runs32(RleSink<kbo_rle32> *sink) { HostOut o{OutMode::Rle32}; o.rle32 = sink; return o; }
+    static HostOut sparse(RecordSink<kbo_aln_run> *sink) { HostOut o{OutMode::Sparse}; o.sparse_runs = sink; return o; }
+    static HostOut summary(kbo_aln_summary *out) { HostOut o{OutMode::Summary}; o.summary_out = out; return o; }
+    bool takes_strands() const { return mode == OutMode::Chars || mode == OutMode::Words || mode == OutMode::Rle || mode == OutMode::Rle32; }
+    // the destinations of a batch run in `strands` (KBO_STRAND_*) are there
+    bool complete(int strands) const
+    {
+        const void *fwd = mode == OutMode::Chars ? (const void *)chars_out : packed_out, *rev = mode == OutMode::Chars ? (const void *)chars_rev : packed_rev;
+        if (mode == OutMode::Chars || mode == OutMode::Words) return (fwd || !(strands & 1)) && (rev || !(strands & 2));
+        return ms_out || rle || rle32 || sparse_runs || summary_out;
+    }
+};
+// kbo::matches over a batch (lib.rs:618-627) into HostOut::chars (optional relative_to_ref, lib.rs:756-757), ::runs (the characters
+// are turned into run lengths on the device instead of being downloaded, lib.rs:816-820) or ::summary.  strands = 0: one strand as
+// given; else KBO_STRAND_*
+void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
+                        const HostOut &out, int strands = 0);
+// the same over 2-bit packed reads (pack_kernels.hip layout) with the non-ACGT bases in a side list, into HostOut::words (the characters
+// 2-bit packed as well: M, -, X, R = 0 .. 3), ::runs32, ::sparse (their runs other than 'M') or ::summary
 struct PackedBatch {
     const uint32_t *words;
     const uint64_t *exc_pos;
@@ -517,8 +559,7 @@ struct PackedBatch {
 };
 void summary_slab_routes(uint64_t *kernel_slabs, uint64_t *reducer_slabs);
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink<kbo_rle32> *sink = nullptr, RecordSink<kbo_aln_run> *sparse = nullptr,
-                               int strands = 0, uint32_t *rev_out = nullptr, kbo_aln_summary *summary_out = nullptr);
+                               const HostOut &out, int strands = 0);
 // host -> device bytes the calling thread's last host batch staged (kbo_last_batch_staged_bytes)
 extern thread_local uint64_t t_last_staged;
 // A1 over a host batch: MS values, and intervals when lo/hi are given

@@ -49,6 +49,13 @@ int current_device()
     return dev;
 }
 
+DevCopy &copy_on(kbo_index *idx, int device)
+{
+    auto it = idx->dev.find(resolve_device(device));
+    KBO_REQUIRE(it != idx->dev.end(), KBO_E_BAD_ARG, "the index has no copy on that device");
+    return *it->second;
+}
+
 // the arena transient indexes borrow (DevCopy::arena_borrowed): one per host thread, reallocated when the thread has
 // moved to another device (DevBuf::ensure), freed by kbo_release_scratch() for the calling thread and at thread exit
 static DevBuf &transient_arena()
@@ -419,71 +426,63 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
         const uint64_t n_rows = idx->host.n_sets;
         const uint64_t lay_n_blocks = n_rows / kbo::kRankRowsPerBlock + 2;
         const size_t lay_ent_words = 3 * (size_t)(n_rows + 1) + 4, lay_pair_words = want_pairs ? (size_t)16 * lay_n_blocks * 4 : 0;
-        int prev = current_device();
-        if (prev != device) HIP_OK(hipSetDevice(device));
-        DevCopy *dc = new DevCopy();
+        DeviceScope scope(device);
+        std::unique_ptr<DevCopy> dc(new DevCopy());
         dc->setup.layout_s = since(t0);
-        try {
-            t0 = clk::now();
-            const size_t per = lay_n_blocks * 16;
-            // arena = rank blocks of A,C,G,T | one all-zero "null" block | contraction entries.
-            // When that exceeds the 32-bit offset range (n_sets * 12 B of entries >= ~4 GiB) the
-            // entries get their own allocation and 64-bit offsets ("big" kernels).
-            const size_t ent_bytes = lay_ent_words * sizeof(uint32_t);
-            const size_t rank_bytes = per * 4 + 16;
-            KBO_REQUIRE(rank_bytes < 0xFFFFFFF0ull, KBO_E_UNSUPPORTED, "rank blocks >= 4 GiB");
-            dc->big = g_force_big || rank_bytes + ent_bytes >= 0xFFFFFFF0ull;
-            const size_t pair_bytes = dc->big ? 0 : lay_pair_words * sizeof(uint32_t);
-            const size_t base_bytes = ((dc->big ? rank_bytes : rank_bytes + ent_bytes) + 15) / 16 * 16;
-            const size_t arena_bytes = base_bytes + pair_bytes;
-            if (idx->transient && !dc->big && !DevCopy::transient_arena_in_use()) {
-                DevBuf &t_arena = transient_arena(); // (the current device is `device` here)
-                t_arena.ensure(arena_bytes);
-                dc->arena.p = t_arena.p;
-                dc->arena_borrowed = true;
-                DevCopy::transient_arena_in_use() = true;
-            } else {
-                dc->arena.alloc(arena_bytes);
-            }
-            HIP_OK(hipMemset(dc->arena.p, 0, arena_bytes));
-            if (dc->big) dc->ent.alloc(ent_bytes + 16);
-            uint8_t *d_ent = dc->big ? dc->ent.as<uint8_t>() : dc->arena.as<uint8_t>() + rank_bytes;
-            if (on_device) {
-                const size_t n_words = (size_t)((n_rows + 63) / 64);
-                if (dc->big) HIP_OK(hipMemset(dc->ent.p, 0, ent_bytes + 16));
-                uint4 *d_pair = pair_bytes ? reinterpret_cast<uint4 *>(dc->arena.as<uint8_t>() + base_bytes) : nullptr;
-                if (built) {
-                    layout_from_device_rows(idx, built->rows, built->lcs, n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
-                } else {
-                    DevBuf d_rows(4 * n_words * 8 + 64), d_lcs((size_t)n_rows + 64);
-                    for (int c = 0; c < 4; c++)
-                        HIP_OK(hipMemcpy(d_rows.as<uint8_t>() + (size_t)c * n_words * 8, idx->host.rows[c].data(), n_words * 8, hipMemcpyHostToDevice));
-                    if (n_rows) HIP_OK(hipMemcpy(d_lcs.p, idx->host.lcs.data(), (size_t)n_rows, hipMemcpyHostToDevice));
-                    layout_from_device_rows(idx, d_rows.as<uint64_t>(), d_lcs.as<uint8_t>(), n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
-                }
-            } else {
-                for (int c = 0; c < 4; c++)
-                    HIP_OK(hipMemcpy(dc->arena.as<uint8_t>() + per * c, lay.rank[c].data(), per, hipMemcpyHostToDevice));
-                HIP_OK(hipMemcpy(d_ent, lay.ent.data(), ent_bytes, hipMemcpyHostToDevice));
-                if (pair_bytes) HIP_OK(hipMemcpy(dc->arena.as<uint8_t>() + base_bytes, lay.pair.data(), pair_bytes, hipMemcpyHostToDevice));
-            }
-            if (pair_bytes) dc->pair_off = (uint32_t)(base_bytes / 16);
-            dc->n_blocks = lay_n_blocks;
-            idx->rank_bytes = per * 4;
-            idx->lcs_bytes = ent_bytes;
-            dc->setup.rank_bytes = rank_bytes;
-            dc->setup.entry_bytes = ent_bytes;
-            dc->setup.pair_bytes = pair_bytes;
-            dc->setup.upload_s = since(t0);
-        } catch (...) {
-            delete dc;
-            if (prev != device) (void)hipSetDevice(prev);
-            throw;
+        t0 = clk::now();
+        const size_t per = lay_n_blocks * 16;
+        // arena = rank blocks of A,C,G,T | one all-zero "null" block | contraction entries.
+        // When that exceeds the 32-bit offset range (n_sets * 12 B of entries >= ~4 GiB) the
+        // entries get their own allocation and 64-bit offsets ("big" kernels).
+        const size_t ent_bytes = lay_ent_words * sizeof(uint32_t);
+        const size_t rank_bytes = per * 4 + 16;
+        KBO_REQUIRE(rank_bytes < 0xFFFFFFF0ull, KBO_E_UNSUPPORTED, "rank blocks >= 4 GiB");
+        dc->big = g_force_big || rank_bytes + ent_bytes >= 0xFFFFFFF0ull;
+        const size_t pair_bytes = dc->big ? 0 : lay_pair_words * sizeof(uint32_t);
+        const size_t base_bytes = ((dc->big ? rank_bytes : rank_bytes + ent_bytes) + 15) / 16 * 16;
+        const size_t arena_bytes = base_bytes + pair_bytes;
+        if (idx->transient && !dc->big && !DevCopy::transient_arena_in_use()) {
+            DevBuf &t_arena = transient_arena(); // (the current device is `device` here)
+            t_arena.ensure(arena_bytes);
+            dc->arena.p = t_arena.p;
+            dc->arena_borrowed = true;
+            DevCopy::transient_arena_in_use() = true;
+        } else {
+            dc->arena.alloc(arena_bytes);
         }
-        if (prev != device) HIP_OK(hipSetDevice(prev));
-        it = idx->dev.emplace(device, dc).first;
+        HIP_OK(hipMemset(dc->arena.p, 0, arena_bytes));
+        if (dc->big) dc->ent.alloc(ent_bytes + 16);
+        uint8_t *d_ent = dc->big ? dc->ent.as<uint8_t>() : dc->arena.as<uint8_t>() + rank_bytes;
+        if (on_device) {
+            const size_t n_words = (size_t)((n_rows + 63) / 64);
+            if (dc->big) HIP_OK(hipMemset(dc->ent.p, 0, ent_bytes + 16));
+            uint4 *d_pair = pair_bytes ? reinterpret_cast<uint4 *>(dc->arena.as<uint8_t>() + base_bytes) : nullptr;
+            if (built) {
+                layout_from_device_rows(idx, built->rows, built->lcs, n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
+            } else {
+                DevBuf d_rows(4 * n_words * 8 + 64), d_lcs((size_t)n_rows + 64);
+                for (int c = 0; c < 4; c++)
+                    HIP_OK(hipMemcpy(d_rows.as<uint8_t>() + (size_t)c * n_words * 8, idx->host.rows[c].data(), n_words * 8, hipMemcpyHostToDevice));
+                if (n_rows) HIP_OK(hipMemcpy(d_lcs.p, idx->host.lcs.data(), (size_t)n_rows, hipMemcpyHostToDevice));
+                layout_from_device_rows(idx, d_rows.as<uint64_t>(), d_lcs.as<uint8_t>(), n_words, lay_n_blocks, dc->arena.as<uint4>(), d_ent, d_pair);
+            }
+        } else {
+            for (int c = 0; c < 4; c++)
+                HIP_OK(hipMemcpy(dc->arena.as<uint8_t>() + per * c, lay.rank[c].data(), per, hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d_ent, lay.ent.data(), ent_bytes, hipMemcpyHostToDevice));
+            if (pair_bytes) HIP_OK(hipMemcpy(dc->arena.as<uint8_t>() + base_bytes, lay.pair.data(), pair_bytes, hipMemcpyHostToDevice));
+        }
+        if (pair_bytes) dc->pair_off = (uint32_t)(base_bytes / 16);
+        dc->n_blocks = lay_n_blocks;
+        idx->rank_bytes = per * 4;
+        idx->lcs_bytes = ent_bytes;
+        dc->setup.rank_bytes = rank_bytes;
+        dc->setup.entry_bytes = ent_bytes;
+        dc->setup.pair_bytes = pair_bytes;
+        dc->setup.upload_s = since(t0);
+        it = idx->dev.emplace(device, std::move(dc)).first;
     }
-    DevCopy *dc = it->second;
+    DevCopy *dc = it->second.get();
     // ---- the plan structures: at once when asked for (kbo_index_to_device) or cheap, else once the copy has seen the bases that
     // pay for them (plan_break_even_bases); a copy that may not hold them walks plainly, with the same results
     const bool plan_on = plan_enabled(idx); // (this index's own option first: kbo_index_set_opts)
@@ -492,8 +491,7 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
     if (!dc->plan_built && !dc->plan_failed && plan_on && !idx->transient) {
         dc->bases_seen += work_bases;
         if (prepare || dc->bases_seen >= plan_break_even_bases(idx)) {
-            int prev = current_device();
-            if (prev != device) HIP_OK(hipSetDevice(device));
+            DeviceScope scope(device);
             try {
                 build_plan_structures(idx, dc);
             } catch (const KboError &e) {
@@ -508,14 +506,9 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
                 dc->fat_null = 0;
                 dc->plan_failed = true;
                 (void)hipGetLastError();
-                if (prev != device) (void)hipSetDevice(prev);
                 if (prepare) throw;
                 last_error() = std::string("plan structures not built (the copy walks plainly): ") + e.what();
-            } catch (...) {
-                if (prev != device) (void)hipSetDevice(prev);
-                throw;
             }
-            if (prev != device && !dc->plan_failed) HIP_OK(hipSetDevice(prev));
         }
     }
     if (plan) *plan = &dc->plan;

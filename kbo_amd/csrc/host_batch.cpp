@@ -96,27 +96,15 @@ void check_batch(const void *concat, const uint64_t *offsets, size_t n_seqs)
     KBO_REQUIRE(offsets[0] == 0, KBO_E_BAD_ARG, "offsets[0] must be 0");
 }
 
-// KBO_TIMING=1 in the environment prints a phase breakdown of the host batch entry points to stderr
-struct PhaseClock {
-    bool on = std::getenv("KBO_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what)
-    {
-        if (!on) return;
-        const auto n = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[kbo timing] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
-};
-
 
 // The upload of a host batch (on `copy_stream` where given, `stream` waiting for it) and what is made of it on the device: the
 // other strand, the offsets, the work items, a packed batch's scanned words.  Returns the queries, offsets and items of the batch's
 // view (batch_route.hpp); the bytes of a packed batch are unpacked only when a route needs them
 static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, BatchOnDevice &B,
-                                 std::vector<kbo::WalkItem> &items_keep, hipStream_t stream, uint32_t longest, hipStream_t copy_stream,
-                                 hipEvent_t copied, bool call, const PackedIn *packed, const HostStage *hs)
+                                 std::vector<kbo::WalkItem> &items_keep, hipStream_t stream, const WalkHostAsk &ask)
 {
+    const PackedIn *packed = ask.packed;
+    const HostStage *hs = ask.stage;
     // strands (HostStage): what is uploaded is the first n_up sequences' up_total bases; `rev` = a reverse complement is made of it
     const int strands = hs ? hs->strands : 1;
     const bool both = strands == 3, rev = (strands & 2) != 0;
@@ -127,10 +115,10 @@ static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const ui
     v.total = B.total = offsets[n_seqs];
     // reads (nothing to chunk): the item list is derived from the offsets on the device;
     // otherwise it is built here (chunks with k-1 warm-up bases) and uploaded
-    v.longest = longest ? longest : max_len(offsets, n_seqs);
+    v.longest = ask.longest ? ask.longest : max_len(offsets, n_seqs);
     const uint64_t chunk = walk_chunk(v.total, n_seqs, idx->host.k);
     if (v.longest > chunk) v.chunk = (uint32_t)chunk;
-    if (v.chunk) make_items_host(offsets, n_seqs, idx->host.k, items_keep, call);
+    if (v.chunk) make_items_host(offsets, n_seqs, idx->host.k, items_keep, ask.call != nullptr);
     const size_t n_items = v.chunk ? items_keep.size() : n_seqs;
     KBO_REQUIRE(n_items < (1ull << 28), KBO_E_UNSUPPORTED, "more than 2^28 work items per launch");
     KBO_REQUIRE(v.total < 0xFFFFFF00ull, KBO_E_UNSUPPORTED, "4 GiB or more of query in one launch");
@@ -144,7 +132,7 @@ static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const ui
     v.q = v.bytes_out = B.q.as<uint8_t>();
     v.offsets = B.off.as<uint64_t>();
     v.items = B.items.as<kbo::WalkItem>();
-    hipStream_t up = copy_stream ? copy_stream : stream;
+    hipStream_t up = ask.copy_stream ? ask.copy_stream : stream;
     auto upload = [&](void *dst, const void *src, size_t n) {
         HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, up));
         if (hs && hs->staged) hs->staged->fetch_add(n, std::memory_order_relaxed);
@@ -168,9 +156,9 @@ static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const ui
     }
     if (!uniform) upload(B.off.p, offsets, (n_up + 1) * sizeof(uint64_t));
     if (v.chunk) upload(B.items.p, items_keep.data(), items_keep.size() / (both ? 2 : 1) * sizeof(kbo::WalkItem));
-    if (copy_stream) {
-        HIP_OK(hipEventRecord(copied, copy_stream));
-        HIP_OK(hipStreamWaitEvent(stream, copied, 0));
+    if (ask.copy_stream) {
+        HIP_OK(hipEventRecord(ask.copied, ask.copy_stream));
+        HIP_OK(hipStreamWaitEvent(stream, ask.copied, 0));
     }
     if (both && !uniform) HIP_OK(kbo::launch_double_offsets(B.off.as<uint64_t>(), (uint32_t)n_up, stream));
     if (both && v.chunk) // (a sequence's chunks depend on its length alone: the second half's items are the first's, up_total on)
@@ -210,17 +198,18 @@ static BatchView stage_walk_host(kbo_index *idx, const uint8_t *concat, const ui
 
 // upload + A1 over a host batch (asynchronous on `stream`); leaves ms (and lo/hi) on the device.
 // `items_keep` must stay alive until the stream has been synchronised.
-void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                       bool want_ival, BatchOnDevice &B, std::vector<kbo::WalkItem> &items_keep, hipStream_t stream,
-                       uint32_t longest, hipStream_t copy_stream, hipEvent_t copied, const CallSink *call, const PackedIn *packed, FusedMap *map,
-                       const HostStage *hs)
+void enqueue_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, BatchOnDevice &B,
+                       std::vector<kbo::WalkItem> &items_keep, hipStream_t stream, const WalkHostAsk &ask)
 {
+    const bool want_ival = ask.want_ival;
+    const CallSink *call = ask.call;
+    FusedMap *map = ask.map;
     KBO_REQUIRE(idx->host.k <= 255, KBO_E_UNSUPPORTED, "k > 255");
-    KBO_REQUIRE(!hs || hs->strands != 3 || n_seqs % 2 == 0, KBO_E_BAD_ARG, "both strands: a doubled slab");
+    KBO_REQUIRE(!ask.stage || ask.stage->strands != 3 || n_seqs % 2 == 0, KBO_E_BAD_ARG, "both strands: a doubled slab");
     const std::vector<kbo_index *> shards = shards_of(idx);
     KBO_REQUIRE(shards.size() == 1 || (!want_ival && !call), KBO_E_UNSUPPORTED,
                 "intervals and the call mode need the rows of one index; this handle is a sharded index");
-    BatchView v = stage_walk_host(idx, concat, offsets, n_seqs, B, items_keep, stream, longest, copy_stream, copied, call != nullptr, packed, hs);
+    BatchView v = stage_walk_host(idx, concat, offsets, n_seqs, B, items_keep, stream, ask);
     // the slab's own buffers for what the routes leave or need on the way; those not every route takes grow when one does
     for (DevBuf *b : {&B.lo, &B.hi})
         if (want_ival) b->ensure(v.total * sizeof(uint32_t));
@@ -243,7 +232,9 @@ void run_walk_host(kbo_index *idx, const uint8_t *concat, const uint64_t *offset
 {
     check_batch(concat, offsets, n_seqs);
     std::vector<kbo::WalkItem> items;
-    enqueue_walk_host(idx, concat, offsets, n_seqs, want_ival, B, items, stream);
+    WalkHostAsk ask;
+    ask.want_ival = want_ival;
+    enqueue_walk_host(idx, concat, offsets, n_seqs, B, items, stream, ask);
     HIP_OK(hipStreamSynchronize(stream)); // the items vector must outlive the async copy
 }
 
@@ -487,44 +478,25 @@ void widen_rles(kbo_rle *dst, const uint32_t *src, size_t n, HostTeam &team)
 
 // ---- the slab pipeline of kbo::matches / map / find / the MS values over a host batch (lib.rs:618-627; relative_to_ref
 // lib.rs:756-757; run lengths lib.rs:816-820): every slab is staged, walked, and leaves by its mode's output stage
+thread_local uint64_t t_last_staged = 0;
+
 namespace {
 
 // slabs of kbo_summary_batch[_packed] by the route they took (kbo_hip_tuning.h kbo_summary_slab_routes)
 std::atomic<uint64_t> g_summary_kernel_slabs{0}, g_summary_reducer_slabs{0};
 
-// what leaves the device for a slab of a host batch, and where it goes
-enum class OutMode {
-    Ms,     // kbo_ms_batch: the MS values (and the intervals, when lo / hi are given)
-    Chars,  // kbo_matches_batch, kbo_map_batch: one character per base
-    Words,  // kbo_matches_batch_packed: the characters as 2-bit words
-    Rle,    // kbo_find_batch, kbo_find_batch_into: run-length records, widened to kbo_rle
-    Rle32,  // kbo_find_batch_packed: run-length records as the device writes them
-    Sparse, // kbo_matches_batch_sparse: the runs of characters other than 'M'
-    Summary, // kbo_summary_batch, kbo_summary_batch_packed: one kbo_aln_summary per sequence, the characters stay on the device
-};
-
 // what a batch call hands to its per-device workers
 struct BatchJob {
-    OutMode mode;
+    HostOut out; // the mode and its destination
     kbo_index *idx;
     const uint8_t *concat = nullptr; // nullptr for a packed batch
     const uint64_t *offsets;
     uint32_t k, threshold = 0;
-    bool format = false; // Chars: apply format::relative_to_ref
     bool in_pinned = false, out_pinned = false; // user buffers the DMA engines reach directly are used in place
     std::vector<Slab> slabs;
     std::vector<int> devices;
     size_t n_workers = 1; // one per device of the list, as far as there are slabs
     PhaseClock *clk;      // phase timing (worker 0 only)
-    // the mode's destination
-    uint8_t *ms_out = nullptr;                     // Ms ...
-    uint32_t *lo_out = nullptr, *hi_out = nullptr; // ... with the intervals when these are given
-    uint8_t *chars_out = nullptr;                  // Chars
-    uint32_t *packed_out = nullptr;                // Words
-    RleSink<kbo_rle> *rle = nullptr;               // Rle
-    RleSink<kbo_rle32> *rle32 = nullptr;           // Rle32
-    RecordSink<kbo_aln_run> *sparse = nullptr;     // Sparse
-    kbo_aln_summary *summary_out = nullptr;        // Summary: n_seqs records
     size_t max_gap_len = 0;                        // Rle, Rle32: FindOpts' max_gap_len
     // a packed batch (kbo_matches_batch_packed / kbo_find_batch_packed / kbo_matches_batch_sparse): 2-bit words in
     const PackedBatch *packed = nullptr;
@@ -532,13 +504,11 @@ struct BatchJob {
     uint32_t uniform_len = 0;       // ... all sequences have this many bases
     uint64_t word_of(size_t s) const { return pw.empty() ? (uint64_t)s * ((uniform_len + 15u) / 16u) : pw[s]; }
     uint32_t words_per_seq() const { return uniform_len ? (uniform_len + 15u) / 16u : 0u; }
-    bool rle_mode() const { return mode == OutMode::Rle || mode == OutMode::Rle32; }
+    bool rle_mode() const { return out.mode == OutMode::Rle || out.mode == OutMode::Rle32; }
     // the strands the batch is compared in (KBO_STRAND_*; Chars, Words, Rle, Rle32).  With both, every slab is doubled on the
-    // device (HostStage): uploaded once, walked as 2 ns sequences, and its two halves leave for chars_out / packed_out ('+')
-    // and chars_rev / packed_rev ('-'); a sink puts the records in (sequence, strand) order.  One strand: that destination only.
+    // device (HostStage): uploaded once, walked as 2 ns sequences, and its two halves leave for out.chars_out / packed_out ('+')
+    // and out.chars_rev / packed_rev ('-'); a sink puts the records in (sequence, strand) order.  One strand: that destination only.
     int strands = 1;
-    uint8_t *chars_rev = nullptr;
-    uint32_t *packed_rev = nullptr;
     std::atomic<uint64_t> *staged = nullptr; // host -> device bytes of the whole batch
     template <typename T, typename F> void for_strands(T *fwd, T *rev, size_t half, F f) const // f(destination, where the strand begins in the slab's output)
     {
@@ -627,7 +597,7 @@ private:
                        // context (and the caller's pinned buffers the copies read) can be reused
         const SlabIn in = stage(S, slab_id);
         lap("  offsets + copy in");
-        switch (job_.mode) {
+        switch (job_.out.mode) {
         case OutMode::Ms: submit_ms(S, in); break;
         case OutMode::Chars: submit_chars(S, in); break;
         case OutMode::Words: submit_words(S, in); break;
@@ -714,14 +684,21 @@ private:
     void walk(HostSlot &S, const SlabIn &in, FusedMap *fm)
     {
         const HostStage hs{job_.strands, job_.staged};
-        enqueue_walk_host(job_.idx, in.src, in.off, in.ns, job_.lo_out != nullptr, S.B, S.items, C_->st_run, in.longest, C_->st_up,
-                          S.copied, nullptr, job_.packed ? &in.pin : nullptr, fm, &hs);
+        WalkHostAsk ask;
+        ask.want_ival = job_.out.lo_out != nullptr;
+        ask.longest = in.longest;
+        ask.copy_stream = C_->st_up;
+        ask.copied = S.copied;
+        ask.packed = job_.packed ? &in.pin : nullptr;
+        ask.map = fm;
+        ask.stage = &hs;
+        enqueue_walk_host(job_.idx, in.src, in.off, in.ns, S.B, S.items, C_->st_run, ask);
     }
     // kbo::matches / map / find: the characters' buffer (and, words = true, that of their 2-bit words) before the walk, so
     // that the one kernel can write into it
     FusedMap fused_map(HostSlot &S, const SlabIn &in, bool words)
     {
-        FusedMap fm{nullptr, job_.threshold, job_.format};
+        FusedMap fm{nullptr, job_.threshold, job_.out.format};
         S.chars.ensure(((in.bytes + 15) / 16) * 16 + 32);
         fm.d_chars = S.chars.as<uint8_t>();
         if (words) {
@@ -735,7 +712,7 @@ private:
     {
         if (fm.done) return;
         derand_translate_host_offsets(S.B.ms.as<uint8_t>(), S.B.off.as<uint64_t>(), in.off, in.ns, job_.k, job_.threshold,
-                                      job_.format ? S.B.q.as<uint8_t>() : nullptr, S.chars.as<uint8_t>(), nullptr, C_->st_run,
+                                      job_.out.format ? S.B.q.as<uint8_t>() : nullptr, S.chars.as<uint8_t>(), nullptr, C_->st_run,
                                       in.longest, &S.dt_work);
     }
     // ... and their 2-bit words (a quarter of the bytes) where the packed-native kernel has not written them itself
@@ -760,8 +737,8 @@ private:
         const uint64_t bytes = in.bytes;
         walk(S, in, nullptr);
         download_waits_for_kernels(S);
-        uint8_t *dst = job_.ms_out + in.sl->b0;
-        uint32_t *dlo = job_.lo_out ? job_.lo_out + in.sl->b0 : nullptr, *dhi = job_.hi_out ? job_.hi_out + in.sl->b0 : nullptr;
+        uint8_t *dst = job_.out.ms_out + in.sl->b0;
+        uint32_t *dlo = job_.out.lo_out ? job_.out.lo_out + in.sl->b0 : nullptr, *dhi = job_.out.hi_out ? job_.out.hi_out + in.sl->b0 : nullptr;
         if (!job_.out_pinned) {
             S.out.ensure(bytes + 32);
             dst = S.out.as<uint8_t>();
@@ -790,7 +767,7 @@ private:
         if (!job_.out_pinned) S.out.ensure(in.bytes + 32);
         chars_after_walk(S, in, fm);
         download_waits_for_kernels(S);
-        job_.for_strands(job_.chars_out, job_.chars_rev, in.hbytes, [&](uint8_t *user, size_t at) {
+        job_.for_strands(job_.out.chars_out, job_.out.chars_rev, in.hbytes, [&](uint8_t *user, size_t at) {
             uint8_t *dst = job_.out_pinned ? user + in.sl->b0 : S.out.as<uint8_t>() + at;
             HIP_OK(hipMemcpyAsync(dst, S.chars.as<uint8_t>() + at, in.hbytes, hipMemcpyDeviceToHost, C_->st_down));
         });
@@ -805,7 +782,7 @@ private:
         words_after_walk(S, in, fm);
         download_waits_for_kernels(S);
         if (!job_.out_pinned) S.out.ensure((size_t)in.n_words * 4 + 32);
-        job_.for_strands(job_.packed_out, job_.packed_rev, (size_t)in.hwords, [&](uint32_t *user, size_t at) {
+        job_.for_strands(job_.out.packed_out, job_.out.packed_rev, (size_t)in.hwords, [&](uint32_t *user, size_t at) {
             uint32_t *dst = job_.out_pinned ? user + in.w0 : S.out.as<uint32_t>() + at;
             HIP_OK(hipMemcpyAsync(dst, S.B.packed_out.as<uint32_t>() + at, (size_t)in.hwords * 4, hipMemcpyDeviceToHost, C_->st_down));
         });
@@ -856,7 +833,7 @@ private:
             HIP_OK(kbo::launch_summary_bytes(S.chars.as<uint8_t>(), S.B.off.as<uint64_t>(), (uint32_t)in.ns, in.bytes, S.summary.as<uint4>(), C_->st_run));
         }
         download_waits_for_kernels(S);
-        kbo_aln_summary *dst = job_.summary_out + in.sl->s0;
+        kbo_aln_summary *dst = job_.out.summary_out + in.sl->s0;
         if (!job_.out_pinned) {
             S.out.ensure(in.ns * sizeof(kbo_aln_summary));
             dst = S.out.as<kbo_aln_summary>();
@@ -954,12 +931,12 @@ private:
     {
         HostSlot &S = slot(turn);
         HIP_OK(hipEventSynchronize(S.done));
-        switch (job_.mode) {
+        switch (job_.out.mode) {
         case OutMode::Ms: finish_ms(S); break;
         case OutMode::Chars: finish_chars(S); break;
         case OutMode::Words: finish_words(S); break;
-        case OutMode::Rle: finish_rle(S, *job_.rle); break;
-        case OutMode::Rle32: finish_rle(S, *job_.rle32); break;
+        case OutMode::Rle: finish_rle(S, *job_.out.rle); break;
+        case OutMode::Rle32: finish_rle(S, *job_.out.rle32); break;
         case OutMode::Sparse: finish_sparse(S); break;
         case OutMode::Summary: finish_summary(S); break;
         }
@@ -977,17 +954,17 @@ private:
         if (job_.out_pinned) return;
         const Slab &sl = job_.slabs[S.slab_id];
         const uint64_t bytes = sl.b1 - sl.b0;
-        HostTeam::out().copy(job_.ms_out + sl.b0, S.out.p, bytes);
-        if (job_.lo_out) {
-            HostTeam::out().copy(job_.lo_out + sl.b0, S.lo_pin.p, bytes * sizeof(uint32_t));
-            HostTeam::out().copy(job_.hi_out + sl.b0, S.hi_pin.p, bytes * sizeof(uint32_t));
+        HostTeam::out().copy(job_.out.ms_out + sl.b0, S.out.p, bytes);
+        if (job_.out.lo_out) {
+            HostTeam::out().copy(job_.out.lo_out + sl.b0, S.lo_pin.p, bytes * sizeof(uint32_t));
+            HostTeam::out().copy(job_.out.hi_out + sl.b0, S.hi_pin.p, bytes * sizeof(uint32_t));
         }
     }
     void finish_chars(HostSlot &S)
     {
         const Slab &sl = job_.slabs[S.slab_id];
         if (job_.out_pinned) return;
-        job_.for_strands(job_.chars_out, job_.chars_rev, (size_t)(sl.b1 - sl.b0), [&](uint8_t *user, size_t at) {
+        job_.for_strands(job_.out.chars_out, job_.out.chars_rev, (size_t)(sl.b1 - sl.b0), [&](uint8_t *user, size_t at) {
             HostTeam::out().copy(user + sl.b0, S.out.as<uint8_t>() + at, sl.b1 - sl.b0);
         });
     }
@@ -996,7 +973,7 @@ private:
         const Slab &sl = job_.slabs[S.slab_id];
         const uint64_t w0 = job_.word_of(sl.s0), w1 = job_.word_of(sl.s1);
         if (job_.out_pinned) return;
-        job_.for_strands(job_.packed_out, job_.packed_rev, (size_t)(w1 - w0), [&](uint32_t *user, size_t at) {
+        job_.for_strands(job_.out.packed_out, job_.out.packed_rev, (size_t)(w1 - w0), [&](uint32_t *user, size_t at) {
             HostTeam::out().copy(user + w0, S.out.as<uint32_t>() + at, (size_t)(w1 - w0) * 4);
         });
     }
@@ -1004,7 +981,7 @@ private:
     {
         const Slab &sl = job_.slabs[S.slab_id];
         if (job_.out_pinned) return;
-        HostTeam::out().copy(job_.summary_out + sl.s0, S.out.p, (sl.s1 - sl.s0) * sizeof(kbo_aln_summary));
+        HostTeam::out().copy(job_.out.summary_out + sl.s0, S.out.p, (sl.s1 - sl.s0) * sizeof(kbo_aln_summary));
     }
     template <typename T> void finish_rle(HostSlot &S, RleSink<T> &sink)
     {
@@ -1015,7 +992,7 @@ private:
         const uint32_t total = *S.sp_total_pin.as<uint32_t>();
         if (total > S.sp_spec) fetch_sparse_rest(S, total);
         sp_runs_per_kseq_.store(std::max<uint64_t>(1, (uint64_t)total * 1024 / std::max<size_t>(1, S.n_seqs)), std::memory_order_relaxed);
-        job_.sparse->append(S.slab_id, S.out.p, total, HostTeam::out());
+        job_.out.sparse_runs->append(S.slab_id, S.out.p, total, HostTeam::out());
     }
 
     void drain_loop()
@@ -1076,11 +1053,7 @@ void run_on_devices(const BatchJob &job)
 {
     const size_t nd = job.n_workers;
     if (nd == 1) {
-        const int prev = current_device();
-        struct Restore { // also when run() throws
-            int prev, used;
-            ~Restore() { if (prev != used) (void)hipSetDevice(prev); }
-        } restore{prev, job.devices[0]};
+        DeviceScope scope(job.devices[0]); // (restores also when run() throws)
         SlabWorker(job, job.devices[0], 0, 1, true).run();
         return;
     }
@@ -1124,97 +1097,90 @@ OffsetScan checked_scan(const uint64_t *offsets, size_t n_seqs, bool matches, si
     return scan;
 }
 
-// the slab list, the devices and their workers, and what else of a job does not depend on its mode
-BatchJob make_job(OutMode mode, kbo_index *idx, const uint64_t *offsets, size_t n_seqs, size_t slab_bytes, size_t threshold,
+// the strands of a job (0: a single-strand entry point); slabs of half the bytes when they are doubled
+size_t strand_slab_bytes(size_t bytes, int strands) { return strands == 3 ? std::max<size_t>(bytes / 2, 1u << 15) : bytes; }
+
+// the slab list, the devices and their workers, and the destination: its sink begun, or whether the DMA engines reach it
+BatchJob make_job(const HostOut &out, int strands, kbo_index *idx, const uint64_t *offsets, size_t n_seqs, size_t slab_bytes, size_t threshold,
                   PhaseClock &clk)
 {
     BatchJob job;
-    job.mode = mode;
+    job.out = out;
+    job.strands = strands ? strands : 1;
     job.idx = idx;
     job.offsets = offsets;
     job.k = idx->host.k;
     job.threshold = (uint32_t)threshold;
-    job.slabs = make_slabs(offsets, n_seqs, slab_bytes);
+    job.slabs = make_slabs(offsets, n_seqs, strand_slab_bytes(slab_bytes, strands));
     job.devices = devices_for(idx);
     if (job.devices.empty()) job.devices.push_back(current_device());
     job.n_workers = std::min(job.devices.size(), std::max<size_t>(1, job.slabs.size()));
     job.clk = &clk;
+    auto pinned = [&](const void *fwd, const void *rev) { return (!(job.strands & 1) || is_pinned_host(fwd)) && (!(job.strands & 2) || is_pinned_host(rev)); };
+    auto begin_runs = [&](auto *sink) {
+        job.max_gap_len = sink->max_gap_len;
+        sink->strands = strands;
+        sink->begin(job.slabs, n_seqs, job.n_workers == 1);
+    };
+    switch (out.mode) {
+    case OutMode::Ms: job.out_pinned = is_pinned_host(out.ms_out) && (!out.lo_out || (is_pinned_host(out.lo_out) && is_pinned_host(out.hi_out))); break;
+    case OutMode::Chars: job.out_pinned = pinned(out.chars_out, out.chars_rev); break;
+    case OutMode::Words: job.out_pinned = pinned(out.packed_out, out.packed_rev); break;
+    case OutMode::Rle: begin_runs(out.rle); break;
+    case OutMode::Rle32: begin_runs(out.rle32); break;
+    case OutMode::Sparse: out.sparse_runs->begin(job.slabs.size(), n_seqs, job.n_workers == 1); break;
+    case OutMode::Summary: job.out_pinned = is_pinned_host(out.summary_out); break;
+    }
     return job;
 }
 
-} // namespace
-
-thread_local uint64_t t_last_staged = 0;
-
-namespace {
-// the strands of a job (0: a single-strand entry point) and its upload count; slabs of half the bytes when they are doubled
-size_t strand_slab_bytes(size_t bytes, int strands) { return strands == 3 ? std::max<size_t>(bytes / 2, 1u << 15) : bytes; }
-void run_counted(BatchJob &job)
+void run_counted(BatchJob &job) // ... and the count of what it uploads
 {
     std::atomic<uint64_t> staged{0};
     job.staged = &staged;
     run_on_devices(job);
     t_last_staged = staged.load();
 }
+
+const char *const kBadStrands = "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both";
+
 } // namespace
 
-void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
-                        double max_error_prob, bool format, uint8_t *chars_out, RleSink<kbo_rle> *sink, int strands, uint8_t *rev_out,
-                        kbo_aln_summary *summary_out)
+void matches_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, double max_error_prob, const HostOut &out,
+                        int strands)
 {
-    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!summary_out || (!strands && !sink && !format)), KBO_E_BAD_ARG, "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
-    KBO_REQUIRE(idx && (sink || summary_out || ((chars_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))), KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!strands || out.takes_strands()), KBO_E_BAD_ARG, kBadStrands);
+    KBO_REQUIRE(idx && out.complete(strands ? strands : 1), KBO_E_BAD_ARG, "null argument");
     PhaseClock clk;
     const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
     KBO_REQUIRE(concat && offsets, KBO_E_BAD_ARG, "null concat/offsets");
     checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
     clk.lap("argument checks");
-    BatchJob job = make_job(sink ? OutMode::Rle : summary_out ? OutMode::Summary : OutMode::Chars, idx, offsets, n_seqs,
-                            strand_slab_bytes(slab_bytes_for(idx), strands), threshold, clk);
+    BatchJob job = make_job(out, strands, idx, offsets, n_seqs, slab_bytes_for(idx), threshold, clk);
     job.concat = concat;
     job.in_pinned = is_pinned_host(concat);
-    job.strands = strands ? strands : 1;
-    if (sink) {
-        job.rle = sink;
-        job.max_gap_len = sink->max_gap_len;
-        sink->strands = strands;
-        sink->begin(job.slabs, n_seqs, job.n_workers == 1);
-    } else if (summary_out) {
-        job.summary_out = summary_out;
-        job.out_pinned = is_pinned_host(summary_out);
-    } else {
-        job.format = format;
-        job.chars_out = chars_out;
-        job.chars_rev = rev_out;
-        job.out_pinned = (!(job.strands & 1) || is_pinned_host(chars_out)) && (!(job.strands & 2) || is_pinned_host(rev_out));
-    }
     clk.lap("slab list");
     run_counted(job);
 }
 
 // kbo::matches / kbo::find over a batch of 2-bit packed reads: the same pipeline, a quarter of the bytes over PCIe each way
 void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint64_t *offsets, size_t n_seqs, double max_error_prob,
-                               uint32_t *packed_out, RleSink<kbo_rle32> *sink, RecordSink<kbo_aln_run> *sparse, int strands, uint32_t *rev_out,
-                               kbo_aln_summary *summary_out)
+                               const HostOut &out, int strands)
 {
-    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!sparse || !strands) && (!summary_out || (!strands && !sink && !sparse)), KBO_E_BAD_ARG,
-                "strands: KBO_STRAND_FWD, KBO_STRAND_REV or both");
-    KBO_REQUIRE(idx && in.words && (sink || sparse || summary_out || ((packed_out || !((strands ? strands : 1) & 1)) && (rev_out || !(strands & 2)))),
-                KBO_E_BAD_ARG, "null argument");
+    KBO_REQUIRE(strands >= 0 && strands <= 3 && (!strands || out.takes_strands()), KBO_E_BAD_ARG, kBadStrands);
+    KBO_REQUIRE(idx && in.words && out.complete(strands ? strands : 1), KBO_E_BAD_ARG, "null argument");
     KBO_REQUIRE(in.n_exc == 0 || (in.exc_pos && in.exc_byte), KBO_E_BAD_ARG, "null exception list");
     PhaseClock clk;
     const size_t threshold = random_match_threshold(idx->host.k, idx->host.n_kmers, 4, max_error_prob); // lib.rs:620
     KBO_REQUIRE(offsets, KBO_E_BAD_ARG, "null offsets");
     const OffsetScan scan = checked_scan(offsets, n_seqs, true, idx->host.k, threshold);
-    KBO_REQUIRE(!sparse || scan.longest < (1ull << 30), KBO_E_UNSUPPORTED, "sequence of 2^30 bases or more (kbo_aln_run has 30 bits of length)");
+    KBO_REQUIRE(out.mode != OutMode::Sparse || scan.longest < (1ull << 30), KBO_E_UNSUPPORTED, "sequence of 2^30 bases or more (kbo_aln_run has 30 bits of length)");
     for (size_t x = 0; x < in.n_exc; x++) // (ascending, inside the batch: the slabs cut the list by binary search)
         KBO_REQUIRE(in.exc_pos[x] < offsets[n_seqs] && (x == 0 || in.exc_pos[x] > in.exc_pos[x - 1]), KBO_E_BAD_ARG,
                     "exception positions must ascend and lie inside the batch");
     clk.lap("argument checks");
-    const OutMode mode = sink ? OutMode::Rle32 : sparse ? OutMode::Sparse : summary_out ? OutMode::Summary : OutMode::Words;
-    BatchJob job = make_job(mode, idx, offsets, n_seqs, strand_slab_bytes(packed_slab_bytes(idx), strands), threshold, clk);
+    BatchJob job = make_job(out, strands, idx, offsets, n_seqs, packed_slab_bytes(idx), threshold, clk);
     job.packed = &in;
-    job.strands = strands ? strands : 1;
     job.in_pinned = is_pinned_host(in.words);
     if (scan.shortest == scan.longest) {
         job.uniform_len = (uint32_t)scan.longest;
@@ -1222,22 +1188,6 @@ void matches_batch_packed_impl(kbo_index *idx, const PackedBatch &in, const uint
         job.pw.resize(n_seqs + 1);
         job.pw[0] = 0;
         for (size_t s = 0; s < n_seqs; s++) job.pw[s + 1] = job.pw[s] + (offsets[s + 1] - offsets[s] + 15) / 16;
-    }
-    if (sink) {
-        job.rle32 = sink;
-        job.max_gap_len = sink->max_gap_len;
-        sink->strands = strands;
-        sink->begin(job.slabs, n_seqs, job.n_workers == 1);
-    } else if (sparse) {
-        job.sparse = sparse;
-        sparse->begin(job.slabs.size(), n_seqs, job.n_workers == 1);
-    } else if (summary_out) {
-        job.summary_out = summary_out;
-        job.out_pinned = is_pinned_host(summary_out);
-    } else {
-        job.packed_out = packed_out;
-        job.packed_rev = rev_out;
-        job.out_pinned = (!(job.strands & 1) || is_pinned_host(packed_out)) && (!(job.strands & 2) || is_pinned_host(rev_out));
     }
     clk.lap("slab list");
     run_counted(job);
@@ -1254,13 +1204,9 @@ void ms_batch_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *offset
     PhaseClock clk;
     // intervals cost 8 more bytes per base on the device and on the way back: smaller slabs
     const size_t slab_bytes = lo_out ? std::max<size_t>(1u << 16, slab_bytes_for(idx) / 4) : slab_bytes_for(idx);
-    BatchJob job = make_job(OutMode::Ms, idx, offsets, n_seqs, slab_bytes, 0, clk);
+    BatchJob job = make_job(HostOut::ms(d_out, lo_out, hi_out), 0, idx, offsets, n_seqs, slab_bytes, 0, clk);
     job.concat = concat;
-    job.ms_out = d_out;
-    job.lo_out = lo_out;
-    job.hi_out = hi_out;
     job.in_pinned = is_pinned_host(concat);
-    job.out_pinned = is_pinned_host(d_out) && (!lo_out || (is_pinned_host(lo_out) && is_pinned_host(hi_out)));
     run_counted(job);
 }
 

@@ -1,13 +1,15 @@
 // host_util.hpp — small host-side utilities of the C ABI layer: the error type that carries a
-// KBO_E_* code across internal calls, RAII device / pinned buffers, and the helper-thread team
-// used for staging copies and offset scans.
+// KBO_E_* code across internal calls, the scope that moves the calling thread to a device, the phase
+// clock, RAII device / pinned buffers, and the helper-thread team used for staging copies and offset scans.
 #pragma once
 #include "../../include/kbo_hip.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -66,6 +68,40 @@ template <typename F> inline int guarded(F f)
         return KBO_E_BAD_ARG;
     }
 }
+
+// the calling thread on `device` until the scope ends (device < 0: left where it is); a restore that fails is ignored
+struct DeviceScope {
+    int prev = -1;
+    bool moved = false;
+    explicit DeviceScope(int device)
+    {
+        HIP_OK(hipGetDevice(&prev));
+        if (device >= 0 && device != prev) {
+            HIP_OK(hipSetDevice(device));
+            moved = true;
+        }
+    }
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+    ~DeviceScope()
+    {
+        if (moved) (void)hipSetDevice(prev);
+    }
+};
+
+// KBO_TIMING=1 in the environment prints a phase breakdown of the host batch entry points to stderr
+struct PhaseClock {
+    const char *prefix = "[kbo timing]";
+    bool on = std::getenv("KBO_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what)
+    {
+        if (!on) return;
+        const auto n = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "%s %-28s %8.3f ms\n", prefix, what, std::chrono::duration<double, std::milli>(n - t).count());
+        t = n;
+    }
+};
 
 // RAII device buffer
 struct DevBuf {

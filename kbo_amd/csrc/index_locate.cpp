@@ -29,24 +29,6 @@ namespace {
 std::atomic<uint64_t> g_slab_bases{0}; // kbo_set_positions_slab_bases: source bases a slab of kbo_index_add_positions adds (0 = the default)
 constexpr uint64_t kDefaultSlabBases = 32ull << 20;
 
-// the current device changed for a scope (device < 0: left as it is)
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceScope(int device)
-    {
-        prev = current_device();
-        if (device >= 0 && device != prev) {
-            HIP_OK(hipSetDevice(device));
-            switched = true;
-        }
-    }
-    ~DeviceScope()
-    {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
 void ok(int rc)
 {
     if (rc != KBO_OK) throw KboError(rc, last_error());
@@ -90,7 +72,7 @@ const uint32_t *positions_on(kbo_index *idx, int dev, bool make)
         if (!idx->positions.empty())
             HIP_OK(hipMemcpy(b.p, idx->positions.data(), idx->positions.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    if (make) upload_src_off(idx, it->second);
+    if (make) upload_src_off(idx, it->second.get());
     return b.as<uint32_t>();
 }
 
@@ -182,7 +164,7 @@ void add_positions(kbo_index *idx, const uint8_t *const *seqs, const size_t *len
     std::swap(keep.p, mn.p);
     std::swap(keep.cap, mn.cap);
     std::swap(keep.dev, mn.dev);
-    upload_src_off(idx, idx->dev.at(dev));
+    upload_src_off(idx, idx->dev.at(dev).get());
 }
 
 struct HostIn {

@@ -59,7 +59,7 @@ struct HostRing {
     plc::State get(uint32_t slot) const { return st[slot]; }
     void set(uint32_t slot, const plc::State &v) { st[slot] = v; }
 };
-struct HostOut {
+struct HostPlaces {
     kbo_seq_place *p;
     plc::Place get(uint32_t s) const
     {
@@ -128,7 +128,7 @@ int kbo_place_from_segments_host(const kbo_seq_segment *segs, uint64_t n_segs, s
         w.e.resize(n_seqs);
         w.s.resize(n_segs);
         HostRing ring;
-        HostOut out{place};
+        HostPlaces out{place};
         plc::place_serial(HostSegs{segs}, (uint32_t)n_segs, (uint32_t)n_seqs, HostOff{src_off}, (uint32_t)n_src, plc::Limits{k, max_gap, max_indel},
                           merge != 0, w, ring, out);
     });

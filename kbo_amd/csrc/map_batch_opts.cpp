@@ -261,7 +261,7 @@ void map_batch_opts_impl(kbo_index *idx, const uint8_t *concat, const uint64_t *
     if (o.fill_gaps) fill_gaps_core(idx, sub.concat, soff, m, threshold, o.max_error_prob, res, st.data(), run);
     else {
         clk::time_point t0 = clk::now();
-        matches_batch_impl(idx, sub.concat, soff, m, o.max_error_prob, o.format != 0 && !o.call_variants, res);
+        matches_batch_impl(idx, sub.concat, soff, m, o.max_error_prob, HostOut::chars(res, nullptr, o.format != 0 && !o.call_variants));
         run.phase[0] += since(t0);
     }
     // ---- variants (lib.rs:749-754): the whole batch through kbo_call_batch_flat, then add_variants per sequence

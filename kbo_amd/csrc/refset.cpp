@@ -44,7 +44,7 @@ DevSet *device_set(kbo_refset *set, int device)
 {
     std::lock_guard<std::mutex> g(set->mu);
     auto it = set->dev.find(device);
-    if (it != set->dev.end()) return it->second;
+    if (it != set->dev.end()) return it->second.get();
     DeviceScope on(device);
     std::unique_ptr<DevSet> d(new DevSet());
     d->arena.alloc(set->arena.size() * sizeof(uint32_t) + 16);
@@ -73,8 +73,7 @@ DevSet *device_set(kbo_refset *set, int device)
         HIP_OK(hipMemcpy(d->cov.p, set->cov_off.data(), (n_refs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d->cov.as<uint8_t>() + (n_refs + 1) * sizeof(uint64_t), lens.data(), n_refs * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    set->dev[device] = d.get();
-    return d.release();
+    return (set->dev[device] = std::move(d)).get();
 }
 
 std::vector<uint32_t> refset_thresholds(const kbo_refset *set, double max_error_prob)
@@ -148,7 +147,7 @@ DevSet *require_device_set(kbo_refset *set, bool any_first)
     std::lock_guard<std::mutex> g(set->mu);
     auto it = set->dev.find(device);
     KBO_REQUIRE(it != set->dev.end(), KBO_E_BAD_ARG, "the set has no copy on the current device (kbo_refset_to_device)");
-    return it->second;
+    return it->second.get();
 }
 
 kbo::RefsetScreenArgs screen_args(const DevSet *ds, size_t n_seqs, uint64_t total, int strands)
@@ -589,7 +588,7 @@ void index_route_extents(kbo_refset *set, const uint8_t *concat, const uint64_t 
         if (set->descs[r].status || set->descs[r].route != kbo::kRefsetRouteIndex) continue;
         if (strands & KBO_STRAND_FWD) fwd.resize(total);
         if (strands & KBO_STRAND_REV) rev.resize(total);
-        matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, max_error_prob, false, fwd.data(), nullptr, strands, rev.data());
+        matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, max_error_prob, HostOut::chars(fwd.data(), rev.data(), false), strands);
         for (size_t s = 0; s < n_seqs; s++)
             for (uint32_t strand = 1; strand <= 2; strand++) {
                 if (!(strands & strand)) continue;
@@ -713,7 +712,7 @@ int kbo_refset_to_device(kbo_refset_t *set, int device)
 {
     return guarded([&] {
         KBO_REQUIRE(set, KBO_E_BAD_ARG, "null set");
-        const int dev = device < 0 ? current_device() : device;
+        const int dev = resolve_device(device);
         (void)device_set(set, dev);
         for (auto &idx : set->own)
             if (idx) (void)device_view(idx.get(), dev, nullptr, 0, true);
@@ -862,7 +861,7 @@ int kbo_find_refset(kbo_refset_t *set, const uint8_t *concat, const uint64_t *of
             RleSink<kbo_rle> sink;
             sink.max_gap_len = o.max_gap_len;
             sink.rle_offsets = rle_off.data();
-            matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, o.max_error_prob, false, nullptr, &sink, strands);
+            matches_batch_impl(set->own[r].get(), concat, offsets, n_seqs, o.max_error_prob, HostOut::runs(&sink), strands);
             kbo_rle *got = nullptr;
             sink.take(&got);
             MallocPtr<kbo_rle> hold(got);

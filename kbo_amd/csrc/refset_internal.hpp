@@ -40,23 +40,6 @@ struct DevSet {
     DevBuf cov;                            // ... and its base offsets (n_refs + 1 u64), then every reference's length (n_refs u32)
 };
 
-struct DeviceScope { // the calling thread on `device` until the scope ends
-    int prev = -1;
-    bool moved = false;
-    explicit DeviceScope(int device)
-    {
-        HIP_OK(hipGetDevice(&prev));
-        if (device >= 0 && device != prev) {
-            HIP_OK(hipSetDevice(device));
-            moved = true;
-        }
-    }
-    ~DeviceScope()
-    {
-        if (moved) (void)hipSetDevice(prev);
-    }
-};
-
 struct StreamScope {
     hipStream_t s = nullptr;
     StreamScope() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -89,11 +72,7 @@ struct kbo_refset {
     // none for a reference without entries (n_refs + 1 offsets)
     std::vector<uint64_t> cov_off;
     std::mutex mu;
-    std::map<int, kbo_host::DevSet *> dev;
-    ~kbo_refset()
-    {
-        for (auto &kv : dev) delete kv.second;
-    }
+    std::map<int, std::unique_ptr<kbo_host::DevSet>> dev;
 };
 
 namespace kbo_host {

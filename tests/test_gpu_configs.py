@@ -483,6 +483,43 @@ def test_host_batches_over_two_distinct_devices(oracle):
         assert [(q, a.decode(), b.decode()) for q, a, b in per_dev[1][s]] == exp
 
 
+def test_hooks_on_another_device_leave_the_thread_where_it_was():
+    """kbo_index_to_device, kbo_index_plan_part and kbo_index_depth_table asked for device 1 while device 0 is current: the calling
+    thread is on device 0 after every call - also after the one that is refused for a buffer one byte short - and what comes back
+    from the copy on device 1 is what the copy on device 0 holds.  Skipped on boxes with one GPU."""
+    import ctypes as C
+    import torch
+    from kbo_amd import _capi
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    L = kbo_amd.lib()
+    sbwt, _ = kbo_amd.build([synth.genome(20_000, seed=53)], kbo_amd.BuildOpts(k=31, num_threads=_threads()))
+    part = _capi.PLAN_PARTS["pc_t"][0]
+    with torch.cuda.device(0):
+        kbo_amd.check(L.kbo_index_to_device(sbwt._h, 1))
+        assert torch.cuda.current_device() == 0
+        nb, info = C.c_size_t(0), (C.c_uint32 * 4)()
+        kbo_amd.check(L.kbo_index_plan_part(sbwt._h, 1, part, None, C.byref(nb), info))
+        assert torch.cuda.current_device() == 0
+        need = nb.value
+        assert need > 0, "an index of this size has the text's digits"
+        buf = np.zeros(need, dtype=np.uint8)
+        nb.value = need - 1
+        assert L.kbo_index_plan_part(sbwt._h, 1, part, buf.ctypes.data, C.byref(nb), info) == -4  # KBO_E_BAD_ARG
+        assert torch.cuda.current_device() == 0
+        nb.value = need
+        assert L.kbo_index_plan_part(sbwt._h, 1, part, buf.ctypes.data, C.byref(nb), info) == 0 and nb.value == need
+        assert torch.cuda.current_device() == 0
+        table, order = sbwt.depth_table(device=1)
+        assert torch.cuda.current_device() == 0
+        assert order > 0 and table.size == 4 ** order
+        here, _ = sbwt.plan_part("pc_t", device=0)
+        assert np.array_equal(buf.view(here.dtype), here)
+        table0, order0 = sbwt.depth_table(device=0)
+        assert order0 == order and np.array_equal(table0, table)
+        assert torch.cuda.current_device() == 0
+
+
 def test_device_made_layout_equals_the_hosts(plan_restore):
     """a device copy's rank blocks, contraction entries and two-base blocks are made on the device from the row bit-vectors and the LCS bytes
     (layout_kernels.hip), its path cover from those (cover_kernels.hip): byte for byte the host's make_device_layout / make_path_cover - 32-bit entries in the arena, 64-bit entries by force, two-base
