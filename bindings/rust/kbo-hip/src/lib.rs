@@ -294,6 +294,25 @@ pub mod ffi {
                                             k: u32, max_gap: u32, max_indel: u32, merge: c_int, place: *mut super::SeqPlace) -> c_int;
         pub fn kbo_place_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
                                max_gap: u32, max_indel: u32, place_out: *mut super::SeqPlace) -> c_int;
+        // pileup: what the reads say at every source base - one integer atomic per base that no exact window of its segment covers,
+        // into d_pile ([source_bases][4] u32, zeroed once, shared by batches and strands like d_delta) - behind kbo_segments_dev on
+        // the same stream and without scratch; pileup_sites_dev turns pile and depth into candidate sites (flag, scan, emit);
+        // the *_host calls restate both on the CPU, pileup_batch is the host form (sites released by kbo_free)
+        pub fn kbo_pileup_dev(idx: *mut KboIndex, d_concat: *const u8, d_ms: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                              d_segs: *const super::SeqSegment, d_n_segs: *const u64, capacity: usize, skip_multi: c_int, d_pile: *mut u32,
+                              stream: *mut c_void) -> c_int;
+        pub fn kbo_pileup_sites_work_bytes(idx: *const KboIndex) -> usize;
+        pub fn kbo_pileup_sites_dev(idx: *mut KboIndex, d_pile: *const u32, d_depth: *const u32, min_count: u32, frac_num: u32, frac_den: u32,
+                                    d_sites: *mut super::PileSite, capacity: usize, d_n_sites: *mut u64, d_work: *mut c_void,
+                                    work_bytes: usize, stream: *mut c_void) -> c_int;
+        pub fn kbo_pileup_from_segments_host(segs: *const super::SeqSegment, n_segs: u64, concat: *const u8, ms: *const u8, offsets: *const u64,
+                                             n_seqs: usize, total_bases: u64, k: u32, skip_multi: c_int, pile: *mut u32, source_bases: u64,
+                                             n_bridged: *mut u64) -> c_int;
+        pub fn kbo_pileup_sites_host(pile: *const u32, depth: *const u32, source_bases: u64, src_off: *const u64, n_src: usize, min_count: u32,
+                                     frac_num: u32, frac_den: u32, sites: *mut super::PileSite, capacity: usize, n_sites: *mut u64) -> c_int;
+        pub fn kbo_pileup_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
+                                skip_multi: c_int, min_count: u32, frac_num: u32, frac_den: u32, sites: *mut *mut super::PileSite,
+                                n_sites: *mut u64, depth_out: *mut u32, pile_out: *mut u32) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -485,6 +504,19 @@ pub struct SeqPlace {
     pub indel: u32,
     pub n_multi: u32,
     pub second: u32,
+    pub reserved: u32,
+}
+
+/// `kbo_pile_site` (32 bytes): a source base where a column of the pile holds at least `min_count` reads and at least
+/// `frac_num / frac_den` of the depth.  `pos` in source coordinates, `source` the sequence that holds it, `count`: the reads whose
+/// bridged base there is A, C, G, T - the column of the source's own base among them, which the caller drops against its text.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct PileSite {
+    pub pos: u32,
+    pub source: u32,
+    pub depth: u32,
+    pub count: [u32; 4],
     pub reserved: u32,
 }
 

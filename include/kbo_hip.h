@@ -1351,6 +1351,83 @@ int kbo_place_from_segments_host(const kbo_seq_segment *segs, uint64_t n_segs, s
                                  uint32_t max_gap, uint32_t max_indel, int merge, kbo_seq_place *place);
 int kbo_place_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands,
                     uint32_t max_gap, uint32_t max_indel, kbo_seq_place *place_out);
+/* ------------------------------------------------------------------ Pileup: what the reads SAY at every source base, candidate sites
+ * DEPTH says that 31 reads cover source base j; this section says that 29 of them carry a T there where the source has a C (DESIGN.md
+ * 4.15; the arithmetic: kbo_amd/csrc/index_pileup.hpp, the kernels: kbo_amd/csrc/pileup_kernels.hip).  A segment fixes a diagonal, so
+ * every base inside its extent has one source coordinate, and the only bases that can differ from the source are the ones no exact
+ * k-mer window of the segment covers: about 1 % of the bases at 1 % divergence.  A pileup is one integer atomic per such base.
+ *
+ * DEFINITIONS.  Take the records of one kbo_segments_dev call, the batch as it was walked (d_concat, d_offsets; for the '-' strand
+ * the reverse-complemented batch, as everywhere) and the MS bytes that walk wrote (d_ms).
+ * ANCHORS AND BRIDGED BASES.  For a record with sequence s and o = offsets[s], a window w in [q_first, q_last] is an ANCHOR iff
+ * ms[o + w + k - 1] == k; every such anchor belongs to the segment, segments being maximal stretches of the anchor list.  A base x in
+ * [q_first, q_last + k) is COVERED when some anchor a has a <= x < a + k, and BRIDGED otherwise.  Equivalently, for a record as
+ * kbo_segments_dev writes it: for consecutive anchors a < b with b - a > k the bridged bases are a + k .. b - 1.
+ * PROJECTION.  A bridged base x of a FWD record is counted at j = pos_first + (x - q_first) as the byte at x; of a REV record (flag bit
+ * 0) at j = pos_first + k - 1 - (x - q_first) as the complement of the byte at x.  Base codes: A, C, G, T = 0 .. 3 as kbo_pack_reads
+ * codes them; every other byte (N, lower case) is counted in no column.
+ * THE PILE is uint32_t pile[source_bases][4] (16-byte aligned), zeroed once by the caller and shared by any number of batches and
+ * strands, exactly like d_delta; it is added to by integer atomics, so the result is the same whatever the arrival order.
+ * skip_multi != 0 leaves out a record whose flags hold either MULTI bit: a k-mer that also occurs elsewhere is placed at its stored
+ * occurrence only, which is evidence a SNP caller does not want.
+ * RECORDS THAT HOLD ANYTHING.  A record contributes nothing when seq >= n_seqs, when q_first > q_last, when o + q_last + k is past the
+ * sequence's end, or when the sequence's offsets descend or end beyond total_bases; a single projected j outside [0, source_bases)
+ * is skipped.  No load or store leaves the caller's buffers.  The host form applies the same rules: host and device agree byte for byte
+ * on any list.
+ * RELATION TO DEPTH.  When d_delta was accumulated by the same kbo_segments_dev calls, the sum over b of pile[j][b] is at most
+ * DEPTH[j] for every j, and DEPTH[j] minus that sum is the number of reads that match the source exactly at j plus those whose
+ * bridged byte there is no base.
+ * SITES.  Base j is a SITE iff some b has pile[j][b] >= min_count and pile[j][b] * frac_den >= frac_num * DEPTH[j], the products in 64
+ * bits; frac_den == 0 or min_count == 0 is KBO_E_BAD_ARG.  A column that equals the source base can qualify - a base between two
+ * nearby substitutions is bridged too - and the device does not hold the source text: the caller drops that column
+ * (kbo_amd.pileup_snps).  One kbo_pile_site is 32 bytes: pos in source coordinates, source by a bisection of the device copy of src_off
+ * (the last source whose offset is <= pos), depth, count[4], reserved = 0.  Sites are in ascending pos; record x is written iff x <
+ * capacity, *d_n_sites (8-byte aligned) is the full count, nothing at or behind element `capacity` is touched.
+ *
+ * kbo_pileup_dev uses min(*d_n_segs, capacity) records, read on the device, as kbo_place_dev does, and is a device-resident call like
+ * the others: ONE launch on `stream` - waves stride over the records, a wave takes a record's windows 64 at a time, a lane loads one
+ * MS byte, one ballot gives the anchors, the lane of an anchor counts the bridged bases in front of it - that allocates nothing,
+ * synchronises nothing and reads nothing back.  It takes no scratch.  d_concat and d_ms: total_bases bytes; d_offsets: n_seqs + 1
+ * values; d_pile is added to, never cleared.  d_segs may be NULL when capacity == 0.  Errors, before anything is enqueued and in this
+ * order: KBO_E_BAD_ARG for null or misaligned pointers (d_segs 4-byte, d_offsets and d_n_segs 8-byte, d_pile 16-byte);
+ * KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_UNSUPPORTED for total_bases + 16 > 2^32, n_seqs >= 2^28 or capacity >= 2^32 - 1 and for a
+ * sharded handle; KBO_E_BAD_ARG for a handle without positions and for one without positions on the current device.
+ * kbo_pileup_sites_dev is flag, scan, emit - the plain three-pass scan of kbo_segments_dev and kbo_depth_finish_dev, three launches,
+ * no workgroup waits for another - over d_pile and d_depth (source_bases words, as kbo_depth_finish_dev wrote them).  No byte of
+ * d_work beyond kbo_pileup_sites_work_bytes(idx) - exact: 4 bytes per 2048 source bases rounded up to 16, at least 16; 0 for a handle
+ * without positions - or of d_sites beyond `capacity` records is touched; d_sites may be NULL when capacity == 0.  Errors, in this
+ * order: KBO_E_BAD_ARG for null or misaligned pointers (d_depth 4-byte, d_n_sites 8-byte, d_pile, d_sites and d_work 16-byte) and for
+ * min_count == 0 or frac_den == 0; KBO_E_UNSUPPORTED for a sharded handle; KBO_E_BAD_ARG for a handle without positions, for one
+ * without positions on the current device, and for a short work_bytes.
+ * kbo_pileup_from_segments_host and kbo_pileup_sites_host are the two calls restated on the CPU (no HIP call; host arrays; src_off:
+ * n_src + 1 values as kbo_index_source_offsets gives them): byte-identical pile, sites and count, for any list.  *n_bridged (or NULL)
+ * receives the bridged bases of the records taken, counted in a column or not.  KBO_E_BAD_ARG for null arguments (segs may be NULL
+ * when n_segs == 0, sites when capacity == 0), k == 0, n_src == 0, the two thresholds and src_off that does not start at 0 or
+ * descends; KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_UNSUPPORTED beyond the limits above and for sources of 2^30 bases or more.
+ * kbo_pileup_batch is the host form: upload, the '-' strand made on the device, the interval walk, kbo_segments_dev (once to count,
+ * once to write, with one delta for all strands) and kbo_pileup_dev per strand into one pile, the depth finish, the sites (once to
+ * count, once to write), one download.  *sites is malloc'ed (kbo_free); depth_out (source_bases words) and pile_out (4 * source_bases
+ * words) may be NULL and are written, not added to.  Errors as kbo_segments_batch, the two threshold checks behind bridge > 255. */
+typedef struct {
+    uint32_t pos;      /* source coordinates */
+    uint32_t source;   /* the last source whose offset is <= pos */
+    uint32_t depth;    /* DEPTH[pos] */
+    uint32_t count[4]; /* pile[pos][A, C, G, T] */
+    uint32_t reserved; /* 0 */
+} kbo_pile_site;       /* 32 bytes */
+int kbo_pileup_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint8_t *d_ms, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                   const kbo_seq_segment *d_segs, const uint64_t *d_n_segs, size_t capacity, int skip_multi, uint32_t *d_pile, void *stream);
+size_t kbo_pileup_sites_work_bytes(const kbo_index_t *idx);
+int kbo_pileup_sites_dev(kbo_index_t *idx, const uint32_t *d_pile, const uint32_t *d_depth, uint32_t min_count, uint32_t frac_num, uint32_t frac_den,
+                         kbo_pile_site *d_sites, size_t capacity, uint64_t *d_n_sites, void *d_work, size_t work_bytes, void *stream);
+int kbo_pileup_from_segments_host(const kbo_seq_segment *segs, uint64_t n_segs, const uint8_t *concat, const uint8_t *ms, const uint64_t *offsets,
+                                  size_t n_seqs, uint64_t total_bases, uint32_t k, int skip_multi, uint32_t *pile, uint64_t source_bases,
+                                  uint64_t *n_bridged);
+int kbo_pileup_sites_host(const uint32_t *pile, const uint32_t *depth, uint64_t source_bases, const uint64_t *src_off, size_t n_src, uint32_t min_count,
+                          uint32_t frac_num, uint32_t frac_den, kbo_pile_site *sites, size_t capacity, uint64_t *n_sites);
+int kbo_pileup_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands, int skip_multi,
+                     uint32_t min_count, uint32_t frac_num, uint32_t frac_den, kbo_pile_site **sites, uint64_t *n_sites, uint32_t *depth_out,
+                     uint32_t *pile_out);
 
 /* ---- alignment summaries (kbo_aln_summary, above) of device-resident batches; asynchronous, the library never synchronises.
  * kbo_summary_batch_dev: kbo::matches over the batch as kbo_map_batch_dev_tail runs it (format = 0: the same routes, streams and

@@ -31,6 +31,8 @@ from .refset import call_refset, call_refset_dev, variant_chars  # noqa: F401,E4
 from . import locate  # noqa: F401,E402
 from .locate import add_positions, depth_finish_dev, segment_source, segments, segments_dev  # noqa: F401,E402
 from .locate import place, place_dev, place_from_segments_host, place_local, place_work_bytes  # noqa: F401,E402
+from .locate import pileup, pileup_dev, pileup_from_segments_host, pileup_sites_dev, pileup_sites_host  # noqa: F401,E402
+from .locate import pileup_sites_work_bytes, pileup_snps  # noqa: F401,E402
 
 
 @dataclass

@@ -160,6 +160,8 @@ SYMBOLS = [
     "kbo_index_source_bases", "kbo_index_positions_to_device", "kbo_positions_from_ms_host", "kbo_segments_work_bytes", "kbo_segments_dev",
     "kbo_segments_from_ms_host", "kbo_depth_work_bytes", "kbo_depth_finish_dev", "kbo_segments_batch",
     "kbo_place_work_bytes", "kbo_place_dev", "kbo_place_from_segments_host", "kbo_place_batch",
+    "kbo_pileup_dev", "kbo_pileup_sites_work_bytes", "kbo_pileup_sites_dev", "kbo_pileup_from_segments_host", "kbo_pileup_sites_host",
+    "kbo_pileup_batch",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -456,6 +458,12 @@ def lib():
     L.kbo_place_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, C.c_int, vp, vp, sz, vp]
     L.kbo_place_from_segments_host.argtypes = [vp, u64, sz, vp, sz, u32, u32, u32, C.c_int, vp]
     L.kbo_place_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, u32, u32, vp]
+    L.kbo_pileup_dev.argtypes = [vp, vp, vp, vp, sz, u64, vp, vp, sz, C.c_int, vp, vp]
+    L.kbo_pileup_sites_work_bytes.argtypes = [vp]; L.kbo_pileup_sites_work_bytes.restype = sz
+    L.kbo_pileup_sites_dev.argtypes = [vp, vp, vp, u32, u32, u32, vp, sz, vp, vp, sz, vp]
+    L.kbo_pileup_from_segments_host.argtypes = [vp, u64, vp, vp, vp, sz, u64, u32, C.c_int, vp, u64, C.POINTER(u64)]
+    L.kbo_pileup_sites_host.argtypes = [vp, vp, u64, vp, sz, u32, u32, u32, vp, sz, C.POINTER(u64)]
+    L.kbo_pileup_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, C.c_int, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), vp, vp]
     L.kbo_segments_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.kbo_set_positions_slab_bases.argtypes = [u64]
     _lib = L

@@ -7,7 +7,8 @@
 //   batch_route.cpp   the kernel route of a batch, for host slabs and device calls alike (batch_route.hpp),
 //   build_device.cpp  kbo_index_build_device (the index built by the device),
 //   index_locate.cpp  the position table of an index, the segments of a batch and the depth of the sources,
-//   index_place.cpp   one placement per sequence from those segments.
+//   index_place.cpp   one placement per sequence from those segments,
+//   index_pileup.cpp  allele counts per source base from those segments, and the candidate sites.
 #pragma once
 #include <atomic>
 #include <cstdint>

@@ -856,6 +856,33 @@ struct PlaceArgs {
 // at most four launches, sized by n_seqs and capacity alone: the ranges cleared, a lane per record, a lane per sequence, a wave per
 // sequence with a long list (the second and the fourth only when capacity can hold such records)
 hipError_t launch_place(const PlaceArgs &a, hipStream_t stream);
+// ---- pileup_kernels.hip (the arithmetic and the d_work figure: index_pileup.hpp)
+struct PileupArgs {
+    const uint32_t *segs;    // records of 7 words as launch_segments left them: min(*n_segs, capacity) are looked at
+    const uint64_t *n_segs;
+    uint64_t capacity;
+    const uint8_t *concat;   // the batch as it was walked, and the MS bytes of that walk: `total` bytes each
+    const uint8_t *ms;
+    const uint64_t *off;     // n_seqs + 1 values
+    uint32_t n_seqs, k;
+    uint64_t total, source_bases;
+    bool skip_multi;
+    uint32_t *pile;          // source_bases rows of four words, added to
+};
+// one launch, sized by capacity alone (none when capacity, total or source_bases is 0)
+hipError_t launch_pileup(const PileupArgs &a, hipStream_t stream);
+struct PileupSitesArgs {
+    const void *pile;        // source_bases rows of four words, 16-byte aligned
+    const uint32_t *depth;   // source_bases words
+    const uint64_t *src_off; // n_src + 1 values
+    uint32_t n_src, min_count, frac_num, frac_den;
+    uint64_t source_bases, capacity;
+    void *sites;             // capacity records of 32 bytes, 16-byte aligned
+    uint64_t *n_sites;
+    void *work;              // idxpile::sites_work(source_bases) bytes
+};
+// three launches: the sites of every chunk counted, the counts scanned by one workgroup, the records written
+hipError_t launch_pileup_sites(const PileupSitesArgs &a, hipStream_t stream);
 
 void set_pair_min_depth(int d);            // tuning: depth from which two-base steps are tried
 constexpr uint32_t kRankRows = 96; // rows per 16-byte rank block (== kRankRowsPerBlock)

@@ -4,6 +4,9 @@ add_positions() gives an index its position table; segments() turns a batch into
 coordinates and, when asked, the depth of every source base; segments_dev() / depth_finish_dev() are the same over device buffers.
 place() chains the segments of every sequence to one record - source, strand, extent, score, runner-up; place_dev() is the same over
 device buffers behind segments_dev(), place_from_segments_host() its restatement on the CPU.
+pileup() counts what the reads say at every source base and gives the candidate sites; pileup_dev() / pileup_sites_dev() are the same
+over device buffers behind segments_dev() and depth_finish_dev(), pileup_from_segments_host() / pileup_sites_host() their restatements
+on the CPU, pileup_snps() the step from sites to substitutions against the source text.
 """
 import ctypes as C
 
@@ -23,6 +26,10 @@ PLACE_NONE, PLACE_REV, PLACE_SPILLS, PLACE_WINDOW, PLACE_LANE_MAX = 0xFFFFFFFF, 
 PLACE_DTYPE = np.dtype([("source", "<u4"), ("strand", "<u2"), ("flags", "<u2")] + [(n, "<u4") for n in (
     "q_start", "q_end", "pos_start", "pos_end", "score", "n_segs", "indel", "n_multi", "second", "reserved")])
 assert PLACE_DTYPE.itemsize == 48
+# kbo_pile_site
+SITE_DTYPE = np.dtype([("pos", "<u4"), ("source", "<u4"), ("depth", "<u4"), ("count", "<u4", (4,)), ("reserved", "<u4")])
+assert SITE_DTYPE.itemsize == 32
+SNP_DTYPE = np.dtype([("source", "<u4"), ("pos", "<u4"), ("ref", "u1"), ("alt", "u1"), ("count", "<u4"), ("depth", "<u4")])
 
 
 def _batch(query_seqs):
@@ -206,3 +213,100 @@ def place_local(rec, src_off):
     start = np.where(none, 0, np.asarray(rec["pos_start"], dtype=np.int64) - base)
     end = np.where(none, 0, np.asarray(rec["pos_end"], dtype=np.int64) - base)
     return src, start, end, np.where(none, 0, np.asarray(rec["flags"]) & PLACE_REV).astype(np.uint8)
+
+
+def pileup(query_seqs, sbwt, bridge=None, strands=STRAND_FWD, skip_multi=True, min_count=3, frac_num=1, frac_den=2, depth=False, pile=False):
+    """kbo_pileup_batch -> the candidate sites (SITE_DTYPE, ascending pos) of the batch piled up on the sources over the strands asked
+    for, or (sites, depth uint32[source bases]) / (sites, pile uint32[source bases, 4]) / (sites, depth, pile).  A site has a column
+    with at least min_count reads and count * frac_den >= frac_num * depth; min_count 3 and one half are choices that suit a haploid
+    sample at tens of reads a base, not derived figures.  query_seqs: a list of sequences or (concat, offsets); bridge: None = k"""
+    concat, offsets = _batch(query_seqs)
+    b = sbwt.k() if bridge is None else int(bridge)
+    bases = int(lib().kbo_index_source_bases(sbwt._h))
+    d = np.zeros(bases, dtype=np.uint32) if depth else None
+    pl = np.zeros((bases, 4), dtype=np.uint32) if pile else None
+    p, n = C.c_void_p(), C.c_uint64(0)
+    check(lib().kbo_pileup_batch(sbwt._h, concat.ctypes.data if len(concat) else None, offsets.ctypes.data, len(offsets) - 1, min(b, 0xFFFFFFFF), int(strands),
+                                 int(bool(skip_multi)), int(min_count), int(frac_num), int(frac_den), C.byref(p), C.byref(n),
+                                 d.ctypes.data if depth else None, pl.ctypes.data if pile else None))
+    try:
+        sites = np.frombuffer(C.string_at(p.value, n.value * SITE_DTYPE.itemsize), dtype=SITE_DTYPE).copy()
+    finally:
+        lib().kbo_free(p)
+    extra = tuple(x for x in (d, pl) if x is not None)
+    return (sites,) + extra if extra else sites
+
+
+def pileup_dev(sbwt, concat, ms, offsets, n_seqs, total_bases, segs, n_segs, capacity, pile, skip_multi=True, stream=None):
+    """kbo_pileup_dev over torch tensors (or raw device pointers): the batch as it was walked, the MS bytes of that walk, and segs, n_segs
+    and capacity as segments_dev() left them; `pile` (uint32[source bases, 4]) is added to; everything on `stream`, no scratch"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_pileup_dev(sbwt._h, ptr(concat), ptr(ms), ptr(offsets), n_seqs, total_bases, ptr(segs), ptr(n_segs), int(capacity), int(bool(skip_multi)),
+                               ptr(pile), s))
+
+
+def pileup_sites_work_bytes(sbwt):
+    return int(lib().kbo_pileup_sites_work_bytes(sbwt._h))
+
+
+def pileup_sites_dev(sbwt, pile, depth, sites, capacity, n_sites, work, work_bytes=None, min_count=3, frac_num=1, frac_den=2, stream=None):
+    """kbo_pileup_sites_dev: the sites of `pile` against `depth` as depth_finish_dev() wrote it; record x is written iff x < capacity,
+    n_sites (8 bytes) receives the full count"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    wb = pileup_sites_work_bytes(sbwt) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_pileup_sites_dev(sbwt._h, ptr(pile), ptr(depth), int(min_count), int(frac_num), int(frac_den), ptr(sites), int(capacity), ptr(n_sites),
+                                     ptr(work), wb, s))
+
+
+def pileup_from_segments_host(segs, concat, ms, offsets, k, source_bases, skip_multi=True, pile=None):
+    """kbo_pileup_from_segments_host -> (pile uint32[source_bases, 4], bridged bases of the records taken); pile: an earlier call's
+    (another batch or strand) to add to, in place"""
+    segs = np.ascontiguousarray(segs, dtype=SEGMENT_DTYPE)
+    concat = np.ascontiguousarray(concat, dtype=np.uint8)
+    ms = np.ascontiguousarray(ms, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if pile is None:
+        pile = np.zeros((source_bases, 4), dtype=np.uint32)
+    assert pile.dtype == np.uint32 and pile.flags.c_contiguous and pile.shape == (source_bases, 4) and len(ms) >= len(concat)
+    n = C.c_uint64(0)
+    check(lib().kbo_pileup_from_segments_host(segs.ctypes.data if len(segs) else None, len(segs), concat.ctypes.data if len(concat) else None,
+                                              ms.ctypes.data if len(concat) else None, offsets.ctypes.data, len(offsets) - 1, len(concat), k,
+                                              int(bool(skip_multi)), pile.ctypes.data if source_bases else None, source_bases, C.byref(n)))
+    return pile, int(n.value)
+
+
+def pileup_sites_host(pile, depth, src_off, capacity=None, min_count=3, frac_num=1, frac_den=2):
+    """kbo_pileup_sites_host -> (records written (SITE_DTYPE), count); capacity: None = every site"""
+    pile = np.ascontiguousarray(pile, dtype=np.uint32)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    src_off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    bases = len(depth)
+    assert pile.size == 4 * bases
+    cap = bases if capacity is None else int(capacity)
+    sites = np.zeros(cap, dtype=SITE_DTYPE)
+    n = C.c_uint64(0)
+    check(lib().kbo_pileup_sites_host(pile.ctypes.data if bases else None, depth.ctypes.data if bases else None, bases, src_off.ctypes.data,
+                                      len(src_off) - 1, int(min_count), int(frac_num), int(frac_den), sites.ctypes.data if cap else None, cap, C.byref(n)))
+    return sites[:min(cap, n.value)].copy(), int(n.value)
+
+
+def pileup_snps(sites, sources, min_count=3, frac_num=1, frac_den=2):
+    """the substitutions among `sites` against the source text (SNP_DTYPE): the column that equals the source base is dropped - the
+    device does not hold the text, and a base between two nearby substitutions is bridged and counted too - and a site gives a row when
+    exactly one of its remaining columns meets the thresholds the sites were made with: source, position within the source, ref and
+    alt as bytes, the column's count, depth.  sources: the sequences the index was built from, in order"""
+    srcs = [_u8(s) for s in sources]
+    off = np.concatenate([[0], np.cumsum([len(s) for s in srcs])]).astype(np.int64)
+    out = []
+    for st in sites:
+        src, at = int(st["source"]), int(st["pos"]) - int(off[int(st["source"])])
+        ref = int(srcs[src][at])
+        depth = int(st["depth"])
+        alts = [(b, int(c)) for b, c in zip(b"ACGT", st["count"]) if b != ref and c >= min_count and int(c) * frac_den >= frac_num * depth]
+        if len(alts) == 1:
+            out.append((src, at, ref, alts[0][0], alts[0][1], depth))
+    return np.array(out, dtype=SNP_DTYPE)
