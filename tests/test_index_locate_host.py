@@ -144,8 +144,8 @@ def queries(srcs, k):
 # ---- brute force: the chain builder
 def brute_segments(seqs, occ, k, bridge, strand):
     """records of the batch as tuples (seq, strand, q_first, q_last, pos_first, pos_last, flags), in (seq, q_first) order"""
-    out = []
-    for s, q in enumerate(seqs):
+    lists = []
+    for q in seqs:
         ok = np.isin(q, ACGT)
         anchors = []
         for i in range(0, len(q) - k + 1):
@@ -153,6 +153,15 @@ def brute_segments(seqs, occ, k, bridge, strand):
                 o = occ.get(q[i:i + k].tobytes())
                 if o:
                     anchors.append((i, entry_of(o)))
+        lists.append(anchors)
+    return brute_chains(lists, bridge, strand)
+
+
+def brute_chains(anchor_lists, bridge, strand):
+    """the chain-building half of brute_segments: anchor_lists[s] holds the anchors of sequence s as (q, entry) by ascending q - from
+    the occurrence dict as above, or synthetic"""
+    out = []
+    for s, anchors in enumerate(anchor_lists):
         chain = []
         for a in anchors:
             if chain:

@@ -53,9 +53,10 @@ def brute_pile(segs, seqs, ms, off, k, n_bases, skip_multi, pile=None):
     return pile, bridged
 
 
-def brute_sites(pile, depth, soff, min_count, num, den):
+def brute_sites(pile, depth, soff, min_count, num, den, rows=None):
+    """rows: the bases looked at, ascending (None: every one)"""
     out = []
-    for j in range(len(depth)):
+    for j in (range(len(depth)) if rows is None else rows):
         d = int(depth[j])
         if any(int(c) >= min_count and int(c) * den >= num * d for c in pile[j]):
             src = max(s for s in range(len(soff) - 1) if int(soff[s]) <= j)

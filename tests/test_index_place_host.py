@@ -101,9 +101,11 @@ def py_merge(a, b):
 def py_place(segs, n_seqs, k, src_off, max_gap=MAX_GAP, max_indel=MAX_INDEL, merge_into=None):
     """records of a batch in (seq, q_first) order -> PLACE_DTYPE[n_seqs]"""
     out = np.zeros(n_seqs, dtype=locate.PLACE_DTYPE)
-    rows = [tuple(int(v) for v in r) for r in segs.tolist()]
+    by_seq = {}
+    for r in segs.tolist():  # (one pass: the records of a sequence in list order, wherever they lie)
+        by_seq.setdefault(int(r[0]), []).append(tuple(int(v) for v in r))
     for s in range(n_seqs):
-        rec = py_record([r for r in rows if r[0] == s], k, src_off, max_gap, max_indel)
+        rec = py_record(by_seq.get(s, []), k, src_off, max_gap, max_indel)
         if merge_into is not None:
             rec = py_merge({n: int(merge_into[s][n]) for n in FIELDS}, rec)
         out[s] = tuple(rec[n] for n in FIELDS)
