@@ -313,6 +313,30 @@ pub mod ffi {
         pub fn kbo_pileup_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
                                 skip_multi: c_int, min_count: u32, frac_num: u32, frac_den: u32, sites: *mut *mut super::PileSite,
                                 n_sites: *mut u64, depth_out: *mut u32, pile_out: *mut u32) -> c_int;
+        // indels: one event per clean junction of two consecutive records (a left-aligned deletion, or an insertion with its bases),
+        // appended to one list behind *d_n_events (zeroed once, shared by batches and strands like d_delta); indel_sites_dev sorts
+        // and counts the list into sites behind kbo_depth_finish_dev; the *_host calls restate both on the CPU, indels_batch is the
+        // host form (sites released by kbo_free)
+        pub fn kbo_indels_work_bytes(n_segs_capacity: usize) -> usize;
+        pub fn kbo_indels_dev(idx: *mut KboIndex, d_concat: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64,
+                              d_segs: *const super::SeqSegment, d_n_segs: *const u64, capacity: usize, skip_multi: c_int, max_indel: u32,
+                              d_events: *mut super::IndelEvent, event_capacity: usize, d_n_events: *mut u64, d_work: *mut c_void,
+                              work_bytes: usize, stream: *mut c_void) -> c_int;
+        pub fn kbo_indel_sites_work_bytes(event_capacity: usize) -> usize;
+        pub fn kbo_indel_sites_dev(idx: *mut KboIndex, d_events: *const super::IndelEvent, d_n_events: *const u64, event_capacity: usize,
+                                   d_depth: *const u32, min_count: u32, frac_num: u32, frac_den: u32, d_sites: *mut super::IndelSite,
+                                   site_capacity: usize, d_n_sites: *mut u64, d_work: *mut c_void, work_bytes: usize,
+                                   stream: *mut c_void) -> c_int;
+        pub fn kbo_indels_from_segments_host(segs: *const super::SeqSegment, n_segs: u64, concat: *const u8, offsets: *const u64, n_seqs: usize,
+                                             total_bases: u64, k: u32, skip_multi: c_int, max_indel: u32, src_off: *const u64, n_src: usize,
+                                             events: *mut super::IndelEvent, event_capacity: usize, n_events: *mut u64,
+                                             n_complex: *mut u64) -> c_int;
+        pub fn kbo_indel_sites_host(events: *const super::IndelEvent, n_events: u64, event_capacity: usize, depth: *const u32,
+                                    src_off: *const u64, n_src: usize, min_count: u32, frac_num: u32, frac_den: u32,
+                                    sites: *mut super::IndelSite, site_capacity: usize, n_sites: *mut u64) -> c_int;
+        pub fn kbo_indels_batch(idx: *mut KboIndex, concat: *const u8, offsets: *const u64, n_seqs: usize, bridge: u32, strands: c_int,
+                                skip_multi: c_int, max_indel: u32, min_count: u32, frac_num: u32, frac_den: u32,
+                                sites: *mut *mut super::IndelSite, n_sites: *mut u64, depth_out: *mut u32) -> c_int;
         // format::run_lengths_gapped over device-resident characters at any sequence length: a chunk per lane (records of seven u32)
         pub fn kbo_run_lengths_seq_work_bytes(n_seqs: usize, total_bases: u64) -> usize;
         pub fn kbo_run_lengths_seq_dev(d_chars: *const u8, d_offsets: *const u64, n_seqs: usize, total_bases: u64, max_gap_len: usize,
@@ -517,6 +541,39 @@ pub struct PileSite {
     pub source: u32,
     pub depth: u32,
     pub count: [u32; 4],
+    pub reserved: u32,
+}
+
+/// `KBO_INDEL_INS` / `KBO_INDEL_LONG` / `KBO_INDEL_LEN_MASK`: the fields of `kind_len`; `KBO_INDEL_MINUS`: bit 0 of `IndelEvent::flags`.
+pub const INDEL_INS: u32 = 1 << 31;
+pub const INDEL_LONG: u32 = 1 << 30;
+pub const INDEL_LEN_MASK: u32 = (1 << 30) - 1;
+pub const INDEL_MINUS: u32 = 1;
+
+/// `kbo_indel_event` (16 bytes): one clean junction of two consecutive segments.  `pos` in source coordinates, left-aligned: the first
+/// deleted base, or the base in front of which the inserted bases go; `code`: the inserted bases of an insertion of at most 16, two
+/// bits each, the lowest in source order lowest.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct IndelEvent {
+    pub pos: u32,
+    pub kind_len: u32,
+    pub code: u32,
+    pub flags: u32,
+}
+
+/// `kbo_indel_site` (32 bytes): a group of equal events that holds at least `min_count` of them and at least `frac_num / frac_den` of
+/// `depth`, the depth of the base in front of the event.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct IndelSite {
+    pub pos: u32,
+    pub source: u32,
+    pub kind_len: u32,
+    pub code: u32,
+    pub count: u32,
+    pub n_minus: u32,
+    pub depth: u32,
     pub reserved: u32,
 }
 

@@ -1428,6 +1428,119 @@ int kbo_pileup_sites_host(const uint32_t *pile, const uint32_t *depth, uint64_t 
 int kbo_pileup_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands, int skip_multi,
                      uint32_t min_count, uint32_t frac_num, uint32_t frac_den, kbo_pile_site **sites, uint64_t *n_sites, uint32_t *depth_out,
                      uint32_t *pile_out);
+/* ------------------------------------------------------------------ Indels: junction events in source coordinates, counted sites
+ * The pileup sees substitutions; an insertion or deletion inside a read changes the diagonal, so it is TWO consecutive records of
+ * kbo_segments_dev on one strand with nothing bridged between them (the arithmetic: kbo_amd/csrc/index_indel.hpp, the
+ * kernels: kbo_amd/csrc/indel_kernels.hip).  This section turns every clean junction into one EVENT, collects the events of any number
+ * of batches and strands in one list, and counts the list into SITES behind the depth finish.
+ *
+ * DEFINITIONS.  Take the records of ONE kbo_segments_dev call in list order and the batch as it was walked (d_concat, d_offsets; for
+ * the '-' strand the reverse-complemented batch, as everywhere).
+ * INTERVALS of a record s, rev = flag bit 0: the query interval Q(s) = [q_first, q_last + k); the source interval S(s) =
+ * [pos_first, pos_last + k) FWD, [pos_last, pos_first + k) REV.
+ * A PAIR is records x - 1 = A and x = B.  It counts when both hold something by the pileup's rules (RECORDS THAT HOLD ANYTHING above,
+ * skip_multi included), both have the same seq and the same rev, and A.q_last < B.q_first.  FWD: lower = A, upper = B; REV: lower = B,
+ * upper = A.  In signed 64 bits: gq = B.q_first - (A.q_last + k); gs = S(upper).lo - S(lower).hi; shift = gs - gq, which is
+ * kbo_place_dev's shift.
+ * EVENTS.  shift == 0, or |shift| > max_indel: nothing (a max_indel above 2^30 - 1 counts as 2^30 - 1: a len has 30 bits).
+ * gq > 0 and gs > 0 together: a COMPLEX junction, an indel with a mismatch next to it - counted by the host form in *n_complex, never
+ * written.  Otherwise shift > 0 (then gq <= 0: no unmatched read base lies between the segments) is a DELETION with len = shift and
+ * pos = S(upper).lo - len, and shift < 0 (then gs <= 0) an INSERTION with len = -shift and pos = S(upper).lo, the source base in
+ * front of which the bases go.  pos is the LEFT-ALIGNED placement: the upper segment extends down exactly as far as the read matches
+ * its diagonal, so the event depends on `upper` and `shift` alone, and two reads that carry the same indel inside a homopolymer get
+ * the same key.
+ * THE INSERTED BASES in source orientation are, FWD, the bytes [B.q_first - len, B.q_first) of the sequence and, REV, the reverse
+ * complement of the bytes [A.q_last + k, A.q_last + k + len).  For len <= KBO_INDEL_CODE_LEN = 16, `code` packs base i in ascending
+ * source order at bits [2i, 2i + 2), coded as kbo_pack_reads codes them (A, C, G, T = 0 .. 3); for len > 16, code = 0 and the LONG
+ * bit is set: such insertions are told apart by position and length only.  A deletion's code is 0.
+ * NO EVENT is written when an inserted byte is not A, C, G or T; when those bytes would leave the sequence; when pos < 0; when
+ * pos + (deletion ? len : 0) > source_bases; or when S(upper).lo and S(lower).hi - 1 lie in different sources (the last source whose
+ * offset is <= the value, by bisection of the device copy of src_off).
+ * kbo_indel_event, 16 bytes: pos; kind_len = len | LONG << 30 | INS << 31; code; flags, bit 0 MINUS - the read lies on the source's
+ * '-' strand: rev XOR (the record's strand field == KBO_STRAND_REV) - the other bits 0.
+ * THE LIST.  The events of a call are APPENDED behind the *d_n_events already in the list, in record order: event n of the list is
+ * written iff n < event_capacity, and *d_n_events (8-byte aligned, zeroed once by the caller, shared by batches and strands like
+ * d_delta) becomes the full count.  The order is deterministic, so the list is byte-comparable with the host form's.
+ * SITES.  Of the first min(*d_n_events, event_capacity) events, those that hold an event - flags <= 1, len >= 1, pos <= source_bases,
+ * a deletion with code == 0, no LONG bit and pos + len <= source_bases, an insertion with LONG set iff len > 16, code == 0 when LONG
+ * and code < 4^len otherwise; every other word pattern is skipped - are grouped by (pos, kind_len, code).  A group is a SITE iff
+ * count >= min_count and count * frac_den >= frac_num * depth, the products in 64 bits; min_count == 0 or frac_den == 0 is
+ * KBO_E_BAD_ARG.  kbo_indel_site, 32 bytes: pos, source (the last source whose offset is <= pos), kind_len, code, count (the events
+ * of the group), n_minus (those with MINUS), depth = DEPTH[pos - 1] for pos > 0, else DEPTH[0] - the base in front of the event,
+ * which reads with and without the indel both cover - and reserved = 0.  Sites come in ascending (pos, kind_len, code) order as
+ * unsigned words; site x is written iff x < site_capacity and *d_n_sites is the full count.  The sites do not depend on the order of
+ * the events in the list.
+ *
+ * kbo_indels_dev uses min(*d_n_segs, capacity) records, read on the device, and is a device-resident call like its neighbours: flag,
+ * scan, emit - the plain three-pass scan, THREE launches on `stream` sized by `capacity` alone (none at capacity == 0), a lane per
+ * record x >= 1 that evaluates its pair and loads an insertion's bytes; nothing is allocated, synchronised or read back.  No byte of
+ * d_work (16-byte aligned) beyond kbo_indels_work_bytes(capacity) - exact: 4 bytes per 2048 records of capacity rounded up to 16, and
+ * 16 - or of d_events beyond event_capacity records is touched.  d_segs may be NULL at capacity == 0, d_events at event_capacity == 0.
+ * Whatever the records hold, no load or store leaves the caller's buffers.  Errors, before anything is enqueued and in this order:
+ * KBO_E_BAD_ARG for null or misaligned pointers (d_segs 4-byte; d_offsets, d_n_segs and d_n_events 8-byte; d_events and d_work
+ * 16-byte) and max_indel == 0; KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_UNSUPPORTED for total_bases + 16 > 2^32, n_seqs >= 2^28,
+ * capacity or event_capacity >= 2^32 - 1 and for a sharded handle; KBO_E_BAD_ARG for a handle without positions, for one without
+ * positions on the current device, and for a short work_bytes.
+ * kbo_indel_sites_dev: the events become sort keys of two 64-bit words, the places [n, event_capacity) padded with keys of all ones
+ * so that the sort's size is a host value; a stable LSD radix sort of 8-bit digits over the key bits a pos <= source_bases, kind_len
+ * and code can set - P = ceil((64 + bits of source_bases) / 8) passes of four launches; the group heads flagged and scanned together
+ * with the MINUS bits in one 64-bit word, count and n_minus taken as differences at the next head; the threshold, a second scan, the
+ * records.  7 + 4 P launches on `stream` (4 at event_capacity == 0), sized by event_capacity alone.  No byte of d_work beyond
+ * kbo_indel_sites_work_bytes(event_capacity) - exact, with n = event_capacity and every part rounded up to 16: 32 n for the keys and
+ * the sort's other buffer, 1024 bytes per 4096 keys of n for the passes' histogram and 4 bytes per 1024 words of that, + 8, for its
+ * sums, 8 (n + 1) for the groups, 8 bytes per 2048 of n + 1 and 4 bytes per 2048 of n for the two scans' sums, and 16 - or of d_sites
+ * beyond site_capacity records is touched.  d_events may be NULL at event_capacity == 0, d_sites at site_capacity == 0.  Errors, in
+ * this order: KBO_E_BAD_ARG for null or misaligned pointers (d_depth 4-byte; d_n_events and d_n_sites 8-byte; d_events, d_sites and
+ * d_work 16-byte) and the two thresholds; KBO_E_UNSUPPORTED for event_capacity >= 2^32 - 1 and a sharded handle; KBO_E_BAD_ARG for a
+ * handle without positions, for one without positions on the current device, and for a short work_bytes.  Both work-size functions
+ * give 0 beyond their limit.
+ * kbo_indels_from_segments_host and kbo_indel_sites_host are the two calls restated on the CPU (no HIP call; host arrays; src_off:
+ * n_src + 1 values as kbo_index_source_offsets gives them, the last one being source_bases; depth: that many words): byte-identical
+ * events, sites and counts, for any list.  *n_events is read and grows like *d_n_events; *n_complex (or NULL) grows by the COMPLEX
+ * junctions.  KBO_E_BAD_ARG for null arguments (segs may be NULL when n_segs == 0, events at event_capacity == 0, sites at
+ * site_capacity == 0), k == 0, n_src == 0, max_indel == 0, the two thresholds, and src_off that does not start at 0 or descends;
+ * KBO_E_EMPTY_QUERY for n_seqs == 0; KBO_E_UNSUPPORTED beyond the limits above and for sources of 2^30 bases or more.
+ * kbo_indels_batch is the host form, built from the stages of kbo_pileup_batch: upload, the '-' strand made on the device, the
+ * interval walk, kbo_segments_dev (once to count, once to write, with one delta for all strands), the events of every strand into one
+ * list, the depth finish, the sites (once to count, once to write), one download.  *sites is malloc'ed (kbo_free); depth_out
+ * (source_bases words) may be NULL and is written, not added to.  Errors as kbo_pileup_batch, max_indel == 0 beside the thresholds. */
+#define KBO_INDEL_INS (1u << 31)
+#define KBO_INDEL_LONG (1u << 30)
+#define KBO_INDEL_LEN_MASK ((1u << 30) - 1u)
+#define KBO_INDEL_MINUS 1u
+#define KBO_INDEL_CODE_LEN 16u
+typedef struct {
+    uint32_t pos;      /* source coordinates: the first deleted base; the base in front of which the inserted bases go */
+    uint32_t kind_len; /* len | KBO_INDEL_LONG | KBO_INDEL_INS */
+    uint32_t code;     /* an insertion's bases, 2 bits each, base 0 (the lowest in source order) lowest; 0 for LONG and for deletions */
+    uint32_t flags;    /* bit 0: KBO_INDEL_MINUS */
+} kbo_indel_event;     /* 16 bytes */
+typedef struct {
+    uint32_t pos;      /* as the events of the group */
+    uint32_t source;   /* the last source whose offset is <= pos */
+    uint32_t kind_len, code;
+    uint32_t count;    /* events in the group */
+    uint32_t n_minus;  /* ... with KBO_INDEL_MINUS */
+    uint32_t depth;    /* DEPTH[pos - 1]; DEPTH[0] at pos 0 */
+    uint32_t reserved; /* 0 */
+} kbo_indel_site;      /* 32 bytes */
+size_t kbo_indels_work_bytes(size_t n_segs_capacity);
+int kbo_indels_dev(kbo_index_t *idx, const uint8_t *d_concat, const uint64_t *d_offsets, size_t n_seqs, uint64_t total_bases,
+                   const kbo_seq_segment *d_segs, const uint64_t *d_n_segs, size_t capacity, int skip_multi, uint32_t max_indel,
+                   kbo_indel_event *d_events, size_t event_capacity, uint64_t *d_n_events, void *d_work, size_t work_bytes, void *stream);
+size_t kbo_indel_sites_work_bytes(size_t event_capacity);
+int kbo_indel_sites_dev(kbo_index_t *idx, const kbo_indel_event *d_events, const uint64_t *d_n_events, size_t event_capacity, const uint32_t *d_depth,
+                        uint32_t min_count, uint32_t frac_num, uint32_t frac_den, kbo_indel_site *d_sites, size_t site_capacity, uint64_t *d_n_sites,
+                        void *d_work, size_t work_bytes, void *stream);
+int kbo_indels_from_segments_host(const kbo_seq_segment *segs, uint64_t n_segs, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs,
+                                  uint64_t total_bases, uint32_t k, int skip_multi, uint32_t max_indel, const uint64_t *src_off, size_t n_src,
+                                  kbo_indel_event *events, size_t event_capacity, uint64_t *n_events, uint64_t *n_complex);
+int kbo_indel_sites_host(const kbo_indel_event *events, uint64_t n_events, size_t event_capacity, const uint32_t *depth, const uint64_t *src_off,
+                         size_t n_src, uint32_t min_count, uint32_t frac_num, uint32_t frac_den, kbo_indel_site *sites, size_t site_capacity,
+                         uint64_t *n_sites);
+int kbo_indels_batch(kbo_index_t *idx, const uint8_t *concat, const uint64_t *offsets, size_t n_seqs, uint32_t bridge, int strands, int skip_multi,
+                     uint32_t max_indel, uint32_t min_count, uint32_t frac_num, uint32_t frac_den, kbo_indel_site **sites, uint64_t *n_sites,
+                     uint32_t *depth_out);
 
 /* ---- alignment summaries (kbo_aln_summary, above) of device-resident batches; asynchronous, the library never synchronises.
  * kbo_summary_batch_dev: kbo::matches over the batch as kbo_map_batch_dev_tail runs it (format = 0: the same routes, streams and

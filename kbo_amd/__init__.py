@@ -33,6 +33,8 @@ from .locate import add_positions, depth_finish_dev, segment_source, segments, s
 from .locate import place, place_dev, place_from_segments_host, place_local, place_work_bytes  # noqa: F401,E402
 from .locate import pileup, pileup_dev, pileup_from_segments_host, pileup_sites_dev, pileup_sites_host  # noqa: F401,E402
 from .locate import pileup_sites_work_bytes, pileup_snps  # noqa: F401,E402
+from .locate import INDEL_EVENT_DTYPE, INDEL_SITE_DTYPE, indel_sites_dev, indel_sites_host, indel_sites_work_bytes  # noqa: F401,E402
+from .locate import indel_variants, indels, indels_dev, indels_from_segments_host, indels_work_bytes  # noqa: F401,E402
 
 
 @dataclass

@@ -162,6 +162,8 @@ SYMBOLS = [
     "kbo_place_work_bytes", "kbo_place_dev", "kbo_place_from_segments_host", "kbo_place_batch",
     "kbo_pileup_dev", "kbo_pileup_sites_work_bytes", "kbo_pileup_sites_dev", "kbo_pileup_from_segments_host", "kbo_pileup_sites_host",
     "kbo_pileup_batch",
+    "kbo_indels_work_bytes", "kbo_indels_dev", "kbo_indel_sites_work_bytes", "kbo_indel_sites_dev", "kbo_indels_from_segments_host",
+    "kbo_indel_sites_host", "kbo_indels_batch",
 ]
 # ... and include/kbo_hip_tuning.h (knobs, experiment switches, test hooks: not part of the drop-in boundary)
 TUNING_SYMBOLS = [
@@ -464,6 +466,13 @@ def lib():
     L.kbo_pileup_from_segments_host.argtypes = [vp, u64, vp, vp, vp, sz, u64, u32, C.c_int, vp, u64, C.POINTER(u64)]
     L.kbo_pileup_sites_host.argtypes = [vp, vp, u64, vp, sz, u32, u32, u32, vp, sz, C.POINTER(u64)]
     L.kbo_pileup_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, C.c_int, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), vp, vp]
+    L.kbo_indels_work_bytes.argtypes = [sz]; L.kbo_indels_work_bytes.restype = sz
+    L.kbo_indels_dev.argtypes = [vp, vp, vp, sz, u64, vp, vp, sz, C.c_int, u32, vp, sz, vp, vp, sz, vp]
+    L.kbo_indel_sites_work_bytes.argtypes = [sz]; L.kbo_indel_sites_work_bytes.restype = sz
+    L.kbo_indel_sites_dev.argtypes = [vp, vp, vp, sz, vp, u32, u32, u32, vp, sz, vp, vp, sz, vp]
+    L.kbo_indels_from_segments_host.argtypes = [vp, u64, vp, vp, sz, u64, u32, C.c_int, u32, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64)]
+    L.kbo_indel_sites_host.argtypes = [vp, u64, sz, vp, vp, sz, u32, u32, u32, vp, sz, C.POINTER(u64)]
+    L.kbo_indels_batch.argtypes = [vp, vp, vp, sz, u32, C.c_int, C.c_int, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), vp]
     L.kbo_segments_geometry.argtypes = [C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.kbo_set_positions_slab_bases.argtypes = [u64]
     _lib = L

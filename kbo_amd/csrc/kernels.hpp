@@ -883,6 +883,40 @@ struct PileupSitesArgs {
 };
 // three launches: the sites of every chunk counted, the counts scanned by one workgroup, the records written
 hipError_t launch_pileup_sites(const PileupSitesArgs &a, hipStream_t stream);
+// ---- indel_kernels.hip (the arithmetic and the d_work figures: index_indel.hpp)
+struct IndelEventArgs {
+    const uint32_t *segs;    // records of 7 words as launch_segments left them: min(*n_segs, capacity) are looked at
+    const uint64_t *n_segs;
+    uint64_t capacity;
+    const uint8_t *concat;   // the batch as it was walked: `total` bytes
+    const uint64_t *off;     // n_seqs + 1 values
+    const uint64_t *src_off; // n_src + 1 values
+    uint32_t n_seqs, n_src, k, max_indel;
+    uint64_t total, source_bases;
+    bool skip_multi;
+    void *events;            // event_capacity records of 16 bytes, 16-byte aligned: appended to behind *n_events
+    uint64_t event_capacity;
+    uint64_t *n_events;      // grows by the events of the call
+    void *work;              // idxindel::event_work(capacity).bytes
+};
+// three launches, sized by capacity alone (none when capacity is 0): the events of every chunk counted, the counts scanned by one
+// workgroup, the records written
+hipError_t launch_indel_events(const IndelEventArgs &a, hipStream_t stream);
+struct IndelSitesArgs {
+    const void *events;      // min(*n_events, event_capacity) records are looked at
+    const uint64_t *n_events;
+    uint64_t event_capacity;
+    const uint32_t *depth;   // source_bases words
+    const uint64_t *src_off; // n_src + 1 values
+    uint32_t n_src, min_count, frac_num, frac_den;
+    uint64_t source_bases, capacity;
+    void *sites;             // capacity records of 32 bytes, 16-byte aligned
+    uint64_t *n_sites;
+    void *work;              // idxindel::site_work(event_capacity).bytes
+};
+// 7 + 4 * idxindel::sort_passes(source_bases) launches, sized by event_capacity alone (4 when it is 0): the keys, four per radix pass,
+// three for the heads, three for the sites
+hipError_t launch_indel_sites(const IndelSitesArgs &a, hipStream_t stream);
 
 void set_pair_min_depth(int d);            // tuning: depth from which two-base steps are tried
 constexpr uint32_t kRankRows = 96; // rows per 16-byte rank block (== kRankRowsPerBlock)

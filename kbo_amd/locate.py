@@ -7,6 +7,10 @@ device buffers behind segments_dev(), place_from_segments_host() its restatement
 pileup() counts what the reads say at every source base and gives the candidate sites; pileup_dev() / pileup_sites_dev() are the same
 over device buffers behind segments_dev() and depth_finish_dev(), pileup_from_segments_host() / pileup_sites_host() their restatements
 on the CPU, pileup_snps() the step from sites to substitutions against the source text.
+indels() gives the insertion and deletion sites - one event per clean junction of two consecutive segments, the events of all batches
+and strands sorted and counted; indels_dev() / indel_sites_dev() are the same over device buffers behind segments_dev() and
+depth_finish_dev(), indels_from_segments_host() / indel_sites_host() their restatements on the CPU, indel_variants() the step from
+sites to deleted and inserted bytes against the source text.
 """
 import ctypes as C
 
@@ -310,3 +314,122 @@ def pileup_snps(sites, sources, min_count=3, frac_num=1, frac_den=2):
         if len(alts) == 1:
             out.append((src, at, ref, alts[0][0], alts[0][1], depth))
     return np.array(out, dtype=SNP_DTYPE)
+
+
+# kbo_indel_event, kbo_indel_site
+INDEL_INS, INDEL_LONG, INDEL_LEN_MASK, INDEL_MINUS, INDEL_CODE_LEN = 1 << 31, 1 << 30, (1 << 30) - 1, 1, 16
+INDEL_EVENT_DTYPE = np.dtype([(n, "<u4") for n in ("pos", "kind_len", "code", "flags")])
+INDEL_SITE_DTYPE = np.dtype([(n, "<u4") for n in ("pos", "source", "kind_len", "code", "count", "n_minus", "depth", "reserved")])
+assert INDEL_EVENT_DTYPE.itemsize == 16 and INDEL_SITE_DTYPE.itemsize == 32
+
+
+def indels(query_seqs, sbwt, bridge=None, strands=STRAND_FWD, skip_multi=True, max_indel=16, min_count=3, frac_num=1, frac_den=2, depth=False):
+    """kbo_indels_batch -> the insertion and deletion sites (INDEL_SITE_DTYPE, ascending (pos, kind_len, code)) of the batch over the
+    strands asked for, or (sites, depth uint32[source bases]).  A site is a group of equal events - one per clean junction of two
+    consecutive segments of a read - with at least min_count events and count * frac_den >= frac_num * the depth of the base in front;
+    max_indel 16, min_count 3 and one half are choices that suit a haploid sample at tens of reads a base, not derived figures.
+    query_seqs: a list of sequences or (concat, offsets); bridge: None = k"""
+    concat, offsets = _batch(query_seqs)
+    b = sbwt.k() if bridge is None else int(bridge)
+    d = np.zeros(int(lib().kbo_index_source_bases(sbwt._h)), dtype=np.uint32) if depth else None
+    p, n = C.c_void_p(), C.c_uint64(0)
+    check(lib().kbo_indels_batch(sbwt._h, concat.ctypes.data if len(concat) else None, offsets.ctypes.data, len(offsets) - 1, min(b, 0xFFFFFFFF), int(strands),
+                                 int(bool(skip_multi)), int(max_indel), int(min_count), int(frac_num), int(frac_den), C.byref(p), C.byref(n),
+                                 d.ctypes.data if depth else None))
+    try:
+        sites = np.frombuffer(C.string_at(p.value, n.value * INDEL_SITE_DTYPE.itemsize), dtype=INDEL_SITE_DTYPE).copy()
+    finally:
+        lib().kbo_free(p)
+    return (sites, d) if depth else sites
+
+
+def indels_work_bytes(capacity):
+    return int(lib().kbo_indels_work_bytes(int(capacity)))
+
+
+def indels_dev(sbwt, concat, offsets, n_seqs, total_bases, segs, n_segs, capacity, events, event_capacity, n_events, work, work_bytes=None,
+               skip_multi=True, max_indel=16, stream=None):
+    """kbo_indels_dev over torch tensors (or raw device pointers): the batch as it was walked and segs, n_segs and capacity as
+    segments_dev() left them; the events are appended to `events` behind n_events (8 bytes, zeroed once by the caller, shared by batches
+    and strands), which becomes the full count; everything on `stream`"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    wb = indels_work_bytes(capacity) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_indels_dev(sbwt._h, ptr(concat), ptr(offsets), n_seqs, total_bases, ptr(segs), ptr(n_segs), int(capacity), int(bool(skip_multi)),
+                               int(max_indel), ptr(events), int(event_capacity), ptr(n_events), ptr(work), wb, s))
+
+
+def indel_sites_work_bytes(event_capacity):
+    return int(lib().kbo_indel_sites_work_bytes(int(event_capacity)))
+
+
+def indel_sites_dev(sbwt, events, n_events, event_capacity, depth, sites, site_capacity, n_sites, work, work_bytes=None, min_count=3, frac_num=1,
+                    frac_den=2, stream=None):
+    """kbo_indel_sites_dev: the first min(n_events, event_capacity) events sorted, grouped and counted against `depth` as
+    depth_finish_dev() wrote it; site x is written iff x < site_capacity, n_sites (8 bytes) receives the full count"""
+    def ptr(x):
+        return None if x is None else x if isinstance(x, int) else x.data_ptr()
+    wb = indel_sites_work_bytes(event_capacity) if work_bytes is None else int(work_bytes)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(lib().kbo_indel_sites_dev(sbwt._h, ptr(events), ptr(n_events), int(event_capacity), ptr(depth), int(min_count), int(frac_num), int(frac_den),
+                                    ptr(sites), int(site_capacity), ptr(n_sites), ptr(work), wb, s))
+
+
+def indels_from_segments_host(segs, concat, offsets, k, src_off, skip_multi=True, max_indel=16, events=None, n_events=0, capacity=None):
+    """kbo_indels_from_segments_host -> (the list (INDEL_EVENT_DTYPE[capacity]), its full count, the complex junctions of this call);
+    events, n_events: the list of earlier calls (other batches or strands) to append to, in place; capacity: None = one event per record
+    on top of what the list holds"""
+    segs = np.ascontiguousarray(segs, dtype=SEGMENT_DTYPE)
+    concat = np.ascontiguousarray(concat, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    src_off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    if events is None:
+        events = np.zeros(int(n_events) + len(segs) if capacity is None else int(capacity), dtype=INDEL_EVENT_DTYPE)
+    assert events.dtype == INDEL_EVENT_DTYPE and events.flags.c_contiguous
+    n, cx = C.c_uint64(int(n_events)), C.c_uint64(0)
+    check(lib().kbo_indels_from_segments_host(segs.ctypes.data if len(segs) else None, len(segs), concat.ctypes.data if len(concat) else None,
+                                              offsets.ctypes.data, len(offsets) - 1, len(concat), k, int(bool(skip_multi)), int(max_indel),
+                                              src_off.ctypes.data, len(src_off) - 1, events.ctypes.data if len(events) else None, len(events),
+                                              C.byref(n), C.byref(cx)))
+    return events, int(n.value), int(cx.value)
+
+
+def indel_sites_host(events, n_events, depth, src_off, capacity=None, min_count=3, frac_num=1, frac_den=2):
+    """kbo_indel_sites_host over the first min(n_events, len(events)) events -> (records written (INDEL_SITE_DTYPE), count);
+    capacity: None = every site"""
+    events = np.ascontiguousarray(events, dtype=INDEL_EVENT_DTYPE)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    src_off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    assert len(depth) == int(src_off[-1])
+    cap = min(int(n_events), len(events)) if capacity is None else int(capacity)
+    sites = np.zeros(cap, dtype=INDEL_SITE_DTYPE)
+    n = C.c_uint64(0)
+    check(lib().kbo_indel_sites_host(events.ctypes.data if len(events) else None, int(n_events), len(events), depth.ctypes.data if len(depth) else None,
+                                     src_off.ctypes.data, len(src_off) - 1, int(min_count), int(frac_num), int(frac_den),
+                                     sites.ctypes.data if cap else None, cap, C.byref(n)))
+    return sites[:min(cap, n.value)].copy(), int(n.value)
+
+
+def indel_code_bases(code, length):
+    """the bases a `code` packs, in source order (bytes); length <= INDEL_CODE_LEN"""
+    return bytes(b"ACGT"[(int(code) >> (2 * i)) & 3] for i in range(length))
+
+
+def indel_variants(sites, sources):
+    """the sites against the source text, the counterpart of pileup_snps: a list of (source, position within the source, ref, alt,
+    count, depth) - a deletion has the deleted source bytes as ref and alt b"", an insertion ref b"" and its bases as alt, in front of
+    the position (b"" for a LONG one: told apart by position and length only).  sources: the sequences the index was built from"""
+    srcs = [_u8(s) for s in sources]
+    off = np.concatenate([[0], np.cumsum([len(s) for s in srcs])]).astype(np.int64)
+    text = np.concatenate(srcs + [np.zeros(0, dtype=np.uint8)])
+    out = []
+    for st in sites:
+        pos, kl = int(st["pos"]), int(st["kind_len"])
+        length, src = kl & INDEL_LEN_MASK, int(st["source"])
+        if kl & INDEL_INS:
+            ref, alt = b"", b"" if kl & INDEL_LONG else indel_code_bases(st["code"], length)
+        else:
+            ref, alt = text[pos:pos + length].tobytes(), b""
+        out.append((src, pos - int(off[src]), ref, alt, int(st["count"]), int(st["depth"])))
+    return out
