@@ -106,7 +106,11 @@ int kbo_index_depth_table(kbo_index_t *idx, int device, int view, uint8_t *table
  *   DFILT     a bit per string of F bases, 4^F / 8 bytes                        info = { F, order of the depth table }
  *   ANCHOR    2^bits slots of { text position, (uint32_t)key + 1 }, 8 bytes     info = { bits, order of the depth table }
  *   SUB_CLEAN a bit per text position (kbo_amd/csrc/map_subst.hpp), 4 * ((U + 1) / 2) bytes
- *                                                      info = { U, order of the depth table, threshold, 1 with anchors else 0 } */
+ *                                                      info = { U, order of the depth table, threshold, 1 with anchors else 0 }
+ *   SUB_GROUP a bit per group of 4 text positions, set where all four of SUB_CLEAN's are (bit G of the array: positions 4 G .. 4 G + 3,
+ *             counted as SUB_CLEAN counts them), 4 * ((U + 7) / 8) bytes and the 64 zeroed bytes of slack a window's one 8-byte load may read;
+ *             there when SUB_CLEAN is, unless the copy was made under KBO_SUBST_GROUPS=0
+ *                                  info = as SUB_CLEAN */
 #define KBO_PLAN_PART_PC_TM 0
 #define KBO_PLAN_PART_PC_T 1
 #define KBO_PLAN_PART_PC_MU 2
@@ -116,7 +120,8 @@ int kbo_index_depth_table(kbo_index_t *idx, int device, int view, uint8_t *table
 #define KBO_PLAN_PART_DFILT 6
 #define KBO_PLAN_PART_ANCHOR 7
 #define KBO_PLAN_PART_SUB_CLEAN 8
-#define KBO_PLAN_PARTS 9
+#define KBO_PLAN_PART_SUB_GROUP 9
+#define KBO_PLAN_PARTS 10
 int kbo_index_plan_part(kbo_index_t *idx, int device, int part, void *out, size_t *n_bytes, uint32_t info[4]);
 /* tests: depth of the seed table of device copies made after the call (0 = by index size: 8 / 10 / 12 / 13 bases;
  * 1 .. 13 = that many, capped at k).  Large tables are what large indexes get: 12 bases = 128 MiB, 13 = 512 MiB. */
@@ -156,10 +161,11 @@ int kbo_set_plan_stats(int on);
  * (kbo_set_depth_table) out[12]: table look-ups, [13]: values written from the table, [14] = [15]: items the table could not
  * resolve (counted by the lanes / by the launch's control word; out[8] is meaningless in that form), [16]: bases read off the
  * path-cover text (anchors), [17]: items resolved without a plan;  map_reads_kernel's direct form (kbo_map_batch_dev) [18]:
- * words looked up of the copy's bit per text position for lone substitutions, [19]: mismatches those bits settled without a
- * filter word or a table byte (out[6] and out[12] count the filter words and table bytes actually looked up).  Meaningless
+ * lone substitutions asked of the copy's bit per text position (a word each, but for those of [20]), [19]: mismatches those bits settled without a
+ * filter word or a table byte (out[6] and out[12] count the filter words and table bytes actually looked up), [20]: those of [18]
+ * and [19] alike that the read's own lane settled by its window of clean groups, before anything was dealt or looked up.  Meaningless
  * (stale or zero) when that launch did not plan (plain walk, hold-off, intervals requested) or did not count. */
-#define KBO_PLAN_STATS 20
+#define KBO_PLAN_STATS 21
 int kbo_plan_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, uint32_t k, const void *d_work,
                        uint64_t out[KBO_PLAN_STATS], void *stream);
 

@@ -85,7 +85,7 @@ class RefCalls(C.Structure):
 OPT_INHERIT = -2147483648
 # kbo_hip_tuning.h KBO_PLAN_PART_*: name -> (part, numpy dtype of its entries)
 PLAN_PARTS = {"pc_tm": (0, "<u4"), "pc_t": (1, "<u4"), "pc_mu": (2, "u1"), "pc_mc": (3, "<u4"), "seed_tab": (4, "<u4"),
-              "seed_pos": (5, "<u4"), "dfilt": (6, "<u4"), "anchor": (7, "<u8"), "sub_clean": (8, "<u4")}
+              "seed_pos": (5, "<u4"), "dfilt": (6, "<u4"), "anchor": (7, "<u8"), "sub_clean": (8, "<u4"), "sub_group": (9, "<u4")}
 
 
 class IndexOpts(C.Structure):

@@ -56,6 +56,7 @@ struct DevCopy {
     DevBuf sub_clean;                // ... and a bit per text position: a lone substitution there needs no table (map_subst.hpp), for the
     uint32_t sub_thr = 0;            // proof's windows at this threshold - what a call with default options gets on this index -
     bool sub_anch = false;           // with or without anchors
+    DevBuf sub_group;                // ... and a bit per group of four positions whose bits are all set: a read's window of them in one load
     DevBuf positions;                // the position table (index_locate.cpp): a word per row, empty without one
     DevBuf src_off;                  // ... and where every source begins (kbo_index::src_off), made with it: what kbo_place_dev bisects
     // what making this copy cost (kbo_index_device_layout): seconds of host work / device builds / uploads, by part

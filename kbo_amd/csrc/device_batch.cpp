@@ -223,6 +223,7 @@ int kbo_plan_stats_dev(size_t n_seqs, uint64_t total_bases, size_t max_seq_len, 
             out[16] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatTabAnchored];
             out[18] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSubstBits];
             out[19] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSubstClean];
+            out[20] += st[sl * kbo::kPlanStatWords + kbo::kPlanStatSubstGroups];
         }
         out[15] = ctl[4];
         out[17] = ctl[5];

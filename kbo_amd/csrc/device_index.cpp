@@ -359,12 +359,19 @@ void build_plan_structures(kbo_index *idx, DevCopy *dc)
             sv.dtab = dc->dtab.as<uint8_t>();
             sv.dtab_order = dc->dtab_order;
             sv.dtab_grouped = dc->dtab_grouped ? 1u : 0u;
-            HIP_OK(kbo::launch_subst_bits(sv, units, (uint32_t)thr, anch, dc->sub_clean.as<uint32_t>(), bs));
+            // ... and the clean groups of those bits (map_subst.hpp), from the bits just made.  KBO_SUBST_GROUPS=0: none, read like KBO_SUBST_BITS
+            const char *env_grp = std::getenv("KBO_SUBST_GROUPS");
+            const uint64_t grp_bytes = (env_grp && std::atoi(env_grp) == 0) ? 0 : kbo::mapsubst::group_words(units) * 4;
+            if (grp_bytes) {
+                dc->sub_group.alloc(grp_bytes + kbo::mapsubst::kGroupSlack);
+                HIP_OK(hipMemsetAsync(dc->sub_group.as<uint8_t>() + grp_bytes, 0, kbo::mapsubst::kGroupSlack, bs));
+            }
+            HIP_OK(kbo::launch_subst_bits(sv, units, (uint32_t)thr, anch, dc->sub_clean.as<uint32_t>(), grp_bytes ? dc->sub_group.as<uint32_t>() : nullptr, bs));
             HIP_OK(hipStreamSynchronize(bs));
             dc->sub_thr = (uint32_t)thr;
             dc->sub_anch = anch;
-            dc->setup.cover_bytes += sub_bytes;
-            idx->plan_bytes += sub_bytes;
+            dc->setup.cover_bytes += sub_bytes + grp_bytes;
+            idx->plan_bytes += sub_bytes + grp_bytes;
             dc->setup.cover_s += since(t0);
         }
     }
@@ -499,7 +506,7 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
                 // table's depth without its table, a text without its positions - must not reach a launch), the copy is marked so
                 // that the build is not paid again by every later call, and it walks plainly - with the same results.  An explicit
                 // kbo_index_to_device still reports the failure.
-                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->pc_t, &dc->pc_mu, &dc->pc_mc, &dc->sub_clean, &dc->seed_pos})
+                for (DevBuf *b : {&dc->pc_text, &dc->pc_pos, &dc->pc_node, &dc->fat, &dc->seed_tab, &dc->dtab, &dc->anchor, &dc->dfilt, &dc->pc_tm, &dc->pc_t, &dc->pc_mu, &dc->pc_mc, &dc->sub_clean, &dc->sub_group, &dc->seed_pos})
                     b->release();
                 dc->seed_d = dc->dtab_order = dc->anchor_bits = dc->dfilt_bases = 0;
                 dc->dtab_grouped = false;
@@ -542,6 +549,7 @@ kbo::DevIndexView device_view(kbo_index *idx, int device, DevCopy::PlanState **p
     v.dfilt = (use_tab && dc->dfilt_bases) ? dc->dfilt.as<uint32_t>() : nullptr;
     v.dfilt_bases = v.dfilt ? dc->dfilt_bases : 0u;
     v.sub_clean = (v.pc_t && dc->sub_clean.p) ? dc->sub_clean.as<uint32_t>() : nullptr;
+    v.sub_group = (v.sub_clean && dc->sub_group.p) ? dc->sub_group.as<uint8_t>() : nullptr;
     v.sub_thr = dc->sub_thr;
     v.sub_anch = dc->sub_anch ? 1u : 0u;
     v.seed_pos = (use_tab && dc->seed_pos.p) ? dc->seed_pos.as<uint32_t>() : nullptr;

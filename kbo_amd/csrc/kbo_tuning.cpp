@@ -106,6 +106,7 @@ int kbo_index_plan_part(kbo_index_t *idx, int device, int part, void *out, size_
         case KBO_PLAN_PART_SEED_POS: buf = &dc.seed_pos, need = (size_t)4 << (2u * dc.seed_d), inf[0] = dc.seed_d, inf[1] = seed_on_device; break;
         case KBO_PLAN_PART_DFILT: buf = &dc.dfilt, need = dc.dfilt_bases ? ((size_t)1 << (2u * dc.dfilt_bases)) / 8u : 0, inf[0] = dc.dfilt_bases, inf[1] = dc.dtab_order; break;
         case KBO_PLAN_PART_ANCHOR: buf = &dc.anchor, need = dc.anchor_bits ? (size_t)8 << dc.anchor_bits : 0, inf[0] = dc.anchor_bits, inf[1] = dc.dtab_order; break;
+        case KBO_PLAN_PART_SUB_GROUP: buf = &dc.sub_group, need = kbo::mapsubst::group_words(units) * 4 + kbo::mapsubst::kGroupSlack, inf[0] = (uint32_t)units, inf[1] = dc.dtab_order, inf[2] = dc.sub_thr, inf[3] = dc.sub_anch ? 1u : 0u; break;
         default: buf = &dc.sub_clean, need = kbo::mapsubst::bitmap_words(units) * 4, inf[0] = (uint32_t)units, inf[1] = dc.dtab_order, inf[2] = dc.sub_thr, inf[3] = dc.sub_anch ? 1u : 0u; break;
         }
         if (!buf->p) need = 0; // (a part this copy does not have)

@@ -65,6 +65,10 @@ struct DevIndexView {
     // copy has none; launch_map_reads hands the kernel nullptr when the launch's threshold is another
     const uint32_t *sub_clean;
     uint32_t sub_thr, sub_anch;
+    // ... and its coarser form: a bit per group of mapsubst::kGroup positions, set where all of the group's bits are - a read's whole
+    // window of them is one 8-byte load beside the text's (any byte address; 64 zeroed bytes of slack behind the array).  There exactly
+    // when sub_clean is (unless the copy was made under KBO_SUBST_GROUPS=0), nulled with it
+    const uint8_t *sub_group;
 };
 
 // One unit of walk work: `len` bases starting at absolute offset `start` of the
@@ -189,7 +193,8 @@ struct WalkArgs {
 enum : uint32_t { kPlanStatUnits = 0, kPlanStatAccepted, kPlanStatFailed, kPlanStatLevels, kPlanStatEntryLevels,
                   kPlanStatSeedLookups, kPlanStatSeedExtensions, kPlanStatMismatches,
                   kPlanStatTabLookups, kPlanStatTabWritten, kPlanStatTabFlagged, kPlanStatTabAnchored,
-                  kPlanStatSubstBits, kPlanStatSubstClean, // (map_reads_kernel: words of sub_clean looked up, mismatches they settled)
+                  kPlanStatSubstBits, kPlanStatSubstClean, // (map_reads_kernel: eligible lone substitutions asked, those settled - by a word of sub_clean or in the owner lane)
+                  kPlanStatSubstGroups,                    // (... of which the owner lane settled by its window of sub_group, before stage 3 deals)
                   kPlanStatWords };
 constexpr uint32_t kPlanStatSlots = 8;
 // where the pieces of a launch's plan work live inside its work buffer (attach_plan)
@@ -244,7 +249,8 @@ inline uint64_t pack_text_units(uint64_t n_sets) { return (n_sets + kMapPad + 25
 inline uint64_t pack_text_mu_bytes(uint64_t n_units) { return (n_units + 255u) / 256u * 32u; } // (a bit per unit, whole workgroups of pack_text_kernel)
 // the bit per text position of map_subst.hpp from the copy's own text and depth table (ix.pc_tm, ix.pc_t, ix.dtab), for the proof's
 // windows at threshold thr: d_bits gets mapsubst::bitmap_words(n_units) words
-hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, hipStream_t stream);
+// d_groups (may be nullptr: none): the clean groups of those bits, mapsubst::group_words(n_units) words, made from the bits just written
+hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, uint32_t *d_groups, hipStream_t stream);
 hipError_t launch_seed_pos(const uint2 *d_seed_tab, const uint32_t *d_pc_pos, uint32_t *d_out, uint32_t seed_d, hipStream_t stream);
 // true when the launch described by `a` (plan work attached, chars_out set) can take map_reads_kernel: reads of at most 160
 // bases, MS values / characters only, an index copy with a depth table, the 2-bit text and the position table

@@ -190,6 +190,13 @@ __global__ __launch_bounds__(256) void subst_bits_kernel(SubstText tx, SubstTabl
     }
 }
 
+// the clean groups of those bits (map_subst.hpp): a thread per word of them
+__global__ __launch_bounds__(256) void subst_groups_kernel(SubstBits bits, uint64_t n_bit_words, uint32_t *__restrict__ out, uint64_t n_words)
+{
+    const uint64_t W = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (W < n_words) out[W] = mapsubst::group_word(bits, W, n_bit_words);
+}
+
 // the coarse summary of the marks (map_text.hpp): a thread per cell
 __global__ __launch_bounds__(64) void mark_cells_kernel(const uint8_t *__restrict__ mu, uint32_t *__restrict__ out, uint32_t shift, uint64_t n_units)
 {
@@ -536,8 +543,15 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     uint32_t mmw[kMapWords];
 #pragma unroll
     for (uint32_t g = 0; g < kMapWords; g++) mmw[g] = 0;
+    // (DIRECT) ... and, in the same round, the clean groups of the diagonal's window (map_subst.hpp): 8 bytes that depend on nothing but
+    // p0.  They speak for this diagonal alone: zeroed wherever p0 changes (2b's front swap, a whole diagonal from the second seed -
+    // the one place where nothing else would keep a stale word from being asked) and, for the reader, where the read is cut or loses
+    // its seed (eligible() and the list walk's own condition refuse those anyway).  A read seeded only in 2b never has them: its
+    // mismatches are all dealt, as before
+    uint64_t gword = 0;
     if (__ballot(seeded)) {
         const bool nm = near_mark(p0 + kMapPad);
+        if (DIRECT && a.ix.sub_group && seeded) __builtin_memcpy(&gword, a.ix.sub_group + mapsubst::group_load_byte(p0 + kMapPad), 8);
         if (seeded) cnt = compare(p0, nm, mmw);
     }
     // ---- 2b. (DIRECT) a SECOND diagonal for a read that leaves its first - an insertion or a deletion, a chimera, or a first seed
@@ -598,6 +612,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                 if (front) { // the seed's diagonal is the second one
                     pB = p0;
                     p0 = pA;
+                    gword = 0;
                     cnt = compare(p0, nm, mmw);
                     seedB = true;
                 }
@@ -668,6 +683,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                         for (uint32_t g = 0; g < kMapWords; g++) mmw[g] = mmB[g];
                         cnt = cB;
                         p0 = pB;
+                        gword = 0;
                     } else if (gcut < len) {
                         // bases [0, gcut) keep the first diagonal's marks, [gcut, len) get the second's; base gcut - 1 gets a mark as
                         // the junction unless it mismatches already (a mismatch there is the same break)
@@ -675,6 +691,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                         int32_t lastA = -1; // the first diagonal's last mismatch in front of the cut
                         cnt = 0;
                         cut = true;
+                        gword = 0;
 #pragma unroll
                         for (uint32_t g = 0; g < kMapWords; g++) {
                             const uint32_t lo_b = 16u * g; // bases of this word: [lo_b, lo_b + 16)
@@ -747,6 +764,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         junction = 0xFFu;
         jov = 0;
         cnt = 0;
+        gword = 0;
     }
     // the ramp of a read's first bases (depth i + 1 while nothing mismatches: the bases equal a path of the text)
     bool flag = plannable && seeded && cnt > a.plan_list + 1u; // more mismatches than the list holds: the plain walk
@@ -767,7 +785,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     uint32_t w_e = 0, w_owner = 0, w_at = 0, w_len = 0, w_pre[6] = {0, 0, 0, 0, 0, 0};
     // ---- 3. the stretches behind the mismatches from the depth table (rule: dtab_kernels.hip), dealt out to the lanes
     uint32_t st_look = 0, st_written = 0, st_anch = 0, st_filt = 0; // (direct form: st_written = windows the filter settled)
-    uint32_t st_bits = 0, st_clean = 0;                             // (direct form: words of sub_clean looked up, mismatches they settled)
+    uint32_t st_bits = 0, st_clean = 0, st_groups = 0;              // (direct form: lone substitutions asked, those settled, those the owner lane settled)
     {
         const uint32_t order = a.ix.dtab_order;
         // DIRECT: cov = bases between two windows of the proof (header), n_e = windows per mismatch (<= 4: launch_map_reads);
@@ -778,7 +796,27 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
         const bool have_anch = DIRECT && a.ix.anchor != nullptr && thr_gt(a.map_thr, order);
         const uint32_t thr = a.map_thr, covb = DIRECT ? mapsubst::window_step(order, thr, false) : 1u, cov = DIRECT ? mapsubst::window_step(order, thr, have_anch) : 1u;
         const uint32_t n_blockwin = (DIRECT && len > thr) ? (len - order + covb - 1u) / covb + 1u : 0u;
-        const uint32_t my_n = !plannable || flag ? 0u : DIRECT ? (no_plan ? (n_blockwin + 3u) / 4u : (len > thr ? cnt : 0u))
+        // (DIRECT) the lone substitutions whose group is clean the read's own lane settles here - the rule the dealt code applies
+        // below, with the bit of the window loaded in stage 2 -: bit i of `settled` = entry i of the list asks nothing and is not
+        // dealt (what the dealt code leaves of it: no look-up, no byte, nothing pending)
+        uint32_t settled_m = 0;
+        if (DIRECT) {
+            const uint32_t n_walk = (plannable && !flag && seeded && len > thr && gword != 0ull) ? cnt : 0u;
+            uint32_t prev_m = 0, cur_m = n_walk ? (uint32_t)sp[0] : 0u;
+            for (uint32_t i = 0; __ballot(i < n_walk) != 0; i++) {
+                if (i < n_walk) {
+                    const bool has_prev = i > 0u, has_next = i + 1u < n_walk;
+                    const uint32_t next_m = has_next ? (uint32_t)sp[i + 1u] : 0u;
+                    if (mapsubst::eligible(false, cut, i == junction, has_prev, prev_m, cur_m, has_next, next_m, order) &&
+                        mapsubst::group_in_window(gword, p0 + kMapPad, cur_m))
+                        settled_m |= 1u << i;
+                    prev_m = cur_m;
+                    cur_m = next_m;
+                }
+            }
+            if (STATS) st_groups = (uint32_t)__popc(settled_m), st_bits = st_groups, st_clean = st_groups;
+        }
+        const uint32_t my_n = !plannable || flag ? 0u : DIRECT ? (no_plan ? (n_blockwin + 3u) / 4u : (len > thr ? cnt - (uint32_t)__popc(settled_m) : 0u))
                                                                : (no_plan ? (len + 15u) / 16u : cnt);
         uint32_t incl = my_n;
 #pragma unroll
@@ -810,10 +848,14 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                            o_len = __shfl(len, (int)owner), o_np = __shfl(no_plan ? 1u : 0u, (int)owner), o_junc = __shfl(junction, (int)owner), o_jov = __shfl(jov, (int)owner);
             // (what the bit of a lone substitution is keyed by, map_subst.hpp: the owner's diagonal, and whether it has only one)
             const uint32_t o_p0 = __shfl(p0, (int)owner), o_cut = __shfl(cut ? 1u : 0u, (int)owner);
+            // (... and which entries of its list the owner settled itself: item u of an owner is its u-th entry that is left)
+            const uint32_t o_settled = DIRECT ? __shfl(settled_m, (int)owner) : 0u;
             const bool blockmode = o_np != 0;
             if (DIRECT) {
                 if (work) {
-                    const uint32_t t = w - (o_incl - o_n);
+                    const uint32_t u_item = w - (o_incl - o_n);
+                    const uint32_t t = o_settled ? mapsubst::nth_unsettled(o_settled, u_item) : u_item; // (the entry's index in the owner's list)
+                    const uint32_t o_cnt = o_n + (uint32_t)__popc(o_settled);
                     const uint32_t m = blockmode ? 0u : (uint32_t)spw[owner * 16u + t];
                     uint32_t bytes[4], ee[4];
                     bool use[4], lastw[4], look[4];
@@ -824,7 +866,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
                     bool lone = false, settled = false;
                     if (a.ix.sub_clean && !blockmode) {
                         const uint8_t *osp = spw + owner * 16u;
-                        const bool has_prev = t > 0u, has_next = t + 1u < o_n;
+                        const bool has_prev = t > 0u, has_next = t + 1u < o_cnt;
                         lone = mapsubst::eligible(false, o_cut != 0u, t == o_junc, has_prev, has_prev ? (uint32_t)osp[t - 1u] : 0u, m, has_next,
                                                   has_next ? (uint32_t)osp[t + 1u] : 0u, order);
                         if (lone) {
@@ -1393,7 +1435,7 @@ __global__ __launch_bounds__(KBO_MAP_LB) void map_reads_kernel(WalkArgs a, uint3
     if (STATS) plan_stats_add(a.pstats, kPlanStatSeedLookups, st_lookups, kPlanStatSeedExtensions, st_filt /* (this kernel: filter look-ups) */, kPlanStatMismatches, seeded ? cnt : 0u, 0, 0);
     if (STATS) plan_stats_add(a.pstats, kPlanStatTabLookups, st_look, kPlanStatTabWritten, st_written, kPlanStatTabFlagged, flag ? 1u : 0u,
                    kPlanStatTabAnchored, st_anch);
-    if (STATS) plan_stats_add(a.pstats, kPlanStatSubstBits, st_bits, kPlanStatSubstClean, st_clean, 0, 0, 0, 0);
+    if (STATS) plan_stats_add(a.pstats, kPlanStatSubstBits, st_bits, kPlanStatSubstClean, st_clean, kPlanStatSubstGroups, st_groups, 0, 0);
     const uint64_t fm = __ballot(flag), nm = __ballot(no_plan);
     if (lane == 0) {
         if (fm) atomicAdd(a.qctl + 4, (uint32_t)__popcll(fm));
@@ -1547,11 +1589,13 @@ hipError_t launch_pack_text(const uint8_t *d_text_padded, uint64_t n_bytes, uint
     return hipGetLastError();
 }
 
-hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, hipStream_t stream)
+hipError_t launch_subst_bits(const DevIndexView &ix, uint64_t n_units, uint32_t thr, bool have_anch, uint32_t *d_bits, uint32_t *d_groups, hipStream_t stream)
 {
-    const uint64_t n_words = mapsubst::bitmap_words(n_units);
+    const uint64_t n_words = mapsubst::bitmap_words(n_units), n_gwords = mapsubst::group_words(n_units);
     hipLaunchKernelGGL(subst_bits_kernel, dim3((unsigned)((32u * n_words + 255u) / 256u)), dim3(256), 0, stream, SubstText{ix.pc_tm, n_units},
                        SubstTable{ix.dtab, ix.dtab_order, ix.dtab_grouped}, thr, have_anch ? 1u : 0u, d_bits, n_words);
+    if (d_groups)
+        hipLaunchKernelGGL(subst_groups_kernel, dim3((unsigned)((n_gwords + 255u) / 256u)), dim3(256), 0, stream, SubstBits{d_bits}, n_words, d_groups, n_gwords);
     return hipGetLastError();
 }
 
@@ -1606,6 +1650,7 @@ hipError_t launch_map_reads(WalkArgs &a, hipStream_t stream)
     const bool direct = map_reads_direct(a);
     // (the bits of lone substitutions speak for the windows of one threshold: another one's launch runs without them)
     if (!direct || a.map_thr != a.ix.sub_thr || (a.ix.sub_anch != 0u) != (a.ix.anchor != nullptr && a.map_thr > a.ix.dtab_order)) a.ix.sub_clean = nullptr;
+    if (!a.ix.sub_clean) a.ix.sub_group = nullptr;
     static const bool env_nouni = std::getenv("KBO_MAP_NO_UNIFORM") != nullptr; // experiments
     a.uniform_len = (a.seq_off && !env_nouni && a.max_item_len != 0 && (uint64_t)a.n_items * a.max_item_len == a.q_bytes) ? a.max_item_len : 0u;
     const int io = a.qp ? (a.packed_out ? 2 : 1) : 0;

@@ -85,5 +85,52 @@ KBO_MS_FN bool clean(const Text &tx, const Table &tab, uint64_t q, uint32_t orde
     return !window_used(kWindows, cov, order, 0u);
 }
 
+// ---- clean GROUPS: a coarser bitmap next to the bits, sub_group - bit G set when the kGroup bits of positions kGroup G ..
+// kGroup G + kGroup - 1 (counted like bit_of's result, padding included) are all set.  A set group bit implies the position's own
+// bit, so it settles a lone substitution by the same proof; a clear one promises nothing.  A read's whole window of groups is ONE
+// byte-aligned load of 8 bytes that depends on nothing but its diagonal: stage 2 of map_reads_kernel issues it beside the text's, and
+// the read's own lane settles its list before stage 3 deals what is left.
+//   q0 = p0 + kPad, the window's first position; its first group q0 / 4 lies in byte q0 / 32 of the array, at bit (q0 / 4) mod 8
+//   base m <= 159 of the read: bit (q0 + m) / 4 - 8 (q0 / 32) of the 64 loaded ones, at most (31 + 159) / 4 = 47
+//   the load's byte offset: at most group_load_max(units) for any q0 inside the padded text; behind the array's 4 group_words(units)
+//   bytes lie kGroupSlack zeroed ones (a window near the text's end reads into them: no group there is clean)
+constexpr uint32_t kGroup = 4, kGroupSlack = 64;
+KBO_MS_FN uint64_t group_of(uint64_t q) { return q / kGroup; }
+KBO_MS_FN uint64_t group_words(uint64_t n_units) { return (n_units * (16u / kGroup) + 31u) / 32u; }
+KBO_MS_FN uint64_t group_load_byte(uint32_t q0) { return group_of(q0) >> 3; }
+KBO_MS_FN uint64_t group_load_max(uint64_t n_units) { return group_of(16u * n_units - 1u) >> 3; }
+KBO_MS_FN bool group_in_window(uint64_t loaded, uint32_t q0, uint32_t m)
+{
+    return (loaded >> (uint32_t)(group_of((uint64_t)q0 + m) - 8u * group_load_byte(q0))) & 1u;
+}
+// the 32 / kGroup group bits of one word of position bits (any_bit: an OR where the rule says AND - only tools/map_group_check.cpp
+// sets it, to see its own check fail)
+KBO_MS_FN uint32_t group_bits_of_word(uint32_t w, bool any_bit = false)
+{
+    uint32_t out = 0;
+    for (uint32_t j = 0; j < 32u / kGroup; j++) {
+        const uint32_t f = (w >> (kGroup * j)) & ((1u << kGroup) - 1u);
+        if (any_bit ? f != 0u : f == (1u << kGroup) - 1u) out |= 1u << j;
+    }
+    return out;
+}
+// word W of the group bitmap from the position bits (Bits: uint32_t word(uint64_t w), zero behind its last word)
+template <class Bits> KBO_MS_FN uint32_t group_word(const Bits &bits, uint64_t W, uint64_t n_bit_words, bool any_bit = false)
+{
+    uint32_t out = 0;
+    for (uint32_t i = 0; i < kGroup; i++) {
+        const uint64_t w = kGroup * W + i;
+        if (w < n_bit_words) out |= group_bits_of_word(bits.word(w), any_bit) << (32u / kGroup * i);
+    }
+    return out;
+}
+// ---- dealing what is left of a read's list: `settled` has bit i set for entry i; -> the list index of the t-th entry that is not
+KBO_MS_FN uint32_t nth_unsettled(uint32_t settled, uint32_t t)
+{
+    uint32_t open = ~settled;
+    for (uint32_t i = 0; i < t; i++) open &= open - 1u;
+    return (uint32_t)__builtin_ctz(open);
+}
+
 } // namespace mapsubst
 } // namespace kbo
