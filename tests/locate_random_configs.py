@@ -1,8 +1,9 @@
-"""The generator of the third randomized oracle soak, over positions, segments, depth, placement and pileup (imported by
+"""The generator of the third randomized oracle soak, over positions, segments, depth, placement, pileup and indels (imported by
 tests/test_locate_random_configs_host.py, tests/test_gpu_locate_random_configs.py and tools/stress.py; holds no test itself).
 config(seed) draws everything one iteration checks - k by class, the sources and how their index and its position table are made, the
 batch's shape and its edits, bridge, strands and their order, skip_multi, the site thresholds, max_gap / max_indel, merge and the
-capacities of d_segs and d_sites - and make_inputs(cfg) makes the bytes.  Pure numpy: no GPU, no product library, no oracle; the same
+capacities of d_segs and d_sites; from a stream of its own the indel calls' max_indel, thresholds and the capacities of d_events and
+their d_sites - and make_inputs(cfg) makes the bytes.  Pure numpy: no GPU, no product library, no oracle; the same
 seed gives the same bytes on any machine.
 
 What the draws are for (kbo_amd/csrc/locate_kernels.hip, place_kernels.hip, pileup_kernels.hip): a tile of TILE positions looks HALO
@@ -62,13 +63,20 @@ class Config:
     merge: bool                # the second strand's kbo_place_dev merges into the first's records (else it writes over them)
     seg_cap: str               # of d_segs, every strand: CAPS
     site_cap: str              # of d_sites: CAPS
+    ev_max_indel: int          # kbo_indels_dev's own max_indel (cfg.max_indel is placement's and may be 0, which the events refuse)
+    ev_min_count: int          # the indel sites' thresholds
+    ev_frac_num: int
+    ev_frac_den: int
+    event_cap: str             # of d_events, the list of every strand: CAPS
+    ev_site_cap: str           # of the indel d_sites: CAPS
 
     def describe(self):
         return ("seed=%d k=%d rc=%s srcs=%d (%d bases) how=%s slab=%d shape=%s subs=%g bridge=%d strands=%s skip_multi=%s sites=%d,%d/%d "
-                "max_gap=%d max_indel=%d merge=%s seg_cap=%s site_cap=%s"
+                "max_gap=%d max_indel=%d merge=%s seg_cap=%s site_cap=%s events: max_indel=%d sites=%d,%d/%d event_cap=%s site_cap=%s"
                 % (self.seed, self.k, self.add_revcomp, len(self.src_lens), sum(self.src_lens), self.how, self.slab, self.shape, self.sub_rate,
                    self.bridge, self.strands, self.skip_multi, self.min_count, self.frac_num, self.frac_den, self.max_gap, self.max_indel,
-                   self.merge, self.seg_cap, self.site_cap))
+                   self.merge, self.seg_cap, self.site_cap, self.ev_max_indel, self.ev_min_count, self.ev_frac_num, self.ev_frac_den, self.event_cap,
+                   self.ev_site_cap))
 
 
 def config(seed):
@@ -89,13 +97,17 @@ def config(seed):
     where = int(rng.integers(0, n_srcs))  # sources in front of the long one too: its coordinates do not start at 0
     lens = small[:where] + [main] + small[where:]
     bridge = int(rng.choice([0, 1, k - 1, k, k, min(k + 1, 255), 255, 255, int(rng.integers(0, 256))]))
+    ev = np.random.default_rng([0x6C6F6361, int(seed), 3])  # the indel calls' fields from a stream of their own: every field above keeps its value
+    indel = dict(ev_max_indel=int(ev.choice([1, 5, 16, 17, 100, 0xFFFFFFFF])), ev_min_count=int(ev.choice([1, 1, 2, 3])), ev_frac_num=int(ev.choice([0, 1, 1, 2])),
+                 ev_frac_den=int(ev.choice([1, 2, 3])), event_cap=str(ev.choice(CAPS, p=[0.4, 0.25, 0.25, 0.1])),
+                 ev_site_cap=str(ev.choice(CAPS, p=[0.4, 0.25, 0.25, 0.1])))
     return Config(seed=int(seed), k=k, add_revcomp=bool(rng.random() < 0.5), src_lens=tuple(lens), how=str(rng.choice(HOWS)),
                   slab=int(rng.choice([0, int(rng.integers(1, k + 1)), int(rng.integers(k + 1, 2000))])), shape=str(rng.choice(SHAPES)),
                   sub_rate=float(rng.choice([0.0, 0.01, 0.05])), bridge=bridge, strands=((1,), (2,), (1, 2), (2, 1))[int(rng.integers(0, 4))],
                   skip_multi=bool(rng.random() < 0.5), min_count=int(rng.choice([1, 1, 2, 3])), frac_num=int(rng.choice([0, 1, 1, 2])),
                   frac_den=int(rng.choice([1, 2, 3])), max_gap=int(rng.choice([0, 50, 1000, 1000])), max_indel=int(rng.choice([0, 5, 100, 100])),
                   merge=bool(rng.random() < 0.7), seg_cap=str(rng.choice(CAPS, p=[0.4, 0.25, 0.25, 0.1])),
-                  site_cap=str(rng.choice(CAPS, p=[0.4, 0.25, 0.25, 0.1])))
+                  site_cap=str(rng.choice(CAPS, p=[0.4, 0.25, 0.25, 0.1])), **indel)
 
 
 def _rnd(rng, n):
@@ -217,6 +229,25 @@ def make_inputs(cfg):
             out.append(_edit(rng, cat[max(0, j - a):j + b], cfg))
         return out
 
+    def indel_reads(n):
+        """n reads over one place of the longest source, k + 1 .. k + 40 bases to either side of it, four in five with the same insertion
+        or deletion of 1 .. 20 bases there, on either strand: two segments and one event a read, a site that counts up to n.  From a
+        generator of their own and behind everything else: no other sequence of any seed changes"""
+        own = np.random.default_rng([0x6C6F6361, int(cfg.seed), 4])
+        at, ln = int(own.integers(m0 + k + 45, m1 - k - 65)), int(own.integers(1, 21))
+        ins = _rnd(own, ln) if own.random() < 0.5 else None
+        out = []
+        for _ in range(n):
+            a, b = int(own.integers(k + 1, k + 41)), int(own.integers(k + 1, k + 41))
+            if own.random() >= 0.8:
+                q = cat[at - a:at + b].copy()
+            elif ins is not None:
+                q = np.concatenate([cat[at - a:at], ins, cat[at:at + b]])
+            else:
+                q = np.concatenate([cat[at - a:at], cat[at + ln:at + ln + b]])
+            out.append(revcomp(q) if own.random() < 0.5 else q)
+        return out
+
     if cfg.shape == "reads":
         seqs = reads(int(rng.integers(60, 201))) + dense(2) + snp_reads(8)
     elif cfg.shape == "tiny":
@@ -229,6 +260,7 @@ def make_inputs(cfg):
     else:
         seqs = reads(30) + tiny(3000, 700) + [text(TILE + HALO + 1)] + junctions(10) + dense(2) + snp_reads(8)
         seqs = [seqs[i] for i in rng.permutation(len(seqs))]
+    seqs = seqs + indel_reads(6 if cfg.shape == "tiny" else 8) + ([np.zeros(0, dtype=np.uint8)] if cfg.shape == "tiny" else [])  # (tiny ends with an empty sequence)
     return srcs, [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
 
 

@@ -1,8 +1,9 @@
 """The third randomized oracle soak, inside the suite: a fixed list of seeded configurations (tests/locate_random_configs.py: k by class
 over 3 .. 255, sources of every kind behind an index made on the host, on the device or from parts, batch shapes at the tiles'
-boundaries, every call parameter and capacity) through positions, segments, depth, placement and pileup - the device composition
-kbo_ms_batch_dev -> kbo_segments_dev (with delta) -> kbo_place_dev -> kbo_pileup_dev per strand, kbo_depth_finish_dev and
-kbo_pileup_sites_dev behind them, all on ONE stream, and the host-batch forms kbo_amd.segments, kbo_amd.place and kbo_amd.pileup - every
+boundaries, every call parameter and capacity) through positions, segments, depth, placement, pileup and indels - the device composition
+kbo_ms_batch_dev -> kbo_segments_dev (with delta) -> kbo_place_dev -> kbo_pileup_dev -> kbo_indels_dev per strand, kbo_depth_finish_dev,
+kbo_pileup_sites_dev and kbo_indel_sites_dev behind them, all on ONE stream, and the host-batch forms kbo_amd.segments, kbo_amd.place,
+kbo_amd.pileup and kbo_amd.indels - every
 output word compared with brute force over the oracle's index, never with the product itself.  The expected values are World's
 (tests/test_locate_random_configs_host.py), which that module has already compared with the CPU restatements of the kernels on every
 seed: a failure here points at the device code.
@@ -23,6 +24,7 @@ import locate_random_configs as lrc
 from gpu_helpers import Guarded
 from test_gpu_index_locate import _Batch, _build, _geometry
 from test_gpu_index_pileup import _Piles
+from test_index_indel_host import event_tuples
 from test_index_pileup_host import site_tuples
 from test_index_place_host import same
 from test_locate_random_configs_host import World, coverage
@@ -31,6 +33,7 @@ pytestmark = pytest.mark.gpu
 
 SEEN = {}  # seed -> (Config, World.stats()): what the last test of the module counts
 SEG, REC = locate.SEGMENT_DTYPE.itemsize, locate.PLACE_DTYPE.itemsize
+EV, EV_SITE = locate.INDEL_EVENT_DTYPE.itemsize, locate.INDEL_SITE_DTYPE.itemsize
 E_HIP, E_EMPTY_QUERY = -7, -1
 
 
@@ -61,6 +64,16 @@ def check_config(cfg):
     pwb = {st: locate.place_work_bytes(b.n, w.caps[st]) for st in cfg.strands}
     pworks = {st: Guarded("d_work", pwb[st], 1 << 16, b.dev, seed=40 + st) for st in cfg.strands}
     place = Guarded("d_place", REC * b.n, 1 << 16, b.dev, seed=50)
+    # the indel calls: one list for every strand, its count zeroed once; d_work of kbo_indels_dev by each strand's d_segs capacity
+    ecap, icap = w.event_cap, w.ev_site_cap
+    events = Guarded("d_events", EV * ecap, 1 << 16, b.dev, seed=60)
+    ecnt = Guarded("d_n_events", 8, 4096, b.dev, seed=61, data=np.zeros(8, dtype=np.uint8))
+    ewb = {st: locate.indels_work_bytes(w.caps[st]) for st in cfg.strands}
+    eworks = {st: Guarded("d_work", ewb[st], 1 << 16, b.dev, seed=62 + st) for st in cfg.strands}
+    twb = locate.indel_sites_work_bytes(ecap)
+    twork = Guarded("d_work", twb, 1 << 16, b.dev, seed=65)
+    isites = Guarded("d_sites", EV_SITE * icap, 1 << 16, b.dev, seed=66)
+    icnt = Guarded("d_n_sites", 8, 4096, b.dev, seed=67)
     q0, off0 = b.q.clone(), b.d_off.clone()
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
@@ -73,9 +86,14 @@ def check_config(cfg):
                          max_indel=cfg.max_indel, merge=cfg.merge and i > 0, stream=stream)
         locate.pileup_dev(sbwt, b.qr if st == 2 else b.q, b.ms, b.d_off, b.n, b.total, segs[st].ptr if cap else None, cnts[st].ptr, cap, p.pile.ptr,
                           skip_multi=cfg.skip_multi, stream=stream)
+        locate.indels_dev(sbwt, b.qr if st == 2 else b.q, b.d_off, b.n, b.total, segs[st].ptr if cap else None, cnts[st].ptr, cap, events.ptr if ecap else None, ecap,
+                          ecnt.ptr, eworks[st].ptr, ewb[st], skip_multi=cfg.skip_multi, max_indel=cfg.ev_max_indel, stream=stream)
     p.finish((cfg.min_count, cfg.frac_num, cfg.frac_den), stream)
+    locate.indel_sites_dev(sbwt, events.ptr if ecap else None, ecnt.ptr, ecap, p.depth.ptr, isites.ptr if icap else None, icap, icnt.ptr, twork.ptr, twb,
+                           min_count=cfg.ev_min_count, frac_num=cfg.ev_frac_num, frac_den=cfg.ev_frac_den, stream=stream)
     torch.cuda.synchronize()
-    for g in list(segs.values()) + list(cnts.values()) + list(sworks.values()) + list(pworks.values()) + [place, b.swork, b.cnt]:
+    for g in list(segs.values()) + list(cnts.values()) + list(sworks.values()) + list(pworks.values()) + [place, b.swork, b.cnt] + list(eworks.values()) + [
+            events, ecnt, twork, isites, icnt]:
         g.assert_intact(tag)
     assert torch.equal(b.q, q0) and torch.equal(b.d_off, off0), "the inputs are read only | " + tag
     pile, depth, sites, n_sites = p.results(tag)
@@ -89,6 +107,15 @@ def check_config(cfg):
     same(place.host().view(locate.PLACE_DTYPE), w.place)
     assert np.array_equal(pile, w.pile), "pile: %s | %s" % (np.argwhere(pile != w.pile)[:5].tolist(), tag)
     assert n_sites == len(w.sites) and site_tuples(sites) == w.sites[:w.site_cap], "sites (%d vs %d) | %s" % (n_sites, len(w.sites), tag)
+    n_events, n_isites = int(ecnt.host().view(np.uint64)[0]), int(icnt.host().view(np.uint64)[0])
+    got_ev = events.host().view(locate.INDEL_EVENT_DTYPE)[:min(n_events, ecap)]
+    want_ev = np.array(w.events, dtype=locate.INDEL_EVENT_DTYPE)
+    assert n_events == len(w.all_events) and got_ev.tobytes() == want_ev.tobytes(), "indel events (%d vs %d): %s | %s" % (
+        n_events, len(w.all_events), [(i, a, x) for i, (a, x) in enumerate(zip(event_tuples(got_ev), w.events)) if a != x][:4], tag)
+    got_is = isites.host().view(locate.INDEL_SITE_DTYPE)[:min(n_isites, icap)]
+    want_is = np.array(w.ev_sites[:icap], dtype=locate.INDEL_SITE_DTYPE)
+    assert n_isites == len(w.ev_sites) and got_is.tobytes() == want_is.tobytes(), "indel sites (%d vs %d): %s | %s" % (
+        n_isites, len(w.ev_sites), [(i, a, x) for i, (a, x) in enumerate(zip(event_tuples(got_is), w.ev_sites)) if a != x][:4], tag)
     # the host-batch forms: a batch with an empty sequence is refused as kbo_find_batch_strands refuses it (kbo_hip.h), so they get
     # the sequences that are not empty, and the records' seq is counted among those
     recs, h_place, h_pile, h_sites = w.host_batch()
@@ -97,7 +124,7 @@ def check_config(cfg):
     seqs = [w.seqs[i] for i in keep]
     if len(keep) < w.n_seqs:
         for call in (lambda: kbo_amd.segments(w.seqs, sbwt, strands=mask), lambda: kbo_amd.place(w.seqs, sbwt, strands=mask),
-                     lambda: kbo_amd.pileup(w.seqs, sbwt, strands=mask)):
+                     lambda: kbo_amd.pileup(w.seqs, sbwt, strands=mask), lambda: kbo_amd.indels(w.seqs, sbwt, strands=mask)):
             with pytest.raises(kbo_amd.KboError) as ei:
                 call()
             assert ei.value.code == E_EMPTY_QUERY, tag
@@ -109,6 +136,9 @@ def check_config(cfg):
     s3, d3, p3 = kbo_amd.pileup(seqs, sbwt, bridge=cfg.bridge, strands=mask, skip_multi=cfg.skip_multi, min_count=cfg.min_count, frac_num=cfg.frac_num,
                                 frac_den=cfg.frac_den, depth=True, pile=True)
     assert np.array_equal(p3, h_pile) and np.array_equal(d3, w.depth) and site_tuples(s3) == h_sites, "kbo_amd.pileup | " + tag
+    s4, d4 = kbo_amd.indels(seqs, sbwt, bridge=cfg.bridge, strands=mask, skip_multi=cfg.skip_multi, max_indel=cfg.ev_max_indel, min_count=cfg.ev_min_count,
+                            frac_num=cfg.ev_frac_num, frac_den=cfg.ev_frac_den, depth=True)
+    assert np.array_equal(d4, w.depth) and event_tuples(s4) == w.host_indels(), "kbo_amd.indels | " + tag
     return w.stats()
 
 

@@ -1,21 +1,24 @@
 """The third randomized oracle soak on the host: the generator of tests/locate_random_configs.py is deterministic and well formed, the
 coverage conditions that the generator and the brute force alone decide hold over its SEEDS, and for every seed the CPU restatements
-of the kernels - kbo_positions_from_ms_host, kbo_segments_from_ms_host, kbo_place_from_segments_host, kbo_pileup_from_segments_host
-and kbo_pileup_sites_host - agree word for word with the yardsticks tests/test_gpu_locate_random_configs.py compares the device code
-with.  No GPU.
+of the kernels - kbo_positions_from_ms_host, kbo_segments_from_ms_host, kbo_place_from_segments_host, kbo_pileup_from_segments_host,
+kbo_pileup_sites_host, kbo_indels_from_segments_host and kbo_indel_sites_host - agree word for word with the yardsticks
+tests/test_gpu_locate_random_configs.py compares the device code with.  No GPU.
 
 World(cfg) is the reference side of one configuration, and the GPU module's: the oracle's index over the sources and its walk of the
 batch, the occurrence dict and the expected table of tests/test_index_locate_host.py, and over them that module's brute_segments,
-brute_delta and brute_depth, py_place of tests/test_index_place_host.py and brute_pile and brute_sites of
-tests/test_index_pileup_host.py - imported, not copied.  Nothing expected comes from the library under test.  The calls run strand by
-strand in the configuration's order; a d_segs capacity below the count leaves placement and pileup the records that fit, while delta
-counts every segment (kbo_hip.h)."""
+brute_delta and brute_depth, py_place of tests/test_index_place_host.py, brute_pile and brute_sites of
+tests/test_index_pileup_host.py and brute_events and brute_sites of tests/test_index_indel_host.py - imported, not copied.  Nothing
+expected comes from the library under test.  The calls run strand by strand in the configuration's order; a d_segs capacity below the
+count leaves placement, pileup and the indel events the records that fit, while delta counts every segment (kbo_hip.h); the events of
+every strand go into one list, whose capacity cuts it to a prefix."""
 import numpy as np
 import pytest
 
 from kbo_amd import locate
 
 import locate_random_configs as lrc
+from test_index_indel_host import INS, LONG, brute_events, event_tuples
+from test_index_indel_host import brute_sites as brute_indel_sites
 from test_index_locate_host import (NONE, brute_delta, brute_depth, brute_segments, covered, expected_table, occurrences, revcomp,
                                     src_offsets, stretches, walk)
 from test_index_pileup_host import brute_pile, brute_sites, site_tuples
@@ -36,7 +39,7 @@ class World:
         self.occ = occurrences(self.srcs, k, self.rc)
         self.table = expected_table(self.oi, self.occ)
         self.strand_seqs = {st: [revcomp(s) for s in self.seqs] if st == 2 else self.seqs for st in cfg.strands}
-        self.walks, self.segs, self.kept, self.caps, self.places, self.bridged = {}, {}, {}, {}, {}, {}
+        self.walks, self.segs, self.kept, self.kept_tuples, self.caps, self.places, self.bridged = {}, {}, {}, {}, {}, {}, {}
         delta = np.zeros(self.n_bases + 1, dtype=np.int64)
         self.depth = np.zeros(self.n_bases, dtype=np.uint32)
         self.pile = np.zeros((self.n_bases, 4), dtype=np.int64)
@@ -48,6 +51,7 @@ class World:
             self.segs[st] = recs
             self.caps[st] = lrc.capacity(cfg.seg_cap, len(recs))
             kept = recs[:self.caps[st]]
+            self.kept_tuples[st] = kept
             self.kept[st] = np.array(kept, dtype=locate.SEGMENT_DTYPE)
             delta += brute_delta(recs, k, self.n_bases).astype(np.int64)
             self.depth += brute_depth(recs, k, self.n_bases)
@@ -59,6 +63,20 @@ class World:
         self.place = place
         self.sites = brute_sites(self.pile, self.depth, self.soff, cfg.min_count, cfg.frac_num, cfg.frac_den, rows=np.flatnonzero(self.pile.any(axis=1)).tolist())
         self.site_cap = lrc.capacity(cfg.site_cap, len(self.sites))
+        # the indel events of the kept records, strand behind strand in one list, and their sites against the depth above
+        self.all_events, self.ev_made, self.ev_complex = self.events_of(self.kept_tuples)
+        self.event_cap = lrc.capacity(cfg.event_cap, len(self.all_events))
+        self.events = self.all_events[:self.event_cap]
+        self.ev_sites = brute_indel_sites(self.events, self.depth, self.soff, cfg.ev_min_count, cfg.ev_frac_num, cfg.ev_frac_den)
+        self.ev_site_cap = lrc.capacity(cfg.ev_site_cap, len(self.ev_sites))
+
+    def events_of(self, recs):
+        """brute_events over {strand: records} in the configuration's order into one list -> (the list, events per strand, complex
+        junctions per strand)"""
+        cfg, out, made, cx = self.cfg, [], {}, {}
+        for st in cfg.strands:
+            made[st], cx[st] = brute_events(recs[st], self.strand_seqs[st], self.walks[st][2], self.k, self.soff, cfg.skip_multi, cfg.ev_max_indel, out, 1 << 62)
+        return out, made, cx
 
     def host_batch(self):
         """what the host-batch forms (kbo_segments_batch, kbo_place_batch, kbo_pileup_batch) give: every record of every strand asked
@@ -77,6 +95,13 @@ class World:
                 brute_pile(self.segs[st], self.strand_seqs[st], self.walks[st][0], self.walks[st][2], k, self.n_bases, cfg.skip_multi, pile)
         sites = brute_sites(pile, self.depth, self.soff, cfg.min_count, cfg.frac_num, cfg.frac_den, rows=np.flatnonzero(pile.any(axis=1)).tolist())
         return recs, place, pile, sites
+
+    def host_indels(self):
+        """what kbo_indels_batch gives: the sites of the events of every record of every strand asked for, no list cut short"""
+        cfg = self.cfg
+        if all(self.caps[st] >= len(self.segs[st]) for st in cfg.strands) and self.event_cap >= len(self.all_events):
+            return self.ev_sites
+        return brute_indel_sites(self.events_of(self.segs)[0], self.depth, self.soff, cfg.ev_min_count, cfg.ev_frac_num, cfg.ev_frac_den)
 
     def stats(self):
         """what the coverage conditions count, from the generator and the brute force alone"""
@@ -105,6 +130,20 @@ class World:
         st["second"] = bool((self.place["second"] > 0).any())
         st["segs_below"] = any(self.caps[s] < len(self.segs[s]) for s in cfg.strands)
         st["sites_below"] = self.site_cap < len(self.sites)
+        # the indel calls, on the brute force's full list: an event's records were REV when MINUS differs from "the '-' strand's call"
+        ev, at = self.all_events, 0
+        st["ev_rev"] = False
+        for i, s in enumerate(cfg.strands):
+            st["ev_rev"] |= any((e[3] == 1) != (s == 2) for e in ev[at:at + self.ev_made[s]])
+            at += self.ev_made[s]
+        st["ev_any"] = len(ev) > 0
+        st["ev_ins_del"] = any(e[1] & INS for e in ev) and any(not e[1] & INS for e in ev)
+        st["ev_long"] = any(e[1] & LONG for e in ev)
+        st["ev_complex"] = sum(self.ev_complex.values()) > 0
+        st["ev_second"] = len(cfg.strands) == 2 and self.ev_made[cfg.strands[0]] > 0 and self.ev_made[cfg.strands[1]] > 0
+        st["ev_below"] = self.event_cap < len(ev)
+        st["ev_site2"] = any(s[4] >= 2 for s in self.ev_sites)
+        st["ev_sites_below"] = self.ev_site_cap < len(self.ev_sites)
         return st
 
 
@@ -138,6 +177,20 @@ def check_host(cfg):
     assert np.array_equal(pile, w.pile), "pile: %s | %s" % (np.argwhere(pile != w.pile)[:5].tolist(), tag)
     sites, n = locate.pileup_sites_host(pile, w.depth, w.soff, capacity=w.site_cap, min_count=cfg.min_count, frac_num=cfg.frac_num, frac_den=cfg.frac_den)
     assert n == len(w.sites) and site_tuples(sites) == w.sites[:w.site_cap], "pileup_sites_host (%d vs %d) | %s" % (n, len(w.sites), tag)
+    # kbo_indels_from_segments_host, strand behind strand into one list of exactly the capacity, and kbo_indel_sites_host over it
+    events, n_events = np.zeros(w.event_cap, dtype=locate.INDEL_EVENT_DTYPE), 0
+    for st in cfg.strands:
+        cat = np.concatenate(w.strand_seqs[st] + [np.zeros(0, dtype=np.uint8)])
+        _, after, cx = locate.indels_from_segments_host(w.kept[st], cat, w.walks[st][2], k, w.soff, skip_multi=cfg.skip_multi, max_indel=cfg.ev_max_indel,
+                                                        events=events, n_events=n_events)
+        assert after - n_events == w.ev_made[st] and cx == w.ev_complex[st], "indels_from_segments_host strand %d (%d vs %d events, %d vs %d complex) | %s" % (
+            st, after - n_events, w.ev_made[st], cx, w.ev_complex[st], tag)
+        n_events = after
+    assert n_events == len(w.all_events) and event_tuples(events[:n_events]) == w.events, "indels_from_segments_host: the list | " + tag
+    assert not events[n_events:].view(np.uint32).any(), "nothing behind the count is written | " + tag
+    sites, n = locate.indel_sites_host(events, n_events, w.depth, w.soff, capacity=w.ev_site_cap, min_count=cfg.ev_min_count, frac_num=cfg.ev_frac_num,
+                                       frac_den=cfg.ev_frac_den)
+    assert n == len(w.ev_sites) and event_tuples(sites) == w.ev_sites[:w.ev_site_cap], "indel_sites_host (%d vs %d) | %s" % (n, len(w.ev_sites), tag)
     return w
 
 
@@ -205,6 +258,15 @@ CONDITIONS = [("k class %d %s" % (i, (cls[0], cls[-1])), 5, (lambda i: lambda c,
     ("a place record with second > 0", 10, lambda c, st: st["second"]),
     ("d_segs capacity below the count", 10, lambda c, st: st["segs_below"]),
     ("d_sites capacity below the count", 10, lambda c, st: st["sites_below"]),
+    ("an indel event", 10, lambda c, st: st["ev_any"]),
+    ("an insertion and a deletion in one list", 5, lambda c, st: st["ev_ins_del"]),
+    ("a LONG insertion", 3, lambda c, st: st["ev_long"]),
+    ("an event from REV records", 5, lambda c, st: st["ev_rev"]),
+    ("a complex junction", 5, lambda c, st: st["ev_complex"]),
+    ("events appended by a second strand", 5, lambda c, st: st["ev_second"]),
+    ("d_events capacity below the count", 5, lambda c, st: st["ev_below"]),
+    ("an indel site with count >= 2", 5, lambda c, st: st["ev_site2"]),
+    ("indel site capacity below the count", 3, lambda c, st: st["ev_sites_below"]),
 ]
 
 
