@@ -227,7 +227,8 @@ int kbo_map_batch_opts_phases(double out[6]);
 int kbo_index_build_device_phases(double out[9]);
 /* Test hook: bytes the calling thread's last host batch (kbo_ms_batch, kbo_matches_batch / kbo_map_batch / kbo_find_batch, their
  * packed and *_strands forms) copied from the host to the device: bases or words, exception lists, offsets, work items.  A batch
- * run in both strands stages what it stages for one (tests/test_gpu_strands.py). */
+ * run in both strands stages what it stages for one (tests/test_gpu_strands.py) cut into the same slabs - both strands cut slabs of
+ * half of kbo_set_slab_bytes, 32 KiB at least, and every slab stages one offset more than it has sequences. */
 uint64_t kbo_last_batch_staged_bytes(void);
 /* inspection / tests: slabs of kbo_summary_batch[_packed] since the process started, by route - records straight from map_reads_kernel's
  * summary form and its second pass (no character made), or characters on the device and the reducer over them.  Either may be NULL. */

@@ -23,6 +23,17 @@ LEGS = ("packed", "find", "device", "call", "devbuild", "map_opts", "fill_gaps",
 # probability of each optional leg (a is always run): a seed decides, not the clock
 LEG_P = {"packed": 0.4, "find": 0.5, "device": 0.9, "call": 0.3, "devbuild": 0.2, "map_opts": 0.3, "fill_gaps": 0.35, "sparse": 0.4,
          "stream": 0.4, "shards": 0.25}
+# the second set of legs (l - q of the GPU module), drawn into Config.extra from a stream of their own (_extra): entry points added
+# after the first set, which take map_reads_kernel / finish_reads_kernel through their summary and run-count forms, double a slab on
+# the device for the other strand, or take a real walk's MS bytes and characters at a threshold per sequence
+LEGS2 = ("summary", "strands", "find_dev", "seq_thresholds", "rle_dev", "revcomp_dev")
+LEG2_P = {"summary": 0.6, "strands": 0.55, "find_dev": 0.6, "seq_thresholds": 0.5, "rle_dev": 0.5, "revcomp_dev": 0.5}
+SUMMARY_FORMS = ("host", "packed", "device", "stream")
+# kbo_derand_*_seq_dev: what a sequence's threshold is drawn from, t the oracle's threshold of the index (resolved by thresholds_of)
+N_THR_CANDIDATES = 7
+COMP = np.arange(256, dtype=np.uint8)  # kbo_hip.h "both strands": A <-> T, C <-> G, a <-> t, c <-> g, every other byte unchanged
+for _a, _b in zip(b"ACGTacgt", b"TGCAtgca"):
+    COMP[_a] = _b
 
 
 def k_class(k):
@@ -82,7 +93,7 @@ class Config:
         return ("seed=%d k=%d G=%d rc=%s contigs=%d+%d repeats=%s shape=%s n=%d max_len=%d sub=%g p=%g knobs=%s legs=%s"
                 % (self.seed, self.k, self.G, self.add_revcomp, self.n_contigs, self.short_contigs, self.repeats, self.shape,
                    len(self.lens), max(self.lens), self.sub_rate, self.max_error_prob, self.knobs,
-                   [n for n in LEGS if self.legs[n]]))
+                   [n for n in LEGS if self.legs[n]] + [n for n in LEGS2 if self.extra.get("legs", {}).get(n)]))
 
 
 def _knobs(rng):
@@ -134,6 +145,43 @@ def _lens(rng, k, shape, glen):
     return tuple(lens[i] for i in order)
 
 
+def _extra(seed, k, knobs, lens, short_seqs):
+    """Config.extra: the draws of legs l - q, from a stream of their own - no draw of config() moves"""
+    rng = np.random.default_rng([0x6B626F, int(seed), 3])
+    n = len(lens)
+    ex = {"legs": {name: bool(rng.random() < LEG2_P[name]) for name in LEGS2}}  # ("strands" below is which strands, not the leg)
+    order = rng.permutation(n)
+    minus = np.zeros(n, dtype=bool)
+    minus[order[:(n + 1) // 2]] = True  # half of the sequences, whichever the batch's size
+    ex["minus"] = tuple(bool(x) for x in minus)
+    ex["strands"] = int(rng.choice([1, 2, 3, 3, 3, 3]))
+    ex["strand_format"] = bool(rng.random() < 0.5)
+    ex["strand_gap"] = int(rng.choice([0, 0, 3, 50]))
+    ex["find_dev_gap"] = int(rng.choice([0, 0, 5, 2**32 - 1]))
+    ex["find_dev_cap"] = float(rng.random())  # the second run's capacity, as a part of the oracle's count
+    forms = {name: bool(rng.random() < p) for name, p in zip(SUMMARY_FORMS, (0.6, 0.5, 0.8, 0.6))}
+    ex["summary_max_len_known"] = bool(rng.random() < 0.5)  # kbo_summary_dev / _words_dev: max_seq_len = the longest, or 0
+    ns = n + len(short_seqs)  # (a threshold per sequence of the device legs' batch, with_shorts)
+    choice = rng.integers(0, N_THR_CANDIDATES, ns)
+    choice[:2] = (0, 1)[:ns]  # 2 and 3: two thresholds in every batch of two sequences or more, whatever t is
+    ex["thr_choice"] = tuple(int(x) for x in choice)
+    ex["rle_capacity_mode"] = str(rng.choice(["full", "third", "zero"]))
+    ex["rle_gap"] = int(rng.choice([0, 3, 50, 2**32 - 1]))
+    # map_reads_kernel's NP = 18 summary forms need reads over a depth table of order 16: the few configurations that have both run them
+    if knobs["depth_table"] == 16 and max(lens) <= 160 and k >= 16:
+        ex["legs"]["summary"] = forms["device"] = True
+    ex["summary_forms"] = forms
+    return ex
+
+
+def thresholds_of(cfg, t, n_seqs):
+    """the threshold of every sequence of the device legs' batch: cfg.extra["thr_choice"] into {2, 3, t - 1, t, t + 1, k - 1, k}
+    clipped to [2, k], t the oracle's threshold -> int32[n_seqs]"""
+    cand = np.clip(np.array([2, 3, t - 1, t, t + 1, cfg.k - 1, cfg.k], dtype=np.int64), 2, cfg.k)
+    assert len(cand) == N_THR_CANDIDATES and len(cfg.extra["thr_choice"]) == n_seqs
+    return cand[np.asarray(cfg.extra["thr_choice"], dtype=np.int64)].astype(np.int32)
+
+
 def config(seed):
     """everything one iteration draws, from `seed` alone"""
     rng = np.random.default_rng([0x6B626F, int(seed)])
@@ -169,12 +217,13 @@ def config(seed):
         n_contigs, short_contigs = int(rng.integers(2, 9)), int(rng.integers(1, 4))
     n_short = int(rng.integers(1, 5)) if rng.random() < 0.5 else 0
     short_seqs = tuple(sorted((int(rng.integers(0, len(lens) + 1)), int(rng.integers(0, 3))) for _ in range(n_short)))
+    extra = _extra(seed, k, knobs, lens, short_seqs)
     return Config(seed=int(seed), k=k, G=G, genome_seed=genome_seed, repeats=repeats, n_contigs=n_contigs, short_contigs=short_contigs,
                   add_revcomp=rc, knobs=knobs, shape=shape, lens=lens, short_seqs=short_seqs, refuse_len=refuse_len, refuse_at=refuse_at, sub_rate=sub, indel=indel, n_bytes=n_bytes,
                   max_error_prob=p_err, gap_len=gap_len, packed_gap_len=packed_gap_len, legs=legs, call_emit=call_emit,
                   call_pick=call_pick, map_opts=map_opts, opts_lens=opts_lens, dev_format=bool(rng.random() < 0.5),
                   dev_zero_sizing=bool(rng.random() < 0.3), tail_stream=bool(rng.random() < 0.5),
-                  stream_pipelines=int(rng.integers(1, 3)), stream_parts=int(rng.integers(3, 7)), shards=int(rng.choice([2, 3])))
+                  stream_pipelines=int(rng.integers(1, 3)), stream_parts=int(rng.integers(3, 7)), shards=int(rng.choice([2, 3])), extra=extra)
 
 
 def _genome(cfg, rng):
@@ -242,6 +291,48 @@ def with_refused(cfg, concat, offsets):
     concat2 = np.concatenate([concat[:a], concat[:cfg.refuse_len], concat[a:]]).astype(np.uint8)
     lens2 = np.concatenate([lens[:cfg.refuse_at], [cfg.refuse_len], lens[cfg.refuse_at:]])
     return concat2, np.concatenate([[0], np.cumsum(lens2)]).astype(np.uint64)
+
+
+def revcomp(concat, offsets):
+    """the reverse complement of every sequence in place of the sequence (kbo_hip.h "both strands"), in numpy"""
+    off = np.asarray(offsets).astype(np.int64)
+    lens = np.diff(off)
+    src = np.repeat(off[:-1] + off[1:] - 1, lens) - np.arange(int(off[-1]), dtype=np.int64)  # base i of s <- base a + b - 1 - i
+    return COMP[np.asarray(concat, dtype=np.uint8)[src]]
+
+
+def make_strand_inputs(cfg, concat, offsets):
+    """the main batch with the sequences of cfg.extra["minus"] reverse-complemented: the reads of the other strand, without which the
+    '-' outputs over a forward-only index are all '-' and compare nothing -> concat"""
+    minus = np.asarray(cfg.extra["minus"], dtype=bool)
+    assert len(minus) == len(offsets) - 1
+    per_base = np.repeat(minus, np.diff(np.asarray(offsets).astype(np.int64)))
+    return np.where(per_base, revcomp(concat, offsets), concat).astype(np.uint8)
+
+
+PACK_CODE = np.full(256, 4, dtype=np.uint8)
+PACK_CODE[list(b"ACGT")] = (0, 1, 2, 3)
+
+
+def pack_words(codes, offsets):
+    """2-bit codes (one per base, 0 .. 3) -> the packed layout of kbo_hip.h: every sequence starts a word, 16 bases a word from the
+    low bits up, the padding bits of a sequence's last word zero -> uint32 words"""
+    off = np.asarray(offsets).astype(np.int64)
+    lens = np.diff(off)
+    wo = np.concatenate([[0], np.cumsum((lens + 15) // 16)])
+    pos = np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], lens)
+    words = np.zeros(int(wo[-1]), dtype=np.uint64)
+    np.add.at(words, np.repeat(wo[:-1], lens) + pos // 16, np.asarray(codes, dtype=np.uint64) << (2 * (pos % 16)).astype(np.uint64))
+    return words.astype(np.uint32)
+
+
+def pack_reads(concat, offsets):
+    """bytes -> (words, exception positions uint64, exception bytes, mask of the bits that are specified: not those of a listed base)"""
+    concat = np.asarray(concat, dtype=np.uint8)
+    code = PACK_CODE[concat]
+    pos = np.flatnonzero(code == 4).astype(np.uint64)
+    mask = ~pack_words(np.where(code == 4, 3, 0), offsets)
+    return pack_words(code & 3, offsets), pos, concat[pos.astype(np.int64)].copy(), mask
 
 
 def genome_of(cfg):

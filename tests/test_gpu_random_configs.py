@@ -3,6 +3,11 @@ index content, every process-wide knob, batch shapes at the kernels' boundaries)
 compared with the CPU oracle - never with the product itself.  check_config() returns the routes it saw the product take; the last
 test of the module asserts, over all seeds, that the kernels the module claims to cover were reached (ROUTE_CONDITIONS).
 
+Legs a - k: the host entry points, the packed ones, find, the device-resident map, call, the device builder, map_batch_opts, fill_gaps,
+the sparse form, map streams, a sharded index.  Legs l - q (random_configs.LEGS2, drawn into Config.extra): the per-sequence summaries
+(host, packed, device, map stream, the reducer alone), both strands, kbo_find_batch_dev, a threshold per sequence over the oracle's MS
+bytes, run lengths of the oracle's characters on the device, the reverse complement of a device-resident batch.
+
 A failure names its seed and prints the configuration: `SEED=<n> SECONDS=1 python tools/stress.py` replays exactly that case."""
 import ctypes
 
@@ -51,6 +56,98 @@ def _eq(got, want, offsets, what, tag):
 # oracle error code -> the product's (kbo_hip.h): the same reference assertion
 _CODE = {-1: -1, -2: -2, -3: -3, -6: -11}
 
+# ---- legs l - q: what the oracle's characters say, in numpy written here - nothing of kbo_amd makes an expected value
+SENTINEL = 0x5A5A5A5A  # behind a record buffer's capacity
+
+
+def _np_summary(oracle, chars, offsets):
+    """kbo_aln_summary of every sequence: the numbers of 'M', 'X' and 'R', and the runs the oracle's run_lengths_gapped counts with
+    max_gap_len = 0; all zero for a sequence of fewer than 3 bases -> (n, 4) uint32"""
+    off = np.asarray(offsets).astype(np.int64)
+    out = np.zeros((len(off) - 1, 4), dtype=np.uint32)
+    for j, ch in enumerate(b"MXR"):
+        cs = np.concatenate([[0], np.cumsum(chars == ch)])
+        out[:, j] = cs[off[1:]] - cs[off[:-1]]
+    out[:, 3] = np.diff(oracle.run_lengths_batch(chars, offsets, 0)[1].astype(np.int64))
+    out[np.diff(off) < 3] = 0
+    return out
+
+
+def _eq_records(got, want, offsets, what, tag):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, "%s: %s vs %s | %s" % (what, got.shape, want.shape, tag)
+    if not np.array_equal(got, want):
+        bad = np.flatnonzero((got != want).any(axis=1))
+        s = int(bad[0])
+        raise AssertionError("%s: %d of %d records differ; first: sequence %d (len %d) got %s want %s | %s" % (
+            what, len(bad), len(want), s, int(offsets[s + 1] - offsets[s]), got[s].tolist(), want[s].tolist(), tag))
+
+
+def _eq_runs(got_recs, got_first, want_recs, want_first, what, tag):
+    assert np.array_equal(np.asarray(got_first, dtype=np.uint64), np.asarray(want_first, dtype=np.uint64)), "%s: first-run indices | %s" % (what, tag)
+    got = np.asarray(got_recs, dtype=np.uint64).reshape(-1, 7)
+    assert got.shape == want_recs.shape and np.array_equal(got, want_recs), "%s: run-length records (%d vs %d) | %s" % (what, len(got), len(want_recs), tag)
+
+
+def _interleave_strands(per, n, strands):
+    """kbo_find_batch_strands' layout from the oracle's run lengths per strand: per sequence the '+' runs, then the '-' runs; a strand
+    not asked for has none -> (records, rle_offsets uint64[2 n + 1])"""
+    counts = np.zeros(2 * n, dtype=np.int64)
+    for st in (1, 2):
+        if strands & st:
+            counts[st - 1::2] = np.diff(per[st][1].astype(np.int64))
+    ro = np.concatenate([[0], np.cumsum(counts)])
+    recs = np.zeros((int(ro[-1]), 7), dtype=np.uint64)
+    for st in (1, 2):
+        if strands & st:
+            r, o = per[st]
+            o = o.astype(np.int64)
+            seq = np.repeat(np.arange(n), np.diff(o))
+            recs[ro[2 * seq + st - 1] + np.arange(len(r)) - o[seq]] = r
+    return recs, ro.astype(np.uint64)
+
+
+def _n_slabs(offsets, max_bytes):
+    """how many slabs the host pipeline cuts a batch into (DESIGN 4.8): whole sequences, as many as fit max_bytes and one at least;
+    of three slabs or more the last - if it holds 64 sequences or more - in a half and two quarters"""
+    off = np.asarray(offsets).astype(np.int64)
+    n, s0, slabs = len(off) - 1, 0, []
+    while s0 < n:
+        s1 = max(int(np.searchsorted(off, off[s0] + max_bytes, side="right")) - 1, s0 + 1)
+        slabs.append(s1 - s0)
+        s0 = s1
+    return len(slabs) + (2 if len(slabs) >= 3 and slabs[-1] >= 64 else 0)
+
+
+def _slab_routes(L):
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    assert L.kbo_summary_slab_routes(ctypes.byref(a), ctypes.byref(b)) == 0
+    return int(a.value), int(b.value)
+
+
+def _rle_buffers(torch, dev, capacity):
+    """a DeviceBatch's run-length buffers with room for `capacity` records and eight rows of SENTINEL behind them"""
+    import kbo_amd
+    L = kbo_amd.lib()
+    dev.rle_work = torch.zeros(int(L.kbo_run_lengths_work_bytes(dev.n_seqs)) // 4 + 1, dtype=torch.int32, device=dev.device)
+    dev.rle_capacity = int(capacity)
+    dev.rle_records = torch.full((int(capacity) + 8, 7), SENTINEL, dtype=torch.int32, device=dev.device)
+
+
+def _rle_total(dev):
+    """the number of runs the last run_lengths() / run_find() counted: the last word of its work buffer"""
+    n = dev.n_seqs
+    return int(dev.rle_work.cpu().numpy().view(np.uint32)[n + 1 + (n + 1 + 1023) // 1024])
+
+
+def _check_capped(records, capacity, total, want_recs, what, tag):
+    """a record buffer of fewer slots than runs: the runs that fit are there, nothing is written behind `capacity`"""
+    got = records.cpu().numpy().view(np.uint32)
+    assert total == len(want_recs), "%s: %d runs counted, the oracle has %d | %s" % (what, total, len(want_recs), tag)
+    m = min(capacity, total)
+    assert np.array_equal(got[:m].astype(np.uint64), want_recs[:m]), "%s: the %d records that fit | %s" % (what, m, tag)
+    assert (got[capacity:] == SENTINEL).all(), "%s: a record written behind capacity %d | %s" % (what, capacity, tag)
+
 
 def check_config(cfg, oracle):  # noqa: C901 (one leg after the other)
     """one configuration through every leg it draws, each against the oracle -> the set of routes the product reported"""
@@ -96,6 +193,73 @@ def check_config(cfg, oracle):  # noqa: C901 (one leg after the other)
     sc, so, keep = rc.with_shorts(cfg, concat, offsets)
     if cfg.short_seqs:
         routes.update("short_%d_in_device_legs" % n for _, n in cfg.short_seqs)
+    slens = np.diff(so.astype(np.int64))
+    ex, legs2 = cfg.extra, cfg.extra["legs"]
+    # the oracle's characters in the layout of the device legs' batch, 'M' at the sequences of fewer than 3 bases
+    full_chars = np.full(len(sc), ord("M"), dtype=np.uint8)
+    full_chars[keep] = exp_chars
+    strand_exp = {}
+
+    def strand_expect():
+        """leg m's batch - the main batch with the sequences of `minus` reverse-complemented - and what the oracle says of it: its
+        matches_batch of that batch ('+') and of the batch's numpy reverse complement ('-').  One oracle call more: a sequence not
+        of `minus` is the main batch's (exp_chars) on '+', and the reverse complement of a reverse complement is the sequence itself"""
+        if not strand_exp:
+            pm = np.repeat(np.asarray(ex["minus"], dtype=bool), lens)
+            sin = rc.make_strand_inputs(cfg, concat, offsets)
+            srev = rc.revcomp(sin, offsets)
+            other = oi.matches_batch(rc.revcomp(concat, offsets), offsets, p_err, n_threads=8)
+            assert np.array_equal(srev, np.where(pm, concat, rc.revcomp(concat, offsets)))
+            strand_exp["in"] = sin
+            strand_exp[1] = np.where(pm, other, exp_chars)
+            strand_exp[2] = np.where(pm, exp_chars, other)
+            strand_exp["fmt", 1] = np.frombuffer(oracle.relative_to_ref(sin, strand_exp[1]), dtype=np.uint8)
+            strand_exp["fmt", 2] = np.frombuffer(oracle.relative_to_ref(srev, strand_exp[2]), dtype=np.uint8)
+            per = {st: oracle.run_lengths_batch(strand_exp[st], offsets, ex["strand_gap"]) for st in (1, 2)}
+            strand_exp["runs"] = _interleave_strands(per, len(lens), ex["strands"])
+            strand_exp["words"] = batch.pack_reads(sin, offsets)
+        return strand_exp
+
+    def leg_m(h, name):
+        """both strands through handle h, every strand asked for against the oracle"""
+        E = strand_expect()
+        st, fmt, n = ex["strands"], ex["strand_format"], len(lens)
+        fwd, rev = batch.matches_batch_strands(h, E["in"], offsets, p_err, format=fmt, strands=st)
+        staged = batch.last_batch_staged_bytes()
+        assert (fwd is not None) == bool(st & 1) and (rev is not None) == bool(st & 2), name + " strands | " + tag
+        for bit, got in ((1, fwd), (2, rev)):
+            if st & bit:
+                _eq(got, E["fmt", bit] if fmt else E[bit], offsets, "%s matches_batch_strands %d, format %s, strand %d" % (name, st, fmt, bit), tag)
+        if st == 3:  # the batch is staged once: both strands stage what one strand stages - the bases and, per slab, one offset more
+            # than it has sequences.  Both strands cut slabs of half the configured size (of 32 KiB at least); kbo_set_slab_bytes takes
+            # 64 KiB at least.  Where one strand can be cut the same way the figures are equal; else they differ by the slabs' offsets
+            half = max(cfg.knobs["slab_bytes"] // 2, 1 << 15)
+            same_cut = half >= 1 << 16
+            L.kbo_set_slab_bytes(half if same_cut else cfg.knobs["slab_bytes"])
+            try:
+                batch.matches_batch_strands(h, E["in"], offsets, p_err, format=fmt, strands=1)
+            finally:
+                L.kbo_set_slab_bytes(cfg.knobs["slab_bytes"])
+            more = 0 if same_cut else 8 * (_n_slabs(offsets, half) - _n_slabs(offsets, cfg.knobs["slab_bytes"]))
+            one = batch.last_batch_staged_bytes()
+            what = "%s: staged %d bytes for one strand (+ %d of offsets), %d for both | %s" % (name, one, more, staged, tag)
+            if same_cut or max_len <= 160:
+                assert one + more == staged, what
+            else:  # (longer sequences are cut into work items by the slab's size, and those are uploaded: another cut, other items -
+                # a few bytes each; a batch staged twice would be all of its bases more)
+                assert 2 * abs(staged - one - more) < len(concat), what
+        words, epos, ebyt = E["words"]
+        wf, wr = batch.matches_batch_packed_strands(h, words, offsets, epos, ebyt, p_err, strands=st)
+        for bit, got in ((1, wf), (2, wr)):
+            assert (got is not None) == bool(st & bit), name + " packed strands | " + tag
+            if st & bit:
+                _eq(batch.unpack_matches(got, offsets), E[bit], offsets, "%s matches_batch_packed_strands %d, strand %d" % (name, st, bit), tag)
+        exp_recs, exp_ro = E["runs"]
+        fo = kbo_amd.FindOpts(max_error_prob=p_err, max_gap_len=ex["strand_gap"])
+        for what, (recs, ro) in (("find_batch_strands", batch.find_batch_strands(h, E["in"], offsets, fo, strands=st)),
+                                 ("find_batch_packed_strands", batch.find_batch_packed_strands(h, words, offsets, epos, ebyt, fo, strands=st))):
+            assert len(ro) == 2 * n + 1, "%s %s: 2 n + 1 offsets | %s" % (name, what, tag)
+            _eq_runs(recs, ro, exp_recs, exp_ro, "%s %s %d, gap %d" % (name, what, st, ex["strand_gap"]), tag)
 
     def leg_a(h, name):
         d, _, _ = batch.ms_batch(h, concat, offsets)
@@ -309,18 +473,22 @@ def check_config(cfg, oracle):  # noqa: C901 (one leg after the other)
             del pb
 
     # ---- j: the batch cut into sub-batches through a MapStream, two rounds (slots reused), each against the ORACLE's characters
-    if cfg.legs["stream"]:
-        slens = np.diff(so.astype(np.int64))
+    def stream_subs(fmt):
+        """the device legs' batch cut into cfg.stream_parts sub-batches -> (cuts, [(first base, last base, DeviceBatch)])"""
         n = len(slens)
         parts = min(cfg.stream_parts, n)
         cuts = [n * i // parts for i in range(parts + 1)]
-        wfull = np.zeros(len(sc), dtype=np.uint8)
-        wfull[keep] = exp_map if cfg.dev_format else exp_chars
         subs = []
         for a, b in zip(cuts[:-1], cuts[1:]):
             lo, hi = int(so[a]), int(so[b])
             subs.append((lo, hi, batch.DeviceBatch(sbwt, sc[lo:hi], so[a:b + 1] - so[a], device=dev0, max_error_prob=p_err,
-                                                   format=cfg.dev_format, want_ms=False)))
+                                                   format=fmt, want_ms=False)))
+        return cuts, subs
+
+    if cfg.legs["stream"]:
+        cuts, subs = stream_subs(cfg.dev_format)
+        wfull = np.zeros(len(sc), dtype=np.uint8)
+        wfull[keep] = exp_map if cfg.dev_format else exp_chars
         ms = batch.MapStream(sbwt, max(d.n_seqs for _, _, d in subs), max(d.total for _, _, d in subs), max_len if max_len <= 160 else 0,
                              pipelines=cfg.stream_pipelines)
         try:
@@ -350,9 +518,241 @@ def check_config(cfg, oracle):  # noqa: C901 (one leg after the other)
             L.kbo_set_index_shards(0)
         leg_a(ssbwt, "sharded x%d" % ssbwt.shards())
         leg_i(ssbwt, "sharded x%d" % ssbwt.shards())
+        if legs2["strands"]:
+            leg_m(ssbwt, "sharded x%d" % ssbwt.shards())
         if ssbwt.shards() > 1:  # (an index of fewer k-mers than shards stays whole: it does not count as leg k)
             routes.add("k")
+            if legs2["strands"]:
+                routes.add("strands_sharded")
         del ssbwt
+
+    off_t = torch.from_numpy(so.view(np.int64)).to(dev0)
+    n_s, total_s, max_s = len(slens), len(sc), int(slens.max())
+    cur = torch.cuda.current_stream(dev0)
+
+    # ---- l: per-sequence summaries - map_reads_kernel's and finish_reads_kernel's summary forms, the reducer - against the oracle's
+    # characters counted by numpy; the host forms over the main batch (they refuse short sequences), the device forms over the batch
+    # with sequences of 0 / 1 / 2 bases, whose records are all zero
+    if legs2["summary"]:
+        forms = ex["summary_forms"]
+        want_d = _np_summary(oracle, full_chars, so)
+        assert (want_d[slens < 3] == 0).all()
+        if forms["host"] or forms["packed"]:
+            want_h = _np_summary(oracle, exp_chars, offsets)
+        for packed in (False, True):
+            if forms["packed" if packed else "host"]:
+                k0, r0 = _slab_routes(L)
+                got = batch.summary_batch(sbwt, (concat, offsets), p_err, packed=packed)
+                k1, r1 = _slab_routes(L)
+                _eq_records(got, want_h, offsets, "summary_batch, packed %s" % packed, tag)
+                assert (k1 - k0) + (r1 - r0) > 0, "summary_batch: no slab counted | " + tag
+                if k1 > k0:
+                    routes.add("summary_host_packed_kernel" if packed else "summary_host_kernel")
+                if r1 > r0:
+                    routes.add("summary_host_reducer")
+        if forms["device"]:
+            dev = batch.DeviceBatch(sbwt, sc, so, device=dev0, max_error_prob=p_err, format=False, want_ms=False)
+            dev._summary_buffers()
+            dev.summary.view(torch.uint8).fill_(0xEE)
+            dev.ms.fill_(0xEE)
+            dev.run_summary(tail_stream=torch.cuda.Stream(dev0) if cfg.tail_stream else None)
+            torch.cuda.synchronize()
+            _eq_records(dev.summary_host(), want_d, so, "kbo_summary_batch_dev (fused %s)" % dev.fused, tag)
+            if dev.fused and max_s <= 160:  # the one kernel's summary form: no MS value and no character reaches memory
+                assert bool((dev.ms == 0xEE).all()), "kbo_summary_batch_dev: the one-kernel route touched d_ms | " + tag
+                flags = np.zeros(n_s, dtype=np.uint8)  # (off the summary batch's own work memory)
+                kbo_amd.check(L.kbo_plan_flags_dev(n_s, total_s, dev.max_len, k, dev.summary_work.data_ptr(), flags.ctypes.data, cur.cuda_stream))
+                routes.add("summary_dev_fused")
+                if np.count_nonzero(flags):
+                    routes.add("summary_dev_second_pass")
+                if lay["dtab_order"] >= 16:
+                    routes.add("summary_fused_np18")
+                if cfg.short_seqs:
+                    routes.add("summary_fused_shorts")
+            else:
+                routes.add("summary_dev_reducer")
+            del dev
+        if forms["stream"] and cfg.legs["stream"]:  # summaries and characters in turn through one MapStream, over leg j's sub-batches
+            cuts, subs = stream_subs(False)
+            ms = batch.MapStream(sbwt, max(d.n_seqs for _, _, d in subs), max(d.total for _, _, d in subs), max_len if max_len <= 160 else 0,
+                                 pipelines=cfg.stream_pipelines)
+            try:
+                tickets = []
+                for i, (_, _, d) in enumerate(subs):
+                    d.chars.fill_(0xEE)
+                    if i % 2 == 0:
+                        d._summary_buffers()
+                        d.summary.view(torch.uint8).fill_(0xEE)
+                torch.cuda.synchronize()
+                for i, (_, _, d) in enumerate(subs):
+                    tickets.append(ms.submit_summary(d) if i % 2 == 0 else ms.submit(d))
+                for i, ((lo, hi, d), t) in enumerate(zip(subs, tickets)):
+                    ms.wait(t)
+                    sub_off = so[cuts[i]:cuts[i + 1] + 1] - so[cuts[i]]
+                    if i % 2 == 0:
+                        _eq_records(d.summary_host(), want_d[cuts[i]:cuts[i + 1]], sub_off, "map stream summary, sub-batch %d (fused %s)" % (i, d.fused), tag)
+                    else:
+                        kp = keep[lo:hi]
+                        _eq(d.chars[:d.total].cpu().numpy()[kp], full_chars[lo:hi][kp], sub_off, "map stream characters between summaries, sub-batch %d" % i, tag)
+                routes.add("summary_stream")
+            finally:
+                ms.close()
+            del subs
+        # the reducer alone over the ORACLE's characters, as bytes and as 2-bit words (M - X R = 0 .. 3)
+        code = np.zeros(256, dtype=np.uint8)
+        code[ord("-")], code[ord("X")], code[ord("R")] = 1, 2, 3
+        d_chars = torch.from_numpy(full_chars).to(dev0)
+        d_words = torch.from_numpy(rc.pack_words(code[full_chars], so).view(np.int32)).to(dev0)
+        d_wwork = torch.zeros(int(L.kbo_summary_words_work_bytes(n_s)) // 8 + 2, dtype=torch.int64, device=dev0)
+        known = max_s if ex["summary_max_len_known"] else 0
+        for what in ("kbo_summary_dev", "kbo_summary_words_dev"):
+            out = torch.full((n_s, 4), -0x11111112, dtype=torch.int32, device=dev0)  # (0xEE bytes)
+            if what == "kbo_summary_dev":
+                kbo_amd.check(L.kbo_summary_dev(d_chars.data_ptr(), off_t.data_ptr(), n_s, known, out.data_ptr(), cur.cuda_stream))
+            else:
+                kbo_amd.check(L.kbo_summary_words_dev(d_words.data_ptr(), off_t.data_ptr(), n_s, known, out.data_ptr(), d_wwork.data_ptr(), cur.cuda_stream))
+            torch.cuda.synchronize()
+            _eq_records(out.cpu().numpy().view(np.uint32), want_d, so, "%s, max_seq_len %d" % (what, known), tag)
+        routes.add("l")
+
+    # ---- m: both strands of the main batch, half of its sequences reverse-complemented, under the configuration's knobs
+    if legs2["strands"]:
+        leg_m(sbwt, "host-built")
+        routes.add("m")
+        routes.add("strands_%d" % ex["strands"])
+
+    # ---- n: kbo::find on the device (with max_gap_len = 0 the one kernel counts the runs while the characters are in LDS)
+    if legs2["find_dev"]:
+        gap = ex["find_dev_gap"]
+        er, eo = oracle.run_lengths_batch(exp_chars, offsets, gap)
+        cnt = np.zeros(n_s, dtype=np.int64)  # (no run for a sequence of fewer than 3 bases)
+        cnt[slens >= 3] = np.diff(eo.astype(np.int64))
+        efirst = np.concatenate([[0], np.cumsum(cnt)])
+        dev = batch.DeviceBatch(sbwt, sc, so, device=dev0, max_error_prob=p_err, format=False, want_ms=False)
+        tail = torch.cuda.Stream(dev0) if cfg.tail_stream else None
+        _rle_buffers(torch, dev, len(er))
+        dev.chars.fill_(0xEE)
+        dev.run_find(gap, tail_stream=tail)
+        torch.cuda.synchronize()
+        _eq(dev.chars.cpu().numpy()[:len(sc)][keep], exp_chars, offsets, "kbo_find_batch_dev chars (fused %s)" % dev.fused, tag)
+        assert _rle_total(dev) == len(er), "kbo_find_batch_dev gap %d: %d runs, the oracle has %d | %s" % (gap, _rle_total(dev), len(er), tag)
+        recs, first = dev.run_lengths_host()
+        _eq_runs(recs, first, er, efirst, "kbo_find_batch_dev gap %d (fused %s)" % (gap, dev.fused), tag)
+        _check_capped(dev.rle_records, len(er), len(er), er, "kbo_find_batch_dev gap %d" % gap, tag)
+        if len(er):  # a capacity below the count: every run is counted, only those that fit are written
+            cap = int(len(er) * ex["find_dev_cap"])
+            _rle_buffers(torch, dev, cap)
+            dev.run_find(gap, tail_stream=tail)
+            torch.cuda.synchronize()
+            _check_capped(dev.rle_records, cap, _rle_total(dev), er, "kbo_find_batch_dev gap %d, capacity %d" % (gap, cap), tag)
+        routes.add(("find_dev_fused_reads" if dev.fused and max_s <= 160 else "find_dev_fused_long" if dev.fused else "find_dev_two_kernel")
+                   + ("_gap0" if gap == 0 else "_gapped"))
+        routes.add("n")
+        del dev
+
+    # ---- o: a threshold per sequence over the ORACLE's MS bytes of a real walk (anything - here 0 - at the sequences of fewer than 3 bases)
+    if legs2["seq_thresholds"] and k >= 3:
+        thr_s = rc.thresholds_of(cfg, thr, n_s)
+        ms_full = np.zeros(len(sc), dtype=np.uint8)
+        ms_full[keep] = exp_d
+        want_c = np.full(len(sc), ord("-"), dtype=np.uint8)
+        want_x = np.zeros((n_s, 6), dtype=np.uint32)
+        for s in np.flatnonzero(slens >= 3):
+            a, b, t = int(so[s]), int(so[s + 1]), int(thr_s[s])
+            c = np.frombuffer(oracle.translate_ms_vec(oracle.derandomize_ms_vec(ms_full[a:b], k, t), k, t).encode(), dtype=np.uint8)
+            want_c[a:b] = c
+            nd = np.flatnonzero(c != ord("-"))
+            if len(nd):
+                want_x[s, 4:] = (nd[0], nd[-1] + 1)
+        want_x[:, :4] = _np_summary(oracle, want_c, so)
+        want_f = np.frombuffer(oracle.relative_to_ref(sc, want_c), dtype=np.uint8)
+        ms_t, ref_t = torch.from_numpy(ms_full).to(dev0), torch.from_numpy(sc.copy()).to(dev0)
+        thr_t = torch.from_numpy(thr_s).to(dev0)
+        for min_t in sorted({int(thr_s.min()), 2}, reverse=True):  # the true minimum, and the loosest bound there is
+            what = "k %d, thresholds %s, min_threshold %d" % (k, sorted(set(thr_s.tolist())), min_t)
+            got = batch.derand_translate_seq(ms_t, off_t, k, thr_t, min_threshold=min_t)
+            gotf = batch.derand_translate_seq(ms_t, off_t, k, thr_t, ref=ref_t, min_threshold=min_t)
+            gots = batch.derand_summary_seq(ms_t, off_t, k, thr_t, min_threshold=min_t)
+            torch.cuda.synchronize()
+            _eq(got.cpu().numpy()[keep], want_c[keep], offsets, "derand_translate_seq, " + what, tag)
+            _eq(gotf.cpu().numpy()[keep], want_f[keep], offsets, "derand_translate_seq with ref, " + what, tag)
+            _eq_records(gots.cpu().numpy().view(np.uint32), want_x, so, "derand_summary_seq, " + what, tag)
+        if len(set(thr_s[slens >= 3].tolist())) > 1:
+            routes.add("seq_thresholds_differ")
+        routes.add("o")
+
+    # ---- p: run lengths of device-resident characters - the ORACLE's, in the layout of the device legs' batch ('M' at the sequences
+    # of 1 and 2 bases).  kbo_run_lengths_seq_dev promises every sequence, any byte values, "sequences of length 0 are legal": all of
+    # it is compared.  kbo_run_lengths_dev says "device-resident characters" and nothing of empty sequences: its records are compared
+    # over the sequences of 1 base or more, and the total it counts (an empty sequence has no character to make a run of)
+    if legs2["rle_dev"]:
+        gap, mode = ex["rle_gap"], ex["rle_capacity_mode"]
+        er, eo = oracle.run_lengths_batch(full_chars, so, gap)
+        cap = {"full": len(er), "third": len(er) // 3, "zero": 0}[mode]
+        d_chars = torch.zeros(len(sc) + 16, dtype=torch.uint8, device=dev0)
+        d_chars[:len(sc)] = torch.from_numpy(full_chars).to(dev0)
+        recs, first = batch.run_lengths_seq(d_chars, off_t, gap)
+        torch.cuda.synchronize()
+        _eq_runs(recs.cpu().numpy().view(np.uint32), first.cpu().numpy().view(np.uint32), er, eo, "run_lengths_seq gap %d" % gap, tag)
+        if mode != "full":
+            wb = int(L.kbo_run_lengths_seq_work_bytes(n_s, total_s))
+            work = torch.zeros(wb // 8 + 2, dtype=torch.int64, device=dev0)
+            recs = torch.full((cap + 8, 7), SENTINEL, dtype=torch.int32, device=dev0)
+            first = torch.zeros(n_s + 1, dtype=torch.int32, device=dev0)
+            kbo_amd.check(L.kbo_run_lengths_seq_dev(d_chars.data_ptr(), off_t.data_ptr(), n_s, total_s, gap, work.data_ptr(), wb, recs.data_ptr(), cap,
+                                                    first.data_ptr(), cur.cuda_stream))
+            torch.cuda.synchronize()
+            fh = first.cpu().numpy().view(np.uint32)
+            assert np.array_equal(fh.astype(np.uint64), eo), "kbo_run_lengths_seq_dev capacity %d: first-run indices | %s" % (cap, tag)
+            _check_capped(recs, cap, int(fh[-1]), er, "kbo_run_lengths_seq_dev gap %d, capacity %d" % (gap, cap), tag)
+        dev = batch.DeviceBatch(sbwt, sc, so, device=dev0, max_error_prob=p_err, format=False, want_ms=False)
+        dev.chars[:len(sc)] = d_chars[:len(sc)]
+        _rle_buffers(torch, dev, cap)
+        dev.run_lengths(max_gap_len=gap)
+        torch.cuda.synchronize()
+        _check_capped(dev.rle_records, cap, _rle_total(dev), er, "kbo_run_lengths_dev gap %d, capacity %d" % (gap, cap), tag)
+        if mode == "full":
+            _, first = dev.run_lengths_host()
+            some = slens >= 1
+            assert np.array_equal(np.asarray(first, dtype=np.uint64)[:-1][some], eo[:-1][some]), "kbo_run_lengths_dev gap %d: first-run indices | %s" % (gap, tag)
+        del dev
+        routes.add("p")
+        routes.add("rle_capacity_" + mode)
+
+    # ---- q: the reverse complement of a device-resident batch, bytes and 2-bit words, empty and 1-base sequences included, against
+    # numpy; plain buffers at the documented sizes (behind guard bands: test_gpu_strands.py)
+    if legs2["revcomp_dev"]:
+        want = rc.revcomp(sc, so)
+        d_in = torch.zeros(total_s + 16, dtype=torch.uint8, device=dev0)
+        d_in[:total_s] = torch.from_numpy(sc.copy()).to(dev0)
+        d_out = torch.full((total_s,), 0xEE, dtype=torch.uint8, device=dev0)
+        kbo_amd.check(L.kbo_revcomp_batch_dev(d_in.data_ptr(), off_t.data_ptr(), n_s, total_s, max_s if ex["summary_max_len_known"] else 0,
+                                              d_out.data_ptr(), cur.cuda_stream))
+        torch.cuda.synchronize()
+        _eq(d_out.cpu().numpy(), want, so, "kbo_revcomp_batch_dev", tag)
+        words, epos, ebyt, _ = rc.pack_reads(sc, so)
+        want_w, want_pos, want_byt, mask = rc.pack_reads(want, so)
+        nw, ne = len(words), len(epos)
+        d_w = torch.from_numpy(words.view(np.int32)).to(dev0)
+        d_wo = torch.full((nw,), -0x11111112, dtype=torch.int32, device=dev0)
+        d_scr = torch.zeros(int(L.kbo_revcomp_packed_scratch_bytes(n_s)) // 8 + 2, dtype=torch.int64, device=dev0)
+        d_ep = torch.from_numpy(epos.view(np.int64)).to(dev0) if ne else None
+        d_eb = torch.from_numpy(ebyt).to(dev0) if ne else None
+        d_epo = torch.full((ne,), -1, dtype=torch.int64, device=dev0) if ne else None
+        d_ebo = torch.full((ne,), 0xEE, dtype=torch.uint8, device=dev0) if ne else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        kbo_amd.check(L.kbo_revcomp_packed_dev(d_w.data_ptr(), off_t.data_ptr(), n_s, nw, ptr(d_ep), ptr(d_eb), ne, d_wo.data_ptr(), ptr(d_epo), ptr(d_ebo),
+                                               d_scr.data_ptr(), cur.cuda_stream))
+        torch.cuda.synchronize()
+        got_w = d_wo.cpu().numpy().view(np.uint32)
+        bad = np.flatnonzero((got_w & mask) != (want_w & mask))
+        assert len(bad) == 0, "kbo_revcomp_packed_dev: %d of %d words differ, first %d: %08x against %08x | %s" % (
+            len(bad), nw, int(bad[0]), got_w[bad[0]], want_w[bad[0]], tag)
+        if ne:
+            assert np.array_equal(d_epo.cpu().numpy().view(np.uint64), want_pos), "kbo_revcomp_packed_dev: mirrored exception positions | " + tag
+            assert np.array_equal(d_ebo.cpu().numpy(), want_byt), "kbo_revcomp_packed_dev: complemented exception bytes | " + tag
+            routes.add("revcomp_packed_exceptions")
+        routes.add("q")
     return routes
 
 
@@ -429,7 +829,31 @@ ROUTE_CONDITIONS = [
     ("sequences of 0 - 2 bases in a map stream's batches", 5, lambda c, r: c.short_seqs and "j" in r),
     ("sequences of 0 - 2 bases under kbo_sparse_runs_dev", 3, lambda c, r: c.short_seqs and "sparse_dev" in r),
     ("sequences of 1 / 2 bases through kbo_ms_batch", 10, lambda c, r: "ms_batch_short" in r),
-] + [("leg %s" % leg, 15, (lambda leg: lambda c, r: leg in r)(leg)) for leg in "fghijk"] + [
+    # legs l - q: the summary and run-count forms of map_reads_kernel / finish_reads_kernel, the reducer, both strands, a threshold per sequence
+    ("kbo_summary_batch_dev through map_reads_kernel's summary form, k >= 64", 5, lambda c, r: "summary_dev_fused" in r and c.k >= 64),
+    ("kbo_summary_batch_dev through map_reads_kernel's summary form, k < 64", 5, lambda c, r: "summary_dev_fused" in r and c.k < 64),
+    ("... with reads left to finish_reads_kernel's summary form, k >= 64", 3, lambda c, r: "summary_dev_second_pass" in r and c.k >= 64),
+    ("... over a depth table of order 16 or more (the NP = 18 summary forms)", 3, lambda c, r: "summary_fused_np18" in r),
+    ("... with sequences of 0 - 2 bases in the batch", 3, lambda c, r: "summary_fused_shorts" in r),
+    ("kbo_summary_batch_dev through the reducer, k >= 64", 3, lambda c, r: "summary_dev_reducer" in r and c.k >= 64),
+    ("kbo_summary_batch: slabs through the kernel's summary form (bytes in)", 3, lambda c, r: "summary_host_kernel" in r),
+    ("kbo_summary_batch_packed: slabs through the kernel's summary form (words in)", 3, lambda c, r: "summary_host_packed_kernel" in r),
+    ("kbo_summary_batch[_packed]: slabs through the reducer", 3, lambda c, r: "summary_host_reducer" in r),
+    ("summaries and characters in turn through a map stream", 3, lambda c, r: "summary_stream" in r),
+    ("kbo_find_batch_dev through map_reads_kernel, gap 0 (runs counted in LDS), k >= 64", 3, lambda c, r: "find_dev_fused_reads_gap0" in r and c.k >= 64),
+    ("kbo_find_batch_dev through map_reads_kernel, gap > 0", 3, lambda c, r: "find_dev_fused_reads_gapped" in r),
+    ("kbo_find_batch_dev through map_long_kernel, k >= 64", 3,
+     lambda c, r: ("find_dev_fused_long_gap0" in r or "find_dev_fused_long_gapped" in r) and c.k >= 64),
+    ("kbo_find_batch_dev through the two-kernel route", 3, lambda c, r: "find_dev_two_kernel_gap0" in r or "find_dev_two_kernel_gapped" in r),
+    ("both strands at once (strands = 3)", 15, lambda c, r: "strands_3" in r),
+    ("both strands at once, k >= 64", 5, lambda c, r: "strands_3" in r and c.k >= 64),
+    ("one strand alone, '+' / '-'", 3, lambda c, r: "strands_1" in r or "strands_2" in r),
+    ("both strands through a sharded index", 3, lambda c, r: "strands_sharded" in r and c.extra["strands"] == 3),
+    ("a threshold per sequence, two or more different ones in the batch", 15, lambda c, r: "seq_thresholds_differ" in r),
+    ("run lengths of device characters with room for a third of the records", 3, lambda c, r: "rle_capacity_third" in r),
+    ("run lengths of device characters with room for none", 3, lambda c, r: "rle_capacity_zero" in r),
+    ("kbo_revcomp_packed_dev with an exception list", 3, lambda c, r: "revcomp_packed_exceptions" in r),
+] + [("leg %s" % leg, 15, (lambda leg: lambda c, r: leg in r)(leg)) for leg in "fghijklmnopq"] + [
     ("device build, %s, revcomp %s" % (name, rcomp), 1, (lambda lo, hi, rcomp: lambda c, r: "f" in r and lo < c.k <= hi and c.add_revcomp == rcomp)(lo, hi, rcomp))
     for name, lo, hi in (("k <= 32", 0, 32), ("k <= 64", 32, 64), ("k <= 128", 64, 128), ("k <= 255", 128, 255)) for rcomp in (False, True)]
 

@@ -88,6 +88,79 @@ def test_seed_list_holds_every_class_length_leg_and_knob(configs):
             assert any(c.legs["devbuild"] and lo < c.k <= hi and c.add_revcomp == rcomp for c in configs.values()), (lo, hi, rcomp)
 
 
+def test_no_draw_of_the_first_legs_moved_and_the_new_ones_are_deterministic(configs):
+    """Config.extra comes from a stream of its own: without it a configuration is what it was before legs l - q (the digest over the
+    list, LABNOTES); helpers of the new legs against their definitions"""
+    for s in list(rc.SEEDS[:6]):
+        c = configs[s]
+        assert repr(rc.config(s).extra) == repr(c.extra) and set(c.extra["legs"]) == set(rc.LEGS2)
+        _, concat, off = rc.make_inputs(c)
+        lens = np.diff(off.astype(np.int64))
+        r = rc.revcomp(concat, off)
+        for i in (0, len(lens) // 2, len(lens) - 1):  # the definition, sequence by sequence
+            a, b = int(off[i]), int(off[i + 1])
+            assert np.array_equal(r[a:b], rc.COMP[concat[a:b][::-1]])
+        assert np.array_equal(rc.revcomp(r, off), concat)
+        assert rc.COMP[ord("N")] == ord("N") and bytes(rc.COMP[list(b"ACGTacgt")]) == b"TGCAtgca"
+        sin = rc.make_strand_inputs(c, concat, off)
+        pm = np.repeat(np.asarray(c.extra["minus"]), lens)
+        assert np.array_equal(sin[pm], r[pm]) and np.array_equal(sin[~pm], concat[~pm])
+        words, pos, byt, mask = rc.pack_reads(concat, off)
+        assert len(words) == int(((lens + 15) // 16).sum()) and np.array_equal(concat[pos.astype(np.int64)], byt)
+        a, b = int(off[1]), int(off[2])  # sequence 1 starts a word; 16 bases a word from the low bits up
+        w0 = int(((lens[0] + 15) // 16))
+        for i in range(min(b - a, 40)):
+            if rc.PACK_CODE[concat[a + i]] < 4:
+                assert (int(words[w0 + i // 16]) >> (2 * (i % 16))) & 3 == rc.PACK_CODE[concat[a + i]]
+                assert (int(mask[w0 + i // 16]) >> (2 * (i % 16))) & 3 == 3
+
+
+def test_seed_list_holds_the_second_set_of_legs(configs):
+    """what the reference side alone decides about legs l - q (the product's routes: test_routes_covered of the GPU module)"""
+    cs = list(configs.values())
+    for leg in rc.LEGS2:
+        has = [c for c in cs if c.extra["legs"][leg]]
+        assert len(has) >= 15 and sum(1 for c in has if c.k >= 64) >= 5 and sum(1 for c in has if c.k >= 128) >= 3, leg
+    # what the list holds for them to run over: reads, reads at k >= 64, reads over a depth table of order 16
+    reads = [c for c in cs if max(c.lens) <= 160]
+    assert len(reads) >= 100 and sum(1 for c in reads if c.k >= 64) >= 50 and sum(1 for c in reads if c.knobs["depth_table"] == 16) >= 15
+    for c in reads:  # the NP = 18 summary forms: every configuration that can reach them runs the device summaries
+        if c.knobs["depth_table"] == 16 and c.k >= 16:
+            assert c.extra["legs"]["summary"] and c.extra["summary_forms"]["device"], c.seed
+    summ = [c for c in cs if c.extra["legs"]["summary"]]
+    for form in rc.SUMMARY_FORMS:
+        assert sum(1 for c in summ if c.extra["summary_forms"][form]) >= 15, form
+    assert sum(1 for c in summ if c.extra["summary_forms"]["stream"] and c.legs["stream"]) >= 5
+    assert sum(1 for c in summ if c.extra["summary_forms"]["device"] and c.short_seqs and max(c.lens) <= 160 and c.k >= 64) >= 3
+    # both strands: under small slabs, two workers, a sharded index, an index with its reverse complement, large k
+    both = [c for c in cs if c.extra["legs"]["strands"] and c.extra["strands"] == 3]
+    assert sum(1 for c in both if c.knobs["slab_bytes"] == 1 << 16) >= 3
+    assert sum(1 for c in both if c.knobs["two_workers"]) >= 3
+    assert sum(1 for c in both if c.legs["shards"]) >= 3
+    assert sum(1 for c in both if c.add_revcomp) >= 3
+    assert sum(1 for c in both if c.k >= 64) >= 5
+    assert {c.extra["strands"] for c in cs if c.extra["legs"]["strands"]} == {1, 2, 3}
+    n_minus = sum(sum(c.extra["minus"]) for c in cs)
+    n_all = sum(len(c.lens) for c in cs)
+    assert n_all <= 4 * n_minus <= 3 * n_all
+    for c in cs:
+        assert len(c.extra["minus"]) == len(c.lens)
+        if len(c.lens) >= 2:
+            assert len(c.lens) <= 4 * sum(c.extra["minus"]) <= 3 * len(c.lens), c.seed
+        # a threshold per sequence of the device legs' batch; two different ones in every batch, whatever the oracle's threshold is
+        n_s = len(c.lens) + len(c.short_seqs)
+        for t in (2, 3, min(c.k, 12), c.k):
+            if c.k >= 3 and t <= c.k:
+                thr = rc.thresholds_of(c, t, n_s)
+                assert thr.dtype == np.int32 and thr.min() >= 2 and thr.max() <= c.k
+                assert n_s < 2 or len(set(thr[:2].tolist())) == 2, (c.seed, t)
+    for key, values in (("strand_gap", {0, 3, 50}), ("find_dev_gap", {0, 5, 2**32 - 1}), ("rle_gap", {0, 3, 50, 2**32 - 1}),
+                        ("rle_capacity_mode", {"full", "third", "zero"}), ("strand_format", {False, True})):
+        leg = {"strand_gap": "strands", "strand_format": "strands", "find_dev_gap": "find_dev"}.get(key, "rle_dev")
+        for v in values:
+            assert sum(1 for c in cs if c.extra["legs"][leg] and c.extra[key] == v) >= 3, (key, v)
+
+
 def test_the_oracle_alone_over_the_seed_list(oracle, configs):
     """index build + matches over every configuration: few refusals; legs g / h run to an answer or a refusal and have gaps to fill"""
     refused, filled = [], 0
